@@ -2,7 +2,7 @@
 """ALS iterations/sec of the c_nmf loop on the synthetic config-3 matrix
 (30 000 genes x 1 000 000 cells, 5 % non-zeros, k = 50), BASELINE.json's metric.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]                  (no launcher: ONE process drives the N devices)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (no launcher: ONE process drives the N devices)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (one process per GPU)
 
 Which form runs is decided by the environment (plan()): with WORLD_SIZE set (torch.distributed.run) every process is
@@ -74,7 +74,13 @@ def parse(argv=None):
     ap.add_argument("--force-allreduce", action="store_true",
                     help="with one rank: still create the RCCL process group and route the two per-iteration sums through "
                          "the all-reduce hook (plumbing check of the hook path on a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (the factors w, d, h as c_nmf / c_ard_nmf "
+                         "return them, and the step's tol) as DIR/<name>.npy in float64, at most 64 MB in all: a factor too "
+                         "large for that is written as a fixed seeded sample of its columns (indices beside it)")
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.cpu_sample_cells is None:
         a.cpu_sample_cells = 200000 if a.workload == "als" else 10000
     return a
@@ -393,6 +399,58 @@ def emit(line):
     print(line, flush=True)
 
 
+DUMP_BYTES = 64 * 10 ** 6   # --dump-outputs: the files written hold at most this many bytes (64 MB) in all
+DUMP_SEED = 0x5EED          # the fixed sample of a factor's columns when the factor does not fit its share
+
+
+def dump_rows(nrows, row_bytes, budget):
+    """--dump-outputs: the rows of a factor (as the library holds it: one row per gene or per cell) that are written --
+    None (all) when they fit `budget` bytes, else the sorted indices of a fixed seeded sample that does, the stored
+    index of every sampled row (8 bytes) included."""
+    import numpy as np
+    if nrows * row_bytes <= budget:
+        return None
+    s = max(int(budget // (row_bytes + 8)), 1)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(nrows, size=s, replace=False))
+
+
+def dump_plan(m, n, k):
+    """-> (genes of w, cells of h) that --dump-outputs writes (None = all).  w may take half of DUMP_BYTES, h what w
+    leaves; d, the scalars and the .npy headers are set aside first."""
+    room = DUMP_BYTES - 8 * k - 64 * 1024
+    genes = dump_rows(m, 8 * k, room // 2)
+    w_bytes = 8 * k * m if genes is None else (8 * k + 8) * genes.size
+    return genes, dump_rows(n, 8 * k, room - w_bytes)
+
+
+def dump_outputs(dirname, w, d, h, genes, cells, **scalars):
+    """Writes the last step's outputs as dirname/<name>.npy in float64: w (k x genes) and h (k x cells) in the orientation
+    c_nmf returns them, d, and each of `scalars` as a 1-D array (a scalar: one element).  `w` / `h` are the library's
+    row-major factors (one row per gene / cell), already reduced to the rows `genes` / `cells` of dump_plan(); those
+    indices go to w_genes.npy / h_cells.npy when a factor is sampled, so that two builds compare output for output."""
+    import numpy as np
+    arrays = {"w": w.T, "d": d, "h": h.T}
+    if genes is not None:
+        arrays["w_genes"] = genes
+    if cells is not None:
+        arrays["h_cells"] = cells
+    arrays.update({name: np.atleast_1d(v) for name, v in scalars.items()})
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(dirname, name + ".npy")
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        total += os.path.getsize(path)
+    if total > DUMP_BYTES:
+        raise SystemExit("bench.py: --dump-outputs wrote %d bytes, more than %d" % (total, DUMP_BYTES))
+
+
+def dump_factors(dirname, W, d, H, **scalars):
+    """dump_outputs() of the whole factors W (genes x k) and H (cells x k) of one process"""
+    genes, cells = dump_plan(W.shape[0], H.shape[0], W.shape[1])
+    dump_outputs(dirname, W if genes is None else W[genes], d, H if cells is None else H[cells], genes, cells, **scalars)
+
+
 def run_single_process(args, pl):
     """One process, N devices, no launcher and no torch: the library's own team (sgl_multi_create -> ncclCommInitAll over
     the N devices, or the loopback exchange when all ranks sit on device 0), one host thread per device inside the
@@ -440,6 +498,9 @@ def run_single_process(args, pl):
         for c in ranks:
             c.timing_enable(False)
         phases = phases_all[0]
+        if args.dump_outputs:
+            W, D, H = M.get_factors()     # every rank's cells, in cell order
+            dump_factors(args.dump_outputs, W, D, H, tol=tols[-1])
         m = dims[0][0]
         mb = (m + world - 1) // world if world > 1 else m
         run = {"world": world, "elapsed": elapsed, "tols": tols, "dims": dims[0], "nnz_total": int(sum(d[2] for d in dims)),
@@ -560,6 +621,9 @@ def run_ard(args):
                                       "frac_of_fp64_mfma_peak": (tf / FP64_MFMA_PEAK_TFLOPS) if tf else None}})
     total = time.perf_counter() - t_all
     ctx.timing_enable(False)
+    if args.dump_outputs:
+        W, D, H = ctx.get_factors()       # the grid's last fit, and its trace rows
+        dump_factors(args.dump_outputs, W, D, H, test_mse=r["test_mse"], tol=r["tol"])
     with_tf = [q for q in per_rank if q["downdate"]["achieved_tflops"]]
     dom = max(with_tf, key=lambda q: q["downdate"]["ms_per_iteration"]) if with_tf else None
     nfits = len(fits)
@@ -763,6 +827,20 @@ def main():
         got = [None] * world
         dist.all_gather_object(got, (phases, rank_info[0]))
         phases_all, rank_info = [g[0] for g in got], [g[1] for g in got]
+
+    if args.dump_outputs:
+        # w and d are replicated; each rank holds h of its own cells lo .. lo + n_loc - 1: rank 0 gathers the dumped ones
+        import numpy as np
+        W, D, H = ctx.get_factors()
+        genes, cells = dump_plan(m, args.cells, args.k)
+        mine = np.arange(lo, lo + n_loc) if cells is None else cells[(cells >= lo) & (cells < lo + n_loc)]
+        parts = [H[mine - lo]]
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, H[mine - lo])
+        if rank == 0:
+            dump_outputs(args.dump_outputs, W if genes is None else W[genes], D, np.concatenate(parts), genes, cells,
+                         tol=tols[-1])
 
     if rank == 0:
         mb = (m + world - 1) // world if (world > 1 and mode == "native") else m

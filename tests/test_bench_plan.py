@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -129,3 +130,45 @@ def test_process_per_gpu_device_pick_survives_a_launcher_that_isolates_the_devic
     assert bench.pick_device(3, 8, forced="") == (3, "LOCAL_RANK")
     with pytest.raises(SystemExit):
         bench.pick_device(0, 0)
+
+
+def test_steps_and_warmup_are_checked():
+    """ms_per_step divides by --steps: a run with no timed step is refused before anything starts."""
+    assert bench.parse(["--steps", "7", "--warmup", "0"]).steps == 7
+    for argv in (["--steps", "0"], ["--steps", "-1"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit) as e:
+            bench.parse(argv)
+        assert e.value.code not in (0, None)
+
+
+def test_dump_plan_keeps_the_headline_outputs_under_the_limit():
+    """Config 3 (30 000 genes x 1 000 000 cells, k = 50): w whole, h a fixed seeded sample of cells; 64 MB in all."""
+    m, n, k = 30000, 1000000, 50
+    genes, cells = bench.dump_plan(m, n, k)
+    assert genes is None and cells is not None
+    assert cells.size > 10000 and np.all(np.diff(cells) > 0) and cells[0] >= 0 and cells[-1] < n
+    assert 8 * k * m + (8 * k + 8) * cells.size + 8 * k + 64 * 1024 <= bench.DUMP_BYTES
+    g2, c2 = bench.dump_plan(m, n, k)
+    assert g2 is None and np.array_equal(cells, c2)            # the same cells on every run
+    assert bench.dump_plan(300, 1000, 5) == (None, None)       # small problems: everything
+    genes, cells = bench.dump_plan(200000, 1000000, 256)       # w alone over half the limit: both sampled
+    assert genes is not None and cells is not None
+    assert (8 * 256 + 8) * (genes.size + cells.size) + 8 * 256 + 64 * 1024 <= bench.DUMP_BYTES
+
+
+def test_dump_outputs_writes_what_c_nmf_returns(tmp_path, monkeypatch):
+    rng = np.random.default_rng(1)
+    W, d, H = rng.random((300, 5)), rng.random(5), rng.random((1000, 5))
+    bench.dump_factors(str(tmp_path / "all"), W, d, H, tol=0.25)
+    got = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in os.listdir(str(tmp_path / "all"))}
+    assert sorted(got) == ["d", "h", "tol", "w"] and all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["w"], W.T) and np.array_equal(got["h"], H.T) and np.array_equal(got["d"], d)
+    assert got["tol"].tolist() == [0.25]
+    # a limit h does not fit: a sample of its cells, their indices beside it, nothing over the limit
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 * 1024 + 40 * 1000)
+    bench.dump_factors(str(tmp_path / "part"), W, d, H, tol=0.25)
+    out = tmp_path / "part"
+    cells = np.load(str(out / "h_cells.npy")).astype(np.int64)
+    assert 0 < cells.size < 1000 and np.array_equal(np.load(str(out / "h.npy")), H[cells].T)
+    assert np.array_equal(np.load(str(out / "w.npy")), W.T) and not (out / "w_genes.npy").exists()
+    assert sum(os.path.getsize(str(out / f)) for f in os.listdir(str(out))) <= bench.DUMP_BYTES
