@@ -187,6 +187,29 @@ SGL_API int sgl_c_linked_nmf(const double* Ax, const int32_t* Ai, const int32_t*
                      double* w_out, double* d_out, double* h_out,
                      int32_t* n_iter, double* tol_trace, const sgl_callbacks* cb);
 
+/* c_gcnmf (src/singlet.cpp:1668-1730; glue src/RcppExports.cpp:399-417), the
+ * graph-convolutional NMF behind R/RunGCNMF.R:77.  Replaces _singlet_c_gcnmf
+ * (10 args).  G (G_nrow x G_ncol, a dgCMatrix) is the n x n cell graph, n = ncol;
+ * it may be asymmetric.  Each iteration: the H side convolves the right-hand
+ * sides over G (Bc = B G, l.1684-1688) and solves EVERY cell, empty ones
+ * included; the W side forms its right-hand sides from H G (l.1703-1706) with
+ * the Gram of the plain scaled H and solves EVERY gene.  At may be NULL (the
+ * device transposes).  w_init is w_rows x w_cols column-major, transposed iff
+ * w_rows == nrow && w_rows != w_cols (l.1713); k = the factor dimension after
+ * that.  Outputs: w_out nrow x k column-major (the reference returns
+ * w.transpose()), d_out k, h_out k x ncol, n_iter / tol_trace as sgl_c_nmf.
+ * An invalid G (shape, unsorted or out-of-range rows, non-finite values) is
+ * SGL_EINVAL. */
+SGL_API int sgl_c_gcnmf(const double* Ax, const int32_t* Ai, const int32_t* Ap,
+                        const double* Atx, const int32_t* Ati, const int32_t* Atp,
+                        int32_t nrow, int32_t ncol,
+                        const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol,
+                        double tol, uint16_t maxit, int verbose,
+                        double L1, double L2, uint16_t threads,
+                        const double* w_init, int32_t w_rows, int32_t w_cols, int32_t k,
+                        double* w_out, double* d_out, double* h_out,
+                        int32_t* n_iter, double* tol_trace, const sgl_callbacks* cb);
+
 /* c_project_model (src/singlet.cpp:405-413).
  * Replaces _singlet_c_project_model (src/RcppExports.cpp:444-447 region).
  * w is w_rows x w_cols column-major; if w_rows == nrow it is transposed first
@@ -293,6 +316,19 @@ SGL_API int sgl_fit_init(sgl_ctx* ctx, int32_t k, const double* w_init, uint64_t
  * rules of sgl_c_linked_nmf; link_h columns are the cells of this shard). */
 SGL_API int sgl_set_links(sgl_ctx* ctx, const double* link_h, int32_t link_h_rows, int32_t link_h_cols,
                           const double* link_w, int32_t link_w_rows, int32_t link_w_cols);
+
+/* Cell graph of c_gcnmf for the current fit (after sgl_fit_init, which drops
+ * it again; all-NULL slots clear it).  G is an n x n dgCMatrix, n = the cells of
+ * the resident matrix; an invalid G is SGL_EINVAL with a message.  While it is
+ * set, sgl_step_h convolves its right-hand sides over G and solves every cell,
+ * and sgl_step_w accumulates over t(A) against H G and solves every gene (the
+ * rules of sgl_c_gcnmf); the convolution's time counts in the rhs_h / rhs_w
+ * phases.  Edges cross shards and the reference defines no such combination, so
+ * a graph is refused (SGL_EINVAL) on a native team or with an all-reduce hook,
+ * after a dense upload and next to link matrices, and the masked steps /
+ * sgl_ard_run refuse while one is set. */
+SGL_API int sgl_set_graph(sgl_ctx* ctx, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow,
+                          int32_t G_ncol);
 
 /* Collective hook for cell-sharded runs.  Called with a device pointer to
  * `count` doubles that must be summed in place over all shards.  Ordering:

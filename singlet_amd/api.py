@@ -5,7 +5,9 @@ the R drivers call are mirrored here one-for-one in Python, with the same
 names, argument order, defaults and return fields:
 
   c_nmf / c_ard_nmf / c_project_model   R/RcppExports.R:28-30, 78-80, 24-26
+  c_gcnmf                               src/RcppExports.cpp:399-417
   run_nmf                               R/run_nmf.R:18-77
+  run_gcnmf                             R/RunGCNMF.R:20-98
   ard_nmf                               R/ard_nmf.R:31-193
   cross_validate_nmf                    R/cross_validate_nmf.R:18-105
   GetBestRank                           R/GetBestRank.R:8-46
@@ -231,6 +233,33 @@ def c_linked_nmf(A, At, tol, maxit, verbose, L1, L2, threads, w, link_h, link_w)
     return {"w": w_out.T, "d": d_out, "h": h_out.T, "iter": n_iter.value, "tol": tr[:n_iter.value].copy()}
 
 
+def c_gcnmf(A, At, G, tol, maxit, verbose, L1, L2, threads, w):
+    """.Call(`_singlet_c_gcnmf`, ...) -> list(w = m x k, d, h = k x n)  (src/singlet.cpp:1668-1730).  G: the n x n cell
+    graph (may be asymmetric).  w: k x m or m x k, transposed iff nrow(w) == nrow(A) and w is not square (l.1713).
+    Unlike c_nmf, w comes back m x k, as the reference returns it; "iter" / "tol" are extras of this mirror."""
+    L = _lib.load()
+    A = as_dgCMatrix(A)
+    At = None if At is None else as_dgCMatrix(At)
+    G = as_dgCMatrix(G)
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim != 2:
+        raise ValueError("w must be a matrix")
+    w_rows, w_cols = w.shape
+    k = w_cols if (w_rows == A.nrow and w_rows != w_cols) else w_rows
+    wf = np.ascontiguousarray(w.T)   # column-major image of w
+    m, n = A.nrow, A.ncol
+    w_out, h_out, d_out = np.empty((k, m)), np.empty((n, k)), np.empty(k)   # w_out: m x k column-major
+    n_iter = C.c_int32()
+    tr = np.zeros(max(int(maxit), 1))
+    cb = make_callbacks(_verbose_log(verbose))
+    t = (ptr(At.x, f64p), ptr(At.i, i32p), ptr(At.p, i32p)) if At is not None else (None, None, None)
+    check(L.sgl_c_gcnmf(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), *t, m, n, ptr(G.x, f64p), ptr(G.i, i32p),
+                        ptr(G.p, i32p), G.nrow, G.ncol, float(tol), int(maxit), int(bool(verbose)), float(L1), float(L2),
+                        int(threads), ptr(wf, f64p), w_rows, w_cols, k, ptr(w_out, f64p), ptr(d_out, f64p), ptr(h_out, f64p),
+                        C.byref(n_iter), ptr(tr, f64p), C.byref(cb)))
+    return {"w": w_out.T, "d": d_out, "h": h_out.T, "iter": n_iter.value, "tol": tr[:n_iter.value].copy()}
+
+
 def c_ard_nmf(A, At, tol, maxit, verbose, L1, L2, threads, w, seed, inv_density, overfit_threshold, trace_test_mse):
     """.Call(`_singlet_c_ard_nmf`, ...) -> list(w, d, h, test_mse, iter, tol, score_overfit) (src/singlet.cpp:1144-1151)."""
     L = _lib.load()
@@ -331,6 +360,42 @@ def run_nmf(A, rank, tol=1e-4, maxit=100, verbose=True, L1=0.01, L2=0, threads=0
         return _sort_model(model, None, None)
     model = c_nmf(A, None, tol, maxit, bool(verbose), L1[0], L1[1], L2[0], L2[1], threads, w_init)
     return _sort_model(model, A.Dimnames[0], A.Dimnames[1])
+
+
+def run_gcnmf(A, graph, k, split_by=None, tol=1e-5, L1=0.01, L2=0, verbose=2, maxit=100, threads=0, seed=None):
+    """The numeric steps of RunGCNMF.Seurat (R/RunGCNMF.R:20-98) on a genes x cells matrix: PreprocessData when every value
+    is integral (l.42-45), weight_by_split when `split_by` (0-based group per cell) is given (l.62-68), w_init uniform k x
+    nrow(A) (l.73-75; `seed` replaces R's RNG state: an int or numpy Generator), c_gcnmf, factor names GCNMF_1..k (l.78).
+    There is NO sort by d (the reference has none).  Returns the c_gcnmf list (w m x k, d, h k x n) with "factor_names",
+    "rownames_w" and "colnames_h".
+
+    Two places follow the evident intent rather than the R code, which cannot run as written:
+      - l.77 passes `G`, a name defined nowhere in the function, to c_gcnmf; here the `graph` argument is passed;
+      - when `k` is a matrix, `w_init` is never assigned (l.71-76); here that matrix is the initial w (k x m or m x k,
+        oriented by c_gcnmf's rule)."""
+    A = as_dgCMatrix(A)
+    rn, cn = A.Dimnames[0], A.Dimnames[1]
+    v = A.x
+    if np.sum(np.trunc(v)) == np.sum(v):   # sum(as.integer(v)) == sum(v)
+        A = PreprocessData(A)
+    if split_by is not None:
+        sb = np.asarray(split_by)
+        groups = np.unique(sb)
+        sb = np.searchsorted(groups, sb).astype(np.int32)   # as.integer(as.numeric(as.factor(.))) - 1
+        A = weight_by_split(A, sb, int(groups.size))
+    At = None   # Matrix::t(A): built on the device
+    if isinstance(k, np.ndarray) and k.ndim == 2:
+        if A.nrow not in k.shape:
+            raise ValueError("dimensions of matrix specified for 'k' are not compatible with number of rows in 'A'")
+        w_init = k
+    else:
+        w_init = _rng(seed).random((A.nrow, int(k))).T   # matrix(runif(k * nrow(A)), k, nrow(A)), filled by column
+    model = c_gcnmf(A, At, graph, tol, maxit, bool(verbose), L1, L2, threads, w_init)
+    kk = model["d"].shape[0]
+    model["factor_names"] = ["GCNMF_%d" % (q + 1) for q in range(kk)]
+    model["rownames_w"] = rn
+    model["colnames_h"] = cn
+    return model
 
 
 def _staged(A, op):

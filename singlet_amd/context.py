@@ -208,6 +208,16 @@ class Context:
         check(self._L.sgl_fit_init(self._h, int(k), ptr(w, f64p), synth_seed))
         self.k = int(k)
 
+    def set_graph(self, G):
+        """c_gcnmf's cell graph (sgl_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over the resident cells, or None
+        to clear it.  Call after fit_init (which drops it)."""
+        if G is None:
+            check(self._L.sgl_set_graph(self._h, None, None, None, 0, 0))
+            return
+        from .sparse import as_dgCMatrix
+        G = as_dgCMatrix(G)
+        check(self._L.sgl_set_graph(self._h, ptr(G.x, f64p), ptr(G.i, i32p), ptr(G.p, i32p), G.nrow, G.ncol))
+
     def set_stream(self, stream_ptr):
         check(self._L.sgl_set_stream(self._h, C.c_void_p(stream_ptr) if stream_ptr else None))
 

@@ -142,6 +142,26 @@ struct DevMaskList {
     bool refused = false;      // too large for the memory budget under this key: the hashing kernel runs
 };
 
+// Cell graph of graph-convolutional NMF (c_gcnmf, src/singlet.cpp:1668-1730): n x n CSC, 64-bit offsets, uploaded by
+// sgl_set_graph.  Columns with more than SGL_GRAPH_HUB entries ("hubs") are cut into segments of SGL_GRAPH_SEG entries that
+// separate waves sum into partials, added afterwards in segment order (kernels_graph.hip).
+#define SGL_GRAPH_HUB 128
+#define SGL_GRAPH_SEG 64
+struct DevGraph {
+    double* x = nullptr;
+    int32_t* i = nullptr;
+    int64_t* p = nullptr;
+    int64_t nnz = 0;
+    int32_t n = 0;              // 0: no graph set
+    int32_t* seg_col = nullptr; // [nseg] hub column of each segment (segments of one hub are contiguous, in entry order)
+    int64_t* seg_q0 = nullptr;  // [nseg] first entry of each segment
+    int32_t* hub_col = nullptr; // [nhub] the hub columns
+    int32_t* hub_seg0 = nullptr;// [nhub + 1] first segment of each hub
+    double* part = nullptr;     // [nseg * k] partial sums of the segments
+    int32_t nseg = 0, nhub = 0;
+    double* buf = nullptr;      // k x n (+ 2): the convolved right-hand sides of the H-update
+};
+
 struct sgl_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -172,6 +192,8 @@ struct sgl_ctx {
     double* link_h = nullptr;  // c_linked_nmf: link_rows x ncol / x nrow multipliers of the right-hand sides
     double* link_w = nullptr;
     int link_h_rows = 0, link_w_rows = 0;
+    DevGraph graph;            // c_gcnmf: right-hand sides convolved over the cell graph (sgl_set_graph); dropped with the fit
+    bool dense_input = false;  // the resident matrix came from sgl_upload_dense (a graph is refused there)
     DevMaskList ML[2];         // masked path: the drawn rows of every column, per orientation (kernels_mask.hip); live with the entry streams
     int64_t ml_builds[2] = {0, 0};        // times the lists of an orientation were hashed out on this context (sgl_layout_builds)
     DevMaskList MLkeep[2][SGL_ML_KEEP];   // the lists of the masks used before this one, most recent first (sgl_mask_list_select)
@@ -293,6 +315,9 @@ bool sgl_dense_gemm_available();
 int k_colsum(hipStream_t s, const DevCSC& M, double* sums);
 int k_cell_factor(hipStream_t s, DevCSC& A, DevCSC& At, const double* f, int mode, double scale);
 int k_link_mul(hipStream_t s, double* B, const double* L, int k, int link_rows, int64_t ncols);
+
+// graph convolution (kernels_graph.hip): Y = X G, X and Y k x n column-major (Y must not alias X)
+int k_graph_conv(hipStream_t s, DevGraph& g, const double* X, double* Y, int k);
 
 // NNLS
 #define SGL_NNLS_MAX_PASSES 10

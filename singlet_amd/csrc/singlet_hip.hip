@@ -164,6 +164,20 @@ static void free_csc(DevCSC& M) {
     M = DevCSC();
 }
 
+static void free_graph(sgl_ctx* c) {
+    DevGraph& g = c->graph;
+    dev_free(g.x);
+    dev_free(g.i);
+    dev_free(g.p);
+    dev_free(g.seg_col);
+    dev_free(g.seg_q0);
+    dev_free(g.hub_col);
+    dev_free(g.hub_seg0);
+    dev_free(g.part);
+    dev_free(g.buf);
+    g = DevGraph();
+}
+
 // keep_streams: the entry streams (and their buffers) survive a re-init of the fit on the SAME matrix -- every
 // path that changes the matrix calls free_fit(c) without it
 static void free_fit(sgl_ctx* c, bool keep_streams = false) {
@@ -185,6 +199,7 @@ static void free_fit(sgl_ctx* c, bool keep_streams = false) {
     dev_free(c->link_w);
     c->link_h = c->link_w = nullptr;
     c->link_h_rows = c->link_w_rows = 0;
+    free_graph(c);
     dev_free(c->A.seg);
     dev_free(c->At.seg);
     if (!keep_streams) {
@@ -204,6 +219,7 @@ static void free_matrix(sgl_ctx* c) {
     dev_free(c->col_nnz_At);
     dev_free(c->col_nnz_At_global);
     c->gene_nnz_global = false;
+    c->dense_input = false;
 }
 
 #define CTX_GUARD(c)                                                 \
@@ -276,6 +292,7 @@ extern "C" int sgl_set_stream(sgl_ctx* c, void* hip_stream) {
 extern "C" int sgl_set_allreduce(sgl_ctx* c, sgl_allreduce_fn fn, void* user) {
     CTX_GUARD(c);
     if (c->team) { sgl_set_error("sgl_set_allreduce: the context belongs to a native team (sgl_multi_* / sgl_comm_init_rank)"); return SGL_ESTATE; }
+    if (fn && c->graph.n) { sgl_set_error("sgl_set_allreduce: a cell graph is set (graph-convolutional NMF runs on one shard: its edges cross shards)"); return SGL_EINVAL; }
     c->allreduce = fn;
     c->allreduce_user = user;
     // which W columns predict() skips (l.340) depends on the gene counts over ALL shards: they are
@@ -490,6 +507,7 @@ extern "C" int sgl_upload_dense(sgl_ctx* c, const double* A, int32_t nrow, int32
     if (!A || nrow <= 0 || ncol <= 0) { sgl_set_error("sgl_upload_dense: missing or empty matrix"); return SGL_EINVAL; }
     free_fit(c);
     free_matrix(c);
+    c->dense_input = true;
     c->cell_offset = 0;
     c->ncells_total = ncol;
     const size_t tot = (size_t)nrow * (size_t)ncol;
@@ -722,7 +740,7 @@ static int fit_init_impl(sgl_ctx* c, int32_t k, const double* w_init, uint64_t s
     SGLCHK(dev_alloc(&c->Wprev, (size_t)k * m));
     SGLCHK(dev_alloc(&c->H, (size_t)k * n + 2));
     SGLCHK(dev_alloc(&c->d, (size_t)k));
-    SGLCHK(dev_alloc(&c->B, (size_t)k * n));
+    SGLCHK(dev_alloc(&c->B, (size_t)k * n + 2));   // (+ 2 as H: with a graph B holds H G, read like H by the W-side accumulate)
     SGLCHK(dev_alloc(&c->red, (size_t)k * mpad + (size_t)k * k + (size_t)k));
     SGLCHK(dev_alloc(&c->G, (size_t)k * k));
     SGLCHK(dev_alloc(&c->Gpad, (size_t)SGL_LANE_NNLS_MAX_K * (SGL_LANE_NNLS_MAX_K + 16) + 64));
@@ -860,9 +878,12 @@ extern "C" int sgl_step_h(sgl_ctx* c, double L1, double L2) {
       if (c->dense_gemm) SGLCHK(k_dense_rhs(c, 0, c->W, k, c->B));   // dense predict: b = w * A.col(i), src/singlet.cpp:377
       else if (c->use_tiled) SGLCHK(k_acc_tiled_all(c->stream, c->TA, c->W, c->B, k));
       else SGLCHK(k_acc(c->stream, c->A, c->W, k, c->B, 0, 1, 0, 0, 0));
-      if (c->link_h) SGLCHK(k_link_mul(c->stream, c->B, c->link_h, k, c->link_h_rows, c->A.ncol)); }  // predict_link l.429-430
+      if (c->link_h) SGLCHK(k_link_mul(c->stream, c->B, c->link_h, k, c->link_h_rows, c->A.ncol));  // predict_link l.429-430
+      if (c->graph.n) SGLCHK(k_graph_conv(c->stream, c->graph, c->B, c->graph.buf, k)); }  // gcnmf_update_h l.1684-1688: Bc = B G
     { Phase ph(c, SGL_PH_NNLS_H);
-      SGLCHK(sgl_nnls_shared(c, c->G, c->B, c->H, c->solve_empty ? nullptr : c->col_nnz_A, c->A.ncol, L1, L2, c->sweep_counters + 0, true)); }
+      // with a graph EVERY column is solved (l.1689), from the convolved right-hand sides
+      if (c->graph.n) SGLCHK(sgl_nnls_shared(c, c->G, c->graph.buf, c->H, nullptr, c->A.ncol, L1, L2, c->sweep_counters + 0, true));
+      else SGLCHK(sgl_nnls_shared(c, c->G, c->B, c->H, c->solve_empty ? nullptr : c->col_nnz_A, c->A.ncol, L1, L2, c->sweep_counters + 0, true)); }
     return SGL_OK;
 }
 
@@ -890,9 +911,12 @@ extern "C" int sgl_step_w(sgl_ctx* c, double L1, double L2) {
     const int64_t* gene_nnz = nullptr;
     SGLCHK(gene_counts(c, &gene_nnz));
     { Phase ph(c, SGL_PH_RHS_W);
-      if (c->dense_gemm) SGLCHK(k_dense_rhs(c, 1, c->H, k, Bw));
-      else if (c->use_tiled && c->TAt.roff) SGLCHK(k_acc_tiled_all(c->stream, c->TAt, c->H, Bw, k));
-      else SGLCHK(k_acc(c->stream, c->At, c->H, k, Bw, 0, 1, 0, 0, 0)); }
+      // gcnmf_update_w l.1703-1706: b_j = sum over t(A)'s column j of A(j, c) (H G)(:, c) -- H G goes to B, which the H solve is done with
+      const double* F = c->H;
+      if (c->graph.n) { SGLCHK(k_graph_conv(c->stream, c->graph, c->H, c->B, k)); F = c->B; }
+      if (c->dense_gemm) SGLCHK(k_dense_rhs(c, 1, F, k, Bw));
+      else if (c->use_tiled && c->TAt.roff) SGLCHK(k_acc_tiled_all(c->stream, c->TAt, F, Bw, k));
+      else SGLCHK(k_acc(c->stream, c->At, F, k, Bw, 0, 1, 0, 0, 0)); }
     { Phase ph(c, SGL_PH_GRAM); SGLCHK(k_gram(c, c->H, k, c->A.ncol, Gh, 0.0)); }
     SGLCHK(do_allreduce(c, c->red, (int64_t)k * m + (int64_t)k * k));
     { Phase ph(c, SGL_PH_GRAM);
@@ -901,7 +925,7 @@ extern "C" int sgl_step_w(sgl_ctx* c, double L1, double L2) {
       SGLCHK(k_gram_add_diag(c->stream, c->G, k, 1e-15)); }
     { Phase ph(c, SGL_PH_NNLS_W);
       if (c->link_w) SGLCHK(k_link_mul(c->stream, Bw, c->link_w, k, c->link_w_rows, m));  // on the complete (all-reduced) sums
-      SGLCHK(sgl_nnls_shared(c, c->G, Bw, c->W, c->solve_empty ? nullptr : gene_nnz, m, L1, L2, c->sweep_counters + 1)); }
+      SGLCHK(sgl_nnls_shared(c, c->G, Bw, c->W, (c->solve_empty || c->graph.n) ? nullptr : gene_nnz, m, L1, L2, c->sweep_counters + 1)); }
     return SGL_OK;
 }
 
@@ -1097,6 +1121,7 @@ extern "C" int sgl_op_mse_test(sgl_ctx* c, uint64_t seed, uint64_t inv_density, 
 }
 
 static int masked_step_guard(sgl_ctx* c, uint64_t inv_density, const char* who) {
+    if (c->graph.n) { sgl_set_error("%s: a cell graph is set (graph-convolutional NMF has no masked variant)", who); return SGL_EINVAL; }
     if (c->allreduce || (c->team && sgl_team_size(c) > 1)) { sgl_set_error("%s: single shard only (the sharded masked loop is sgl_ard_run on a native team)", who); return SGL_ESTATE; }
     if (c->k > SGL_MASK_MAX_K) { sgl_set_error("%s: rank %d above the masked path's limit of %d", who, c->k, SGL_MASK_MAX_K); return SGL_EINVAL; }
     if (inv_density == 0) { sgl_set_error("%s: inv_density must be positive", who); return SGL_EINVAL; }
@@ -1125,6 +1150,7 @@ extern "C" int sgl_ard_run(sgl_ctx* c, double tol, int32_t maxit, double L1, dou
                            int32_t* iter, double* tol_out, double* score_overfit, int32_t* n_trace, int32_t* n_iter,
                            const sgl_callbacks* cb) {
     FIT_GUARD(c);
+    if (c->graph.n) { sgl_set_error("sgl_ard_run: a cell graph is set (graph-convolutional NMF has no masked variant)"); return SGL_EINVAL; }
     if (c->allreduce) { sgl_set_error("the masked (ARD) path is cell-sharded on a native team only (sgl_multi_* / sgl_comm_init_rank), not through the all-reduce hook"); return SGL_EINVAL; }
     if (c->k > SGL_MASK_MAX_K) { sgl_set_error("c_ard_nmf: rank %d above the masked path's limit of %d", c->k, SGL_MASK_MAX_K); return SGL_EINVAL; }
     if (trace_test_mse <= 0 || inv_density == 0 || !test_mse || !iter || !tol_out || !score_overfit || !n_trace) {
@@ -1339,6 +1365,10 @@ extern "C" int sgl_c_nmf(const double* Ax, const int32_t* Ai, const int32_t* Ap,
 extern "C" int sgl_set_links(sgl_ctx* c, const double* link_h, int32_t link_h_rows, int32_t link_h_cols, const double* link_w,
                              int32_t link_w_rows, int32_t link_w_cols) {
     FIT_GUARD(c);
+    if (c->graph.n && ((link_h && link_h_cols == c->A.ncol && link_h_rows > 0) || (link_w && link_w_cols == c->A.nrow && link_w_rows > 0))) {
+        sgl_set_error("sgl_set_links: a cell graph is set (the reference has no linked graph-convolutional NMF)");
+        return SGL_EINVAL;
+    }
     dev_free(c->link_h);
     dev_free(c->link_w);
     c->link_h = c->link_w = nullptr;
@@ -1377,6 +1407,123 @@ extern "C" int sgl_c_linked_nmf(const double* Ax, const int32_t* Ai, const int32
     SGLCHK(sgl_set_links(hd.c, link_h, link_h_rows, link_h_cols, link_w, link_w_rows, link_w_cols));
     SGLCHK(sgl_nmf_run(hd.c, tol, maxit, L1, L1, L2, L2, n_iter, tol_trace, cb));
     return sgl_get_factors(hd.c, w_out, d_out, h_out);
+}
+
+// c_gcnmf's cell graph G (src/singlet.cpp:1668-1730): n x n, n = the cells of the resident matrix, as a dgCMatrix.  Checked
+// on the host (the kernels index factor columns by its rows): p[0] = 0 and monotone, rows strictly ascending within a column
+// and in [0, n), values finite.  Columns above SGL_GRAPH_HUB entries get their segment lists here (kernels_graph.hip).
+extern "C" int sgl_set_graph(sgl_ctx* c, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol) {
+    FIT_GUARD(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    free_graph(c);
+    if (!Gx && !Gi && !Gp) return SGL_OK;   // NULL clears it
+    if (!Gx || !Gi || !Gp) { sgl_set_error("sgl_set_graph: G must be fully given or fully NULL"); return SGL_EINVAL; }
+    // edges cross shards, and the reference defines none of these combinations
+    if (c->team) { sgl_set_error("sgl_set_graph: the context is a rank of a native team (graph-convolutional NMF runs on one shard)"); return SGL_EINVAL; }
+    if (c->allreduce) { sgl_set_error("sgl_set_graph: an all-reduce hook is installed (graph-convolutional NMF runs on one shard)"); return SGL_EINVAL; }
+    if (c->dense_input) { sgl_set_error("sgl_set_graph: the matrix was uploaded dense (c_gcnmf takes a dgCMatrix)"); return SGL_EINVAL; }
+    if (c->link_h || c->link_w) { sgl_set_error("sgl_set_graph: link matrices are set (the reference has no linked graph-convolutional NMF)"); return SGL_EINVAL; }
+    const int32_t n = c->A.ncol;
+    if (G_nrow != n || G_ncol != n) {
+        sgl_set_error("sgl_set_graph: G is %d x %d, the matrix has %d cells (G must be n x n)", G_nrow, G_ncol, n);
+        return SGL_EINVAL;
+    }
+    if (Gp[0] != 0) { sgl_set_error("sgl_set_graph: not a valid dgCMatrix: p[0] = %d", Gp[0]); return SGL_EINVAL; }
+    std::vector<int64_t> p64((size_t)n + 1);
+    std::vector<int32_t> seg_col, hub_col, hub_seg0;
+    std::vector<int64_t> seg_q0;
+    p64[0] = 0;
+    for (int32_t j = 0; j < n; ++j) {
+        const int64_t lo = Gp[j], hi = Gp[j + 1];
+        if (hi < lo) { sgl_set_error("sgl_set_graph: not a valid dgCMatrix: p decreases at column %d", j); return SGL_EINVAL; }
+        for (int64_t q = lo; q < hi; ++q) {
+            if (Gi[q] < 0 || Gi[q] >= n) { sgl_set_error("sgl_set_graph: not a valid dgCMatrix: row index %d outside [0, %d) in column %d", Gi[q], n, j); return SGL_EINVAL; }
+            if (q > lo && Gi[q] <= Gi[q - 1]) { sgl_set_error("sgl_set_graph: not a valid dgCMatrix: row indices not strictly ascending in column %d", j); return SGL_EINVAL; }
+            if (!std::isfinite(Gx[q])) { sgl_set_error("sgl_set_graph: non-finite value (NA / NaN / Inf) in column %d of G", j); return SGL_EINVAL; }
+        }
+        p64[(size_t)j + 1] = hi;
+        if (hi - lo > SGL_GRAPH_HUB) {
+            hub_col.push_back(j);
+            hub_seg0.push_back((int32_t)seg_col.size());
+            for (int64_t q = lo; q < hi; q += SGL_GRAPH_SEG) { seg_col.push_back(j); seg_q0.push_back(q); }
+        }
+    }
+    hub_seg0.push_back((int32_t)seg_col.size());
+    DevGraph& g = c->graph;
+    const int k = c->k;
+    g.nnz = p64[(size_t)n];
+    int rc = dev_alloc(&g.x, (size_t)g.nnz);
+    if (rc == SGL_OK) rc = dev_alloc(&g.i, (size_t)g.nnz);
+    if (rc == SGL_OK) rc = dev_alloc(&g.p, (size_t)n + 1);
+    if (rc == SGL_OK) rc = dev_alloc(&g.buf, (size_t)k * n + 2);
+    if (rc == SGL_OK && !hub_col.empty()) {
+        g.nhub = (int32_t)hub_col.size();
+        g.nseg = (int32_t)seg_col.size();
+        rc = dev_alloc(&g.seg_col, seg_col.size());
+        if (rc == SGL_OK) rc = dev_alloc(&g.seg_q0, seg_q0.size());
+        if (rc == SGL_OK) rc = dev_alloc(&g.hub_col, hub_col.size());
+        if (rc == SGL_OK) rc = dev_alloc(&g.hub_seg0, hub_seg0.size());
+        if (rc == SGL_OK) rc = dev_alloc(&g.part, (size_t)g.nseg * k);
+    }
+    hipError_t e = hipSuccess;
+    auto h2d = [&](void* dst, const void* src, size_t bytes) {
+        if (e == hipSuccess && bytes > 0) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
+    };
+    if (rc == SGL_OK) {
+        h2d(g.x, Gx, sizeof(double) * (size_t)g.nnz);
+        h2d(g.i, Gi, sizeof(int32_t) * (size_t)g.nnz);
+        h2d(g.p, p64.data(), sizeof(int64_t) * p64.size());
+        if (g.nhub > 0) {
+            h2d(g.seg_col, seg_col.data(), sizeof(int32_t) * seg_col.size());
+            h2d(g.seg_q0, seg_q0.data(), sizeof(int64_t) * seg_q0.size());
+            h2d(g.hub_col, hub_col.data(), sizeof(int32_t) * hub_col.size());
+            h2d(g.hub_seg0, hub_seg0.data(), sizeof(int32_t) * hub_seg0.size());
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host vectors leave scope
+        if (e != hipSuccess) { (void)hipGetLastError(); sgl_set_error("sgl_set_graph: %s", hipGetErrorString(e)); rc = SGL_EHIP; }
+    }
+    if (rc != SGL_OK) { free_graph(c); return rc; }
+    g.n = n;
+    return SGL_OK;
+}
+
+// c_gcnmf (src/singlet.cpp:1712-1730, src/RcppExports.cpp:399-417): w_init as R passes it (w_rows x w_cols, column-major) --
+// transposed when w.rows() == A.rows() && w.rows() != w.cols() (l.1713); h starts at 0, d at 1.  w_out: m x k column-major
+// (the reference returns w.transpose()), h_out: k x n column-major.
+extern "C" int sgl_c_gcnmf(const double* Ax, const int32_t* Ai, const int32_t* Ap, const double* Atx, const int32_t* Ati,
+                           const int32_t* Atp, int32_t nrow, int32_t ncol, const double* Gx, const int32_t* Gi, const int32_t* Gp,
+                           int32_t G_nrow, int32_t G_ncol, double tol, uint16_t maxit, int verbose, double L1, double L2,
+                           uint16_t threads, const double* w_init, int32_t w_rows, int32_t w_cols, int32_t k, double* w_out,
+                           double* d_out, double* h_out, int32_t* n_iter, double* tol_trace, const sgl_callbacks* cb) {
+    (void)verbose; (void)threads;
+    if (!w_init || !w_out || !d_out || !h_out) { sgl_set_error("sgl_c_gcnmf: NULL factor buffer"); return SGL_EINVAL; }
+    if (!Gx || !Gi || !Gp) { sgl_set_error("sgl_c_gcnmf: G is required"); return SGL_EINVAL; }
+    const bool transpose = (w_rows == nrow && w_rows != w_cols);
+    if ((transpose ? w_cols : w_rows) != k || (transpose ? w_rows : w_cols) != nrow) {
+        sgl_set_error("sgl_c_gcnmf: w is %d x %d; expected k x m or m x k with k = %d, m = %d", w_rows, w_cols, k, nrow);
+        return SGL_EINVAL;
+    }
+    if (k <= 0 || k > SGL_MAX_K) { sgl_set_error("rank k=%d unsupported (1..%d)", k, SGL_MAX_K); return SGL_EINVAL; }
+    // the fit's W is k x m column-major (factor rows of a gene contiguous)
+    std::vector<double> wk;
+    const double* w0 = w_init;
+    if (transpose) {
+        wk.resize((size_t)k * nrow);
+        for (int32_t g = 0; g < nrow; ++g)
+            for (int32_t f = 0; f < k; ++f) wk[(size_t)g * k + f] = w_init[(size_t)f * nrow + g];
+        w0 = wk.data();
+    }
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, Atx, Ati, Atp, nrow, ncol, 0, ncol));
+    SGLCHK(sgl_fit_init(hd.c, k, w0, 0));
+    SGLCHK(sgl_set_graph(hd.c, Gx, Gi, Gp, G_nrow, G_ncol));
+    SGLCHK(sgl_nmf_run(hd.c, tol, maxit, L1, L1, L2, L2, n_iter, tol_trace, cb));
+    std::vector<double> wkm((size_t)k * nrow);
+    SGLCHK(sgl_get_factors(hd.c, wkm.data(), d_out, h_out));
+    for (int32_t f = 0; f < k; ++f)   // w.transpose(): m x k column-major
+        for (int32_t g = 0; g < nrow; ++g) w_out[(size_t)f * nrow + g] = wkm[(size_t)g * k + f];
+    return SGL_OK;
 }
 
 // c_nmf_dense (src/singlet.cpp:1052-1054): sgl_upload_dense keeps the matrix as its CSC image (zeros add exact zeros

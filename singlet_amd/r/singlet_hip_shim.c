@@ -400,11 +400,39 @@ SEXP _singlet_weight_by_split(SEXP A_, SEXP split_by_, SEXP n_groups_) {
     return A_;
 }
 
+/* ---- c_gcnmf(A, At, G, tol, maxit, verbose, L1, L2, threads, w) ---- *
+ * (src/singlet.cpp:1668-1730, glue src/RcppExports.cpp:399-417; R/RunGCNMF.R:77).  G is the n x n cell
+ * graph (dgCMatrix).  w may be k x m or m x k (transposed iff nrow(w) == nrow(A) && nrow(w) != ncol(w),
+ * l.1713); w comes back m x k, as the reference returns w.transpose(). */
+SEXP _singlet_c_gcnmf(SEXP A_, SEXP At_, SEXP G_, SEXP tol_, SEXP maxit_, SEXP verbose_, SEXP L1_, SEXP L2_, SEXP threads_, SEXP w_) {
+    dgc_view A = view_dgc(A_, "A"), At = view_dgc(At_, "At"), G = view_dgc(G_, "G");
+    if (!Rf_isMatrix(w_) || TYPEOF(w_) != REALSXP) Rf_error("w must be a numeric matrix");
+    const int w_rows = Rf_nrows(w_), w_cols = Rf_ncols(w_);
+    const int k = (w_rows == A.nrow && w_rows != w_cols) ? w_cols : w_rows;
+    const int verbose = Rf_asLogical(verbose_);
+    SEXP w = PROTECT(Rf_allocMatrix(REALSXP, A.nrow, k)), d = PROTECT(Rf_allocVector(REALSXP, k)),
+         h = PROTECT(Rf_allocMatrix(REALSXP, k, A.ncol));
+    sgl_callbacks cb = {NULL, verbose ? log_nmf : NULL, poll_cb};
+    if (verbose) Rprintf("\n%4s | %8s \n---------------\n", "iter", "tol");
+    int n_iter = 0;
+    int rc = sgl_c_gcnmf(A.x, A.i, A.p, At.x, At.i, At.p, A.nrow, A.ncol, G.x, G.i, G.p, G.nrow, G.ncol, Rf_asReal(tol_),
+                         (uint16_t)Rf_asInteger(maxit_), verbose, Rf_asReal(L1_), Rf_asReal(L2_), (uint16_t)Rf_asInteger(threads_),
+                         REAL(w_), w_rows, w_cols, k, REAL(w), REAL(d), REAL(h), &n_iter, NULL, &cb);
+    if (rc == SGL_EINTR) { UNPROTECT(3); Rf_onintr(); }
+    fail_if(rc);
+    const char* names[3] = {"w", "d", "h"};
+    SEXP vals[3] = {w, d, h};
+    SEXP out = named_list(3, names, vals);
+    UNPROTECT(3);
+    return out;
+}
+
 static const R_CallMethodDef call_entries[] = {
     {"_singlet_weight_by_split", (DL_FUNC)&_singlet_weight_by_split, 3},
     {"_singlet_c_nmf", (DL_FUNC)&_singlet_c_nmf, 11},
     {"_singlet_c_ard_nmf", (DL_FUNC)&_singlet_c_ard_nmf, 13},
     {"_singlet_c_linked_nmf", (DL_FUNC)&_singlet_c_linked_nmf, 11},
+    {"_singlet_c_gcnmf", (DL_FUNC)&_singlet_c_gcnmf, 10},
     {"_singlet_c_nmf_dense", (DL_FUNC)&_singlet_c_nmf_dense, 11},
     {"_singlet_c_nmf_sparse_list", (DL_FUNC)&_singlet_c_nmf_sparse_list, 9},
     {"_singlet_c_ard_nmf_sparse_list", (DL_FUNC)&_singlet_c_ard_nmf_sparse_list, 13},
