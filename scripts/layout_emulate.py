@@ -1,37 +1,128 @@
 #!/usr/bin/env python3
-"""Host emulation of the entry-stream layout arithmetic (kernels_tiled.hip: tiled_count_kernel) -- stored entries per
-non-zero for a CSC matrix, with the columns in matrix order or in descending-count order, pairs (p, 32 + p) or
-neighbours (2p, 2p + 1).  Usage: layout_emulate.py [pbmc3k | iid M N INV] k"""
+"""Host model of the entry-stream layout (kernels_tiled.hip: tiled_count_kernel) -- the sliding-window schedule, stored entries
+per non-zero for a CSC matrix.  `stream_counts` returns the same group counts the device writes; `entries` their total in
+stored entries, which is what sgl_layout_get reports.  Usage: layout_emulate.py [pbmc3k | iid M N INV] k"""
 import sys
 import os
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LDS_BYTES = 160 * 1024 - 512
 
 
-def entries(p, i, nrow, k, order="sorted", pairing="adjacent"):
-    ncol = p.shape[0] - 1
-    KS = (k + 1) & ~1
-    TR = (160 * 1024 - 512) // (KS * 8) // 8 * 8
-    TR = min(TR, 984)
+def tile_rows(k, nsl):
+    """LDS-sized tile rows of the build (before the small-matrix shortening)"""
+    KS = 32 if nsl == 4 else (k + 1) & ~1
+    return min(LDS_BYTES // (KS * 8) // 8 * 8, 984)
+
+
+def sorted_perm(p):
+    """column order of the stream: descending non-zero count, ties in matrix order"""
+    return np.argsort(-np.diff(np.asarray(p, dtype=np.int64)), kind="stable")
+
+
+def block_ranges(T, nb, nr):
+    """row-block ranges [b0, b1) of the nr tile ranges (floor / ceil of T / nr tiles each, two blocks per tile)"""
+    return [(2 * (y * T // nr), min(2 * ((y + 1) * T // nr), nb)) for y in range(nr)]
+
+
+def stream_counts(p, i, nrow, TR, nsl, ranges=1, order="sorted", tail_wg0=-1, tail_R=1, trace=None):
+    """Group counts cnt[wb, b, pair] of the sliding-window stream (b = row block of D = TR / 2 rows = the stage).
+
+    In stage b the LDS holds blocks b and b + 1 of the range; every column finishes its entries in block b and may run ahead
+    into block b + 1.  Per pair: n = the larger number of entries left in block b over its nsl columns, rounded up to
+    groups of four; every column takes min(n, entries left in the window) real entries, pads for the rest.  The chunk
+    (wave block, stage) is rounded up to whole 64-slot sets by extra groups on the last pairs, each taking as many as
+    its columns still have run-ahead entries for; what is left goes on pair 31 as pads.
+    trace: a list that receives (col, first entry, entries, b) for every run of real entries, in stream order."""
+    p = np.asarray(p, dtype=np.int64)
+    i = np.asarray(i, dtype=np.int64)
+    ncol = p.size - 1
+    D = TR // 2
+    T = (nrow + TR - 1) // TR
+    nb = (nrow + D - 1) // D
+    CW = 32 * nsl
+    nwb = (ncol + CW - 1) // CW
+    gps = 16 // nsl
+    perm = sorted_perm(p) if order == "sorted" else np.arange(ncol)
+    # seg[b, c] = first entry of column c at or below row b * D
+    col_of = np.repeat(np.arange(ncol), np.diff(p))
+    per = np.zeros((nb + 1, ncol + 1), dtype=np.int64)
+    np.add.at(per, (i // D + 1, col_of), 1)
+    seg = p[:-1][None, :] + np.cumsum(per, axis=0)[:, :ncol]
+    # slot (wb, pair, h) -> column (-1: none); seg of an absent column is 0 everywhere
+    slot = np.full(nwb * CW, -1, dtype=np.int64)
+    slot[:ncol] = perm
+    slot = slot.reshape(nwb, 32, nsl)
+    present = slot >= 0
+    sc = np.where(present, slot, 0)
+    cnt = np.zeros((nwb, nb, 32), dtype=np.int64)
+    nwg = (nwb + 7) // 8
+    for wb in range(nwb):
+        wg = wb // 8
+        nr = tail_R if (tail_R > 1 and tail_wg0 >= 0 and wg >= tail_wg0) else ranges
+        nr = max(1, min(nr, T))
+        cols, pres = sc[wb], present[wb]
+        for b0, b1 in block_ranges(T, nb, nr):
+            if b0 >= b1:
+                continue
+            pos = np.where(pres, seg[b0][cols], 0)
+            for b in range(b0, b1):
+                hi = min(b + 2, b1)
+                end_b = np.where(pres, seg[b + 1][cols], 0)
+                end_w = np.where(pres, seg[hi][cols], 0)
+                g = (np.max(end_b - pos, axis=1) + 3) // 4
+                cap = (np.max(end_w - pos, axis=1) + 3) // 4 - g
+                rem = (-int(g.sum())) % gps
+                for q in range(31, -1, -1):
+                    if rem == 0:
+                        break
+                    e = min(int(cap[q]), rem)
+                    g[q] += e
+                    rem -= e
+                g[31] += rem
+                take = np.minimum(4 * g[:, None], end_w - pos)
+                if trace is not None:
+                    for q in range(32):
+                        for h in range(nsl):
+                            if pres[q, h] and take[q, h] > 0:
+                                trace.append((int(cols[q, h]), int(pos[q, h]), int(take[q, h]), b))
+                pos = pos + take
+                cnt[wb, b] = g
+            assert np.array_equal(pos[pres], seg[b1][cols][pres]), "a column left entries behind"
+    return cnt
+
+
+def entries(p, i, nrow, k, nsl=2, TR=None, **kw):
+    """stored entries of the stream (all column slots, pads included)"""
+    TR = TR or tile_rows(k, nsl)
+    return int(stream_counts(p, i, nrow, TR, nsl, **kw).sum()) * 4 * nsl
+
+
+def lockstep_entries(p, i, nrow, TR, nsl, order="sorted"):
+    """the previous rule for comparison: runs padded to equal length per tile of TR rows, chunks of (wave block, tile)"""
+    p = np.asarray(p, dtype=np.int64)
+    ncol = p.size - 1
     T = (nrow + TR - 1) // TR
     col_of = np.repeat(np.arange(ncol), np.diff(p))
-    cnt = np.zeros((ncol, T), dtype=np.int64)
-    np.add.at(cnt, (col_of, i // TR), 1)
-    nnzc = np.diff(p)
-    perm = np.argsort(-nnzc, kind="stable") if order == "sorted" else np.arange(ncol)
-    nwb = (ncol + 63) // 64
-    padded = np.zeros((nwb * 64, T), dtype=np.int64)
-    padded[:ncol] = cnt[perm]
-    blk = padded.reshape(nwb, 64, T)
-    if pairing == "adjacent":
-        a, b = blk[:, 0::2, :], blk[:, 1::2, :]
-    else:
-        a, b = blk[:, :32, :], blk[:, 32:, :]
-    g = (np.maximum(a, b) + 3) // 4          # groups per (wb, pair, t)
-    tot = g.sum(axis=1)                      # per (wb, t)
-    tot += (8 - tot % 8) % 8
-    return int(tot.sum()) * 8
+    c = np.zeros((ncol, T), dtype=np.int64)
+    np.add.at(c, (col_of, np.asarray(i) // TR), 1)
+    perm = sorted_perm(p) if order == "sorted" else np.arange(ncol)
+    CW = 32 * nsl
+    nwb = (ncol + CW - 1) // CW
+    pad = np.zeros((nwb * CW, T), dtype=np.int64)
+    pad[:ncol] = c[perm]
+    g = (pad.reshape(nwb, 32, nsl, T).max(axis=2) + 3) // 4
+    tot = g.sum(axis=1)
+    tot += (-tot) % (16 // nsl)
+    return int(tot.sum()) * 4 * nsl
+
+
+def transpose(p, i, nrow):
+    p = np.asarray(p, dtype=np.int64)
+    col_of = np.repeat(np.arange(p.size - 1), np.diff(p))
+    o = np.argsort(i, kind="stable")
+    return np.concatenate([[0], np.cumsum(np.bincount(i, minlength=nrow))]).astype(np.int64), col_of[o]
 
 
 def main():
@@ -52,16 +143,13 @@ def main():
         p = np.concatenate([[0], np.cumsum(D.sum(axis=0))]).astype(np.int64)
         nrow, ncol = m, n
     nnz = int(p[-1])
-    # transpose
-    col_of = np.repeat(np.arange(ncol), np.diff(p))
-    o = np.argsort(i, kind="stable")
-    ti = col_of[o]
-    tp = np.concatenate([[0], np.cumsum(np.bincount(i, minlength=nrow))]).astype(np.int64)
-    for name, (pp, ii, nr) in {"H side (columns = cells)": (p, i, nrow), "W side (columns = genes)": (tp, ti, ncol)}.items():
-        for order in ("matrix", "sorted"):
-            for pairing in ("p,32+p", "adjacent"):
-                e = entries(pp, ii, nr, k, order, pairing)
-                print("%-26s k=%-3d order=%-7s pairs=%-8s entries/nnz = %.3f" % (name, k, order, pairing, e / nnz))
+    tp, ti = transpose(p, i, nrow)
+    for nsl in ((4, 2) if k <= 32 else (2,)):
+        TR = tile_rows(k, nsl)
+        for name, (pp, ii, nr) in {"H side (columns = cells)": (p, i, nrow), "W side (columns = genes)": (tp, ti, ncol)}.items():
+            old = lockstep_entries(pp, ii, nr, TR, nsl)
+            new = entries(pp, ii, nr, k, nsl, TR)
+            print("%-26s k=%-3d nsl=%d TR=%-3d entries/nnz: lock-step tiles %.3f, sliding window %.3f" % (name, k, nsl, TR, old / nnz, new / nnz))
 
 
 if __name__ == "__main__":

@@ -14,20 +14,26 @@
 // Layout ("re-blocked stream", built once per (matrix, k) by sgl_tiled_build):
 //   * rows are cut into tiles of TR rows, TR * KS * 8 B <= 160 KiB - 512 B (one LDS
 //     tile; KS = k rounded up to even so every row starts 16-byte aligned);
+//   * the LDS tile is a ring of two slots of D = TR / 2 rows: row block b (rows [b D, (b + 1) D)) sits in slot
+//     b % 2, and stage b of the loop has blocks b and b + 1 in LDS.  After stage b one barrier frees the slot of
+//     block b, block b + 2 is staged into it, a second barrier; the first stage of a tile range stages two blocks;
 //   * columns are cut into wave blocks of 64 columns; a workgroup of 8 waves
 //     owns 512 columns and keeps their k-vectors in VGPRs across all row tiles.
 //     Lanes 0-31 of a wave accumulate column p of the block, lanes 32-63 column
 //     32 + p ("column pair" p = 0..31), lane l holding factors 2(l&31), +1;
-//   * per (wave block wb, tile t) -- a chunk -- the entries of the pair's two
-//     columns are stored as two half-streams that advance in lockstep: the runs
-//     of both columns are padded (x = 0 entries) to the same multiple of 4, the
-//     chunk to a multiple of 32 entries per half.  64 consecutive stream slots
-//     hold 32 entries of the A half then 32 of the B half, so one coalesced
-//     64-lane load fetches a "set".  Two arrays: roff (byte offset of the row
-//     inside the LDS tile) and x.  Chunks are ordered (wb, t): one wave reads
-//     ONE linear stream;
-//   * cnt[(wb * T + t) * 32 + p] = number of 4-entry groups of pair p (chunk
-//     padding is booked on the last pair).
+//   * per (wave block wb, stage b) -- a chunk -- the entries of the pair's two
+//     columns are stored as two half-streams that advance in lockstep.  Sliding window (round 7): in stage b every
+//     column finishes its entries of block b and may run ahead into block b + 1 -- the pair takes n = the most
+//     block-b entries either column has left, rounded up to 4, and each column fills those n steps with its own
+//     next entries of the window (x = 0 pads only where it has none left; tiled_count_kernel).  The chunk is
+//     rounded up to a multiple of 32 entries per half the same way, by extra groups on the last pairs.  64
+//     consecutive stream slots hold 32 entries of the A half then 32 of the B half, so one coalesced
+//     64-lane load fetches a "set".  Two arrays: roff (byte offset of the row inside the LDS ring: slot
+//     (r / D) % 2, row r % D) and x.  Chunks are ordered (wb, b): one wave reads ONE linear stream;
+//   * cnt[(wb * NB + b) * 32 + p] = number of 4-entry groups of pair p.
+// The schedule never runs ahead across the edge of a tile range (blockIdx.y, tail pieces): each range is a slab of
+// its own.  Against runs padded to equal length inside every tile (rounds 1 - 6: 1.207 stored entries per
+// non-zero at config 3) the window stores ~1.05 (scripts/layout_emulate.py models the count exactly).
 // Inside a column the products are added in stored (ascending row) order, as
 // in the reference; pads add x = 0 times a finite F entry.
 //
@@ -65,37 +71,91 @@ __device__ __forceinline__ int64_t tiled_slot_col(const int32_t* __restrict__ pe
     return perm ? (int64_t)perm[pos] : pos;
 }
 
-__global__ void tiled_count_kernel(const int64_t* __restrict__ seg, const int32_t* __restrict__ perm, int64_t ncol, int T, int64_t nwb,
-                                   uint8_t* __restrict__ cnt, int64_t* __restrict__ chunk_entries, int nsl) {
-    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // u = wb * T + t
-    if (u >= nwb * T) return;
-    const int64_t wb = u / T;
-    const int t = (int)(u - wb * T);
-    int64_t tot = 0;
-    for (int p = 0; p < TILED_NP; ++p) {
-        int64_t n = 0;
-        for (int h = 0; h < nsl; ++h) {
-            const int64_t col = tiled_slot_col(perm, ncol, wb, h, p, nsl);
-            if (col >= 0) {
-                const int64_t c = seg[(int64_t)(t + 1) * ncol + col] - seg[(int64_t)t * ncol + col];
-                n = c > n ? c : n;
-            }
-        }
-        int g = (int)((n + 3) >> 2);
-        const int gps = 16 / nsl;   // groups (of 4 entries per slot) in a 64-slot set: whole sets per chunk
-        if (p == TILED_NP - 1) g += (int)((gps - ((tot + g) & (gps - 1))) & (gps - 1));
-        cnt[u * TILED_NP + p] = (uint8_t)g;
-        tot += g;
-    }
-    chunk_entries[u] = tot * 4 * nsl;  // all slots
+// Tile ranges of wave block wb (blockIdx.y of the accumulate, or the pieces of a tail-split workgroup): nr ranges of floor / ceil
+// of T / nr tiles.  The range holding row block b ends at block tiled_range_end(...) (exclusive): the schedule never runs ahead
+// across it -- an entry taken into another range would land in another slab and change the sums.
+__device__ __forceinline__ int tiled_ranges_of(int64_t wb, int R, int64_t tail_wg0, int tail_R) {
+    return (tail_R > 1 && tail_wg0 >= 0 && wb / TILED_NW >= tail_wg0) ? tail_R : R;
+}
+__device__ __forceinline__ int tiled_range_end(int b, int T, int NB, int nr) {
+    const int t = b >> 1;
+    const int y = (int)(((int64_t)(t + 1) * nr - 1) / T);           // range of tile t: floor(y T / nr) <= t < floor((y + 1) T / nr)
+    const int b1 = 2 * (int)(((int64_t)(y + 1) * T) / nr);
+    return b1 < NB ? b1 : NB;
 }
 
-// one wave per chunk (wb, t): copy / pad the runs of the 32 column pairs
+// The schedule (sliding window).  The LDS tile is a ring of two row blocks of D = TR / 2 rows; stage b of a tile range holds
+// blocks b and b + 1.  In the chunk (wb, b) every column finishes its entries of block b and may run ahead into block b + 1:
+// a column unit (pair / quad) takes n = the most entries any of its columns has left in block b, rounded up to groups of
+// four, and each of its columns fills those n steps with its own next entries of the window -- pads (x = 0) only where a
+// column has none left.  The chunk is rounded up to whole 64-slot sets by extra groups on the last units, each taking as
+// many as its columns still have window entries for; what no unit can fill goes on unit 31 as pads.
+// One wave per wave block, lane p = unit p (lanes 32-63 mirror 0-31), walking the stages of each of its ranges in order.
+// cnt = groups per (chunk, unit) -- at most D / 4 + D / 4 + 7 <= 253: a byte; ahead = entries of block b a column took in
+// stage b - 1 (<= D); chunk_entries = stored entries of the chunk (all slots).
+__global__ __launch_bounds__(256) void tiled_count_kernel(const int64_t* __restrict__ seg, const int32_t* __restrict__ perm, int64_t ncol,
+                                                          int T, int NB, int64_t nwb, int R, int64_t tail_wg0, int tail_R,
+                                                          uint8_t* __restrict__ cnt, uint16_t* __restrict__ ahead,
+                                                          int64_t* __restrict__ chunk_entries, int nsl) {
+    const int lane = threadIdx.x & 63, p = lane & 31;
+    const int64_t wb = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (wb >= nwb) return;   // wave-uniform
+    const int gps = 16 / nsl;   // groups (of 4 entries per slot) in a 64-slot set
+    int64_t col[4];
+    for (int h = 0; h < 4; ++h) col[h] = h < nsl ? tiled_slot_col(perm, ncol, wb, h, p, nsl) : -1;
+    const int nr = tiled_ranges_of(wb, R, tail_wg0, tail_R);
+    for (int b0 = 0; b0 < NB;) {
+        const int b1 = tiled_range_end(b0, T, NB, nr);
+        int64_t pos[4];
+        for (int h = 0; h < 4; ++h) pos[h] = col[h] >= 0 ? seg[(int64_t)b0 * ncol + col[h]] : 0;
+        for (int b = b0; b < b1; ++b) {
+            const int hi = b + 2 < b1 ? b + 2 : b1;
+            int64_t must = 0, avail = 0, ew[4];
+            for (int h = 0; h < 4; ++h) {
+                ew[h] = 0;
+                if (col[h] >= 0) {
+                    const int64_t eb = seg[(int64_t)(b + 1) * ncol + col[h]];
+                    ew[h] = seg[(int64_t)hi * ncol + col[h]];
+                    must = eb - pos[h] > must ? eb - pos[h] : must;
+                    avail = ew[h] - pos[h] > avail ? ew[h] - pos[h] : avail;
+                }
+            }
+            int g = (int)((must + 3) >> 2);
+            const int cap = (int)((avail + 3) >> 2) - g;
+            int tot = g;
+            for (int o = 16; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 32);
+            const int rem = (gps - (tot & (gps - 1))) & (gps - 1);
+            int suf = cap;   // run-ahead groups units p .. 31 can fill
+            for (int o = 1; o < 32; o <<= 1) {
+                const int v = __shfl_down(suf, o, 32);
+                if (p + o < 32) suf += v;
+            }
+            const int above = suf - cap;
+            int extra = rem - above < cap ? rem - above : cap;
+            if (extra < 0) extra = 0;
+            const int all = __shfl(suf, 0, 32);
+            if (p == TILED_NP - 1 && rem > all) extra += rem - all;
+            g += extra;
+            const int64_t u = wb * NB + b;
+            if (lane < 32) {
+                cnt[u * TILED_NP + p] = (uint8_t)g;
+                for (int h = 0; h < nsl; ++h)
+                    ahead[u * (TILED_NP * nsl) + nsl * p + h] = col[h] >= 0 ? (uint16_t)(pos[h] - seg[(int64_t)b * ncol + col[h]]) : (uint16_t)0;
+            }
+            if (lane == 0) chunk_entries[u] = (int64_t)(tot + rem) * 4 * nsl;
+            for (int h = 0; h < 4; ++h) pos[h] += (4 * (int64_t)g < ew[h] - pos[h]) ? 4 * (int64_t)g : ew[h] - pos[h];
+        }
+        b0 = b1;
+    }
+}
+
+// one wave per chunk (wb, b): copy / pad the runs of the 32 column units.  roff is ring-relative: row r of block r / D sits
+// in LDS slot (r / D) % 2
 __global__ __launch_bounds__(256) void tiled_fill_kernel(const double* __restrict__ x, const int32_t* __restrict__ idx,
                                                          const int64_t* __restrict__ seg, const int32_t* __restrict__ perm,
-                                                         int64_t ncol, int T, int64_t nwb, int TR, int row_bytes,
-                                                         const uint8_t* __restrict__ cnt,
-                                                         const int64_t* __restrict__ cstart,
+                                                         int64_t ncol, int T, int NB, int64_t nwb, int R, int64_t tail_wg0, int tail_R,
+                                                         int D, int row_bytes, const uint8_t* __restrict__ cnt,
+                                                         const uint16_t* __restrict__ ahead, const int64_t* __restrict__ cstart,
                                                          uint32_t* __restrict__ sroff, double* __restrict__ sx,
                                                          int masked, uint64_t seed, SglDiv inv_density, int mask_t,
                                                          int64_t col_off, int64_t row_off, int nsl) {
@@ -103,9 +163,11 @@ __global__ __launch_bounds__(256) void tiled_fill_kernel(const double* __restric
     const int eps = 64 / nsl, eps_sh = nsl == 4 ? 4 : 5;   // entries of one column slot in a 64-slot set
     const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t u = gw; u < nwb * T; u += nw) {
-        const int64_t wb = u / T;
-        const int t = (int)(u - wb * T);
+    for (int64_t u = gw; u < nwb * NB; u += nw) {
+        const int64_t wb = u / NB;
+        const int b = (int)(u - wb * NB);
+        const int b1 = tiled_range_end(b, T, NB, tiled_ranges_of(wb, R, tail_wg0, tail_R));
+        const int hi = b + 2 < b1 ? b + 2 : b1;
         const int64_t c0 = cstart[u];
         int P = 0;  // position in the half-streams
         for (int p = 0; p < TILED_NP; ++p) {
@@ -113,14 +175,18 @@ __global__ __launch_bounds__(256) void tiled_fill_kernel(const double* __restric
             if (n4 == 0) continue;
             for (int h = 0; h < nsl; ++h) {
                 const int64_t col = tiled_slot_col(perm, ncol, wb, h, p, nsl);
-                int64_t a = 0, b = 0;
-                if (col >= 0) { a = seg[(int64_t)t * ncol + col]; b = seg[(int64_t)(t + 1) * ncol + col]; }
+                int64_t a = 0, e = 0;
+                if (col >= 0) {
+                    a = seg[(int64_t)b * ncol + col] + ahead[u * (TILED_NP * nsl) + nsl * p + h];
+                    e = seg[(int64_t)hi * ncol + col];
+                }
                 for (int q = lane; q < n4; q += 64) {
                     uint32_t ro = 0;
                     double xv = 0.0;
-                    if (a + q < b) {
+                    if (a + q < e) {
                         const int32_t r = idx[a + q];
-                        ro = (uint32_t)(r - t * TR) * (uint32_t)row_bytes;
+                        const int blk = r >= (b + 1) * D ? b + 1 : b;
+                        ro = (uint32_t)((blk & 1) * D + (r - blk * D)) * (uint32_t)row_bytes;
                         xv = x[a + q];
                         if (masked) {  // predict_mask leaves the drawn entries out (src/singlet.cpp:449-457): x = 0 adds +0 * F
                             const uint64_t gc = (uint64_t)(col + col_off), gr = (uint64_t)(r + row_off);
@@ -190,6 +256,7 @@ void sgl_tiled_free(DevTiled& S) {
     if (S.x) (void)sgl_pool_free(S.x);
     if (S.cstart) (void)sgl_pool_free(S.cstart);
     if (S.cnt) (void)sgl_pool_free(S.cnt);
+    if (S.ahead) (void)sgl_pool_free(S.ahead);
     if (S.gtab) (void)sgl_pool_free(S.gtab);
     if (S.part) (void)sgl_pool_free(S.part);
     if (S.xm) (void)sgl_pool_free(S.xm);
@@ -291,10 +358,12 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
     }
     S.TR = TR;
     S.T = (int)((M.nrow + TR - 1) / TR);
+    const int D = TR / 2;   // rows of one LDS ring slot (TR is a multiple of 8)
+    S.NB = (int)((M.nrow + D - 1) / D);
     S.ncol = M.ncol;
     S.nrow = M.nrow;
     S.src_nnz = M.nnz;
-    const int64_t nchunks = S.nwb * S.T;
+    const int64_t nchunks = S.nwb * S.NB;
 
     // column order of the stream: descending non-zero count (stable: ties in matrix order); depends on the matrix
     // only, so a rank sweep computes it once
@@ -305,60 +374,10 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
         rc = tiled_build_perm(c, M, S);
     }
     sgl_trace_setup("  stream: column order");
-    // segment starts per (tile, column); kept for the masked value array
-    if (rc == SGL_OK) rc = t_reserve(&S.seg, &S.cap_seg, (size_t)(S.T + 1) * (size_t)M.ncol);
-    sgl_trace_setup("  stream: segment buffer reserved");
-    DevCSC tmp = M;
-    tmp.tile_rows = TR;
-    tmp.ntiles = S.T;
-    tmp.seg = S.seg;
-    if (rc == SGL_OK) rc = k_build_segments(s, tmp);
-    int64_t* chunk_entries = nullptr;
-    if (rc == SGL_OK) rc = t_alloc(&chunk_entries, (size_t)nchunks);
-    if (rc == SGL_OK) rc = t_reserve(&S.cnt, &S.cap_cnt, (size_t)nchunks * TILED_NP);
-    if (rc == SGL_OK) rc = t_reserve(&S.cstart, &S.cap_cstart, (size_t)nchunks + 1);
-    if (rc == SGL_OK) {
-        tiled_count_kernel<<<dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, s>>>(S.seg, S.perm, M.ncol, S.T, S.nwb, S.cnt,
-                                                                                         chunk_entries, nsl);
-        if (hipGetLastError() != hipSuccess) { sgl_set_error("tiled build: count kernel launch failed"); rc = SGL_EHIP; }
-    }
-    if (rc == SGL_OK) rc = k_exclusive_scan(c, chunk_entries, S.cstart, nchunks);
-    if (rc == SGL_OK) rc = k_scan_total(s, chunk_entries, S.cstart, nchunks);
-    int64_t E = 0;
-    if (rc == SGL_OK) {
-        if (hipMemcpyAsync(&E, S.cstart + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { sgl_set_error("tiled build: reading the stream size failed"); rc = SGL_EHIP; }
-    }
-    S.E = E;
-    sgl_trace_setup("  stream: segments, counts, scan");
-    // + TILED_SLACK entries of slack: the kernel prefetches its ring (four or eight 64-entry sets) past the end
-    if (rc == SGL_OK) rc = t_reserve(&S.roff, &S.cap_roff, (size_t)E + TILED_SLACK);
-    if (rc == SGL_OK) rc = t_reserve(&S.x, &S.cap_x, (size_t)E + TILED_SLACK);
-    sgl_trace_setup("  stream: roff / x buffers reserved");
-    if (rc == SGL_OK) {
-        if (hipMemsetAsync(S.roff + E, 0, TILED_SLACK * sizeof(uint32_t), s) != hipSuccess ||
-            hipMemsetAsync(S.x + E, 0, TILED_SLACK * sizeof(double), s) != hipSuccess) { sgl_set_error("tiled build: clearing the stream slack failed"); rc = SGL_EHIP; }
-    }
-    if (rc == SGL_OK && nchunks > 0) {
-        int64_t blocks = (nchunks + 3) / 4;
-        if (blocks > 256 * 64) blocks = 256 * 64;
-        tiled_fill_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(M.x, M.i, S.seg, S.perm, M.ncol, S.T, S.nwb, TR, KS * 8,
-                                                                       S.cnt, S.cstart, S.roff, S.x, 0, 0, sgl_div_make(1), 0, 0, 0, nsl);
-        if (hipGetLastError() != hipSuccess) { sgl_set_error("tiled build: fill kernel launch failed"); rc = SGL_EHIP; }
-    }
-    // the chunk loop's schedule table: E / (4 nsl) groups + slack (a lap of 32 groups is loaded one ahead)
-    const size_t ngroups = (size_t)(E / (4 * nsl));
-    if (rc == SGL_OK) rc = t_reserve(&S.gtab, &S.cap_gtab, ngroups + 256);
-    if (rc == SGL_OK) {
-        if (hipMemsetAsync(S.gtab + ngroups, 0, 256 * sizeof(uint16_t), s) != hipSuccess) { sgl_set_error("tiled build: clearing the schedule slack failed"); rc = SGL_EHIP; }
-    }
-    if (rc == SGL_OK && nchunks > 0) {
-        int64_t blocks = (nchunks + 3) / 4;
-        if (blocks > 256 * 64) blocks = 256 * 64;
-        tiled_gtab_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(S.cnt, S.cstart, nchunks, nsl, S.gtab);
-        if (hipGetLastError() != hipSuccess) { sgl_set_error("tiled build: schedule kernel launch failed"); rc = SGL_EHIP; }
-    }
-    // split of the tile range over blockIdx.y so that the grid fills 256 CUs (1 workgroup per CU)
+    // split of the tile range over blockIdx.y so that the grid fills 256 CUs (1 workgroup per CU).  Decided before the stream is
+    // counted: the schedule does not run ahead across a range edge.  Its cost model needs the stream size, estimated here from
+    // the padding of the sliding-window layout (1.03 - 1.06 entries per non-zero on i.i.d. columns; scripts/layout_emulate.py).
+    const double E_est = (double)M.nnz * 1.06;
     // Two reasons to split: too few column groups to fill the chip (W-update: 30 k genes = 59 workgroups), and -- with
     // the columns sorted by count -- a heaviest workgroup that alone would outlast the average CU's whole share (skewed
     // genes: the top 512 of 30 000 held 11 % of the non-zeros and the pass took 22 ms instead of 11): its tile range is
@@ -397,7 +416,7 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
         //   time(R) = rounds x (largest unit x t_tile + t_wg) + t_reduce(R),   rounds = ceil(groups x R / 256 CUs)
         // t_tile = one workgroup's entry tuples of one tile at the measured 2.4 ns per tuple per CU + 2.5 us of staging,
         // t_wg = 6 us per workgroup (launch, zeroing, output), t_reduce = the slabs written and read back at 4 TB/s.
-        const double t_tile = (double)E / (double)nsl / ((double)nwg_x * (double)S.T) * 2.4e-9 + 2.5e-6;
+        const double t_tile = E_est / (double)nsl / ((double)nwg_x * (double)S.T) * 2.4e-9 + 2.5e-6;
         const double t_wg = 6e-6;
         double best = 1e300;
         for (int r = 1; r <= std::min<int64_t>(S.T, 64); ++r) {
@@ -430,10 +449,10 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
     // only their columns go through slabs.  Same cost model as above.
     S.tail_wg0 = -1;
     S.tail_R = 1;
-    if (S.R == 1 && !S.range_fastest && nwg_x > 256 && S.T > 1 && E >= (4ll << 20) && !getenv("SGL_TILED_NO_TAIL")) {
+    if (S.R == 1 && !S.range_fastest && nwg_x > 256 && S.T > 1 && E_est >= (double)(4ll << 20) && !getenv("SGL_TILED_NO_TAIL")) {
         const int64_t tail = nwg_x % 256;
         if (tail > 0) {
-            const double t_tile = (double)E / (double)nsl / ((double)nwg_x * (double)S.T) * 2.4e-9 + 2.5e-6;
+            const double t_tile = E_est / (double)nsl / ((double)nwg_x * (double)S.T) * 2.4e-9 + 2.5e-6;
             const double t_wg = 6e-6;
             const double tail_cols = (double)tail * TILED_NW * S.CW;
             double best = (double)S.T * t_tile + t_wg;   // left whole: one more round of full length
@@ -445,6 +464,61 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
             }
             if (Rt > 1) { S.tail_wg0 = nwg_x - tail; S.tail_R = Rt; }
         }
+    }
+    // segment starts per (row block, column); kept for the masked value array
+    if (rc == SGL_OK) rc = t_reserve(&S.seg, &S.cap_seg, (size_t)(S.NB + 1) * (size_t)M.ncol);
+    sgl_trace_setup("  stream: segment buffer reserved");
+    DevCSC tmp = M;
+    tmp.tile_rows = D;
+    tmp.ntiles = S.NB;
+    tmp.seg = S.seg;
+    if (rc == SGL_OK) rc = k_build_segments(s, tmp);
+    int64_t* chunk_entries = nullptr;
+    if (rc == SGL_OK) rc = t_alloc(&chunk_entries, (size_t)nchunks);
+    if (rc == SGL_OK) rc = t_reserve(&S.cnt, &S.cap_cnt, (size_t)nchunks * TILED_NP);
+    if (rc == SGL_OK) rc = t_reserve(&S.ahead, &S.cap_ahead, (size_t)nchunks * (size_t)S.CW);
+    if (rc == SGL_OK) rc = t_reserve(&S.cstart, &S.cap_cstart, (size_t)nchunks + 1);
+    if (rc == SGL_OK && S.nwb > 0) {
+        tiled_count_kernel<<<dim3((unsigned)((S.nwb + 3) / 4)), dim3(256), 0, s>>>(S.seg, S.perm, M.ncol, S.T, S.NB, S.nwb, S.R,
+                                                                                   S.tail_wg0, S.tail_R, S.cnt, S.ahead, chunk_entries, nsl);
+        if (hipGetLastError() != hipSuccess) { sgl_set_error("tiled build: count kernel launch failed"); rc = SGL_EHIP; }
+    }
+    if (rc == SGL_OK) rc = k_exclusive_scan(c, chunk_entries, S.cstart, nchunks);
+    if (rc == SGL_OK) rc = k_scan_total(s, chunk_entries, S.cstart, nchunks);
+    int64_t E = 0;
+    if (rc == SGL_OK) {
+        if (hipMemcpyAsync(&E, S.cstart + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) { sgl_set_error("tiled build: reading the stream size failed"); rc = SGL_EHIP; }
+    }
+    S.E = E;
+    sgl_trace_setup("  stream: segments, counts, scan");
+    // + TILED_SLACK entries of slack: the kernel prefetches its ring (four or eight 64-entry sets) past the end
+    if (rc == SGL_OK) rc = t_reserve(&S.roff, &S.cap_roff, (size_t)E + TILED_SLACK);
+    if (rc == SGL_OK) rc = t_reserve(&S.x, &S.cap_x, (size_t)E + TILED_SLACK);
+    sgl_trace_setup("  stream: roff / x buffers reserved");
+    if (rc == SGL_OK) {
+        if (hipMemsetAsync(S.roff + E, 0, TILED_SLACK * sizeof(uint32_t), s) != hipSuccess ||
+            hipMemsetAsync(S.x + E, 0, TILED_SLACK * sizeof(double), s) != hipSuccess) { sgl_set_error("tiled build: clearing the stream slack failed"); rc = SGL_EHIP; }
+    }
+    if (rc == SGL_OK && nchunks > 0) {
+        int64_t blocks = (nchunks + 3) / 4;
+        if (blocks > 256 * 64) blocks = 256 * 64;
+        tiled_fill_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(M.x, M.i, S.seg, S.perm, M.ncol, S.T, S.NB, S.nwb, S.R, S.tail_wg0,
+                                                                       S.tail_R, D, KS * 8, S.cnt, S.ahead, S.cstart, S.roff, S.x,
+                                                                       0, 0, sgl_div_make(1), 0, 0, 0, nsl);
+        if (hipGetLastError() != hipSuccess) { sgl_set_error("tiled build: fill kernel launch failed"); rc = SGL_EHIP; }
+    }
+    // the chunk loop's schedule table: E / (4 nsl) groups + slack (a lap of 32 groups is loaded one ahead)
+    const size_t ngroups = (size_t)(E / (4 * nsl));
+    if (rc == SGL_OK) rc = t_reserve(&S.gtab, &S.cap_gtab, ngroups + 256);
+    if (rc == SGL_OK) {
+        if (hipMemsetAsync(S.gtab + ngroups, 0, 256 * sizeof(uint16_t), s) != hipSuccess) { sgl_set_error("tiled build: clearing the schedule slack failed"); rc = SGL_EHIP; }
+    }
+    if (rc == SGL_OK && nchunks > 0) {
+        int64_t blocks = (nchunks + 3) / 4;
+        if (blocks > 256 * 64) blocks = 256 * 64;
+        tiled_gtab_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(S.cnt, S.cstart, nchunks, nsl, S.gtab);
+        if (hipGetLastError() != hipSuccess) { sgl_set_error("tiled build: schedule kernel launch failed"); rc = SGL_EHIP; }
     }
     if (rc == SGL_OK && S.R > 1) rc = t_reserve(&S.part, &S.cap_part, (size_t)S.R * (size_t)k * (size_t)M.ncol);
     if (rc == SGL_OK && S.tail_R > 1)
@@ -469,20 +543,20 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
 // allocation per fit and orientation).
 int sgl_tiled_mask_values(sgl_ctx* c, const DevCSC& M, DevTiled& S, uint64_t seed, uint64_t inv_density, int mask_t,
                           int64_t col_off, int64_t row_off) {
-    if (!S.built || !S.seg) { sgl_set_error("masked values: no entry stream"); return SGL_ESTATE; }
+    if (!S.built || !S.seg || !S.ahead) { sgl_set_error("masked values: no entry stream"); return SGL_ESTATE; }
     if (S.xm && S.xm_seed == seed && S.xm_inv == inv_density && S.xm_mask_t == mask_t) return SGL_OK;
     hipStream_t s = c->stream;
     S.xm_mask_t = -1;
     SGLCHK(t_reserve(&S.xm, &S.cap_xm, (size_t)S.E + TILED_SLACK));
     HIPCHK(hipMemsetAsync(S.xm + S.E, 0, TILED_SLACK * sizeof(double), s));
-    const int64_t nchunks = S.nwb * S.T;
+    const int64_t nchunks = S.nwb * S.NB;
     if (nchunks > 0) {
         const int KS = S.KS;
         int64_t blocks = (nchunks + 3) / 4;
         if (blocks > 256 * 64) blocks = 256 * 64;
-        tiled_fill_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(M.x, M.i, S.seg, S.perm, M.ncol, S.T, S.nwb, S.TR, KS * 8, S.cnt,
-                                                                       S.cstart, nullptr, S.xm, 1, seed, sgl_div_make(inv_density),
-                                                                       mask_t, col_off, row_off, S.NSL);
+        tiled_fill_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(M.x, M.i, S.seg, S.perm, M.ncol, S.T, S.NB, S.nwb, S.R, S.tail_wg0,
+                                                                       S.tail_R, S.TR / 2, KS * 8, S.cnt, S.ahead, S.cstart, nullptr, S.xm,
+                                                                       1, seed, sgl_div_make(inv_density), mask_t, col_off, row_off, S.NSL);
         HIPCHK(hipGetLastError());
     }
     S.xm_seed = seed; S.xm_inv = inv_density; S.xm_mask_t = mask_t;
@@ -528,6 +602,106 @@ __device__ __forceinline__ void acc_load(int idx4, double& v0, double& v1) {
 
 #include "acc_tiled_gen.inc"
 
+// Stage `rows` rows of F (first row src, row stride ldf) into the LDS ring slot at `tile` (row stride KS doubles; 32 in the quad
+// layout).  sync: the workgroup barrier between the first round's loads and the writes -- every wave is done with what the
+// slot held before (the loads in front of it overlap the tail of the other waves' chunk).
+template <int NSL>
+__device__ __forceinline__ void tiled_stage(double* __restrict__ tile, const double* __restrict__ src, int rows, int k, int KS, int ldf,
+                                            bool sync) {
+    const int n = rows * k;
+    if constexpr (NSL == 4) {
+        // Quad layout: LDS rows of 32 doubles.  16 lanes per tile row (lane c moves the 16-byte piece c, or -- odd
+        // rank / unaligned rows -- the doubles c and c + 16), 32 rows per round of the workgroup: no divisions, every
+        // row's k * 8 contiguous bytes read by neighbouring lanes.  First round's loads before the barrier.
+        const int c16 = (int)threadIdx.x & 15, r0 = (int)threadIdx.x >> 4;
+        constexpr int RPR = 64 * TILED_NW / 16;   // rows per round
+        const bool vec = ((k | ldf) & 1) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+        if (vec) {
+            constexpr int RST = 4;
+            double2 stg[RST];
+            const bool cact = 2 * c16 < k;
+#pragma unroll
+            for (int j = 0; j < RST; ++j) {
+                const int r = r0 + j * RPR;
+                stg[j] = double2{0.0, 0.0};
+                if (cact && r < rows) stg[j] = *reinterpret_cast<const double2*>(src + (int64_t)r * ldf + 2 * c16);
+            }
+            if (sync) __syncthreads();  // everyone is done with what the slot held
+            for (int rb = 0; rb < rows; rb += RST * RPR) {
+#pragma unroll
+                for (int j = 0; j < RST; ++j) {
+                    const int r = rb + r0 + j * RPR;
+                    if (cact && r < rows) *reinterpret_cast<double2*>(tile + r * 32 + 2 * c16) = stg[j];
+                }
+                if (rb + RST * RPR < rows) {
+#pragma unroll
+                    for (int j = 0; j < RST; ++j) {
+                        const int r = rb + RST * RPR + r0 + j * RPR;
+                        stg[j] = double2{0.0, 0.0};
+                        if (cact && r < rows) stg[j] = *reinterpret_cast<const double2*>(src + (int64_t)r * ldf + 2 * c16);
+                    }
+                }
+            }
+        } else {
+            if (sync) __syncthreads();
+            for (int r = r0; r < rows; r += RPR) {
+                if (c16 < k) tile[r * 32 + c16] = src[(int64_t)r * ldf + c16];
+                if (c16 + 16 < k) tile[r * 32 + c16 + 16] = src[(int64_t)r * ldf + c16 + 16];
+            }
+        }
+    } else if (KS == k && ldf == k) {
+        // Each thread moves up to NRND * RST 16-byte pieces of the (contiguous) tile in NRND rounds of
+        // RST loads in flight.  The loads of the first round are issued before the barrier: they overlap
+        // the tail of the previous chunk's work of the other waves.
+        constexpr int RST = 8;
+        constexpr int NRND = (TILED_LDS_BYTES / 32 + RST * 64 * TILED_NW - 1) / (RST * 64 * TILED_NW);
+        static_assert(NRND * RST * 64 * TILED_NW * 16 >= TILED_LDS_BYTES / 2, "staging must cover a whole ring slot");
+        double2 stg[RST];
+#pragma unroll
+        for (int j = 0; j < RST; ++j) {
+            const int e = ((int)threadIdx.x + j * 64 * TILED_NW) * 2;
+            stg[j] = double2{0.0, 0.0};
+            if (e < n) stg[j] = *reinterpret_cast<const double2*>(src + e);
+        }
+        if (sync) __syncthreads();  // everyone is done with what the slot held
+#pragma unroll
+        for (int rd = 0; rd < NRND; ++rd) {
+#pragma unroll
+            for (int j = 0; j < RST; ++j) {
+                const int e = ((int)threadIdx.x + (rd * RST + j) * 64 * TILED_NW) * 2;
+                if (e < n) *reinterpret_cast<double2*>(tile + e) = stg[j];
+            }
+            if (rd + 1 < NRND) {
+#pragma unroll
+                for (int j = 0; j < RST; ++j) {
+                    const int e = ((int)threadIdx.x + ((rd + 1) * RST + j) * 64 * TILED_NW) * 2;
+                    stg[j] = double2{0.0, 0.0};
+                    if (e < n) stg[j] = *reinterpret_cast<const double2*>(src + e);
+                }
+            }
+        }
+    } else {
+        // odd k: rows are re-pitched to KS = k + 1 doubles (the pad column is never summed into a
+        // stored factor row: lane 2l+1 == k is not written out)
+        if (sync) __syncthreads();
+        // (also the path of a rank split into parts: rows of F are then ldf > k apart)
+        if (((k | ldf) & 1) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+            const int hp = k >> 1;  // 16-byte pieces per row
+            for (int e = (int)threadIdx.x; e < rows * hp; e += 64 * TILED_NW) {
+                const int r = e / hp, c2 = (e - r * hp) * 2;
+                *reinterpret_cast<double2*>(tile + r * KS + c2) = *reinterpret_cast<const double2*>(src + (int64_t)r * ldf + c2);
+            }
+        } else {
+            for (int e = (int)threadIdx.x; e < n; e += 64 * TILED_NW) {
+                const int r = e / k, f = e - r * k;
+                tile[r * KS + f] = src[(int64_t)r * ldf + f];
+            }
+        }
+        if (KS != k)
+            for (int r = (int)threadIdx.x; r < rows; r += 64 * TILED_NW) tile[r * KS + k] = 0.0;
+    }
+}
+
 // The chunk loop is the hand-scheduled inline asm of gen_acc_tiled.py (register plan there).  The compiler's budget
 // is v0..v63 (amdgpu_waves_per_eu(8, 8) caps its allocation at 512 / 8 registers); the clobber makes the kernel
 // descriptor allocate all 256: v64..v255 belong to the asm, whose stream ring stays in flight across compiler code.
@@ -537,7 +711,7 @@ __device__ __forceinline__ void acc_load(int idx4, double& v0, double& v1) {
 template <int MODE>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void acc_tiled_kernel(
     const uint32_t* __restrict__ sroff, const double* __restrict__ sx, const int64_t* __restrict__ cstart,
-    const uint8_t* __restrict__ cnt, int T, int64_t nwb, const double* __restrict__ F, int k, int TR, int64_t nrow,
+    const uint8_t* __restrict__ cnt, int T, int NB, int64_t nwb, const double* __restrict__ F, int k, int TR, int64_t nrow,
     int tiles_per_range, double* __restrict__ Bout, int64_t ncol, int KS, int ldf, int ldb, int64_t slab,
     const int32_t* __restrict__ perm, int range_fastest, const uint16_t* __restrict__ gtab, int tail_wg0, int tail_R,
     double* __restrict__ tail_part, int64_t tail_slab) {
@@ -575,6 +749,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // tile range `by` of nry: sizes floor / ceil of T / ranges (tiles_per_range = the ceil, kept for the layout query)
     const int t0 = (int)(((int64_t)by * T) / nry);
     const int t1 = (int)((((int64_t)by + 1) * T) / nry);
+    // its stages: row blocks [b0, b1) of D = TR / 2 rows; block j of F sits in LDS ring slot j & 1
+    const int D = TR >> 1;
+    const int b0 = 2 * t0, b1 = 2 * t1 < NB ? 2 * t1 : NB;
     const bool wact = wb < nwb;
     typedef __attribute__((address_space(3))) char lds_char;
     // LDS byte address of this lane's pair of factor rows inside a tile row (NSL = 4: 16 lanes cover a column)
@@ -598,9 +775,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     uint64_t qn0 = 0, qn1 = 0, qn2 = 0, qn3 = 0;
     int64_t pos_next = 0;
     if (wact) {
-        const int64_t pos = cstart[wb * T + t0];
-        pos_next = cstart[wb * T + t0 + 1];
-        const uint64_t* cq = reinterpret_cast<const uint64_t*>(cnt + (wb * T + t0) * TILED_NP);
+        const int64_t pos = cstart[wb * NB + b0];
+        pos_next = cstart[wb * NB + b0 + 1];
+        const uint64_t* cq = reinterpret_cast<const uint64_t*>(cnt + (wb * NB + b0) * TILED_NP);
         qn0 = cq[0]; qn1 = cq[1]; qn2 = cq[2]; qn3 = cq[3];
         const uint64_t r_ = reinterpret_cast<uint64_t>(sroff + pos), x_ = reinterpret_cast<uint64_t>(sx + pos);
         rp = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(r_ >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((unsigned)r_);
@@ -618,118 +795,33 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         for (int e = (int)threadIdx.x; e < TILED_LDS_BYTES / 8; e += 64 * TILED_NW) tile[e] = 0.0;
     }
 
-    int64_t pos_cur = wact ? cstart[wb * T + t0] : 0;
-    for (int t = t0; t < t1; ++t) {
+    int64_t pos_cur = wact ? cstart[wb * NB + b0] : 0;
+    for (int b = b0; b < b1; ++b) {
         const uint64_t q0 = qn0, q1 = qn1, q2 = qn2, q3 = qn3;
         const int nsets = (int)((pos_next - pos_cur) >> 6);  // 64-entry sets (32 per half) of this chunk
         const int64_t pos_chunk = pos_cur;                   // its first entry
         pos_cur = pos_next;
-        if (wact && t + 1 < t1) {
-            const uint64_t* cq = reinterpret_cast<const uint64_t*>(cnt + (wb * T + t + 1) * TILED_NP);
+        if (wact && b + 1 < b1) {
+            const uint64_t* cq = reinterpret_cast<const uint64_t*>(cnt + (wb * NB + b + 1) * TILED_NP);
             qn0 = cq[0]; qn1 = cq[1]; qn2 = cq[2]; qn3 = cq[3];
-            pos_next = cstart[wb * T + t + 2];
+            pos_next = cstart[wb * NB + b + 2];
         }
 
-        // stage rows [t*TR, ...) of F into LDS, row stride KS doubles
-        const int64_t row0 = (int64_t)t * TR;
-        const int rows = (int)((nrow - row0 < TR) ? (nrow - row0) : TR);
-        const int n = rows * k;
-        const double* __restrict__ src = F + row0 * ldf;
-        if constexpr (NSL == 4) {
-            // Quad layout: LDS rows of 32 doubles.  16 lanes per tile row (lane c moves the 16-byte piece c, or -- odd
-            // rank / unaligned rows -- the doubles c and c + 16), 32 rows per round of the workgroup: no divisions, every
-            // row's k * 8 contiguous bytes read by neighbouring lanes.  First round's loads before the barrier.
-            const int c16 = (int)threadIdx.x & 15, r0 = (int)threadIdx.x >> 4;
-            constexpr int RPR = 64 * TILED_NW / 16;   // rows per round
-            const bool vec = ((k | ldf) & 1) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-            if (vec) {
-                constexpr int RST = 4;
-                double2 stg[RST];
-                const bool cact = 2 * c16 < k;
-#pragma unroll
-                for (int j = 0; j < RST; ++j) {
-                    const int r = r0 + j * RPR;
-                    stg[j] = double2{0.0, 0.0};
-                    if (cact && r < rows) stg[j] = *reinterpret_cast<const double2*>(src + (int64_t)r * ldf + 2 * c16);
-                }
-                __syncthreads();  // everyone is done reading the previous tile
-                for (int rb = 0; rb < rows; rb += RST * RPR) {
-#pragma unroll
-                    for (int j = 0; j < RST; ++j) {
-                        const int r = rb + r0 + j * RPR;
-                        if (cact && r < rows) *reinterpret_cast<double2*>(tile + r * 32 + 2 * c16) = stg[j];
-                    }
-                    if (rb + RST * RPR < rows) {
-#pragma unroll
-                        for (int j = 0; j < RST; ++j) {
-                            const int r = rb + RST * RPR + r0 + j * RPR;
-                            stg[j] = double2{0.0, 0.0};
-                            if (cact && r < rows) stg[j] = *reinterpret_cast<const double2*>(src + (int64_t)r * ldf + 2 * c16);
-                        }
-                    }
-                }
-            } else {
-                __syncthreads();
-                for (int r = r0; r < rows; r += RPR) {
-                    if (c16 < k) tile[r * 32 + c16] = src[(int64_t)r * ldf + c16];
-                    if (c16 + 16 < k) tile[r * 32 + c16 + 16] = src[(int64_t)r * ldf + c16 + 16];
-                }
-            }
-        } else if (KS == k && ldf == k) {
-            // Each thread moves up to NRND * RST 16-byte pieces of the (contiguous) tile in NRND rounds of
-            // RST loads in flight.  The loads of the first round are issued before the barrier: they overlap
-            // the tail of the previous tile's work of the other waves.
-            constexpr int RST = 8;
-            constexpr int NRND = (TILED_LDS_BYTES / 16 + RST * 64 * TILED_NW - 1) / (RST * 64 * TILED_NW);
-            static_assert(NRND * RST * 64 * TILED_NW * 16 >= TILED_LDS_BYTES, "staging must cover the whole tile");
-            double2 stg[RST];
-#pragma unroll
-            for (int j = 0; j < RST; ++j) {
-                const int e = ((int)threadIdx.x + j * 64 * TILED_NW) * 2;
-                stg[j] = double2{0.0, 0.0};
-                if (e < n) stg[j] = *reinterpret_cast<const double2*>(src + e);
-            }
-            __syncthreads();  // everyone is done reading the previous tile
-#pragma unroll
-            for (int rd = 0; rd < NRND; ++rd) {
-#pragma unroll
-                for (int j = 0; j < RST; ++j) {
-                    const int e = ((int)threadIdx.x + (rd * RST + j) * 64 * TILED_NW) * 2;
-                    if (e < n) *reinterpret_cast<double2*>(tile + e) = stg[j];
-                }
-                if (rd + 1 < NRND) {
-#pragma unroll
-                    for (int j = 0; j < RST; ++j) {
-                        const int e = ((int)threadIdx.x + ((rd + 1) * RST + j) * 64 * TILED_NW) * 2;
-                        stg[j] = double2{0.0, 0.0};
-                        if (e < n) stg[j] = *reinterpret_cast<const double2*>(src + e);
-                    }
-                }
-            }
-        } else {
-            // odd k: rows are re-pitched to KS = k + 1 doubles (the pad column is never summed into a
-            // stored factor row: lane 2l+1 == k is not written out)
-            __syncthreads();
-            // (also the path of a rank split into parts: rows of F are then ldf > k apart)
-            if (((k | ldf) & 1) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-                const int hp = k >> 1;  // 16-byte pieces per row
-                for (int e = (int)threadIdx.x; e < rows * hp; e += 64 * TILED_NW) {
-                    const int r = e / hp, c2 = (e - r * hp) * 2;
-                    *reinterpret_cast<double2*>(tile + r * KS + c2) = *reinterpret_cast<const double2*>(src + (int64_t)r * ldf + c2);
-                }
-            } else {
-                for (int e = (int)threadIdx.x; e < n; e += 64 * TILED_NW) {
-                    const int r = e / k, f = e - r * k;
-                    tile[r * KS + f] = src[(int64_t)r * ldf + f];
-                }
-            }
-            if (KS != k)
-                for (int r = (int)threadIdx.x; r < rows; r += 64 * TILED_NW) tile[r * KS + k] = 0.0;
+        // stage b reads blocks b and b + 1: the range's first stage stages both, every later one block b + 1 into the slot
+        // block b - 1 held (the chunk of stage b - 1 was its last reader)
+        // (one call site: the staging's registers come out of the compiler's 64)
+#pragma clang loop unroll(disable)
+        for (int j = b == b0 ? b : b + 1; j <= b + 1 && j < b1; ++j) {
+            const int64_t row0 = (int64_t)j * D;
+            tiled_stage<NSL>(tile + (j & 1) * D * KS, F + row0 * ldf, (int)(nrow - row0 < D ? nrow - row0 : D), k, KS, ldf, j == b || b != b0);
         }
         // all staging loads (and the ring loads in front of them) have landed: the asm's counted vmcnt waits see
-        // only its own eight loads in flight
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-        __syncthreads();
+        // only its own eight loads in flight.  (The range's last stage stages nothing: its blocks landed behind the
+        // barrier of the stage before.)
+        if (b == b0 || b + 1 < b1) {
+            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+            __syncthreads();
+        }
         if (wact && nsets > 0) {
             if constexpr (MODE == 6 || MODE == 7) {
                 // first schedule word of this chunk (wave-uniform address)
@@ -855,7 +947,7 @@ int k_acc_tiled(hipStream_t s, const DevTiled& S, const double* F, int ldf, doub
     auto launch = [&](auto mode) {
         constexpr int MODE = decltype(mode)::value;
         acc_tiled_kernel<MODE><<<grid, dim3(64 * TILED_NW), lds, s>>>(
-            S.roff, xvals ? xvals : S.x, S.cstart, S.cnt, S.T, S.nwb, F, kf, S.TR, S.nrow, S.tiles_per_range, out, S.ncol, KS, ldf,
+            S.roff, xvals ? xvals : S.x, S.cstart, S.cnt, S.T, S.NB, S.nwb, F, kf, S.TR, S.nrow, S.tiles_per_range, out, S.ncol, KS, ldf,
             slabs ? kf : ldb, slabs ? n : 0, S.perm, S.range_fastest ? 1 : 0, S.gtab, tail ? (int)S.tail_wg0 : -1, tail ? S.tail_R : 1,
             S.part, tail_slab);
     };

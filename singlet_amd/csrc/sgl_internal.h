@@ -58,15 +58,16 @@ struct DevCSC {
 struct DevTiled {
     uint32_t* roff = nullptr;   // byte offset of the row inside the LDS tile, per entry
     double* x = nullptr;        // value per entry (0 for pads)
-    int64_t* cstart = nullptr;  // [nwb * T + 1] first entry of chunk (wb, t)
-    uint8_t* cnt = nullptr;     // [nwb * T * CW] 4-entry groups of slot s in chunk (wb, t)
+    int64_t* cstart = nullptr;  // [nwb * NB + 1] first entry of chunk (wb, b): wave block wb, stage = row block b
+    uint8_t* cnt = nullptr;     // [nwb * NB * 32] 4-entry groups of column unit p in chunk (wb, b)
+    uint16_t* ahead = nullptr;  // [nwb * NB * CW] entries of block b a column slot already took in stage b - 1 (run-ahead)
     uint16_t* gtab = nullptr;   // [E / (4 NSL) + slack] schedule: the M0 word (0x8000 | 4 * column unit) of every group of 4 entry tuples
     size_t cap_gtab = 0;
     double* part = nullptr;     // [R][k * ncol] partial slabs when the tile range is split
     double* xm = nullptr;       // value per entry with the cross-validation mask applied (0 at drawn entries), per fit
     uint64_t xm_seed = 0, xm_inv = 0;
     int xm_mask_t = -1;
-    int64_t* seg = nullptr;     // [(T + 1) * ncol] first non-zero of column c at or below row t * TR (kept for the masked values)
+    int64_t* seg = nullptr;     // [(NB + 1) * ncol] first non-zero of column c at or below row b * TR / 2 (kept for the masked values)
     int32_t* perm = nullptr;    // [ncol] column at position pos of the descending-non-zero-count order (nullptr: matrix order)
     size_t cap_perm = 0;
     int64_t perm_nnz = -1;      // the matrix (by its non-zero count) perm was computed for
@@ -76,11 +77,12 @@ struct DevTiled {
     // The buffers outlive a fit: a rank sweep re-inits the fit tens of times on one matrix, and hipMalloc / hipFree of
     // tens of GB cost up to seconds each at config-5 size.  cap_* = allocated element counts; `built` = the stream
     // content is valid for (k, src_nnz); any change of the matrix frees everything (sgl_tiled_free).
-    size_t cap_roff = 0, cap_x = 0, cap_cstart = 0, cap_cnt = 0, cap_part = 0, cap_xm = 0, cap_seg = 0;
+    size_t cap_roff = 0, cap_x = 0, cap_cstart = 0, cap_cnt = 0, cap_part = 0, cap_xm = 0, cap_seg = 0, cap_ahead = 0;
     bool built = false;
     int64_t builds = 0;         // times the stream content was (re)written on this context (sgl_layout_builds)
     int64_t src_nnz = -1;
     int32_t TR = 0, T = 0, CW = 0, k = 0, R = 1, tiles_per_range = 0;
+    int32_t NB = 0;             // row blocks of TR / 2 rows (the LDS tile is a ring of two): stages of the chunk loop
     int64_t tail_wg0 = -1;      // tail split (R == 1): first workgroup (x) of the last, partly filled round of 256 (-1: none)
     int32_t tail_R = 1;         //   its workgroups' tile ranges are cut into this many pieces (own slabs, summed in order)
     int32_t NSL = 2;            // column slots per LDS instruction: 2 (pairs, k <= 64) or 4 (quads, k <= 32); CW = 32 * NSL
