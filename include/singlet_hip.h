@@ -480,6 +480,10 @@ SGL_API int sgl_op_rhs(sgl_ctx* ctx, int which, const double* F, int32_t k, doub
  * B k x ncols (destroyed on the device, not written back), X k x ncols in/out. */
 SGL_API int sgl_op_nnls(sgl_ctx* ctx, const double* G, const double* B, double* X, int32_t k, int64_t ncols,
                 double L1, double L2, int32_t* sweeps_out);
+/* Rebuild the resident t(A) from A on the device, sorting at most max_batch_entries non-zeros at a time (0: the default,
+ * 2^31 - 1; a column with more entries than the cap is a batch of its own).  Any cap gives the same t(A); a small one
+ * sends a small matrix through many batches, as a matrix past 2^31 non-zeros goes.  A running fit is dropped. */
+SGL_API int sgl_op_transpose(sgl_ctx* ctx, int64_t max_batch_entries);
 /* scale (src/singlet.cpp:219-225) and cor (:184-197). */
 SGL_API int sgl_op_scale(sgl_ctx* ctx, double* F, int32_t k, int64_t cols, double* d);
 SGL_API int sgl_op_cor(sgl_ctx* ctx, const double* x, const double* y, int64_t n, double* out);

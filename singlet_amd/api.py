@@ -26,7 +26,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from .context import make_callbacks
+from .context import _chunk_list, make_callbacks
 from .sparse import as_dgCMatrix, dgCMatrix
 
 
@@ -105,17 +105,6 @@ def c_nmf_dense(A, At, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w):
                             int(threads), ptr(wb, f64p), k, ptr(w_out, f64p), ptr(d_out, f64p), ptr(h_out, f64p),
                             C.byref(n_iter), ptr(tr, f64p), C.byref(cb)))
     return {"w": w_out.T, "d": d_out, "h": h_out.T, "iter": n_iter.value, "tol": tr[:n_iter.value].copy()}
-
-
-def _chunk_list(chunks):
-    """ctypes image of a list of dgCMatrix column chunks: (n, x**, i**, p**, ncol*) and what must stay alive"""
-    chunks = [as_dgCMatrix(a) for a in chunks]
-    n = len(chunks)
-    xs = (f64p * n)(*[ptr(a.x, f64p) for a in chunks])
-    is_ = (i32p * n)(*[ptr(a.i, i32p) for a in chunks])
-    ps = (i32p * n)(*[ptr(a.p, i32p) for a in chunks])
-    nc = np.array([a.ncol for a in chunks], dtype=np.int32)
-    return (n, xs, is_, ps, ptr(nc, i32p)), (chunks, xs, is_, ps, nc)
 
 
 def _list_args(A_, At_):

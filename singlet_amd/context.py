@@ -6,6 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
+from .sparse import as_dgCMatrix
 
 SYNTH_SEED = 0x5EED
 # 16 value levels of the synthetic generator: log1p(1 + level)
@@ -74,6 +75,18 @@ def split_cells_by_nnz(p, n):
     return lo
 
 
+def _chunk_list(chunks):
+    """ctypes image of a list of dgCMatrix column chunks: (n, x**, i**, p**, ncol*) and what must stay alive.  A chunk
+    that already is a dgCMatrix is not copied: a chunk listed twice passes the same host pointers twice."""
+    chunks = [as_dgCMatrix(a) for a in chunks]
+    n = len(chunks)
+    xs = (f64p * n)(*[ptr(a.x, f64p) for a in chunks])
+    is_ = (i32p * n)(*[ptr(a.i, i32p) for a in chunks])
+    ps = (i32p * n)(*[ptr(a.p, i32p) for a in chunks])
+    nc = np.array([a.ncol for a in chunks], dtype=np.int32)
+    return (n, xs, is_, ps, ptr(nc, i32p)), (chunks, xs, is_, ps, nc)
+
+
 class Context:
     def __init__(self, device=0, _borrowed=None):
         self._L = _lib.load()
@@ -138,6 +151,23 @@ class Context:
         else:
             t = (None, None, None)
         check(self._L.sgl_upload_csc(self._h, *a, *t, A.nrow, A.ncol, int(cell_offset), int(ncells_total)))
+        self.k = 0
+
+    def upload_list(self, chunks, t_chunks=None, cell_offset=0, ncells_total=0):
+        """sgl_upload_csc_list: a list of column chunks of A joined into one resident shard (64-bit column pointers);
+        t_chunks: the column chunks of t(A), or None / empty to build the transpose on the device."""
+        chunks = list(chunks)
+        if not chunks:
+            raise ValueError("the chunk list must hold at least one matrix")
+        a, keep_a = _chunk_list(chunks)
+        nrow = keep_a[0][0].nrow
+        if any(q.nrow != nrow for q in keep_a[0]):
+            raise ValueError("all chunks must have the same number of rows")
+        if t_chunks is not None and len(t_chunks) > 0:
+            t, keep_t = _chunk_list(t_chunks)
+        else:
+            t, keep_t = (0, None, None, None, None), None
+        check(self._L.sgl_upload_csc_list(self._h, *a, *t, nrow, int(cell_offset), int(ncells_total)))
         self.k = 0
 
     def upload_dense(self, A):
@@ -351,6 +381,12 @@ class Context:
         check(self._L.sgl_op_mask_gram(self._h, ptr(F, f64p), Gp, k, nrow, ncols, int(seed), int(inv_density), int(mask_t),
                                        int(col_offset), int(row_offset), 1 if use_lists else 0, ptr(out, f64p)))
         return out
+
+    def op_transpose(self, max_batch_entries=0):
+        """Rebuild the resident t(A) from A on the device, at most max_batch_entries non-zeros per sort (0: the
+        default).  Drops a running fit."""
+        check(self._L.sgl_op_transpose(self._h, int(max_batch_entries)))
+        self.k = 0
 
     def op_scale(self, F):
         F = np.array(F, dtype=np.float64, order="C")

@@ -430,7 +430,7 @@ static int finish_matrix(sgl_ctx* c) {
     return SGL_OK;
 }
 
-int sgl_device_transpose(sgl_ctx* c);  // kernels_transpose.hip
+int sgl_device_transpose(sgl_ctx* c, int64_t max_batch_entries = 0);  // kernels_transpose.hip
 
 extern "C" int sgl_upload_csc(sgl_ctx* c, const double* Ax, const int32_t* Ai, const int32_t* Ap, const double* Atx,
                               const int32_t* Ati, const int32_t* Atp, int32_t nrow, int32_t ncol, int64_t cell_offset,
@@ -1841,6 +1841,20 @@ extern "C" int sgl_op_nnls(sgl_ctx* c, const double* G, const double* B, double*
     nnls_scratch_free(scr);
     if (sweeps_out) *sweeps_out = (int32_t)sw;
     return rc;
+}
+
+extern "C" int sgl_op_transpose(sgl_ctx* c, int64_t max_batch_entries) {
+    CTX_GUARD(c);
+    if (!c->A.p || !c->col_nnz_A) { sgl_set_error("sgl_op_transpose: no resident matrix"); return SGL_EINVAL; }
+    free_fit(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    free_csc(c->At);
+    dev_free(c->col_nnz_At);
+    SGLCHK(sgl_device_transpose(c, max_batch_entries));
+    SGLCHK(dev_alloc(&c->col_nnz_At, (size_t)c->At.ncol));
+    SGLCHK(k_col_counts(c->stream, c->At.p, c->At.ncol, c->col_nnz_At));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return SGL_OK;
 }
 
 extern "C" int sgl_op_scale(sgl_ctx* c, double* F, int32_t k, int64_t cols, double* d) {

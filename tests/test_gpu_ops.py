@@ -585,6 +585,112 @@ def test_device_transpose(ctx, ora, sa):
     assert np.array_equal(p, At.p.astype(np.int64)) and np.array_equal(i, At.i) and np.array_equal(x, At.x)
 
 
+def _drop_columns(A, cols, ora):
+    """A with the columns `cols` emptied (their entries removed, the shape kept)."""
+    cnt = np.diff(A.p).astype(np.int64)
+    keep = ~np.isin(np.repeat(np.arange(A.ncol), cnt), cols)
+    cnt[cols] = 0
+    return ora.CSC(A.x[keep], A.i[keep], np.concatenate([[0], np.cumsum(cnt)]), A.nrow, A.ncol)
+
+
+def _one_heavy_column(ora):
+    """500 x 60 with column 17 holding 480 of its rows and the others about 5 each: most entries in one column."""
+    rng = np.random.default_rng(11)
+    D = np.where(rng.random((500, 60)) < 0.01, rng.random((500, 60)) + 0.5, 0.0)
+    D[:, 17] = 0.0
+    D[rng.choice(500, 480, replace=False), 17] = rng.random(480) + 0.5
+    cols = [np.nonzero(D[:, c])[0] for c in range(60)]
+    p = np.concatenate([[0], np.cumsum([r.size for r in cols])])
+    return ora.CSC(np.concatenate([D[r, c] for c, r in enumerate(cols)]), np.concatenate(cols), p, 500, 60)
+
+
+def _batch_caps(A):
+    cmax, nnz = int(np.diff(A.p).max()), A.nnz
+    return [1, 7, 64, cmax - 1, cmax, cmax + 1, nnz - 1, nnz]
+
+
+def _assert_transpose_for_caps(ctx, A):
+    At = A.t()
+    for cap in _batch_caps(A):
+        ctx.op_transpose(cap)
+        x, i, p = ctx.download(1)
+        assert np.array_equal(p, At.p.astype(np.int64)), cap
+        assert np.array_equal(i, At.i), cap
+        assert np.array_equal(x.view(np.uint64), At.x.view(np.uint64)), cap
+        assert np.array_equal(ctx.col_counts(1), np.diff(At.p)), cap
+    ctx.op_transpose(0)                                              # the default: one batch at these sizes
+    x, i, p = ctx.download(1)
+    assert np.array_equal(p, At.p.astype(np.int64)) and np.array_equal(i, At.i) and np.array_equal(x, At.x)
+
+
+def test_device_transpose_batched(ctx, ora, sa):
+    """sgl_op_transpose: t(A) built in column batches of at most `cap` non-zeros (the path of a matrix past 2^31
+    non-zeros) equals t(A) of the oracle byte for byte, from one entry per batch up to one batch."""
+    A = ora.synth_csc(123, 321, 7)
+    ctx.upload(to_dgc(sa, A), None)
+    _assert_transpose_for_caps(ctx, A)
+
+
+def test_device_transpose_batched_empty_columns(ctx, ora, sa):
+    """Leading, trailing and runs of empty columns: batches that hold no entry, and rows that skip batches."""
+    A = _drop_columns(ora.synth_csc(97, 300, 5), np.r_[0:5, 40:41, 100:131, 200:202, 290:300], ora)
+    assert np.all(np.diff(A.p)[:5] == 0) and np.all(np.diff(A.p)[-10:] == 0)
+    ctx.upload(to_dgc(sa, A), None)
+    _assert_transpose_for_caps(ctx, A)
+
+
+def test_device_transpose_batched_one_heavy_column(ctx, ora, sa):
+    """One column holds most of the entries: a batch never splits a column, a column above the cap is a batch of its own."""
+    A = _one_heavy_column(ora)
+    assert np.diff(A.p)[17] == 480 and 2 * 480 > A.nnz
+    ctx.upload(to_dgc(sa, A), None)
+    _assert_transpose_for_caps(ctx, A)
+
+
+def test_device_transpose_batched_chunk_list(ctx, ora, sa):
+    """A list upload (sgl_upload_csc_list, n_t_chunks = 0): the transpose built on the device from the joined chunks,
+    by the upload itself and in batches; one chunk listed twice is joined twice."""
+    A = ora.synth_csc(150, 400, 9)
+    edges = [0, 1, 130, 131, 400]
+    chunks = [to_dgc(sa, ora.CSC(A.x[A.p[a]:A.p[b]], A.i[A.p[a]:A.p[b]], A.p[a:b + 1] - A.p[a], A.nrow, b - a))
+              for a, b in zip(edges[:-1], edges[1:])]
+    ctx.upload_list(chunks)
+    assert ctx.dims() == (A.nrow, A.ncol, A.nnz)
+    x, i, p = ctx.download(0)
+    assert np.array_equal(p, A.p.astype(np.int64)) and np.array_equal(i, A.i) and np.array_equal(x, A.x)
+    At = A.t()
+    x, i, p = ctx.download(1)
+    assert np.array_equal(p, At.p.astype(np.int64)) and np.array_equal(i, At.i) and np.array_equal(x, At.x)
+    _assert_transpose_for_caps(ctx, A)
+    C = chunks[1]
+    ctx.upload_list([C, C, C])
+    AA = ora.CSC(np.tile(C.x, 3), np.tile(C.i, 3), np.concatenate([C.p[:-1] + q * C.nnz for q in range(3)] + [[3 * C.nnz]]),
+                 C.nrow, 3 * C.ncol)
+    _assert_transpose_for_caps(ctx, AA)
+
+
+def test_fit_step_on_batched_transpose_is_bit_identical(ctx, ora, sa):
+    """One ALS iteration (H and W updates, both scales) on a t(A) built in batches equals the one on the default t(A)
+    bit for bit: the W-update reads t(A)."""
+    A = ora.synth_csc(260, 300, 20)
+    w0 = ora.synth_winit(10, 260)
+    ctx.upload(to_dgc(sa, A), None)
+    out = []
+    for cap in (0, 7, 64):
+        ctx.op_transpose(cap)
+        ctx.fit_init(10, w0)
+        ctx.step_begin()
+        ctx.step_h(0.01, 0.0)
+        ctx.step_scale_h()
+        ctx.step_w(0.01, 0.0)
+        tol = ctx.step_scale_w()
+        out.append((tol,) + tuple(ctx.get_factors()))
+    for got in out[1:]:
+        assert got[0] == out[0][0]
+        for a, b in zip(got[1:], out[0][1:]):
+            assert np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
 def test_log_normalize_and_weight_by_split(sa, ora):
     """Device staging operators against the oracle, on A and on the resident transpose; the float
     tolerance (1e-14 relative) covers the device log1p and the tree-order column sums."""

@@ -209,3 +209,18 @@ def test_r_drivers_pick_the_list_and_dense_entry_points(sa, monkeypatch):
         assert [n for n, _ in seen] == ["c_ard_nmf" + tag] * 4 and len(df) == 8
     with pytest.raises(ValueError):   # "number of rows in all provided 'A' matrices are not identical"
         api.ard_nmf([one, sa.dgCMatrix.from_dense(np.eye(5))], verbose=0)
+
+
+def test_chunk_list_passes_a_repeated_chunk_without_copies(sa):
+    """A chunk listed R times reaches sgl_upload_csc_list / sgl_c_nmf_sparse_list as the same host slots R times (no
+    copy per entry: a list of one large chunk repeated stays at one chunk of host memory)."""
+    import ctypes
+    from singlet_amd.context import _chunk_list
+    C = sa.dgCMatrix([1.0, 2.0, 3.0], [0, 2, 1], [0, 2, 3], (3, 2))
+    assert sa.as_dgCMatrix(C) is C
+    same = sa.dgCMatrix(C.x, C.i, C.p, C.Dim)                        # slots of the right type are taken as they are
+    assert same.x is C.x and same.i is C.i and same.p is C.p
+    (n, xs, is_, ps, _), keep = _chunk_list(4 * [C])
+    assert n == 4 and all(c is C for c in keep[0])
+    for arr, slot in ((xs, C.x), (is_, C.i), (ps, C.p)):
+        assert {ctypes.cast(arr[q], ctypes.c_void_p).value for q in range(4)} == {slot.ctypes.data}
