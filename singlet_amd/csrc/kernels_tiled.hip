@@ -403,16 +403,16 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
             const double eff = wgs / (ceil(wgs / 256.0) * 256.0);
             if (eff > best + 1e-9) { best = eff; R = reff; }
         }
-    } else if (r_fill > 1 && S.T > 1 && !getenv("SGL_TILED_OLD_SPLIT")) {
+    } else if (r_fill > 1 && S.T > 1) {
         // (matrices of every size: for most of round 4 the range stayed whole below 4 M entries -- "a pass takes microseconds
         // either way" -- and pbmc3k, 2.3 M non-zeros in 3 column groups of the quad layout, ran its 22 tiles on THREE CUs:
         // 0.83 / 1.07 ms per pass where config 2, with 22 times the non-zeros, takes 0.21.  A split adds the ranges' partial
         // sums: equal to the whole range up to rounding, and SGL_TILED_RANGES=1 keeps the reference's order for the tests that
         // compare bits.)
-        // Too few column groups to fill the chip: cut the tile range into R pieces (sizes floor / ceil of T / R).  Round 4:
-        // R by a cost model instead of "the count of workgroups nearest a multiple of 256" -- that rule took R = T at
+        // Too few column groups to fill the chip: cut the tile range into R pieces (sizes floor / ceil of T / R), R by a
+        // cost model.  (Taking the count of workgroups nearest a multiple of 256 instead gave R = T at
         // BASELINE config 2 in the quad layout (49 column groups x 32 tiles: 1568 workgroups of ONE tile each, every
-        // one clearing and staging 160 KB and writing a 245 KB slab: 0.41 ms per pass; 5 ranges: see profiles/).
+        // one clearing and staging 160 KB and writing a 245 KB slab: 0.41 ms per pass; 5 ranges: see profiles/.)
         //   time(R) = rounds x (largest unit x t_tile + t_wg) + t_reduce(R),   rounds = ceil(groups x R / 256 CUs)
         // t_tile = one workgroup's entry tuples of one tile at the measured 2.4 ns per tuple per CU + 2.5 us of staging,
         // t_wg = 6 us per workgroup (launch, zeroing, output), t_reduce = the slabs written and read back at 4 TB/s.
@@ -425,15 +425,6 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
             const int largest = (S.T + r - 1) / r;
             const double cost = rounds * ((double)largest * t_tile + t_wg) + (r > 1 ? (double)r * (double)k * (double)M.ncol * 16.0 / 4e12 : 0.0);
             if (cost < best * (1.0 - 1e-9)) { best = cost; R = r; }
-        }
-    } else if (r_fill > 1 && getenv("SGL_TILED_OLD_SPLIT")) {   // rounds 1 - 3: the workgroup count nearest a multiple of 256 (A/B)
-        double best = -1.0;
-        for (int r = r_fill; r <= std::min<int64_t>(S.T, 4 * r_fill); ++r) {
-            const int tpr = (S.T + r - 1) / r;
-            const int reff = (S.T + tpr - 1) / tpr;
-            const double wgs = (double)nwg_x * reff;
-            const double eff = wgs / (ceil(wgs / 256.0) * 256.0);
-            if (eff > best + 1e-9) { best = eff; R = reff; }
         }
     }
     if (const char* fr = getenv("SGL_TILED_RANGES")) {   // tests: force the slab path (or the whole range) on small matrices
@@ -575,9 +566,9 @@ int sgl_tiled_mask_values(sgl_ctx* c, const DevCSC& M, DevTiled& S, uint64_t see
 //     ds_read_b128   w, addr                                   (F[2l, 2l+1 ; row])
 //     v_fmac_f64_dpp acc0, x, w.x              row_newbcast:j   (acc += x_j * w)
 //     v_fmac_f64_dpp acc1, x, w.y              row_newbcast:j
-// A 64-entry set (one coalesced load per array) becomes two such 16-pair
-// batches with ONE v_permlane16_swap per dword: rows [A0 A1 B0 B1] ->
-// [A0 A0 B0 B0] and [A1 A1 B1 B1].
+// The stream ring loads each half of a 64-entry set straight into that
+// layout: lanes 0-15 and 16-31 read the same 16 entries of the A half, lanes
+// 32-47 and 48-63 the same 16 of the B half (two 16-pair batches per set).
 //
 // Register plan.  The 32 pairs x 2 FP64 accumulators of a wave live in v[128:255], OUTSIDE the compiler's register
 // allocation, and are updated IN PLACE: VGPR index mode is on inside the chunk loop and M0 (destination-relative,
@@ -586,8 +577,8 @@ int sgl_tiled_mask_values(sgl_ctx* c, const DevCSC& M, DevTiled& S, uint64_t see
 // 32-register vectors around every slot change.  (Rounds 1 - 2 ran the loop as compiler-scheduled C++ with the
 // running pair swapped in and out of fixed registers: same arithmetic, 6 % slower; see DESIGN.md.)
 //
-// Four stream sets are in flight per wave (3 KiB), refilled right after a set is prepared and waited with a
-// counted vmcnt (loads return in order); which ring slot is next is the wave-uniform `phase`.
+// Eight ring slots of the stream are in flight per wave, each refilled once its last operand has been read and waited
+// with a counted vmcnt (loads return in order); which ring slot is next is the wave-uniform `phase`.
 
 // accumulators of pair p -> (v0, v1), for the output stage
 __device__ __forceinline__ void acc_load(int idx4, double& v0, double& v1) {
@@ -705,10 +696,9 @@ __device__ __forceinline__ void tiled_stage(double* __restrict__ tile, const dou
 // The chunk loop is the hand-scheduled inline asm of gen_acc_tiled.py (register plan there).  The compiler's budget
 // is v0..v63 (amdgpu_waves_per_eu(8, 8) caps its allocation at 512 / 8 registers); the clobber makes the kernel
 // descriptor allocate all 256: v64..v255 belong to the asm, whose stream ring stays in flight across compiler code.
-// MODE 6 / 7: MODE 3 / 4 with the schedule table instead of the countdown + byte queue (round 4, the default);
-// MODE 2: pairs of columns, sets prepared (rounds 2 - 3; SGL_TILED_PREP=1);  MODE 3: pairs of columns on half-set ring
-// slots loaded with doubled lane rows, no preparation (round 4, the default for ranks 33 - 64);  MODE 4: quads of columns
-template <int MODE>
+// NSL = 2: pairs of columns on half-set ring slots loaded with doubled lane rows (parts of 33 - 64 factors);  NSL = 4: quads
+// of columns (parts up to 32).  Both walk the schedule table gtab.
+template <int NSL>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void acc_tiled_kernel(
     const uint32_t* __restrict__ sroff, const double* __restrict__ sx, const int64_t* __restrict__ cstart,
     const uint8_t* __restrict__ cnt, int T, int NB, int64_t nwb, const double* __restrict__ F, int k, int TR, int64_t nrow,
@@ -717,9 +707,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     double* __restrict__ tail_part, int64_t tail_slab) {
     // k = factor rows handled by this launch (a part of the rank when it is above 64), KS = LDS row
     // stride the stream's offsets were built for, ldf / ldb = strides (doubles) between rows of F /
-    // columns of the output, slab = doubles between the outputs of two tile ranges (blockIdx.y)
-    constexpr int NSL = (MODE == 4 || MODE == 7) ? 4 : 2;
-    constexpr bool PAIRRING = MODE == 3 || MODE == 6;
+    // columns of the output, slab = doubles between the outputs of two tile ranges (blockIdx.y).
+    // cnt is unused (gtab carries the schedule); it stays because dropping it reorders the pair instance's scalar code.
     asm volatile("" ::: "v255");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* tile = reinterpret_cast<double*>(smem);
@@ -757,9 +746,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // LDS byte address of this lane's pair of factor rows inside a tile row (NSL = 4: 16 lanes cover a column)
     constexpr int LMASK = NSL == 4 ? 15 : 31;
     const unsigned lane16 = (unsigned)(uintptr_t)(lds_char*)smem + (lane & LMASK) * 16;
-    // stream slot this lane loads of a (half) set.  MODE 3: lane rows doubled -- lanes 0-15 and 16-31 the A half's 16
+    // stream slot this lane loads of a (half) set.  NSL = 2: lane rows doubled -- lanes 0-15 and 16-31 the A half's 16
     // entries, lanes 32-47 and 48-63 the B half's (slots 32 ..): the [A A B B] layout the row broadcasts read
-    const unsigned slot = PAIRRING ? (unsigned)((lane >> 5) * 32 + (lane & 15)) : (unsigned)lane;
+    const unsigned slot = NSL == 2 ? (unsigned)((lane >> 5) * 32 + (lane & 15)) : (unsigned)lane;
     const unsigned voff4 = slot * 4, voff8 = slot * 8;
     // L2 prefetch of the stream (gen_acc_tiled.py, GenTab.wrap): lane offset into the row-offset stream that spreads the 64
     // lanes over one lap of it (8 ring slots: 1 KB in the pair layout, 2 KB in the quad layout), ACC_TILED_PF_LAPS laps ahead
@@ -770,24 +759,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 
     uint64_t rp = 0, xp = 0;   // next 64-entry set to LOAD (row offsets / values)
     int phase = 0;
-    // group counts of the next chunk (32 bytes = one per column pair) and its size, read on the scalar side one
-    // tile ahead: wb is wave-uniform
-    uint64_t qn0 = 0, qn1 = 0, qn2 = 0, qn3 = 0;
+    // start of the next chunk, read on the scalar side one stage ahead: wb is wave-uniform
     int64_t pos_next = 0;
     if (wact) {
         const int64_t pos = cstart[wb * NB + b0];
         pos_next = cstart[wb * NB + b0 + 1];
-        const uint64_t* cq = reinterpret_cast<const uint64_t*>(cnt + (wb * NB + b0) * TILED_NP);
-        qn0 = cq[0]; qn1 = cq[1]; qn2 = cq[2]; qn3 = cq[3];
         const uint64_t r_ = reinterpret_cast<uint64_t>(sroff + pos), x_ = reinterpret_cast<uint64_t>(sx + pos);
         rp = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(r_ >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((unsigned)r_);
         xp = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(x_ >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((unsigned)x_);
         if constexpr (NSL == 4)
             asm volatile(ACC_TILED4_RING_FILL_ASM : [rp] "+s"(rp), [xp] "+s"(xp) : [voff4] "v"(voff4), [voff8] "v"(voff8) : ACC_TILED_CLOBBERS);
-        else if constexpr (PAIRRING)
-            asm volatile(ACC_TILED2R_RING_FILL_ASM : [rp] "+s"(rp), [xp] "+s"(xp) : [voff4] "v"(voff4), [voff8] "v"(voff8) : ACC_TILED_CLOBBERS);
         else
-            asm volatile(ACC_TILED_RING_FILL_ASM : [rp] "+s"(rp), [xp] "+s"(xp) : [voff4] "v"(voff4), [voff8] "v"(voff8) : ACC_TILED_CLOBBERS);
+            asm volatile(ACC_TILED2_RING_FILL_ASM : [rp] "+s"(rp), [xp] "+s"(xp) : [voff4] "v"(voff4), [voff8] "v"(voff8) : ACC_TILED_CLOBBERS);
     }
     if constexpr (NSL == 4) {
         // the tile rows are 256 B apart whatever the rank: bytes k * 8 .. 255 of a row are never staged; clear them
@@ -797,15 +780,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 
     int64_t pos_cur = wact ? cstart[wb * NB + b0] : 0;
     for (int b = b0; b < b1; ++b) {
-        const uint64_t q0 = qn0, q1 = qn1, q2 = qn2, q3 = qn3;
         const int nsets = (int)((pos_next - pos_cur) >> 6);  // 64-entry sets (32 per half) of this chunk
         const int64_t pos_chunk = pos_cur;                   // its first entry
         pos_cur = pos_next;
-        if (wact && b + 1 < b1) {
-            const uint64_t* cq = reinterpret_cast<const uint64_t*>(cnt + (wb * NB + b + 1) * TILED_NP);
-            qn0 = cq[0]; qn1 = cq[1]; qn2 = cq[2]; qn3 = cq[3];
-            pos_next = cstart[wb * NB + b + 2];
-        }
+        if (wact && b + 1 < b1) pos_next = cstart[wb * NB + b + 2];
 
         // stage b reads blocks b and b + 1: the range's first stage stages both, every later one block b + 1 into the slot
         // block b - 1 held (the chunk of stage b - 1 was its last reader)
@@ -816,49 +794,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             tiled_stage<NSL>(tile + (j & 1) * D * KS, F + row0 * ldf, (int)(nrow - row0 < D ? nrow - row0 : D), k, KS, ldf, j == b || b != b0);
         }
         // all staging loads (and the ring loads in front of them) have landed: the asm's counted vmcnt waits see
-        // only its own eight loads in flight.  (The range's last stage stages nothing: its blocks landed behind the
+        // only its own ring loads in flight.  (The range's last stage stages nothing: its blocks landed behind the
         // barrier of the stage before.)
         if (b == b0 || b + 1 < b1) {
             __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
             __syncthreads();
         }
         if (wact && nsets > 0) {
-            if constexpr (MODE == 6 || MODE == 7) {
-                // first schedule word of this chunk (wave-uniform address)
-                const uint64_t t_ = reinterpret_cast<uint64_t>(gtab + pos_chunk / (4 * NSL));
-                const uint64_t tp = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(t_ >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((unsigned)t_);
-                if constexpr (MODE == 6)
-                    asm volatile(ACC_TILED2T_CHUNK_ASM
-                                 : [rp] "+s"(rp), [xp] "+s"(xp), [phase] "+s"(phase)
-                                 : [ns] "s"(2 * nsets), [tp] "s"(tp), [lane16] "v"(lane16), [voff4] "v"(voff4), [voff8] "v"(voff8), [pfl] "v"(pfl)
-                                 : ACC_TILEDT_CLOBBERS);
-                else
-                    asm volatile(ACC_TILED4T_CHUNK_ASM
-                                 : [rp] "+s"(rp), [xp] "+s"(xp), [phase] "+s"(phase)
-                                 : [ns] "s"(nsets), [tp] "s"(tp), [lane16] "v"(lane16), [voff4] "v"(voff4), [voff8] "v"(voff8), [pfl] "v"(pfl)
-                                 : ACC_TILEDT_CLOBBERS);
-            } else if constexpr (MODE == 4)
+            // first schedule word of this chunk (wave-uniform address)
+            const uint64_t t_ = reinterpret_cast<uint64_t>(gtab + pos_chunk / (4 * NSL));
+            const uint64_t tp = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((unsigned)(t_ >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((unsigned)t_);
+            if constexpr (NSL == 2)
+                asm volatile(ACC_TILED2_CHUNK_ASM
+                             : [rp] "+s"(rp), [xp] "+s"(xp), [phase] "+s"(phase)
+                             : [ns] "s"(2 * nsets), [tp] "s"(tp), [lane16] "v"(lane16), [voff4] "v"(voff4), [voff8] "v"(voff8), [pfl] "v"(pfl)
+                             : ACC_TILED_CHUNK_CLOBBERS);
+            else
                 asm volatile(ACC_TILED4_CHUNK_ASM
                              : [rp] "+s"(rp), [xp] "+s"(xp), [phase] "+s"(phase)
-                             : [ns] "s"(nsets), [q0] "s"(q0), [q1] "s"(q1), [q2] "s"(q2), [q3] "s"(q3), [lane16] "v"(lane16),
-                               [voff4] "v"(voff4), [voff8] "v"(voff8)
-                             : ACC_TILED_CLOBBERS);
-            else if constexpr (MODE == 3)
-                asm volatile(ACC_TILED2R_CHUNK_ASM
-                             : [rp] "+s"(rp), [xp] "+s"(xp), [phase] "+s"(phase)
-                             : [ns] "s"(2 * nsets), [q0] "s"(q0), [q1] "s"(q1), [q2] "s"(q2), [q3] "s"(q3), [lane16] "v"(lane16),
-                               [voff4] "v"(voff4), [voff8] "v"(voff8)
-                             : ACC_TILED_CLOBBERS);
-            else
-                asm volatile(ACC_TILED_CHUNK_ASM
-                             : [rp] "+s"(rp), [xp] "+s"(xp), [phase] "+s"(phase)
-                             : [ns] "s"(nsets), [q0] "s"(q0), [q1] "s"(q1), [q2] "s"(q2), [q3] "s"(q3), [lane16] "v"(lane16),
-                               [voff4] "v"(voff4), [voff8] "v"(voff8)
-                             : ACC_TILED_CLOBBERS);
+                             : [ns] "s"(nsets), [tp] "s"(tp), [lane16] "v"(lane16), [voff4] "v"(voff4), [voff8] "v"(voff8), [pfl] "v"(pfl)
+                             : ACC_TILED_CHUNK_CLOBBERS);
         }
     }
-    // Up to four (eight) refills (issued past the end of this wave's range, into the stream's slack) are still in
-    // flight; they write the ring registers v64..v75 (v64..v87) only, which nothing below touches
+    // Up to eight refills (issued past the end of this wave's range, into the stream's slack) are still in flight;
+    // they write the ring registers v64..v87 only, which nothing below touches
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (wact) {
         double* out = Bout + (size_t)by * (size_t)slab;
@@ -927,12 +886,6 @@ int k_acc_tiled(hipStream_t s, const DevTiled& S, const double* F, int ldf, doub
                                    hipFuncAttributeMaxDynamicSharedMemorySize, TILED_LDS_BYTES + 512));
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&acc_tiled_kernel<4>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, TILED_LDS_BYTES + 512));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&acc_tiled_kernel<3>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, TILED_LDS_BYTES + 512));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&acc_tiled_kernel<6>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, TILED_LDS_BYTES + 512));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&acc_tiled_kernel<7>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, TILED_LDS_BYTES + 512));
         if (dev >= 0 && dev < 64) attr_set[dev] = true;
     }
     const int64_t nwg_x = (S.nwb + TILED_NW - 1) / TILED_NW;
@@ -943,18 +896,13 @@ int k_acc_tiled(hipStream_t s, const DevTiled& S, const double* F, int ldf, doub
     const int64_t tail_cols = tail ? (nwg_x - S.tail_wg0) * TILED_NW * S.CW : 0;
     const int64_t tail_slab = tail_cols * kf;
     const dim3 grid(tail ? (unsigned)(S.tail_wg0 + (nwg_x - S.tail_wg0) * S.tail_R) : (unsigned)nwg_x, (unsigned)S.R);
-    const bool table = !getenv("SGL_TILED_NO_TABLE") && !getenv("SGL_TILED_PREP") && S.gtab != nullptr;
-    auto launch = [&](auto mode) {
-        constexpr int MODE = decltype(mode)::value;
-        acc_tiled_kernel<MODE><<<grid, dim3(64 * TILED_NW), lds, s>>>(
+    auto launch = [&](auto nsl) {
+        acc_tiled_kernel<decltype(nsl)::value><<<grid, dim3(64 * TILED_NW), lds, s>>>(
             S.roff, xvals ? xvals : S.x, S.cstart, S.cnt, S.T, S.NB, S.nwb, F, kf, S.TR, S.nrow, S.tiles_per_range, out, S.ncol, KS, ldf,
             slabs ? kf : ldb, slabs ? n : 0, S.perm, S.range_fastest ? 1 : 0, S.gtab, tail ? (int)S.tail_wg0 : -1, tail ? S.tail_R : 1,
             S.part, tail_slab);
     };
-    if (S.NSL == 4 && table) launch(std::integral_constant<int, 7>());
-    else if (S.NSL == 2 && table) launch(std::integral_constant<int, 6>());
-    else if (S.NSL == 4) launch(std::integral_constant<int, 4>());
-    else if (!getenv("SGL_TILED_PREP")) launch(std::integral_constant<int, 3>());
+    if (S.NSL == 4) launch(std::integral_constant<int, 4>());
     else launch(std::integral_constant<int, 2>());
     HIPCHK(hipGetLastError());
     if (tail) {
@@ -991,15 +939,14 @@ int k_acc_tiled_all(hipStream_t s, const DevTiled& S, const double* F, double* B
 // k = 64 pass) instead of two pair passes (2 x); 97 - 128 as FOUR quad passes (2.0 x the k = 64 pass; the two pair passes measure
 // 2.4 x -- rhs_h per 200 000 cells at k = 100: 5.84 -> 4.89 ms, k = 128: 6.48 -> 5.01; profiles/r5_k_sweep_200k_cells.txt).
 // One pass over half-height tiles with four factors per lane was priced and loses: 15 % more LDS time than the two passes
-// (scripts/r5/r5_pad_model.py).  SGL_TILED_NO_QUAD3=1: two pair passes (A/B, tests).
+// (scripts/r5/r5_pad_model.py).
 // Round 6: ranks above 128 too -- ceil(k / 32) quad passes over the same stream (the reference's nnls / predict have no rank
 // limit, src/singlet.cpp:229-250, and RunNMF hands ard_nmf k_max = 1e4, R/RunNMF.R:131); until then they fell to the plain
-// wave-per-column gather (acc_kernel).  SGL_TILED_MAX_K=128 restores that (A/B, tests).
+// wave-per-column gather (acc_kernel).
 int tiled_part_size(int k) {
     if (k <= 64) return k;
-    const char* mk = getenv("SGL_TILED_MAX_K");
-    if (k > ((mk && atoi(mk) > 0) ? atoi(mk) : SGL_MAX_K)) return 0;
-    const bool quad = !getenv("SGL_TILED_NO_QUAD3") && !getenv("SGL_TILED_NO_QUAD");
+    if (k > SGL_MAX_K) return 0;
+    const bool quad = !getenv("SGL_TILED_NO_QUAD");
     const int parts = quad ? (k <= 96 ? 3 : (k + 31) / 32) : (k + 63) / 64;
     return ((k + parts - 1) / parts + 1) & ~1;
 }

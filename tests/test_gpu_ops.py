@@ -265,9 +265,10 @@ def test_rhs_tiled_split_tile_ranges(sa, ora, k, ranges, monkeypatch):
 @pytest.mark.parametrize("layout", ["quad", "pair"])
 @pytest.mark.parametrize("shape", ["very_sparse", "dense_blocks", "one_pair_only"])
 def test_rhs_tiled_pair_bookkeeping_extremes(ctx, ora, sa, shape, layout, monkeypatch):
-    """The chunk loop of the tiled accumulate walks a byte queue of per-pair group counts (gen_acc_tiled.py): most
-    counts zero (long skips, queue rotation over empty 64-bit words), counts near the byte's limit (whole columns
-    dense inside a tile), and a chunk whose entries all belong to one pair.  Against the plain kernel and the oracle."""
+    """The stream builder counts groups per column unit in bytes and writes the schedule table the chunk loop of the tiled
+    accumulate walks, one word per group (gen_acc_tiled.py): most counts zero (long runs of empty units), counts near the
+    byte's limit (whole columns dense inside a tile), and a chunk whose entries all belong to one pair.  Against the
+    plain kernel and the oracle."""
     if layout == "pair":
         monkeypatch.setenv("SGL_TILED_NO_QUAD", "1")
     monkeypatch.setenv("SGL_TILED_RANGES", "1")   # bit for bit: the tile range whole

@@ -1,7 +1,7 @@
 """Static checks of the tiled accumulate's generated code (no GPU needed: hipcc cross-compiles).
 
 acc_tiled_kernel keeps its 64 FP64 accumulator pairs in v[128:255] and the working set of its generated
-chunk loop (gen_acc_tiled.py: stream ring, prepared sets, LDS addresses, factor quads) in v[64:127], all
+chunk loop (gen_acc_tiled.py: stream ring, LDS addresses, factor quads) in v[64:127], all
 outside hipcc's register allocation; the ring's loads stay in flight across compiler code.  That is only
 sound while the compiler itself never allocates a register at or above v64 and keeps scratch out of the
 tile loop: both are properties of a particular hipcc, so they are asserted on the assembly this toolchain
@@ -44,7 +44,7 @@ def tiled_asm(tmp_path_factory):
     subprocess.run(["make", "-C", os.path.dirname(SRC), "acc_tiled_gen.inc"], check=True, capture_output=True, timeout=120)
     text = _device_asm(SRC, tmp_path_factory.mktemp("asm"))
     inst = {}
-    for nsl in (2, 3, 4, 6, 7):   # acc_tiled_kernel<MODE>: pairs with prepared sets, pairs on the ring layout, quads (k <= 32); 6 / 7: 3 / 4 with the schedule table
+    for nsl in (2, 4):   # acc_tiled_kernel<NSL>: pairs of columns (parts of 33 - 64 factors), quads (parts up to 32)
         m = re.search(r"^(_Z16acc_tiled_kernelILi%dEE\w*):[^\n]*\n(.*?)s_endpgm" % nsl, text, re.S | re.M)
         assert m, "acc_tiled_kernel<%d> not found in the assembly" % nsl
         meta = text[text.index(".amdhsa_kernel " + m.group(1)):]
@@ -60,7 +60,7 @@ def _vregs(line):
     return regs
 
 
-@pytest.mark.parametrize("nsl", [2, 3, 4, 6, 7])
+@pytest.mark.parametrize("nsl", [2, 4], ids=["pair", "quad"])
 def test_compiler_stays_below_v64_and_keeps_scratch_out_of_the_loop(tiled_asm, nsl):
     body, meta = tiled_asm[nsl]
     in_asm, worst = False, -1
@@ -84,50 +84,24 @@ def test_compiler_stays_below_v64_and_keeps_scratch_out_of_the_loop(tiled_asm, n
     assert m and int(m.group(1)) <= 64, "acc_tiled_kernel spills %s bytes per lane" % (m.group(1) if m else "?")
 
 
-def test_chunk_loop_is_the_generated_asm_with_counted_waits(tiled_asm):
-    """The chunk loop must be the generated block: four ring-slot bodies + four prologues, each preparing a set behind
-    the counted stream wait vmcnt(6); one counted LDS wait per group of four entry pairs (a full drain only in front
-    of the last group of a chunk), no vmcnt(0); vector destinations are only written while M0 indexes nothing."""
-    body, _ = tiled_asm[2]
-    blocks = re.findall(r"#ASMSTART(.*?)#ASMEND", body, re.S)
-    chunk = [b for b in blocks if "v_fmac_f64_dpp" in b]
-    assert len(chunk) == 1, "expected exactly one asm block with the FMAs"
-    text = chunk[0]
-    assert text.count("s_waitcnt vmcnt(6)") == 8          # 4 prologues + 4 in-loop preparations
-    assert "vmcnt(0)" not in text
-    assert text.count("v_fmac_f64_dpp") == 4 * (4 + 1) * 16  # 4 bodies x (4 octets + the no-prefetch copy of the last) x 16
-    assert text.count("ds_read_b128") == 4 * 8 + 4 * 4 * 8  # prologues + one read behind every prefetching pair
-    assert text.count("s_waitcnt lgkmcnt(4)") == 4 * (4 * 2 + 1) and text.count("s_waitcnt lgkmcnt(0)") == 4
-    assert "v_readlane" not in text                       # pair switches are scalar (byte queue in SGPRs)
-    # walk the block in program order: the cold section (last octets, pair switches) sits behind the loop and is
-    # entered / left by branches, so the linear M0 state only holds for the hot part
-    hot = text[:text.index("s_set_gpr_idx_off")]
-    m0 = None
-    for l in (x.strip() for x in hot.splitlines()):
-        if l.startswith("s_mov_b32 m0"):
-            m0 = l.split(",")[1].strip()
-        elif l.startswith(".Ltiled_last") or l.startswith(".Ltiled_sw"):
-            m0 = "cold"    # out-of-line code: FMAs behind a group head, no vector-destination VALU besides them
-        elif l.startswith(("v_add_u32_dpp", "v_mov_b32", "v_permlane16_swap")):
-            assert m0 == "0", "VALU with a vector destination while M0 indexes destinations: %s" % l
-
-
-@pytest.mark.parametrize("mode", [4, 3])
-def test_quad_chunk_loop_reads_its_operands_from_the_ring(tiled_asm, mode):
-    """acc_tiled_kernel<4> (ranks up to 32, four columns per LDS instruction): eight ring-slot bodies of two octets, no
-    set preparation (no v_mov / v_permlane16_swap: the DPP operands are the ring registers, written by vector loads
-    only -- no VALU-write -> DPP-read hazard can exist), counted stream waits, destinations written only with M0 off."""
-    body, _ = tiled_asm[mode]   # (mode 3: the pair layout on the same loop, half-set ring slots with doubled lane rows)
+@pytest.mark.parametrize("nsl", [2, 4], ids=["pair", "quad"])
+def test_schedule_table_chunk_loop(tiled_asm, nsl):
+    """acc_tiled_kernel<2 / 4>: one s_bfe_u32 m0 per group of four entry tuples out of the 32 schedule words of the running
+    lap, no countdown, no switch code, no branch inside an octet; the next lap's words loaded a lap ahead and waited with a
+    full lgkmcnt drain (SMEM returns out of order); eight ring slots of two octets, no set preparation (no v_mov /
+    v_permlane16_swap: the DPP operands are the ring registers, written by vector loads only -- no VALU-write -> DPP-read
+    hazard can exist), counted stream waits, address adds only with M0 off."""
+    body, _ = tiled_asm[nsl]
     blocks = re.findall(r"#ASMSTART(.*?)#ASMEND", body, re.S)
     chunk = [b for b in blocks if "v_fmac_f64_dpp" in b]
     assert len(chunk) == 1
     text = chunk[0]
     assert "v_permlane16_swap" not in text and "v_mov_b32 v" not in text and "v_readlane" not in text
     assert "vmcnt(0)" not in text
-    assert text.count("s_waitcnt vmcnt(14)") == 8 and text.count("s_waitcnt vmcnt(12)") == 8
-    assert text.count("v_fmac_f64_dpp") == 8 * (2 + 1) * 16
-    assert text.count("ds_read_b128") == 8 * 8 + 8 * 2 * 8
-    assert text.count("global_load_dword ") == 8 and text.count("global_load_dwordx2") == 8
+    assert text.count("s_waitcnt vmcnt(14)") == 8 and text.count("s_waitcnt vmcnt(12)") == 8   # 8 prologues, 8 bodies
+    assert text.count("v_fmac_f64_dpp") == 8 * (2 + 2) * 16      # eight bodies + eight copies for a chunk's last half-set
+    assert text.count("ds_read_b128") == 8 * 8 + 8 * 2 * 8 + 8 * 8   # prologues, bodies, the last half-sets' first octets
+    assert text.count("global_load_dword ") == 16 and text.count("global_load_dwordx2") == 16   # a refill per body and per last half-set
     # DPP sources: ring registers only (v64..v71 row offsets, v[72:87] values)
     for l in (x.strip() for x in text.splitlines()):
         if l.startswith("v_add_u32_dpp"):
@@ -136,30 +110,6 @@ def test_quad_chunk_loop_reads_its_operands_from_the_ring(tiled_asm, mode):
         elif l.startswith("v_fmac_f64_dpp"):
             src = int(re.match(r"v_fmac_f64_dpp v\[\d+:\d+\], v\[(\d+):\d+\],", l).group(1))
             assert 72 <= src <= 86 and src % 2 == 0, l
-    hot = text[:text.index("s_set_gpr_idx_off")]
-    m0 = None
-    for l in (x.strip() for x in hot.splitlines()):
-        if l.startswith("s_mov_b32 m0"):
-            m0 = l.split(",")[1].strip()
-        elif l.startswith(".Ltiled_last") or l.startswith(".Ltiled_sw"):
-            m0 = "cold"
-        elif l.startswith("v_add_u32_dpp"):
-            assert m0 == "0", "VALU with a vector destination while M0 indexes destinations: %s" % l
-
-
-@pytest.mark.parametrize("mode", [6, 7])
-def test_schedule_table_chunk_loop(tiled_asm, mode):
-    """acc_tiled_kernel<6 / 7> (the default): one s_bfe_u32 m0 per group of four entry tuples out of the 32 schedule words of
-    the running lap, no countdown, no switch code, no branch inside an octet; the next lap's words loaded a lap ahead and
-    waited with a full lgkmcnt drain (SMEM returns out of order); operands straight from the ring."""
-    body, _ = tiled_asm[mode]
-    blocks = re.findall(r"#ASMSTART(.*?)#ASMEND", body, re.S)
-    chunk = [b for b in blocks if "v_fmac_f64_dpp" in b]
-    assert len(chunk) == 1
-    text = chunk[0]
-    assert "v_permlane16_swap" not in text and "v_mov_b32 v" not in text and "v_readlane" not in text
-    assert "vmcnt(0)" not in text
-    assert text.count("v_fmac_f64_dpp") == 8 * (2 + 2) * 16      # eight bodies + eight copies for a chunk's last half-set
     heads = re.findall(r"s_bfe_u32 m0, s(\d+), (0x[0-9a-f]+)", text)
     assert len(heads) == 8 * (2 + 2) * 2                     # one per group; the last half-sets' copies included
     hot = [(int(r), int(f, 16)) for r, f in heads[:0]]
