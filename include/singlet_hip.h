@@ -23,6 +23,9 @@
  *    outputs go to caller-allocated buffers.
  *  - all arithmetic on the path is FP64 on the GPU; there is no CPU fallback:
  *    without a usable gfx950 device every entry point fails with SGL_ENODEV.
+ *    The two neighbour-graph entries are the exception, as in the reference:
+ *    sgl_c_lknn is FP32 (its distances are floats, returned as doubles) and
+ *    sgl_c_snn is integer counting with one FP64 quotient per entry.
  *  - ranks: every entry point takes 1 <= k <= 1024 (SGL_EINVAL above, before anything is uploaded; the
  *    reference's nnls / predict_mask have no limit, src/singlet.cpp:229-250, 436-466).  The tuned kernels cover
  *    k <= 128 (LDS-tiled accumulate, MFMA Grams and Gram downdates, lane NNLS); the plain fit runs ranks 129 - 256 on the
@@ -209,6 +212,45 @@ SGL_API int sgl_c_gcnmf(const double* Ax, const int32_t* Ai, const int32_t* Ap,
                         const double* w_init, int32_t w_rows, int32_t w_cols, int32_t k,
                         double* w_out, double* d_out, double* h_out,
                         int32_t* n_iter, double* tol_trace, const sgl_callbacks* cb);
+
+/* c_LKNN (src/singlet.cpp:1491-1603; glue _singlet_c_LKNN, 10 args), the local
+ * k-nearest-neighbour graph of R/FindLocalNeighbors.R:95.  m is m_rows x m_cols
+ * column-major, transposed iff m_cols != m_rows && m_rows == n_coords (l.1492);
+ * n = n_coords points.  FP32 throughout: m, the coordinates, radius and
+ * max_dist are rounded to float once.  For each point, the other points with
+ * sqrt(dx*dx + dy*dy) <= radius (float, l.1520-1523) get a distance in the
+ * embedding ("jaccard", "cosine", "manhattan", "hamming", "kl", anything else
+ * euclidean; l.1426-1478, in dimension order, no FMA, quirks kept); those with
+ * max_dist != 0 && d > max_dist are dropped; of more than k, the k smallest
+ * are kept.  Ranking is by (distance, index): ties at the cut go to the lower
+ * index and NaN distances rank after every number (this build's rule; the
+ * reference's std::sort leaves both unspecified).  Zero distances (+-0) are
+ * dropped AFTER the selection (l.1572-1588).  Output: the n x n dgCMatrix,
+ * column j = the neighbours of point j, rows ascending, x = the distances.
+ * Refused (SGL_EINVAL, with a message): the reference's two stop()s, k < 0,
+ * non-finite m or coordinates, a negative or non-finite radius, and a point
+ * that keeps more than ceil((2 radius + 1)^2) - 1 neighbours (the slots per
+ * point the reference allocates, l.1496: it would overwrite the next point's).
+ * Two-call contract: with i_out / x_out NULL, fills p_out (n + 1) and *nnz_out;
+ * with buffers of cap >= nnz, fills them too; cap < nnz is SGL_EINVAL.  The
+ * result is deterministic, bit for bit. */
+SGL_API int sgl_c_lknn(const double* m, int32_t m_rows, int32_t m_cols,
+                       const double* coord_x, const double* coord_y, int32_t n_coords,
+                       int64_t k, double radius, const char* metric, int similarity, double max_dist,
+                       int32_t* p_out, int64_t* nnz_out, int32_t* i_out, double* x_out, int64_t cap);
+
+/* c_SNN (src/singlet.cpp:1606-1665; glue _singlet_c_SNN, 3 args), the shared
+ * nearest-neighbour graph of R/FindLocalNeighbors.R:98.  Only G's pattern is
+ * read (G_nrow x G_ncol, any shape).  Output: the G_ncol x G_ncol dgCMatrix
+ * whose column i, for nnz_i > 0, holds (i, i) = 1 and every j != i whose row
+ * sets meet with sim = inter / (nnz_i + nnz_j - inter) > min_similarity (FP64,
+ * strict); empty columns stay empty; rows ascend.  Unsorted or out-of-range
+ * rows of G are SGL_EINVAL, and so is an output of 2^31 entries or more
+ * (refused after the count pass, before anything is allocated for it).  Same
+ * two-call contract as sgl_c_lknn; deterministic. */
+SGL_API int sgl_c_snn(const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol,
+                      double min_similarity,
+                      int32_t* p_out, int64_t* nnz_out, int32_t* i_out, double* x_out, int64_t cap);
 
 /* c_project_model (src/singlet.cpp:405-413).
  * Replaces _singlet_c_project_model (src/RcppExports.cpp:444-447 region).

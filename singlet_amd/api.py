@@ -8,6 +8,9 @@ names, argument order, defaults and return fields:
   c_gcnmf                               src/RcppExports.cpp:399-417
   run_nmf                               R/run_nmf.R:18-77
   run_gcnmf                             R/RunGCNMF.R:20-98
+  c_LKNN / c_SNN                        src/singlet.cpp:1491-1665 (glue src/RcppExports.cpp:466-467)
+  find_local_neighbors                  R/FindLocalNeighbors.R:32-101
+  rescale_spatial                       R/RescaleSpatial.R:10-22
   ard_nmf                               R/ard_nmf.R:31-193
   cross_validate_nmf                    R/cross_validate_nmf.R:18-105
   GetBestRank                           R/GetBestRank.R:8-46
@@ -814,3 +817,122 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
     finally:
         fits.close()
     return df2
+
+
+# ---------------------------------------------------------------------------
+# Spatial neighbour graphs (FindLocalNeighbors / RescaleSpatial)
+# ---------------------------------------------------------------------------
+def _two_call(fn, n):
+    """Run a two-call sgl_c_lknn / sgl_c_snn entry: counts first, then the slots."""
+    p = np.empty(n + 1, dtype=np.int32)
+    nnz = C.c_int64()
+    check(fn(ptr(p, i32p), C.byref(nnz), None, None, 0))
+    i = np.empty(max(nnz.value, 1), dtype=np.int32)
+    x = np.empty(max(nnz.value, 1), dtype=np.float64)
+    check(fn(ptr(p, i32p), C.byref(nnz), ptr(i, i32p), ptr(x, f64p), nnz.value))
+    return p, i[:nnz.value], x[:nnz.value]
+
+
+def c_LKNN(m, coord_x, coord_y, k, radius, metric, similarity, max_dist, verbose, threads):
+    """.Call(`_singlet_c_LKNN`, ...) -> the n x n local k-nearest-neighbour dgCMatrix (src/singlet.cpp:1491-1603); column j
+    holds the neighbours of point j, x their float distances.  Rules where the reference is undefined (ties, NaN distances,
+    more neighbours than its slots per point): include/singlet_hip.h, sgl_c_lknn.  `threads` is ignored."""
+    L = _lib.load()
+    m = np.asarray(m, dtype=np.float64)
+    if m.ndim == 1:
+        m = m.reshape(-1, 1)
+    if m.ndim != 2:
+        raise ValueError("m must be a matrix")
+    cx = np.ascontiguousarray(coord_x, dtype=np.float64).ravel()
+    cy = np.ascontiguousarray(coord_y, dtype=np.float64).ravel()
+    m_rows, m_cols = m.shape
+    if m_cols != m_rows and m_rows == cx.size:
+        m_cols_t = m_rows
+    else:
+        m_cols_t = m_cols
+    if m_cols_t != cx.size:   # l.1493, in the reference's order
+        raise _lib.SingletHipError(-1, "number of columns in 'm' must be equal to number of coordinates")
+    if cx.size != cy.size:    # l.1494
+        raise _lib.SingletHipError(-1, "length of coordinate vectors must be equivalent")
+    mf = np.asfortranarray(m)
+    n = int(cx.size)
+    if verbose:
+        base = np.float32(np.float32(radius) * np.float32(2) + np.float32(1))
+        n_max_edges = int(math.ceil(float(base) * float(base))) - 1
+        print("number of edges per node: %d" % (n_max_edges & 0xffffffff))
+        print("filtering %d edges" % (n * n_max_edges))
+    p, i, x = _two_call(lambda po, no, io, xo, cap: L.sgl_c_lknn(
+        mf.ctypes.data_as(f64p), m_rows, m_cols, ptr(cx, f64p), ptr(cy, f64p), n, int(k), float(radius),
+        str(metric).encode(), int(bool(similarity)), float(max_dist), po, no, io, xo, cap), n)
+    if verbose:
+        print("selected %d edges" % int(p[-1]))
+    return dgCMatrix(x, i, p, (n, n))
+
+
+def c_SNN(G, min_similarity, threads):
+    """.Call(`_singlet_c_SNN`, ...) -> the ncol(G) x ncol(G) shared-nearest-neighbour dgCMatrix (src/singlet.cpp:1606-1665):
+    the Jaccard index of the row sets of every two columns that share a row, kept when > min_similarity, and 1 on the
+    diagonal of every non-empty column.  Only G's pattern is read.  `threads` is ignored."""
+    L = _lib.load()
+    G = as_dgCMatrix(G)
+    n = G.ncol
+    p, i, x = _two_call(lambda po, no, io, xo, cap: L.sgl_c_snn(ptr(G.i, i32p), ptr(G.p, i32p), G.nrow, G.ncol,
+                                                                float(min_similarity), po, no, io, xo, cap), n)
+    return dgCMatrix(x, i, p, (n, n))
+
+
+def rescale_spatial(coords):
+    """RescaleSpatial.Seurat (R/RescaleSpatial.R:10-22) on an n x 2 coordinate matrix: each axis shifted to start at 0,
+    scaled to [0, 1], divided by the median gap between its sorted unique values, and rounded half to even (R's round)."""
+    df = np.array(coords, dtype=np.float64)
+    if df.ndim != 2 or df.shape[1] < 2:
+        raise ValueError("coords must be an n x 2 matrix")
+    for a in (0, 1):
+        c = df[:, a] - np.min(df[:, a])
+        c = c / np.max(c)
+        c = c * 1 / np.median(np.diff(np.sort(np.unique(c))))
+        df[:, a] = c
+    return np.round(df)
+
+
+def find_local_neighbors(h, spatial, k_param=20, spatial_radius=4, nn_metric="jaccard", use_dist=False, compute_snn=True,
+                         prune_snn=1 / 15, prune_knn=1 / 10, return_dist=False, verbose=False, dims=None, threads=0):
+    """The numeric steps of FindLocalNeighbors.Seurat (R/FindLocalNeighbors.R:32-101): `h` is the reduction's embedding,
+    cells x factors (as cell.embeddings), `spatial` the n x 2 spatial coordinates; `dims` are 1-based, as in R.
+    Returns {"knn": c_LKNN graph (x = 1 unless return_dist), "snn": c_SNN of it or None}.
+
+    The message of l.74 is R's own `stop(..., max(sp[,1], "or", max(sp[,2]), ...))`: its max() swallows the text.  Here it
+    reads as intended."""
+    sp = np.asarray(spatial, dtype=np.float64)
+    if sp.ndim != 2 or sp.shape[1] < 2:
+        raise ValueError("spatial must be an n x 2 matrix")
+    if np.max(sp[:, 0]) == 1 and np.max(sp[:, 1]) == 1:   # l.64-65 (a warning in R)
+        import warnings
+        warnings.warn("maximum value in spatial.reduction is 1 in both dimensions. Double-check that your coordinates are "
+                      "fixed and on the same scale in both dimensions.")
+    hm = np.asarray(h, dtype=np.float64).T   # h <- t(cell.embeddings) (l.67)
+    if hm.shape[1] != sp.shape[0]:
+        raise ValueError("there were %d samples in reduction but %d samples in spatial reduction" % (hm.shape[1], sp.shape[0]))
+    if dims is not None:
+        dims = np.atleast_1d(np.asarray(dims, dtype=np.int64))
+        if np.max(dims) > hm.shape[0]:
+            raise ValueError("you requested up to %d dims but there are only %d dimensions in reduction" % (np.max(dims), hm.shape[0]))
+        hm = hm[dims - 1, :]
+    if spatial_radius > np.max(sp[:, 0]) or spatial_radius > np.max(sp[:, 1]):
+        raise ValueError("your spatial radius of %s is greater than the maximum value of %s or %s in your spatial coordinates "
+                         "reduction" % (spatial_radius, np.max(sp[:, 0]), np.max(sp[:, 1])))
+    if nn_metric not in ("jaccard", "euclidean", "manhattan", "hamming", "kl", "cosine"):
+        raise ValueError("specified nn.metric = %s is not one of c('jaccard', 'euclidean', 'manhattan', 'hamming', 'kl', or "
+                         "'cosine')" % nn_metric)
+    if use_dist and nn_metric not in ("jaccard", "cosine"):
+        raise ValueError("it doesn't make sense to use dissimilarity (use.dist = FALSE) on a distance metric not strictly "
+                         "bounded between 0 and 1. Try using 'cosine' or 'jaccard' distance instead.")
+    if prune_knn >= 1:
+        raise ValueError("prune.knn must be less than 1. You are currently asking to prune everything.")
+    if prune_snn >= 1:
+        raise ValueError("prune.snn must be less than 1. You are currently asking to prune everything.")
+    knn = c_LKNN(hm, sp[:, 0], sp[:, 1], k_param, spatial_radius, nn_metric, not use_dist, prune_knn, verbose, threads)
+    if not return_dist:
+        knn.x = np.ones_like(knn.x)
+    snn = c_SNN(knn, prune_snn, threads) if compute_snn else None
+    return {"knn": knn, "snn": snn}

@@ -1,0 +1,939 @@
+// Spatial neighbour graphs of FindLocalNeighbors (R/FindLocalNeighbors.R:95-98): c_LKNN (src/singlet.cpp:1491-1603) and
+// c_SNN (:1606-1665) on the GPU.  The reference checks every pair of points (c_LKNN, O(n^2) radius tests) and every pair of
+// columns (c_SNN, O(n^2) serial list merges); here a spatial cell list bounds the LKNN candidates to the 3 x 3 buckets around
+// a point, and SNN counts the columns that share a row of G through G's row-major pattern.
+//
+// LKNN arithmetic is FP32 as in the reference (Eigen::MatrixXf, float radius / max_dist), summed in dimension order, with NO
+// contraction: the reference is built for x86-64 without FMA, so every distance, the radius test and the zero test are
+// bit-identical to it (kl: the log is within an ulp of glibc's, so a few ulps).  tests/test_kernel_codegen_neighbors.py checks the
+// emitted gfx950 code of the lknn kernels for fused multiply-adds.
+//
+// Where the reference is undefined, this build's rules (include/singlet_hip.h, sgl_c_lknn): candidates are ranked by
+// (distance, index) -- ties at the k-th place go to the lower index, NaN distances (0/0 of all-zero embedding columns) rank
+// after every number -- and a point that keeps more neighbours than the reference's n_max_edges slots per point is refused.
+#include "sgl_internal.h"
+#include <hipcub/hipcub.hpp>
+#include <math.h>
+#include <string.h>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+enum { NB_EUCLIDEAN = 0, NB_JACCARD, NB_COSINE, NB_MANHATTAN, NB_HAMMING, NB_KL };
+
+constexpr int LKNN_CAP = 512;    // candidates a point sorts in LDS (one 64-lane workgroup, 4 KB); above: segmented sort in HBM
+constexpr int SNN_CAP = 2048;    // gathered column indices a column sorts in LDS (8 KB); above: dense counters in HBM
+constexpr uint64_t NO_KEY = ~0ull;
+
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    ~DevBuf() { if (p) (void)sgl_pool_free(p); }
+    int alloc(size_t count) {
+        if (p) { (void)sgl_pool_free(p); p = nullptr; }
+        if (count == 0) count = 1;
+        if (sgl_pool_malloc(&p, count * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            sgl_set_error("hipMalloc of %zu bytes failed", count * sizeof(T));
+            return SGL_ENOMEM;
+        }
+        return SGL_OK;
+    }
+};
+
+struct CtxHold {
+    sgl_ctx* c = nullptr;
+    ~CtxHold() { if (c) sgl_destroy(c); }
+};
+
+int current_device() {
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; }
+    return d;
+}
+
+unsigned grid_for(int64_t n, int per_block) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, 65535)); }
+
+// ---------------------------------------------------------------------------------------------------------------- LKNN ---
+// Order-preserving 32-bit key of a distance: -0 is +0 (they tie and are both dropped), every NaN is one value above +inf.
+// key_dist returns that NaN as x86's default NaN (0xffc00000, sign set), the one the reference's 0/0 gives.
+__device__ __forceinline__ uint32_t dist_key(float d) {
+    uint32_t u = __float_as_uint(d);
+    if (d != d) u = 0x7fc00000u;
+    else if (d == 0.0f) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float key_dist(uint32_t k) {
+    if (k == (0x7fc00000u | 0x80000000u)) return __uint_as_float(0xffc00000u);
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// Correctly rounded float root and quotient through double (53 >= 2 * 24 + 2 bits: the double rounding is innocuous), so that
+// the distance kernels hold no f32 fused multiply-add at all -- not even the ones of the f32 division / root expansions --
+// and the codegen test can tell a contraction from them.  logf likewise goes through the double log.  The empty asm keeps
+// the compiler from folding the widened operation back to f32 (which it may: the results are the same).
+__device__ __forceinline__ double widen(float x) {
+    double d = (double)x;
+    asm volatile("" : "+v"(d));
+    return d;
+}
+__device__ __forceinline__ float sqrt_rn(float x) { return (float)__builtin_sqrt(widen(x)); }
+__device__ __forceinline__ float div_rn(float a, float b) { return (float)(widen(a) / widen(b)); }
+__device__ __forceinline__ float log_f(float x) { return (float)log(widen(x)); }
+
+// The six distance functions of src/singlet.cpp:1426-1478, in float, in dimension order (p = the point, q = the candidate).
+template <int MET>
+__device__ __forceinline__ float nb_distance(const float* __restrict__ p, const float* __restrict__ q, int D, int similarity) {
+    if (MET == NB_JACCARD || MET == NB_COSINE) {
+        float pq = 0.0f, pp = 0.0f, qq = 0.0f;
+        for (int d = 0; d < D; ++d) {
+            const float a = p[d], b = q[d];
+            pq += a * b;
+            pp += a * a;
+            qq += b * b;
+        }
+        float r = (MET == NB_JACCARD) ? 1.0f - div_rn(pq, pp + qq - pq) : 1.0f - div_rn(pq, sqrt_rn(pp) * sqrt_rn(qq));
+        if (!similarity) r = 1.0f - r;
+        return r;
+    } else if (MET == NB_MANHATTAN) {
+        float s = 0.0f;
+        for (int d = 0; d < D; ++d) s += __builtin_fabsf(p[d] - q[d]);
+        return sqrt_rn(s);   // sic: the reference takes the root of the L1 sum
+    } else if (MET == NB_HAMMING) {
+        float s = 0.0f;
+        for (int d = 0; d < D; ++d)
+            if (p[d] != q[d]) s += 1.0f;
+        return s;
+    } else if (MET == NB_KL) {
+        float pdivq = 0.0f, psum = 0.0f;
+        for (int d = 0; d < D; ++d) {
+            if (q[d] != 0.0f) pdivq += div_rn(p[d], q[d]);
+            psum += p[d];
+        }
+        return psum * log_f(pdivq);
+    } else {
+        float s = 0.0f;
+        for (int d = 0; d < D; ++d) {
+            const float t = p[d] - q[d];
+            s += t * t;
+        }
+        return sqrt_rn(s);
+    }
+}
+
+struct LknnArgs {
+    const float* m;          // D x n, column-major
+    int D;
+    const float* cx;
+    const float* cy;
+    float radius, max_dist;
+    int similarity;
+    const uint32_t* sidx;    // point at each sorted position
+    const int32_t* rng;      // 6 per sorted position: the three [lo, hi) runs of sorted positions of the 3 x 3 buckets
+    int64_t k;
+};
+
+// The candidate c (0 <= c < C) of the point at sorted position pos -> its sort key (distance key << 32 | index), or NO_KEY when
+// it is the point itself, outside the radius (the reference's exact test, :1520-1523) or pruned by max_dist (:1541).
+template <int MET>
+__device__ __forceinline__ uint64_t lknn_candidate(const LknnArgs& a, int64_t pos, uint32_t pt, int c) {
+    const int32_t* r = a.rng + pos * 6;
+    int32_t sp;
+    const int32_t l0 = r[1] - r[0], l1 = r[3] - r[2];
+    if (c < l0) sp = r[0] + c;
+    else if (c < l0 + l1) sp = r[2] + (c - l0);
+    else sp = r[4] + (c - l0 - l1);
+    const uint32_t j = a.sidx[sp];
+    if (j == pt) return NO_KEY;
+    const float dx = a.cx[pt] - a.cx[j], dy = a.cy[pt] - a.cy[j];
+    const float d = sqrt_rn(dx * dx + dy * dy);
+    if (!(d <= a.radius)) return NO_KEY;
+    const float d12 = nb_distance<MET>(a.m + (size_t)pt * a.D, a.m + (size_t)j * a.D, a.D, a.similarity);
+    if (a.max_dist != 0.0f && d12 > a.max_dist) return NO_KEY;
+    return ((uint64_t)dist_key(d12) << 32) | j;
+}
+
+// In-LDS bitonic sort of s[0, P) ascending, P a power of two; one 64-lane workgroup.
+__device__ __forceinline__ void bitonic_lds(uint64_t* s, int P) {
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < P; t += 64) {
+                const int u = t ^ stride;
+                if (u > t) {
+                    const uint64_t x = s[t], y = s[u];
+                    const bool up = (t & size) == 0;
+                    if ((x > y) == up) { s[t] = y; s[u] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// Points whose 3 x 3 buckets hold at most LKNN_CAP candidates, one 64-lane workgroup each, in spatial (sorted) order so that
+// neighbouring workgroups gather the same embedding columns.  Keeps the k smallest (distance, index), re-sorts them by index,
+// and writes them (zeros included) to the point's slots [toff[pt], toff[pt] + kept) of the staging list.
+template <int MET>
+__global__ __launch_bounds__(64) void lknn_fast_kernel(LknnArgs a, const int32_t* __restrict__ work, int64_t nwork,
+                                                       const int64_t* __restrict__ toff, int32_t* __restrict__ ti,
+                                                       float* __restrict__ tx, int32_t* __restrict__ kept,
+                                                       int32_t* __restrict__ nzc) {
+    __shared__ uint64_t s[LKNN_CAP];
+    __shared__ int npass;
+    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int64_t pos = work[w];
+        const uint32_t pt = a.sidx[pos];
+        const int32_t* r = a.rng + pos * 6;
+        const int C = (r[1] - r[0]) + (r[3] - r[2]) + (r[5] - r[4]);
+        int P = 64;
+        while (P < C) P <<= 1;
+        if (threadIdx.x == 0) npass = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int c = threadIdx.x; c < P; c += 64) {
+            const uint64_t key = c < C ? lknn_candidate<MET>(a, pos, pt, c) : NO_KEY;
+            mine += key != NO_KEY;
+            s[c] = key;
+        }
+        atomicAdd(&npass, mine);
+        __syncthreads();
+        bitonic_lds(s, P);
+        const int kk = (int)std::min<int64_t>(a.k, (int64_t)npass);
+        for (int c = threadIdx.x; c < P; c += 64) {   // the kept ones, index-major
+            const uint64_t v = s[c];
+            s[c] = c < kk ? (((v & 0xffffffffull) << 32) | (v >> 32)) : NO_KEY;
+        }
+        __syncthreads();
+        bitonic_lds(s, P);
+        int nz = 0;
+        const int64_t o = toff[pt];
+        for (int c = threadIdx.x; c < kk; c += 64) {
+            const uint64_t v = s[c];
+            const float d = key_dist((uint32_t)v);
+            ti[o + c] = (int32_t)(v >> 32);
+            tx[o + c] = d;
+            nz += d != 0.0f;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) npass = 0;
+        __syncthreads();
+        atomicAdd(&npass, nz);
+        __syncthreads();
+        if (threadIdx.x == 0) { kept[pt] = kk; nzc[pt] = npass; }
+        __syncthreads();
+    }
+}
+
+// Points with more than LKNN_CAP candidates, one workgroup each: every candidate's key goes to the point's segment
+// [soff[w], soff[w + 1]) of an HBM list, sorted afterwards by a segmented radix sort.
+template <int MET>
+__global__ __launch_bounds__(256) void lknn_slow_keys_kernel(LknnArgs a, const int32_t* __restrict__ work, int64_t nwork,
+                                                            const int32_t* __restrict__ soff, uint64_t* __restrict__ keys,
+                                                            int32_t* __restrict__ npass) {
+    __shared__ int cnt;
+    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int64_t pos = work[w];
+        const uint32_t pt = a.sidx[pos];
+        const int C = soff[w + 1] - soff[w];
+        if (threadIdx.x == 0) cnt = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int c = threadIdx.x; c < C; c += blockDim.x) {
+            const uint64_t key = lknn_candidate<MET>(a, pos, pt, c);
+            mine += key != NO_KEY;
+            keys[soff[w] + c] = key;
+        }
+        atomicAdd(&cnt, mine);
+        __syncthreads();
+        if (threadIdx.x == 0) npass[w] = cnt;
+        __syncthreads();
+    }
+}
+
+// After the (distance, index) sort: the kept prefix of each segment becomes index-major keys, whose segments [soff, kend) are
+// sorted next.
+__global__ void lknn_slow_trim_kernel(const uint64_t* __restrict__ sorted, uint64_t* __restrict__ keys2, const int32_t* __restrict__ soff,
+                                      const int32_t* __restrict__ npass, int64_t nwork, int64_t k, int32_t* __restrict__ kend) {
+    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int kk = (int)std::min<int64_t>(k, (int64_t)npass[w]);
+        for (int c = threadIdx.x; c < kk; c += blockDim.x) {
+            const uint64_t v = sorted[soff[w] + c];
+            keys2[soff[w] + c] = ((v & 0xffffffffull) << 32) | (v >> 32);
+        }
+        if (threadIdx.x == 0) kend[w] = soff[w] + kk;
+    }
+}
+
+__global__ void lknn_slow_write_kernel(const uint64_t* __restrict__ sorted2, const int32_t* __restrict__ soff,
+                                       const int32_t* __restrict__ kend, const int32_t* __restrict__ work, int64_t nwork,
+                                       const uint32_t* __restrict__ sidx, const int64_t* __restrict__ toff,
+                                       int32_t* __restrict__ ti, float* __restrict__ tx, int32_t* __restrict__ kept,
+                                       int32_t* __restrict__ nzc) {
+    __shared__ int cnt;
+    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const uint32_t pt = sidx[work[w]];
+        const int kk = kend[w] - soff[w];
+        const int64_t o = toff[pt];
+        if (threadIdx.x == 0) cnt = 0;
+        __syncthreads();
+        int nz = 0;
+        for (int c = threadIdx.x; c < kk; c += blockDim.x) {
+            const uint64_t v = sorted2[soff[w] + c];
+            const float d = key_dist((uint32_t)v);
+            ti[o + c] = (int32_t)(v >> 32);
+            tx[o + c] = d;
+            nz += d != 0.0f;
+        }
+        atomicAdd(&cnt, nz);
+        __syncthreads();
+        if (threadIdx.x == 0) { kept[pt] = kk; nzc[pt] = cnt; }
+        __syncthreads();
+    }
+}
+
+// m (m_rows x m_cols, column-major doubles) -> D x n floats, column-major, rounded to nearest once; flag = 1 on NaN / Inf.
+__global__ void lknn_to_float_kernel(const double* __restrict__ m, int64_t m_rows, int transpose, int64_t D, int64_t n,
+                                     float* __restrict__ out, int* __restrict__ flag) {
+    int bad = 0;
+    const int64_t tot = D * n;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t d = e % D, pt = e / D;
+        const double v = transpose ? m[pt + d * m_rows] : m[e];
+        if (!(__builtin_fabs(v) < __builtin_inf())) bad = 1;
+        out[e] = (float)v;
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+// Bucket key of every point: by * W + bx, with b = floor((c - cmin) / s) computed in double (see lknn_buckets for why this
+// is conservative).
+__global__ void lknn_keys_kernel(const float* __restrict__ cx, const float* __restrict__ cy, int64_t n, double xmin, double ymin,
+                                 double s, int64_t W, uint64_t* __restrict__ keys, uint32_t* __restrict__ iota) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t bx = (int64_t)floor(((double)cx[e] - xmin) / s), by = (int64_t)floor(((double)cy[e] - ymin) / s);
+        keys[e] = (uint64_t)(by * W + bx);
+        iota[e] = (uint32_t)e;
+    }
+}
+
+__device__ __forceinline__ int64_t lower_bound_u64(const uint64_t* a, int64_t n, uint64_t v) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The three runs of sorted positions (buckets bx-1 .. bx+1 of rows by-1 .. by+1 are contiguous in key order) and their total.
+__global__ void lknn_ranges_kernel(const uint64_t* __restrict__ skeys, int64_t n, int64_t W, int64_t H, int32_t* __restrict__ rng,
+                                   int64_t* __restrict__ C) {
+    for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t key = (int64_t)skeys[pos], by = key / W, bx = key % W;
+        int64_t tot = 0;
+        for (int q = 0; q < 3; ++q) {
+            const int64_t yy = by - 1 + q;
+            int64_t lo = 0, hi = 0;
+            if (yy >= 0 && yy < H) {
+                lo = lower_bound_u64(skeys, n, (uint64_t)(yy * W + std::max<int64_t>(bx - 1, 0)));
+                hi = lower_bound_u64(skeys, n, (uint64_t)(yy * W + std::min<int64_t>(bx + 1, W - 1) + 1));
+            }
+            rng[pos * 6 + 2 * q] = (int32_t)lo;
+            rng[pos * 6 + 2 * q + 1] = (int32_t)hi;
+            tot += hi - lo;
+        }
+        C[pos] = tot;
+    }
+}
+
+// Drop the zeros (:1572-1588) and widen to double: point pt's staged entries -> its output column at off[pt].
+__global__ void lknn_compact_kernel(const int64_t* __restrict__ toff, const int32_t* __restrict__ kept, const int64_t* __restrict__ off,
+                                    const int32_t* __restrict__ ti, const float* __restrict__ tx, int64_t n,
+                                    int32_t* __restrict__ oi, double* __restrict__ ox) {
+    for (int64_t pt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pt < n; pt += (int64_t)gridDim.x * blockDim.x) {
+        int64_t o = off[pt];
+        const int64_t t0 = toff[pt], t1 = t0 + kept[pt];
+        for (int64_t t = t0; t < t1; ++t)
+            if (tx[t] != 0.0f) { oi[o] = ti[t]; ox[o] = (double)tx[t]; ++o; }
+    }
+}
+
+template <int MET>
+int lknn_launch_fast(hipStream_t s, const LknnArgs& a, const int32_t* work, int64_t nwork, const int64_t* toff, int32_t* ti, float* tx,
+                     int32_t* kept, int32_t* nzc) {
+    if (nwork > 0)
+        lknn_fast_kernel<MET><<<dim3(grid_for(nwork, 1)), dim3(64), 0, s>>>(a, work, nwork, toff, ti, tx, kept, nzc);
+    return hipGetLastError() == hipSuccess ? SGL_OK : SGL_EHIP;
+}
+template <int MET>
+int lknn_launch_slow_keys(hipStream_t s, const LknnArgs& a, const int32_t* work, int64_t nwork, const int32_t* soff, uint64_t* keys,
+                          int32_t* npass) {
+    lknn_slow_keys_kernel<MET><<<dim3(grid_for(nwork, 1)), dim3(256), 0, s>>>(a, work, nwork, soff, keys, npass);
+    return hipGetLastError() == hipSuccess ? SGL_OK : SGL_EHIP;
+}
+
+#define NB_DISPATCH(met, fn, ...)                                   \
+    ((met) == NB_JACCARD     ? fn<NB_JACCARD>(__VA_ARGS__)          \
+     : (met) == NB_COSINE    ? fn<NB_COSINE>(__VA_ARGS__)           \
+     : (met) == NB_MANHATTAN ? fn<NB_MANHATTAN>(__VA_ARGS__)        \
+     : (met) == NB_HAMMING   ? fn<NB_HAMMING>(__VA_ARGS__)          \
+     : (met) == NB_KL        ? fn<NB_KL>(__VA_ARGS__)               \
+                             : fn<NB_EUCLIDEAN>(__VA_ARGS__))
+
+int hip_ok(hipError_t e, const char* what) {
+    if (e == hipSuccess) return SGL_OK;
+    (void)hipGetLastError();
+    sgl_set_error("%s failed: %s", what, hipGetErrorString(e));
+    return SGL_EHIP;
+}
+#define NBCHK(expr, what) SGLCHK(hip_ok((expr), what))
+
+}  // namespace
+
+extern "C" int sgl_c_lknn(const double* m, int32_t m_rows, int32_t m_cols, const double* coord_x, const double* coord_y,
+                          int32_t n_coords, int64_t k, double radius_d, const char* metric, int similarity, double max_dist_d,
+                          int32_t* p_out, int64_t* nnz_out, int32_t* i_out, double* x_out, int64_t cap) {
+    // --- arguments, in the reference's order (:1492-1494)
+    if (!p_out || !nnz_out || (!m && (int64_t)m_rows * m_cols > 0) || (n_coords > 0 && (!coord_x || !coord_y)) || !metric ||
+        m_rows < 0 || m_cols < 0 || n_coords < 0) {
+        sgl_set_error("sgl_c_lknn: bad arguments");
+        return SGL_EINVAL;
+    }
+    if ((i_out == nullptr) != (x_out == nullptr)) { sgl_set_error("sgl_c_lknn: i_out and x_out go together"); return SGL_EINVAL; }
+    const int64_t n = n_coords;
+    const bool transpose = m_cols != m_rows && m_rows == n;
+    const int64_t D = transpose ? m_cols : m_rows, mcols = transpose ? m_rows : m_cols;
+    if (mcols != n) { sgl_set_error("number of columns in 'm' must be equal to number of coordinates"); return SGL_EINVAL; }
+    if (k < 0) { sgl_set_error("sgl_c_lknn: k = %lld is negative", (long long)k); return SGL_EINVAL; }
+    const float radius = (float)radius_d, max_dist = (float)max_dist_d;
+    if (!(radius >= 0.0f) || !(radius < INFINITY)) {
+        sgl_set_error("c_LKNN: radius %g must be finite and non-negative", radius_d);
+        return SGL_EINVAL;
+    }
+    if (max_dist != max_dist) { sgl_set_error("c_LKNN: max_dist is NaN"); return SGL_EINVAL; }
+    std::vector<float> cx((size_t)n), cy((size_t)n);
+    double xmin = 0, xmax = 0, ymin = 0, ymax = 0;
+    for (int64_t e = 0; e < n; ++e) {
+        cx[e] = (float)coord_x[e];
+        cy[e] = (float)coord_y[e];
+        if (!(fabsf(cx[e]) < INFINITY) || !(fabsf(cy[e]) < INFINITY)) {
+            sgl_set_error("c_LKNN: coordinate %lld is not finite (as float)", (long long)e);
+            return SGL_EINVAL;
+        }
+        if (e == 0 || cx[e] < xmin) xmin = cx[e];
+        if (e == 0 || cx[e] > xmax) xmax = cx[e];
+        if (e == 0 || cy[e] < ymin) ymin = cy[e];
+        if (e == 0 || cy[e] > ymax) ymax = cy[e];
+    }
+    int met = NB_EUCLIDEAN;   // an unknown name is euclidean (:1539-1540)
+    if (!strcmp(metric, "jaccard")) met = NB_JACCARD;
+    else if (!strcmp(metric, "cosine")) met = NB_COSINE;
+    else if (!strcmp(metric, "manhattan")) met = NB_MANHATTAN;
+    else if (!strcmp(metric, "hamming")) met = NB_HAMMING;
+    else if (!strcmp(metric, "kl")) met = NB_KL;
+    // slots per point of the reference (:1496): ceil(pow(radius * 2 + 1, 2)) - 1, the base in float, the power in double
+    const float base = radius * 2.0f + 1.0f;
+    const double n_max_edges = ceil((double)base * (double)base) - 1.0;
+
+    CtxHold hd;
+    SGLCHK(sgl_create(current_device(), &hd.c));
+    hipStream_t s = hd.c->stream;
+    if (n == 0) {
+        p_out[0] = 0;
+        *nnz_out = 0;
+        return SGL_OK;
+    }
+
+    // --- embedding as float, D x n
+    DevBuf<double> dm;
+    DevBuf<float> mf, dcx, dcy;
+    DevBuf<int> flag;
+    SGLCHK(dm.alloc((size_t)(D * n)));
+    SGLCHK(mf.alloc((size_t)(D * n)));
+    SGLCHK(dcx.alloc((size_t)n));
+    SGLCHK(dcy.alloc((size_t)n));
+    SGLCHK(flag.alloc(1));
+    NBCHK(hipMemsetAsync(flag.p, 0, sizeof(int), s), "hipMemsetAsync");
+    if (D > 0) {
+        NBCHK(hipMemcpyAsync(dm.p, m, sizeof(double) * (size_t)(D * n), hipMemcpyHostToDevice, s), "upload of m");
+        lknn_to_float_kernel<<<dim3(grid_for(D * n, 256)), dim3(256), 0, s>>>(dm.p, m_rows, transpose ? 1 : 0, D, n, mf.p, flag.p);
+        NBCHK(hipGetLastError(), "lknn_to_float_kernel");
+    }
+    NBCHK(hipMemcpyAsync(dcx.p, cx.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s), "upload of coord_x");
+    NBCHK(hipMemcpyAsync(dcy.p, cy.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s), "upload of coord_y");
+    int hflag = 0;
+    NBCHK(hipMemcpyAsync(&hflag, flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "download of the flag");
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    if (hflag) { sgl_set_error("c_LKNN: 'm' holds a NaN or infinite value (or one that overflows float)"); return SGL_EINVAL; }
+    { DevBuf<double> tmp; std::swap(tmp.p, dm.p); }   // the double copy is done with
+
+    // --- spatial cell list.  Conservative prefilter: let the float test sqrt(dx*dx + dy*dy) <= r pass with dx = fl(x1 - x2).
+    // If |dx| < 2^-63, then |x1 - x2| < 2^-62.  Otherwise dx*dx >= 2^-126 is normal, so fl(dx*dx) >= dx^2 (1 - 2^-24); adding a
+    // non-negative fl(dy*dy) and taking the rounded root are monotone, each losing at most a factor (1 - 2^-24), so
+    // |x1 - x2| <= r (1 + 2^-21).  Either way |x1 - x2| <= R = max(r, 2^-62) (1 + 2^-21), and the same holds for y.  Buckets have
+    // side s >= max(r, 2^-62) (1 + 2^-10), so |x1 - x2| / s < 1 - 2^-11.  The bucket coordinate u = fl(fl(x - xmin) / s) in
+    // double is off by at most 2^-52 u <= 2^-21 (s is also raised so that u <= 2^30), so |u1 - u2| < 1 and floor(u1), floor(u2)
+    // differ by at most one: every pair that passes the radius test lies in adjacent buckets.  The test itself is then
+    // evaluated exactly as the reference does.  (radius 0 gives buckets of side ~2^-62: exact coordinates, up to the float
+    // underflow of dx*dx that the reference's test also lets through.)
+    const double ext = std::max(xmax - xmin, ymax - ymin);
+    const double side = std::max({std::max((double)radius, ldexp(1.0, -62)) * (1.0 + ldexp(1.0, -10)), ext * ldexp(1.0, -30)});
+    const int64_t W = (int64_t)floor((xmax - xmin) / side) + 2, H = (int64_t)floor((ymax - ymin) / side) + 2;
+    DevBuf<uint64_t> keys, skeys;
+    DevBuf<uint32_t> iota, sidx;
+    SGLCHK(keys.alloc((size_t)n));
+    SGLCHK(skeys.alloc((size_t)n));
+    SGLCHK(iota.alloc((size_t)n));
+    SGLCHK(sidx.alloc((size_t)n));
+    lknn_keys_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(dcx.p, dcy.p, n, xmin, ymin, side, W, keys.p, iota.p);
+    NBCHK(hipGetLastError(), "lknn_keys_kernel");
+    int end_bit = 1;
+    while (end_bit < 64 && ((uint64_t)1 << end_bit) <= (uint64_t)(W * H)) ++end_bit;
+    {
+        size_t tb = 0;
+        NBCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, iota.p, sidx.p, (int)n, 0, end_bit, s), "radix sort");
+        DevBuf<char> tmp;
+        SGLCHK(tmp.alloc(tb));
+        NBCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.p, skeys.p, iota.p, sidx.p, (int)n, 0, end_bit, s), "radix sort");
+    }
+    DevBuf<int32_t> rng;
+    DevBuf<int64_t> dC;
+    SGLCHK(rng.alloc((size_t)n * 6));
+    SGLCHK(dC.alloc((size_t)n));
+    lknn_ranges_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(skeys.p, n, W, H, rng.p, dC.p);
+    NBCHK(hipGetLastError(), "lknn_ranges_kernel");
+    std::vector<int64_t> C((size_t)n);
+    std::vector<uint32_t> hsidx((size_t)n);
+    NBCHK(hipMemcpyAsync(C.data(), dC.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download of the candidate counts");
+    NBCHK(hipMemcpyAsync(hsidx.data(), sidx.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download of the order");
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+
+    // --- staging slots: min(k, candidates) per point, in point order; work lists in sorted (spatial) order
+    std::vector<int64_t> toff((size_t)n + 1);
+    std::vector<int32_t> fast, slow;
+    toff[0] = 0;
+    {
+        std::vector<int64_t> room((size_t)n);
+        for (int64_t pos = 0; pos < n; ++pos) {
+            room[hsidx[pos]] = std::min<int64_t>(k, C[pos]);
+            if (C[pos] <= LKNN_CAP) fast.push_back((int32_t)pos);
+            else slow.push_back((int32_t)pos);
+        }
+        for (int64_t pt = 0; pt < n; ++pt) toff[pt + 1] = toff[pt] + room[pt];
+    }
+    const int64_t staged = toff[n];
+    DevBuf<int64_t> dtoff;
+    DevBuf<int32_t> ti, kept, nzc, dfast;
+    DevBuf<float> tx;
+    SGLCHK(dtoff.alloc((size_t)n + 1));
+    SGLCHK(ti.alloc((size_t)staged));
+    SGLCHK(tx.alloc((size_t)staged));
+    SGLCHK(kept.alloc((size_t)n));
+    SGLCHK(nzc.alloc((size_t)n));
+    SGLCHK(dfast.alloc(fast.size()));
+    NBCHK(hipMemcpyAsync(dtoff.p, toff.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload");
+    if (!fast.empty())
+        NBCHK(hipMemcpyAsync(dfast.p, fast.data(), sizeof(int32_t) * fast.size(), hipMemcpyHostToDevice, s), "upload");
+    LknnArgs a{mf.p, (int)D, dcx.p, dcy.p, radius, max_dist, similarity ? 1 : 0, sidx.p, rng.p, k};
+    if (NB_DISPATCH(met, lknn_launch_fast, s, a, dfast.p, (int64_t)fast.size(), dtoff.p, ti.p, tx.p, kept.p, nzc.p) != SGL_OK) {
+        sgl_set_error("lknn_fast_kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        return SGL_EHIP;
+    }
+
+    // --- points with more than LKNN_CAP candidates: segmented sorts in HBM, in batches of at most 2^27 candidates
+    const int64_t BATCH = (int64_t)1 << 27;
+    for (size_t b0 = 0; b0 < slow.size();) {
+        size_t b1 = b0;
+        int64_t tot = 0;
+        while (b1 < slow.size() && (b1 == b0 || tot + C[slow[b1]] <= BATCH)) tot += C[slow[b1++]];
+        if (tot >= INT32_MAX) { sgl_set_error("c_LKNN: one point has %lld candidates in its 3 x 3 buckets (limit 2^31)", (long long)tot); return SGL_EINVAL; }
+        const int64_t nw = (int64_t)(b1 - b0);
+        std::vector<int32_t> hsoff((size_t)nw + 1);
+        hsoff[0] = 0;
+        for (int64_t w = 0; w < nw; ++w) hsoff[w + 1] = hsoff[w] + (int32_t)C[slow[b0 + w]];
+        DevBuf<int32_t> dwork, dsoff, dnpass, dkend;
+        DevBuf<uint64_t> k1, k2;
+        SGLCHK(dwork.alloc((size_t)nw));
+        SGLCHK(dsoff.alloc((size_t)nw + 1));
+        SGLCHK(dnpass.alloc((size_t)nw));
+        SGLCHK(dkend.alloc((size_t)nw));
+        SGLCHK(k1.alloc((size_t)tot));
+        SGLCHK(k2.alloc((size_t)tot));
+        NBCHK(hipMemcpyAsync(dwork.p, slow.data() + b0, sizeof(int32_t) * (size_t)nw, hipMemcpyHostToDevice, s), "upload");
+        NBCHK(hipMemcpyAsync(dsoff.p, hsoff.data(), sizeof(int32_t) * ((size_t)nw + 1), hipMemcpyHostToDevice, s), "upload");
+        if (NB_DISPATCH(met, lknn_launch_slow_keys, s, a, dwork.p, nw, dsoff.p, k1.p, dnpass.p) != SGL_OK) {
+            sgl_set_error("lknn_slow_keys_kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+            return SGL_EHIP;
+        }
+        size_t tb = 0, tb2 = 0;
+        NBCHK(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, tb, k1.p, k2.p, (int)tot, (int)nw, dsoff.p, dsoff.p + 1, 0, 64, s), "segmented sort");
+        NBCHK(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, tb2, k1.p, k2.p, (int)tot, (int)nw, dsoff.p, dkend.p, 0, 64, s), "segmented sort");
+        DevBuf<char> tmp;
+        SGLCHK(tmp.alloc(std::max(tb, tb2)));
+        NBCHK(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.p, tb, k1.p, k2.p, (int)tot, (int)nw, dsoff.p, dsoff.p + 1, 0, 64, s), "segmented sort");
+        lknn_slow_trim_kernel<<<dim3(grid_for(nw, 1)), dim3(256), 0, s>>>(k2.p, k1.p, dsoff.p, dnpass.p, nw, k, dkend.p);
+        NBCHK(hipGetLastError(), "lknn_slow_trim_kernel");
+        NBCHK(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.p, tb2, k1.p, k2.p, (int)tot, (int)nw, dsoff.p, dkend.p, 0, 64, s), "segmented sort");
+        lknn_slow_write_kernel<<<dim3(grid_for(nw, 1)), dim3(256), 0, s>>>(k2.p, dsoff.p, dkend.p, dwork.p, nw, sidx.p, dtoff.p, ti.p, tx.p,
+                                                                            kept.p, nzc.p);
+        NBCHK(hipGetLastError(), "lknn_slow_write_kernel");
+        NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");   // the batch's buffers go back to the pool
+        b0 = b1;
+    }
+
+    // --- counts, slot overflow, column pointers
+    std::vector<int32_t> hkept((size_t)n), hnz((size_t)n);
+    NBCHK(hipMemcpyAsync(hkept.data(), kept.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download");
+    NBCHK(hipMemcpyAsync(hnz.data(), nzc.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download");
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    std::vector<int64_t> off((size_t)n + 1);
+    off[0] = 0;
+    for (int64_t pt = 0; pt < n; ++pt) {
+        if ((double)hkept[pt] > n_max_edges) {
+            sgl_set_error("c_LKNN: point %lld keeps %d neighbours, more than the %.0f slots per point the reference allocates "
+                          "(ceil((2 * radius + 1)^2) - 1): the reference would write into the next point's slots",
+                          (long long)pt, hkept[pt], n_max_edges);
+            return SGL_EINVAL;
+        }
+        off[pt + 1] = off[pt] + hnz[pt];
+    }
+    const int64_t nnz = off[n];
+    if (nnz > INT32_MAX) { sgl_set_error("c_LKNN: %lld edges do not fit a dgCMatrix", (long long)nnz); return SGL_EINVAL; }
+    for (int64_t pt = 0; pt <= n; ++pt) p_out[pt] = (int32_t)off[pt];
+    *nnz_out = nnz;
+    if (!i_out) return SGL_OK;
+    if (cap < nnz) { sgl_set_error("sgl_c_lknn: output capacity %lld < %lld edges", (long long)cap, (long long)nnz); return SGL_EINVAL; }
+
+    DevBuf<int64_t> doff;
+    DevBuf<int32_t> oi;
+    DevBuf<double> ox;
+    SGLCHK(doff.alloc((size_t)n + 1));
+    SGLCHK(oi.alloc((size_t)nnz));
+    SGLCHK(ox.alloc((size_t)nnz));
+    NBCHK(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload");
+    lknn_compact_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(dtoff.p, kept.p, doff.p, ti.p, tx.p, n, oi.p, ox.p);
+    NBCHK(hipGetLastError(), "lknn_compact_kernel");
+    if (nnz > 0) {
+        NBCHK(hipMemcpyAsync(i_out, oi.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download");
+        NBCHK(hipMemcpyAsync(x_out, ox.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download");
+    }
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    return SGL_OK;
+}
+
+// ----------------------------------------------------------------------------------------------------------------- SNN ---
+namespace {
+
+__global__ void snn_row_hist_kernel(const int32_t* __restrict__ Gi, int64_t nnz, int64_t* __restrict__ rcnt) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += (int64_t)gridDim.x * blockDim.x)
+        atomicAdd((unsigned long long*)&rcnt[Gi[e]], 1ull);
+}
+
+// Row-major pattern: the columns of each row (in no particular order: every use sorts or counts them).
+__global__ void snn_row_fill_kernel(const int32_t* __restrict__ Gi, const int64_t* __restrict__ Gp, int64_t ncol,
+                                    int64_t* __restrict__ cursor, int32_t* __restrict__ Rj) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t c = wave; c < ncol; c += nwaves)
+        for (int64_t e = Gp[c] + lane; e < Gp[c + 1]; e += 64)
+            Rj[atomicAdd((unsigned long long*)&cursor[Gi[e]], 1ull)] = (int32_t)c;
+}
+
+// T[i] = the gathered list length of column i: the sum of its rows' lengths.
+__global__ void snn_gather_len_kernel(const int32_t* __restrict__ Gi, const int64_t* __restrict__ Gp, const int64_t* __restrict__ Rp,
+                                      int64_t ncol, int64_t* __restrict__ T) {
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < ncol; c += (int64_t)gridDim.x * blockDim.x) {
+        int64_t t = 0;
+        for (int64_t e = Gp[c]; e < Gp[c + 1]; ++e) t += Rp[Gi[e] + 1] - Rp[Gi[e]];
+        T[c] = t;
+    }
+}
+
+// Entry (i, j) of the SNN (:1612-1652): the diagonal always, else the Jaccard index of the two columns' row sets, in FP64,
+// kept when strictly above min_similarity.
+__device__ __forceinline__ bool snn_keep(int64_t i, int64_t j, int64_t inter, const int64_t* Gp, double min_sim, double* sim) {
+    if (j == i) { *sim = 1.0; return true; }
+    const int64_t ni = Gp[i + 1] - Gp[i], nj = Gp[j + 1] - Gp[j];
+    *sim = (double)inter / (double)(ni + nj - inter);
+    return *sim > min_sim;
+}
+
+__device__ __forceinline__ void bitonic_lds_u32(uint32_t* s, int P) {
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < P; t += 64) {
+                const int u = t ^ stride;
+                if (u > t) {
+                    const uint32_t x = s[t], y = s[u];
+                    const bool up = (t & size) == 0;
+                    if ((x > y) == up) { s[t] = y; s[u] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// Columns whose gathered list fits LDS, one 64-lane workgroup each: sort the list; a run of j of length L means |rows(i) and
+// rows(j)| = L.  FILL = false: count the entries; FILL = true: write them at off[i], ascending j.
+template <bool FILL>
+__global__ __launch_bounds__(64) void snn_fast_kernel(const int32_t* __restrict__ Gi, const int64_t* __restrict__ Gp,
+                                                      const int64_t* __restrict__ Rp, const int32_t* __restrict__ Rj,
+                                                      const int32_t* __restrict__ work, int64_t nwork, const int64_t* __restrict__ T,
+                                                      double min_sim, int64_t* __restrict__ cnt, const int64_t* __restrict__ off,
+                                                      int32_t* __restrict__ oi, double* __restrict__ ox) {
+    __shared__ uint32_t s[SNN_CAP + 1];
+    const int lane = threadIdx.x;
+    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int64_t i = work[w];
+        const int Tn = (int)T[i];
+        int P = 64;
+        while (P < Tn) P <<= 1;
+        int at = 0;
+        for (int64_t e = Gp[i]; e < Gp[i + 1]; ++e) {
+            const int64_t r0 = Rp[Gi[e]], len = Rp[Gi[e] + 1] - r0;
+            for (int q = lane; q < len; q += 64) s[at + q] = (uint32_t)Rj[r0 + q];
+            at += (int)len;
+        }
+        for (int q = Tn + lane; q < P; q += 64) s[q] = 0xffffffffu;
+        if (lane == 0) s[P] = 0xffffffffu;
+        __syncthreads();
+        bitonic_lds_u32(s, P);
+        int64_t base = FILL ? off[i] : 0;
+        for (int q0 = 0; q0 < Tn; q0 += 64) {
+            const int q = q0 + lane;
+            bool emit = false;
+            double sim = 0.0;
+            uint32_t j = 0;
+            if (q < Tn && (q == 0 || s[q - 1] != s[q])) {
+                j = s[q];
+                int L = 1;
+                while (s[q + L] == j) ++L;   // s[P] is a sentinel; j < ncol
+                emit = snn_keep(i, j, L, Gp, min_sim, &sim);
+            }
+            const uint64_t bal = __ballot(emit);
+            if (FILL && emit) {
+                const int64_t o = base + __popcll(bal & ((1ull << lane) - 1ull));
+                oi[o] = (int32_t)j;
+                ox[o] = sim;
+            }
+            base += __popcll(bal);
+        }
+        if (!FILL && lane == 0) cnt[i] = base;
+        __syncthreads();
+    }
+}
+
+// Columns whose gathered list does not fit LDS (hub rows): one workgroup per column at a time, with a dense counter row of
+// ncol entries per resident workgroup (slot) in HBM.  Counting: atomicAdd per gathered j; then each j is claimed once by
+// atomicExch(.., 0) (which also leaves the counters zero for the next column).  FILL writes the column's entries, unordered,
+// to [soff[w], ...) of a staging list that a segmented sort puts in order.
+template <bool FILL>
+__global__ __launch_bounds__(256) void snn_slow_kernel(const int32_t* __restrict__ Gi, const int64_t* __restrict__ Gp,
+                                                       const int64_t* __restrict__ Rp, const int32_t* __restrict__ Rj,
+                                                       const int32_t* __restrict__ work, int64_t nwork, int64_t ncol,
+                                                       uint32_t* __restrict__ counters, double min_sim, int64_t* __restrict__ cnt,
+                                                       const int64_t* __restrict__ soff, int32_t* __restrict__ si,
+                                                       double* __restrict__ sx) {
+    __shared__ unsigned long long total;
+    uint32_t* my = counters + (size_t)blockIdx.x * (size_t)ncol;
+    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int64_t i = work[w];
+        if (threadIdx.x == 0) total = 0;
+        for (int64_t e = Gp[i]; e < Gp[i + 1]; ++e)
+            for (int64_t q = Rp[Gi[e]] + threadIdx.x; q < Rp[Gi[e] + 1]; q += blockDim.x) atomicAdd(&my[Rj[q]], 1u);
+        __syncthreads();
+        unsigned long long mine = 0;
+        for (int64_t e = Gp[i]; e < Gp[i + 1]; ++e)
+            for (int64_t q = Rp[Gi[e]] + threadIdx.x; q < Rp[Gi[e] + 1]; q += blockDim.x) {
+                const int32_t j = Rj[q];
+                const uint32_t L = atomicExch(&my[j], 0u);
+                double sim;
+                if (L && snn_keep(i, j, L, Gp, min_sim, &sim)) {
+                    if (FILL) {
+                        const unsigned long long o = atomicAdd(&total, 1ull);
+                        si[soff[w] + (int64_t)o] = j;
+                        sx[soff[w] + (int64_t)o] = sim;
+                    } else {
+                        ++mine;
+                    }
+                }
+            }
+        if (!FILL) atomicAdd(&total, mine);
+        __syncthreads();
+        if (!FILL && threadIdx.x == 0) cnt[i] = (int64_t)total;
+        __syncthreads();
+    }
+}
+
+__global__ void snn_scatter_kernel(const int32_t* __restrict__ si, const double* __restrict__ sx, const int64_t* __restrict__ soff,
+                                   const int32_t* __restrict__ work, int64_t nwork, const int64_t* __restrict__ off,
+                                   int32_t* __restrict__ oi, double* __restrict__ ox) {
+    for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
+        const int64_t o = off[work[w]];
+        for (int64_t q = soff[w] + threadIdx.x; q < soff[w + 1]; q += blockDim.x) {
+            oi[o + q - soff[w]] = si[q];
+            ox[o + q - soff[w]] = sx[q];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int sgl_c_snn(const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol, double min_similarity,
+                         int32_t* p_out, int64_t* nnz_out, int32_t* i_out, double* x_out, int64_t cap) {
+    if (!Gp || !p_out || !nnz_out || G_nrow < 0 || G_ncol < 0) { sgl_set_error("sgl_c_snn: bad arguments"); return SGL_EINVAL; }
+    if ((i_out == nullptr) != (x_out == nullptr)) { sgl_set_error("sgl_c_snn: i_out and x_out go together"); return SGL_EINVAL; }
+    const int64_t n = G_ncol;
+    if (Gp[0] != 0) { sgl_set_error("c_SNN: invalid column pointer array (p[0] = %d)", Gp[0]); return SGL_EINVAL; }
+    std::vector<int64_t> hp((size_t)n + 1);
+    for (int64_t c = 0; c <= n; ++c) {
+        if (c > 0 && Gp[c] < Gp[c - 1]) { sgl_set_error("c_SNN: invalid column pointer array: p decreases at column %lld", (long long)(c - 1)); return SGL_EINVAL; }
+        hp[c] = Gp[c];
+    }
+    const int64_t gnnz = hp[n];
+    if (gnnz > 0 && !Gi) { sgl_set_error("sgl_c_snn: bad arguments"); return SGL_EINVAL; }
+
+    CtxHold hd;
+    SGLCHK(sgl_create(current_device(), &hd.c));
+    hipStream_t s = hd.c->stream;
+    DevBuf<int32_t> dGi, Rj, dfast, dslow;
+    DevBuf<int64_t> dGp, Rp, rcnt, T, cnt;
+    DevBuf<int> flag;
+    SGLCHK(dGi.alloc((size_t)gnnz));
+    SGLCHK(dGp.alloc((size_t)n + 1));
+    SGLCHK(flag.alloc(1));
+    if (gnnz > 0) NBCHK(hipMemcpyAsync(dGi.p, Gi, sizeof(int32_t) * (size_t)gnnz, hipMemcpyHostToDevice, s), "upload of G@i");
+    NBCHK(hipMemcpyAsync(dGp.p, hp.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload of G@p");
+    NBCHK(hipMemsetAsync(flag.p, 0, sizeof(int), s), "hipMemsetAsync");
+    SGLCHK(k_validate_csc(s, dGi.p, dGp.p, n, G_nrow, flag.p));
+    int hflag = 0;
+    NBCHK(hipMemcpyAsync(&hflag, flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "download of the flag");
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    if (hflag) {
+        sgl_set_error("c_SNN: G is not a valid dgCMatrix: %s%s", (hflag & 1) ? "row index outside [0, nrow) " : "",
+                      (hflag & 2) ? "row indices not strictly ascending within a column" : "");
+        return SGL_EINVAL;
+    }
+
+    // --- row-major pattern, gathered list lengths
+    const int64_t nr = G_nrow;
+    SGLCHK(rcnt.alloc((size_t)nr + 1));
+    SGLCHK(Rp.alloc((size_t)nr + 1));
+    SGLCHK(Rj.alloc((size_t)gnnz));
+    SGLCHK(T.alloc((size_t)n));
+    SGLCHK(cnt.alloc((size_t)n));
+    NBCHK(hipMemsetAsync(rcnt.p, 0, sizeof(int64_t) * ((size_t)nr + 1), s), "hipMemsetAsync");
+    if (gnnz > 0) {
+        snn_row_hist_kernel<<<dim3(grid_for(gnnz, 256)), dim3(256), 0, s>>>(dGi.p, gnnz, rcnt.p);
+        NBCHK(hipGetLastError(), "snn_row_hist_kernel");
+    }
+    SGLCHK(k_exclusive_scan(hd.c, rcnt.p, Rp.p, nr));
+    SGLCHK(k_scan_total(s, rcnt.p, Rp.p, nr));
+    NBCHK(hipMemcpyAsync(rcnt.p, Rp.p, sizeof(int64_t) * (size_t)nr, hipMemcpyDeviceToDevice, s), "copy");
+    if (n > 0) {
+        snn_row_fill_kernel<<<dim3(grid_for(n, 4)), dim3(256), 0, s>>>(dGi.p, dGp.p, n, rcnt.p, Rj.p);
+        NBCHK(hipGetLastError(), "snn_row_fill_kernel");
+        snn_gather_len_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(dGi.p, dGp.p, Rp.p, n, T.p);
+        NBCHK(hipGetLastError(), "snn_gather_len_kernel");
+    }
+    std::vector<int64_t> hT((size_t)n);
+    if (n > 0) NBCHK(hipMemcpyAsync(hT.data(), T.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download");
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    std::vector<int32_t> fast, slow;
+    std::vector<int64_t> hcnt((size_t)n, 0);
+    for (int64_t c = 0; c < n; ++c) {
+        if (hT[c] == 0) continue;   // empty column: no entries (:1611)
+        if (hT[c] <= SNN_CAP) fast.push_back((int32_t)c);
+        else slow.push_back((int32_t)c);
+    }
+    SGLCHK(dfast.alloc(fast.size()));
+    SGLCHK(dslow.alloc(slow.size()));
+    if (!fast.empty()) NBCHK(hipMemcpyAsync(dfast.p, fast.data(), sizeof(int32_t) * fast.size(), hipMemcpyHostToDevice, s), "upload");
+    if (!slow.empty()) NBCHK(hipMemcpyAsync(dslow.p, slow.data(), sizeof(int32_t) * slow.size(), hipMemcpyHostToDevice, s), "upload");
+    NBCHK(hipMemsetAsync(cnt.p, 0, sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1), s), "hipMemsetAsync");
+    DevBuf<uint32_t> counters;
+    int64_t nslots = 0;
+    if (!slow.empty()) {   // one counter row of ncol per resident workgroup, at most 256 MB of them
+        nslots = std::max<int64_t>(1, std::min<int64_t>({(int64_t)slow.size(), 1024, ((int64_t)1 << 26) / std::max<int64_t>(n, 1)}));
+        SGLCHK(counters.alloc((size_t)(nslots * n)));
+        NBCHK(hipMemsetAsync(counters.p, 0, sizeof(uint32_t) * (size_t)(nslots * n), s), "hipMemsetAsync");
+    }
+
+    // --- count pass
+    if (!fast.empty()) {
+        snn_fast_kernel<false><<<dim3(grid_for((int64_t)fast.size(), 1)), dim3(64), 0, s>>>(
+            dGi.p, dGp.p, Rp.p, Rj.p, dfast.p, (int64_t)fast.size(), T.p, min_similarity, cnt.p, nullptr, nullptr, nullptr);
+        NBCHK(hipGetLastError(), "snn_fast_kernel");
+    }
+    if (!slow.empty()) {
+        snn_slow_kernel<false><<<dim3((unsigned)nslots), dim3(256), 0, s>>>(dGi.p, dGp.p, Rp.p, Rj.p, dslow.p, (int64_t)slow.size(), n,
+                                                                          counters.p, min_similarity, cnt.p, nullptr, nullptr, nullptr);
+        NBCHK(hipGetLastError(), "snn_slow_kernel");
+    }
+    if (n > 0) NBCHK(hipMemcpyAsync(hcnt.data(), cnt.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download");
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    std::vector<int64_t> off((size_t)n + 1);
+    off[0] = 0;
+    for (int64_t c = 0; c < n; ++c) off[c + 1] = off[c] + hcnt[c];
+    const int64_t nnz = off[n];
+    if (nnz > INT32_MAX) {
+        sgl_set_error("c_SNN: the graph would hold %lld entries, which a dgCMatrix (32-bit column pointers) cannot hold; "
+                      "raise min_similarity", (long long)nnz);
+        return SGL_EINVAL;
+    }
+    for (int64_t c = 0; c <= n; ++c) p_out[c] = (int32_t)off[c];
+    *nnz_out = nnz;
+    if (!i_out) return SGL_OK;
+    if (cap < nnz) { sgl_set_error("sgl_c_snn: output capacity %lld < %lld entries", (long long)cap, (long long)nnz); return SGL_EINVAL; }
+
+    // --- fill pass
+    DevBuf<int64_t> doff;
+    DevBuf<int32_t> oi;
+    DevBuf<double> ox;
+    SGLCHK(doff.alloc((size_t)n + 1));
+    SGLCHK(oi.alloc((size_t)nnz));
+    SGLCHK(ox.alloc((size_t)nnz));
+    NBCHK(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload");
+    if (!fast.empty()) {
+        snn_fast_kernel<true><<<dim3(grid_for((int64_t)fast.size(), 1)), dim3(64), 0, s>>>(
+            dGi.p, dGp.p, Rp.p, Rj.p, dfast.p, (int64_t)fast.size(), T.p, min_similarity, nullptr, doff.p, oi.p, ox.p);
+        NBCHK(hipGetLastError(), "snn_fast_kernel");
+    }
+    if (!slow.empty()) {
+        const int64_t ns = (int64_t)slow.size();
+        std::vector<int64_t> hsoff((size_t)ns + 1);
+        hsoff[0] = 0;
+        for (int64_t w = 0; w < ns; ++w) hsoff[w + 1] = hsoff[w] + hcnt[slow[w]];
+        const int64_t stot = hsoff[ns];
+        DevBuf<int64_t> dsoff;
+        DevBuf<int32_t> si, si2;
+        DevBuf<double> sx, sx2;
+        SGLCHK(dsoff.alloc((size_t)ns + 1));
+        SGLCHK(si.alloc((size_t)stot));
+        SGLCHK(si2.alloc((size_t)stot));
+        SGLCHK(sx.alloc((size_t)stot));
+        SGLCHK(sx2.alloc((size_t)stot));
+        NBCHK(hipMemcpyAsync(dsoff.p, hsoff.data(), sizeof(int64_t) * ((size_t)ns + 1), hipMemcpyHostToDevice, s), "upload");
+        snn_slow_kernel<true><<<dim3((unsigned)nslots), dim3(256), 0, s>>>(dGi.p, dGp.p, Rp.p, Rj.p, dslow.p, ns, n, counters.p,
+                                                                         min_similarity, nullptr, dsoff.p, si.p, sx.p);
+        NBCHK(hipGetLastError(), "snn_slow_kernel");
+        size_t tb = 0;
+        NBCHK(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, tb, si.p, si2.p, sx.p, sx2.p, (int)stot, (int)ns, dsoff.p, dsoff.p + 1,
+                                                          0, 32, s), "segmented sort");
+        DevBuf<char> tmp;
+        SGLCHK(tmp.alloc(tb));
+        NBCHK(hipcub::DeviceSegmentedRadixSort::SortPairs(tmp.p, tb, si.p, si2.p, sx.p, sx2.p, (int)stot, (int)ns, dsoff.p, dsoff.p + 1,
+                                                          0, 32, s), "segmented sort");
+        snn_scatter_kernel<<<dim3(grid_for(ns, 1)), dim3(256), 0, s>>>(si2.p, sx2.p, dsoff.p, dslow.p, ns, doff.p, oi.p, ox.p);
+        NBCHK(hipGetLastError(), "snn_scatter_kernel");
+        NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    }
+    if (nnz > 0) {
+        NBCHK(hipMemcpyAsync(i_out, oi.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download");
+        NBCHK(hipMemcpyAsync(x_out, ox.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download");
+    }
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    return SGL_OK;
+}

@@ -38,6 +38,11 @@ singlet_hip_enable <- function(shim = Sys.getenv("SINGLET_HIP_SHIM", "singlet_hi
     .Call(dll[["_singlet_c_project_model"]], A, w, L1, L2, threads))
   rebind("Rcpp_predict", function(A, w, L1, L2, threads)
     .Call(dll[["_singlet_Rcpp_predict"]], A, w, L1, L2, threads))
+  # R/FindLocalNeighbors.R:95-98 builds the spatial graphs with these two (R/RcppExports.R: c_LKNN, c_SNN)
+  rebind("c_LKNN", function(m, coord_x, coord_y, k, radius, metric, similarity, max_dist, verbose, threads)
+    .Call(dll[["_singlet_c_LKNN"]], m, coord_x, coord_y, k, radius, metric, similarity, max_dist, verbose, threads))
+  rebind("c_SNN", function(G, min_similarity, threads)
+    .Call(dll[["_singlet_c_SNN"]], G, min_similarity, threads))
   # R/RunNMF.R:86-93 re-weights the matrix by group before the fit (R/RcppExports.R: weight_by_split(A_, split_by, n_groups))
   rebind("weight_by_split", function(A_, split_by, n_groups)
     .Call(dll[["_singlet_weight_by_split"]], A_, split_by, n_groups))

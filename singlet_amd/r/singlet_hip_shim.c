@@ -1,5 +1,6 @@
 /*
- * singlet_hip_shim.c -- the only R-aware C file of the HIP back end.
+ * singlet_hip_shim.c -- the R-aware C layer of the HIP back end (with singlet_hip_graph_shim.c, the bodies of the
+ * two spatial neighbour-graph entries it registers).
  *
  * It provides .Call entry points with the SAME names and arity as the Rcpp glue
  * of the reference (src/RcppExports.cpp:98-116 _singlet_c_nmf,
@@ -13,7 +14,8 @@
  *
  * NOT COMPILED IN THIS REPOSITORY'S CI: the build image has neither R nor its
  * headers.  Build where R exists with
- *     R CMD SHLIB singlet_hip_shim.c -I<repo>/include -L<repo>/singlet_amd -lsinglet_hip
+ *     R CMD SHLIB -o singlet_hip_shim.so singlet_hip_shim.c singlet_hip_graph_shim.c -I<repo>/include \
+ *         -L<repo>/singlet_amd -lsinglet_hip
  * (or add the file to the package's src/ and the two flags to src/Makevars;
  * see INTEGRATION.md).  All numerical testing of the library goes through the
  * same C ABI from Python (tests/).
@@ -427,6 +429,10 @@ SEXP _singlet_c_gcnmf(SEXP A_, SEXP At_, SEXP G_, SEXP tol_, SEXP maxit_, SEXP v
     return out;
 }
 
+/* the spatial neighbour graphs: bodies in singlet_hip_graph_shim.c (src/RcppExports.cpp:466-467) */
+SEXP _singlet_c_LKNN(SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP);
+SEXP _singlet_c_SNN(SEXP, SEXP, SEXP);
+
 static const R_CallMethodDef call_entries[] = {
     {"_singlet_weight_by_split", (DL_FUNC)&_singlet_weight_by_split, 3},
     {"_singlet_c_nmf", (DL_FUNC)&_singlet_c_nmf, 11},
@@ -439,6 +445,8 @@ static const R_CallMethodDef call_entries[] = {
     {"_singlet_c_ard_nmf_dense", (DL_FUNC)&_singlet_c_ard_nmf_dense, 13},
     {"_singlet_c_project_model", (DL_FUNC)&_singlet_c_project_model, 5},
     {"_singlet_Rcpp_predict", (DL_FUNC)&_singlet_Rcpp_predict, 5},
+    {"_singlet_c_LKNN", (DL_FUNC)&_singlet_c_LKNN, 10},
+    {"_singlet_c_SNN", (DL_FUNC)&_singlet_c_SNN, 3},
     {NULL, NULL, 0}};
 
 void R_init_singlet_hip_shim(DllInfo* dll) {
