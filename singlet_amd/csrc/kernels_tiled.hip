@@ -640,38 +640,8 @@ __device__ __forceinline__ void tiled_stage(double* __restrict__ tile, const dou
                 if (c16 + 16 < k) tile[r * 32 + c16 + 16] = src[(int64_t)r * ldf + c16 + 16];
             }
         }
-    } else if (KS == k && ldf == k) {
-        // Each thread moves up to NRND * RST 16-byte pieces of the (contiguous) tile in NRND rounds of
-        // RST loads in flight.  The loads of the first round are issued before the barrier: they overlap
-        // the tail of the previous chunk's work of the other waves.
-        constexpr int RST = 8;
-        constexpr int NRND = (TILED_LDS_BYTES / 32 + RST * 64 * TILED_NW - 1) / (RST * 64 * TILED_NW);
-        static_assert(NRND * RST * 64 * TILED_NW * 16 >= TILED_LDS_BYTES / 2, "staging must cover a whole ring slot");
-        double2 stg[RST];
-#pragma unroll
-        for (int j = 0; j < RST; ++j) {
-            const int e = ((int)threadIdx.x + j * 64 * TILED_NW) * 2;
-            stg[j] = double2{0.0, 0.0};
-            if (e < n) stg[j] = *reinterpret_cast<const double2*>(src + e);
-        }
-        if (sync) __syncthreads();  // everyone is done with what the slot held
-#pragma unroll
-        for (int rd = 0; rd < NRND; ++rd) {
-#pragma unroll
-            for (int j = 0; j < RST; ++j) {
-                const int e = ((int)threadIdx.x + (rd * RST + j) * 64 * TILED_NW) * 2;
-                if (e < n) *reinterpret_cast<double2*>(tile + e) = stg[j];
-            }
-            if (rd + 1 < NRND) {
-#pragma unroll
-                for (int j = 0; j < RST; ++j) {
-                    const int e = ((int)threadIdx.x + ((rd + 1) * RST + j) * 64 * TILED_NW) * 2;
-                    stg[j] = double2{0.0, 0.0};
-                    if (e < n) stg[j] = *reinterpret_cast<const double2*>(src + e);
-                }
-            }
-        }
     } else {
+        // (pair layout with KS == k == ldf: tiled_issue / tiled_commit below, from the stage loop of acc_tiled_kernel)
         // odd k: rows are re-pitched to KS = k + 1 doubles (the pad column is never summed into a
         // stored factor row: lane 2l+1 == k is not written out)
         if (sync) __syncthreads();
@@ -693,18 +663,89 @@ __device__ __forceinline__ void tiled_stage(double* __restrict__ tile, const dou
     }
 }
 
+// Pair layout with KS == k == ldf (even ranks 34 - 64: both passes of config 3).  A row block is n = rows * k contiguous
+// doubles, moved by the workgroup as 16-byte pieces: piece j of thread t is doubles 2 (t + 512 j), 2 (t + 512 j) + 1, so a
+// ring slot (at most TILED_LDS_BYTES / 2 bytes) is at most TILED_PIECES pieces per thread -- 40 registers.
+// The stage loop splits the move in two: tiled_issue loads a thread's pieces of block b + 2 into registers BEFORE the chunk
+// of stage b (the last reader of the slot the block goes to), and they stay in flight while it runs; tiled_commit writes them
+// into the slot between the two barriers after it.  Both are inline asm, because hipcc cannot count these loads right: the
+// chunk issues ring refills behind them (loads the compiler does not see), and its own wait before the writes -- vmcnt(9 - j)
+// for piece j -- would drain the ring's refills at every edge.  Loads retire in issue order: after a chunk of s >= 4 sets the
+// chunk's refills (two loads per half-set slot: 4 s >= 16) are all younger than the pieces, so vmcnt(16) covers every piece
+// and leaves a whole ring lap in flight; after a shorter chunk (or none) vmcnt(0).  (The chunk's own counted ring waits stay
+// correct with the pieces in flight: older loads only make them wait longer.)
+// Every piece is loaded (a piece past the block reads the block's last one, clamped), so the count is static; the writes of
+// pieces past the block are masked off.
+#define TILED_PIECES 10
+static_assert(TILED_PIECES * 64 * TILED_NW * 16 >= TILED_LDS_BYTES / 2, "the pieces must cover a whole ring slot");
+// The pieces sit in v[24:63] from the issue to the commit, OUTSIDE hipcc's allocation (acc_tiled_kernel<2> caps it at v0..v23):
+// hipcc must never copy, spill or reuse a register whose load is still in flight, and it cannot know that it is.
+#define TILED_PIECE_CLOBBERS "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", "v38", \
+    "v39", "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", \
+    "v58", "v59", "v60", "v61", "v62", "v63"
+
+#define TILED_ISSUE_PIECE(regs, off) \
+    "v_add_u32 %[t], " off ", %[o]\n\tv_min_u32 %[t], %[last], %[t]\n\tglobal_load_dwordx4 " regs ", %[t], %[src]\n\t"
+
+// thread's pieces of the block at src (n doubles, 16-byte aligned) -> v[24:63]; returns at once
+__device__ __forceinline__ void tiled_issue(const double* src, int n) {
+    static_assert(TILED_PIECES == 10, "tiled_issue / tiled_commit move ten pieces");
+    const unsigned o = threadIdx.x * 16u, last = (unsigned)n * 8u - 16u;
+    unsigned t;
+    asm volatile(
+        "v_min_u32 %[t], %[last], %[o]\n\tglobal_load_dwordx4 v[24:27], %[t], %[src]\n\t"
+        TILED_ISSUE_PIECE("v[28:31]", "0x2000") TILED_ISSUE_PIECE("v[32:35]", "0x4000") TILED_ISSUE_PIECE("v[36:39]", "0x6000")
+        TILED_ISSUE_PIECE("v[40:43]", "0x8000") TILED_ISSUE_PIECE("v[44:47]", "0xa000") TILED_ISSUE_PIECE("v[48:51]", "0xc000")
+        TILED_ISSUE_PIECE("v[52:55]", "0xe000") TILED_ISSUE_PIECE("v[56:59]", "0x10000") TILED_ISSUE_PIECE("v[60:63]", "0x12000")
+        : [t] "=&v"(t)
+        : [o] "v"(o), [last] "s"(last), [src] "s"(src)
+        : TILED_PIECE_CLOBBERS);
+}
+
+// piece j at LDS byte a (+ 8192 j; past the 16-bit offset field from a1 = a + 65536) if a + 8192 j < lim, else masked off
+#define TILED_COMMIT_PIECE(regs, addr, off) \
+    "v_cmp_gt_i32 vcc, %[lim], %[a]\n\ts_and_b64 exec, exec, vcc\n\tds_write_b128 " addr ", " regs off "\n\ts_sub_i32 %[lim], %[lim], 0x2000\n\t"
+#define TILED_COMMIT_ASM(wait) \
+    "s_waitcnt vmcnt(" wait ")\n\ts_mov_b64 %[sv], exec\n\t" \
+    TILED_COMMIT_PIECE("v[24:27]", "%[a]", "") TILED_COMMIT_PIECE("v[28:31]", "%[a]", " offset:8192") \
+    TILED_COMMIT_PIECE("v[32:35]", "%[a]", " offset:16384") TILED_COMMIT_PIECE("v[36:39]", "%[a]", " offset:24576") \
+    TILED_COMMIT_PIECE("v[40:43]", "%[a]", " offset:32768") TILED_COMMIT_PIECE("v[44:47]", "%[a]", " offset:40960") \
+    TILED_COMMIT_PIECE("v[48:51]", "%[a]", " offset:49152") TILED_COMMIT_PIECE("v[52:55]", "%[a]", " offset:57344") \
+    TILED_COMMIT_PIECE("v[56:59]", "%[a1]", "") TILED_COMMIT_PIECE("v[60:63]", "%[a1]", " offset:8192") \
+    "s_mov_b64 exec, %[sv]\n\ts_waitcnt lgkmcnt(0)"
+#define TILED_COMMIT_OPERANDS : [sv] "=&s"(sv), [lim] "+s"(lim) : [a] "v"(a), [a1] "v"(a + 65536u) : "vcc", "scc", "memory"
+
+// v[24:63] -> the ring slot at tile (n doubles of the block); the LDS writes have landed on return.  ring_after: a chunk of at
+// least four sets ran since tiled_issue (above)
+__device__ __forceinline__ void tiled_commit(double* tile, int n, bool ring_after) {
+    typedef __attribute__((address_space(3))) char lds_char;
+    const unsigned base = (unsigned)(uintptr_t)(lds_char*)tile;
+    const unsigned a = base + threadIdx.x * 16u;
+    int lim = (int)(base + (unsigned)n * 8u);
+    uint64_t sv;
+    if (ring_after)
+        asm volatile(TILED_COMMIT_ASM("16") TILED_COMMIT_OPERANDS);
+    else
+        asm volatile(TILED_COMMIT_ASM("0") TILED_COMMIT_OPERANDS);
+}
+
 // The chunk loop is the hand-scheduled inline asm of gen_acc_tiled.py (register plan there).  The compiler's budget
 // is v0..v63 (amdgpu_waves_per_eu(8, 8) caps its allocation at 512 / 8 registers); the clobber makes the kernel
 // descriptor allocate all 256: v64..v255 belong to the asm, whose stream ring stays in flight across compiler code.
+// The pair instance gives hipcc v0..v23 only: v24..v63 hold tiled_issue's pieces across the chunk.
 // NSL = 2: pairs of columns on half-set ring slots loaded with doubled lane rows (parts of 33 - 64 factors);  NSL = 4: quads
 // of columns (parts up to 32).  Both walk the schedule table gtab.
+#define ACC_TILED_PARAMS                                                                                                          \
+    const uint32_t* __restrict__ sroff, const double* __restrict__ sx, const int64_t* __restrict__ cstart,                            \
+        const uint8_t* __restrict__ cnt, int T, int NB, int64_t nwb, const double* __restrict__ F, int k, int TR, int64_t nrow,       \
+        int tiles_per_range, double* __restrict__ Bout, int64_t ncol, int KS, int ldf, int ldb, int64_t slab,                        \
+        const int32_t* __restrict__ perm, int range_fastest, const uint16_t* __restrict__ gtab, int tail_wg0, int tail_R,            \
+        double* __restrict__ tail_part, int64_t tail_slab
+#define ACC_TILED_ARGS \
+    sroff, sx, cstart, cnt, T, NB, nwb, F, k, TR, nrow, tiles_per_range, Bout, ncol, KS, ldf, ldb, slab, perm, range_fastest, gtab, \
+        tail_wg0, tail_R, tail_part, tail_slab
 template <int NSL>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void acc_tiled_kernel(
-    const uint32_t* __restrict__ sroff, const double* __restrict__ sx, const int64_t* __restrict__ cstart,
-    const uint8_t* __restrict__ cnt, int T, int NB, int64_t nwb, const double* __restrict__ F, int k, int TR, int64_t nrow,
-    int tiles_per_range, double* __restrict__ Bout, int64_t ncol, int KS, int ldf, int ldb, int64_t slab,
-    const int32_t* __restrict__ perm, int range_fastest, const uint16_t* __restrict__ gtab, int tail_wg0, int tail_R,
-    double* __restrict__ tail_part, int64_t tail_slab) {
+__device__ __forceinline__ void acc_tiled_body(ACC_TILED_PARAMS) {
     // k = factor rows handled by this launch (a part of the rank when it is above 64), KS = LDS row
     // stride the stream's offsets were built for, ldf / ldb = strides (doubles) between rows of F /
     // columns of the output, slab = doubles between the outputs of two tile ranges (blockIdx.y).
@@ -778,6 +819,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         for (int e = (int)threadIdx.x; e < TILED_LDS_BYTES / 8; e += 64 * TILED_NW) tile[e] = 0.0;
     }
 
+    // pair layout, rows of F contiguous: block b + 2 is loaded while the chunk of stage b runs (tiled_issue)
+    const bool pf = NSL == 2 && KS == k && ldf == k;
+    auto block_rows = [&](int j) { const int64_t row0 = (int64_t)j * D; return (int)(nrow - row0 < D ? nrow - row0 : D); };
     int64_t pos_cur = wact ? cstart[wb * NB + b0] : 0;
     for (int b = b0; b < b1; ++b) {
         const int nsets = (int)((pos_next - pos_cur) >> 6);  // 64-entry sets (32 per half) of this chunk
@@ -787,18 +831,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 
         // stage b reads blocks b and b + 1: the range's first stage stages both, every later one block b + 1 into the slot
         // block b - 1 held (the chunk of stage b - 1 was its last reader)
-        // (one call site: the staging's registers come out of the compiler's 64)
+        if (pf) {
+            if (b == b0) {
 #pragma clang loop unroll(disable)
-        for (int j = b == b0 ? b : b + 1; j <= b + 1 && j < b1; ++j) {
-            const int64_t row0 = (int64_t)j * D;
-            tiled_stage<NSL>(tile + (j & 1) * D * KS, F + row0 * ldf, (int)(nrow - row0 < D ? nrow - row0 : D), k, KS, ldf, j == b || b != b0);
-        }
-        // all staging loads (and the ring loads in front of them) have landed: the asm's counted vmcnt waits see
-        // only its own ring loads in flight.  (The range's last stage stages nothing: its blocks landed behind the
-        // barrier of the stage before.)
-        if (b == b0 || b + 1 < b1) {
-            __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-            __syncthreads();
+                for (int j = b; j <= b + 1 && j < b1; ++j) {
+                    tiled_issue(F + (int64_t)j * D * ldf, block_rows(j) * k);
+                    tiled_commit(tile + (j & 1) * D * KS, block_rows(j) * k, false);
+                }
+                __syncthreads();
+            }
+            if (b + 2 < b1) tiled_issue(F + (int64_t)(b + 2) * D * ldf, block_rows(b + 2) * k);
+        } else {
+            // (one call site: the staging's registers come out of the compiler's budget)
+#pragma clang loop unroll(disable)
+            for (int j = b == b0 ? b : b + 1; j <= b + 1 && j < b1; ++j) {
+                const int64_t row0 = (int64_t)j * D;
+                tiled_stage<NSL>(tile + (j & 1) * D * KS, F + row0 * ldf, block_rows(j), k, KS, ldf, j == b || b != b0);
+            }
+            // all staging loads (and the ring loads in front of them) have landed: the asm's counted vmcnt waits see
+            // only its own ring loads in flight.  (The range's last stage stages nothing: its blocks landed behind the
+            // barrier of the stage before.)
+            if (b == b0 || b + 1 < b1) {
+                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+                __syncthreads();
+            }
         }
         if (wact && nsets > 0) {
             // first schedule word of this chunk (wave-uniform address)
@@ -814,6 +870,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                              : [rp] "+s"(rp), [xp] "+s"(xp), [phase] "+s"(phase)
                              : [ns] "s"(nsets), [tp] "s"(tp), [lane16] "v"(lane16), [voff4] "v"(voff4), [voff8] "v"(voff8), [pfl] "v"(pfl)
                              : ACC_TILED_CHUNK_CLOBBERS);
+        }
+        if (pf && b + 2 < b1) {
+            __syncthreads();   // every wave is done with block b: its slot takes block b + 2
+            tiled_commit(tile + (b & 1) * D * KS, block_rows(b + 2) * k, wact && nsets >= 4);
+            __syncthreads();
         }
     }
     // Up to eight refills (issued past the end of this wave's range, into the stream's slack) are still in flight;
@@ -841,6 +902,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             }
         }
     }
+}
+
+template <int NSL>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void acc_tiled_kernel(ACC_TILED_PARAMS) {
+    acc_tiled_body<NSL>(ACC_TILED_ARGS);
+}
+// the pair instance: v24..v63 hold tiled_issue's pieces across the chunk, hipcc gets v0..v23.  (On gfx950 amdgpu_num_vgpr counts
+// the unified register file, arch + accumulation registers: 12 here caps the arch registers at 24.)
+template <>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8), amdgpu_num_vgpr(12))) void acc_tiled_kernel<2>(ACC_TILED_PARAMS) {
+    acc_tiled_body<2>(ACC_TILED_ARGS);
 }
 
 // B[col * ldb + f] = sum over the R tile-range slabs (compact k x ncol each, fixed order)
