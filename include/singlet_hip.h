@@ -24,8 +24,9 @@
  *  - all arithmetic on the path is FP64 on the GPU; there is no CPU fallback:
  *    without a usable gfx950 device every entry point fails with SGL_ENODEV.
  *    The two neighbour-graph entries are the exception, as in the reference:
- *    sgl_c_lknn is FP32 (its distances are floats, returned as doubles) and
- *    sgl_c_snn is integer counting with one FP64 quotient per entry.
+ *    sgl_c_lknn is FP32 (its distances are floats, returned as doubles),
+ *    sgl_c_snn is integer counting with one FP64 quotient per entry, and
+ *    sgl_spatial_graph is FP64 as the reference.
  *  - ranks: every entry point takes 1 <= k <= 1024 (SGL_EINVAL above, before anything is uploaded; the
  *    reference's nnls / predict_mask have no limit, src/singlet.cpp:229-250, 436-466).  The tuned kernels cover
  *    k <= 128 (LDS-tiled accumulate, MFMA Grams and Gram downdates, lane NNLS); the plain fit runs ranks 129 - 256 on the
@@ -251,6 +252,37 @@ SGL_API int sgl_c_lknn(const double* m, int32_t m_rows, int32_t m_cols,
 SGL_API int sgl_c_snn(const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol,
                       double min_similarity,
                       int32_t* p_out, int64_t* nnz_out, int32_t* i_out, double* x_out, int64_t cap);
+
+/* spatial_graph (src/singlet.cpp:1365-1414; glue _singlet_spatial_graph, 5
+ * args), the distance-weighted cell graph that GCNMF convolves with.  n points
+ * (c1[e], c2[e]), FP64.  For each point i the points j = 0, 1, ... are scanned
+ * in INDEX order and j is kept when d = sqrt((c1[i]-c1[j])^2 + (c2[i]-c2[j])^2)
+ * < max_dist (double, strict, no contraction), until max_k are kept: the
+ * selection is by index, not by distance, and i itself (d = 0) is kept when it
+ * falls among the first max_k.  Weight (max_dist - d) * scale, scale =
+ * 1 / max_dist rounded once (the reference's product and reciprocal); each
+ * column divided by its sum.  Output: the n x n dgCMatrix, column i = the
+ * points kept by i, rows ascending.  This build's rules where the reference is
+ * undefined or unsound:
+ *  - refused (SGL_EINVAL, with a message): a non-finite coordinate (the
+ *    reference writes max_k NaN entries of row 0), max_dist not finite and > 0
+ *    or 1 / max_dist not finite (NaN columns), max_k < 0, and an output of 2^31
+ *    entries or more (refused after the count pass, before anything is
+ *    allocated for it).  c1 and c2 of different lengths (the reference reads
+ *    past c2) are refused by the Python and R layers, which see both lengths.
+ *    With these refused every column holds at least its own point and a sum
+ *    > 0, and no weight is 0, so every kept point is an entry.
+ *  - max_k = 0 and n = 0 give the empty n x n graph (p all 0); max_k > n acts
+ *    as n, and nothing of max_k x n is ever allocated.
+ *  - the column sum is sequential, in ascending row order (the reference's
+ *    Eigen sum() is a vectorised reduction whose order depends on the Eigen
+ *    version, the SIMD width and the column's alignment).
+ *  - bit-exact: the pattern (p, i) and the weights before the division; the
+ *    normalised x with the sequential sum above, and within max_k ulps
+ *    (relative) of any other summation order.  Deterministic, bit for bit.
+ * Same two-call contract as sgl_c_lknn.  One device: the current one. */
+SGL_API int sgl_spatial_graph(const double* c1, const double* c2, int32_t n, double max_dist, int64_t max_k,
+                              int32_t* p_out, int64_t* nnz_out, int32_t* i_out, double* x_out, int64_t cap);
 
 /* c_project_model (src/singlet.cpp:405-413).
  * Replaces _singlet_c_project_model (src/RcppExports.cpp:444-447 region).

@@ -823,7 +823,7 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
 # Spatial neighbour graphs (FindLocalNeighbors / RescaleSpatial)
 # ---------------------------------------------------------------------------
 def _two_call(fn, n):
-    """Run a two-call sgl_c_lknn / sgl_c_snn entry: counts first, then the slots."""
+    """Run a two-call sgl_c_lknn / sgl_c_snn / sgl_spatial_graph entry: counts first, then the slots."""
     p = np.empty(n + 1, dtype=np.int32)
     nnz = C.c_int64()
     check(fn(ptr(p, i32p), C.byref(nnz), None, None, 0))
@@ -879,6 +879,25 @@ def c_SNN(G, min_similarity, threads):
     p, i, x = _two_call(lambda po, no, io, xo, cap: L.sgl_c_snn(ptr(G.i, i32p), ptr(G.p, i32p), G.nrow, G.ncol,
                                                                 float(min_similarity), po, no, io, xo, cap), n)
     return dgCMatrix(x, i, p, (n, n))
+
+
+def spatial_graph(c1, c2, max_dist, max_k=100, threads=0):
+    """spatial_graph(c1, c2, max_dist, max_k, threads) (src/singlet.cpp:1365-1414) -> the n x n dgCMatrix whose column i
+    holds, of the points within max_dist of point i (strict), the max_k lowest-numbered ones (i itself included), weighted
+    (max_dist - d) * (1 / max_dist) and normalised to sum 1.  The selection is by index, not by distance.  Refusals, the column
+    sum's order and what is bit-exact: include/singlet_hip.h, sgl_spatial_graph.  `threads` is ignored."""
+    L = _lib.load()
+    x = np.ascontiguousarray(c1, dtype=np.float64).ravel()
+    y = np.ascontiguousarray(c2, dtype=np.float64).ravel()
+    if x.size != y.size:   # the reference reads past the shorter one
+        raise _lib.SingletHipError(-1, "spatial_graph: c1 (%d) and c2 (%d) differ in length" % (x.size, y.size))
+    if x.size > 2**31 - 1:
+        raise _lib.SingletHipError(-1, "spatial_graph: %d points do not fit a dgCMatrix" % x.size)
+    n = int(x.size)
+    k = min(int(max_k), 2**63 - 1)   # truncates toward zero; above n it acts as n
+    p, i, v = _two_call(lambda po, no, io, xo, cap: L.sgl_spatial_graph(ptr(x, f64p), ptr(y, f64p), n, float(max_dist), k,
+                                                                          po, no, io, xo, cap), n)
+    return dgCMatrix(v, i, p, (n, n))
 
 
 def rescale_spatial(coords):

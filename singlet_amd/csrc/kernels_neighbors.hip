@@ -937,3 +937,302 @@ extern "C" int sgl_c_snn(const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, i
     NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
     return SGL_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------- spatial_graph ---
+// spatial_graph (src/singlet.cpp:1365-1414): for every point i, the points j = 0, 1, ... in INDEX order with
+// d = sqrt((c1[i]-c1[j])^2 + (c2[i]-c2[j])^2) < max_dist (double, no contraction), up to max_k of them, weighted
+// (max_dist - d) * (1 / max_dist) and divided by the column's sum.  The selection is by index, not by distance, and the
+// reference stops scanning at the max_k-th accepted point.  Here a cell list bounds the candidates to the 3 x 3 buckets of
+// a point; each bucket's members stay in ascending index order (stable sort), and one 64-lane workgroup per point visits the
+// nine lists as a merge in ascending index, in batches: T = the smallest "64th remaining index" over the nine lists, and a
+// batch is every remaining candidate <= T (at most 64 per list, at least 64 in all unless the lists run out).  The accepted
+// ones of a batch are ranked by index across the lists (binary searches in LDS) and taken in that order until max_k.  The
+// early stop keeps the all-in-range case (max_dist above the data's extent) at O(n max_k), as the reference's loop is.
+// Count pass (per point: kept entries, and the column sum, sequential in ascending row order), a host scan, fill pass.
+namespace {
+
+constexpr int SG_LISTS = 9;
+
+struct SgArgs {
+    const double* sx;        // coordinates at each sorted position
+    const double* sy;
+    const uint32_t* sidx;    // point at each sorted position
+    const int32_t* bnd;      // 12 per sorted position: for rows by-1 .. by+1, the sorted positions where buckets bx-1 .. bx+2 start
+    int64_t n;
+    double max_dist, scale;  // scale = 1 / max_dist, rounded once on the host (the reference's scale_factor)
+    int64_t K;               // min(max_k, n) >= 1
+};
+
+// Bucket key of every point, in double: by * W + bx, b = floor((c - cmin) / side); one bucket when W = H = 1 (an extent that
+// overflows).  See sgl_spatial_graph for why this is conservative.
+__global__ void sg_keys_kernel(const double* __restrict__ c1, const double* __restrict__ c2, int64_t n, double xmin, double ymin,
+                               double side, int64_t W, int64_t H, uint64_t* __restrict__ keys, uint32_t* __restrict__ iota) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        int64_t bx = 0, by = 0;
+        if (W > 1) {   // the host's W, H hold every point: the clamps never bind
+            bx = std::min<int64_t>((int64_t)floor((c1[e] - xmin) / side), W - 1);
+            by = std::min<int64_t>((int64_t)floor((c2[e] - ymin) / side), H - 1);
+        }
+        keys[e] = (uint64_t)(by * W + bx);
+        iota[e] = (uint32_t)e;
+    }
+}
+
+// Coordinates in sorted order, and the bucket boundaries of the 3 x 3 neighbourhood of each sorted position.
+__global__ void sg_ranges_kernel(const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ sidx, const double* __restrict__ c1,
+                                 const double* __restrict__ c2, int64_t n, int64_t W, int64_t H, double* __restrict__ sx,
+                                 double* __restrict__ sy, int32_t* __restrict__ bnd) {
+    for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t pt = sidx[pos];
+        sx[pos] = c1[pt];
+        sy[pos] = c2[pt];
+        const int64_t key = (int64_t)skeys[pos], by = key / W, bx = key % W;
+        for (int q = 0; q < 3; ++q) {
+            const int64_t yy = by - 1 + q;
+            for (int r = 0; r < 4; ++r) {
+                int64_t b = 0;
+                if (yy >= 0 && yy < H) b = lower_bound_u64(skeys, n, (uint64_t)(yy * W + std::min<int64_t>(std::max<int64_t>(bx - 1 + r, 0), W)));
+                bnd[pos * 12 + q * 4 + r] = (int32_t)b;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+    for (int m = 32; m > 0; m >>= 1) v = std::min(v, (uint32_t)__shfl_xor((int)v, m));
+    return v;
+}
+
+__device__ __forceinline__ double readlane_f64(double v, int l) {
+    const uint64_t u = __double_as_longlong(v);
+    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, l), hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), l);
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// One 64-lane workgroup per point, in sorted (spatial) order.  FILL = false: cnt[pt] = the kept entries, colsum[pt] = their
+// weights summed in ascending row order.  FILL = true: rows and weights / colsum[pt] at off[pt], ascending rows.
+template <bool FILL>
+__global__ __launch_bounds__(64) void sg_merge_kernel(SgArgs a, int32_t* __restrict__ cnt, double* __restrict__ colsum,
+                                                      const int32_t* __restrict__ off, int32_t* __restrict__ oi, double* __restrict__ ox) {
+    __shared__ uint32_t aj[SG_LISTS * 64];   // accepted indices of the batch, list b's at [64 b, 64 b + acnt[b]), ascending
+    __shared__ double aw[SG_LISTS * 64];     // their weights
+    __shared__ uint16_t order[SG_LISTS * 64];   // slot of aj / aw at each rank (ascending index) of the batch
+    __shared__ int acnt[SG_LISTS];
+    const int lane = threadIdx.x;
+    for (int64_t pos = blockIdx.x; pos < a.n; pos += gridDim.x) {
+        const uint32_t pt = a.sidx[pos];
+        const double px = a.sx[pos], py = a.sy[pos];
+        int cur = 0, end = 0;   // lane b < 9: the remaining run [cur, end) of list b
+        if (lane < SG_LISTS) {
+            const int32_t* bb = a.bnd + pos * 12 + (lane / 3) * 4 + lane % 3;
+            cur = bb[0];
+            end = bb[1];
+        }
+        int64_t acc = 0;
+        double sum = FILL ? colsum[pt] : 0.0;
+        const int64_t base = FILL ? off[pt] : 0;
+        while (acc < a.K) {
+            if (__ballot(cur < end) == 0) break;   // every list exhausted
+            const uint32_t T = wave_min_u32((lane < SG_LISTS && end - cur >= 64) ? a.sidx[cur + 63] : 0xffffffffu);
+            int took = 0;   // lane b < 9: the candidates of list b this batch consumes
+            for (int b = 0; b < SG_LISTS; ++b) {
+                const int cb = __shfl(cur, b), eb = __shfl(end, b);
+                int na = 0;
+                if (cb < eb) {
+                    const int e = cb + lane;
+                    bool in = false, ok = false;
+                    uint32_t j = 0;
+                    double w = 0.0;
+                    if (e < eb) {
+                        j = a.sidx[e];
+                        in = j <= T;   // a prefix of the list's remaining run
+                        if (in) {
+                            const double dx = px - a.sx[e], dy = py - a.sy[e];
+                            const double d = __builtin_sqrt(dx * dx + dy * dy);
+                            ok = d < a.max_dist;
+                            w = (a.max_dist - d) * a.scale;
+                        }
+                    }
+                    const uint64_t bok = __ballot(ok);
+                    if (ok) {
+                        const int slot = b * 64 + __popcll(bok & ((1ull << lane) - 1ull));
+                        aj[slot] = j;
+                        aw[slot] = w;
+                    }
+                    na = __popcll(bok);
+                    const int nin = __popcll(__ballot(in));
+                    if (lane == b) took = nin;
+                }
+                if (lane == 0) acnt[b] = na;
+            }
+            __syncthreads();
+            int A = 0;
+            for (int b = 0; b < SG_LISTS; ++b) A += acnt[b];
+            if (A > 0) {
+                // rank of each accepted candidate among the batch's: its place in its own list plus, in every other list, the
+                // number of accepted indices below it (the indices are distinct: a point lies in one bucket)
+                for (int e = lane; e < SG_LISTS * 64; e += 64) {
+                    const int b = e >> 6, q = e & 63;
+                    if (q < acnt[b]) {
+                        const uint32_t j = aj[e];
+                        int r = q;
+                        for (int o = 0; o < SG_LISTS; ++o) {
+                            if (o == b) continue;
+                            int lo = 0, hi = acnt[o];
+                            while (lo < hi) {
+                                const int mid = (lo + hi) >> 1;
+                                if (aj[o * 64 + mid] < j) lo = mid + 1;
+                                else hi = mid;
+                            }
+                            r += lo;
+                        }
+                        order[r] = (uint16_t)e;
+                    }
+                }
+                __syncthreads();
+                const int take = (int)std::min<int64_t>(A, a.K - acc);
+                for (int r0 = 0; r0 < take; r0 += 64) {
+                    const int r = r0 + lane;
+                    if (FILL) {
+                        if (r < take) {
+                            const int e = order[r];
+                            oi[base + acc + r] = (int32_t)aj[e];
+                            ox[base + acc + r] = aw[e] / sum;
+                        }
+                    } else {   // the column sum, one weight after the other in ascending row order
+                        const double v = r < take ? aw[order[r]] : 0.0;
+                        const int m = std::min(64, take - r0);
+                        for (int l = 0; l < m; ++l) sum += readlane_f64(v, l);
+                    }
+                }
+                acc += take;
+            }
+            __syncthreads();   // the batch's LDS is read by every lane before the next batch writes it
+            cur += took;
+        }
+        if (!FILL && lane == 0) {
+            cnt[pt] = (int32_t)acc;
+            colsum[pt] = sum;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int sgl_spatial_graph(const double* c1, const double* c2, int32_t n, double max_dist, int64_t max_k,
+                                 int32_t* p_out, int64_t* nnz_out, int32_t* i_out, double* x_out, int64_t cap) {
+    if (!p_out || !nnz_out || n < 0 || (n > 0 && (!c1 || !c2))) { sgl_set_error("sgl_spatial_graph: bad arguments"); return SGL_EINVAL; }
+    if ((i_out == nullptr) != (x_out == nullptr)) { sgl_set_error("sgl_spatial_graph: i_out and x_out go together"); return SGL_EINVAL; }
+    if (max_k < 0) { sgl_set_error("spatial_graph: max_k = %lld is negative", (long long)max_k); return SGL_EINVAL; }
+    if (!(max_dist > 0.0) || !(max_dist < INFINITY)) {
+        sgl_set_error("spatial_graph: max_dist = %g must be finite and > 0", max_dist);
+        return SGL_EINVAL;
+    }
+    const double scale = 1.0 / max_dist;   // the reference's scale_factor
+    if (!(scale < INFINITY)) { sgl_set_error("spatial_graph: 1 / max_dist (max_dist = %g) is not finite", max_dist); return SGL_EINVAL; }
+    double xmin = 0, xmax = 0, ymin = 0, ymax = 0;
+    for (int64_t e = 0; e < n; ++e) {
+        const double x = c1[e], y = c2[e];
+        if (!(fabs(x) < INFINITY) || !(fabs(y) < INFINITY)) {
+            sgl_set_error("spatial_graph: coordinate %lld is not finite", (long long)e);
+            return SGL_EINVAL;
+        }
+        if (e == 0 || x < xmin) xmin = x;
+        if (e == 0 || x > xmax) xmax = x;
+        if (e == 0 || y < ymin) ymin = y;
+        if (e == 0 || y > ymax) ymax = y;
+    }
+    const int64_t K = std::min<int64_t>(max_k, n);   // max_k > n acts as n: the scan of n points ends there
+
+    CtxHold hd;
+    SGLCHK(sgl_create(current_device(), &hd.c));
+    hipStream_t s = hd.c->stream;
+    if (K == 0) {   // n = 0 or max_k = 0: the empty n x n graph
+        for (int64_t c = 0; c <= n; ++c) p_out[c] = 0;
+        *nnz_out = 0;
+        return SGL_OK;
+    }
+
+    // --- spatial cell list.  Conservative prefilter: let d = fl(sqrt(fl(fl(dx*dx) + fl(dy*dy)))) < max_dist pass, with
+    // dx = fl(x1 - x2) (double, no contraction).  If |dx| < 2^-511, then |x1 - x2| < 2^-510 (a difference that rounds below
+    // 2^-511 is below it too, or subnormal and exact).  Otherwise dx*dx >= 2^-1022 is normal, so fl(dx*dx) >= dx^2 (1 - 2^-53);
+    // adding a non-negative fl(dy*dy) and taking the rounded root are monotone, each losing at most a factor (1 - 2^-53), so
+    // |dx| <= d (1 + 2^-51) and |x1 - x2| <= |dx| (1 + 2^-52) < max_dist (1 + 2^-50).  Either way |x1 - x2| < R =
+    // max(max_dist, 2^-510) (1 + 2^-50), and the same holds for y.  Buckets have side s >= max(max_dist, 2^-510) (1 + 2^-10),
+    // so |x1 - x2| / s < 1 - 2^-11.  The bucket coordinate u = fl(fl(x - xmin) / s) is off by at most 2^-52 u (+ 2^-1074 if
+    // the quotient is subnormal) <= 2^-21, since s is also raised so that u <= 2^30; so |u1 - u2| < 1 and floor(u1), floor(u2)
+    // differ by at most one: every pair the reference accepts lies in adjacent buckets, underflow of dx*dx included.  (An extent
+    // that overflows double is one bucket: every pair is a candidate.)
+    const double ext = std::max(xmax - xmin, ymax - ymin);
+    int64_t W = 1, H = 1;
+    double side = INFINITY;
+    if (ext < INFINITY) {
+        side = std::max(std::max(max_dist, ldexp(1.0, -510)) * (1.0 + ldexp(1.0, -10)), ext * ldexp(1.0, -30));
+        W = (int64_t)floor((xmax - xmin) / side) + 2;
+        H = (int64_t)floor((ymax - ymin) / side) + 2;
+    }
+    DevBuf<double> d1, d2, sx, sy, colsum;
+    DevBuf<uint64_t> keys, skeys;
+    DevBuf<uint32_t> iota, sidx;
+    DevBuf<int32_t> bnd, cnt;
+    SGLCHK(d1.alloc((size_t)n));
+    SGLCHK(d2.alloc((size_t)n));
+    NBCHK(hipMemcpyAsync(d1.p, c1, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s), "upload of c1");
+    NBCHK(hipMemcpyAsync(d2.p, c2, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s), "upload of c2");
+    SGLCHK(keys.alloc((size_t)n));
+    SGLCHK(skeys.alloc((size_t)n));
+    SGLCHK(iota.alloc((size_t)n));
+    SGLCHK(sidx.alloc((size_t)n));
+    sg_keys_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(d1.p, d2.p, n, xmin, ymin, side, W, H, keys.p, iota.p);
+    NBCHK(hipGetLastError(), "sg_keys_kernel");
+    int end_bit = 1;
+    while (end_bit < 64 && ((uint64_t)1 << end_bit) <= (uint64_t)(W * H)) ++end_bit;
+    {   // LSD radix sort is stable: each bucket's members stay in ascending index order
+        size_t tb = 0;
+        NBCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, iota.p, sidx.p, (int)n, 0, end_bit, s), "radix sort");
+        DevBuf<char> tmp;
+        SGLCHK(tmp.alloc(tb));
+        NBCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.p, skeys.p, iota.p, sidx.p, (int)n, 0, end_bit, s), "radix sort");
+    }
+    SGLCHK(sx.alloc((size_t)n));
+    SGLCHK(sy.alloc((size_t)n));
+    SGLCHK(bnd.alloc((size_t)n * 12));
+    sg_ranges_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(skeys.p, sidx.p, d1.p, d2.p, n, W, H, sx.p, sy.p, bnd.p);
+    NBCHK(hipGetLastError(), "sg_ranges_kernel");
+
+    // --- count pass, scan, 2^31 check
+    SGLCHK(cnt.alloc((size_t)n));
+    SGLCHK(colsum.alloc((size_t)n));
+    const SgArgs a{sx.p, sy.p, sidx.p, bnd.p, n, max_dist, scale, K};
+    sg_merge_kernel<false><<<dim3(grid_for(n, 1)), dim3(64), 0, s>>>(a, cnt.p, colsum.p, nullptr, nullptr, nullptr);
+    NBCHK(hipGetLastError(), "sg_merge_kernel (count)");
+    std::vector<int32_t> hcnt((size_t)n);
+    NBCHK(hipMemcpyAsync(hcnt.data(), cnt.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download of the counts");
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    int64_t nnz = 0;
+    for (int64_t c = 0; c < n; ++c) nnz += hcnt[c];
+    if (nnz > INT32_MAX) {
+        sgl_set_error("spatial_graph: the graph would hold %lld entries, which a dgCMatrix (32-bit column pointers) cannot hold; "
+                      "lower max_dist or max_k", (long long)nnz);
+        return SGL_EINVAL;
+    }
+    p_out[0] = 0;
+    for (int64_t c = 0; c < n; ++c) p_out[c + 1] = p_out[c] + hcnt[c];
+    *nnz_out = nnz;
+    if (!i_out) return SGL_OK;
+    if (cap < nnz) { sgl_set_error("sgl_spatial_graph: output capacity %lld < %lld entries", (long long)cap, (long long)nnz); return SGL_EINVAL; }
+
+    // --- fill pass
+    DevBuf<int32_t> doff, oi;
+    DevBuf<double> ox;
+    SGLCHK(doff.alloc((size_t)n + 1));
+    SGLCHK(oi.alloc((size_t)nnz));
+    SGLCHK(ox.alloc((size_t)nnz));
+    NBCHK(hipMemcpyAsync(doff.p, p_out, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload of p");
+    sg_merge_kernel<true><<<dim3(grid_for(n, 1)), dim3(64), 0, s>>>(a, nullptr, colsum.p, doff.p, oi.p, ox.p);
+    NBCHK(hipGetLastError(), "sg_merge_kernel (fill)");
+    NBCHK(hipMemcpyAsync(i_out, oi.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download of i");
+    NBCHK(hipMemcpyAsync(x_out, ox.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download of x");
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    return SGL_OK;
+}

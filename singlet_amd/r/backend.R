@@ -43,6 +43,13 @@ singlet_hip_enable <- function(shim = Sys.getenv("SINGLET_HIP_SHIM", "singlet_hi
     .Call(dll[["_singlet_c_LKNN"]], m, coord_x, coord_y, k, radius, metric, similarity, max_dist, verbose, threads))
   rebind("c_SNN", function(G, min_similarity, threads)
     .Call(dll[["_singlet_c_SNN"]], G, min_similarity, threads))
+  # the distance-weighted cell graph GCNMF convolves with (R/RcppExports.R: spatial_graph)
+  rebind("spatial_graph", function(c1, c2, max_dist, max_k, threads)
+    .Call(dll[["_singlet_spatial_graph"]], c1, c2, max_dist, max_k, threads))
+  sg <- get("spatial_graph", envir = ns)   # with the wrapper's defaults (R/RcppExports.R:90): max_k = 100L, threads = 0L
+  formals(sg)$max_k <- 100L
+  formals(sg)$threads <- 0L
+  rebind("spatial_graph", sg)
   # R/RunNMF.R:86-93 re-weights the matrix by group before the fit (R/RcppExports.R: weight_by_split(A_, split_by, n_groups))
   rebind("weight_by_split", function(A_, split_by, n_groups)
     .Call(dll[["_singlet_weight_by_split"]], A_, split_by, n_groups))

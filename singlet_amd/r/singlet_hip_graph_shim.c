@@ -1,8 +1,8 @@
 /*
- * singlet_hip_graph_shim.c -- .Call bodies of the two spatial neighbour-graph entry points, registered by
+ * singlet_hip_graph_shim.c -- .Call bodies of the three spatial graph entry points, registered by
  * singlet_hip_shim.c's call_entries table.  Same names and arity as the reference's Rcpp glue
- * (src/RcppExports.cpp:466-467: _singlet_c_LKNN, 10 args; _singlet_c_SNN, 3 args), so that
- * R/FindLocalNeighbors.R:95-98 works unchanged.  They need two R API pieces the main shim does not: the string of
+ * (src/RcppExports.cpp:465-467: _singlet_spatial_graph, 5 args; _singlet_c_LKNN, 10 args; _singlet_c_SNN, 3 args), so that
+ * R/FindLocalNeighbors.R:95-98 and singlet:::spatial_graph work unchanged.  They need two R API pieces the main shim does not: the string of
  * `metric`, and a new Matrix::dgCMatrix object for the result.
  *
  * Not compiled in this repository's CI (no R here); build it together with singlet_hip_shim.c.
@@ -17,12 +17,13 @@
 SEXP _singlet_c_LKNN(SEXP m_, SEXP coord_x_, SEXP coord_y_, SEXP k_, SEXP radius_, SEXP metric_, SEXP similarity_,
                      SEXP max_dist_, SEXP verbose_, SEXP threads_);
 SEXP _singlet_c_SNN(SEXP G_, SEXP min_similarity_, SEXP threads_);
+SEXP _singlet_spatial_graph(SEXP c1_, SEXP c2_, SEXP max_dist_, SEXP max_k_, SEXP threads_);
 
 static void graph_fail_if(int rc) {
     if (rc != SGL_OK) Rf_error("singlet HIP back end: %s", sgl_last_error());
 }
 
-/* new("dgCMatrix", i = , p = , x = , Dim = c(n, n)) from the two-call output of sgl_c_lknn / sgl_c_snn. */
+/* new("dgCMatrix", i = , p = , x = , Dim = c(n, n)) from the two-call output of sgl_c_lknn / sgl_c_snn / sgl_spatial_graph. */
 typedef int (*graph_call)(void* args, int32_t* p_out, int64_t* nnz_out, int32_t* i_out, double* x_out, int64_t cap);
 
 static SEXP graph_result(graph_call fn, void* args, int n) {
@@ -128,4 +129,51 @@ SEXP _singlet_c_SNN(SEXP G_, SEXP min_similarity_, SEXP threads_) {
     if (XLENGTH(p) != (R_xlen_t)a.ncol + 1) Rf_error("G: not a dgCMatrix (length(p) != ncol + 1)");
     a.min_similarity = Rf_asReal(min_similarity_);
     return graph_result(snn_call, &a, a.ncol);
+}
+
+typedef struct {
+    const double *c1, *c2;
+    int n;
+    double max_dist;
+    int64_t max_k;
+} spatial_args;
+
+static int spatial_call(void* a_, int32_t* p_out, int64_t* nnz_out, int32_t* i_out, double* x_out, int64_t cap) {
+    const spatial_args* a = (const spatial_args*)a_;
+    return sgl_spatial_graph(a->c1, a->c2, a->n, a->max_dist, a->max_k, p_out, nnz_out, i_out, x_out, cap);
+}
+
+/* A numeric vector as doubles, as Rcpp's std::vector<double> takes it: integers are widened (NA_integer_ becomes NaN, which
+ * sgl_spatial_graph refuses). */
+static SEXP as_doubles(SEXP v, const char* what) {
+    if (TYPEOF(v) == REALSXP) return v;
+    if (TYPEOF(v) != INTSXP) Rf_error("%s must be a numeric vector", what);
+    const R_xlen_t n = XLENGTH(v);
+    SEXP out = PROTECT(Rf_allocVector(REALSXP, n));
+    const int* src = INTEGER(v);
+    double* dst = REAL(out);
+    for (R_xlen_t e = 0; e < n; ++e) dst[e] = src[e] == INT32_MIN ? NAN : (double)src[e];
+    UNPROTECT(1);
+    return out;
+}
+
+/* ---- spatial_graph(c1, c2, max_dist, max_k, threads) ---- *
+ * (src/singlet.cpp:1365-1414).  c1, c2: numeric vectors of one length; max_k truncates toward zero as Rcpp's size_t
+ * conversion does (NA and negative values refused). */
+SEXP _singlet_spatial_graph(SEXP c1_, SEXP c2_, SEXP max_dist_, SEXP max_k_, SEXP threads_) {
+    (void)threads_;
+    SEXP c1 = PROTECT(as_doubles(c1_, "c1")), c2 = PROTECT(as_doubles(c2_, "c2"));
+    if (XLENGTH(c1) != XLENGTH(c2)) Rf_error("spatial_graph: c1 and c2 differ in length");
+    if (XLENGTH(c1) > 2147483647) Rf_error("spatial_graph: too many points for a dgCMatrix");
+    const double k = Rf_asReal(max_k_);
+    if (ISNAN(k) || k < 0) Rf_error("spatial_graph: max_k must be a non-negative number");
+    spatial_args a;
+    a.c1 = REAL(c1);
+    a.c2 = REAL(c2);
+    a.n = (int)XLENGTH(c1);
+    a.max_dist = Rf_asReal(max_dist_);
+    a.max_k = k >= 9.2e18 ? INT64_MAX : (int64_t)k;   /* above n it acts as n */
+    SEXP out = graph_result(spatial_call, &a, a.n);
+    UNPROTECT(2);
+    return out;
 }

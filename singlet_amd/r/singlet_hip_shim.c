@@ -1,6 +1,6 @@
 /*
  * singlet_hip_shim.c -- the R-aware C layer of the HIP back end (with singlet_hip_graph_shim.c, the bodies of the
- * two spatial neighbour-graph entries it registers).
+ * three spatial graph entries it registers).
  *
  * It provides .Call entry points with the SAME names and arity as the Rcpp glue
  * of the reference (src/RcppExports.cpp:98-116 _singlet_c_nmf,
@@ -429,9 +429,10 @@ SEXP _singlet_c_gcnmf(SEXP A_, SEXP At_, SEXP G_, SEXP tol_, SEXP maxit_, SEXP v
     return out;
 }
 
-/* the spatial neighbour graphs: bodies in singlet_hip_graph_shim.c (src/RcppExports.cpp:466-467) */
+/* the spatial graphs: bodies in singlet_hip_graph_shim.c (src/RcppExports.cpp:465-467) */
 SEXP _singlet_c_LKNN(SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP);
 SEXP _singlet_c_SNN(SEXP, SEXP, SEXP);
+SEXP _singlet_spatial_graph(SEXP, SEXP, SEXP, SEXP, SEXP);
 
 static const R_CallMethodDef call_entries[] = {
     {"_singlet_weight_by_split", (DL_FUNC)&_singlet_weight_by_split, 3},
@@ -447,6 +448,7 @@ static const R_CallMethodDef call_entries[] = {
     {"_singlet_Rcpp_predict", (DL_FUNC)&_singlet_Rcpp_predict, 5},
     {"_singlet_c_LKNN", (DL_FUNC)&_singlet_c_LKNN, 10},
     {"_singlet_c_SNN", (DL_FUNC)&_singlet_c_SNN, 3},
+    {"_singlet_spatial_graph", (DL_FUNC)&_singlet_spatial_graph, 5},
     {NULL, NULL, 0}};
 
 void R_init_singlet_hip_shim(DllInfo* dll) {
