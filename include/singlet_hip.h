@@ -376,6 +376,38 @@ SGL_API int sgl_weight_by_split(sgl_ctx* ctx, const int32_t* split_by, int32_t n
 SGL_API int sgl_c_weight_by_split(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol,
                                   const int32_t* split_by, int32_t n_groups, double* x_out);
 
+/* Row-wise rasterisation: rowwise_compress_sparse / rowwise_compress_dense (src/singlet.cpp:146-180; glue
+ * _singlet_rowwise_compress_sparse / _dense, 3 args, src/RcppExports.cpp:446-447), which RasterizeRowwise
+ * (R/rasterize_rowwise.R) calls for a dgCMatrix / anything else.  This build's rules:
+ *  - out is floor(nrow / n) x ncol, column-major doubles.  Entry (b, j) = (sum over r in [b n, b n + n) of A[r, j]) / n:
+ *    the sum in ascending r starting from +0.0, without contraction, then one true division by (double)n (a product
+ *    with 1 / n gives other bits).  Bit-exact with the reference wherever it is defined (nrow % n == 0, n >= 1), and the
+ *    sparse and dense forms of one matrix give the same bits: skipped zeros are additions of +0.0, which change no sum
+ *    that starts at +0.0 (it is never -0.0).
+ *  - the last nrow mod n rows are left out (their entries have no effect): the shape both references allocate and the
+ *    row names the R wrapper assigns.  The reference is undefined there: the sparse form adds those entries to res(0,
+ *    col + 1) -- the next column's first bin, racing with its thread, or past the result for the last column -- and the
+ *    dense form reads past the column and writes the same alias.
+ *  - n < 1 is refused (SGL_EINVAL, with a message; the reference divides by zero, and a negative n from R becomes a huge
+ *    size_t): the R and Python layers refuse NA and truncate a fractional n toward zero as Rcpp's as<size_t> does.
+ *    n > nrow gives the 0 x ncol result (nothing written).
+ *  - values are not checked for finiteness (unlike the fit uploads): NaN / Inf propagate through the IEEE sums as in
+ *    the reference.  The structure of the sparse form is validated (row indices in [0, nrow), strictly ascending
+ *    within a column, p non-decreasing from 0): an invalid dgCMatrix is SGL_EINVAL with a message.
+ *  - 64-bit indexing throughout: the result and a dense input may exceed 2^31 elements.  threads is the caller's to ignore.
+ * One-shot entries: their own context on the current device, out sized floor(nrow / n) * ncol; neither uses nor touches
+ * the SINGLET_HIP_CACHE context.  The dense form copies the matrix to the device as it is (no CSC image). */
+SGL_API int sgl_c_rowwise_compress_sparse(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol,
+                                          int64_t n, double* out);
+SGL_API int sgl_c_rowwise_compress_dense(const double* A, int32_t nrow, int32_t ncol, int64_t n, double* out);
+/* The resident form: the context's matrix (its CSC image A, from any upload, synth or staging step) is replaced by its
+ * rasterisation, resident exactly as if sgl_upload_dense had received it (CSC image and transpose built on the device,
+ * the dense copy kept when more than half of it is non-zero).  A running fit is dropped.  Refused, with the matrix kept:
+ * SGL_ESTATE on a team member or with an all-reduce hook set (the gene-side images would differ across shards) or with
+ * no matrix resident; SGL_EINVAL for n < 1 or n > nrow (a resident matrix cannot be empty).  A non-finite result (a
+ * sum that overflows) is refused like sgl_upload_dense refuses one, and then no matrix stays resident. */
+SGL_API int sgl_rasterize_rowwise(sgl_ctx* ctx, int64_t n);
+
 /* Start a fit at rank k.  w_init: k x nrow host array, or NULL to fill W on
  * the device with the synthetic init ((rand_{S+2}(f,g) >> 11) + 0.5) * 2^-53.
  * h = 0, d = 1 as in src/singlet.cpp:639-641.

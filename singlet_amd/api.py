@@ -11,6 +11,7 @@ names, argument order, defaults and return fields:
   c_LKNN / c_SNN                        src/singlet.cpp:1491-1665 (glue src/RcppExports.cpp:466-467)
   find_local_neighbors                  R/FindLocalNeighbors.R:32-101
   rescale_spatial                       R/RescaleSpatial.R:10-22
+  RasterizeRowwise, rowwise_compress_*  R/rasterize_rowwise.R; src/singlet.cpp:146-180
   ard_nmf                               R/ard_nmf.R:31-193
   cross_validate_nmf                    R/cross_validate_nmf.R:18-105
   GetBestRank                           R/GetBestRank.R:8-46
@@ -421,6 +422,90 @@ def weight_by_split(A_, split_by, n_groups):
     check(_lib.load().sgl_c_weight_by_split(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow, A.ncol, ptr(sb, i32p),
                                             int(n_groups), ptr(x, f64p)))
     return dgCMatrix(x, A.i, A.p, A.Dim, A.Dimnames)
+
+
+# ---------------------------------------------------------------------------
+# Row-wise rasterisation (RasterizeRowwise)
+# ---------------------------------------------------------------------------
+def _bin_size(n, who):
+    """n as Rcpp's as<size_t> takes it: truncated toward zero.  NA is refused here; values below 1 by the library, with a
+    message (include/singlet_hip.h: sgl_c_rowwise_compress_sparse)."""
+    v = float(n)
+    if math.isnan(v):
+        raise _lib.SingletHipError(-1, "%s: n is NA: the bin size must be at least 1" % who)
+    if v >= 2.0**63:
+        return 2**63 - 1
+    if v <= -2.0**63:
+        return -2**63
+    return int(v)
+
+
+class RasterMatrix(np.ndarray):
+    """The dense result of RasterizeRowwise: a Fortran-ordered float64 ndarray with R's dimnames, `rownames` and
+    `colnames` (None where R's are NULL).  Arrays derived from it carry no names."""
+
+    def __array_finalize__(self, obj):
+        self.rownames = None
+        self.colnames = None
+
+
+def _raster_out(nb, ncol):
+    return np.zeros((nb, ncol), dtype=np.float64, order="F")
+
+
+def rowwise_compress_sparse(A, n=10, threads=0):
+    """.Call(`_singlet_rowwise_compress_sparse`, A, n, threads)  (src/singlet.cpp:146-162): the floor(nrow / n) x ncol
+    matrix of the means of every n consecutive rows of the dgCMatrix A (the last nrow mod n rows left out).  Rules:
+    include/singlet_hip.h, sgl_c_rowwise_compress_sparse.  `threads` is ignored."""
+    A = as_dgCMatrix(A)
+    nn = _bin_size(n, "rowwise_compress_sparse")
+    out = _raster_out(A.nrow // nn if 1 <= nn <= A.nrow else 0, A.ncol)
+    check(_lib.load().sgl_c_rowwise_compress_sparse(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow, A.ncol, nn,
+                                                    ptr(out, f64p)))
+    return out
+
+
+def rowwise_compress_dense(A, n=10, threads=0):
+    """.Call(`_singlet_rowwise_compress_dense`, A, n, threads)  (src/singlet.cpp:164-180): the same on a dense matrix,
+    bit-identical to rowwise_compress_sparse on the same values.  `threads` is ignored."""
+    A = np.asarray(A, dtype=np.float64)
+    if A.ndim != 2:
+        raise ValueError("rowwise_compress_dense: A must be a matrix")
+    Af = np.asfortranarray(A)
+    nrow, ncol = A.shape
+    nn = _bin_size(n, "rowwise_compress_dense")
+    out = _raster_out(nrow // nn if 1 <= nn <= nrow else 0, ncol)
+    check(_lib.load().sgl_c_rowwise_compress_dense(ptr(Af, f64p) if Af.size else None, nrow, ncol, nn, ptr(out, f64p)))
+    return out
+
+
+def RasterizeRowwise(A, n=10, threads=0):
+    """RasterizeRowwise (R/rasterize_rowwise.R): a dgCMatrix goes to rowwise_compress_sparse, anything else (as a dense
+    matrix) to rowwise_compress_dense.  The result is a RasterMatrix with the names the R wrapper assigns: rownames
+    rownames(A)[seq(1, floor(nrow / n) * n, n)], colnames colnames(A).  As in R, seq() fails when that range is empty
+    (n > nrow)."""
+    if isinstance(A, dgCMatrix):
+        rn, cn = A.Dimnames
+        B = rowwise_compress_sparse(A, n, threads)
+        nrow = A.nrow
+    else:
+        rn = cn = None
+        M = A.toarray() if hasattr(A, "toarray") else A   # as.matrix(A)
+        B = rowwise_compress_dense(M, n, threads)
+        nrow = np.shape(M)[0]
+    to = math.floor(nrow / float(n)) * float(n)
+    if to < 1:   # seq(1, to, n) with to < 1 and n > 0
+        raise ValueError("RasterizeRowwise: wrong sign in 'by' argument (seq(1, %g, %g))" % (to, float(n)))
+    steps = math.floor((to - 1) / float(n) + 1e-10)
+    rows = [int(1 + q * float(n)) - 1 for q in range(steps + 1)]   # R truncates a double subscript
+    out = B.view(RasterMatrix)
+    if rn is not None:
+        names = [rn[r] for r in rows]
+        if len(names) != B.shape[0]:
+            raise ValueError("RasterizeRowwise: length of 'dimnames' [1] not equal to array extent")
+        out.rownames = names
+    out.colnames = list(cn) if cn is not None else None
+    return out
 
 
 def project_model(A, w, L1=0.01, L2=0, threads=0):

@@ -218,6 +218,13 @@ class Context:
         check(self._L.sgl_log_normalize(self._h, float(scale_factor)))
         self.k = 0
 
+    def rasterize_rowwise(self, n):
+        """RasterizeRowwise on the resident matrix (sgl_rasterize_rowwise): it becomes the floor(nrow / n) x ncol matrix of
+        the means of every n consecutive rows, resident as upload_dense leaves a dense matrix; a running fit is dropped."""
+        from .api import _bin_size
+        check(self._L.sgl_rasterize_rowwise(self._h, _bin_size(n, "rasterize_rowwise")))
+        self.k = 0
+
     def weight_by_split(self, split_by, n_groups):
         """weight_by_split (src/singlet.cpp:119-144) on the resident shard; split_by: 0-based group per local cell."""
         sb = np.ascontiguousarray(split_by, dtype=np.int32)

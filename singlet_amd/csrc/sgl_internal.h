@@ -318,6 +318,12 @@ int k_colsum(hipStream_t s, const DevCSC& M, double* sums);
 int k_cell_factor(hipStream_t s, DevCSC& A, DevCSC& At, const double* f, int mode, double scale);
 int k_link_mul(hipStream_t s, double* B, const double* L, int k, int link_rows, int64_t ncols);
 
+// row-wise rasterisation (kernels_raster.hip): out (nb x ncol, column-major) = means of rows [b n, b n + n), nb >= 1
+int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, double* out);
+int k_raster_dense(hipStream_t s, const double* A, int64_t nrow, int64_t ncol, int64_t n, int64_t nb, double* out);
+// upload of A alone (an empty At) validating the structure only, the values as they are (singlet_hip.hip)
+int sgl_upload_A_structure(sgl_ctx* c, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol);
+
 // graph convolution (kernels_graph.hip): Y = X G, X and Y k x n column-major (Y must not alias X)
 int k_graph_conv(hipStream_t s, DevGraph& g, const double* X, double* Y, int k);
 

@@ -325,8 +325,9 @@ static int sgl_h2d(sgl_ctx* c, void* dst, const void* src, size_t bytes) {
     return SGL_OK;
 }
 
+// check_finite = false: the structure is validated (the kernels rely on it), the values are taken as they are
 static int upload_one(sgl_ctx* c, DevCSC& M, const double* x, const int32_t* i, const int32_t* p, int32_t nrow,
-                      int32_t ncol) {
+                      int32_t ncol, bool check_finite = true) {
     const int64_t nnz = (int64_t)p[ncol];
     if (p[0] != 0 || nnz < 0) { sgl_set_error("invalid column pointer array (p[0]=%d, p[ncol]=%lld)", p[0], (long long)nnz); return SGL_EINVAL; }
     for (int32_t q = 0; q < ncol; ++q)
@@ -352,7 +353,7 @@ static int upload_one(sgl_ctx* c, DevCSC& M, const double* x, const int32_t* i, 
     // the kernels index factor rows by these values: refuse anything that is not a valid dgCMatrix
     int flag = 0;
     if (rc == SGL_OK) rc = k_validate_csc(c->stream, M.i, M.p, ncol, nrow, reinterpret_cast<int*>(p32));
-    if (rc == SGL_OK) rc = k_all_finite(c->stream, M.x, nnz, reinterpret_cast<int*>(p32));
+    if (rc == SGL_OK && check_finite) rc = k_all_finite(c->stream, M.x, nnz, reinterpret_cast<int*>(p32));
     if (rc == SGL_OK && hipMemcpyAsync(&flag, p32, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = SGL_EHIP;
     if (hipStreamSynchronize(c->stream) != hipSuccess && rc == SGL_OK) rc = SGL_EHIP;
     g_times.validate_s += wall_now() - t1;
@@ -482,14 +483,14 @@ extern "C" int sgl_upload_csc_list(sgl_ctx* c, int32_t n_chunks, const double* c
 
 // A only (c_project_model never walks At): At becomes an empty nrow-column matrix.
 static int sgl_upload_csc_A_only(sgl_ctx* c, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow,
-                                 int32_t ncol) {
+                                 int32_t ncol, bool check_finite = true) {
     CTX_GUARD(c);
     if (!Ax || !Ai || !Ap || nrow <= 0 || ncol <= 0) { sgl_set_error("missing slot or empty matrix"); return SGL_EINVAL; }
     free_fit(c);
     free_matrix(c);
     c->cell_offset = 0;
     c->ncells_total = ncol;
-    SGLCHK(upload_one(c, c->A, Ax, Ai, Ap, nrow, ncol));
+    SGLCHK(upload_one(c, c->A, Ax, Ai, Ap, nrow, ncol, check_finite));
     DevCSC& T = c->At;
     T.nrow = ncol; T.ncol = nrow; T.nnz = 0;
     SGLCHK(dev_alloc(&T.x, 1));
@@ -499,20 +500,19 @@ static int sgl_upload_csc_A_only(sgl_ctx* c, const double* Ax, const int32_t* Ai
     return finish_matrix(c);
 }
 
+int sgl_upload_A_structure(sgl_ctx* c, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol) {
+    return sgl_upload_csc_A_only(c, Ax, Ai, Ap, nrow, ncol, false);
+}
+
 // Dense matrix (nrow x ncol, column-major, as R holds it): kept on the device as it is AND as its CSC image (zeros
 // dropped), both orientations, all built there.  More than half of the entries non-zero (or SGL_DENSE_GEMM=1; =0
 // forbids it) -> the plain fit forms its right-hand sides as GEMMs on the dense copy; otherwise the copy is released.
-extern "C" int sgl_upload_dense(sgl_ctx* c, const double* A, int32_t nrow, int32_t ncol) {
-    CTX_GUARD(c);
-    if (!A || nrow <= 0 || ncol <= 0) { sgl_set_error("sgl_upload_dense: missing or empty matrix"); return SGL_EINVAL; }
-    free_fit(c);
-    free_matrix(c);
-    c->dense_input = true;
-    c->cell_offset = 0;
-    c->ncells_total = ncol;
+// The device half of sgl_upload_dense: `dev` (nrow x ncol, column-major, a pool block) becomes the context's dense copy,
+// is refused when it holds a non-finite value (and freed: no matrix stays resident), and its CSC image, the transpose and
+// the GEMM decision are built from it.  The caller has freed the previous matrix; `who` names the entry in messages.
+static int ingest_dense(sgl_ctx* c, double* dev, int32_t nrow, int32_t ncol, const char* who) {
     const size_t tot = (size_t)nrow * (size_t)ncol;
-    SGLCHK(dev_alloc(&c->Adense, tot));
-    HIPCHK(hipMemcpyAsync(c->Adense, A, sizeof(double) * tot, hipMemcpyHostToDevice, c->stream));
+    c->Adense = dev;
     {   // non-finite entries are refused like in the sparse uploads (k_all_finite)
         int* dflag = nullptr;
         SGLCHK(dev_alloc(&dflag, 1));
@@ -522,8 +522,8 @@ extern "C" int sgl_upload_dense(sgl_ctx* c, const double* A, int32_t nrow, int32
         if (rc == SGL_OK && (hipMemcpyAsync(&flag, dflag, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
                              hipStreamSynchronize(c->stream) != hipSuccess)) rc = SGL_EHIP;
         dev_free(dflag);
-        if (rc == SGL_EHIP) sgl_set_error("sgl_upload_dense: HIP call failed");
-        if (rc == SGL_OK && flag != 0) { sgl_set_error("sgl_upload_dense: non-finite value (NA / NaN / Inf) in the matrix -- refused here; singlet's CPU path would return all-NaN factors"); rc = SGL_EINVAL; }
+        if (rc == SGL_EHIP) sgl_set_error("%s: HIP call failed", who);
+        if (rc == SGL_OK && flag != 0) { sgl_set_error("%s: non-finite value (NA / NaN / Inf) in the matrix -- refused here; singlet's CPU path would return all-NaN factors", who); rc = SGL_EINVAL; }
         if (rc != SGL_OK) {   // the refused copy does not stay resident until the next upload
             (void)hipStreamSynchronize(c->stream);
             dev_free(c->Adense);
@@ -541,7 +541,7 @@ extern "C" int sgl_upload_dense(sgl_ctx* c, const double* A, int32_t nrow, int32
     if (rc == SGL_OK) rc = k_scan_total(c->stream, counts, M.p, ncol);
     int64_t nnz = 0;
     if (rc == SGL_OK && (hipMemcpyAsync(&nnz, M.p + ncol, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                         hipStreamSynchronize(c->stream) != hipSuccess)) { sgl_set_error("sgl_upload_dense: HIP call failed"); rc = SGL_EHIP; }
+                         hipStreamSynchronize(c->stream) != hipSuccess)) { sgl_set_error("%s: HIP call failed", who); rc = SGL_EHIP; }
     dev_free(counts);
     SGLCHK(rc);
     M.nnz = nnz;
@@ -554,6 +554,22 @@ extern "C" int sgl_upload_dense(sgl_ctx* c, const double* A, int32_t nrow, int32
     if (c->dense_gemm && !sgl_dense_gemm_available()) c->dense_gemm = false;   // no rocBLAS here: the CSC image runs the fit
     if (!c->dense_gemm) { HIPCHK(hipStreamSynchronize(c->stream)); dev_free(c->Adense); c->Adense = nullptr; }
     return finish_matrix(c);
+}
+
+extern "C" int sgl_upload_dense(sgl_ctx* c, const double* A, int32_t nrow, int32_t ncol) {
+    CTX_GUARD(c);
+    if (!A || nrow <= 0 || ncol <= 0) { sgl_set_error("sgl_upload_dense: missing or empty matrix"); return SGL_EINVAL; }
+    free_fit(c);
+    free_matrix(c);
+    c->dense_input = true;
+    c->cell_offset = 0;
+    c->ncells_total = ncol;
+    const size_t tot = (size_t)nrow * (size_t)ncol;
+    double* dev = nullptr;
+    SGLCHK(dev_alloc(&dev, tot));
+    c->Adense = dev;
+    HIPCHK(hipMemcpyAsync(dev, A, sizeof(double) * tot, hipMemcpyHostToDevice, c->stream));
+    return ingest_dense(c, dev, nrow, ncol, "sgl_upload_dense");
 }
 
 extern "C" int sgl_synth_csc(sgl_ctx* c, uint64_t S, uint64_t inv_density, const double* levels16, int32_t ngenes,
@@ -667,6 +683,39 @@ extern "C" int sgl_log_normalize(sgl_ctx* c, double scale_factor) {
     dev_free(sums);
     if (rc == SGL_OK && e != hipSuccess) { sgl_set_error("sgl_log_normalize: %s", hipGetErrorString(e)); rc = SGL_EHIP; }
     return rc;
+}
+
+// RasterizeRowwise on the resident matrix: its CSC image A becomes the floor(nrow / n) x ncol matrix of bin means
+// (k_raster_sparse, the rules of sgl_c_rowwise_compress_sparse), resident as sgl_upload_dense leaves a dense matrix.
+// Every refusal comes before anything is freed; the old A and At are freed once the dense result is written, before the
+// ingest allocates the new image, so the two are never resident together.
+extern "C" int sgl_rasterize_rowwise(sgl_ctx* c, int64_t n) {
+    CTX_GUARD(c);
+    if (c->team || c->allreduce) {
+        sgl_set_error("sgl_rasterize_rowwise: the context is a shard of a team or has an all-reduce hook; the bins of this shard's "
+                      "genes would leave the shards' gene-side images inconsistent");
+        return SGL_ESTATE;
+    }
+    if (!c->A.p) { sgl_set_error("no matrix resident"); return SGL_ESTATE; }
+    const int32_t nrow = c->A.nrow, ncol = c->A.ncol;
+    if (n < 1 || n > nrow) {
+        sgl_set_error("sgl_rasterize_rowwise: n = %lld must lie in [1, nrow = %d] (a resident matrix cannot be empty)", (long long)n, nrow);
+        return SGL_EINVAL;
+    }
+    const int64_t nb = nrow / n;
+    free_fit(c);
+    c->k = 0;
+    double* R = nullptr;
+    SGLCHK(dev_alloc(&R, (size_t)nb * (size_t)ncol));
+    int rc = k_raster_sparse(c->stream, c->A, n, nb, R);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == SGL_OK && e != hipSuccess) { sgl_set_error("sgl_rasterize_rowwise: %s", hipGetErrorString(e)); rc = SGL_EHIP; }
+    if (rc != SGL_OK) { dev_free(R); return rc; }
+    free_matrix(c);
+    c->dense_input = true;
+    c->cell_offset = 0;
+    c->ncells_total = ncol;
+    return ingest_dense(c, R, (int32_t)nb, ncol, "sgl_rasterize_rowwise");
 }
 
 extern "C" int sgl_weight_by_split(sgl_ctx* c, const int32_t* split_by, int32_t n_groups) {

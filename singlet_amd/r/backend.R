@@ -1,7 +1,7 @@
 # backend.R -- opt-in switch for the HIP back end (source()d or added to the package's R/).
 #
 # With options(singlet.backend = "hip") (or SINGLET_BACKEND=hip in the environment) the
-# wrappers of R/RcppExports.R:4-6, 20-38, 78-88 are rebound to the shim's .Call symbols; with the option
+# wrappers of R/RcppExports.R:4-14, 20-38, 78-88 are rebound to the shim's .Call symbols; with the option
 # unset nothing changes and the package's own OpenMP code runs.  run_nmf / ard_nmf /
 # cross_validate_nmf / RunNMF / project_model call these wrappers by name, so they need no edit.
 
@@ -50,6 +50,15 @@ singlet_hip_enable <- function(shim = Sys.getenv("SINGLET_HIP_SHIM", "singlet_hi
   formals(sg)$max_k <- 100L
   formals(sg)$threads <- 0L
   rebind("spatial_graph", sg)
+  # RasterizeRowwise (R/rasterize_rowwise.R) bins rows with these two (R/RcppExports.R:8-14)
+  rebind("rowwise_compress_sparse", function(A, n, threads) .Call(dll[["_singlet_rowwise_compress_sparse"]], A, n, threads))
+  rebind("rowwise_compress_dense", function(A, n, threads) .Call(dll[["_singlet_rowwise_compress_dense"]], A, n, threads))
+  for (rw in c("rowwise_compress_sparse", "rowwise_compress_dense")) {   # with the wrappers' defaults: n = 10L, threads = 0L
+    fn <- get(rw, envir = ns)
+    formals(fn)$n <- 10L
+    formals(fn)$threads <- 0L
+    rebind(rw, fn)
+  }
   # R/RunNMF.R:86-93 re-weights the matrix by group before the fit (R/RcppExports.R: weight_by_split(A_, split_by, n_groups))
   rebind("weight_by_split", function(A_, split_by, n_groups)
     .Call(dll[["_singlet_weight_by_split"]], A_, split_by, n_groups))

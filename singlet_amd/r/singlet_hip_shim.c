@@ -429,6 +429,48 @@ SEXP _singlet_c_gcnmf(SEXP A_, SEXP At_, SEXP G_, SEXP tol_, SEXP maxit_, SEXP v
     return out;
 }
 
+/* ---- rowwise_compress_sparse(A, n, threads) / rowwise_compress_dense(A, n, threads) ---- *
+ * (src/singlet.cpp:146-180, glue src/RcppExports.cpp:446-447; R/rasterize_rowwise.R): the floor(nrow / n) x ncol matrix
+ * of the means of every n consecutive rows (rules: include/singlet_hip.h).  n is truncated toward zero as Rcpp's
+ * as<size_t> does; NA and values below 1 are refused.  threads is ignored. */
+static int64_t bin_size(SEXP n_) {
+    const double v = Rf_asReal(n_);
+    if (ISNAN(v) || v < 1) Rf_error("rowwise_compress: n must be a number >= 1 (the bin size)");
+    return v >= 9.2e18 ? INT64_MAX : (int64_t)v;
+}
+
+SEXP _singlet_rowwise_compress_sparse(SEXP A_, SEXP n_, SEXP threads_) {
+    (void)threads_;
+    dgc_view A = view_dgc(A_, "A");
+    const int64_t n = bin_size(n_);
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, n > A.nrow ? 0 : (int)(A.nrow / n), A.ncol));
+    fail_if(sgl_c_rowwise_compress_sparse(A.x, A.i, A.p, A.nrow, A.ncol, n, REAL(out)));
+    UNPROTECT(1);
+    return out;
+}
+
+SEXP _singlet_rowwise_compress_dense(SEXP A_, SEXP n_, SEXP threads_) {
+    (void)threads_;
+    if (!Rf_isMatrix(A_) || (TYPEOF(A_) != REALSXP && TYPEOF(A_) != INTSXP)) Rf_error("A must be a numeric matrix");
+    const int m = Rf_nrows(A_), ncol = Rf_ncols(A_);
+    const int64_t n = bin_size(n_);
+    SEXP A = A_;
+    int nprot = 0;
+    if (TYPEOF(A_) == INTSXP) {   /* widened as Rcpp's NumericMatrix takes it (NA_integer_ becomes NaN) */
+        const R_xlen_t len = XLENGTH(A_);
+        A = PROTECT(Rf_allocMatrix(REALSXP, m, ncol));
+        ++nprot;
+        const int* src = INTEGER(A_);
+        double* dst = REAL(A);
+        for (R_xlen_t e = 0; e < len; ++e) dst[e] = src[e] == INT32_MIN ? NAN : (double)src[e];
+    }
+    SEXP out = PROTECT(Rf_allocMatrix(REALSXP, n > m ? 0 : (int)(m / n), ncol));
+    ++nprot;
+    fail_if(sgl_c_rowwise_compress_dense(REAL(A), m, ncol, n, REAL(out)));
+    UNPROTECT(nprot);
+    return out;
+}
+
 /* the spatial graphs: bodies in singlet_hip_graph_shim.c (src/RcppExports.cpp:465-467) */
 SEXP _singlet_c_LKNN(SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP, SEXP);
 SEXP _singlet_c_SNN(SEXP, SEXP, SEXP);
@@ -449,6 +491,8 @@ static const R_CallMethodDef call_entries[] = {
     {"_singlet_c_LKNN", (DL_FUNC)&_singlet_c_LKNN, 10},
     {"_singlet_c_SNN", (DL_FUNC)&_singlet_c_SNN, 3},
     {"_singlet_spatial_graph", (DL_FUNC)&_singlet_spatial_graph, 5},
+    {"_singlet_rowwise_compress_sparse", (DL_FUNC)&_singlet_rowwise_compress_sparse, 3},
+    {"_singlet_rowwise_compress_dense", (DL_FUNC)&_singlet_rowwise_compress_dense, 3},
     {NULL, NULL, 0}};
 
 void R_init_singlet_hip_shim(DllInfo* dll) {
