@@ -32,18 +32,10 @@ int k_nnls_lane_launch1(hipStream_t s, const double* Gpad, int KP, double* B, do
 int k_nnls_lane_launch2(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
                         int64_t ncols, double L1, double L2, unsigned long long* sweep_counter, const NnlsPass& ps, dim3 g,
                         dim3 b);
-int k_nnls_lane_launch3(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
-                        int64_t ncols, double L1, double L2, unsigned long long* sweep_counter, const NnlsPass& ps, dim3 g,
-                        dim3 b);
-
-int k_nnls_lane_launch4(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
-                        int64_t ncols, double L1, double L2, unsigned long long* sweep_counter, const NnlsPass& ps, dim3 g,
-                        dim3 b);
-
 int k_nnls_half_launch(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
                        int64_t ncols, double L1, double L2, unsigned long long* sweep_counter, const NnlsPass& ps);
-// the two-lanes-per-column solve as generated asm (kernels_nnls_half_asm.hip): padded rank it serves k with (0: none)
-int nnls_half_asm_kp(int k, double L1);
+// the two-lanes-per-column solve as generated asm (kernels_nnls_half_asm.hip): whether it serves padded rank KP
+bool nnls_half_asm_has(int KP, double L1);
 int k_nnls_half_launch_asm(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
                            int64_t ncols, double L1, double L2, unsigned long long* sweep_counter, const NnlsPass& ps);
 // the sweep as generated asm (kernels_nnls_asm.hip): the ranks it has instances for, same protocol as the lane kernels
@@ -51,36 +43,35 @@ bool nnls_lane_asm_has(int KP, double L1, int64_t ncols);
 int k_nnls_lane_launch_asm(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
                            int64_t ncols, double L1, double L2, unsigned long long* sweep_counter, const NnlsPass& ps, dim3 g, dim3 b);
 
-int64_t nnls_repack_min_cols() {
+// The two-lane solves put 32 columns in a wave: the chip is as full at half the columns, and re-packing pays from there --
+// nnls_h per 200 000 columns k = 100 6.56 -> 6.16 ms, k = 128 11.44 -> 10.27 (scripts/r5/r5_step26.sh).
+int64_t nnls_repack_min_cols(bool two_lane) {
     // read on every call (cheap): tests lower it to drive small problems through the multi-pass path
     const char* e = getenv("SGL_NNLS_REPACK_MIN_COLS");
     const long long x = e ? atoll(e) : 0;
-    return (int64_t)(x > 0 ? x : (1 << 18));
+    return (int64_t)(x > 0 ? x : (two_lane ? (1 << 17) : (1 << 18)));
 }
 
 // Row stride of the padded Gram the lane kernel reads (nnls_lane.h): KP for the scalar-operand instances
 // (KP <= 40, kernels_nnls_lane1.hip), KP rounded up to 16 for the vector-load + DPP instances (lane2).
 int nnls_gram_stride(int KP) { return KP > 40 ? (KP + 15) / 16 * 16 : KP; }
-// padded rank of the lane kernel instance serving rank k (0: no instance, use the wave kernel)
-int nnls_lane_kp(int k) { return k <= 64 ? (k + 1) / 2 * 2 : (k <= SGL_LANE_NNLS_MAX_K ? (k + 7) / 8 * 8 : 0); }
+// Padded rank of the lane solve serving rank k (0: none, use the wave kernel).  Up to 64 one lane per column (nnls_lane.h),
+// even ranks; above, two lanes per column (nnls_half.h): the generated solve pads to multiples of 4 (k = 100 unpadded), the
+// compiled kernels, which serve what the generated one does not, to multiples of 8.
+int nnls_lane_kp(int k, double L1) {
+    if (k <= 64) return (k + 1) / 2 * 2;
+    if (k > SGL_LANE_NNLS_MAX_K) return 0;
+    const int kp4 = (k + 3) / 4 * 4;
+    return nnls_half_asm_has(kp4, L1) ? kp4 : (k + 7) / 8 * 8;
+}
 
-// 64 < k <= 128: two lanes per column, everything in registers (nnls_half.h; above 104 x sits in the AGPR half of the
-// register file); SGL_NNLS_NO_HALF=1 keeps the x-scratch instances
-static bool nnls_use_half(int KP) { return KP > 64 && KP <= 128 && !getenv("SGL_NNLS_NO_HALF"); }
-static bool nnls_needs_xt(int KP) { return KP > 64 && !nnls_use_half(KP); }
-
-int nnls_scratch_alloc(NnlsScratch& sc, int64_t cap, int k_for_xt) {
+int nnls_scratch_alloc(NnlsScratch& sc, int64_t cap, int k) {
     nnls_scratch_free(sc);
-    if (cap <= 0) return SGL_OK;
-    bool ok = true;
-    // x scratch of the k > 64 instances; lists / per-column state only where re-packing is used
-    if (nnls_needs_xt(nnls_lane_kp(k_for_xt))) ok = sgl_pool_malloc(&sc.xt, sizeof(double) * (size_t)cap * k_for_xt) == hipSuccess;
-    const bool two_lane = k_for_xt > 64 && nnls_use_half(nnls_lane_kp(k_for_xt));   // re-packs from half the columns (k_nnls_lane)
-    if (ok && cap >= ((two_lane && !getenv("SGL_NNLS_REPACK_MIN_COLS")) ? nnls_repack_min_cols() / 2 : nnls_repack_min_cols()))
-        ok = sgl_pool_malloc(&sc.list[0], sizeof(int32_t) * cap) == hipSuccess && sgl_pool_malloc(&sc.list[1], sizeof(int32_t) * cap) == hipSuccess &&
-             sgl_pool_malloc(&sc.counts, sizeof(uint32_t) * (SGL_NNLS_MAX_PASSES + 1)) == hipSuccess &&
-             sgl_pool_malloc(&sc.it_state, (size_t)cap) == hipSuccess && sgl_pool_malloc(&sc.tol_state, sizeof(double) * cap) == hipSuccess;
-    if (!ok) {
+    // lists / per-column state only where re-packing is used (k_nnls_lane)
+    if (cap < nnls_repack_min_cols(k > 64)) return SGL_OK;
+    if (sgl_pool_malloc(&sc.list[0], sizeof(int32_t) * cap) != hipSuccess || sgl_pool_malloc(&sc.list[1], sizeof(int32_t) * cap) != hipSuccess ||
+        sgl_pool_malloc(&sc.counts, sizeof(uint32_t) * (SGL_NNLS_MAX_PASSES + 1)) != hipSuccess ||
+        sgl_pool_malloc(&sc.it_state, (size_t)cap) != hipSuccess || sgl_pool_malloc(&sc.tol_state, sizeof(double) * cap) != hipSuccess) {
         (void)hipGetLastError();
         nnls_scratch_free(sc);
         sgl_set_error("NNLS scratch: out of device memory");
@@ -96,7 +87,6 @@ void nnls_scratch_free(NnlsScratch& sc) {
     if (sc.counts) (void)sgl_pool_free(sc.counts);
     if (sc.it_state) (void)sgl_pool_free(sc.it_state);
     if (sc.tol_state) (void)sgl_pool_free(sc.tol_state);
-    if (sc.xt) (void)sgl_pool_free(sc.xt);
     if (sc.prev_it) (void)sgl_pool_free(sc.prev_it);
     if (sc.packed) (void)sgl_pool_free(sc.packed);
     if (sc.sort_ws) (void)sgl_pool_free(sc.sort_ws);
@@ -194,50 +184,52 @@ int nnls_pack_alloc(NnlsScratch& sc, int64_t ncols) {
     return SGL_OK;
 }
 
+// columns 0 .. ncols - 1 in descending order of scr.prev_it: the three kernels of the counting sort write the list to
+// scr.packed and its length (= ncols) to the device word *count
+static int nnls_pack_order(hipStream_t s, const NnlsScratch& scr, int64_t ncols, const int32_t** order, const uint32_t** count) {
+    const int nblocks = (int)((ncols + SGL_PACK_CPB - 1) / SGL_PACK_CPB);
+    uint32_t* n_dev = scr.sort_ws + (size_t)SGL_PACK_BINS * nblocks;
+    nnls_pack_hist_kernel<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(scr.prev_it, ncols, nblocks, scr.sort_ws);
+    nnls_pack_scan_kernel<<<dim3(1), dim3(1024), 0, s>>>(scr.sort_ws, SGL_PACK_BINS * nblocks, n_dev);
+    nnls_pack_scatter_kernel<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(scr.prev_it, ncols, nblocks, scr.sort_ws, scr.packed);
+    HIPCHK(hipGetLastError());
+    *order = scr.packed;
+    if (count) *count = n_dev;
+    return SGL_OK;
+}
+
 int k_nnls_lane(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
                 int64_t ncols, double L1, double L2, unsigned long long* sweep_counter, const NnlsScratch* scr, bool pack_by_sweeps) {
     if (ncols <= 0) return SGL_OK;
-    auto launch_lane = nnls_lane_asm_has(KP, L1, ncols) ? k_nnls_lane_launch_asm
-                       : (KP <= 40) ? k_nnls_lane_launch1 : (KP <= 64 ? k_nnls_lane_launch2 : (KP <= 104 ? k_nnls_lane_launch3 : k_nnls_lane_launch4));
-    const bool half = nnls_use_half(KP);
-    const bool half_asm = half && nnls_half_asm_kp(k, L1) == KP;
-    auto launch = [&](hipStream_t s_, const double* Gp_, int KP_, double* B_, double* X_, const int64_t* nz_, int k_, int64_t nc_, double L1_,
-                      double L2_, unsigned long long* sw_, const NnlsPass& ps_, dim3 g_, dim3 b_) {
-        return half_asm ? k_nnls_half_launch_asm(s_, Gp_, KP_, B_, X_, nz_, k_, nc_, L1_, L2_, sw_, ps_)
-               : half ? k_nnls_half_launch(s_, Gp_, KP_, B_, X_, nz_, k_, nc_, L1_, L2_, sw_, ps_)
-                    : launch_lane(s_, Gp_, KP_, B_, X_, nz_, k_, nc_, L1_, L2_, sw_, ps_, g_, b_);
-    };
-    if (nnls_needs_xt(KP) && (scr == nullptr || scr->xt == nullptr || scr->cap < ncols)) {
-        sgl_set_error("k_nnls_lane: k > 64 needs the x scratch");
-        return SGL_ESTATE;
-    }
-    double* xt = nnls_needs_xt(KP) ? scr->xt : nullptr;
+    // the kernel serving KP (nnls_lane_kp): up to 64 one lane per column, the generated sweep where it has the instance;
+    // above, two lanes per column, generated where nnls_lane_kp padded for it, else compiled
+    const bool two_lane = KP > 64;
+    const bool half_asm = two_lane && nnls_half_asm_has(KP, L1);
+    auto launch_lane = nnls_lane_asm_has(KP, L1, ncols) ? k_nnls_lane_launch_asm : (KP <= 40) ? k_nnls_lane_launch1 : k_nnls_lane_launch2;
     const dim3 g((unsigned)((ncols + 255) / 256)), b(256);
-    // (the two-lane solves put 32 columns in a wave: the chip is as full at half the columns, and re-packing pays from there --
-    //  nnls_h per 200 000 columns k = 100 6.56 -> 6.16 ms, k = 128 11.44 -> 10.27; scripts/r5/r5_step26.sh)
-    const int64_t repack_min = (half && !getenv("SGL_NNLS_REPACK_MIN_COLS")) ? nnls_repack_min_cols() / 2 : nnls_repack_min_cols();
+    auto launch = [&](const NnlsPass& ps) {
+        return half_asm ? k_nnls_half_launch_asm(s, Gpad, KP, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps)
+               : two_lane ? k_nnls_half_launch(s, Gpad, KP, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps)
+                          : launch_lane(s, Gpad, KP, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps, g, b);
+    };
+    const int64_t repack_min = nnls_repack_min_cols(two_lane);
     const bool repack = scr != nullptr && scr->list[0] != nullptr && scr->cap >= ncols && ncols >= repack_min;
-    // first pass in descending order of the previous solve's sweep counts (lane instances up to k = 64 and the generated two-lane
-    // solve above; SGL_NNLS_NO_PACK: A/B)
-    const bool pack = pack_by_sweeps && (!half || half_asm) && scr != nullptr && scr->prev_it != nullptr && scr->pack_cap >= ncols && ncols >= 65536 &&
-                      !getenv("SGL_NNLS_NO_PACK");
+    // the solve keeps every column's sweep count (the packing key of the next solve) and, from 65 536 columns on, takes its
+    // first pass in descending order of the previous solve's counts: the one-lane kernels and the generated two-lane solve,
+    // not the compiled two-lane kernel (SGL_NNLS_NO_PACK: A/B)
+    uint8_t* const prev_it =
+        pack_by_sweeps && (!two_lane || half_asm) && scr != nullptr && scr->prev_it != nullptr && scr->pack_cap >= ncols ? scr->prev_it : nullptr;
     const int32_t* list0 = nullptr;
     const uint32_t* count0 = nullptr;
-    if (pack) {
-        const int nblocks = (int)((ncols + SGL_PACK_CPB - 1) / SGL_PACK_CPB);
-        uint32_t* n_dev = scr->sort_ws + (size_t)SGL_PACK_BINS * nblocks;
-        nnls_pack_hist_kernel<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(scr->prev_it, ncols, nblocks, scr->sort_ws);
-        nnls_pack_scan_kernel<<<dim3(1), dim3(1024), 0, s>>>(scr->sort_ws, SGL_PACK_BINS * nblocks, n_dev);
-        nnls_pack_scatter_kernel<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(scr->prev_it, ncols, nblocks, scr->sort_ws, scr->packed);
-        HIPCHK(hipGetLastError());
-        list0 = scr->packed;
-        count0 = n_dev;   // = ncols
-    }
-    uint8_t* prev_it = pack_by_sweeps && (!half || half_asm) && scr != nullptr && scr->prev_it != nullptr && scr->pack_cap >= ncols ? scr->prev_it : nullptr;
+    if (prev_it != nullptr && ncols >= 65536 && !getenv("SGL_NNLS_NO_PACK")) SGLCHK(nnls_pack_order(s, *scr, ncols, &list0, &count0));
     if (!repack) {
+        NnlsPass one = {};
+        one.list = list0;
+        one.count = count0;
         // fresh = 2: a packed single pass of one to two workgroups per CU may pair the longest waves with the shortest (kernels_nnls_asm.hip)
-        const NnlsPass one = {list0, count0, nullptr, nullptr, nullptr, nullptr, 0, xt, ncols, (list0 != nullptr && !getenv("SGL_NNLS_NO_SNAKE")) ? 2 : 1, prev_it};
-        SGLCHK(launch(s, Gpad, KP, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, one, g, b));
+        one.fresh = (list0 != nullptr && !getenv("SGL_NNLS_NO_SNAKE")) ? 2 : 1;
+        one.prev_it = prev_it;
+        SGLCHK(launch(one));
         HIPCHK(hipGetLastError());
         return SGL_OK;
     }
@@ -257,9 +249,7 @@ int k_nnls_lane(hipStream_t s, const double* Gpad, int KP, double* B, double* X,
         ps.it_state = scr->it_state;
         ps.tol_state = scr->tol_state;
         ps.final_below = (int32_t)std::min<int64_t>(64 * 1024, repack_min / 4);
-        ps.xt = xt;
-        ps.xt_stride = ncols;
-        SGLCHK(launch(s, Gpad, KP, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps, g, b));
+        SGLCHK(launch(ps));
         HIPCHK(hipGetLastError());
     }
     return SGL_OK;
@@ -639,15 +629,7 @@ int k_nnls_quarter_packed(hipStream_t s, const double* G, const double* B, doubl
                           double L2, unsigned long long* sweep_counter, const NnlsScratch* scr) {
     const bool pack = scr != nullptr && scr->prev_it != nullptr && scr->pack_cap >= ncols && !getenv("SGL_NNLS_NO_PACK");
     const int32_t* order = nullptr;
-    if (pack) {
-        const int nblocks = (int)((ncols + SGL_PACK_CPB - 1) / SGL_PACK_CPB);
-        uint32_t* n_dev = scr->sort_ws + (size_t)SGL_PACK_BINS * nblocks;
-        nnls_pack_hist_kernel<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(scr->prev_it, ncols, nblocks, scr->sort_ws);
-        nnls_pack_scan_kernel<<<dim3(1), dim3(1024), 0, s>>>(scr->sort_ws, SGL_PACK_BINS * nblocks, n_dev);
-        nnls_pack_scatter_kernel<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(scr->prev_it, ncols, nblocks, scr->sort_ws, scr->packed);
-        HIPCHK(hipGetLastError());
-        order = scr->packed;
-    }
+    if (pack) SGLCHK(nnls_pack_order(s, *scr, ncols, &order, nullptr));
     return k_nnls_quarter(s, G, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, order, pack ? scr->prev_it : nullptr);
 }
 

@@ -87,15 +87,14 @@
 
 SGL_NNLS_HALF_ASM_INSTANCES(SGL_DEFINE_NNLS_HALF_ASM_KERNEL)
 
-// padded rank of the generated two-lane solve serving rank k (0: none).  Instances are multiples of 4 -- k = 100 runs unpadded,
-// where the compiled kernels' multiples of 8 make it 104 -- and need L1 >= 0 (a padded coordinate is an exact no-op only then).
-int nnls_half_asm_kp(int k, double L1) {
-    if (k <= 64 || !(L1 >= 0.0) || getenv("SGL_NNLS_NO_ASM") || getenv("SGL_NNLS_NO_HALF")) return 0;
-    const int KP = (k + 3) / 4 * 4;
-#define SGL_NNLS_HALF_ASM_HAS(K_) if (KP == K_) return KP;
+// whether the generated two-lane solve serves padded rank KP.  Instances are multiples of 4 -- k = 100 runs unpadded, where the
+// compiled kernels' multiples of 8 make it 104 -- and need L1 >= 0 (a padded coordinate is an exact no-op only then).
+bool nnls_half_asm_has(int KP, double L1) {
+    if (!(L1 >= 0.0) || getenv("SGL_NNLS_NO_ASM")) return false;
+#define SGL_NNLS_HALF_ASM_HAS(K_) if (KP == K_) return true;
     SGL_NNLS_HALF_ASM_INSTANCES(SGL_NNLS_HALF_ASM_HAS)
 #undef SGL_NNLS_HALF_ASM_HAS
-    return 0;
+    return false;
 }
 
 int k_nnls_half_launch_asm(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,

@@ -12,13 +12,10 @@
 // packing; only the order in which columns land in the list varies from run to run.
 #pragma once
 #include "sgl_internal.h"
-// a wave leaves a pass when fewer than NUM / DEN of the lanes it started with are still iterating
-#ifndef SGL_NNLS_WPE
-#define SGL_NNLS_WPE 2   // minimum waves per SIMD the register allocation must allow
-#endif
 #ifndef SGL_NNLS_GRAM_LDS
 #define SGL_NNLS_GRAM_LDS 1
 #endif
+// a wave leaves a pass when fewer than NUM / DEN of the lanes it started with are still iterating
 #ifndef SGL_NNLS_REPACK_NUM
 #define SGL_NNLS_REPACK_NUM 3
 #define SGL_NNLS_REPACK_DEN 8
@@ -44,21 +41,19 @@ __device__ __forceinline__ double nnls_dpp_bcast(double g) {
     return __hiloint2double(rh, rl);
 }
 
-// XM = true (k > 64): x does not fit the register file next to b any more (4 k VGPRs): it lives in a
-// per-launch scratch xt[i * xt_stride + position] (coalesced over the lanes) and is read PF coordinates
-// ahead; b stays in VGPRs.
-template <int KP, bool GV, bool XM = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SGL_NNLS_WPE))) void nnls_lane_kernel(const double* __restrict__ Gpad, double* __restrict__ B,
+// k <= 64: b and x of a column both live in VGPRs (ranks above run two lanes per column, nnls_half.h).
+template <int KP, bool GV>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void nnls_lane_kernel(const double* __restrict__ Gpad, double* __restrict__ B,
                                                         double* __restrict__ X, const int64_t* __restrict__ col_nnz,
                                                         int k, int64_t ncols, double L1, double L2,
                                                         unsigned long long* __restrict__ sweep_counter, NnlsPass ps) {
     // columns of this pass: all of them (first pass) or the list written by the previous pass
     const int64_t n_in = ps.list ? (int64_t)*ps.count : ncols;
     if ((int64_t)blockIdx.x * blockDim.x >= n_in) return;
-    // GV, k <= 64: the padded Gram (rows 0 .. KP: the Gram and the reciprocals of its diagonal, (KP + 1) x GS doubles, 33 KB
+    // GV: the padded Gram (rows 0 .. KP: the Gram and the reciprocals of its diagonal, (KP + 1) x GS doubles, 33 KB
     // at KP = 64) is staged ONCE per workgroup in LDS and the sweeps read their rows from there: immediate offsets off one
     // per-lane base (no per-coordinate address arithmetic), LDS latency instead of the vector cache's.
-    constexpr bool GLDS = GV && !XM && SGL_NNLS_GRAM_LDS;
+    constexpr bool GLDS = GV && SGL_NNLS_GRAM_LDS;
     constexpr int GS_ = ((KP + 15) / 16) * 16;
     __shared__ double Gl[GLDS ? (KP + 1) * GS_ : 1];
     __shared__ __attribute__((aligned(16))) double Dl[GLDS ? 2 * KP : 2];   // (G_jj, 1 / G_jj) pairs: one uniform 16-byte read per coordinate
@@ -77,31 +72,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SGL_NNLS_WP
     const bool resume = ps.list != nullptr && !ps.fresh;   // a later pass: the column's state was saved by the previous one
     const bool valid = in_range && (resume || col_nnz == nullptr || col_nnz[col] != 0);
     const bool to_end = (ps.next_list == nullptr) || n_in <= (int64_t)ps.final_below;
-    constexpr int PF = XM ? 2 : 4;   // coordinates of x read ahead (XM)
-    // An instance serves KP - 1 <= k <= KP (KP - 7 <= k above 64): for the coordinates below KLOW the run-time test
+    // An instance serves KP - 1 <= k <= KP: for the coordinates below KLOW the run-time test
     // `i < k` is always true.  hipcc implemented it as a lane mask kept in (spilled) SGPRs -- ~10 instructions per
     // coordinate -- but simply dropping it makes the whole sweep ONE basic block, and then the register allocator
     // spills (368 B of scratch per lane at KP = 50 against 20, nnls_h 7.1 -> 10.7 ms at config 3).  So those
     // coordinates keep a branch, on an opaque always-true scalar: s_cmp + s_cbranch, no mask (nnls_h 6.6 -> 5.8 ms).
-    constexpr int KLOW = XM ? KP - 7 : KP - 1;
+    constexpr int KLOW = KP - 1;
     int one = 1;
-    constexpr bool G2 = !XM;          // one-row-ahead double buffer of the Gram rows (registers permitting)
-    double b[KP], x[XM ? PF : KP];
+    double b[KP], x[KP];
     double* bp = B + col * k;
     double* xp = X + col * k;
-    double* __restrict__ xt = XM ? ps.xt + gid : nullptr;  // this lane's column of the scratch
-    const int64_t xs = ps.xt_stride;
     static_for<KP>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         b[j] = (valid && j < k) ? bp[j] : 0.0;
-        if (!XM) x[j] = (valid && j < k) ? xp[j] : 0.0;
+        x[j] = (valid && j < k) ? xp[j] : 0.0;
     });
-    if (XM) {
-        // only lanes that own a column touch the scratch: a lane past the end of the list would land in
-        // another column's slot of the next row
-        if (valid)
-            for (int j = 0; j < k; ++j) xt[j * xs] = xp[j];
-    }
     const double kd = (double)k;
     double tol = 1.0;
     int it = 0;
@@ -130,57 +115,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SGL_NNLS_WP
         auto Gv = [&](int X) -> double { if constexpr (GLDS) return Gl[gl0 + X]; else return Gvg[X]; };
         // GV: explicit one-row-ahead software pipeline of the Gram rows (g2[parity]), fenced with
         // scheduling barriers: left alone, hipcc hoists the loads of dozens of rows of this straight-line
-        // code and spills (kilobytes of scratch per lane at k > 64).
+        // code and spills.
         // row KP of the padded Gram holds the correctly rounded reciprocals 1 / G_jj (k_pad_gram): the step
         // b_i / G_ii then costs a multiply and two FMAs instead of an 11-instruction IEEE division (below)
-        // (not in the k > 64 instances: they have no registers to spare -- measured 11 % slower at k = 100 -- and
-        // keep the division)
-        constexpr bool RCP = !XM;
-        double rrow[(GV && RCP && !GLDS) ? NG : 1];
-        if (GV && RCP && !GLDS) {
+        double rrow[(GV && !GLDS) ? NG : 1];
+        if (GV && !GLDS) {
 #pragma unroll
             for (int m = 0; m < NG; ++m) rrow[m] = Gv(KP * GS + 16 * m);
         }
         // GLDS: the diagonal pair of the coming coordinate, read (uniform address: a broadcast) one coordinate ahead
         double dnext0 = 0.0, dnext1 = 1.0;
         if (GLDS) { dnext0 = Dl[gofs]; dnext1 = Dl[gofs + 1]; }
-        double g2[G2 ? 2 : 1][NG];
-        if (GV && G2) {
+        double g2[2][NG];
+        if (GV) {
 #pragma unroll
             for (int m = 0; m < NG; ++m) g2[0][m] = Gv(16 * m);
-        }
-        if (XM) {  // the first PF coordinates of this sweep (slot = coordinate % PF)
-#pragma unroll
-            for (int q = 0; q < PF; ++q) x[q] = valid ? xt[q * xs] : 0.0;
         }
         static_for<KP>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             bool run_i = i < k;
             if (i < KLOW) { asm volatile("" : "+s"(one)); run_i = one != 0; }   // opaque, always true: keeps one basic block per coordinate
             if (run_i) {
-                const double xi = x[XM ? (i % PF) : i];
-                if (XM && (i + PF < KLOW || i + PF < k)) x[i % PF] = valid ? xt[(i + PF) * xs] : 0.0;  // x of coordinate i + PF (same slot)
+                const double xi = x[i];
                 double grow[NG];
                 double gii, rii;
                 if (GV) {
-                    if (G2) {
-                        if (i + 1 < KLOW || i + 1 < k) {
+                    if (i + 1 < KLOW || i + 1 < k) {
 #pragma unroll
-                            for (int m = 0; m < NG; ++m) g2[(i + 1) & 1][m] = Gv((i + 1) * GS + 16 * m);
-                        }
-                    } else {
-#pragma unroll
-                        for (int m = 0; m < NG; ++m) g2[0][m] = Gv(i * GS + 16 * m);
+                        for (int m = 0; m < NG; ++m) g2[(i + 1) & 1][m] = Gv((i + 1) * GS + 16 * m);
                     }
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int m = 0; m < NG; ++m) grow[m] = g2[G2 ? (i & 1) : 0][m];
+                    for (int m = 0; m < NG; ++m) grow[m] = g2[i & 1][m];
                     if (GLDS) {
                         gii = dnext0; rii = dnext1;
                         if (i + 1 < KP) { dnext0 = Dl[gofs + 2 * (i + 1)]; dnext1 = Dl[gofs + 2 * (i + 1) + 1]; }
                     } else {
                         gii = nnls_dpp_bcast<(i & 15)>(grow[i >> 4]);
-                        rii = RCP ? nnls_dpp_bcast<(i & 15)>(rrow[(RCP && !GLDS) ? (i >> 4) : 0]) : 0.0;
+                        rii = nnls_dpp_bcast<(i & 15)>(rrow[GLDS ? 0 : (i >> 4)]);
                     }
                 } else {
                     gii = Gs[i + KP * i];
@@ -188,22 +160,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SGL_NNLS_WP
                 }
                 // b_i / G_ii, correctly rounded, from the correctly rounded reciprocal (Markstein): q = RN(b r),
                 // rem = b - q G_ii exactly (FMA), RN(q + rem r).  G_ii is the same for all columns and sweeps.
-                double diff0;
-                if (RCP) {
-                    const double q0 = b[i] * rii;
-                    const double rem = fma(-q0, gii, b[i]);
-                    diff0 = fma(rem, rii, q0);
-                } else {
-                    diff0 = sgl_div_normal(b[i], gii);
-                }
+                const double q0 = b[i] * rii;
+                const double rem = fma(-q0, gii, b[i]);
+                const double diff0 = fma(rem, rii, q0);
                 // l.235-247 through sgl_nnls_step (branch-free; a stopped column takes a zero step)
                 double xv = xi;
                 const double nd = sgl_nnls_step(diff0, xv, tol, go, L1, L2);
-                if (XM) {
-                    if (go) xt[i * xs] = xv;
-                } else {
-                    x[i] = xv;
-                }
+                x[i] = xv;
                 static_for<KP>([&](auto jc) {
                     constexpr int j = decltype(jc)::value;
                     if (GV) nnls_dpp_fmac<(j & 15)>(b[j], grow[j >> 4], nd);
@@ -216,14 +179,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SGL_NNLS_WP
     }
     const bool unfinished = valid && it < 100 && (tol / kd) > 1e-8;  // only possible when !to_end
     if (valid) {
-        if (XM) {
-            for (int j = 0; j < k; ++j) xp[j] = xt[j * xs];
-        } else {
-            static_for<KP>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                if (j < k) xp[j] = x[j];
-            });
-        }
+        static_for<KP>([&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (j < k) xp[j] = x[j];
+        });
     }
     if (unfinished) {
         static_for<KP>([&](auto jc) {
@@ -257,5 +216,3 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SGL_NNLS_WP
 // free SGPRs).  nnls_gram_stride() in kernels_nnls.hip must agree.
 #define SGL_NNLS_CASE(K_, GV_) \
     case K_: nnls_lane_kernel<K_, GV_><<<g, b, 0, s>>>(Gpad, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps); break
-#define SGL_NNLS_CASE_XM(K_) \
-    case K_: nnls_lane_kernel<K_, true, true><<<g, b, 0, s>>>(Gpad, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps); break

@@ -12,7 +12,7 @@
 
 #define SGL_WAVE 64
 #define SGL_MAX_K 1024         // rank limit of the library: above 128 (plain fit) / 128 (masked fit) the generic kernels run
-#define SGL_LANE_NNLS_MAX_K 128  // lane-per-column NNLS: k <= 64 all in registers, k <= 128 with x in a memory scratch
+#define SGL_LANE_NNLS_MAX_K 128  // lane-per-column NNLS: one lane per column up to k = 64, two above; all in registers, no scratch
 
 void sgl_set_error(const char* fmt, ...);
 
@@ -105,8 +105,6 @@ struct NnlsPass {
     uint8_t* it_state;    // sweeps done so far, per column
     double* tol_state;    // running tol, per column
     int32_t final_below;  // a pass over at most this many columns runs them to the end
-    double* xt;           // k > 64: scratch holding x, xt[i * xt_stride + position in this pass]
-    int64_t xt_stride;
     int32_t fresh;        // list != nullptr but nothing to resume: a first pass over columns given in packing order (below)
     uint8_t* prev_it;     // sweeps a column needed, written when it stops: the packing key of the NEXT solve (nullptr: not kept)
 };
@@ -116,7 +114,6 @@ struct NnlsScratch {
     uint32_t* counts = nullptr;   // SGL_NNLS_MAX_PASSES + 1
     uint8_t* it_state = nullptr;
     double* tol_state = nullptr;
-    double* xt = nullptr;         // k x cap doubles when the fit's rank is above 64
     int64_t cap = 0;
     // packing by sweep count (H side of a plain fit): per column the sweeps of the previous solve, the columns in descending
     // order of it, and the counting sort's workspace
@@ -329,11 +326,11 @@ int k_graph_conv(hipStream_t s, DevGraph& g, const double* X, double* Y, int k);
 
 // NNLS
 #define SGL_NNLS_MAX_PASSES 10
-// below this many columns the GPU is not full anyway: one pass (env SGL_NNLS_REPACK_MIN_COLS overrides, tests)
-int64_t nnls_repack_min_cols();
+// below this many columns the GPU is not full anyway: one pass; 2^18, 2^17 for the two-lane solve (env SGL_NNLS_REPACK_MIN_COLS overrides, tests)
+int64_t nnls_repack_min_cols(bool two_lane);
 int nnls_gram_stride(int KP);  // row stride of the padded Gram the lane kernel expects
-int nnls_lane_kp(int k);
-int nnls_scratch_alloc(NnlsScratch& sc, int64_t cap, int k_for_xt);
+int nnls_lane_kp(int k, double L1);   // padded rank of the lane solve serving rank k <= SGL_LANE_NNLS_MAX_K
+int nnls_scratch_alloc(NnlsScratch& sc, int64_t cap, int k);
 void nnls_scratch_free(NnlsScratch& sc);
 // B is destroyed (and used as the spill space of b between passes).  scr == nullptr: one pass.
 int k_nnls_lane(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz,

@@ -139,7 +139,7 @@ def _dst_src0(code):
     return (parts[0].split()[0] if parts and parts[0] else ""), (parts[1].split()[0] if len(parts) > 1 and parts[1] else "")
 
 
-def test_nnls_dpp_operands_have_no_valu_write_hazard(tmp_path):
+def test_nnls_lane_kernel_dpp_operands_have_no_valu_write_hazard(tmp_path):
     """nnls_lane_kernel<KP, true> feeds the Gram to its FMAs with inline-asm DPP instructions.  A DPP read
     of a VGPR needs two wait states after a VALU write of it, and hipcc pads nothing around inline asm: the
     DPP source registers must come straight from vector loads.  Also: no scratch."""
@@ -150,7 +150,7 @@ def test_nnls_dpp_operands_have_no_valu_write_hazard(tmp_path):
                     "-I" + os.path.join(ROOT, "singlet_amd", "csrc"), "-S", "--cuda-device-only", "-o", out,
                     os.path.join(ROOT, "tests", "codegen", "nnls_lane_50.hip")], check=True, capture_output=True, timeout=600)
     text = open(out).read()
-    m = re.search(r"^_Z16nnls_lane_kernelILi50ELb1ELb0EE[^\n]*\n(.*?)s_endpgm", text, re.S | re.M)
+    m = re.search(r"^_Z16nnls_lane_kernelILi50ELb1EE[^\n]*\n(.*?)s_endpgm", text, re.S | re.M)
     assert m, "kernel not found"
     prev, n_dpp = [], 0
     for line in m.group(1).splitlines():
@@ -165,7 +165,7 @@ def test_nnls_dpp_operands_have_no_valu_write_hazard(tmp_path):
                     raise AssertionError("DPP hazard: %r followed by %r" % (pl, code))
         prev.append(code)
     assert n_dpp >= 50 * 50, "expected one DPP FMA per (coordinate, row entry)"
-    d = text.index(".amdhsa_kernel _Z16nnls_lane_kernelILi50ELb1ELb0EE")
+    d = text.index(".amdhsa_kernel _Z16nnls_lane_kernelILi50ELb1EE")
     ms = re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", text[d:d + 1500])
     assert ms and int(ms.group(1)) <= 64, "NNLS lane kernel <50> spills %s bytes per lane" % (ms.group(1) if ms else "?")
 
