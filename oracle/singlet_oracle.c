@@ -282,10 +282,14 @@ static void predict_mask(csc_t A, uint64_t seed, uint64_t inv_density, const dou
         /* wsub = submat(w, idx); asub = AAt(wsub); a_i = a - asub */
         double* wsub = (double*)malloc(sizeof(double) * (size_t)k * (size_t)(nidx > 0 ? nidx : 1));
         for (int64_t t = 0; t < nidx; ++t) memcpy(wsub + (size_t)t * k, F + (size_t)idx[t] * k, sizeof(double) * k);
-        double asub[k * k], a_i[k * k];
+        /* on the heap: two k x k arrays on the stack (16 MB at k = 1024) overflow a thread's stack above k ~ 700 */
+        double* asub = (double*)malloc(sizeof(double) * (size_t)k * k);
+        double* a_i = (double*)malloc(sizeof(double) * (size_t)k * k);
         ora_aat(wsub, k, nidx, asub);
         for (int t = 0; t < k * k; ++t) a_i[t] = a[t] - asub[t];
         nnls_col(a_i, b, X + (size_t)c * k, k, L1, L2);
+        free(a_i);
+        free(asub);
         free(wsub);
         free(idx);
     }
@@ -759,10 +763,14 @@ static void predict_mask_dense(const double* A, int64_t rows, int64_t cols, uint
         }
         double* wsub = (double*)malloc(sizeof(double) * (size_t)k * (size_t)(nidx > 0 ? nidx : 1));
         for (int64_t t = 0; t < nidx; ++t) memcpy(wsub + (size_t)t * k, F + (size_t)idx[t] * k, sizeof(double) * k);
-        double asub[k * k], a_i[k * k];
+        /* on the heap, as in predict_mask */
+        double* asub = (double*)malloc(sizeof(double) * (size_t)k * k);
+        double* a_i = (double*)malloc(sizeof(double) * (size_t)k * k);
         ora_aat(wsub, k, nidx, asub);
         for (int t = 0; t < k * k; ++t) a_i[t] = a[t] - asub[t];
         nnls_col(a_i, b, X + (size_t)c * k, k, L1, L2);
+        free(a_i);
+        free(asub);
         free(wsub);
         free(idx);
     }

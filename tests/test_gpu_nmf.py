@@ -21,8 +21,8 @@ def _check(got, ref, keys=("w", "h", "d")):
     (300, 400, 8, 0.0, 0.0, 5), (300, 400, 8, 0.01, 0.0, 5), (300, 400, 8, 0.01, 0.01, 5),
     (500, 260, 30, 0.01, 0.0, 4), (257, 1031, 50, 0.01, 0.0, 3), (200, 300, 1, 0.0, 0.0, 3),
     (150, 200, 64, 0.01, 0.0, 2), (150, 220, 70, 0.01, 0.0, 2),
-    # ranks above 64: two-part tiled accumulate, split Gram, lane NNLS with x in scratch (100), one wave per SIMD
-    # (120, 128), and above 128 the plain CSC accumulate + wave-per-column NNLS (130, 200)
+    # ranks above 64: two-part tiled accumulate, split Gram, two lanes per column in the NNLS (nnls_half.h: 100, and with x in
+    # AGPRs 120, 128), and above 128 the plain CSC accumulate + four columns per wave in the NNLS (nnls_quad_global_kernel: 130, 200)
     (260, 330, 100, 0.01, 0.0, 2), (250, 300, 120, 0.01, 0.0, 2), (270, 310, 128, 0.01, 0.01, 2),
     (280, 300, 130, 0.01, 0.0, 2), (300, 420, 200, 0.01, 0.0, 2),
     # above 256: the any-rank instances (16 coordinates per lane in the wave NNLS, Gram in several launches)

@@ -452,9 +452,10 @@ def _csc_from_dense(D):
     return np.concatenate(xs), np.concatenate(is_), np.array(p), nrow, ncol
 
 
-# every kernel family of the shared-Gram solve (kernels_nnls.hip dispatch): lane kernel with G as scalar operands (k <= 40),
-# DPP rows (42 - 64), x in memory scratch (66 - 104: instances 72, 80, 88, 96, 104), one wave per SIMD (112, 120, 128),
-# wave per column above 128 up to SGL_MAX_K
+# every kernel family of the shared-Gram solve (sgl_op_nnls, kernels_nnls.hip dispatch): one lane per column up to k = 64
+# (nnls_lane.h: G as scalar operands up to 40, DPP rows 42 - 64), two lanes per column for 65 - 128 (nnls_half.h, x in AGPRs
+# above 104), four columns per wave for 129 - 208 at this column count (nnls_quad_global_kernel<9 .. 13>), one wave per column
+# (nnls_wave_kernel) above, up to SGL_MAX_K
 @pytest.mark.parametrize("k", [2, 8, 10, 30, 40, 42, 50, 52, 64, 65, 72, 80, 88, 96, 100, 104, 105, 112, 120, 127, 128, 129, 200, 256, 257, 500])
 @pytest.mark.parametrize("L1,L2", [(0.0, 0.0), (0.01, 0.0), (0.01, 0.05)])
 def test_nnls(ctx, ora, k, L1, L2):
