@@ -6,7 +6,6 @@
 // The hash is the bit-exact uint64 rng of kernels_hash.hip.
 #include "sgl_internal.h"
 #include "nnls_static_for.h"
-#include <atomic>
 #include <hipcub/hipcub.hpp>
 #include <cstdlib>
 #include <utility>
@@ -359,13 +358,7 @@ static int launch_mask_gram_mfma(dim3 g, dim3 b, hipStream_t s, int64_t col0, in
                                  int64_t row_offset, double* Gcols, int raw) {
     constexpr int NTILES = (NT * (NT + 1) / 2 - PART + NPARTS - 1) / NPARTS, NB = NT + (REM > 0 ? 1 : 0);
     constexpr size_t lds = (size_t)MG_TB(NTILES, REM, NB) * 4 * 256 * sizeof(double);
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mask_gram_mfma_kernel<NT, NPARTS, PART, REM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    SGLCHK((sgl_allow_dynamic_lds<&mask_gram_mfma_kernel<NT, NPARTS, PART, REM>>((int)lds)));
     mask_gram_mfma_kernel<NT, NPARTS, PART, REM><<<g, b, lds, s>>>(col0, ncols, nrow, col_nnz, F, G, k, seed, dv, mask_t, col_offset, row_offset, Gcols, raw);
     return SGL_OK;
 }

@@ -17,7 +17,6 @@
 // arithmetic difference to an SSE2 build of the reference is FMA contraction of
 // b - G*delta.
 #include "sgl_internal.h"
-#include <atomic>
 #include "nnls_static_for.h"
 #include "nnls_quad_global.h"
 #include <algorithm>
@@ -300,7 +299,7 @@ __global__ __launch_bounds__(256) void nnls_wave_kernel(const double* __restrict
                     if (ir == r) { bsel = b[r]; xsel = x[r]; gsel = gd[r]; rsel = rg[r]; }
                 }
                 const double bi = rl64(bsel, il), xi = rl64(xsel, il), gii = rl64(gsel, il), rii = rl64(rsel, il);
-                // b_i / g_ii from the reciprocal (Markstein correction; see nnls_lane.h), then l.235-247
+                // b_i / g_ii from the reciprocal, then l.235-247
                 const double diff0 = sgl_nnls_quotient(bi, gii, rii, any_irr);
                 double xn = xi, dpen;
                 const double nd = sgl_nnls_nd_strict(diff0, xi, true, L1, L2, dpen);
@@ -322,10 +321,7 @@ __global__ __launch_bounds__(256) void nnls_wave_kernel(const double* __restrict
             if (j < k) X[col * k + j] = x[r];
         }
     }
-    if (sweep_counter != nullptr && lane == 0 && total_sweeps != 0) {
-        atomicAdd(sweep_counter, (unsigned long long)total_sweeps);
-        atomicAdd(sweep_counter + 2, (unsigned long long)total_sweeps);
-    }
+    sgl_nnls_book_sweeps<false>(sweep_counter, total_sweeps, total_sweeps);   // (the same count in every lane)
 }
 
 template <int J>
@@ -422,7 +418,7 @@ __global__ __launch_bounds__(64) void nnls_quad_kernel(const double* __restrict_
                         else if (r > ir) g[r] = tri[trij[r] + i];                // j > i: a[j, i]
                         else g[r] = tri[(l <= il) ? (ti + l + 16 * r) : (trij[r] + i)];
                     }
-                    const double diff0 = sgl_nnls_quotient(bi, gii, rii, any_irr);   // b_i / g_ii (Markstein, see nnls_lane.h)
+                    const double diff0 = sgl_nnls_quotient(bi, gii, rii, any_irr);   // b_i / g_ii
                     double dpen;
                     const double nd = sgl_nnls_nd_strict(diff0, xi, go, L1, L2, dpen);
                     if (__ballot(nd != 0.0) != 0ull) {   // at rest in all four columns: x, tol and b stay as they are
@@ -446,13 +442,7 @@ __global__ __launch_bounds__(64) void nnls_quad_kernel(const double* __restrict_
         }
         ran_total += ran;
     }
-    if (sweep_counter != nullptr) {
-        for (int off = 32; off > 0; off >>= 1) total_sweeps += __shfl_down(total_sweeps, off, 64);
-        if (lane == 0 && (total_sweeps != 0 || ran_total != 0)) {
-            atomicAdd(sweep_counter, (unsigned long long)total_sweeps);
-            atomicAdd(sweep_counter + 2, (unsigned long long)ran_total);
-        }
-    }
+    sgl_nnls_book_sweeps(sweep_counter, total_sweeps, ran_total);
 }
 
 // ---------------------------------------------------------------------------
@@ -524,8 +514,7 @@ __global__ __launch_bounds__(256) void nnls_quad_shared_kernel(const double* __r
                     nnls_row_bcast2<il>(b[ir], x[ir], bi, xi);
                     const double gii = dn0, rii = dn1;
                     if (i + 1 < 16 * NR) { dn0 = Dl[2 * (i + 1)]; dn1 = Dl[2 * (i + 1) + 1]; }
-                    const double q0 = bi * rii;
-                    const double diff0 = fma(fma(-q0, gii, bi), rii, q0);   // b_i / G_ii (Markstein, see nnls_lane.h)
+                    const double diff0 = sgl_nnls_markstein(bi, gii, rii);
                     double dpen;
                     const double nd = sgl_nnls_nd(diff0, xi, go, L1, L2, dpen);
                     if (__ballot(nd != 0.0) != 0ull) {   // at rest in all four columns: x, tol and b stay as they are
@@ -549,13 +538,7 @@ __global__ __launch_bounds__(256) void nnls_quad_shared_kernel(const double* __r
         }
         ran_total += ran;
     }
-    if (sweep_counter != nullptr) {
-        for (int off = 32; off > 0; off >>= 1) total_sweeps += __shfl_down(total_sweeps, off, 64);
-        if (lane == 0 && (total_sweeps != 0 || ran_total != 0)) {
-            atomicAdd(sweep_counter, (unsigned long long)total_sweeps);
-            atomicAdd(sweep_counter + 2, (unsigned long long)ran_total);
-        }
-    }
+    sgl_nnls_book_sweeps(sweep_counter, total_sweeps, ran_total);
 }
 
 template <int NR>
@@ -573,13 +556,11 @@ static int launch_nnls_quad_shared(hipStream_t s, const double* G, const double*
 int k_nnls_quad_shared(hipStream_t s, const double* G, const double* B, double* X, const int64_t* col_nnz, int k, int64_t ncols,
                        double L1, double L2, unsigned long long* sweep_counter) {
     if (ncols <= 0) return SGL_OK;
-    switch ((k + 15) / 16) {
-        case 1: return launch_nnls_quad_shared<1>(s, G, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        case 2: return launch_nnls_quad_shared<2>(s, G, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        case 3: return launch_nnls_quad_shared<3>(s, G, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        case 4: return launch_nnls_quad_shared<4>(s, G, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        default: sgl_set_error("k_nnls_quad_shared: k=%d above 64", k); return SGL_EINVAL;
-    }
+    const int nr = (k + 15) / 16;
+    if (nr < 1 || nr > 4) { sgl_set_error("k_nnls_quad_shared: k=%d above 64", k); return SGL_EINVAL; }
+    return sgl_rank_dispatch<1, 4>(nr, [&](auto c) {
+        return launch_nnls_quad_shared<decltype(c)::value>(s, G, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
+    });
 }
 
 template <int NR>
@@ -587,13 +568,7 @@ static int launch_nnls_quad(hipStream_t s, const double* G, int64_t gstride, con
                             int k, int64_t ncols, double L1, double L2, unsigned long long* sweep_counter) {
     const int TRI = k * (k + 1) / 2, TS = (TRI + 1) & ~1;
     const size_t lds = sizeof(double) * 4 * (size_t)TS;
-    static std::atomic<bool> attr_set[64];   // per (function, device); several host threads may drive devices at once
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (lds > 48 * 1024 && (dev < 0 || dev >= 64 || !attr_set[dev])) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nnls_quad_kernel<NR>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    if (lds > 48 * 1024) SGLCHK(sgl_allow_dynamic_lds<&nnls_quad_kernel<NR>>(80 * 1024));
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(16, (160 * 1024) / (int64_t)lds));
     const int64_t nquads = (ncols + 3) / 4;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(nquads, 256 * per_cu * 4));
@@ -653,12 +628,9 @@ int k_nnls_percol(hipStream_t s, const double* G, int64_t gstride, const double*
     const char* qfrom = getenv("SGL_NNLS_QUAD_GLOBAL_FROM");
     const int global_from = (qfrom && atoi(qfrom) > 0) ? atoi(qfrom) : (ncols >= long_launch ? 40 : 47);
     if (gstride != 0 && k < global_from && 4 * 4 * sizeof(double) * (size_t)(((k * (k + 1) / 2) + 1) & ~1) <= 160 * 1024 && !getenv("SGL_NNLS_NO_QUAD")) {
-        switch ((k + 15) / 16) {
-            case 1: return launch_nnls_quad<1>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            case 2: return launch_nnls_quad<2>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            case 3: return launch_nnls_quad<3>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            default: return launch_nnls_quad<4>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        }
+        return sgl_rank_dispatch<1, 4>((k + 15) / 16, [&](auto c) {
+            return launch_nnls_quad<decltype(c)::value>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
+        });
     }
     // per-column Grams above that, up to k = 112: four columns per wave on the Gram in global memory.  Measured per masked
     // iteration at 30 000 x 200 000 (nnls_h, ms; wave kernel -> this one): k = 56: 102 -> 50, 64: 119 -> 68, 80: 234 -> 122,
@@ -671,16 +643,9 @@ int k_nnls_percol(hipStream_t s, const double* G, int64_t gstride, const double*
     const int quad_global_max_k = (ncols >= long_launch && !getenv("SGL_NNLS_QUAD_GLOBAL_112")) ? 128 : 112;
     // (instance NR serves 16 (NR - 1) < k <= 16 NR: it runs coordinates 0 .. 16 (NR - 1) unconditionally and prefetches their rows)
     if (gstride != 0 && k <= quad_global_max_k && !getenv("SGL_NNLS_NO_QUAD_GLOBAL")) {
-        switch ((k + 15) / 16) {
-            case 1: return launch_nnls_quad_global<1>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            case 2: return launch_nnls_quad_global<2>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            case 3: return launch_nnls_quad_global<3>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            case 4: return launch_nnls_quad_global<4>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            case 5: return launch_nnls_quad_global<5>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            case 6: return launch_nnls_quad_global<6>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            case 7: return launch_nnls_quad_global<7>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-            default: return launch_nnls_quad_global<8>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        }
+        return sgl_rank_dispatch<1, 8>((k + 15) / 16, [&](auto c) {
+            return launch_nnls_quad_global<decltype(c)::value>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
+        });
     }
     // ranks 129 - 256 against a SHARED Gram: four LANES per column, 16 columns per wave (nnls_quarter.h) from 8192 columns
     // on (SGL_NNLS_QUARTER_MIN_COLS; SGL_NNLS_NO_QUARTER=1: never -- A/B, bit-identity tests); shorter launches and per-column

@@ -1,5 +1,5 @@
 // nnls (src/singlet.cpp:229-250), one lane per column, with the SWEEP as generated, hand-scheduled assembly
-// (gen_nnls_lane.py -> nnls_lane_gen.inc; round 5).  Same interface, same passes / packing protocol (NnlsPass) and the same
+// (gen_nnls_lane.py -> nnls_lane_gen.inc; round 5).  Same interface, same passes / packing protocol (nnls_static_for.h) and the same
 // arithmetic in the same order per column as nnls_lane_kernel<KP, true> (nnls_lane.h): bit-identical results.  What differs
 // is the schedule inside a sweep: the serial chain of a coordinate step is interleaved with the row-update FMAs of its
 // neighbours (header of gen_nnls_lane.py), which the compiler-scheduled kernel leaves to the chance overlap of the two waves
@@ -7,6 +7,7 @@
 // ONE asm statement whose clobbers they are (hipcc cannot be kept out of a register range below 64 ACROSS statements:
 // amdgpu_num_vgpr is not honoured, waves_per_eu caps at 64), the compiler keeps v[0 : V_T - 1] for the statement's operands.
 #include "sgl_internal.h"
+#include "nnls_static_for.h"
 #include "nnls_lane_gen.inc"
 
 #define SGL_DEFINE_NNLS_ASM_KERNEL(KP)                                                                                              \
@@ -15,7 +16,7 @@
         const int64_t* __restrict__ col_nnz, int k, int64_t ncols, double L1, double L2,                                           \
         unsigned long long* __restrict__ sweep_counter, NnlsPass ps) {                                                             \
         constexpr int NG = (KP + 15) / 16, NGP = NNLS_ASM_NGP_##KP, ROW = 16 * NGP;                                                \
-        const int64_t n_in = ps.list ? (int64_t)*ps.count : ncols;                                                                  \
+        const int64_t n_in = sgl_nnls_pass_size(ps, ncols);                                                                         \
         /* A packed single pass (columns in descending order of their previous sweep counts) of 257 ... 512 workgroups is ONE      */ \
         /* round of the chip, two workgroups per CU, and lasts as long as the SIMD whose two waves take longest: in launch order   */ \
         /* CU c would get the sorted workgroups c and c + 256 -- the longest with the next longest.  A SIMD's time is about         */ \
@@ -40,32 +41,24 @@
             Dl[2 * j + 1] = Gpad[KP * gs_in + j];   /* row KP of the padded Gram: the correctly rounded reciprocals */              \
         }                                                                                                                           \
         __syncthreads();                                                                                                            \
-        const int64_t gid = (int64_t)bx * blockDim.x + threadIdx.x;                                                                 \
-        const bool in_range = gid < n_in;                                                                                           \
-        const int64_t col = in_range ? (ps.list ? (int64_t)ps.list[gid] : gid) : 0;                                                 \
-        const bool resume = ps.list != nullptr && !ps.fresh;                                                                        \
-        const bool valid = in_range && (resume || col_nnz == nullptr || col_nnz[col] != 0);                                         \
-        const bool to_end = (ps.next_list == nullptr) || n_in <= (int64_t)ps.final_below;                                           \
-        double* const bp = B + col * k;                                                                                             \
-        double* const xp = X + col * k;                                                                                             \
+        const SglNnlsPassCol pc = sgl_nnls_pass_entry(ps, n_in, (int64_t)bx * blockDim.x + threadIdx.x, col_nnz);                   \
+        double* const bp = B + pc.col * k;                                                                                          \
+        double* const xp = X + pc.col * k;                                                                                          \
         typedef __attribute__((address_space(3))) char lds_char;                                                                    \
         const unsigned gl = (unsigned)(uintptr_t)(lds_char*)Gl + (unsigned)(threadIdx.x & 15) * (NGP * 8);                          \
         const unsigned dl = (unsigned)(uintptr_t)(lds_char*)Dl;                                                                     \
         const double kd = (double)k;                                                                                                \
-        double tol = 1.0;                                                                                                           \
-        int it = 0;                                                                                                                 \
-        if (valid && resume) {                                                                                                      \
-            tol = ps.tol_state[col];                                                                                                \
-            it = (int)ps.it_state[col];                                                                                             \
-        }                                                                                                                           \
+        double tol;                                                                                                                 \
+        int it;                                                                                                                     \
+        sgl_nnls_pass_state(ps, pc, tol, it);                                                                                       \
         /* the column's whole solve -- load b and x, sweep until every lane has stopped (or the pass re-packs), store x and the      \
            b of unfinished columns -- is ONE statement: its registers v[V_T : 255] are clobbers, nothing lives in them outside */   \
         int ran = 0, tlo = __double2loint(tol), thi = __double2hiint(tol);                                                          \
         unsigned long long um = 0ull;                                                                                               \
-        const unsigned long long vm = __ballot(valid);                                                                              \
+        const unsigned long long vm = __ballot(pc.valid);                                                                           \
         const double eps = 1e-15, thr = 1e-8;                                                                                       \
         const unsigned one_hi = 0x3ff00000u;                                                                                        \
-        const int toend_s = __builtin_amdgcn_readfirstlane(to_end ? 1 : 0), klast_s = __builtin_amdgcn_readfirstlane(k == KP ? 1 : 0); \
+        const int toend_s = __builtin_amdgcn_readfirstlane(pc.to_end ? 1 : 0), klast_s = __builtin_amdgcn_readfirstlane(k == KP ? 1 : 0); \
         asm volatile(NNLS_ASM_BODY_##KP                                                                                             \
                      : [it] "+v"(it), [lo] "+v"(tlo), [hi] "+v"(thi), [ran] "+s"(ran), [um] "=s"(um)                                \
                      : [bp] "v"(bp), [xp] "v"(xp), [gl] "v"(gl), [dl] "v"(dl), [one_hi] "v"(one_hi), [valid] "s"(vm),               \
@@ -75,27 +68,7 @@
                        "vcc", "scc", "memory");                                                                                     \
         tol = __hiloint2double(thi, tlo);                                                                                           \
         const bool unfinished = ((um >> (threadIdx.x & 63)) & 1ull) != 0ull; /* only possible when !to_end */                       \
-        if (unfinished) {                                                                                                           \
-            ps.tol_state[col] = tol;                                                                                                \
-            ps.it_state[col] = (uint8_t)it;                                                                                         \
-        }                                                                                                                           \
-        if (valid && !unfinished && ps.prev_it != nullptr) ps.prev_it[col] = (uint8_t)it; /* packing key of the next solve */       \
-        const unsigned long long um2 = __ballot(unfinished);                                                                        \
-        if (um2 != 0ull) { /* wave-aggregated append */                                                                             \
-            const int lane = threadIdx.x & 63;                                                                                      \
-            unsigned base = 0;                                                                                                      \
-            if (lane == 0) base = atomicAdd(ps.next_count, (unsigned)__popcll(um2));                                                \
-            base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);                                                             \
-            if (unfinished) ps.next_list[base + (unsigned)__popcll(um2 & ((1ull << lane) - 1ull))] = (int32_t)col;                  \
-        }                                                                                                                           \
-        if (sweep_counter != nullptr) {                                                                                             \
-            int s = (valid && !unfinished) ? it : 0; /* a column's sweeps are booked once, when it stops */                         \
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);                                                    \
-            if ((threadIdx.x & 63) == 0 && (s != 0 || ran != 0)) {                                                                  \
-                atomicAdd(sweep_counter, (unsigned long long)s);                                                                    \
-                atomicAdd(sweep_counter + 2, (unsigned long long)ran); /* sweeps this wave actually executed */                     \
-            }                                                                                                                       \
-        }                                                                                                                           \
+        sgl_nnls_pass_exit<~0ull>(ps, pc, unfinished, true, tol, it, ran, sweep_counter, [] {});                                    \
     }
 
 SGL_NNLS_ASM_INSTANCES(SGL_DEFINE_NNLS_ASM_KERNEL)

@@ -1,12 +1,12 @@
 // nnls (src/singlet.cpp:229-250) for 64 < k <= 128, TWO lanes per column, with the whole solve as generated, hand-scheduled
-// assembly (gen_nnls_half.py -> nnls_half_gen.inc; round 5).  Same interface, passes / packing protocol (NnlsPass) and results as
+// assembly (gen_nnls_half.py -> nnls_half_gen.inc; round 5).  Same interface, passes / packing protocol (nnls_static_for.h) and results as
 // nnls_half_kernel<KH> (nnls_half.h): lane c and lane 32 + c of a wave share column c of the wave's 32, the lower half-wave holds
 // coordinates 0 .. KH - 1 of b and x, the upper half KH .. 2 KH - 1.  What differs is inside the sweep (header of gen_nnls_half.py):
 // one half computes a coordinate's step, only nd crosses the halves, and the step's chain is interleaved with the row-update FMAs
 // of its neighbours.  As in kernels_nnls_asm.hip the solve is ONE asm statement whose clobbers b, x and its working set are.
 #include "sgl_internal.h"
+#include "nnls_static_for.h"
 #include "nnls_half_gen.inc"
-#include <atomic>
 
 #define SGL_DEFINE_NNLS_HALF_ASM_KERNEL(KP)                                                                                         \
     __global__ __launch_bounds__(NNLS_HALF_ASM_THREADS_##KP) __attribute__((amdgpu_waves_per_eu(NNLS_HALF_ASM_WAVES_##KP, NNLS_HALF_ASM_WAVES_##KP)))      \
@@ -14,7 +14,7 @@
                                    const int64_t* __restrict__ col_nnz, int k, int64_t ncols, double L1, double L2,                 \
                                    unsigned long long* __restrict__ sweep_counter, NnlsPass ps) {                                   \
         constexpr int KH = KP / 2, NGH = NNLS_HALF_ASM_NGH_##KP, NGHP = NNLS_HALF_ASM_NGHP_##KP, ROW = 32 * NGHP;                   \
-        const int64_t n_in = ps.list ? (int64_t)*ps.count : ncols;                                                                  \
+        const int64_t n_in = sgl_nnls_pass_size(ps, ncols);                                                                         \
         const int cpb = (int)(blockDim.x >> 1); /* columns per workgroup */                                                         \
         if ((int64_t)blockIdx.x * cpb >= n_in) return;                                                                              \
         extern __shared__ __attribute__((aligned(16))) double nnls_half_asm_lds[];                                                  \
@@ -30,31 +30,24 @@
         }                                                                                                                           \
         __syncthreads();                                                                                                            \
         const int lane = threadIdx.x & 63, half = lane >> 5;                                                                        \
-        const int64_t gid = (int64_t)blockIdx.x * cpb + (threadIdx.x >> 6) * 32 + (lane & 31);   /* position in this pass */         \
-        const bool in_range = gid < n_in;                                                                                           \
-        const int64_t col = in_range ? (ps.list ? (int64_t)ps.list[gid] : gid) : 0;                                                 \
-        const bool resume = ps.list != nullptr && !ps.fresh;                                                                        \
-        const bool valid = in_range && (resume || col_nnz == nullptr || col_nnz[col] != 0);                                         \
-        const bool to_end = (ps.next_list == nullptr) || n_in <= (int64_t)ps.final_below;                                           \
-        double* const bp = B + col * k + half * KH;                                                                                 \
-        double* const xp = X + col * k + half * KH;                                                                                 \
+        const int64_t gid = (int64_t)blockIdx.x * cpb + (threadIdx.x >> 6) * 32 + (lane & 31);   /* position in this pass */        \
+        const SglNnlsPassCol pc = sgl_nnls_pass_entry(ps, n_in, gid, col_nnz);                                                      \
+        double* const bp = B + pc.col * k + half * KH;                                                                              \
+        double* const xp = X + pc.col * k + half * KH;                                                                              \
         const unsigned kh = (unsigned)(half ? k - KH : KH);   /* coordinates this lane holds */                                     \
         typedef __attribute__((address_space(3))) char lds_char;                                                                    \
         const unsigned gl = (unsigned)(uintptr_t)(lds_char*)Gl + (unsigned)(half * 16 + (lane & 15)) * (NGHP * 8);                  \
         const unsigned dl = (unsigned)(uintptr_t)(lds_char*)Dl;                                                                     \
         const double kd = (double)k;                                                                                                \
-        double tol = 1.0;                                                                                                           \
-        int it = 0;                                                                                                                 \
-        if (valid && resume) {                                                                                                      \
-            tol = ps.tol_state[col];                                                                                                \
-            it = (int)ps.it_state[col];                                                                                             \
-        }                                                                                                                           \
+        double tol;                                                                                                                 \
+        int it;                                                                                                                     \
+        sgl_nnls_pass_state(ps, pc, tol, it);                                                                                       \
         int ran = 0, tlo = __double2loint(tol), thi = __double2hiint(tol);                                                          \
         unsigned long long um = 0ull;                                                                                               \
-        const unsigned long long vm = __ballot(valid);                                                                              \
+        const unsigned long long vm = __ballot(pc.valid);                                                                           \
         const double eps = 1e-15, thr = 1e-8;                                                                                       \
         const unsigned one_hi = 0x3ff00000u;                                                                                        \
-        const int toend_s = __builtin_amdgcn_readfirstlane(to_end ? 1 : 0);                                                         \
+        const int toend_s = __builtin_amdgcn_readfirstlane(pc.to_end ? 1 : 0);                                                      \
         asm volatile(NNLS_HALF_ASM_BODY_##KP                                                                                        \
                      : [it] "+v"(it), [lo] "+v"(tlo), [hi] "+v"(thi), [ran] "+s"(ran), [um] "=s"(um)                                \
                      : [bp] "v"(bp), [xp] "v"(xp), [gl] "v"(gl), [dl] "v"(dl), [one_hi] "v"(one_hi), [kh] "v"(kh), [valid] "s"(vm), \
@@ -63,26 +56,7 @@
                        "s51", "vcc", "scc", "memory");                                                                              \
         tol = __hiloint2double(thi, tlo);                                                                                           \
         const bool unfinished = ((um >> lane) & 1ull) != 0ull; /* only possible when !to_end; both lanes of a column agree */       \
-        if (unfinished && half == 0) {                                                                                              \
-            ps.tol_state[col] = tol;                                                                                                \
-            ps.it_state[col] = (uint8_t)it;                                                                                         \
-        }                                                                                                                           \
-        if (valid && !unfinished && half == 0 && ps.prev_it != nullptr) ps.prev_it[col] = (uint8_t)it; /* packing key of the next solve */ \
-        const unsigned long long um2 = __ballot(unfinished) & 0xffffffffull;                                                        \
-        if (um2 != 0ull) { /* wave-aggregated append (the lower half-wave speaks for the columns) */                                \
-            unsigned base = 0;                                                                                                      \
-            if (lane == 0) base = atomicAdd(ps.next_count, (unsigned)__popcll(um2));                                                \
-            base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);                                                             \
-            if (unfinished && half == 0) ps.next_list[base + (unsigned)__popcll(um2 & ((1ull << lane) - 1ull))] = (int32_t)col;    \
-        }                                                                                                                           \
-        if (sweep_counter != nullptr) {                                                                                             \
-            int s = (valid && !unfinished && half == 0) ? it : 0; /* a column's sweeps are booked once, when it stops */            \
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);                                                    \
-            if (lane == 0 && (s != 0 || ran != 0)) {                                                                                \
-                atomicAdd(sweep_counter, (unsigned long long)s);                                                                    \
-                atomicAdd(sweep_counter + 2, (unsigned long long)ran); /* sweeps this wave actually executed */                     \
-            }                                                                                                                       \
-        }                                                                                                                           \
+        sgl_nnls_pass_exit<0xffffffffull>(ps, pc, unfinished, half == 0, tol, it, ran, sweep_counter, [] {});                       \
     }
 
 SGL_NNLS_HALF_ASM_INSTANCES(SGL_DEFINE_NNLS_HALF_ASM_KERNEL)
@@ -100,8 +74,6 @@ bool nnls_half_asm_has(int KP, double L1) {
 int k_nnls_half_launch_asm(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
                            int64_t ncols, double L1, double L2, unsigned long long* sweep_counter, const NnlsPass& ps) {
     const int gs_in = nnls_gram_stride(KP);
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
 #define SGL_NNLS_HALF_ASM_CASE(K_)                                                                                                  \
     if (KP == K_) {                                                                                                                 \
         const size_t lds = sizeof(double) * ((size_t)K_ * 32 * NNLS_HALF_ASM_NGHP_##K_ + 2 * K_);                                   \
@@ -109,12 +81,7 @@ int k_nnls_half_launch_asm(hipStream_t s, const double* Gpad, int KP, double* B,
         /* there are columns enough, 256 below                                                                                   */ \
         const int cpb = (2 * lds > 160 * 1024 && ncols >= 256 * 256 && NNLS_HALF_ASM_WAVES_##K_ > 1) ? 256 : 128;                   \
         const dim3 g((unsigned)((ncols + cpb - 1) / cpb)), b(2 * cpb);                                                              \
-        static std::atomic<bool> attr_set[64];                                                                                      \
-        if (dev < 0 || dev >= 64 || !attr_set[dev]) {                                                                               \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nnls_half_asm_kernel_##K_),                                   \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                     \
-            if (dev >= 0 && dev < 64) attr_set[dev] = true;                                                                         \
-        }                                                                                                                           \
+        SGLCHK(sgl_allow_dynamic_lds<&nnls_half_asm_kernel_##K_>((int)lds));                                                        \
         nnls_half_asm_kernel_##K_<<<g, b, lds, s>>>(Gpad, gs_in, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps);               \
         HIPCHK(hipGetLastError());                                                                                                  \
         return SGL_OK;                                                                                                              \

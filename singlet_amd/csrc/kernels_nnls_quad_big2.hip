@@ -5,11 +5,9 @@
 
 int k_nnls_quad_global_big2(hipStream_t s, const double* G, int64_t gstride, const double* B, double* X, const int64_t* col_nnz, int k,
                             int64_t ncols, double L1, double L2, unsigned long long* sweep_counter) {
-    switch ((k + 15) / 16) {
-        case 13: return launch_nnls_quad_global<13>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        case 14: return launch_nnls_quad_global<14>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        case 15: return launch_nnls_quad_global<15>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        case 16: return launch_nnls_quad_global<16>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
-        default: sgl_set_error("k_nnls_quad_global_big: k=%d outside this part's ranks", k); return SGL_EINVAL;
-    }
+    const int nr = (k + 15) / 16;
+    if (nr < 13 || nr > 16) { sgl_set_error("k_nnls_quad_global_big: k=%d outside this part's ranks", k); return SGL_EINVAL; }
+    return sgl_rank_dispatch<13, 16>(nr, [&](auto c) {
+        return launch_nnls_quad_global<decltype(c)::value>(s, G, gstride, B, X, col_nnz, k, ncols, L1, L2, sweep_counter);
+    });
 }

@@ -48,7 +48,6 @@
 // the tile range is split over blockIdx.y; each split writes a partial k x ncol
 // slab and acc_tiled_reduce sums the slabs in a fixed order.
 #include "sgl_internal.h"
-#include <atomic>
 #include <hipcub/hipcub.hpp>
 #include <stdlib.h>
 #include <utility>
@@ -949,17 +948,8 @@ int k_acc_tiled(hipStream_t s, const DevTiled& S, const double* F, int ldf, doub
     if (kf <= 0 || kf > S.k) { sgl_set_error("k_acc_tiled: bad part size %d (stream built for %d)", kf, S.k); return SGL_EINVAL; }
     const int KS = S.KS;
     const size_t lds = S.NSL == 4 ? (size_t)TILED_LDS_BYTES + 512 : (size_t)S.TR * KS * 8 + 512;
-    // the attribute belongs to the (function, device) pair: one process may drive several devices
-    static std::atomic<bool> attr_set[64];   // several host threads may drive devices at once (replica sweep)
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&acc_tiled_kernel<2>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, TILED_LDS_BYTES + 512));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&acc_tiled_kernel<4>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, TILED_LDS_BYTES + 512));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    SGLCHK(sgl_allow_dynamic_lds<&acc_tiled_kernel<2>>(TILED_LDS_BYTES + 512));
+    SGLCHK(sgl_allow_dynamic_lds<&acc_tiled_kernel<4>>(TILED_LDS_BYTES + 512));
     const int64_t nwg_x = (S.nwb + TILED_NW - 1) / TILED_NW;
     const bool slabs = S.R > 1;
     double* out = slabs ? S.part : B;

@@ -436,13 +436,7 @@ static int launch_mask_gram_list(dim3 g, dim3 b, hipStream_t s, int64_t col0, in
                                  const double* F, const double* G, int k, double* Gcols, int raw) {
     constexpr int NTILES = (NT * (NT + 1) / 2 - PART + NPARTS - 1) / NPARTS, NB = NT + ((REM > 0 || REMV > 0) ? 1 : 0);
     constexpr size_t lds = (size_t)MG_TB(NTILES, (REMV > 0 ? 4 : REM), NB) * 4 * 256 * sizeof(double);   // REMV: batches of four rows x NB blocks
-    static std::atomic<bool> attr_set[64];
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mask_gram_list_kernel<NT, NPARTS, PART, REM, REMV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    SGLCHK((sgl_allow_dynamic_lds<&mask_gram_list_kernel<NT, NPARTS, PART, REM, REMV>>((int)lds)));
     mask_gram_list_kernel<NT, NPARTS, PART, REM, REMV><<<g, b, lds, s>>>(col0, ncols, col_nnz, L->ptr, L->idx, F, G, k, Gcols, raw,
                                                                    reinterpret_cast<const double*>(L->ptr + L->ncol + 1));
     return SGL_OK;

@@ -9,14 +9,10 @@
 // same step (tol stays consistent), and each lane updates its KH entries of b.  The Gram is staged in LDS as in nnls_lane.h;
 // a lane reads the 16-entry pieces of ITS half of row i, so the DPP row broadcast of FMA jj delivers G[i, jj] to the lower
 // half and G[i, KH + jj] to the upper.  Same operations in the same order per column: bit-identical to the oracle's sweeps.
-// Re-packing passes as in nnls_lane.h (NnlsPass), 32 columns per wave.
+// Re-packing passes (nnls_static_for.h), 32 columns per wave.
 #pragma once
 #include "sgl_internal.h"
 #include "nnls_static_for.h"
-#ifndef SGL_NNLS_REPACK_NUM
-#define SGL_NNLS_REPACK_NUM 3
-#define SGL_NNLS_REPACK_DEN 8
-#endif
 
 #ifndef SGL_HALF_G2
 #define SGL_HALF_G2 1
@@ -71,7 +67,7 @@ __global__ __launch_bounds__(KH > 52 ? 256 : 512) __attribute__((amdgpu_waves_pe
     constexpr bool G2 = SGL_HALF_G2 != 0 && KH <= 48;   // Gram rows one coordinate ahead (registers permitting)
     constexpr bool XA = KH > 52;                        // x in named AGPRs (one wave per SIMD)
     if constexpr (XA) half_xa_reserve<KH>();
-    const int64_t n_in = ps.list ? (int64_t)*ps.count : ncols;
+    const int64_t n_in = sgl_nnls_pass_size(ps, ncols);
     const int cpb = (int)(blockDim.x >> 1);   // columns per workgroup
     if ((int64_t)blockIdx.x * cpb >= n_in) return;
     extern __shared__ __attribute__((aligned(16))) double nnls_half_lds[];
@@ -85,11 +81,9 @@ __global__ __launch_bounds__(KH > 52 ? 256 : 512) __attribute__((amdgpu_waves_pe
     __syncthreads();
     const int lane = threadIdx.x & 63, half = lane >> 5;
     const int64_t gid = (int64_t)blockIdx.x * cpb + (threadIdx.x >> 6) * 32 + (lane & 31);   // position in this pass
-    const bool in_range = gid < n_in;
-    const int64_t col = in_range ? (ps.list ? (int64_t)ps.list[gid] : gid) : 0;
-    const bool resume = ps.list != nullptr && !ps.fresh;
-    const bool valid = in_range && (resume || col_nnz == nullptr || col_nnz[col] != 0);
-    const bool to_end = (ps.next_list == nullptr) || n_in <= (int64_t)ps.final_below;
+    const SglNnlsPassCol pc = sgl_nnls_pass_entry(ps, n_in, gid, col_nnz);
+    const int64_t col = pc.col;
+    const bool valid = pc.valid, to_end = pc.to_end;
     constexpr int KLOW = KP - 7;   // coordinates below it always exist (an instance serves KP - 7 <= k <= KP)
     int one = 1;
     double b[KH], x[XA ? 1 : KH];
@@ -103,12 +97,9 @@ __global__ __launch_bounds__(KH > 52 ? 256 : 512) __attribute__((amdgpu_waves_pe
         if constexpr (XA) half_xa_write<j>(x0); else x[j] = x0;
     });
     const double kd = (double)k;
-    double tol = 1.0;
-    int it = 0;
-    if (valid && resume) {
-        tol = ps.tol_state[col];
-        it = (int)ps.it_state[col];
-    }
+    double tol;
+    int it;
+    sgl_nnls_pass_state(ps, pc, tol, it);
     int gofs = 0, ran = 0;
     const int n_act0 = __popcll(__ballot(valid && it < 100 && (tol / kd) > 1e-8) & 0xffffffffull);
     const int gbase = half * KH + (lane & 15);   // this lane's piece of a Gram row
@@ -153,10 +144,7 @@ __global__ __launch_bounds__(KH > 52 ? 256 : 512) __attribute__((amdgpu_waves_pe
                 half_bcast(b[ii], blo, bhi);
                 half_bcast(xown, xlo, xhi);
                 const double bi = owner ? bhi : blo, xi = owner ? xhi : xlo;
-                // b_i / G_ii, correctly rounded, from the correctly rounded reciprocal (Markstein; see nnls_lane.h)
-                const double q0 = bi * rii;
-                const double rem = fma(-q0, gii, bi);
-                const double diff0 = fma(rem, rii, q0);
+                const double diff0 = sgl_nnls_markstein(bi, gii, rii);
                 double xv = xi;
                 const double nd = sgl_nnls_step(diff0, xv, tol, go, L1, L2);
                 const double xnew = (half == owner) ? xv : xown;
@@ -181,29 +169,11 @@ __global__ __launch_bounds__(KH > 52 ? 256 : 512) __attribute__((amdgpu_waves_pe
     } else if constexpr (XA) {
         asm volatile("" ::: "memory");
     }
-    if (unfinished) {
+    // (the lower half-wave speaks for the columns)
+    sgl_nnls_pass_exit<0xffffffffull>(ps, pc, unfinished, half == 0, tol, it, ran, sweep_counter, [&] {
         static_for<KH>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             if (j < kh) bp[j] = b[j];
         });
-        if (half == 0) {
-            ps.tol_state[col] = tol;
-            ps.it_state[col] = (uint8_t)it;
-        }
-    }
-    const unsigned long long um = __ballot(unfinished) & 0xffffffffull;
-    if (um != 0ull) {  // wave-aggregated append (the lower half-wave speaks for the columns)
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(ps.next_count, (unsigned)__popcll(um));
-        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-        if (unfinished && half == 0) ps.next_list[base + (unsigned)__popcll(um & ((1ull << lane) - 1ull))] = (int32_t)col;
-    }
-    if (sweep_counter != nullptr) {
-        int s = (valid && !unfinished && half == 0) ? it : 0;  // a column's sweeps are booked once, when it stops
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        if (lane == 0 && (s != 0 || ran != 0)) {
-            atomicAdd(sweep_counter, (unsigned long long)s);
-            atomicAdd(sweep_counter + 2, (unsigned long long)ran);  // sweeps this wave actually executed
-        }
-    }
+    });
 }

@@ -1,24 +1,10 @@
 // nnls_lane_kernel<KP>: nnls (src/singlet.cpp:229-250) with ONE LANE PER COLUMN (see kernels_nnls.hip
-// for the two mappings).  Included by kernels_nnls_lane{1,2}.hip, which instantiate disjoint sets of
-// KP so that the (long) compiles run in parallel.
-//
-// Re-packing.  Lanes of a wave run in lock-step, so a wave is busy until its slowest column stops:
-// at config 3 the columns need 31 sweeps on average but a wave runs 46.  The solve is therefore
-// done in PASSES: a wave leaves a pass as soon as fewer than 3/8 of the lanes it started with are
-// still iterating, writes the state of the unfinished columns back (b in place in B, x, the sweep
-// count and the running tol) and appends them to a list; the next pass runs the listed columns
-// densely packed.  A column's own sequence of sweeps is unchanged (same order, same arithmetic, same
-// stop test after every sweep), so results are bit-identical to the one-pass kernel whatever the
-// packing; only the order in which columns land in the list varies from run to run.
+// for the two mappings), in re-packing passes (nnls_static_for.h).  Included by kernels_nnls_lane{1,2}.hip,
+// which instantiate disjoint sets of KP so that the (long) compiles run in parallel.
 #pragma once
 #include "sgl_internal.h"
 #ifndef SGL_NNLS_GRAM_LDS
 #define SGL_NNLS_GRAM_LDS 1
-#endif
-// a wave leaves a pass when fewer than NUM / DEN of the lanes it started with are still iterating
-#ifndef SGL_NNLS_REPACK_NUM
-#define SGL_NNLS_REPACK_NUM 3
-#define SGL_NNLS_REPACK_DEN 8
 #endif
 
 #include "nnls_static_for.h"
@@ -47,8 +33,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
                                                         double* __restrict__ X, const int64_t* __restrict__ col_nnz,
                                                         int k, int64_t ncols, double L1, double L2,
                                                         unsigned long long* __restrict__ sweep_counter, NnlsPass ps) {
-    // columns of this pass: all of them (first pass) or the list written by the previous pass
-    const int64_t n_in = ps.list ? (int64_t)*ps.count : ncols;
+    const int64_t n_in = sgl_nnls_pass_size(ps, ncols);
     if ((int64_t)blockIdx.x * blockDim.x >= n_in) return;
     // GV: the padded Gram (rows 0 .. KP: the Gram and the reciprocals of its diagonal, (KP + 1) x GS doubles, 33 KB
     // at KP = 64) is staged ONCE per workgroup in LDS and the sweeps read their rows from there: immediate offsets off one
@@ -65,13 +50,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
         }
         __syncthreads();
     }
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool in_range = gid < n_in;
-    const int64_t col = in_range ? (ps.list ? (int64_t)ps.list[gid] : gid) : 0;
-    // empty columns are skipped and keep their stale values (src/singlet.cpp:340)
-    const bool resume = ps.list != nullptr && !ps.fresh;   // a later pass: the column's state was saved by the previous one
-    const bool valid = in_range && (resume || col_nnz == nullptr || col_nnz[col] != 0);
-    const bool to_end = (ps.next_list == nullptr) || n_in <= (int64_t)ps.final_below;
+    const SglNnlsPassCol pc = sgl_nnls_pass_entry(ps, n_in, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, col_nnz);
+    const int64_t col = pc.col;
+    const bool valid = pc.valid, to_end = pc.to_end;
     // An instance serves KP - 1 <= k <= KP: for the coordinates below KLOW the run-time test
     // `i < k` is always true.  hipcc implemented it as a lane mask kept in (spilled) SGPRs -- ~10 instructions per
     // coordinate -- but simply dropping it makes the whole sweep ONE basic block, and then the register allocator
@@ -88,12 +69,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
         x[j] = (valid && j < k) ? xp[j] : 0.0;
     });
     const double kd = (double)k;
-    double tol = 1.0;
-    int it = 0;
-    if (valid && resume) {
-        tol = ps.tol_state[col];
-        it = (int)ps.it_state[col];
-    }
+    double tol;
+    int it;
+    sgl_nnls_pass_state(ps, pc, tol, it);
     int gofs = 0, ran = 0;
     const int n_act0 = __popcll(__ballot(valid && it < 100 && (tol / kd) > 1e-8));
     while (true) {
@@ -158,11 +136,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
                     gii = Gs[i + KP * i];
                     rii = Gs[KP * KP + i];
                 }
-                // b_i / G_ii, correctly rounded, from the correctly rounded reciprocal (Markstein): q = RN(b r),
-                // rem = b - q G_ii exactly (FMA), RN(q + rem r).  G_ii is the same for all columns and sweeps.
-                const double q0 = b[i] * rii;
-                const double rem = fma(-q0, gii, b[i]);
-                const double diff0 = fma(rem, rii, q0);
+                const double diff0 = sgl_nnls_markstein(b[i], gii, rii);
                 // l.235-247 through sgl_nnls_step (branch-free; a stopped column takes a zero step)
                 double xv = xi;
                 const double nd = sgl_nnls_step(diff0, xv, tol, go, L1, L2);
@@ -184,35 +158,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void n
             if (j < k) xp[j] = x[j];
         });
     }
-    if (unfinished) {
+    sgl_nnls_pass_exit<~0ull>(ps, pc, unfinished, true, tol, it, ran, sweep_counter, [&] {
         static_for<KP>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             if (j < k) bp[j] = b[j];
         });
-        ps.tol_state[col] = tol;
-        ps.it_state[col] = (uint8_t)it;
-    }
-    if (valid && !unfinished && ps.prev_it != nullptr) ps.prev_it[col] = (uint8_t)it;   // packing key of the next solve
-    const unsigned long long um = __ballot(unfinished);
-    if (um != 0ull) {  // wave-aggregated append
-        const int lane = threadIdx.x & 63;
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(ps.next_count, (unsigned)__popcll(um));
-        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-        if (unfinished) ps.next_list[base + (unsigned)__popcll(um & ((1ull << lane) - 1ull))] = (int32_t)col;
-    }
-    if (sweep_counter != nullptr) {
-        int s = (valid && !unfinished) ? it : 0;  // a column's sweeps are booked once, when it stops
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-        if ((threadIdx.x & 63) == 0 && (s != 0 || ran != 0)) {
-            atomicAdd(sweep_counter, (unsigned long long)s);
-            atomicAdd(sweep_counter + 2, (unsigned long long)ran);  // sweeps this wave actually executed
-        }
-    }
+    });
 }
 
-// GV_ is fixed per translation unit: scalar operands up to KP = 40 (3-10 % faster there), vector loads +
-// DPP broadcast from KP = 42 (11 % faster at k = 50, 2.3x at k = 56 .. 64, where a row no longer fits the
+// the instances for the even KP in [KLO, KHI].  GV is fixed per translation unit: scalar operands up to KP = 40 (3-10 % faster
+// there), vector loads + DPP broadcast from KP = 42 (11 % faster at k = 50, 2.3x at k = 56 .. 64, where a row no longer fits the
 // free SGPRs).  nnls_gram_stride() in kernels_nnls.hip must agree.
-#define SGL_NNLS_CASE(K_, GV_) \
-    case K_: nnls_lane_kernel<K_, GV_><<<g, b, 0, s>>>(Gpad, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps); break
+template <int KLO, int KHI, bool GV>
+static int nnls_lane_launch(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k, int64_t ncols,
+                            double L1, double L2, unsigned long long* sweep_counter, const NnlsPass& ps, dim3 g, dim3 b) {
+    if (KP % 2 != 0 || KP < KLO || KP > KHI) { sgl_set_error("k_nnls_lane: unsupported KP=%d", KP); return SGL_EINVAL; }
+    return sgl_rank_dispatch<KLO / 2, KHI / 2>(KP / 2, [&](auto h) {
+        nnls_lane_kernel<2 * decltype(h)::value, GV><<<g, b, 0, s>>>(Gpad, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps);
+        return SGL_OK;
+    });
+}

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NR <= 8 ? SG
                     nnls_row_bcast2<il>(b[ir], x[ir], bi, xi);
                     const double gii = dn0, rii = dn1;
                     if (i + 1 < 16 * NR) { dn0 = dgc[2 * (i + 1)]; dn1 = dgc[2 * (i + 1) + 1]; }
-                    const double diff0 = sgl_nnls_quotient(bi, gii, rii, any_irr);   // b_i / g_ii (Markstein, see nnls_lane.h)
+                    const double diff0 = sgl_nnls_quotient(bi, gii, rii, any_irr);   // b_i / g_ii
                     double dpen;
                     const double nd = sgl_nnls_nd_strict(diff0, xi, go, L1, L2, dpen);
                     const bool moved = nd != 0.0;   // (x and tol change only with nd != 0; a stopped column has nd = 0)
@@ -165,13 +165,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NR <= 8 ? SG
         }
         ran_total += ran;
     }
-    if (sweep_counter != nullptr) {
-        for (int off = 32; off > 0; off >>= 1) total_sweeps += __shfl_down(total_sweeps, off, 64);
-        if (lane == 0 && (total_sweeps != 0 || ran_total != 0)) {
-            atomicAdd(sweep_counter, (unsigned long long)total_sweeps);
-            atomicAdd(sweep_counter + 2, (unsigned long long)ran_total);
-        }
-    }
+    sgl_nnls_book_sweeps(sweep_counter, total_sweeps, ran_total);
 }
 
 template <int NR>

@@ -98,10 +98,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KQ > 44 ? 1
                     __builtin_amdgcn_sched_barrier(0);
                     const double bi = quarter_from_row(b[ii], 16 * owner + c16);
                     const double xi = quarter_from_row(x[ii], 16 * owner + c16);
-                    // b_i / G_ii, correctly rounded, from the correctly rounded reciprocal (Markstein; see nnls_lane.h)
-                    const double q0 = bi * rii;
-                    const double rem = fma(-q0, gii, bi);
-                    const double diff0 = fma(rem, rii, q0);
+                    const double diff0 = sgl_nnls_markstein(bi, gii, rii);
                     double xv = xi;
                     const double nd = sgl_nnls_step(diff0, xv, tol, go, L1, L2);
                     x[ii] = (q == owner) ? xv : x[ii];
@@ -121,18 +118,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KQ > 44 ? 1
             });
             if (q == 0) {
                 total_sweeps += it;
-                if (prev_it != nullptr) prev_it[col] = (uint8_t)it;   // packing key of the next solve
+                sgl_nnls_packing_key(prev_it, col, it);
             }
         }
         ran_total += ran;
     }
-    if (sweep_counter != nullptr) {
-        for (int off = 32; off > 0; off >>= 1) total_sweeps += __shfl_down(total_sweeps, off, 64);
-        if (lane == 0 && (total_sweeps != 0 || ran_total != 0)) {
-            atomicAdd(sweep_counter, (unsigned long long)total_sweeps);
-            atomicAdd(sweep_counter + 2, (unsigned long long)ran_total);
-        }
-    }
+    sgl_nnls_book_sweeps(sweep_counter, total_sweeps, ran_total);
 }
 
 template <int KQ>

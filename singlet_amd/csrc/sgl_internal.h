@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <atomic>
 #include <vector>
 #include <algorithm>
 
@@ -39,6 +40,20 @@ size_t sgl_pool_cached_bytes(void);
         int r__ = (expr);         \
         if (r__ != SGL_OK) return r__; \
     } while (0)
+
+// Lets kernel F take `bytes` of dynamic LDS (above the default 48 KiB): the attribute belongs to the (function, device) pair, so it
+// is set once per device; several host threads may drive devices at once.  SGL_OK, or SGL_EHIP as HIPCHK returns it.
+template <auto* F>
+int sgl_allow_dynamic_lds(int bytes) {
+    static std::atomic<bool> attr_set[64];
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(F), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    return SGL_OK;
+}
 
 // One orientation of the resident shard: CSC with 64-bit column pointers.
 struct DevCSC {
@@ -95,7 +110,7 @@ struct PhaseEvent {
     hipEvent_t e0, e1;
 };
 
-// one pass of the lane-per-column kernel (nnls_lane.h): columns come from `list` (count at *count)
+// one pass of the re-packing lane solves (protocol: nnls_static_for.h): columns come from `list` (count at *count)
 // or are 0..ncols-1 when list == nullptr; unfinished columns go to next_list (nullptr: run to the end)
 struct NnlsPass {
     const int32_t* list;
