@@ -7,15 +7,19 @@
  * timed CPU baseline.  The product path is the HIP library and fails loudly
  * when it is missing.
  *
- * PARITY UNPINNED: the reference (zdebruine/singlet @ 2025-08-08) ships no
- * golden vectors or known-answer tests for this path (its only test asserts
- * TRUE, tests/testthat/test-pbmc3k.R:1-7) and its own sources cannot be built
- * in this image (src/singlet.cpp needs Rcpp, RcppEigen/Eigen and R, none of
- * which exist here; no stand-in headers are written).  This file is therefore
- * a line-by-line restatement checked against (a) an independent numpy
- * transcription of the same reference lines (oracle/np_transcription.py,
- * bit-for-bit agreement is asserted in tests/test_oracle.py) and (b) the
- * hash known-answer values derived by hand from src/singlet.cpp:30-64.
+ * PARITY: the reference (zdebruine/singlet @ 2025-08-08) ships no golden
+ * vectors or known-answer tests for this path (its only test asserts TRUE,
+ * tests/testthat/test-pbmc3k.R:1-7), and as its authors build it, it cannot
+ * be built in this image (src/singlet.cpp needs Rcpp, RcppEigen/Eigen and R,
+ * none of which exist here).  This file is a line-by-line restatement, held
+ * (a) bit for bit to a build of the reference's OWN ALS statements, cut out
+ * of its tree at build time and compiled against the stand-in headers of
+ * oracle/standin/ (make_ref.sh, tests/test_reference_build.py; DESIGN.md
+ * "Oracle status" says what that pins and what it does not), (b) to an
+ * independent numpy transcription of the same reference lines
+ * (oracle/np_transcription.py, bit-for-bit agreement is asserted in
+ * tests/test_oracle.py) and (c) to the hash known-answer values derived by
+ * hand from src/singlet.cpp:30-64.
  *
  * Third-party arithmetic not under /root/reference: Eigen (via RcppEigen,
  * DESCRIPTION:25,39-41, version unpinned).  Its call sites on the path are
@@ -107,8 +111,9 @@ ORA_API void ora_rng_mask(uint64_t state, uint64_t cell0, uint64_t ncells, uint6
 /* ------------------------------------------------------------- helpers */
 /* cor(x, y) -- src/singlet.cpp:184-197 : 1 - Pearson, one-pass sums. */
 ORA_API double ora_cor(const double* x, const double* y, size_t n) {
-    double x_i, y_i, sum_x = 0, sum_y = 0, sum_xy = 0, sum_x2 = 0, sum_y2 = 0;
-    for (size_t i = 0; i < n; ++i) {
+    double x_i, y_i;
+    double sum_x = 0, sum_y = 0, sum_xy = 0, sum_x2 = 0, sum_y2 = 0;
+    for (size_t i = 0; i != n; ++i) {
         x_i = x[i];
         y_i = y[i];
         sum_x += x_i;
@@ -383,7 +388,7 @@ ORA_API int ora_c_nmf(const double* Ax, const int32_t* Ai, const int32_t* Ap, co
     double tol_ = 1;
     double* w_it = (double*)malloc(sizeof(double) * (size_t)k * (size_t)m);
     int iter_ = 0;
-    for (; iter_ < maxit && tol_ > tol; ++iter_) {
+    for (; (iter_ < maxit) && (tol_ > tol); ++iter_) {
         memcpy(w_it, w, sizeof(double) * (size_t)k * (size_t)m);
         const int timed = iter_ >= g_timing_skip;
         double t0 = now_sec();
@@ -438,7 +443,7 @@ ORA_API int ora_c_nmf_dense(const double* A, const double* At, int32_t m, int32_
     double tol_ = 1;
     double* w_it = (double*)malloc(sizeof(double) * (size_t)k * (size_t)m);
     int iter_ = 0;
-    for (; iter_ < maxit && tol_ > tol; ++iter_) {
+    for (; (iter_ < maxit) && (tol_ > tol); ++iter_) {
         memcpy(w_it, w, sizeof(double) * (size_t)k * (size_t)m);
         predict_dense(A, m, n, w, h, k, L1_h, L2_h, threads);
         ora_scale(h, k, n, d);
@@ -468,7 +473,7 @@ ORA_API int ora_c_linked_nmf(const double* Ax, const int32_t* Ai, const int32_t*
     double tol_ = 1;
     double* w_it = (double*)malloc(sizeof(double) * (size_t)k * (size_t)m);
     int iter_ = 0;
-    for (; iter_ < maxit && tol_ > tol; ++iter_) {
+    for (; (iter_ < maxit) && (tol_ > tol); ++iter_) {
         memcpy(w_it, w, sizeof(double) * (size_t)k * (size_t)m);
         predict_x(A, w, h, k, L1, L2, threads, NULL, linking_h ? link_h : NULL, link_h_rows);
         ora_scale(h, k, n, d);
@@ -529,14 +534,14 @@ ORA_API int ora_c_ard_nmf(const double* Ax, const int32_t* Ai, const int32_t* Ap
     int nt = 0;
     double* w_it = (double*)malloc(sizeof(double) * (size_t)k * (size_t)m);
     int iter_ = 0;
-    for (; iter_ < maxit && tol_ > tol; ++iter_) {
+    for (; (iter_ < maxit) && (tol_ > tol); ++iter_) {
         memcpy(w_it, w, sizeof(double) * (size_t)k * (size_t)m);
         predict_mask(A, rng_seed, inv_density, w, h, k, L1, L2, threads, 0, 0, 0);
         ora_scale(h, k, n, d);
         predict_mask(At, rng_seed, inv_density, h, w, k, L1, L2, threads, 1, 0, 0);
         ora_scale(w, k, m, d);
         tol_ = ora_cor(w, w_it, (size_t)k * (size_t)m);
-        if (iter_ % trace_test_mse == 0) {
+        if ((iter_ % trace_test_mse) == 0) {
             test_mse[nt] = mse_test(A, w, d, h, k, rng_seed, inv_density, threads);
             iter[nt] = iter_;
             fit_tol[nt] = tol_;
@@ -549,7 +554,7 @@ ORA_API int ora_c_ard_nmf(const double* Ax, const int32_t* Ai, const int32_t* Ap
             if (score_overfit[nt - 1] > overfit_threshold) break;
         }
     }
-    if (iter_ % trace_test_mse != 0) {
+    if ((iter_ % trace_test_mse) != 0) {
         test_mse[nt] = mse_test(A, w, d, h, k, rng_seed, inv_density, threads);
         iter[nt] = iter_;
         fit_tol[nt] = tol_;
@@ -672,7 +677,7 @@ ORA_API int ora_c_nmf_sparse_list(int nA, const double* const* Ax, const int32_t
     double tol_ = 1;
     double* w_it = (double*)malloc(sizeof(double) * (size_t)k * (size_t)m);
     int iter_ = 0;
-    for (; iter_ < maxit && tol_ > tol; ++iter_) {
+    for (; (iter_ < maxit) && (tol_ > tol); ++iter_) {
         memcpy(w_it, w, sizeof(double) * (size_t)k * (size_t)m);
         predict_list(A, w, h, k, L1, L2, threads);
         ora_scale(h, k, n, d);
@@ -701,14 +706,14 @@ ORA_API int ora_c_ard_nmf_sparse_list(int nA, const double* const* Ax, const int
     int nt = 0;
     double* w_it = (double*)malloc(sizeof(double) * (size_t)k * (size_t)m);
     int iter_ = 0;
-    for (; iter_ < maxit && tol_ > tol; ++iter_) {
+    for (; (iter_ < maxit) && (tol_ > tol); ++iter_) {
         memcpy(w_it, w, sizeof(double) * (size_t)k * (size_t)m);
         predict_mask_list(A, rng_seed, inv_density, w, h, k, L1, L2, threads, 0);
         ora_scale(h, k, n, d);
         predict_mask_list(At, rng_seed, inv_density, h, w, k, L1, L2, threads, 1);
         ora_scale(w, k, m, d);
         tol_ = ora_cor(w, w_it, (size_t)k * (size_t)m);
-        if (iter_ % trace_test_mse == 0) {
+        if ((iter_ % trace_test_mse) == 0) {
             test_mse[nt] = mse_test_list(A, w, d, h, k, rng_seed, inv_density, threads, n);
             iter[nt] = iter_;
             fit_tol[nt] = tol_;
@@ -721,7 +726,7 @@ ORA_API int ora_c_ard_nmf_sparse_list(int nA, const double* const* Ax, const int
             if (score_overfit[nt - 1] > overfit_threshold) break;
         }
     }
-    if (iter_ % trace_test_mse != 0) {
+    if ((iter_ % trace_test_mse) != 0) {
         test_mse[nt] = mse_test_list(A, w, d, h, k, rng_seed, inv_density, threads, n);
         iter[nt] = iter_;
         fit_tol[nt] = tol_;
@@ -819,14 +824,14 @@ ORA_API int ora_c_ard_nmf_dense(const double* A, const double* At, int32_t m, in
     int nt = 0;
     double* w_it = (double*)malloc(sizeof(double) * (size_t)k * (size_t)m);
     int iter_ = 0;
-    for (; iter_ < maxit && tol_ > tol; ++iter_) {
+    for (; (iter_ < maxit) && (tol_ > tol); ++iter_) {
         memcpy(w_it, w, sizeof(double) * (size_t)k * (size_t)m);
         predict_mask_dense(A, m, n, rng_seed, inv_density, w, h, k, L1, L2, threads, 0);
         ora_scale(h, k, n, d);
         predict_mask_dense(At, n, m, rng_seed, inv_density, h, w, k, L1, L2, threads, 1);
         ora_scale(w, k, m, d);
         tol_ = ora_cor(w, w_it, (size_t)k * (size_t)m);
-        if (iter_ % trace_test_mse == 0) {
+        if ((iter_ % trace_test_mse) == 0) {
             test_mse[nt] = mse_test_dense(A, m, n, w, d, h, k, rng_seed, inv_density, threads);
             iter[nt] = iter_;
             fit_tol[nt] = tol_;
@@ -839,7 +844,7 @@ ORA_API int ora_c_ard_nmf_dense(const double* A, const double* At, int32_t m, in
             if (score_overfit[nt - 1] > overfit_threshold) break;
         }
     }
-    if (iter_ % trace_test_mse != 0) {
+    if ((iter_ % trace_test_mse) != 0) {
         test_mse[nt] = mse_test_dense(A, m, n, w, d, h, k, rng_seed, inv_density, threads);
         iter[nt] = iter_;
         fit_tol[nt] = tol_;

@@ -106,8 +106,55 @@ def test_reference_build_products_stay_out_of_history():
     # (round-5 verdict): .gpurunignore may name oracle/_ref/*.inc, never the directory or the library
     gi = open(os.path.join(ROOT, ".gpurunignore")).read().split() if os.path.exists(os.path.join(ROOT, ".gpurunignore")) else []
     assert all(ln == "oracle/_ref/*.inc" for ln in gi if "oracle/_ref" in ln), gi
-    for f in ("oracle/make_ref.sh", "oracle/ref_rng_shim.cpp", "tests/golden/make_rng_ref.py", "tests/golden/rng_ref.npz"):
+    for f in ("oracle/make_ref.sh", "oracle/ref_rng_shim.cpp", "tests/golden/make_rng_ref.py", "tests/golden/rng_ref.npz",
+              "oracle/ref_als_shim.cpp", "oracle/standin/eigen_standin.h", "oracle/standin/rcpp_standin.h", "oracle/reference.py",
+              "tests/golden/make_als_ref.py", "tests/golden/als_ref.npz"):
         assert os.path.exists(os.path.join(ROOT, f)), f
     # the shim holds no reference text: it includes the extracted class
     shim = open(os.path.join(ROOT, "oracle", "ref_rng_shim.cpp")).read()
     assert '#include "_ref/rng_class.inc"' in shim and "class rng" not in shim
+    # nor does the ALS shim: it includes the cut functions and defines none of them (a definition would carry a body:
+    # a line that starts with the function's return type and name)
+    als = open(os.path.join(ROOT, "oracle", "ref_als_shim.cpp")).read()
+    assert '#include "_ref/als_functions.inc"' in als and '#include "_ref/rng_class.inc"' in als
+    recipe = open(os.path.join(ROOT, "oracle", "make_ref.sh")).read()
+    prefixes = recipe.split("<<'EOF'\n")[1].split("\nEOF")[0].splitlines()
+    assert len(prefixes) >= 30
+    for pre in prefixes:
+        assert not any(ln.startswith(pre) for ln in als.splitlines()), pre
+    # the committed fixture stays below the size limit of a committed file
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "als_ref.npz")) < 1024 * 1024
+
+
+def test_no_line_of_the_cut_reference_text_is_committed():
+    """Where the reference text cut at build time lies (oracle/_ref/*.inc: the authoring container), no line of it longer
+    than 30 characters after stripping occurs as a line of any tracked file under oracle/ or tests/ -- the stand-in
+    headers and the shims above all.  The check quotes nothing: it reads the cut files."""
+    import glob
+    import subprocess
+    incs = glob.glob(os.path.join(ROOT, "oracle", "_ref", "*.inc"))
+    if not incs:
+        pytest.skip("no cut reference text here")
+    tracked = subprocess.run(["git", "-C", ROOT, "ls-files", "--cached", "--others", "--exclude-standard", "oracle", "tests"], capture_output=True, text=True)
+    if tracked.returncode != 0:
+        pytest.skip("not a git checkout")
+    ref_lines = set()
+    for f in incs:
+        for ln in open(f, errors="replace"):
+            ln = ln.strip()
+            if len(ln) > 30:
+                ref_lines.add(ln)
+    assert len(ref_lines) > 100
+    hits = []
+    for f in tracked.stdout.split():
+        path = os.path.join(ROOT, f)
+        if not os.path.isfile(path) or os.path.getsize(path) > 4 * 1024 * 1024:
+            continue
+        try:
+            text = open(path, encoding="utf-8").read()
+        except UnicodeDecodeError:
+            continue    # binary fixtures hold no program text
+        for ln in text.splitlines():
+            if ln.strip() in ref_lines:
+                hits.append((f, ln.strip()))
+    assert not hits, hits[:10]
