@@ -26,34 +26,6 @@ constexpr int LKNN_CAP = 512;    // candidates a point sorts in LDS (one 64-lane
 constexpr int SNN_CAP = 2048;    // gathered column indices a column sorts in LDS (8 KB); above: dense counters in HBM
 constexpr uint64_t NO_KEY = ~0ull;
 
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() { if (p) (void)sgl_pool_free(p); }
-    int alloc(size_t count) {
-        if (p) { (void)sgl_pool_free(p); p = nullptr; }
-        if (count == 0) count = 1;
-        if (sgl_pool_malloc(&p, count * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            p = nullptr;
-            sgl_set_error("hipMalloc of %zu bytes failed", count * sizeof(T));
-            return SGL_ENOMEM;
-        }
-        return SGL_OK;
-    }
-};
-
-struct CtxHold {
-    sgl_ctx* c = nullptr;
-    ~CtxHold() { if (c) sgl_destroy(c); }
-};
-
-int current_device() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; }
-    return d;
-}
-
 unsigned grid_for(int64_t n, int per_block) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, 65535)); }
 
 // ---------------------------------------------------------------------------------------------------------------- LKNN ---
@@ -437,8 +409,8 @@ extern "C" int sgl_c_lknn(const double* m, int32_t m_rows, int32_t m_cols, const
     const float base = radius * 2.0f + 1.0f;
     const double n_max_edges = ceil((double)base * (double)base) - 1.0;
 
-    CtxHold hd;
-    SGLCHK(sgl_create(current_device(), &hd.c));
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     hipStream_t s = hd.c->stream;
     if (n == 0) {
         p_out[0] = 0;
@@ -795,8 +767,8 @@ extern "C" int sgl_c_snn(const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, i
     const int64_t gnnz = hp[n];
     if (gnnz > 0 && !Gi) { sgl_set_error("sgl_c_snn: bad arguments"); return SGL_EINVAL; }
 
-    CtxHold hd;
-    SGLCHK(sgl_create(current_device(), &hd.c));
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     hipStream_t s = hd.c->stream;
     DevBuf<int32_t> dGi, Rj, dfast, dslow;
     DevBuf<int64_t> dGp, Rp, rcnt, T, cnt;
@@ -1144,8 +1116,8 @@ extern "C" int sgl_spatial_graph(const double* c1, const double* c2, int32_t n, 
     }
     const int64_t K = std::min<int64_t>(max_k, n);   // max_k > n acts as n: the scan of n points ends there
 
-    CtxHold hd;
-    SGLCHK(sgl_create(current_device(), &hd.c));
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     hipStream_t s = hd.c->stream;
     if (K == 0) {   // n = 0 or max_k = 0: the empty n x n graph
         for (int64_t c = 0; c <= n; ++c) p_out[c] = 0;

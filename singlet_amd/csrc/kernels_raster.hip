@@ -121,32 +121,6 @@ int hip_ok(hipError_t e, const char* what) {
 }
 #define RCHK(expr, what) SGLCHK(hip_ok((expr), what))
 
-struct Buf {
-    double* p = nullptr;
-    ~Buf() { if (p) (void)sgl_pool_free(p); }
-};
-
-struct CtxHold {
-    sgl_ctx* c = nullptr;
-    ~CtxHold() { if (c) sgl_destroy(c); }
-};
-
-int current_device() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; }
-    return d;
-}
-
-int alloc_doubles(Buf& b, size_t count) {
-    if (sgl_pool_malloc(&b.p, std::max<size_t>(count, 1) * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        sgl_set_error("hipMalloc of %zu bytes failed", std::max<size_t>(count, 1) * sizeof(double));
-        return SGL_ENOMEM;
-    }
-    return SGL_OK;
-}
-
 }  // namespace
 
 // nb = floor(A.nrow / n) >= 1 and n <= A.nrow (so n fits 32 bits); A a valid CSC image (rows in [0, nrow), ascending).
@@ -178,8 +152,8 @@ extern "C" int sgl_c_rowwise_compress_sparse(const double* Ax, const int32_t* Ai
     int64_t nb = 0;
     SGLCHK(bin_count(who, nrow, n, &nb));
     if (nb * (int64_t)ncol > 0 && !out) { sgl_set_error("%s: NULL output", who); return SGL_EINVAL; }
-    CtxHold hd;
-    SGLCHK(sgl_create(current_device(), &hd.c));
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     if (nrow == 0 || ncol == 0) {   // nothing can be stored; nothing to write
         if (Ap[0] != 0 || Ap[ncol] != 0) { sgl_set_error("%s: a matrix with %d rows and %d columns holds no entries", who, nrow, ncol); return SGL_EINVAL; }
         return SGL_OK;
@@ -189,8 +163,8 @@ extern "C" int sgl_c_rowwise_compress_sparse(const double* Ax, const int32_t* Ai
     SGLCHK(sgl_upload_A_structure(c, Ax, Ai, Ap, nrow, ncol));   // row indices valid and ascending; values as they are
     if (nb == 0) return SGL_OK;
     const size_t tot = (size_t)nb * (size_t)ncol;
-    Buf R;
-    SGLCHK(alloc_doubles(R, tot));
+    DevBuf<double> R;
+    SGLCHK(R.alloc(tot));
     SGLCHK(k_raster_sparse(c->stream, c->A, n, nb, R.p));
     RCHK(hipMemcpyAsync(out, R.p, sizeof(double) * tot, hipMemcpyDeviceToHost, c->stream), "download of the result");
     RCHK(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
@@ -203,14 +177,14 @@ extern "C" int sgl_c_rowwise_compress_dense(const double* A, int32_t nrow, int32
     int64_t nb = 0;
     SGLCHK(bin_count(who, nrow, n, &nb));
     if (nb * (int64_t)ncol > 0 && !out) { sgl_set_error("%s: NULL output", who); return SGL_EINVAL; }
-    CtxHold hd;
-    SGLCHK(sgl_create(current_device(), &hd.c));
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     if (nb == 0 || ncol == 0) return SGL_OK;
     hipStream_t s = hd.c->stream;
     const size_t tin = (size_t)nrow * (size_t)ncol, tot = (size_t)nb * (size_t)ncol;
-    Buf dA, R;
-    SGLCHK(alloc_doubles(dA, tin));
-    SGLCHK(alloc_doubles(R, tot));
+    DevBuf<double> dA, R;
+    SGLCHK(dA.alloc(tin));
+    SGLCHK(R.alloc(tot));
     RCHK(hipMemcpyAsync(dA.p, A, sizeof(double) * tin, hipMemcpyHostToDevice, s), "upload of A");
     SGLCHK(k_raster_dense(s, dA.p, nrow, ncol, n, nb, R.p));
     RCHK(hipMemcpyAsync(out, R.p, sizeof(double) * tot, hipMemcpyDeviceToHost, s), "download of the result");

@@ -571,6 +571,32 @@ static int team_exchange(sgl_team* T, int who, std::initializer_list<Xfer> ops) 
     return rc != SGL_OK ? rc : rc_pe;
 }
 
+// A team call is an ordered list of stages: what every rank enqueues on its own device (fn(i), i the local rank), or an
+// exchange step (fn(who), who as in team_exchange).  With worker threads every rank runs the whole list on its own thread;
+// without, the calling thread walks the ranks stage by stage and issues each exchange once, grouped over the ranks.
+struct Stage {
+    bool exchange;
+    std::function<int(int)> fn;
+};
+static int team_stages(sgl_team* T, std::initializer_list<Stage> stages) {
+    const int nl = (int)T->local.size();
+    auto on_rank = [&](const Stage& s, int i) -> int {
+        if (!s.exchange) HIPCHK(hipSetDevice(T->local[i]->device));
+        return s.fn(i);
+    };
+    if (T->pool)
+        return team_parallel(T, [&](int i) -> int {
+            for (const Stage& s : stages) SGLCHK(on_rank(s, i));
+            return SGL_OK;
+        });
+    for (const Stage& s : stages) {
+        if (s.exchange) SGLCHK(s.fn(-1));
+        else
+            for (int i = 0; i < nl; ++i) SGLCHK(on_rank(s, i));
+    }
+    return SGL_OK;
+}
+
 // ---------------------------------------------------------------- team set-up --
 static int team_events(sgl_team* T) {
     if (!T->loopback) return SGL_OK;
@@ -584,29 +610,17 @@ static int team_events(sgl_team* T) {
 // per-gene non-zero counts over all ranks (which W columns predict() skips, src/singlet.cpp:340)
 static int team_gene_counts(sgl_team* T) {
     if (T->nranks <= 1) return SGL_OK;
-    const int nl = (int)T->local.size();
-    std::vector<void*> bufs(nl);
+    std::vector<void*> bufs(T->local.size());
     auto prep = [&](int i) -> int {
         sgl_ctx* c = T->local[i];
-        HIPCHK(hipSetDevice(c->device));
         const int64_t m = c->A.nrow;
-        if (!c->col_nnz_At_global) {
-            hipError_t e = sgl_pool_malloc((void**)&c->col_nnz_At_global, sizeof(int64_t) * (size_t)std::max<int64_t>(m, 1));
-            if (e != hipSuccess) { (void)hipGetLastError(); sgl_set_error("team: out of device memory"); return SGL_ENOMEM; }
-        }
+        if (!c->col_nnz_At_global) SGLCHK(dev_alloc(&c->col_nnz_At_global, (size_t)m));
         HIPCHK(hipMemcpyAsync(c->col_nnz_At_global, c->col_nnz_At, sizeof(int64_t) * (size_t)m, hipMemcpyDeviceToDevice, c->stream));
         bufs[i] = c->col_nnz_At_global;
         return SGL_OK;
     };
-    if (T->pool) {
-        SGLCHK(team_parallel(T, [&](int i) -> int {
-            SGLCHK(prep(i));
-            return team_exchange(T, i, {{0, &bufs, (int64_t)T->nrow, true}});
-        }));
-    } else {
-        for (int i = 0; i < nl; ++i) SGLCHK(prep(i));
-        SGLCHK(team_exchange(T, -1, {{0, &bufs, (int64_t)T->nrow, true}}));
-    }
+    auto exchange = [&](int who) -> int { return team_exchange(T, who, {{0, &bufs, (int64_t)T->nrow, true}}); };
+    SGLCHK(team_stages(T, {{false, prep}, {true, exchange}}));
     for (auto c : T->local) c->gene_nnz_global = true;
     return SGL_OK;
 }
@@ -649,23 +663,16 @@ static int team_iterate(sgl_team* T, double L1_w, double L1_h, double L2_w, doub
     std::vector<double> tols(nl, 0.0);
     auto local_part = [&](int i) -> int {   // h = predict(A_r, w); partials of the unscaled h
         sgl_ctx* c = T->local[i];
-        HIPCHK(hipSetDevice(c->device));
         SGLCHK(sgl_step_begin(c));
         SGLCHK(sgl_step_h(c, L1_h, L2_h));
         double* Bw = c->red;
         double* Gh = c->red + (size_t)k * mpad;
         double* sh = Gh + (size_t)k * k;
-        PhaseEvent pe;
-        SGLCHK(sgl_phase_begin(c, SGL_PH_SCALE, &pe));
-        SGLCHK(k_rowsum(c, c->H, k, c->A.ncol, sh));
-        SGLCHK(sgl_phase_end(c, &pe));
-        SGLCHK(sgl_phase_begin(c, SGL_PH_RHS_W, &pe));
-        if (c->use_tiled && c->TAt.roff) SGLCHK(k_acc_tiled_all(c->stream, c->TAt, c->H, Bw, k));
-        else SGLCHK(k_acc(c->stream, c->At, c->H, k, Bw, 0, 1, 0, 0, 0));
-        SGLCHK(sgl_phase_end(c, &pe));
-        SGLCHK(sgl_phase_begin(c, SGL_PH_GRAM, &pe));
-        SGLCHK(k_gram(c, c->H, k, c->A.ncol, Gh, 0.0));
-        SGLCHK(sgl_phase_end(c, &pe));
+        { Phase ph(c, SGL_PH_SCALE); SGLCHK(k_rowsum(c, c->H, k, c->A.ncol, sh)); }
+        { Phase ph(c, SGL_PH_RHS_W);
+          if (c->use_tiled && c->TAt.roff) SGLCHK(k_acc_tiled_all(c->stream, c->TAt, c->H, Bw, k));
+          else SGLCHK(k_acc(c->stream, c->At, c->H, k, Bw, 0, 1, 0, 0, 0)); }
+        { Phase ph(c, SGL_PH_GRAM); SGLCHK(k_gram(c, c->H, k, c->A.ncol, Gh, 0.0)); }
         red[i] = Bw;
         tail[i] = Gh;
         wbuf[i] = c->W;
@@ -677,23 +684,19 @@ static int team_iterate(sgl_team* T, double L1_w, double L1_h, double L2_w, doub
     };
     auto gene_block = [&](int i) -> int {
         sgl_ctx* c = T->local[i];
-        HIPCHK(hipSetDevice(c->device));
         const int r = T->rank[i];
         double* Gh = c->red + (size_t)k * mpad;
         double* sh = Gh + (size_t)k * k;
-        PhaseEvent pe;
-        SGLCHK(sgl_phase_begin(c, SGL_PH_SCALE, &pe));
-        // d = rowsums + 1e-15; h /= d  (scale(h, d), src/singlet.cpp:219-225, with the GLOBAL row sums)
-        HIPCHK(hipMemcpyAsync(c->d, sh, sizeof(double) * k, hipMemcpyDeviceToDevice, c->stream));
-        SGLCHK(k_scale_apply(c->stream, c->H, k, c->A.ncol, c->d, 1));
-        SGLCHK(sgl_phase_end(c, &pe));
+        { Phase ph(c, SGL_PH_SCALE);
+          // d = rowsums + 1e-15; h /= d  (scale(h, d), src/singlet.cpp:219-225, with the GLOBAL row sums)
+          HIPCHK(hipMemcpyAsync(c->d, sh, sizeof(double) * k, hipMemcpyDeviceToDevice, c->stream));
+          SGLCHK(k_scale_apply(c->stream, c->H, k, c->A.ncol, c->d, 1)); }
         const int64_t g0 = (int64_t)r * mb;
         const int64_t ng = std::max<int64_t>(0, std::min<int64_t>(mb, m - g0));
-        SGLCHK(sgl_phase_begin(c, SGL_PH_GRAM, &pe));
-        HIPCHK(hipMemcpyAsync(c->G, Gh, sizeof(double) * k * k, hipMemcpyDeviceToDevice, c->stream));
-        SGLCHK(k_gram_rescale(c->stream, c->G, k, c->d, 1e-15));   // AAt of the scaled h (+1e-15, l.204)
-        SGLCHK(sgl_phase_end(c, &pe));
-        SGLCHK(sgl_phase_begin(c, SGL_PH_NNLS_W, &pe));
+        { Phase ph(c, SGL_PH_GRAM);
+          HIPCHK(hipMemcpyAsync(c->G, Gh, sizeof(double) * k * k, hipMemcpyDeviceToDevice, c->stream));
+          SGLCHK(k_gram_rescale(c->stream, c->G, k, c->d, 1e-15)); }   // AAt of the scaled h (+1e-15, l.204)
+        Phase ph(c, SGL_PH_NNLS_W);
         if (ng > 0) {
             double* Bblk = c->red + (size_t)g0 * k;
             SGLCHK(k_scale_apply(c->stream, Bblk, k, ng, c->d, 0));
@@ -703,38 +706,15 @@ static int team_iterate(sgl_team* T, double L1_w, double L1_h, double L2_w, doub
             // (the dense front-end solves every column, src/singlet.cpp:370-381: no skip list)
             SGLCHK(sgl_nnls_shared(c, c->G, Bblk, c->W + (size_t)g0 * k, c->solve_empty ? nullptr : gene_nnz + g0, ng, L1_w, L2_w, c->sweep_counters + 1));
         }
-        SGLCHK(sgl_phase_end(c, &pe));
         return SGL_OK;
     };
     auto exchange2 = [&](int who) -> int {   // all-gather of the solved w blocks
         if (N <= 1) return SGL_OK;
         return team_exchange(T, who, {{2, &wbuf, (int64_t)k * mb, false}});
     };
-    auto tail_part = [&](int i) -> int {
-        HIPCHK(hipSetDevice(T->local[i]->device));
-        return sgl_scale_w_enqueue(T->local[i]);
-    };
-    auto fetch = [&](int i) -> int {
-        HIPCHK(hipSetDevice(T->local[i]->device));
-        return sgl_scale_w_fetch(T->local[i], &tols[i]);
-    };
-    if (T->pool) {
-        SGLCHK(team_parallel(T, [&](int i) -> int {
-            SGLCHK(local_part(i));
-            SGLCHK(exchange1(i));
-            SGLCHK(gene_block(i));
-            SGLCHK(exchange2(i));
-            SGLCHK(tail_part(i));
-            return fetch(i);
-        }));
-    } else {
-        for (int i = 0; i < nl; ++i) SGLCHK(local_part(i));
-        SGLCHK(exchange1(-1));
-        for (int i = 0; i < nl; ++i) SGLCHK(gene_block(i));
-        SGLCHK(exchange2(-1));
-        for (int i = 0; i < nl; ++i) SGLCHK(tail_part(i));
-        for (int i = 0; i < nl; ++i) SGLCHK(fetch(i));
-    }
+    auto tail_part = [&](int i) -> int { return sgl_scale_w_enqueue(T->local[i]); };
+    auto fetch = [&](int i) -> int { return sgl_scale_w_fetch(T->local[i], &tols[i]); };
+    SGLCHK(team_stages(T, {{false, local_part}, {true, exchange1}, {false, gene_block}, {true, exchange2}, {false, tail_part}, {false, fetch}}));
     SGLCHK(team_tols_agree(tols));
     if (tol_out) *tol_out = tols[0];   // w is replicated bit for bit: every rank computes the same value
     return SGL_OK;
@@ -742,20 +722,8 @@ static int team_iterate(sgl_team* T, double L1_w, double L1_h, double L2_w, doub
 
 static int team_nmf_run(sgl_team* T, double tol, int32_t maxit, double L1_w, double L1_h, double L2_w, double L2_h,
                         int32_t* n_iter, double* tol_trace, const sgl_callbacks* cb) {
-    double tol_ = 1.0;
-    int it = 0;
-    for (; it < maxit && tol_ > tol; ++it) {   // src/singlet.cpp:647
-        SGLCHK(team_iterate(T, L1_w, L1_h, L2_w, L2_h, &tol_));
-        if (tol_trace) tol_trace[it] = tol_;
-        if (cb && cb->log) cb->log(cb->user, it + 1, tol_, NAN);
-        if (cb && cb->poll && cb->poll(cb->user)) { sgl_set_error("interrupted"); return SGL_EINTR; }
-    }
-    for (auto c : T->local) {
-        HIPCHK(hipSetDevice(c->device));
-        SGLCHK(sgl_fetch_sweeps(c));
-    }
-    if (n_iter) *n_iter = it;
-    return SGL_OK;
+    return sgl_als_loop(tol, maxit, [&](double* t) { return team_iterate(T, L1_w, L1_h, L2_w, L2_h, t); }, nullptr, nullptr,
+                        T->local.data(), (int)T->local.size(), tol_trace, n_iter, cb);
 }
 
 // ---------------------------------------------------- the masked (ARD) loop --
@@ -773,15 +741,14 @@ static int team_mask_workspace(sgl_team* T) {
     for (auto c : T->local) {
         HIPCHK(hipSetDevice(c->device));
         SGLCHK(sgl_mask_workspace(c));
-        if (N > 1 && !c->Sbuf) {
-            const int64_t mb = (T->nrow + N - 1) / N;
-            hipError_t e = sgl_pool_malloc((void**)&c->Sbuf, sizeof(double) * (size_t)mb * N * c->k * c->k);
-            if (e != hipSuccess) { (void)hipGetLastError(); sgl_set_error("team: out of device memory for the per-gene downdates"); return SGL_ENOMEM; }
-            // what the reduce-scatter moves: the lower triangles (SGL_TEAM_FULL_S=1: the full blocks, rounds 2 - 5 -- A/B, tests)
-            if (!getenv("SGL_TEAM_FULL_S")) {
-                e = sgl_pool_malloc((void**)&c->Stri, sizeof(double) * (size_t)mb * N * c->k * (c->k + 1) / 2);
-                if (e != hipSuccess) { (void)hipGetLastError(); sgl_set_error("team: out of device memory for the per-gene downdates"); return SGL_ENOMEM; }
-            }
+        if (N <= 1) continue;
+        const size_t genes = (size_t)((T->nrow + N - 1) / N) * N;
+        if (!c->Sbuf) SGLCHK(dev_alloc(&c->Sbuf, genes * c->k * c->k));
+        // what the reduce-scatter moves: the lower triangles (SGL_TEAM_FULL_S=1: the full blocks, rounds 2 - 5 -- A/B, tests).  A rank
+        // must never be left with Sbuf but without Stri: the ranks have to agree on the layout (s_unit, team_ard_iterate)
+        if (!c->Stri && !getenv("SGL_TEAM_FULL_S")) {
+            const int rc = dev_alloc(&c->Stri, genes * c->k * (c->k + 1) / 2);
+            if (rc != SGL_OK) { dev_free(c->Sbuf); return rc; }   // the next call starts clean
         }
     }
     return SGL_OK;
@@ -798,14 +765,11 @@ static int team_ard_iterate(sgl_team* T, double L1, double L2, uint64_t seed, ui
     std::vector<double> tols(nl, 0.0);
     auto h_update = [&](int i) -> int {   // H-update: local
         sgl_ctx* c = T->local[i];
-        HIPCHK(hipSetDevice(c->device));
         SGLCHK(sgl_step_begin(c));
         SGLCHK(sgl_predict_mask_dev(c, c->A, c->col_nnz_A, c->W, c->H, c->B, seed, inv_density, L1, L2, 0, SGL_PH_RHS_H,
                                     SGL_PH_NNLS_H, c->sweep_counters + 0));
-        PhaseEvent pe;
-        SGLCHK(sgl_phase_begin(c, SGL_PH_SCALE, &pe));
+        Phase ph(c, SGL_PH_SCALE);
         SGLCHK(k_rowsum(c, c->H, k, c->A.ncol, c->d));
-        SGLCHK(sgl_phase_end(c, &pe));
         dv[i] = c->d;
         return SGL_OK;
     };
@@ -815,11 +779,7 @@ static int team_ard_iterate(sgl_team* T, double L1, double L2, uint64_t seed, ui
     };
     auto w_partials = [&](int i) -> int {   // scale(h, d); partials of the W-update
         sgl_ctx* c = T->local[i];
-        HIPCHK(hipSetDevice(c->device));
-        PhaseEvent pe;
-        SGLCHK(sgl_phase_begin(c, SGL_PH_SCALE, &pe));
-        SGLCHK(k_scale_apply(c->stream, c->H, k, c->A.ncol, c->d, 1));
-        SGLCHK(sgl_phase_end(c, &pe));
+        { Phase ph(c, SGL_PH_SCALE); SGLCHK(k_scale_apply(c->stream, c->H, k, c->A.ncol, c->d, 1)); }
         if (N == 1) {
             const int64_t* gene_nnz = c->col_nnz_At;
             return sgl_predict_mask_dev(c, c->At, gene_nnz, c->H, c->W, c->red, seed, inv_density, L1, L2, 1, SGL_PH_RHS_W,
@@ -827,28 +787,22 @@ static int team_ard_iterate(sgl_team* T, double L1, double L2, uint64_t seed, ui
         }
         double* Bw = c->red;
         double* Gh = c->red + (size_t)k * mpad;
-        SGLCHK(sgl_phase_begin(c, SGL_PH_GRAM, &pe));
-        SGLCHK(k_gram(c, c->H, k, c->A.ncol, Gh, 0.0));
-        SGLCHK(sgl_phase_end(c, &pe));
-        SGLCHK(sgl_phase_begin(c, SGL_PH_RHS_W, &pe));
-        SGLCHK(sgl_masked_rhs(c, 1, c->H, Bw, seed, inv_density));   // hash: draw(cell = row + cell_offset, gene = column)
-        SGLCHK(sgl_phase_end(c, &pe));
-        SGLCHK(sgl_phase_begin(c, SGL_PH_MASK, &pe));
-        HIPCHK(hipMemsetAsync(c->Sbuf, 0, sizeof(double) * (size_t)mpad * k * k, c->stream));
-        if (!c->gene_nnz_global) { sgl_set_error("team: global gene counts missing"); return SGL_ESTATE; }
-        const DevMaskList* ML = nullptr;   // this shard's part of every gene's mask as lists (built on the fit's first pass)
-        if (k <= 128 && !getenv("SGL_MASK_NO_LIST")) {
-            SGLCHK(sgl_mask_list_select(c, 1, m, c->At.nrow, seed, inv_density, 1, 0, c->cell_offset));
-            if (c->ML[1].mask_t == 1) ML = &c->ML[1];
-        }
-        SGLCHK(k_mask_gram_cols(c->stream, 0, m, c->At.nrow, c->col_nnz_At_global, c->H, nullptr, k, seed, inv_density, 1, 0,
-                                c->cell_offset, c->Sbuf, ML));
-        SGLCHK(sgl_phase_end(c, &pe));
+        { Phase ph(c, SGL_PH_GRAM); SGLCHK(k_gram(c, c->H, k, c->A.ncol, Gh, 0.0)); }
+        { Phase ph(c, SGL_PH_RHS_W); SGLCHK(sgl_masked_rhs(c, 1, c->H, Bw, seed, inv_density)); }   // hash: draw(cell = row + cell_offset, gene = column)
+        { Phase ph(c, SGL_PH_MASK);
+          HIPCHK(hipMemsetAsync(c->Sbuf, 0, sizeof(double) * (size_t)mpad * k * k, c->stream));
+          if (!c->gene_nnz_global) { sgl_set_error("team: global gene counts missing"); return SGL_ESTATE; }
+          const DevMaskList* ML = nullptr;   // this shard's part of every gene's mask as lists (built on the fit's first pass)
+          if (k <= 128 && !getenv("SGL_MASK_NO_LIST")) {
+              SGLCHK(sgl_mask_list_select(c, 1, m, c->At.nrow, seed, inv_density, 1, 0, c->cell_offset));
+              if (c->ML[1].mask_t == 1) ML = &c->ML[1];
+          }
+          SGLCHK(k_mask_gram_cols(c->stream, 0, m, c->At.nrow, c->col_nnz_At_global, c->H, nullptr, k, seed, inv_density, 1, 0,
+                                  c->cell_offset, c->Sbuf, ML)); }
         red[i] = Bw;
         if (c->Stri) {   // S_g is symmetric: its lower triangle travels, k (k + 1) / 2 doubles per gene instead of k^2
-            SGLCHK(sgl_phase_begin(c, SGL_PH_MASK, &pe));
+            Phase ph(c, SGL_PH_MASK);
             SGLCHK(k_tri_pack(c->stream, c->Sbuf, k, mpad, c->Stri));
-            SGLCHK(sgl_phase_end(c, &pe));
         }
         sb[i] = c->Stri ? c->Stri : c->Sbuf;
         tail[i] = Gh;
@@ -864,26 +818,21 @@ static int team_ard_iterate(sgl_team* T, double L1, double L2, uint64_t seed, ui
     auto gene_block = [&](int i) -> int {   // every rank: its block of genes
         if (N <= 1) return SGL_OK;
         sgl_ctx* c = T->local[i];
-        HIPCHK(hipSetDevice(c->device));
         const int r = T->rank[i];
         const int64_t g0 = (int64_t)r * mb;
         const int64_t ng = std::max<int64_t>(0, std::min<int64_t>(mb, m - g0));
         double* Gh = c->red + (size_t)k * mpad;
-        PhaseEvent pe;
-        SGLCHK(sgl_phase_begin(c, SGL_PH_GRAM, &pe));
-        HIPCHK(hipMemcpyAsync(c->G, Gh, sizeof(double) * k * k, hipMemcpyDeviceToDevice, c->stream));
-        SGLCHK(k_gram_add_diag(c->stream, c->G, k, 1e-15));
-        SGLCHK(sgl_phase_end(c, &pe));
+        { Phase ph(c, SGL_PH_GRAM);
+          HIPCHK(hipMemcpyAsync(c->G, Gh, sizeof(double) * k * k, hipMemcpyDeviceToDevice, c->stream));
+          SGLCHK(k_gram_add_diag(c->stream, c->G, k, 1e-15)); }
         for (int64_t q0 = 0; q0 < ng; q0 += c->gcols_chunk) {
             const int64_t nq = std::min<int64_t>(c->gcols_chunk, ng - q0);
-            SGLCHK(sgl_phase_begin(c, SGL_PH_MASK, &pe));
-            if (c->Stri) SGLCHK(k_mask_gram_finalize_tri(c->stream, c->G, c->Stri + (size_t)(g0 + q0) * s_unit, k, nq, c->Gcols));
-            else SGLCHK(k_mask_gram_finalize(c->stream, c->G, c->Sbuf + (size_t)(g0 + q0) * k * k, k, nq, c->Gcols));
-            SGLCHK(sgl_phase_end(c, &pe));
-            SGLCHK(sgl_phase_begin(c, SGL_PH_NNLS_W, &pe));
+            { Phase ph(c, SGL_PH_MASK);
+              if (c->Stri) SGLCHK(k_mask_gram_finalize_tri(c->stream, c->G, c->Stri + (size_t)(g0 + q0) * s_unit, k, nq, c->Gcols));
+              else SGLCHK(k_mask_gram_finalize(c->stream, c->G, c->Sbuf + (size_t)(g0 + q0) * k * k, k, nq, c->Gcols)); }
+            Phase ph(c, SGL_PH_NNLS_W);
             SGLCHK(k_nnls_percol(c->stream, c->Gcols, (int64_t)k * k, c->red + (size_t)(g0 + q0) * k, c->W + (size_t)(g0 + q0) * k,
                                c->col_nnz_At_global + g0 + q0, k, nq, L1, L2, c->sweep_counters + 1));
-            SGLCHK(sgl_phase_end(c, &pe));
         }
         return SGL_OK;
     };
@@ -891,35 +840,10 @@ static int team_ard_iterate(sgl_team* T, double L1, double L2, uint64_t seed, ui
         if (N <= 1) return SGL_OK;
         return team_exchange(T, who, {{2, &wbuf, (int64_t)k * mb, false}});
     };
-    auto tail_part = [&](int i) -> int {
-        HIPCHK(hipSetDevice(T->local[i]->device));
-        return sgl_scale_w_enqueue(T->local[i]);
-    };
-    auto fetch = [&](int i) -> int {
-        HIPCHK(hipSetDevice(T->local[i]->device));
-        return sgl_scale_w_fetch(T->local[i], &tols[i]);
-    };
-    if (T->pool) {
-        SGLCHK(team_parallel(T, [&](int i) -> int {
-            SGLCHK(h_update(i));
-            SGLCHK(exchange_d(i));
-            SGLCHK(w_partials(i));
-            SGLCHK(exchange_w(i));
-            SGLCHK(gene_block(i));
-            SGLCHK(exchange_gather(i));
-            SGLCHK(tail_part(i));
-            return fetch(i);
-        }));
-    } else {
-        for (int i = 0; i < nl; ++i) SGLCHK(h_update(i));
-        SGLCHK(exchange_d(-1));
-        for (int i = 0; i < nl; ++i) SGLCHK(w_partials(i));
-        SGLCHK(exchange_w(-1));
-        for (int i = 0; i < nl; ++i) SGLCHK(gene_block(i));
-        SGLCHK(exchange_gather(-1));
-        for (int i = 0; i < nl; ++i) SGLCHK(tail_part(i));
-        for (int i = 0; i < nl; ++i) SGLCHK(fetch(i));
-    }
+    auto tail_part = [&](int i) -> int { return sgl_scale_w_enqueue(T->local[i]); };
+    auto fetch = [&](int i) -> int { return sgl_scale_w_fetch(T->local[i], &tols[i]); };
+    SGLCHK(team_stages(T, {{false, h_update}, {true, exchange_d}, {false, w_partials}, {true, exchange_w}, {false, gene_block},
+                           {true, exchange_gather}, {false, tail_part}, {false, fetch}}));
     SGLCHK(team_tols_agree(tols));
     if (tol_out) *tol_out = tols[0];
     return SGL_OK;
@@ -927,11 +851,9 @@ static int team_ard_iterate(sgl_team* T, double L1, double L2, uint64_t seed, ui
 
 // mse_test (src/singlet.cpp:536-568) over the team: local sums of the per-cell losses, one double all-reduced
 static int team_mse_test(sgl_team* T, uint64_t seed, uint64_t inv_density, double* out) {
-    const int nl = (int)T->local.size();
-    std::vector<void*> sc(nl);
+    std::vector<void*> sc(T->local.size());
     auto local_loss = [&](int i) -> int {
         sgl_ctx* c = T->local[i];
-        HIPCHK(hipSetDevice(c->device));
         SGLCHK(sgl_mse_test_enqueue(c, seed, inv_density));
         sc[i] = c->scalars + 1;
         return SGL_OK;
@@ -940,15 +862,7 @@ static int team_mse_test(sgl_team* T, uint64_t seed, uint64_t inv_density, doubl
         if (T->nranks <= 1) return SGL_OK;
         return team_exchange(T, who, {{0, &sc, (int64_t)1, false}});
     };
-    if (T->pool) {
-        SGLCHK(team_parallel(T, [&](int i) -> int {
-            SGLCHK(local_loss(i));
-            return exchange(i);
-        }));
-    } else {
-        for (int i = 0; i < nl; ++i) SGLCHK(local_loss(i));
-        SGLCHK(exchange(-1));
-    }
+    SGLCHK(team_stages(T, {{false, local_loss}, {true, exchange}}));
     sgl_ctx* c0 = T->local[0];
     HIPCHK(hipSetDevice(c0->device));
     HIPCHK(hipMemcpyAsync(c0->pinned + 1, c0->scalars + 1, sizeof(double), hipMemcpyDeviceToHost, c0->stream));
@@ -957,15 +871,12 @@ static int team_mse_test(sgl_team* T, uint64_t seed, uint64_t inv_density, doubl
     return SGL_OK;
 }
 
-static int team_ard_run(sgl_team* T, double tol, int32_t maxit, double L1, double L2, uint64_t seed, uint64_t inv_density,
-                        double overfit_threshold, int32_t trace_test_mse, double* test_mse, int32_t* iter, double* tol_out,
-                        double* score_overfit, int32_t* n_trace, int32_t* n_iter, const sgl_callbacks* cb) {
-    if (trace_test_mse <= 0 || inv_density == 0 || !test_mse || !iter || !tol_out || !score_overfit || !n_trace) {
-        sgl_set_error("ard_run: bad arguments"); return SGL_EINVAL;
-    }
+static int team_ard_run(sgl_team* T, double tol, int32_t maxit, double L1, double L2, const ArdArgs& a, int32_t* n_iter,
+                        const sgl_callbacks* cb) {
+    SGLCHK(sgl_ard_args_check(a, "ard_run"));
     for (auto c : T->local) {
         if (c->k == 0) { sgl_set_error("team: no fit initialised"); return SGL_ESTATE; }
-        if (c->k > SGL_MASK_MAX_K) { sgl_set_error("c_ard_nmf: rank %d above the masked path's limit of %d", c->k, SGL_MASK_MAX_K); return SGL_EINVAL; }
+        SGLCHK(sgl_mask_rank_check(c->k));
     }
     if (T->nranks > 1) {
         bool have = true;
@@ -973,49 +884,17 @@ static int team_ard_run(sgl_team* T, double tol, int32_t maxit, double L1, doubl
         if (!have) SGLCHK(team_gene_counts(T));
     }
     SGLCHK(team_mask_workspace(T));
-    double tol_ = 1.0;
-    int nt = 0, it = 0;
-    auto push_trace = [&](int iter_now) -> int {   // l.1112-1121 / 1130-1141
-        double err = 0.0;
-        SGLCHK(team_mse_test(T, seed, inv_density, &err));
-        test_mse[nt] = err;
-        iter[nt] = iter_now;
-        tol_out[nt] = tol_;
-        double min_err = test_mse[0];
-        for (int t = 1; t <= nt; ++t) min_err = std::min(min_err, test_mse[t]);
-        score_overfit[nt] = (err - min_err) / (err + min_err);
-        ++nt;
-        return SGL_OK;
-    };
-    for (; it < maxit && tol_ > tol; ++it) {
-        SGLCHK(team_ard_iterate(T, L1, L2, seed, inv_density, &tol_));
-        if (it % trace_test_mse == 0) {
-            SGLCHK(push_trace(it));
-            if (cb && cb->log) cb->log(cb->user, it + 1, tol_, score_overfit[nt - 1]);
-            if (score_overfit[nt - 1] > overfit_threshold) break;
-        } else if (cb && cb->log) {
-            cb->log(cb->user, it + 1, tol_, NAN);
-        }
-        if (cb && cb->poll && cb->poll(cb->user)) { sgl_set_error("interrupted"); return SGL_EINTR; }
-    }
-    if (it % trace_test_mse != 0) SGLCHK(push_trace(it));
-    for (auto c : T->local) {
-        HIPCHK(hipSetDevice(c->device));
-        SGLCHK(sgl_fetch_sweeps(c));
-    }
-    *n_trace = nt;
-    if (n_iter) *n_iter = it;
-    return SGL_OK;
+    return sgl_als_loop(tol, maxit, [&](double* t) { return team_ard_iterate(T, L1, L2, a.seed, a.inv_density, t); }, &a,
+                        [&](double* err) { return team_mse_test(T, a.seed, a.inv_density, err); }, T->local.data(), (int)T->local.size(),
+                        nullptr, n_iter, cb);
 }
 
-int sgl_ard_run_team(sgl_ctx* c, double tol, int32_t maxit, double L1, double L2, uint64_t seed, uint64_t inv_density,
-                     double overfit_threshold, int32_t trace_test_mse, double* test_mse, int32_t* iter, double* tol_out,
-                     double* score_overfit, int32_t* n_trace, int32_t* n_iter, const sgl_callbacks* cb) {
+int sgl_ard_run_team(sgl_ctx* c, double tol, int32_t maxit, double L1, double L2, const ArdArgs& a, int32_t* n_iter,
+                     const sgl_callbacks* cb) {
     sgl_team* T = c->team;
     if (!T || T->local.size() != 1) { sgl_set_error("sgl_ard_run: this context is driven by its sgl_multi; call sgl_multi_ard_run"); return SGL_ESTATE; }
     T->nrow = c->A.nrow;
-    return team_ard_run(T, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter, tol_out,
-                        score_overfit, n_trace, n_iter, cb);
+    return team_ard_run(T, tol, maxit, L1, L2, a, n_iter, cb);
 }
 
 // ------------------------------------------------- one process per GPU (ABI) --
@@ -1098,11 +977,7 @@ extern "C" int sgl_nmf_iterate(sgl_ctx* c, double L1_w, double L1_h, double L2_w
         if (T->nranks > 1 && !c->gene_nnz_global) SGLCHK(team_gene_counts(T));
         return team_iterate(T, L1_w, L1_h, L2_w, L2_h, tol);
     }
-    SGLCHK(sgl_step_begin(c));
-    SGLCHK(sgl_step_h(c, L1_h, L2_h));
-    SGLCHK(sgl_step_scale_h(c));
-    SGLCHK(sgl_step_w(c, L1_w, L2_w));
-    return sgl_step_scale_w(c, tol);
+    return sgl_iterate_shard(c, L1_w, L1_h, L2_w, L2_h, nullptr, nullptr, tol);
 }
 
 // ---------------------------------------------- one process, all devices (ABI) --
@@ -1265,8 +1140,8 @@ extern "C" int sgl_multi_ard_run(sgl_multi* M, double tol, int32_t maxit, double
                                  double* tol_out, double* score_overfit, int32_t* n_trace, int32_t* n_iter,
                                  const sgl_callbacks* cb) {
     TEAM_GUARD(M);
-    return team_ard_run(M, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter, tol_out,
-                        score_overfit, n_trace, n_iter, cb);
+    return team_ard_run(M, tol, maxit, L1, L2, {seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter, tol_out, score_overfit, n_trace},
+                        n_iter, cb);
 }
 
 extern "C" int sgl_multi_get_factors(sgl_multi* M, double* w, double* d, double* h) {
@@ -1277,35 +1152,4 @@ extern "C" int sgl_multi_get_factors(sgl_multi* M, double* w, double* d, double*
     if (h)
         for (int r = 0; r < M->nranks; ++r) SGLCHK(sgl_get_factors(M->local[r], nullptr, nullptr, h + (size_t)M->cell_lo[r] * k));
     return SGL_OK;
-}
-
-// c_nmf on all devices of this process: what sgl_c_nmf runs when SINGLET_NGPU asks for more than one
-int sgl_c_nmf_multi(int ndev, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, double tol,
-                    uint16_t maxit, double L1_w, double L1_h, double L2_w, double L2_h, const double* w_init, int32_t k,
-                    double* w_out, double* d_out, double* h_out, int32_t* n_iter, double* tol_trace, const sgl_callbacks* cb) {
-    sgl_multi* M = nullptr;
-    SGLCHK(sgl_multi_create(ndev, nullptr, &M));
-    int rc = sgl_multi_upload_csc(M, Ax, Ai, Ap, nrow, ncol);
-    if (rc == SGL_OK) rc = sgl_multi_fit_init(M, k, w_init, 0);
-    if (rc == SGL_OK) rc = sgl_multi_nmf_run(M, tol, maxit, L1_w, L1_h, L2_w, L2_h, n_iter, tol_trace, cb);
-    if (rc == SGL_OK) rc = sgl_multi_get_factors(M, w_out, d_out, h_out);
-    sgl_multi_destroy(M);
-    return rc;
-}
-
-int sgl_c_ard_nmf_multi(int ndev, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, double tol,
-                        uint16_t maxit, double L1, double L2, const double* w_init, int32_t k, uint64_t seed, uint64_t inv_density,
-                        double overfit_threshold, uint16_t trace_test_mse, double* w_out, double* d_out, double* h_out,
-                        double* test_mse, int32_t* iter, double* tol_out, double* score_overfit, int32_t* n_trace,
-                        const sgl_callbacks* cb) {
-    sgl_multi* M = nullptr;
-    SGLCHK(sgl_multi_create(ndev, nullptr, &M));
-    int32_t nit = 0;
-    int rc = sgl_multi_upload_csc(M, Ax, Ai, Ap, nrow, ncol);
-    if (rc == SGL_OK) rc = sgl_multi_fit_init(M, k, w_init, 0);
-    if (rc == SGL_OK) rc = sgl_multi_ard_run(M, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, test_mse,
-                                             iter, tol_out, score_overfit, n_trace, &nit, cb);
-    if (rc == SGL_OK) rc = sgl_multi_get_factors(M, w_out, d_out, h_out);
-    sgl_multi_destroy(M);
-    return rc;
 }

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <atomic>
+#include <functional>
 #include <vector>
 #include <algorithm>
 
@@ -244,31 +245,89 @@ int sgl_nnls_shared(sgl_ctx* c, const double* G, double* B, double* X, const int
                     double L1, double L2, unsigned long long* counter, bool h_side = false);
 int sgl_scale_w_enqueue(sgl_ctx* c);            // scale(w, d); cor(w, w_prev) -> device scalar
 int sgl_scale_w_fetch(sgl_ctx* c, double* tol); // copy it out (synchronises the stream)
-int sgl_fetch_sweeps(sgl_ctx* c);
 // masked path pieces (singlet_hip.hip) used by the team's sharded c_ard_nmf (multi.hip)
 int sgl_mask_workspace(sgl_ctx* c);
 int sgl_predict_mask_dev(sgl_ctx* c, const DevCSC& M, const int64_t* col_nnz, const double* F, double* X, double* Bbuf,
                          uint64_t seed, uint64_t inv_density, double L1, double L2, int mask_t, int rhs_phase, int nnls_phase,
                          unsigned long long* counter);
 int sgl_mse_test_enqueue(sgl_ctx* c, uint64_t seed, uint64_t inv_density);   // local loss sum -> c->scalars[1]
-int sgl_ard_run_team(sgl_ctx* c, double tol, int32_t maxit, double L1, double L2, uint64_t seed, uint64_t inv_density,
-                     double overfit_threshold, int32_t trace_test_mse, double* test_mse, int32_t* iter, double* tol_out,
-                     double* score_overfit, int32_t* n_trace, int32_t* n_iter, const sgl_callbacks* cb);
-int sgl_c_ard_nmf_multi(int ndev, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, double tol,
-                        uint16_t maxit, double L1, double L2, const double* w_init, int32_t k, uint64_t seed, uint64_t inv_density,
-                        double overfit_threshold, uint16_t trace_test_mse, double* w_out, double* d_out, double* h_out,
-                        double* test_mse, int32_t* iter, double* tol_out, double* score_overfit, int32_t* n_trace,
-                        const sgl_callbacks* cb);
 #define SGL_MASK_MAX_K SGL_MAX_K   // the masked (ARD) path: MFMA Gram downdates up to k = 128, the generic VALU kernel above
 void sgl_team_detach(sgl_ctx* c);               // called by sgl_destroy
-int sgl_c_nmf_multi(int ndev, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, double tol,
-                    uint16_t maxit, double L1_w, double L1_h, double L2_w, double L2_h, const double* w_init, int32_t k,
-                    double* w_out, double* d_out, double* h_out, int32_t* n_iter, double* tol_trace, const sgl_callbacks* cb);
 
 // RAII-free phase timer helpers (driver side).
 int sgl_phase_begin(sgl_ctx* c, int phase, PhaseEvent* pe);
 int sgl_phase_end(sgl_ctx* c, PhaseEvent* pe);
 int sgl_ws_reserve(sgl_ctx* c, size_t bytes);
+struct Phase {  // scope guard: the phase ends on every exit (a failing hipEventRecord only loses the sample, never the call)
+    sgl_ctx* c;
+    PhaseEvent pe;
+    Phase(sgl_ctx* c_, int phase) : c(c_) { (void)sgl_phase_begin(c, phase, &pe); }
+    ~Phase() { (void)sgl_phase_end(c, &pe); }
+};
+
+// ---- host-side helpers every unit shares ------------------------------------
+template <typename T>
+inline int dev_alloc(T** p, size_t count) {
+    *p = nullptr;
+    if (count == 0) count = 1;
+    hipError_t e = sgl_pool_malloc(p, count * sizeof(T));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        sgl_set_error("hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
+        return SGL_ENOMEM;
+    }
+    return SGL_OK;
+}
+template <typename T>
+inline void dev_free(T*& p) {
+    if (p) (void)sgl_pool_free(p);
+    p = nullptr;
+}
+// device buffer released on every return path (alloc on a held buffer frees it first)
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    ~DevBuf() { dev_free(p); }
+    int alloc(size_t n) { dev_free(p); return dev_alloc(&p, n); }
+};
+// the context of a one-shot call, destroyed on every return path
+struct CtxHolder {
+    sgl_ctx* c = nullptr;
+    ~CtxHolder() { if (c) sgl_destroy(c); }
+};
+inline int current_device_or_zero() {
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; }
+    return d;
+}
+
+// ---- the ALS loops (singlet_hip.hip), shared with the team (multi.hip) -------
+// what c_ard_nmf_base (src/singlet.cpp:1090-1152) takes and returns beyond c_nmf_base: the mask, the trace schedule, the traces
+struct ArdArgs {
+    uint64_t seed, inv_density;
+    double overfit_threshold;
+    int32_t trace_test_mse;
+    double* test_mse;
+    int32_t* iter;
+    double* tol_out;
+    double* score_overfit;
+    int32_t* n_trace;
+};
+int sgl_ard_args_check(const ArdArgs& a, const char* who);   // SGL_EINVAL "<who>: bad arguments"
+int sgl_mask_rank_check(int k);                               // SGL_EINVAL above SGL_MASK_MAX_K
+// THE loop of c_nmf_base l.647-664 (ard == nullptr: tol_trace[it]) and c_ard_nmf_base l.1090-1152 (ard + mse_test: a trace row
+// every trace_test_mse iterations and after the last one, the overfit break).  iterate: one iteration, returns tol.  The sweep
+// counters of ctxs[0 .. nctx) are fetched at the end.  log gets NAN as the score of an untraced iteration; poll ends an iteration.
+int sgl_als_loop(double tol, int32_t maxit, const std::function<int(double*)>& iterate, const ArdArgs* ard,
+                 const std::function<int(double*)>& mse_test, sgl_ctx* const* ctxs, int nctx, double* tol_trace, int32_t* n_iter,
+                 const sgl_callbacks* cb);
+// one iteration on ONE shard (no team): step_begin, step_h, scale_h, step_w, scale_w -- the masked steps with `mask`; cb (may be
+// NULL) is polled after scale_h
+int sgl_iterate_shard(sgl_ctx* c, double L1_w, double L1_h, double L2_w, double L2_h, const ArdArgs* mask, const sgl_callbacks* cb,
+                      double* tol);
+int sgl_ard_run_team(sgl_ctx* c, double tol, int32_t maxit, double L1, double L2, const ArdArgs& a, int32_t* n_iter,
+                     const sgl_callbacks* cb);
 
 // ---- kernel launchers (each enqueues on `s`, returns SGL_* code) ----------
 // hash / synthetic generator / mask

@@ -70,25 +70,6 @@ extern "C" int sgl_device_count(void) {
 }
 
 // ------------------------------------------------------------- ctx helpers --
-template <typename T>
-static int dev_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = sgl_pool_malloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        sgl_set_error("hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
-        return SGL_ENOMEM;
-    }
-    return SGL_OK;
-}
-
-template <typename T>
-static void dev_free(T*& p) {
-    if (p) (void)sgl_pool_free(p);
-    p = nullptr;
-}
-
 int sgl_ws_reserve(sgl_ctx* c, size_t bytes) {
     if (bytes <= c->ws_bytes) return SGL_OK;
     // grow; callers never hold ws contents across a reserve
@@ -148,13 +129,6 @@ static int drain_timing(sgl_ctx* c) {
     c->pending.clear();
     return SGL_OK;
 }
-
-struct Phase {  // scope guard
-    sgl_ctx* c;
-    PhaseEvent pe;
-    Phase(sgl_ctx* c_, int phase) : c(c_) { (void)sgl_phase_begin(c, phase, &pe); }
-    ~Phase() { (void)sgl_phase_end(c, &pe); }
-};
 
 static void free_csc(DevCSC& M) {
     dev_free(M.x);
@@ -750,7 +724,6 @@ extern "C" int sgl_weight_by_split(sgl_ctx* c, const int32_t* split_by, int32_t 
     return rc;
 }
 
-static int current_device_or_zero();
 // One-shot form for the Rcpp glue (`_singlet_weight_by_split`, src/RcppExports.cpp:17-27): the dgCMatrix slots in,
 // the re-weighted values out (x_out may alias Ax: the reference rewrites the values of A in place, l.136-141).
 extern "C" int sgl_c_weight_by_split(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol,
@@ -996,7 +969,7 @@ extern "C" int sgl_step_scale_w(sgl_ctx* c, double* tol_out) {
     return sgl_scale_w_fetch(c, tol_out);
 }
 
-int sgl_fetch_sweeps(sgl_ctx* c) {
+static int fetch_sweeps(sgl_ctx* c) {
     unsigned long long h[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(h, c->sweep_counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1008,30 +981,70 @@ int sgl_fetch_sweeps(sgl_ctx* c) {
     return SGL_OK;
 }
 
+static bool interrupted(const sgl_callbacks* cb) {
+    if (!(cb && cb->poll && cb->poll(cb->user))) return false;
+    sgl_set_error("interrupted");
+    return true;
+}
+
+int sgl_iterate_shard(sgl_ctx* c, double L1_w, double L1_h, double L2_w, double L2_h, const ArdArgs* mask, const sgl_callbacks* cb,
+                      double* tol) {
+    SGLCHK(sgl_step_begin(c));
+    SGLCHK(mask ? sgl_step_h_masked(c, L1_h, L2_h, mask->seed, mask->inv_density) : sgl_step_h(c, L1_h, L2_h));
+    SGLCHK(sgl_step_scale_h(c));
+    if (interrupted(cb)) return SGL_EINTR;
+    SGLCHK(mask ? sgl_step_w_masked(c, L1_w, L2_w, mask->seed, mask->inv_density) : sgl_step_w(c, L1_w, L2_w));
+    return sgl_step_scale_w(c, tol);
+}
+
+int sgl_als_loop(double tol, int32_t maxit, const std::function<int(double*)>& iterate, const ArdArgs* ard,
+                 const std::function<int(double*)>& mse_test, sgl_ctx* const* ctxs, int nctx, double* tol_trace, int32_t* n_iter,
+                 const sgl_callbacks* cb) {
+    double tol_ = 1.0;
+    int it = 0, nt = 0;
+    auto push_trace = [&](int iter_now) -> int {   // l.1112-1121 / 1130-1141
+        double err = 0.0;
+        SGLCHK(mse_test(&err));
+        ard->test_mse[nt] = err;
+        ard->iter[nt] = iter_now;
+        ard->tol_out[nt] = tol_;
+        double min_err = ard->test_mse[0];
+        for (int t = 1; t <= nt; ++t) min_err = std::min(min_err, ard->test_mse[t]);
+        ard->score_overfit[nt] = (err - min_err) / (err + min_err);
+        ++nt;
+        return SGL_OK;
+    };
+    // for (iter_ = 0; iter_ < maxit && tol_ > tol; ++iter_)  -- src/singlet.cpp:647, 1101
+    for (; it < maxit && tol_ > tol; ++it) {
+        SGLCHK(iterate(&tol_));
+        if (tol_trace) tol_trace[it] = tol_;
+        double score = NAN;   // what log sees on an untraced iteration, and in the plain fit
+        if (ard && it % ard->trace_test_mse == 0) {
+            SGLCHK(push_trace(it));
+            score = ard->score_overfit[nt - 1];
+        }
+        if (cb && cb->log) cb->log(cb->user, it + 1, tol_, score);
+        if (ard && score > ard->overfit_threshold) break;
+        if (interrupted(cb)) return SGL_EINTR;
+    }
+    if (ard && it % ard->trace_test_mse != 0) SGLCHK(push_trace(it));
+    for (int q = 0; q < nctx; ++q) {
+        HIPCHK(hipSetDevice(ctxs[q]->device));
+        SGLCHK(fetch_sweeps(ctxs[q]));
+    }
+    if (ard) *ard->n_trace = nt;
+    if (n_iter) *n_iter = it;
+    return SGL_OK;
+}
+
 extern "C" int sgl_nmf_run(sgl_ctx* c, double tol, int32_t maxit, double L1_w, double L1_h, double L2_w, double L2_h,
                            int32_t* n_iter, double* tol_trace, const sgl_callbacks* cb) {
     FIT_GUARD(c);
-    double tol_ = 1.0;
-    int it = 0;
-    // for (iter_ = 0; iter_ < maxit && tol_ > tol; ++iter_)  -- src/singlet.cpp:647
-    for (; it < maxit && tol_ > tol; ++it) {
-        if (c->team) {  // native team (one process per GPU): the team iteration of multi.hip
-            SGLCHK(sgl_nmf_iterate(c, L1_w, L1_h, L2_w, L2_h, &tol_));
-        } else {
-            SGLCHK(sgl_step_begin(c));
-            SGLCHK(sgl_step_h(c, L1_h, L2_h));
-            SGLCHK(sgl_step_scale_h(c));
-            if (cb && cb->poll && cb->poll(cb->user)) { sgl_set_error("interrupted"); return SGL_EINTR; }
-            SGLCHK(sgl_step_w(c, L1_w, L2_w));
-            SGLCHK(sgl_step_scale_w(c, &tol_));
-        }
-        if (tol_trace) tol_trace[it] = tol_;
-        if (cb && cb->log) cb->log(cb->user, it + 1, tol_, NAN);
-        if (cb && cb->poll && cb->poll(cb->user)) { sgl_set_error("interrupted"); return SGL_EINTR; }
-    }
-    SGLCHK(sgl_fetch_sweeps(c));
-    if (n_iter) *n_iter = it;
-    return SGL_OK;
+    // a rank of a native team (one process per GPU): the team iteration of multi.hip, looked up anew every iteration
+    auto iterate = [&](double* t) -> int {
+        return c->team ? sgl_nmf_iterate(c, L1_w, L1_h, L2_w, L2_h, t) : sgl_iterate_shard(c, L1_w, L1_h, L2_w, L2_h, nullptr, cb, t);
+    };
+    return sgl_als_loop(tol, maxit, iterate, nullptr, nullptr, &c, 1, tol_trace, n_iter, cb);
 }
 
 // One H-update against the resident (already scaled) W: body of c_project_model l.409-411
@@ -1186,71 +1199,39 @@ extern "C" int sgl_step_w_masked(sgl_ctx* c, double L1, double L2, uint64_t seed
                                 SGL_PH_RHS_W, SGL_PH_NNLS_W, c->sweep_counters + 1);
 }
 
+int sgl_ard_args_check(const ArdArgs& a, const char* who) {
+    if (a.trace_test_mse > 0 && a.inv_density != 0 && a.test_mse && a.iter && a.tol_out && a.score_overfit && a.n_trace) return SGL_OK;
+    sgl_set_error("%s: bad arguments", who);
+    return SGL_EINVAL;
+}
+int sgl_mask_rank_check(int k) {
+    if (k <= SGL_MASK_MAX_K) return SGL_OK;
+    sgl_set_error("c_ard_nmf: rank %d above the masked path's limit of %d", k, SGL_MASK_MAX_K);
+    return SGL_EINVAL;
+}
+
 // c_ard_nmf_base: src/singlet.cpp:1090-1152
+static int ard_run(sgl_ctx* c, double tol, int32_t maxit, double L1, double L2, const ArdArgs& a, int32_t* n_iter,
+                   const sgl_callbacks* cb) {
+    FIT_GUARD(c);
+    if (c->graph.n) { sgl_set_error("sgl_ard_run: a cell graph is set (graph-convolutional NMF has no masked variant)"); return SGL_EINVAL; }
+    if (c->allreduce) { sgl_set_error("the masked (ARD) path is cell-sharded on a native team only (sgl_multi_* / sgl_comm_init_rank), not through the all-reduce hook"); return SGL_EINVAL; }
+    SGLCHK(sgl_mask_rank_check(c->k));
+    SGLCHK(sgl_ard_args_check(a, "sgl_ard_run"));
+    if (c->team) return sgl_ard_run_team(c, tol, maxit, L1, L2, a, n_iter, cb);   // native team, one process per GPU: the sharded loop of multi.hip
+    return sgl_als_loop(tol, maxit, [&](double* t) { return sgl_iterate_shard(c, L1, L1, L2, L2, &a, cb, t); }, &a,
+                        [&](double* err) { return mse_test_dev(c, a.seed, a.inv_density, err); }, &c, 1, nullptr, n_iter, cb);
+}
+
 extern "C" int sgl_ard_run(sgl_ctx* c, double tol, int32_t maxit, double L1, double L2, uint64_t seed,
                            uint64_t inv_density, double overfit_threshold, int32_t trace_test_mse, double* test_mse,
                            int32_t* iter, double* tol_out, double* score_overfit, int32_t* n_trace, int32_t* n_iter,
                            const sgl_callbacks* cb) {
-    FIT_GUARD(c);
-    if (c->graph.n) { sgl_set_error("sgl_ard_run: a cell graph is set (graph-convolutional NMF has no masked variant)"); return SGL_EINVAL; }
-    if (c->allreduce) { sgl_set_error("the masked (ARD) path is cell-sharded on a native team only (sgl_multi_* / sgl_comm_init_rank), not through the all-reduce hook"); return SGL_EINVAL; }
-    if (c->k > SGL_MASK_MAX_K) { sgl_set_error("c_ard_nmf: rank %d above the masked path's limit of %d", c->k, SGL_MASK_MAX_K); return SGL_EINVAL; }
-    if (trace_test_mse <= 0 || inv_density == 0 || !test_mse || !iter || !tol_out || !score_overfit || !n_trace) {
-        sgl_set_error("sgl_ard_run: bad arguments"); return SGL_EINVAL;
-    }
-    if (c->team)   // native team, one process per GPU: the sharded loop of multi.hip
-        return sgl_ard_run_team(c, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter,
-                                tol_out, score_overfit, n_trace, n_iter, cb);
-    double tol_ = 1.0;
-    int nt = 0;
-    int it = 0;
-    auto push_trace = [&](int iter_now) -> int {
-        double err = 0.0;
-        SGLCHK(mse_test_dev(c, seed, inv_density, &err));
-        test_mse[nt] = err;
-        iter[nt] = iter_now;
-        tol_out[nt] = tol_;
-        double min_err = test_mse[0];
-        for (int t = 1; t <= nt; ++t) min_err = std::min(min_err, test_mse[t]);
-        score_overfit[nt] = (err - min_err) / (err + min_err);
-        ++nt;
-        return SGL_OK;
-    };
-    for (; it < maxit && tol_ > tol; ++it) {
-        SGLCHK(sgl_step_begin(c));
-        SGLCHK(sgl_step_h_masked(c, L1, L2, seed, inv_density));
-        SGLCHK(sgl_step_scale_h(c));
-        if (cb && cb->poll && cb->poll(cb->user)) { sgl_set_error("interrupted"); return SGL_EINTR; }
-        SGLCHK(sgl_step_w_masked(c, L1, L2, seed, inv_density));
-        SGLCHK(sgl_step_scale_w(c, &tol_));
-        if (it % trace_test_mse == 0) {
-            SGLCHK(push_trace(it));
-            if (cb && cb->log) cb->log(cb->user, it + 1, tol_, score_overfit[nt - 1]);
-            if (score_overfit[nt - 1] > overfit_threshold) break;
-        } else if (cb && cb->log) {
-            cb->log(cb->user, it + 1, tol_, NAN);
-        }
-        if (cb && cb->poll && cb->poll(cb->user)) { sgl_set_error("interrupted"); return SGL_EINTR; }
-    }
-    if (it % trace_test_mse != 0) SGLCHK(push_trace(it));
-    SGLCHK(sgl_fetch_sweeps(c));
-    *n_trace = nt;
-    if (n_iter) *n_iter = it;
-    return SGL_OK;
+    return ard_run(c, tol, maxit, L1, L2, {seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter, tol_out, score_overfit, n_trace},
+                   n_iter, cb);
 }
 
 // ---------------------------------------------------------- one-shot ABI ----
-struct CtxHolder {
-    sgl_ctx* c = nullptr;
-    ~CtxHolder() { if (c) sgl_destroy(c); }
-};
-
-static int current_device_or_zero() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; }
-    return d;
-}
-
 // ---- resident matrix between one-shot calls (opt-in) -------------------------------------------------
 // R's ard_nmf / cross_validate_nmf call c_ard_nmf / c_nmf tens of times on the SAME A (R/ard_nmf.R:95-160,
 // R/cross_validate_nmf.R:69-97): every call would upload, validate, transpose and re-tile 2 x 18 GB at config 3.
@@ -1294,6 +1275,23 @@ static uint64_t fingerprint(const double* x, const int32_t* idx, const int32_t* 
     return h;
 }
 
+// The context of a one-shot call: a fresh one is destroyed on scope exit; the cached one (acquire_ctx) is kept, and the calls
+// that share it are serialised.
+struct OneShotCtx {
+    std::unique_lock<std::mutex> lk;   // acquire_ctx: held while the cache is in play
+    sgl_ctx* c = nullptr;
+    bool cached = false;
+    bool ok = false;   // set when the call succeeded
+    double t_call = 0.0;   // > 0: this call fills g_times (sgl_c_nmf / sgl_c_ard_nmf)
+    ~OneShotCtx() {
+        if (!c) return;
+        if (!cached) sgl_destroy(c);
+        // a cached context whose call failed (interrupt, sticky HIP error ...) is not handed to the next call
+        else if (!ok && g_cache.c == c) { sgl_destroy(c); g_cache = CachedCtx(); }
+    }
+    int done(int rc) { ok = (rc == SGL_OK); return rc; }
+};
+
 // A context with (Ax, Ai, Ap) resident: from the cache when allowed and matching, else fresh.  *cached tells the
 // caller not to destroy it.
 static int acquire_ctx(const double* Ax, const int32_t* Ai, const int32_t* Ap, const double* Atx, const int32_t* Ati,
@@ -1336,20 +1334,6 @@ static int acquire_ctx(const double* Ax, const int32_t* Ai, const int32_t* Ap, c
     *cached = true;
     return SGL_OK;
 }
-struct AcquiredCtx {   // destroys a non-cached context on scope exit; serialises the calls that share the cached one
-    std::unique_lock<std::mutex> lk{g_cache_mu};
-    sgl_ctx* c = nullptr;
-    bool cached = false;
-    bool ok = false;   // set by the entry point when its call succeeded
-    ~AcquiredCtx() {
-        if (!c) return;
-        if (!cached) sgl_destroy(c);
-        // a cached context whose call failed (interrupt, sticky HIP error ...) is not handed to the next call
-        else if (!ok && g_cache.c == c) { sgl_destroy(c); g_cache = CachedCtx(); }
-    }
-    int done(int rc) { ok = (rc == SGL_OK); return rc; }
-};
-
 // releases the cached context (if any); also what a host calls before unloading the library
 extern "C" int sgl_cache_release(void) {
     std::lock_guard<std::mutex> lk(g_cache_mu);
@@ -1365,6 +1349,90 @@ extern "C" int sgl_pool_info(int64_t* cached_bytes) {
     return SGL_OK;
 }
 
+// What every one-shot fit does once its matrix is resident: sgl_fit_init, the entry point's hook (links, graph, dense rules),
+// the loop -- c_ard_nmf_base with `ard`, else c_nmf_base -- and the factors out.
+struct FitCall {
+    int32_t k;
+    const double* w_init;
+    double tol;
+    int32_t maxit;
+    double L1_w, L1_h, L2_w, L2_h;
+    const ArdArgs* ard;
+    double *w_out, *d_out, *h_out;
+    int32_t* n_iter;
+    double* tol_trace;
+    const sgl_callbacks* cb;
+};
+static int rank_check(int k) {
+    if (k > 0 && k <= SGL_MAX_K) return SGL_OK;
+    sgl_set_error("rank k=%d unsupported (1..%d)", k, SGL_MAX_K);
+    return SGL_EINVAL;
+}
+static int one_shot_fit(OneShotCtx& hd, const FitCall& f, const std::function<int(sgl_ctx*)>& hook = nullptr) {
+    sgl_ctx* c = hd.c;
+    const double t_fit = wall_now();
+    SGLCHK(sgl_fit_init(c, f.k, f.w_init, 0));
+    if (hd.t_call > 0) HIPCHK(hipStreamSynchronize(c->stream));   // delimits fit_init_s
+    if (hook) SGLCHK(hook(c));
+    const double t_run = wall_now();
+    if (f.ard) SGLCHK(ard_run(c, f.tol, f.maxit, f.L1_w, f.L2_w, *f.ard, nullptr, f.cb));
+    else SGLCHK(sgl_nmf_run(c, f.tol, f.maxit, f.L1_w, f.L1_h, f.L2_w, f.L2_h, f.n_iter, f.tol_trace, f.cb));
+    const double t_get = wall_now();
+    const int rc = sgl_get_factors(c, f.w_out, f.d_out, f.h_out);
+    const double t_end = wall_now();
+    if (hd.t_call > 0) {
+        g_times.fit_init_s = t_run - t_fit;
+        g_times.iterate_s = t_get - t_run;
+        g_times.d2h_s = t_end - t_get;
+        g_times.total_s = t_end - hd.t_call;
+    }
+    return hd.done(rc);
+}
+
+// c_nmf / c_ard_nmf on all devices of this process: what SINGLET_NGPU > 1 runs
+struct MultiHolder {
+    sgl_multi* M = nullptr;
+    ~MultiHolder() { if (M) sgl_multi_destroy(M); }
+};
+static int one_shot_fit_multi(int ndev, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, const FitCall& f) {
+    MultiHolder hd;
+    SGLCHK(sgl_multi_create(ndev, nullptr, &hd.M));
+    SGLCHK(sgl_multi_upload_csc(hd.M, Ax, Ai, Ap, nrow, ncol));
+    SGLCHK(sgl_multi_fit_init(hd.M, f.k, f.w_init, 0));
+    if (f.ard) {
+        const ArdArgs& a = *f.ard;
+        SGLCHK(sgl_multi_ard_run(hd.M, f.tol, f.maxit, f.L1_w, f.L2_w, a.seed, a.inv_density, a.overfit_threshold, a.trace_test_mse, a.test_mse,
+                                 a.iter, a.tol_out, a.score_overfit, a.n_trace, nullptr, f.cb));
+    } else {
+        SGLCHK(sgl_multi_nmf_run(hd.M, f.tol, f.maxit, f.L1_w, f.L1_h, f.L2_w, f.L2_h, f.n_iter, f.tol_trace, f.cb));
+    }
+    return sgl_multi_get_factors(hd.M, f.w_out, f.d_out, f.h_out);
+}
+
+// sgl_c_nmf / sgl_c_ard_nmf: the two entry points that honour SINGLET_NGPU and SINGLET_HIP_CACHE and report their wall clock
+// (sgl_call_times_get: of THIS call from here on, whichever way it goes and however it ends)
+static int one_shot_cached(const double* Ax, const int32_t* Ai, const int32_t* Ap, const double* Atx, const int32_t* Ati,
+                           const int32_t* Atp, int32_t nrow, int32_t ncol, const FitCall& f) {
+    g_times = CallTimes();
+    const double t_call = wall_now();
+    // SINGLET_NGPU=N (N > 1): shard the cells over the first N devices of this process (section 2b of the
+    // header); the R side does not change.  Asking for more devices than there are is an error, not a fallback.
+    const char* e = getenv("SINGLET_NGPU");
+    const int want = e ? atoi(e) : 0;
+    if (want > 1) {
+        if (want > sgl_device_count()) { sgl_set_error("SINGLET_NGPU=%d but only %d gfx950 device(s) are visible", want, sgl_device_count()); return SGL_ENODEV; }
+        const int rc = one_shot_fit_multi(want, Ax, Ai, Ap, nrow, ncol, f);
+        g_times = CallTimes();   // (the per-step fields describe a call on one context: the uploads of the ranks are not summed into them)
+        if (rc == SGL_OK) g_times.total_s = wall_now() - t_call;
+        return rc;
+    }
+    OneShotCtx hd;
+    hd.t_call = t_call;
+    hd.lk = std::unique_lock<std::mutex>(g_cache_mu);
+    SGLCHK(acquire_ctx(Ax, Ai, Ap, Atx, Ati, Atp, nrow, ncol, &hd.c, &hd.cached));
+    return one_shot_fit(hd, f);
+}
+
 extern "C" int sgl_c_nmf(const double* Ax, const int32_t* Ai, const int32_t* Ap, const double* Atx, const int32_t* Ati,
                          const int32_t* Atp, int32_t nrow, int32_t ncol, double tol, uint16_t maxit, int verbose,
                          double L1_w, double L1_h, double L2_w, double L2_h, uint16_t threads, const double* w_init,
@@ -1372,33 +1440,9 @@ extern "C" int sgl_c_nmf(const double* Ax, const int32_t* Ai, const int32_t* Ap,
                          const sgl_callbacks* cb) {
     (void)verbose; (void)threads;
     if (!w_init || !w_out || !d_out || !h_out) { sgl_set_error("sgl_c_nmf: NULL factor buffer"); return SGL_EINVAL; }
-    if (k <= 0 || k > SGL_MAX_K) { sgl_set_error("rank k=%d unsupported (1..%d)", k, SGL_MAX_K); return SGL_EINVAL; }   // before any upload
-    // SINGLET_NGPU=N (N > 1): shard the cells over the first N devices of this process (section 2b of the
-    // header); the R side does not change.  Asking for more devices than there are is an error, not a fallback.
-    if (const char* e = getenv("SINGLET_NGPU")) {
-        const int want = atoi(e);
-        if (want > 1) {
-            if (want > sgl_device_count()) { sgl_set_error("SINGLET_NGPU=%d but only %d gfx950 device(s) are visible", want, sgl_device_count()); return SGL_ENODEV; }
-            return sgl_c_nmf_multi(want, Ax, Ai, Ap, nrow, ncol, tol, maxit, L1_w, L1_h, L2_w, L2_h, w_init, k, w_out, d_out, h_out, n_iter, tol_trace, cb);
-        }
-    }
-    g_times = CallTimes();
-    const double t_call = wall_now();
-    AcquiredCtx hd;
-    SGLCHK(acquire_ctx(Ax, Ai, Ap, Atx, Ati, Atp, nrow, ncol, &hd.c, &hd.cached));
-    const double t_fit = wall_now();
-    SGLCHK(sgl_fit_init(hd.c, k, w_init, 0));
-    HIPCHK(hipStreamSynchronize(hd.c->stream));
-    const double t_run = wall_now();
-    SGLCHK(sgl_nmf_run(hd.c, tol, maxit, L1_w, L1_h, L2_w, L2_h, n_iter, tol_trace, cb));
-    const double t_get = wall_now();
-    const int rc = sgl_get_factors(hd.c, w_out, d_out, h_out);
-    const double t_end = wall_now();
-    g_times.fit_init_s = t_run - t_fit;
-    g_times.iterate_s = t_get - t_run;
-    g_times.d2h_s = t_end - t_get;
-    g_times.total_s = t_end - t_call;
-    return hd.done(rc);
+    SGLCHK(rank_check(k));   // before any upload
+    return one_shot_cached(Ax, Ai, Ap, Atx, Ati, Atp, nrow, ncol,
+                           {k, w_init, tol, maxit, L1_w, L1_h, L2_w, L2_h, nullptr, w_out, d_out, h_out, n_iter, tol_trace, cb});
 }
 
 // c_linked_nmf's link matrices (src/singlet.cpp:1059-1065): each is used only if its column count
@@ -1442,13 +1486,11 @@ extern "C" int sgl_c_linked_nmf(const double* Ax, const int32_t* Ai, const int32
                                 double* tol_trace, const sgl_callbacks* cb) {
     (void)verbose; (void)threads;
     if (!w_init || !w_out || !d_out || !h_out) { sgl_set_error("sgl_c_linked_nmf: NULL factor buffer"); return SGL_EINVAL; }
-    CtxHolder hd;
+    OneShotCtx hd;
     SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, Atx, Ati, Atp, nrow, ncol, 0, ncol));
-    SGLCHK(sgl_fit_init(hd.c, k, w_init, 0));
-    SGLCHK(sgl_set_links(hd.c, link_h, link_h_rows, link_h_cols, link_w, link_w_rows, link_w_cols));
-    SGLCHK(sgl_nmf_run(hd.c, tol, maxit, L1, L1, L2, L2, n_iter, tol_trace, cb));
-    return sgl_get_factors(hd.c, w_out, d_out, h_out);
+    return one_shot_fit(hd, {k, w_init, tol, maxit, L1, L1, L2, L2, nullptr, w_out, d_out, h_out, n_iter, tol_trace, cb},
+                        [&](sgl_ctx* c) { return sgl_set_links(c, link_h, link_h_rows, link_h_cols, link_w, link_w_rows, link_w_cols); });
 }
 
 // c_gcnmf's cell graph G (src/singlet.cpp:1668-1730): n x n, n = the cells of the resident matrix, as a dgCMatrix.  Checked
@@ -1545,7 +1587,7 @@ extern "C" int sgl_c_gcnmf(const double* Ax, const int32_t* Ai, const int32_t* A
         sgl_set_error("sgl_c_gcnmf: w is %d x %d; expected k x m or m x k with k = %d, m = %d", w_rows, w_cols, k, nrow);
         return SGL_EINVAL;
     }
-    if (k <= 0 || k > SGL_MAX_K) { sgl_set_error("rank k=%d unsupported (1..%d)", k, SGL_MAX_K); return SGL_EINVAL; }
+    SGLCHK(rank_check(k));
     // the fit's W is k x m column-major (factor rows of a gene contiguous)
     std::vector<double> wk;
     const double* w0 = w_init;
@@ -1555,14 +1597,12 @@ extern "C" int sgl_c_gcnmf(const double* Ax, const int32_t* Ai, const int32_t* A
             for (int32_t f = 0; f < k; ++f) wk[(size_t)g * k + f] = w_init[(size_t)f * nrow + g];
         w0 = wk.data();
     }
-    CtxHolder hd;
+    std::vector<double> wkm((size_t)k * nrow);
+    OneShotCtx hd;
     SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, Atx, Ati, Atp, nrow, ncol, 0, ncol));
-    SGLCHK(sgl_fit_init(hd.c, k, w0, 0));
-    SGLCHK(sgl_set_graph(hd.c, Gx, Gi, Gp, G_nrow, G_ncol));
-    SGLCHK(sgl_nmf_run(hd.c, tol, maxit, L1, L1, L2, L2, n_iter, tol_trace, cb));
-    std::vector<double> wkm((size_t)k * nrow);
-    SGLCHK(sgl_get_factors(hd.c, wkm.data(), d_out, h_out));
+    SGLCHK(one_shot_fit(hd, {k, w0, tol, maxit, L1, L1, L2, L2, nullptr, wkm.data(), d_out, h_out, n_iter, tol_trace, cb},
+                        [&](sgl_ctx* c) { return sgl_set_graph(c, Gx, Gi, Gp, G_nrow, G_ncol); }));
     for (int32_t f = 0; f < k; ++f)   // w.transpose(): m x k column-major
         for (int32_t g = 0; g < nrow; ++g) w_out[(size_t)f * nrow + g] = wkm[(size_t)g * k + f];
     return SGL_OK;
@@ -1571,20 +1611,21 @@ extern "C" int sgl_c_gcnmf(const double* Ax, const int32_t* Ai, const int32_t* A
 // c_nmf_dense (src/singlet.cpp:1052-1054): sgl_upload_dense keeps the matrix as its CSC image (zeros add exact zeros
 // to the right-hand sides) and, when it really is dense, as the dense copy the right-hand sides are then GEMMs on; the
 // one semantic difference of the dense predict (:370-381) is that it solves EVERY column, all-zero ones included.
+static int solve_every_column(sgl_ctx* c) {   // the dense predict has no empty-column skip (src/singlet.cpp:370-381)
+    c->solve_empty = true;
+    return SGL_OK;
+}
 extern "C" int sgl_c_nmf_dense(const double* A, int32_t nrow, int32_t ncol, double tol, uint16_t maxit, int verbose,
                                double L1_w, double L1_h, double L2_w, double L2_h, uint16_t threads, const double* w_init,
                                int32_t k, double* w_out, double* d_out, double* h_out, int32_t* n_iter, double* tol_trace,
                                const sgl_callbacks* cb) {
     (void)verbose; (void)threads;
     if (!A || !w_init || !w_out || !d_out || !h_out || nrow <= 0 || ncol <= 0) { sgl_set_error("sgl_c_nmf_dense: bad arguments"); return SGL_EINVAL; }
-    if (k <= 0 || k > SGL_MAX_K) { sgl_set_error("rank k=%d unsupported (1..%d)", k, SGL_MAX_K); return SGL_EINVAL; }
-    CtxHolder hd;
+    SGLCHK(rank_check(k));
+    OneShotCtx hd;
     SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     SGLCHK(sgl_upload_dense(hd.c, A, nrow, ncol));
-    SGLCHK(sgl_fit_init(hd.c, k, w_init, 0));
-    hd.c->solve_empty = true;
-    SGLCHK(sgl_nmf_run(hd.c, tol, maxit, L1_w, L1_h, L2_w, L2_h, n_iter, tol_trace, cb));
-    return sgl_get_factors(hd.c, w_out, d_out, h_out);
+    return one_shot_fit(hd, {k, w_init, tol, maxit, L1_w, L1_h, L2_w, L2_h, nullptr, w_out, d_out, h_out, n_iter, tol_trace, cb}, solve_every_column);
 }
 
 extern "C" int sgl_c_ard_nmf(const double* Ax, const int32_t* Ai, const int32_t* Ap, const double* Atx,
@@ -1596,34 +1637,10 @@ extern "C" int sgl_c_ard_nmf(const double* Ax, const int32_t* Ai, const int32_t*
                              const sgl_callbacks* cb) {
     (void)verbose; (void)threads;
     if (!w_init || !w_out || !d_out || !h_out) { sgl_set_error("sgl_c_ard_nmf: NULL factor buffer"); return SGL_EINVAL; }
-    if (k > SGL_MASK_MAX_K) { sgl_set_error("c_ard_nmf: rank %d above the masked path's limit of %d", k, SGL_MASK_MAX_K); return SGL_EINVAL; }
-    if (const char* e = getenv("SINGLET_NGPU")) {   // as in sgl_c_nmf
-        const int want = atoi(e);
-        if (want > 1) {
-            if (want > sgl_device_count()) { sgl_set_error("SINGLET_NGPU=%d but only %d gfx950 device(s) are visible", want, sgl_device_count()); return SGL_ENODEV; }
-            return sgl_c_ard_nmf_multi(want, Ax, Ai, Ap, nrow, ncol, tol, maxit, L1, L2, w_init, k, seed, inv_density, overfit_threshold,
-                                       trace_test_mse, w_out, d_out, h_out, test_mse, iter, tol_out, score_overfit, n_trace, cb);
-        }
-    }
-    g_times = CallTimes();
-    const double t_call = wall_now();
-    AcquiredCtx hd;
-    SGLCHK(acquire_ctx(Ax, Ai, Ap, Atx, Ati, Atp, nrow, ncol, &hd.c, &hd.cached));
-    const double t_fit = wall_now();
-    SGLCHK(sgl_fit_init(hd.c, k, w_init, 0));
-    HIPCHK(hipStreamSynchronize(hd.c->stream));
-    const double t_run = wall_now();
-    int32_t nit = 0;
-    SGLCHK(sgl_ard_run(hd.c, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter,
-                       tol_out, score_overfit, n_trace, &nit, cb));
-    const double t_get = wall_now();
-    const int rc = sgl_get_factors(hd.c, w_out, d_out, h_out);
-    const double t_end = wall_now();
-    g_times.fit_init_s = t_run - t_fit;
-    g_times.iterate_s = t_get - t_run;
-    g_times.d2h_s = t_end - t_get;
-    g_times.total_s = t_end - t_call;
-    return hd.done(rc);
+    SGLCHK(sgl_mask_rank_check(k));
+    const ArdArgs a{seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter, tol_out, score_overfit, n_trace};
+    return one_shot_cached(Ax, Ai, Ap, Atx, Ati, Atp, nrow, ncol,
+                           {k, w_init, tol, maxit, L1, L1, L2, L2, &a, w_out, d_out, h_out, nullptr, nullptr, cb});
 }
 
 // c_ard_nmf_dense (src/singlet.cpp:1357-1361; dense predict_mask :506-533, mse_test :608-632): the CSC image through
@@ -1635,17 +1652,13 @@ extern "C" int sgl_c_ard_nmf_dense(const double* A, int32_t nrow, int32_t ncol, 
                                    double* score_overfit, int32_t* n_trace, const sgl_callbacks* cb) {
     (void)verbose; (void)threads;
     if (!A || !w_init || !w_out || !d_out || !h_out || nrow <= 0 || ncol <= 0) { sgl_set_error("sgl_c_ard_nmf_dense: bad arguments"); return SGL_EINVAL; }
-    if (k > SGL_MASK_MAX_K) { sgl_set_error("c_ard_nmf: rank %d above the masked path's limit of %d", k, SGL_MASK_MAX_K); return SGL_EINVAL; }
-    CtxHolder hd;
+    SGLCHK(sgl_mask_rank_check(k));
+    OneShotCtx hd;
     SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     SGLCHK(sgl_upload_dense(hd.c, A, nrow, ncol));
     sgl_dense_release(hd.c);   // the masked right-hand sides are not plain products: the CSC image serves this loop
-    SGLCHK(sgl_fit_init(hd.c, k, w_init, 0));
-    hd.c->solve_empty = true;
-    int32_t nit = 0;
-    SGLCHK(sgl_ard_run(hd.c, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter, tol_out,
-                       score_overfit, n_trace, &nit, cb));
-    return sgl_get_factors(hd.c, w_out, d_out, h_out);
+    const ArdArgs a{seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter, tol_out, score_overfit, n_trace};
+    return one_shot_fit(hd, {k, w_init, tol, maxit, L1, L1, L2, L2, &a, w_out, d_out, h_out, nullptr, nullptr, cb}, solve_every_column);
 }
 
 // c_nmf_sparse_list (src/singlet.cpp:715-743) and c_ard_nmf_sparse_list (:1162-1234)
@@ -1657,12 +1670,10 @@ extern "C" int sgl_c_nmf_sparse_list(int32_t n_chunks, const double* const* Ax, 
                                      double* tol_trace, const sgl_callbacks* cb) {
     (void)verbose; (void)threads;
     if (!w_init || !w_out || !d_out || !h_out) { sgl_set_error("sgl_c_nmf_sparse_list: NULL factor buffer"); return SGL_EINVAL; }
-    CtxHolder hd;
+    OneShotCtx hd;
     SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     SGLCHK(sgl_upload_csc_list(hd.c, n_chunks, Ax, Ai, Ap, chunk_ncol, n_t_chunks, Atx, Ati, Atp, t_chunk_ncol, nrow, 0, 0));
-    SGLCHK(sgl_fit_init(hd.c, k, w_init, 0));
-    SGLCHK(sgl_nmf_run(hd.c, tol, maxit, L1, L1, L2, L2, n_iter, tol_trace, cb));
-    return sgl_get_factors(hd.c, w_out, d_out, h_out);
+    return one_shot_fit(hd, {k, w_init, tol, maxit, L1, L1, L2, L2, nullptr, w_out, d_out, h_out, n_iter, tol_trace, cb});
 }
 
 extern "C" int sgl_c_ard_nmf_sparse_list(int32_t n_chunks, const double* const* Ax, const int32_t* const* Ai,
@@ -1675,15 +1686,12 @@ extern "C" int sgl_c_ard_nmf_sparse_list(int32_t n_chunks, const double* const* 
                                          double* score_overfit, int32_t* n_trace, const sgl_callbacks* cb) {
     (void)verbose; (void)threads;
     if (!w_init || !w_out || !d_out || !h_out) { sgl_set_error("sgl_c_ard_nmf_sparse_list: NULL factor buffer"); return SGL_EINVAL; }
-    if (k > SGL_MASK_MAX_K) { sgl_set_error("c_ard_nmf: rank %d above the masked path's limit of %d", k, SGL_MASK_MAX_K); return SGL_EINVAL; }
-    CtxHolder hd;
+    SGLCHK(sgl_mask_rank_check(k));
+    OneShotCtx hd;
     SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     SGLCHK(sgl_upload_csc_list(hd.c, n_chunks, Ax, Ai, Ap, chunk_ncol, n_t_chunks, Atx, Ati, Atp, t_chunk_ncol, nrow, 0, 0));
-    SGLCHK(sgl_fit_init(hd.c, k, w_init, 0));
-    int32_t nit = 0;
-    SGLCHK(sgl_ard_run(hd.c, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter, tol_out,
-                       score_overfit, n_trace, &nit, cb));
-    return sgl_get_factors(hd.c, w_out, d_out, h_out);
+    const ArdArgs a{seed, inv_density, overfit_threshold, trace_test_mse, test_mse, iter, tol_out, score_overfit, n_trace};
+    return one_shot_fit(hd, {k, w_init, tol, maxit, L1, L1, L2, L2, &a, w_out, d_out, h_out, nullptr, nullptr, cb});
 }
 
 // c_project_model (scale_w = true) and Rcpp_predict (scale_w = false) share everything but the scaling
@@ -1740,13 +1748,6 @@ extern "C" int sgl_rcpp_predict(const double* Ax, const int32_t* Ai, const int32
 }
 
 // ------------------------------------------------------------ operators -----
-// device buffer released on every return path
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() { if (p) (void)sgl_pool_free(p); }
-    int alloc(size_t n) { return dev_alloc(&p, n); }
-};
 // finish an operator: synchronise the stream, map a pending HIP error
 static int op_finish(sgl_ctx* c, int rc, const char* what) {
     const hipError_t e = hipStreamSynchronize(c->stream);
@@ -1947,7 +1948,7 @@ extern "C" int sgl_timing_get(sgl_ctx* c, double* ms, int64_t* calls, int reset)
 
 extern "C" int sgl_sweeps_get(sgl_ctx* c, int64_t* out4, int reset) {
     CTX_GUARD(c);
-    SGLCHK(sgl_fetch_sweeps(c));
+    SGLCHK(fetch_sweeps(c));
     for (int q = 0; q < 4; ++q) {
         if (out4) out4[q] = c->sweeps_acc[q];
         if (reset) c->sweeps_acc[q] = 0;

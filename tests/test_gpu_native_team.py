@@ -87,12 +87,16 @@ def test_rccl_team_of_one_matches_plain_run(sa, ora):
 
 
 def test_c_nmf_honours_singlet_ngpu(sa, ora, monkeypatch):
-    """SINGLET_NGPU above the device count is an error (no silent fallback); = 1 is the plain path."""
+    """SINGLET_NGPU above the device count is an error (no silent fallback); = 1 is the plain path.  The call times are
+    those of the LAST call whichever way it went: a refused multi-GPU call does not leave the previous call's split."""
     A = ora.synth_csc(50, 80, 5)
     w0 = ora.synth_winit(4, 50)
+    sa.c_nmf(to_dgc(sa, A), None, 0.0, 2, False, 0.01, 0.01, 0.0, 0.0, 0, w0.T)
+    assert sa.call_times()["total_s"] > 0 and sa.call_times()["iterate_s"] > 0
     monkeypatch.setenv("SINGLET_NGPU", "64")
     with pytest.raises(sa.SingletHipError):
         sa.c_nmf(to_dgc(sa, A), None, 0.0, 2, False, 0.01, 0.01, 0.0, 0.0, 0, w0.T)
+    assert sa.call_times()["total_s"] == 0 and sa.call_times()["iterate_s"] == 0
     monkeypatch.setenv("SINGLET_NGPU", "1")
     r = sa.c_nmf(to_dgc(sa, A), None, 0.0, 2, False, 0.01, 0.01, 0.0, 0.0, 0, w0.T)
     assert r["iter"] == 2
