@@ -429,10 +429,11 @@ SGL_API int sgl_set_links(sgl_ctx* ctx, const double* link_h, int32_t link_h_row
  * set, sgl_step_h convolves its right-hand sides over G and solves every cell,
  * and sgl_step_w accumulates over t(A) against H G and solves every gene (the
  * rules of sgl_c_gcnmf); the convolution's time counts in the rhs_h / rhs_w
- * phases.  Edges cross shards and the reference defines no such combination, so
- * a graph is refused (SGL_EINVAL) on a native team or with an all-reduce hook,
- * after a dense upload and next to link matrices, and the masked steps /
- * sgl_ard_run refuse while one is set. */
+ * phases.  Edges cross shards: the ranks of a one-process team take the graph
+ * of the whole matrix through sgl_multi_set_graph (section 2b) and exchange a
+ * halo; on a rank's own context, with an all-reduce hook, after a dense upload
+ * and next to link matrices a graph is refused (SGL_EINVAL), and the masked
+ * steps / sgl_ard_run refuse while one is set. */
 SGL_API int sgl_set_graph(sgl_ctx* ctx, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow,
                           int32_t G_ncol);
 
@@ -500,7 +501,7 @@ SGL_API int sgl_nmf_iterate(sgl_ctx* ctx, double L1_w, double L1_h, double L2_w,
  *     (they commute with scale(h, d), src/singlet.cpp:651) -- then every rank solves its block of
  *     genes and the blocks of w are all-gathered.  W, d and tol come out identical on all ranks.
  *     Results equal the one-GPU fit to rounding (the scaling is applied after the sums).
- *     Limits: c_nmf and c_ard_nmf (no links, no dense front-end), k as for one GPU.
+ *     Limits: c_nmf, c_linked_nmf, c_ard_nmf and (one-process team only) c_gcnmf; no dense front-end; k as for one GPU.
  *     RCCL is loaded at run time (librccl.so.1; SGL_RCCL_PATH overrides); SGL_ECOMM if absent.
  * ---------------------------------------------------------------------- */
 /* (a) ONE process drives all devices -- the form an R session uses.  sgl_c_nmf itself takes this
@@ -525,6 +526,29 @@ SGL_API int sgl_multi_fit_init(sgl_multi* m, int32_t k, const double* w_init, ui
  * the columns of link_h that belong to its cells.) */
 SGL_API int sgl_multi_set_links(sgl_multi* m, const double* link_h, int32_t link_h_rows, int32_t link_h_cols,
                                 const double* link_w, int32_t link_w_rows, int32_t link_w_cols);
+/* c_gcnmf on the team (src/singlet.cpp:1668-1730): the cell graph of the WHOLE matrix (arguments, checks and messages as
+ * sgl_set_graph; all-NULL slots clear it; sgl_multi_fit_init drops it).  Rank r keeps the columns of its own cells.  The
+ * rows of those columns that name another rank's cells are that rank's "exports"; E = the longest export list of the
+ * team.  Per iteration and side every rank packs its exported columns of the k x cells operand -- the right-hand sides B
+ * of the H-update (gcnmf_update_h, :1668-1690), the unscaled h of the W-update (gcnmf_update_w, :1693-1710; the row
+ * scaling commutes with the convolution) -- into its block of a slab of team size x E x k doubles, ONE in-place all-gather
+ * of k x E doubles per rank fills the other blocks (phase comm), and the convolution reads [own block of cells | slab].
+ * Sums keep the stored order of every column, so the fit equals the one-GPU sgl_c_gcnmf to the rounding of the team path.
+ * With E = 0 (no edge crosses a rank boundary) no halo step is issued.  Refused next to link matrices, after a dense
+ * upload and by sgl_multi_ard_run.  The process-per-GPU team (sgl_comm_init_rank) still refuses a graph: its ranks do
+ * not know each other's cell blocks. */
+SGL_API int sgl_multi_set_graph(sgl_multi* m, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow,
+                                int32_t G_ncol);
+/* out[0..4] = entries of G, entries whose row lives on another rank than their column, E, sum of the export list lengths,
+ * bytes one rank contributes to one halo all-gather (8 k E); all 0 without a graph. */
+SGL_API int sgl_multi_graph_info(sgl_multi* m, int64_t* out);
+/* The plan behind sgl_multi_set_graph, host only (no device is touched): for an n x n graph (row indices Gi, offsets Gp)
+ * and the n_ranks + 1 block boundaries cell_lo, export_ptr[0 .. n_ranks] / export_idx (room for n entries) receive every
+ * rank's export list (global cell indices, ascending), Gi_local (may be NULL; as long as Gi) the rewritten row indices --
+ * row - cell_lo[r] for a row of the column's own rank r, n_local_r + s * E + (position in rank s's export list) for a row
+ * owned by rank s -- and info[0..3] = entries, crossing entries, E, sum of the export list lengths. */
+SGL_API int sgl_graph_halo_plan(const int32_t* Gi, const int32_t* Gp, int32_t n, int n_ranks, const int64_t* cell_lo,
+                                int32_t* Gi_local, int64_t* export_ptr, int32_t* export_idx, int64_t* info);
 SGL_API int sgl_multi_iterate(sgl_multi* m, double L1_w, double L1_h, double L2_w, double L2_h, double* tol);
 SGL_API int sgl_multi_nmf_run(sgl_multi* m, double tol, int32_t maxit, double L1_w, double L1_h, double L2_w, double L2_h,
                               int32_t* n_iter, double* tol_trace, const sgl_callbacks* cb);

@@ -355,7 +355,30 @@ def run_nmf(A, rank, tol=1e-4, maxit=100, verbose=True, L1=0.01, L2=0, threads=0
     return _sort_model(model, A.Dimnames[0], A.Dimnames[1])
 
 
-def run_gcnmf(A, graph, k, split_by=None, tol=1e-5, L1=0.01, L2=0, verbose=2, maxit=100, threads=0, seed=None):
+def _gcnmf_on_team(A, G, tol, maxit, verbose, L1, L2, w, devices):
+    """c_gcnmf's list from a fit on a one-process team (Multi): cells sharded over `devices`, the graph's crossing edges
+    served by the halo exchange.  w as c_gcnmf takes it."""
+    from .context import Multi
+    A = as_dgCMatrix(A)
+    G = as_dgCMatrix(G)
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim != 2:
+        raise ValueError("w must be a matrix")
+    given = w.shape
+    if not (w.shape[0] == A.nrow and w.shape[0] != w.shape[1]):   # c_gcnmf's rule (l.1713): such a w is k x m; the team takes m x k
+        w = w.T
+    if w.shape[0] != A.nrow:
+        raise ValueError("w is %d x %d; expected k x m or m x k with m = %d" % (given[0], given[1], A.nrow))
+    with Multi([int(d) for d in devices]) as M:
+        M.upload(A)
+        M.fit_init(w.shape[1], w)
+        M.set_graph(G)
+        n_iter, tr = M.nmf_run(float(tol), int(maxit), float(L1), float(L1), float(L2), float(L2), log=_verbose_log(verbose))
+        W, d, H = M.get_factors()
+    return {"w": W, "d": d, "h": H.T, "iter": n_iter, "tol": tr}
+
+
+def run_gcnmf(A, graph, k, split_by=None, tol=1e-5, L1=0.01, L2=0, verbose=2, maxit=100, threads=0, seed=None, devices=None):
     """The numeric steps of RunGCNMF.Seurat (R/RunGCNMF.R:20-98) on a genes x cells matrix: PreprocessData when every value
     is integral (l.42-45), weight_by_split when `split_by` (0-based group per cell) is given (l.62-68), w_init uniform k x
     nrow(A) (l.73-75; `seed` replaces R's RNG state: an int or numpy Generator), c_gcnmf, factor names GCNMF_1..k (l.78).
@@ -365,7 +388,10 @@ def run_gcnmf(A, graph, k, split_by=None, tol=1e-5, L1=0.01, L2=0, verbose=2, ma
     Two places follow the evident intent rather than the R code, which cannot run as written:
       - l.77 passes `G`, a name defined nowhere in the function, to c_gcnmf; here the `graph` argument is passed;
       - when `k` is a matrix, `w_init` is never assigned (l.71-76); here that matrix is the initial w (k x m or m x k,
-        oriented by c_gcnmf's rule)."""
+        oriented by c_gcnmf's rule).
+
+    devices: None runs c_gcnmf on the current device; a list of device ids (all distinct, or all equal: ranks sharing one
+    device) runs the same fit cell-sharded on a Multi and returns the same dictionary."""
     A = as_dgCMatrix(A)
     rn, cn = A.Dimnames[0], A.Dimnames[1]
     v = A.x
@@ -383,7 +409,10 @@ def run_gcnmf(A, graph, k, split_by=None, tol=1e-5, L1=0.01, L2=0, verbose=2, ma
         w_init = k
     else:
         w_init = _rng(seed).random((A.nrow, int(k))).T   # matrix(runif(k * nrow(A)), k, nrow(A)), filled by column
-    model = c_gcnmf(A, At, graph, tol, maxit, bool(verbose), L1, L2, threads, w_init)
+    if devices is None:
+        model = c_gcnmf(A, At, graph, tol, maxit, bool(verbose), L1, L2, threads, w_init)
+    else:
+        model = _gcnmf_on_team(A, graph, tol, maxit, bool(verbose), L1, L2, w_init, devices)
     kk = model["d"].shape[0]
     model["factor_names"] = ["GCNMF_%d" % (q + 1) for q in range(kk)]
     model["rownames_w"] = rn

@@ -75,6 +75,29 @@ def split_cells_by_nnz(p, n):
     return lo
 
 
+def graph_halo_plan(p, i, cell_lo):
+    """The halo plan of Multi.set_graph (sgl_graph_halo_plan; host only, no device): for an n x n cell graph given by its
+    dgCMatrix slots p, i and the block boundaries cell_lo (ranks + 1 values from 0 to n) a dict with
+      "export":   per rank, the cells (global indices, ascending) that columns of other ranks read,
+      "i_local":  i with every row rewritten for its column's rank r: row - cell_lo[r] for a cell of r, n_local_r + s * E +
+                  (position in export[s]) for a cell of rank s,
+      "edges", "crossing" (entries whose row and column live on different ranks), "E" (longest export list)."""
+    p = np.ascontiguousarray(p, dtype=np.int32)
+    i = np.ascontiguousarray(i, dtype=np.int32)
+    lo = np.ascontiguousarray(cell_lo, dtype=np.int64)
+    n, nr = int(p.shape[0] - 1), int(lo.shape[0] - 1)
+    if n < 1 or nr < 1 or i.shape[0] < int(p[-1]):
+        raise ValueError("graph_halo_plan: p, i, cell_lo do not describe a graph and its blocks")
+    i_local = np.zeros(max(int(p[-1]), 1), dtype=np.int32)
+    eptr = np.zeros(nr + 1, dtype=np.int64)
+    eidx = np.zeros(n, dtype=np.int32)
+    info = np.zeros(4, dtype=np.int64)
+    check(_lib.load().sgl_graph_halo_plan(ptr(i, i32p), ptr(p, i32p), n, nr, ptr(lo, i64p), ptr(i_local, i32p), ptr(eptr, i64p),
+                                          ptr(eidx, i32p), ptr(info, i64p)))
+    return dict(export=[eidx[eptr[r]:eptr[r + 1]].copy() for r in range(nr)], i_local=i_local[:int(p[-1])],
+                edges=int(info[0]), crossing=int(info[1]), E=int(info[2]))
+
+
 def _chunk_list(chunks):
     """ctypes image of a list of dgCMatrix column chunks: (n, x**, i**, p**, ncol*) and what must stay alive.  A chunk
     that already is a dgCMatrix is not copied: a chunk listed twice passes the same host pointers twice."""
@@ -519,6 +542,24 @@ class Multi:
         lh, lhr, lhc, k1 = img(link_h)
         lw, lwr, lwc, k2 = img(link_w)
         check(self._L.sgl_multi_set_links(self._h, lh, lhr, lhc, lw, lwr, lwc))
+
+    def set_graph(self, G):
+        """c_gcnmf's cell graph for the team (sgl_multi_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over ALL
+        cells, or None to clear it.  Call after fit_init (which drops it).  Every rank keeps the columns of its cells; the
+        columns of B and h that other ranks read travel in a halo exchange per half-iteration (graph_info())."""
+        if G is None:
+            check(self._L.sgl_multi_set_graph(self._h, None, None, None, 0, 0))
+            return
+        G = as_dgCMatrix(G)
+        check(self._L.sgl_multi_set_graph(self._h, ptr(G.x, f64p), ptr(G.i, i32p), ptr(G.p, i32p), G.nrow, G.ncol))
+
+    def graph_info(self):
+        """dict(edges, crossing, E, exported, halo_bytes) of the graph set by set_graph (all 0 without one): entries of G,
+        entries whose row lives on another rank than their column, the longest export list, the sum of the export list
+        lengths, and the bytes one rank contributes to one halo all-gather (8 k E)."""
+        out = np.zeros(5, dtype=np.int64)
+        check(self._L.sgl_multi_graph_info(self._h, ptr(out, i64p)))
+        return dict(zip(("edges", "crossing", "E", "exported", "halo_bytes"), (int(v) for v in out)))
 
     def iterate(self, L1_w, L1_h, L2_w, L2_h):
         t = C.c_double()

@@ -15,6 +15,12 @@
 // SGL_GRAPH_SEG, one lane group each (same loop, into a partial slab), and a last kernel adds the partials of every hub
 // in segment order.  One long column thus costs its length / SGL_GRAPH_SEG groups of the second pass instead of
 // serialising a wave of the first.
+//
+// Team ranks (multi.hip, sgl_multi_set_graph): a rank holds the columns of its own cells, and the rows it reads from other
+// ranks' cells arrive in a halo slab.  Its row indices are rewritten on the host: below n_src a column of X, from n_src
+// on a column of the slab (n_src + s * E + e = entry e of rank s's export list).  graph_pack_kernel copies a rank's
+// exported columns into its block of the slab; the HALO instances of graph_conv_kernel choose the source per entry and
+// are otherwise the same loop (same lanes per column, four gathers in flight, sequential FMA from zero, hub segments).
 #include "sgl_internal.h"
 
 template <int VEC>
@@ -39,12 +45,19 @@ struct GVec<2> {
 
 // SEGS = false: item = output column j (hubs skipped), written to Y(:, j).
 // SEGS = true:  item = segment s of a hub column, its partial written to part + s * k.
-template <int VEC, int LPC, int NP, bool SEGS>
+// HALO = true: a row index r >= n_src names column r - n_src of `halo` instead of a column of X.
+template <int VEC, int LPC, int NP, bool SEGS, bool HALO>
 __global__ __launch_bounds__(256) void graph_conv_kernel(const double* __restrict__ X, double* __restrict__ Y,
                                                          const int64_t* __restrict__ Gp, const int32_t* __restrict__ Gi,
                                                          const double* __restrict__ Gx, int64_t nitems, int k,
                                                          const int32_t* __restrict__ seg_col,
-                                                         const int64_t* __restrict__ seg_q0) {
+                                                         const int64_t* __restrict__ seg_q0,
+                                                         const double* __restrict__ halo, int32_t n_src) {
+    // column r of the source: of X, or (HALO) of the slab past n_src
+    auto src = [&](int32_t r) -> const double* {
+        if (HALO && r >= n_src) return halo + (int64_t)(r - n_src) * k;
+        return X + (int64_t)r * k;
+    };
     const int gl = threadIdx.x & (LPC - 1);
     const int64_t group = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LPC;
     const int64_t ngroups = ((int64_t)gridDim.x * blockDim.x) / LPC;
@@ -74,10 +87,10 @@ __global__ __launch_bounds__(256) void graph_conv_kernel(const double* __restric
             for (int p = 0; p < NP; ++p) {
                 const int e = gl + LPC * p;
                 if (e < ne) {
-                    const GVec<VEC> x0 = GVec<VEC>::load(X + (int64_t)r0 * k + e * VEC);
-                    const GVec<VEC> x1 = GVec<VEC>::load(X + (int64_t)r1 * k + e * VEC);
-                    const GVec<VEC> x2 = GVec<VEC>::load(X + (int64_t)r2 * k + e * VEC);
-                    const GVec<VEC> x3 = GVec<VEC>::load(X + (int64_t)r3 * k + e * VEC);
+                    const GVec<VEC> x0 = GVec<VEC>::load(src(r0) + e * VEC);
+                    const GVec<VEC> x1 = GVec<VEC>::load(src(r1) + e * VEC);
+                    const GVec<VEC> x2 = GVec<VEC>::load(src(r2) + e * VEC);
+                    const GVec<VEC> x3 = GVec<VEC>::load(src(r3) + e * VEC);
                     acc[p].fma_into(v0, x0);
                     acc[p].fma_into(v1, x1);
                     acc[p].fma_into(v2, x2);
@@ -91,7 +104,7 @@ __global__ __launch_bounds__(256) void graph_conv_kernel(const double* __restric
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 const int e = gl + LPC * p;
-                if (e < ne) acc[p].fma_into(v0, GVec<VEC>::load(X + (int64_t)r0 * k + e * VEC));
+                if (e < ne) acc[p].fma_into(v0, GVec<VEC>::load(src(r0) + e * VEC));
             }
         }
 #pragma unroll
@@ -115,52 +128,90 @@ __global__ __launch_bounds__(256) void graph_hub_combine_kernel(const double* __
     Y[(int64_t)hub_col[h] * k + f] = s;
 }
 
-template <int VEC, int LPC, int NP, bool SEGS>
+template <int VEC, int LPC, int NP, bool SEGS, bool HALO>
 static int launch_conv(hipStream_t s, const DevGraph& g, const double* X, double* Y, int k, int64_t nitems) {
     if (nitems <= 0) return SGL_OK;
     const int64_t per_block = 256 / LPC;
     int64_t blocks = (nitems + per_block - 1) / per_block;
     if (blocks > (int64_t)1 << 20) blocks = (int64_t)1 << 20;   // grid-stride beyond (a million workgroups: 4096 per CU)
-    graph_conv_kernel<VEC, LPC, NP, SEGS><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(X, Y, g.p, g.i, g.x, nitems, k, g.seg_col,
-                                                                                      g.seg_q0);
+    graph_conv_kernel<VEC, LPC, NP, SEGS, HALO><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(X, Y, g.p, g.i, g.x, nitems, k, g.seg_col,
+                                                                                            g.seg_q0, g.halo, g.n_src);
     HIPCHK(hipGetLastError());
     return SGL_OK;
 }
 
-template <int VEC, bool SEGS>
+template <int VEC, bool SEGS, bool HALO>
 static int dispatch_lpc(hipStream_t s, const DevGraph& g, const double* X, double* Y, int k, int64_t nitems) {
     const int ne = k / VEC;
-    if (ne <= 1) return launch_conv<VEC, 1, 1, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 2) return launch_conv<VEC, 2, 1, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 4) return launch_conv<VEC, 4, 1, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 8) return launch_conv<VEC, 8, 1, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 16) return launch_conv<VEC, 16, 1, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 32) return launch_conv<VEC, 32, 1, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 64) return launch_conv<VEC, 64, 1, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 128) return launch_conv<VEC, 64, 2, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 256) return launch_conv<VEC, 64, 4, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 512) return launch_conv<VEC, 64, 8, SEGS>(s, g, X, Y, k, nitems);
-    if (ne <= 1024) return launch_conv<VEC, 64, 16, SEGS>(s, g, X, Y, k, nitems);
+    if (ne <= 1) return launch_conv<VEC, 1, 1, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 2) return launch_conv<VEC, 2, 1, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 4) return launch_conv<VEC, 4, 1, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 8) return launch_conv<VEC, 8, 1, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 16) return launch_conv<VEC, 16, 1, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 32) return launch_conv<VEC, 32, 1, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 64) return launch_conv<VEC, 64, 1, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 128) return launch_conv<VEC, 64, 2, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 256) return launch_conv<VEC, 64, 4, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 512) return launch_conv<VEC, 64, 8, SEGS, HALO>(s, g, X, Y, k, nitems);
+    if (ne <= 1024) return launch_conv<VEC, 64, 16, SEGS, HALO>(s, g, X, Y, k, nitems);
     sgl_set_error("graph convolution: k=%d too large", k);
     return SGL_EINVAL;
 }
 
-template <bool SEGS>
+template <bool SEGS, bool HALO>
 static int dispatch(hipStream_t s, const DevGraph& g, const double* X, double* Y, int k, int64_t nitems) {
     // 16-byte loads need every column start 16-byte aligned: k even (the buffers themselves are 256-byte aligned)
-    return (k % 2 == 0) ? dispatch_lpc<2, SEGS>(s, g, X, Y, k, nitems) : dispatch_lpc<1, SEGS>(s, g, X, Y, k, nitems);
+    return (k % 2 == 0) ? dispatch_lpc<2, SEGS, HALO>(s, g, X, Y, k, nitems) : dispatch_lpc<1, SEGS, HALO>(s, g, X, Y, k, nitems);
 }
 
 int k_graph_conv(hipStream_t s, DevGraph& g, const double* X, double* Y, int k) {
     if (g.n <= 0) return SGL_OK;
     if (k <= 0 || k > SGL_MAX_K) { sgl_set_error("graph convolution: k=%d out of range", k); return SGL_EINVAL; }
-    SGLCHK(dispatch<false>(s, g, X, Y, k, g.n));
+    // a team rank whose team exchanges a halo (E > 0) reads [X | slab]; every other graph keeps the plain instances
+    const bool halo = g.E > 0;
+    if (halo && !g.halo) { sgl_set_error("graph convolution: the halo slab is missing"); return SGL_ESTATE; }
+    SGLCHK((halo ? dispatch<false, true>(s, g, X, Y, k, g.n) : dispatch<false, false>(s, g, X, Y, k, g.n)));
     if (g.nhub > 0) {
-        SGLCHK(dispatch<true>(s, g, X, g.part, k, g.nseg));
+        SGLCHK((halo ? dispatch<true, true>(s, g, X, g.part, k, g.nseg) : dispatch<true, false>(s, g, X, g.part, k, g.nseg)));
         const int64_t threads = (int64_t)g.nhub * k;
         graph_hub_combine_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s>>>(g.part, Y, g.hub_col, g.hub_seg0,
                                                                                                g.nhub, k);
         HIPCHK(hipGetLastError());
     }
+    return SGL_OK;
+}
+
+// slab block of this rank: column e = X(:, exp[e]).  One group of `lpc` lanes (a power of two, the convolution's lanes per
+// column) per exported column, each lane VEC consecutive factor rows per pass.
+template <int VEC>
+__global__ __launch_bounds__(256) void graph_pack_kernel(const double* __restrict__ X, double* __restrict__ block,
+                                                         const int32_t* __restrict__ exp, int64_t n_exp, int k, int lpc) {
+    const int gl = threadIdx.x & (lpc - 1);
+    const int64_t group = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / lpc;
+    const int64_t ngroups = ((int64_t)gridDim.x * blockDim.x) / lpc;
+    const int ne = k / VEC;
+    for (int64_t item = group; item < n_exp; item += ngroups) {
+        const double* from = X + (int64_t)exp[item] * k;
+        double* to = block + item * k;
+        for (int e = gl; e < ne; e += lpc) GVec<VEC>::load(from + e * VEC).store(to + e * VEC);
+    }
+}
+
+// rank `rank` of a team packs the columns of X its peers read (g.exp) into block `rank` of its halo slab
+int k_graph_pack(hipStream_t s, DevGraph& g, const double* X, int k, int rank) {
+    if (g.E <= 0 || g.n_exp <= 0) return SGL_OK;
+    if (k <= 0 || k > SGL_MAX_K) { sgl_set_error("graph pack: k=%d out of range", k); return SGL_EINVAL; }
+    if (!g.halo || !g.exp || g.n_exp > g.E || rank < 0) { sgl_set_error("graph pack: no halo slab or export list"); return SGL_ESTATE; }
+    const int vec = (k % 2 == 0) ? 2 : 1;
+    const int ne = k / vec;
+    int lpc = 1;
+    while (lpc < ne && lpc < 64) lpc *= 2;
+    const int64_t per_block = 256 / lpc;
+    int64_t blocks = (g.n_exp + per_block - 1) / per_block;
+    if (blocks > (int64_t)1 << 20) blocks = (int64_t)1 << 20;
+    double* block = g.halo + (size_t)rank * g.E * k;   // (k even: rank * E * k is even, the 16-byte stores stay aligned)
+    if (vec == 2) graph_pack_kernel<2><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(X, block, g.exp, g.n_exp, k, lpc);
+    else graph_pack_kernel<1><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(X, block, g.exp, g.n_exp, k, lpc);
+    HIPCHK(hipGetLastError());
     return SGL_OK;
 }

@@ -16,6 +16,10 @@
 //                and the m solves are dealt out instead of replicated)
 //   every rank   scale(w, d); tol = cor(w, w_prev)                      replicated, bit-identical   :655-659
 //
+// With a cell graph (c_gcnmf, sgl_multi_set_graph) the two convolutions of an iteration read columns of other ranks' cells:
+// each is preceded by a halo step -- pack the columns the peers name, all-gather k x E doubles per rank in place --
+// see "c_gcnmf on the team" below.
+//
 // Two ways to form a team:
 //   * sgl_multi_create: ONE process drives all devices (the R host: no launcher), communicators from
 //     ncclCommInitAll, collectives issued for all ranks inside ncclGroupStart / ncclGroupEnd;
@@ -156,6 +160,11 @@ struct sgl_team {
     int32_t nrow = 0;
     int64_t ncells_total = 0;
     std::vector<int64_t> cell_lo;  // single-process form: cell block boundaries (nranks + 1)
+    // c_gcnmf on the team (sgl_multi_set_graph): {entries, crossing entries, E, sum of the export lists, halo bytes per
+    // exchange and rank}; graph_E = E, the longest export list -- every rank decides on the halo steps from it
+    int64_t graph_info[5] = {0, 0, 0, 0, 0};
+    int64_t graph_E = 0;
+    bool has_graph = false;
 };
 struct sgl_multi : sgl_team {};
 
@@ -578,7 +587,7 @@ struct Stage {
     bool exchange;
     std::function<int(int)> fn;
 };
-static int team_stages(sgl_team* T, std::initializer_list<Stage> stages) {
+static int team_stages(sgl_team* T, const std::vector<Stage>& stages) {
     const int nl = (int)T->local.size();
     auto on_rank = [&](const Stage& s, int i) -> int {
         if (!s.exchange) HIPCHK(hipSetDevice(T->local[i]->device));
@@ -661,21 +670,67 @@ static int team_iterate(sgl_team* T, double L1_w, double L1_h, double L2_w, doub
     const int64_t mpad = mb * N;
     std::vector<void*> red(nl), tail(nl), wbuf(nl);
     std::vector<double> tols(nl, 0.0);
-    auto local_part = [&](int i) -> int {   // h = predict(A_r, w); partials of the unscaled h
+    // c_gcnmf (sgl_multi_set_graph): with E > 0 the convolutions read other ranks' columns, which travel in a halo slab
+    const bool graph = T->has_graph;
+    const int64_t E = graph ? T->graph_E : 0;
+    std::vector<void*> slab(nl);
+    for (int i = 0; i < nl; ++i) {
         sgl_ctx* c = T->local[i];
-        SGLCHK(sgl_step_begin(c));
-        SGLCHK(sgl_step_h(c, L1_h, L2_h));
+        if ((c->graph.n != 0) != graph || (graph && c->graph.E != E)) { sgl_set_error("team: the ranks disagree on the cell graph"); return SGL_ESTATE; }
+        slab[i] = c->graph.halo;
+    }
+    auto partials = [&](sgl_ctx* c, const double* F) -> int {   // of the unscaled h; F = h, or h G with a graph
         double* Bw = c->red;
         double* Gh = c->red + (size_t)k * mpad;
         double* sh = Gh + (size_t)k * k;
         { Phase ph(c, SGL_PH_SCALE); SGLCHK(k_rowsum(c, c->H, k, c->A.ncol, sh)); }
         { Phase ph(c, SGL_PH_RHS_W);
-          if (c->use_tiled && c->TAt.roff) SGLCHK(k_acc_tiled_all(c->stream, c->TAt, c->H, Bw, k));
-          else SGLCHK(k_acc(c->stream, c->At, c->H, k, Bw, 0, 1, 0, 0, 0)); }
+          if (c->use_tiled && c->TAt.roff) SGLCHK(k_acc_tiled_all(c->stream, c->TAt, F, Bw, k));
+          else SGLCHK(k_acc(c->stream, c->At, F, k, Bw, 0, 1, 0, 0, 0)); }
         { Phase ph(c, SGL_PH_GRAM); SGLCHK(k_gram(c, c->H, k, c->A.ncol, Gh, 0.0)); }
-        red[i] = Bw;
-        tail[i] = Gh;
+        return SGL_OK;
+    };
+    auto book = [&](int i) {
+        sgl_ctx* c = T->local[i];
+        red[i] = c->red;
+        tail[i] = c->red + (size_t)k * mpad;
         wbuf[i] = c->W;
+    };
+    auto local_part = [&](int i) -> int {   // h = predict(A_r, w); partials of the unscaled h
+        sgl_ctx* c = T->local[i];
+        SGLCHK(sgl_step_begin(c));
+        SGLCHK(sgl_step_h_rhs(c, true));
+        SGLCHK(sgl_step_h_solve(c, L1_h, L2_h, false));
+        const double* F = c->H;
+        if (graph) {   // no edge leaves a rank: gcnmf_update_w's h G (src/singlet.cpp:1703-1706) is local
+            Phase ph(c, SGL_PH_RHS_W);
+            SGLCHK(k_graph_conv(c->stream, c->graph, c->H, c->B, k));
+            F = c->B;
+        }
+        SGLCHK(partials(c, F));
+        book(i);
+        return SGL_OK;
+    };
+    // the same with a halo: B = w A_r | pack, all-gather | Bc = [B | slab] G_r, solve h | pack, all-gather | (h G)_r, partials
+    auto halo_rhs = [&](int i) -> int {
+        sgl_ctx* c = T->local[i];
+        SGLCHK(sgl_step_begin(c));
+        SGLCHK(sgl_step_h_rhs(c, false));
+        Phase ph(c, SGL_PH_RHS_H);
+        return k_graph_pack(c->stream, c->graph, c->B, k, T->rank[i]);
+    };
+    auto halo_exchange = [&](int who) -> int { return team_exchange(T, who, {{2, &slab, (int64_t)k * E, false}}); };
+    auto halo_solve = [&](int i) -> int {
+        sgl_ctx* c = T->local[i];
+        SGLCHK(sgl_step_h_solve(c, L1_h, L2_h, true));
+        Phase ph(c, SGL_PH_RHS_W);
+        return k_graph_pack(c->stream, c->graph, c->H, k, T->rank[i]);
+    };
+    auto halo_partials = [&](int i) -> int {
+        sgl_ctx* c = T->local[i];
+        { Phase ph(c, SGL_PH_RHS_W); SGLCHK(k_graph_conv(c->stream, c->graph, c->H, c->B, k)); }
+        SGLCHK(partials(c, c->B));
+        book(i);
         return SGL_OK;
     };
     // exchange 1: one grouped collective
@@ -704,7 +759,8 @@ static int team_iterate(sgl_team* T, double L1_w, double L1_h, double L2_w, doub
             const int64_t* gene_nnz = (N > 1) ? c->col_nnz_At_global : c->col_nnz_At;
             if (N > 1 && !c->gene_nnz_global) { sgl_set_error("team: global gene counts missing"); return SGL_ESTATE; }
             // (the dense front-end solves every column, src/singlet.cpp:370-381: no skip list)
-            SGLCHK(sgl_nnls_shared(c, c->G, Bblk, c->W + (size_t)g0 * k, c->solve_empty ? nullptr : gene_nnz + g0, ng, L1_w, L2_w, c->sweep_counters + 1));
+            // (with a graph every gene is solved too, as sgl_step_w does: gcnmf_update_w has no skip, src/singlet.cpp:1707)
+            SGLCHK(sgl_nnls_shared(c, c->G, Bblk, c->W + (size_t)g0 * k, (c->solve_empty || graph) ? nullptr : gene_nnz + g0, ng, L1_w, L2_w, c->sweep_counters + 1));
         }
         return SGL_OK;
     };
@@ -714,7 +770,11 @@ static int team_iterate(sgl_team* T, double L1_w, double L1_h, double L2_w, doub
     };
     auto tail_part = [&](int i) -> int { return sgl_scale_w_enqueue(T->local[i]); };
     auto fetch = [&](int i) -> int { return sgl_scale_w_fetch(T->local[i], &tols[i]); };
-    SGLCHK(team_stages(T, {{false, local_part}, {true, exchange1}, {false, gene_block}, {true, exchange2}, {false, tail_part}, {false, fetch}}));
+    std::vector<Stage> stages;
+    if (E > 0) stages = {{false, halo_rhs}, {true, halo_exchange}, {false, halo_solve}, {true, halo_exchange}, {false, halo_partials}};
+    else stages = {{false, local_part}};
+    stages.insert(stages.end(), {{true, exchange1}, {false, gene_block}, {true, exchange2}, {false, tail_part}, {false, fetch}});
+    SGLCHK(team_stages(T, stages));
     SGLCHK(team_tols_agree(tols));
     if (tol_out) *tol_out = tols[0];   // w is replicated bit for bit: every rank computes the same value
     return SGL_OK;
@@ -876,6 +936,7 @@ static int team_ard_run(sgl_team* T, double tol, int32_t maxit, double L1, doubl
     SGLCHK(sgl_ard_args_check(a, "ard_run"));
     for (auto c : T->local) {
         if (c->k == 0) { sgl_set_error("team: no fit initialised"); return SGL_ESTATE; }
+        if (c->graph.n) { sgl_set_error("sgl_multi_ard_run: a cell graph is set (graph-convolutional NMF has no masked variant)"); return SGL_EINVAL; }
         SGLCHK(sgl_mask_rank_check(c->k));
     }
     if (T->nranks > 1) {
@@ -1065,11 +1126,18 @@ extern "C" int sgl_split_cells_by_nnz(const int32_t* p, int32_t ncol, int n, int
     return SGL_OK;
 }
 
+static void team_graph_forget(sgl_team* T) {
+    T->has_graph = false;
+    T->graph_E = 0;
+    for (auto& v : T->graph_info) v = 0;
+}
+
 extern "C" int sgl_multi_upload_csc(sgl_multi* M, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol) {
     TEAM_GUARD(M);
     if (!Ax || !Ai || !Ap || nrow <= 0 || ncol <= 0) { sgl_set_error("sgl_multi_upload_csc: missing slot or empty matrix"); return SGL_EINVAL; }
     const int n = M->nranks;
     if (ncol < n) { sgl_set_error("sgl_multi_upload_csc: fewer cells (%d) than devices (%d)", ncol, n); return SGL_EINVAL; }
+    team_graph_forget(M);
     M->cell_lo.assign(n + 1, 0);
     SGLCHK(sgl_split_cells_by_nnz(Ap, ncol, n, M->cell_lo.data()));
     M->nrow = nrow;
@@ -1090,6 +1158,7 @@ extern "C" int sgl_multi_synth_csc(sgl_multi* M, uint64_t S, uint64_t inv_densit
     TEAM_GUARD(M);
     const int n = M->nranks;
     if (ncells_total < n) { sgl_set_error("sgl_multi_synth_csc: fewer cells than devices"); return SGL_EINVAL; }
+    team_graph_forget(M);
     M->cell_lo.assign(n + 1, 0);
     const int64_t base = ncells_total / n, rem = ncells_total % n;
     for (int r = 0; r < n; ++r) M->cell_lo[r + 1] = M->cell_lo[r] + base + (r < rem ? 1 : 0);
@@ -1103,6 +1172,7 @@ extern "C" int sgl_multi_synth_csc(sgl_multi* M, uint64_t S, uint64_t inv_densit
 extern "C" int sgl_multi_fit_init(sgl_multi* M, int32_t k, const double* w_init, uint64_t synth_seed) {
     TEAM_GUARD(M);
     if (M->cell_lo.empty()) { sgl_set_error("sgl_multi_fit_init: no matrix resident"); return SGL_ESTATE; }
+    team_graph_forget(M);   // sgl_fit_init drops every rank's graph
     SGLCHK(team_parallel(M, [&](int r) -> int { return sgl_fit_init(M->local[r], k, w_init, synth_seed); }));
     for (auto c : M->local) c->gene_nnz_global = false;
     return team_gene_counts(M);
@@ -1121,6 +1191,126 @@ extern "C" int sgl_multi_set_links(sgl_multi* M, const double* link_h, int32_t l
         SGLCHK(sgl_set_links(M->local[r], use_h ? link_h + (size_t)lo * link_h_rows : nullptr, link_h_rows, use_h ? (int32_t)nloc : 0, link_w,
                              link_w_rows, link_w_cols));
     }
+    return SGL_OK;
+}
+
+// ------------------------------------------------------- c_gcnmf on the team --
+// The halo plan (header, section 2b): which cells every rank exports and the row indices of every rank's columns in terms
+// of [own cells | slab].  Pure host code.
+extern "C" int sgl_graph_halo_plan(const int32_t* Gi, const int32_t* Gp, int32_t n, int n_ranks, const int64_t* cell_lo,
+                                   int32_t* Gi_local, int64_t* export_ptr, int32_t* export_idx, int64_t* info) {
+    if (!Gi || !Gp || !cell_lo || !export_ptr || !export_idx || n < 1 || n_ranks < 1 || n_ranks > SGL_TEAM_MAX) {
+        sgl_set_error("sgl_graph_halo_plan: bad arguments");
+        return SGL_EINVAL;
+    }
+    if (cell_lo[0] != 0 || cell_lo[n_ranks] != n) { sgl_set_error("sgl_graph_halo_plan: cell_lo must run from 0 to n"); return SGL_EINVAL; }
+    for (int r = 0; r < n_ranks; ++r)
+        if (cell_lo[r + 1] <= cell_lo[r]) { sgl_set_error("sgl_graph_halo_plan: the cell block of rank %d is empty", r); return SGL_EINVAL; }
+    if (Gp[0] != 0) { sgl_set_error("sgl_graph_halo_plan: not a valid dgCMatrix: p[0] = %d", Gp[0]); return SGL_EINVAL; }
+    // a row is exported when a column of another rank names it
+    std::vector<int32_t> pos((size_t)n, -1);   // -1: not exported; then its position in its owner's export list
+    int64_t crossing = 0;
+    for (int r = 0; r < n_ranks; ++r)
+        for (int64_t j = cell_lo[r]; j < cell_lo[r + 1]; ++j) {
+            if (Gp[j + 1] < Gp[j]) { sgl_set_error("sgl_graph_halo_plan: not a valid dgCMatrix: p decreases at column %lld", (long long)j); return SGL_EINVAL; }
+            for (int64_t q = Gp[j]; q < Gp[j + 1]; ++q) {
+                const int32_t g = Gi[q];
+                if (g < 0 || g >= n) { sgl_set_error("sgl_graph_halo_plan: row index %d outside [0, %d) in column %lld", g, n, (long long)j); return SGL_EINVAL; }
+                if (g < cell_lo[r] || g >= cell_lo[r + 1]) { pos[(size_t)g] = 0; ++crossing; }
+            }
+        }
+    int64_t E = 0, total = 0;
+    export_ptr[0] = 0;
+    for (int s = 0; s < n_ranks; ++s) {
+        int32_t cnt = 0;
+        for (int64_t g = cell_lo[s]; g < cell_lo[s + 1]; ++g)
+            if (pos[(size_t)g] == 0) { pos[(size_t)g] = cnt++; export_idx[total++] = (int32_t)g; }
+        export_ptr[s + 1] = total;
+        E = std::max<int64_t>(E, cnt);
+    }
+    if (Gi_local) {
+        for (int r = 0; r < n_ranks; ++r) {
+            const int64_t lo = cell_lo[r], hi = cell_lo[r + 1], n_local = hi - lo;
+            if (n_local + (int64_t)n_ranks * E > INT32_MAX) { sgl_set_error("sgl_graph_halo_plan: halo indices of rank %d leave the 32-bit range", r); return SGL_EINVAL; }
+            for (int64_t q = Gp[lo]; q < Gp[hi]; ++q) {
+                const int32_t g = Gi[q];
+                if (g >= lo && g < hi) { Gi_local[q] = (int32_t)(g - lo); continue; }
+                const int s = (int)(std::upper_bound(cell_lo, cell_lo + n_ranks + 1, (int64_t)g) - cell_lo) - 1;   // the owner
+                Gi_local[q] = (int32_t)(n_local + (int64_t)s * E + pos[(size_t)g]);
+            }
+        }
+    }
+    if (info) { info[0] = Gp[n]; info[1] = crossing; info[2] = E; info[3] = total; }
+    return SGL_OK;
+}
+
+extern "C" int sgl_multi_set_graph(sgl_multi* M, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol) {
+    TEAM_GUARD(M);
+    if (M->cell_lo.empty()) { sgl_set_error("sgl_multi_set_graph: no matrix resident"); return SGL_ESTATE; }
+    const int N = M->nranks;
+    for (auto c : M->local) {
+        if (c->k == 0) { sgl_set_error("sgl_multi_set_graph: no fit initialised (call sgl_multi_fit_init)"); return SGL_ESTATE; }
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        sgl_graph_clear(c);
+    }
+    team_graph_forget(M);
+    if (!Gx && !Gi && !Gp) return SGL_OK;   // NULL clears it
+    if (!Gx || !Gi || !Gp) { sgl_set_error("sgl_multi_set_graph: G must be fully given or fully NULL"); return SGL_EINVAL; }
+    for (auto c : M->local) {
+        if (c->dense_input) { sgl_set_error("sgl_multi_set_graph: the matrix was uploaded dense (c_gcnmf takes a dgCMatrix)"); return SGL_EINVAL; }
+        if (c->link_h || c->link_w) { sgl_set_error("sgl_multi_set_graph: link matrices are set (the reference has no linked graph-convolutional NMF)"); return SGL_EINVAL; }
+    }
+    const int64_t n = M->ncells_total;
+    SGLCHK(sgl_graph_check("sgl_multi_set_graph", Gx, Gi, Gp, G_nrow, G_ncol, n));
+    std::vector<int32_t> gi_local((size_t)std::max<int64_t>(Gp[n], 1)), exp_idx((size_t)n);
+    std::vector<int64_t> exp_ptr((size_t)N + 1);
+    int64_t info[4] = {0, 0, 0, 0};
+    SGLCHK(sgl_graph_halo_plan(Gi, Gp, (int32_t)n, N, M->cell_lo.data(), gi_local.data(), exp_ptr.data(), exp_idx.data(), info));
+    const int64_t E = info[2];
+    int rc = SGL_OK;
+    for (int r = 0; r < N && rc == SGL_OK; ++r) {
+        sgl_ctx* c = M->local[r];
+        const int64_t lo = M->cell_lo[r], n_local = M->cell_lo[r + 1] - lo;
+        if (hipSetDevice(c->device) != hipSuccess) { sgl_set_error("sgl_multi_set_graph: hipSetDevice failed"); rc = SGL_EHIP; break; }
+        rc = sgl_graph_upload(c, "sgl_multi_set_graph", Gx, gi_local.data(), Gp + lo, (int32_t)n_local);
+        if (rc != SGL_OK || E == 0) continue;
+        DevGraph& g = c->graph;
+        const int64_t n_exp = exp_ptr[(size_t)r + 1] - exp_ptr[(size_t)r];
+        std::vector<int32_t> local_exp((size_t)n_exp);
+        for (int64_t e = 0; e < n_exp; ++e) local_exp[(size_t)e] = (int32_t)(exp_idx[(size_t)(exp_ptr[(size_t)r] + e)] - lo);
+        rc = dev_alloc(&g.exp, (size_t)n_exp);
+        if (rc == SGL_OK) {
+            rc = dev_alloc(&g.halo, (size_t)N * (size_t)E * (size_t)c->k);
+            if (rc != SGL_OK)
+                sgl_set_error("sgl_multi_set_graph: no device memory for the halo slab of rank %d (%d ranks x %lld exported cells x k = %d doubles, %.1f MB)",
+                              r, N, (long long)E, c->k, 8e-6 * (double)N * (double)E * c->k);
+        }
+        if (rc == SGL_OK) {
+            hipError_t e = hipSuccess;
+            if (n_exp > 0) e = hipMemcpyAsync(g.exp, local_exp.data(), sizeof(int32_t) * (size_t)n_exp, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(g.halo, 0, sizeof(double) * (size_t)N * (size_t)E * (size_t)c->k, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // local_exp leaves scope
+            if (e != hipSuccess) { (void)hipGetLastError(); sgl_set_error("sgl_multi_set_graph: %s", hipGetErrorString(e)); rc = SGL_EHIP; }
+        }
+        g.n_exp = (int32_t)n_exp;
+        g.E = (int32_t)E;
+    }
+    if (rc != SGL_OK) {   // all ranks or none
+        for (auto c : M->local) { (void)hipSetDevice(c->device); sgl_graph_clear(c); }
+        return rc;
+    }
+    M->has_graph = true;
+    M->graph_E = E;
+    for (int q = 0; q < 4; ++q) M->graph_info[q] = info[q];
+    M->graph_info[4] = 8 * (int64_t)M->local[0]->k * E;
+    return SGL_OK;
+}
+
+extern "C" int sgl_multi_graph_info(sgl_multi* M, int64_t* out) {
+    TEAM_GUARD(M);
+    if (!out) { sgl_set_error("sgl_multi_graph_info: out is NULL"); return SGL_EINVAL; }
+    for (int q = 0; q < 5; ++q) out[q] = M->has_graph ? M->graph_info[q] : 0;
     return SGL_OK;
 }
 

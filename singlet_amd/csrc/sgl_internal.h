@@ -175,6 +175,13 @@ struct DevGraph {
     double* part = nullptr;     // [nseg * k] partial sums of the segments
     int32_t nseg = 0, nhub = 0;
     double* buf = nullptr;      // k x n (+ 2): the convolved right-hand sides of the H-update
+    // rank of a team (sgl_multi_set_graph): n = the rank's own cells; a row index below n_src names a column of the rank's
+    // factor block, n_src + s * E + e names entry e of rank s's export list, held in the halo slab
+    int32_t n_src = 0;
+    int32_t E = 0;              // longest export list of the team (0: no edge crosses a rank boundary, no halo step)
+    int32_t n_exp = 0;          // this rank's export list: its cells that other ranks read, ascending (local indices)
+    int32_t* exp = nullptr;
+    double* halo = nullptr;     // [team size * E * k] block s = the exported columns of rank s (all-gathered in place)
 };
 
 struct sgl_ctx {
@@ -243,6 +250,15 @@ int sgl_team_size(const sgl_ctx* c);   // 1 without a team
 // internals of singlet_hip.hip used by multi.hip
 int sgl_nnls_shared(sgl_ctx* c, const double* G, double* B, double* X, const int64_t* col_nnz, int64_t ncols,
                     double L1, double L2, unsigned long long* counter, bool h_side = false);
+// the two halves of sgl_step_h: Gram of w and right-hand sides B (convolved over the graph into graph.buf when
+// `convolve`), then the solve (which convolves first when `convolve`): a team puts its halo exchange between them
+int sgl_step_h_rhs(sgl_ctx* c, bool convolve);
+int sgl_step_h_solve(sgl_ctx* c, double L1, double L2, bool convolve);
+// cell graph of a context (singlet_hip.hip): checks of sgl_set_graph (messages start with `who`), upload of the columns
+// [0, ncol) described by Gp[0 .. ncol] (entries Gx / Gi [Gp[0], Gp[ncol])), release
+int sgl_graph_check(const char* who, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol, int64_t n);
+int sgl_graph_upload(sgl_ctx* c, const char* who, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t ncol);
+void sgl_graph_clear(sgl_ctx* c);
 int sgl_scale_w_enqueue(sgl_ctx* c);            // scale(w, d); cor(w, w_prev) -> device scalar
 int sgl_scale_w_fetch(sgl_ctx* c, double* tol); // copy it out (synchronises the stream)
 // masked path pieces (singlet_hip.hip) used by the team's sharded c_ard_nmf (multi.hip)
@@ -397,6 +413,7 @@ int sgl_upload_A_structure(sgl_ctx* c, const double* Ax, const int32_t* Ai, cons
 
 // graph convolution (kernels_graph.hip): Y = X G, X and Y k x n column-major (Y must not alias X)
 int k_graph_conv(hipStream_t s, DevGraph& g, const double* X, double* Y, int k);
+int k_graph_pack(hipStream_t s, DevGraph& g, const double* X, int k, int rank);   // X(:, g.exp) -> block `rank` of g.halo
 
 // NNLS
 #define SGL_NNLS_MAX_PASSES 10

@@ -149,8 +149,11 @@ static void free_graph(sgl_ctx* c) {
     dev_free(g.hub_seg0);
     dev_free(g.part);
     dev_free(g.buf);
+    dev_free(g.exp);
+    dev_free(g.halo);
     g = DevGraph();
 }
+void sgl_graph_clear(sgl_ctx* c) { free_graph(c); }
 
 // keep_streams: the entry streams (and their buffers) survive a re-init of the fit on the SAME matrix -- every
 // path that changes the matrix calls free_fit(c) without it
@@ -884,9 +887,8 @@ extern "C" int sgl_step_begin(sgl_ctx* c) {
     return SGL_OK;
 }
 
-// predict(A, w, h, L1, L2): src/singlet.cpp:333-347
-extern "C" int sgl_step_h(sgl_ctx* c, double L1, double L2) {
-    FIT_GUARD(c);
+// predict(A, w, h, L1, L2): src/singlet.cpp:333-347, in two halves (a team exchanges the halo of B between them)
+int sgl_step_h_rhs(sgl_ctx* c, bool convolve) {
     const int k = c->k;
     { Phase ph(c, SGL_PH_GRAM); SGLCHK(k_gram(c, c->W, k, c->A.nrow, c->G, 1e-15)); }
     { Phase ph(c, SGL_PH_RHS_H);
@@ -894,12 +896,24 @@ extern "C" int sgl_step_h(sgl_ctx* c, double L1, double L2) {
       else if (c->use_tiled) SGLCHK(k_acc_tiled_all(c->stream, c->TA, c->W, c->B, k));
       else SGLCHK(k_acc(c->stream, c->A, c->W, k, c->B, 0, 1, 0, 0, 0));
       if (c->link_h) SGLCHK(k_link_mul(c->stream, c->B, c->link_h, k, c->link_h_rows, c->A.ncol));  // predict_link l.429-430
-      if (c->graph.n) SGLCHK(k_graph_conv(c->stream, c->graph, c->B, c->graph.buf, k)); }  // gcnmf_update_h l.1684-1688: Bc = B G
+      if (c->graph.n && convolve) SGLCHK(k_graph_conv(c->stream, c->graph, c->B, c->graph.buf, k)); }  // gcnmf_update_h l.1684-1688: Bc = B G
+    return SGL_OK;
+}
+
+int sgl_step_h_solve(sgl_ctx* c, double L1, double L2, bool convolve) {
+    const int k = c->k;
+    if (c->graph.n && convolve) { Phase ph(c, SGL_PH_RHS_H); SGLCHK(k_graph_conv(c->stream, c->graph, c->B, c->graph.buf, k)); }
     { Phase ph(c, SGL_PH_NNLS_H);
       // with a graph EVERY column is solved (l.1689), from the convolved right-hand sides
       if (c->graph.n) SGLCHK(sgl_nnls_shared(c, c->G, c->graph.buf, c->H, nullptr, c->A.ncol, L1, L2, c->sweep_counters + 0, true));
       else SGLCHK(sgl_nnls_shared(c, c->G, c->B, c->H, c->solve_empty ? nullptr : c->col_nnz_A, c->A.ncol, L1, L2, c->sweep_counters + 0, true)); }
     return SGL_OK;
+}
+
+extern "C" int sgl_step_h(sgl_ctx* c, double L1, double L2) {
+    FIT_GUARD(c);
+    SGLCHK(sgl_step_h_rhs(c, true));
+    return sgl_step_h_solve(c, L1, L2, false);
 }
 
 // scale(h, d): src/singlet.cpp:219-225; row sums are global over all shards
@@ -1496,35 +1510,34 @@ extern "C" int sgl_c_linked_nmf(const double* Ax, const int32_t* Ai, const int32
 // c_gcnmf's cell graph G (src/singlet.cpp:1668-1730): n x n, n = the cells of the resident matrix, as a dgCMatrix.  Checked
 // on the host (the kernels index factor columns by its rows): p[0] = 0 and monotone, rows strictly ascending within a column
 // and in [0, n), values finite.  Columns above SGL_GRAPH_HUB entries get their segment lists here (kernels_graph.hip).
-extern "C" int sgl_set_graph(sgl_ctx* c, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol) {
-    FIT_GUARD(c);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    free_graph(c);
-    if (!Gx && !Gi && !Gp) return SGL_OK;   // NULL clears it
-    if (!Gx || !Gi || !Gp) { sgl_set_error("sgl_set_graph: G must be fully given or fully NULL"); return SGL_EINVAL; }
-    // edges cross shards, and the reference defines none of these combinations
-    if (c->team) { sgl_set_error("sgl_set_graph: the context is a rank of a native team (graph-convolutional NMF runs on one shard)"); return SGL_EINVAL; }
-    if (c->allreduce) { sgl_set_error("sgl_set_graph: an all-reduce hook is installed (graph-convolutional NMF runs on one shard)"); return SGL_EINVAL; }
-    if (c->dense_input) { sgl_set_error("sgl_set_graph: the matrix was uploaded dense (c_gcnmf takes a dgCMatrix)"); return SGL_EINVAL; }
-    if (c->link_h || c->link_w) { sgl_set_error("sgl_set_graph: link matrices are set (the reference has no linked graph-convolutional NMF)"); return SGL_EINVAL; }
-    const int32_t n = c->A.ncol;
+int sgl_graph_check(const char* who, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol, int64_t n) {
     if (G_nrow != n || G_ncol != n) {
-        sgl_set_error("sgl_set_graph: G is %d x %d, the matrix has %d cells (G must be n x n)", G_nrow, G_ncol, n);
+        sgl_set_error("%s: G is %d x %d, the matrix has %lld cells (G must be n x n)", who, G_nrow, G_ncol, (long long)n);
         return SGL_EINVAL;
     }
-    if (Gp[0] != 0) { sgl_set_error("sgl_set_graph: not a valid dgCMatrix: p[0] = %d", Gp[0]); return SGL_EINVAL; }
+    if (Gp[0] != 0) { sgl_set_error("%s: not a valid dgCMatrix: p[0] = %d", who, Gp[0]); return SGL_EINVAL; }
+    for (int32_t j = 0; j < (int32_t)n; ++j) {
+        const int64_t lo = Gp[j], hi = Gp[j + 1];
+        if (hi < lo) { sgl_set_error("%s: not a valid dgCMatrix: p decreases at column %d", who, j); return SGL_EINVAL; }
+        for (int64_t q = lo; q < hi; ++q) {
+            if (Gi[q] < 0 || Gi[q] >= n) { sgl_set_error("%s: not a valid dgCMatrix: row index %d outside [0, %lld) in column %d", who, Gi[q], (long long)n, j); return SGL_EINVAL; }
+            if (q > lo && Gi[q] <= Gi[q - 1]) { sgl_set_error("%s: not a valid dgCMatrix: row indices not strictly ascending in column %d", who, j); return SGL_EINVAL; }
+            if (!std::isfinite(Gx[q])) { sgl_set_error("%s: non-finite value (NA / NaN / Inf) in column %d of G", who, j); return SGL_EINVAL; }
+        }
+    }
+    return SGL_OK;
+}
+
+// the columns [0, ncol) of a checked graph onto the context: offsets rebased to Gp[0], hubs cut into segments
+int sgl_graph_upload(sgl_ctx* c, const char* who, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t ncol) {
+    const int32_t n = ncol;
+    const int64_t q_base = Gp[0];
     std::vector<int64_t> p64((size_t)n + 1);
     std::vector<int32_t> seg_col, hub_col, hub_seg0;
     std::vector<int64_t> seg_q0;
     p64[0] = 0;
     for (int32_t j = 0; j < n; ++j) {
-        const int64_t lo = Gp[j], hi = Gp[j + 1];
-        if (hi < lo) { sgl_set_error("sgl_set_graph: not a valid dgCMatrix: p decreases at column %d", j); return SGL_EINVAL; }
-        for (int64_t q = lo; q < hi; ++q) {
-            if (Gi[q] < 0 || Gi[q] >= n) { sgl_set_error("sgl_set_graph: not a valid dgCMatrix: row index %d outside [0, %d) in column %d", Gi[q], n, j); return SGL_EINVAL; }
-            if (q > lo && Gi[q] <= Gi[q - 1]) { sgl_set_error("sgl_set_graph: not a valid dgCMatrix: row indices not strictly ascending in column %d", j); return SGL_EINVAL; }
-            if (!std::isfinite(Gx[q])) { sgl_set_error("sgl_set_graph: non-finite value (NA / NaN / Inf) in column %d of G", j); return SGL_EINVAL; }
-        }
+        const int64_t lo = Gp[j] - q_base, hi = Gp[j + 1] - q_base;
         p64[(size_t)j + 1] = hi;
         if (hi - lo > SGL_GRAPH_HUB) {
             hub_col.push_back(j);
@@ -1554,8 +1567,8 @@ extern "C" int sgl_set_graph(sgl_ctx* c, const double* Gx, const int32_t* Gi, co
         if (e == hipSuccess && bytes > 0) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
     };
     if (rc == SGL_OK) {
-        h2d(g.x, Gx, sizeof(double) * (size_t)g.nnz);
-        h2d(g.i, Gi, sizeof(int32_t) * (size_t)g.nnz);
+        h2d(g.x, Gx + q_base, sizeof(double) * (size_t)g.nnz);
+        h2d(g.i, Gi + q_base, sizeof(int32_t) * (size_t)g.nnz);
         h2d(g.p, p64.data(), sizeof(int64_t) * p64.size());
         if (g.nhub > 0) {
             h2d(g.seg_col, seg_col.data(), sizeof(int32_t) * seg_col.size());
@@ -1564,11 +1577,29 @@ extern "C" int sgl_set_graph(sgl_ctx* c, const double* Gx, const int32_t* Gi, co
             h2d(g.hub_seg0, hub_seg0.data(), sizeof(int32_t) * hub_seg0.size());
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the host vectors leave scope
-        if (e != hipSuccess) { (void)hipGetLastError(); sgl_set_error("sgl_set_graph: %s", hipGetErrorString(e)); rc = SGL_EHIP; }
+        if (e != hipSuccess) { (void)hipGetLastError(); sgl_set_error("%s: %s", who, hipGetErrorString(e)); rc = SGL_EHIP; }
     }
     if (rc != SGL_OK) { free_graph(c); return rc; }
     g.n = n;
+    g.n_src = n;
     return SGL_OK;
+}
+
+extern "C" int sgl_set_graph(sgl_ctx* c, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol) {
+    FIT_GUARD(c);
+    // edges cross shards: a team exchanges a halo and owns its ranks' graphs (sgl_multi_set_graph) -- nothing is touched here
+    if (c->team && (Gx || Gi || Gp)) { sgl_set_error("sgl_set_graph: the context is a rank of a native team (the graph of a team spans its ranks: sgl_multi_set_graph)"); return SGL_EINVAL; }
+    if (c->team && c->graph.n) { sgl_set_error("sgl_set_graph: the graph of a team rank is cleared by sgl_multi_set_graph"); return SGL_EINVAL; }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    free_graph(c);
+    if (!Gx && !Gi && !Gp) return SGL_OK;   // NULL clears it
+    if (!Gx || !Gi || !Gp) { sgl_set_error("sgl_set_graph: G must be fully given or fully NULL"); return SGL_EINVAL; }
+    // the reference defines none of these combinations
+    if (c->allreduce) { sgl_set_error("sgl_set_graph: an all-reduce hook is installed (graph-convolutional NMF runs on one shard)"); return SGL_EINVAL; }
+    if (c->dense_input) { sgl_set_error("sgl_set_graph: the matrix was uploaded dense (c_gcnmf takes a dgCMatrix)"); return SGL_EINVAL; }
+    if (c->link_h || c->link_w) { sgl_set_error("sgl_set_graph: link matrices are set (the reference has no linked graph-convolutional NMF)"); return SGL_EINVAL; }
+    SGLCHK(sgl_graph_check("sgl_set_graph", Gx, Gi, Gp, G_nrow, G_ncol, c->A.ncol));
+    return sgl_graph_upload(c, "sgl_set_graph", Gx, Gi, Gp, c->A.ncol);
 }
 
 // c_gcnmf (src/singlet.cpp:1712-1730, src/RcppExports.cpp:399-417): w_init as R passes it (w_rows x w_cols, column-major) --
