@@ -2,7 +2,7 @@
 """ALS iterations/sec of the c_nmf loop on the synthetic config-3 matrix
 (30 000 genes x 1 000 000 cells, 5 % non-zeros, k = 50), BASELINE.json's metric.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]   (no launcher: ONE process drives the N devices)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (no launcher: ONE process drives the N devices)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (one process per GPU)
 
 Which form runs is decided by the environment (plan()): with WORLD_SIZE set (torch.distributed.run) every process is
@@ -11,6 +11,11 @@ library's one-process team -- sgl_multi_create (ncclCommInitAll), one host threa
 which is what an R session uses (no launcher, no torch).  `--single-process` forces that form at N = 1 (an RCCL team
 of one); `--loopback` puts all N ranks on device 0 (the exchange is then a HIP kernel, RCCL refuses duplicate
 devices): the team logic end to end on a 1-GPU box, marked "loopback": true.
+
+A plain run does what its headline figure needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the JSON
+line (with the phases and the roofline that the timed steps' own hipEvents give).  `--full` adds what takes runs of its
+own: the CPU baseline (the oracle timed on this host's cores: `cpu_baseline`, `speedup_vs_cpu_baseline`), for either
+workload.  The timed steps and the headline are the same with and without it.
 
 A step = one ALS iteration (H-update, scale, W-update, scale, cor) over the
 whole matrix, inputs resident in HBM (generated on the device by the hash
@@ -42,7 +47,7 @@ def parse(argv=None):
     ap.add_argument("--workload", choices=("als", "ard"), default="als",
                     help="als = the headline: plain ALS iterations of c_nmf on config 3; ard = BASELINE config 5 on one GPU: the "
                          "(rank, replicate) grid of masked fits behind ard_nmf / cross_validate_nmf on one resident matrix, with "
-                         "the Gram downdate's FP64-MFMA roofline and the CPU oracle's c_ard_nmf timed beside it")
+                         "the Gram downdate's FP64-MFMA roofline and, with --full, the CPU oracle's c_ard_nmf timed beside it")
     ap.add_argument("--ranks", default="10,20,30,40,50,60,70,80,90,100", help="--workload ard: the ranks of the grid")
     ap.add_argument("--replicates", type=int, default=3, help="--workload ard: restarts per rank (R's n_replicates)")
     ap.add_argument("--maxit", type=int, default=10, help="--workload ard: iterations per masked fit")
@@ -58,7 +63,11 @@ def parse(argv=None):
     ap.add_argument("--data", choices=("iid", "skewed"), default="iid",
                     help="iid = BASELINE's synthetic matrix (the headline); skewed = the same generator with log-normal weights "
                          "per cell (sigma 0.5) and per gene (sigma 1.5): heavy-tailed row and column counts (secondary record)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need and what takes runs of its own: the CPU baseline "
+                         "(the oracle timed on this host's cores, tens of seconds).  Off by default: a plain run sets up, warms "
+                         "up, times the steps, writes --dump-outputs and prints the JSON line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out all the same")
     ap.add_argument("--cpu-sample-cells", type=int, default=None,
                     help="cells of the CPU baseline sample (0 = all); default 200 000 (als) / 10 000 (ard)")
     ap.add_argument("--comm", choices=("auto", "native", "hook", "none"), default="auto",
@@ -79,6 +88,7 @@ def parse(argv=None):
                          "return them, and the step's tol) as DIR/<name>.npy in float64, at most 64 MB in all: a factor too "
                          "large for that is written as a fixed seeded sample of its columns (indices beside it)")
     a = ap.parse_args(argv)
+    a.cpu_baseline = a.full and not a.no_cpu_baseline
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.cpu_sample_cells is None:
@@ -378,7 +388,7 @@ def report(args, run):
     out["nnls_mean_sweeps"] = {"h": sweeps["h_sweeps"] / (args.steps * n_loc), "w": sweeps["w_sweeps"] / (args.steps * max(run["w_cols_rank0"], 1)),
                                "h_per_wave": sweeps["h_wave_sweeps"] / (args.steps * ((n_loc + 63) // 64)),
                                "w_per_wave": sweeps["w_wave_sweeps"] / (args.steps * ((run["w_cols_rank0"] + 63) // 64))}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(args, run.get("w_start"), args.warmup + args.steps)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
@@ -648,7 +658,7 @@ def run_ard(args):
         "per_rank": per_rank, "fits": fits, "generate_s": gen_s,
         "grid_is": "the masked fits only, in rank order; mask lists of the %d seeds are built in the first rank's fits and kept" % args.replicates,
     }
-    if not args.no_cpu_baseline:
+    if args.cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline_ard(args, ranks)
             out["speedup_vs_cpu_baseline"] = out["cpu_baseline"]["value"] / out["value"]
@@ -844,7 +854,7 @@ def main():
 
     if rank == 0:
         mb = (m + world - 1) // world if (world > 1 and mode == "native") else m
-        w_start = ctx.get_factors(h=False)[0] if (world == 1 and not args.no_cpu_baseline) else None   # for the CPU baseline's window
+        w_start = ctx.get_factors(h=False)[0] if (world == 1 and args.cpu_baseline) else None   # for the CPU baseline's window
         out = report(args, {"world": world, "w_start": w_start, "elapsed": elapsed, "tols": tols, "dims": (m, n_loc, nnz_local), "nnz_total": nnz_total,
                             "phases": phases, "phases_all": phases_all, "rank_info": rank_info if world > 1 else None,
                             "sweeps": sweeps, "layout": layout, "gen_s": gen_s, "w_cols_rank0": min(mb, m),

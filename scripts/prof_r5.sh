@@ -22,7 +22,7 @@ run_pmc() {  # name, "counters", command...
   rm -rf $O/$name.d
 }
 BENCH="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline"
-python3 bench.py > $O/r5_bench_default.json 2> $O/r5_bench_default.err
+python3 bench.py --full > $O/r5_bench_default.json 2> $O/r5_bench_default.err
 run_stats r5_kernel_stats python3 bench.py --no-cpu-baseline
 run_pmc r5_pmc_fetch_size "FETCH_SIZE" $BENCH
 run_pmc r5_pmc_write_size "WRITE_SIZE" $BENCH

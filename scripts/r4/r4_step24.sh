@@ -21,5 +21,5 @@ for k in 10 50 70 100; do
   rm -rf $O/$name.d
   echo "== k=$k"; head -8 $O/$name.csv | cut -c1-150
 done
-python3 bench.py > $O/r4_bench_step.json 2> /dev/null; tail -1 $O/r4_bench_step.json | cut -c1-400
+python3 bench.py --full > $O/r4_bench_step.json 2> /dev/null; tail -1 $O/r4_bench_step.json | cut -c1-400
 python3 bench.py --cells 125000 --no-cpu-baseline --steps 20 > $O/r4_shard_125k_step.json 2> /dev/null; tail -1 $O/r4_shard_125k_step.json | cut -c1-300

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:?}" || exit 1
 O=gpurun_out; mkdir -p $O
 timeout 1800 python3 -m pytest tests -x -q -m gpu > $O/r5_s11_fullsuite.log 2>&1; rc=$?; echo "full GPU suite rc=$rc"; tail -3 $O/r5_s11_fullsuite.log
 if [ $rc -ne 0 ]; then grep -E "Error|error|assert" $O/r5_s11_fullsuite.log | head -20; exit 1; fi
-timeout 900 python3 bench.py --steps 20 --warmup 5 > $O/r5_bench.json 2> $O/r5_bench.err; echo "bench rc=$?"
+timeout 900 python3 bench.py --full --steps 20 --warmup 5 > $O/r5_bench.json 2> $O/r5_bench.err; echo "bench rc=$?"
 timeout 600 python3 bench.py --cells 125000 --steps 40 --warmup 5 --no-cpu-baseline > $O/r5_shard_125k.json 2>/dev/null
 timeout 600 python3 bench.py --genes 20000 --cells 50000 --k 30 --steps 50 --warmup 5 --no-cpu-baseline > $O/r5_bench_config2.json 2>/dev/null
 timeout 600 python3 bench.py --gpus 8 --loopback --steps 10 --warmup 2 --no-cpu-baseline > $O/r5_bench_loopback_8.json 2>/dev/null

@@ -3,10 +3,11 @@
 # config 5, the one-shot call, ranks above 128
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
+O=$_   # the output folder just made
 ( time python -m pytest tests -m gpu -x -q --durations=6 ) > gpurun_out/r6_gpu_tests_end_of_round.log 2>&1
 tail -12 gpurun_out/r6_gpu_tests_end_of_round.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-python bench.py > gpurun_out/r6_bench_end_of_round.json 2> gpurun_out/r6_bench_end_of_round.err
+python bench.py --full > $O/r6_bench_end_of_round.json 2> $O/r6_bench_end_of_round.err
 python bench.py --cells 125000 --no-cpu-baseline --steps 40 --warmup 5 > gpurun_out/r6_shard_125k_end_of_round.json 2>/dev/null
 python bench.py --workload ard --no-cpu-baseline > gpurun_out/r6_config5_full_size_end_of_round.json 2>/dev/null
 python scripts/one_shot_rate.py > gpurun_out/r6_one_shot_config3_end_of_round.json 2>/dev/null

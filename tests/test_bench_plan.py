@@ -141,6 +141,25 @@ def test_steps_and_warmup_are_checked():
         assert e.value.code not in (0, None)
 
 
+def test_plain_run_leaves_the_cpu_baseline_to_full(monkeypatch):
+    """A plain run does what the headline needs: the CPU baseline (runs of the oracle on the host's cores) is measured behind
+    --full only, off by default; the headline fields are the same either way."""
+    calls = []
+    monkeypatch.setattr(bench, "cpu_baseline", lambda args, w_start, it_start: calls.append(it_start) or {"value": 0.04, "unit": "iter/s"})
+    shape = ["--gpus", "1", "--steps", "10", "--warmup", "2", "--genes", "300", "--cells", "1000", "--k", "5"]
+    one = _fake_run(1)
+    plain = bench.report(bench.parse(shape), one)
+    assert bench.parse(shape).full is False and not calls
+    assert "cpu_baseline" not in plain and "speedup_vs_cpu_baseline" not in plain
+    full = bench.report(bench.parse(shape + ["--full"]), one)
+    assert calls == [12] and full["cpu_baseline"]["value"] == 0.04
+    assert full["speedup_vs_cpu_baseline"] == pytest.approx(full["value"] / 0.04)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline", "phases_ms_per_step"):
+        assert plain[key] == full[key], key
+    assert plain["value"] == pytest.approx(20.0) and plain["ms_per_step"] == pytest.approx(50.0)
+    assert "cpu_baseline" not in bench.report(bench.parse(shape + ["--full", "--no-cpu-baseline"]), one) and calls == [12]
+
+
 def test_dump_plan_keeps_the_headline_outputs_under_the_limit():
     """Config 3 (30 000 genes x 1 000 000 cells, k = 50): w whole, h a fixed seeded sample of cells; 64 MB in all."""
     m, n, k = 30000, 1000000, 50

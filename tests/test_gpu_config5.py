@@ -276,8 +276,8 @@ def test_r_driver_list_and_dense_branches_equal_the_one_matrix_result(sa, ora):
 
 def test_bench_ard_workload_prints_roofline_and_cpu_baseline():
     """`bench.py --workload ard` is how config 5 is measured (round 5): the grid's wall seconds, per rank the Gram downdate's
-    FP64-MFMA TFLOP/s from its hipEvent phase and the drawn-pair count, and the oracle's c_ard_nmf timed on a cell slice --
-    run here end to end on a small shape and held to the bench contract's keys."""
+    FP64-MFMA TFLOP/s from its hipEvent phase and the drawn-pair count, and -- with --full -- the oracle's c_ard_nmf timed on a
+    cell slice: run here end to end on a small shape and held to the bench contract's keys."""
     import json
     import os
     import subprocess
@@ -285,7 +285,7 @@ def test_bench_ard_workload_prints_roofline_and_cpu_baseline():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "ard", "--genes", "3000", "--cells", "20000", "--ranks", "6,20,50",
-                        "--replicates", "2", "--maxit", "3", "--trace", "2", "--cpu-sample-cells", "1500"],
+                        "--replicates", "2", "--maxit", "3", "--trace", "2", "--cpu-sample-cells", "1500", "--full"],
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])

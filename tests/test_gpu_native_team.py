@@ -276,6 +276,36 @@ def test_bench_launcher_free_forms_print_one_json_line(argv, mode, n):
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(d["roofline"])
 
 
+def test_bench_plain_run_is_lean_and_full_adds_the_cpu_baseline():
+    """The driver's 1-GPU command `python bench.py --gpus 1 --steps N --warmup W` does what the headline needs and prints the
+    contract's keys; the CPU baseline (runs of the oracle on the host) comes with --full only, beside the same headline fields.
+    Small shape, both forms end to end."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    lines = {}
+    for form, extra in (("plain", []), ("full", ["--full", "--cpu-sample-cells", "2000"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--genes", "3000", "--cells", "40000", "--k", "12"] + extra,
+                           capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = lines[form] = json.loads(r.stdout.strip().splitlines()[-1])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                    "dtype", "data", "config", "roofline", "comm", "phases_ms_per_step"):
+            assert key in d, (form, key)
+        assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["comm"]["mode"] == "none"
+        assert d["value"] == pytest.approx(1e3 / d["ms_per_step"])
+    plain, full = lines["plain"], lines["full"]
+    assert "cpu_baseline" not in plain and "speedup_vs_cpu_baseline" not in plain
+    assert full["cpu_baseline"]["value"] > 0 and full["speedup_vs_cpu_baseline"] == pytest.approx(full["value"] / full["cpu_baseline"]["value"])
+    for key in ("metric", "unit", "higher_is_better", "dtype", "config"):
+        assert plain[key] == full[key], key
+    assert plain["tol_last"] == pytest.approx(full["tol_last"], rel=1e-9)                  # the same fit
+    assert set(full) - set(plain) == {"cpu_baseline", "speedup_vs_cpu_baseline"}
+
+
 @pytest.mark.parametrize("nproc", [2, 3])
 def test_bench_process_per_gpu_form_with_several_processes_on_one_device(nproc):
     """The driver's N > 1 command -- `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` -- with every rank's
