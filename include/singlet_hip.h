@@ -617,6 +617,11 @@ SGL_API int sgl_op_transpose(sgl_ctx* ctx, int64_t max_batch_entries);
 /* scale (src/singlet.cpp:219-225) and cor (:184-197). */
 SGL_API int sgl_op_scale(sgl_ctx* ctx, double* F, int32_t k, int64_t cols, double* d);
 SGL_API int sgl_op_cor(sgl_ctx* ctx, const double* x, const double* y, int64_t n, double* out);
+/* The graph convolution of c_gcnmf (src/singlet.cpp:1684-1688) over the graph set by sgl_set_graph:
+ * Y(:, j) = sum over column j of G, in stored order, of G(r, j) * X(:, r); X, Y k x n column-major, n = the cells of the
+ * resident matrix.  Needs a fit of rank k with a graph (SGL_ESTATE without one, SGL_EINVAL for another k); the fit's
+ * factors are not touched.  Refused (SGL_EINVAL) on a rank of a native team, whose convolution reads a halo. */
+SGL_API int sgl_op_graph_conv(sgl_ctx* ctx, const double* X, int32_t k, double* Y);
 /* mse_test (src/singlet.cpp:536-568) on the resident shard with the current factors. */
 SGL_API int sgl_op_mse_test(sgl_ctx* ctx, uint64_t seed, uint64_t inv_density, double* out);
 

@@ -431,6 +431,20 @@ class Context:
         check(self._L.sgl_op_cor(self._h, ptr(x, f64p), ptr(y, f64p), x.size, C.byref(out)))
         return out.value
 
+    def op_graph_conv(self, X, out=None):
+        """Y = X G over the graph of the current fit (set_graph): X (n, k) C-contiguous (== k x n column-major), k the fit's
+        rank.  out: an (n, k) float64 C-contiguous array to write into (a fresh one otherwise)."""
+        X = _f(X)
+        n, k = X.shape
+        _, nc, _ = self.dims()
+        if n != nc:
+            raise ValueError("X must have %d rows (the cells of the resident matrix)" % nc)
+        Y = np.empty((n, k)) if out is None else out
+        if Y.shape != (n, k) or Y.dtype != np.float64 or not Y.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous float64 array of X's shape")
+        check(self._L.sgl_op_graph_conv(self._h, ptr(X, f64p), k, ptr(Y, f64p)))
+        return Y
+
     def op_mse_test(self, seed, inv_density):
         out = C.c_double()
         check(self._L.sgl_op_mse_test(self._h, int(seed), int(inv_density), C.byref(out)))

@@ -140,6 +140,9 @@ static int launch_conv(hipStream_t s, const DevGraph& g, const double* X, double
     return SGL_OK;
 }
 
+// One ladder for both VEC.  Two of its rungs no rank reaches: <1, 2, 1> (an odd k with ne <= 2 is k = 1) and <2, 64, 16>
+// (an even k <= SGL_MAX_K = 1024 has ne <= 512); they stay so that the ladder reads the same for both and a larger
+// SGL_MAX_K needs no new rung.  The 20 reachable ones are run one by one by tests/test_gpu_graph_conv.py.
 template <int VEC, bool SEGS, bool HALO>
 static int dispatch_lpc(hipStream_t s, const DevGraph& g, const double* X, double* Y, int k, int64_t nitems) {
     const int ne = k / VEC;

@@ -1958,6 +1958,25 @@ extern "C" int sgl_op_cor(sgl_ctx* c, const double* x, const double* y, int64_t 
     return op_finish(c, rc, "sgl_op_cor");
 }
 
+// The graph convolution of the fit (kernels_graph.hip) on its own: Y = X G over the context's graph, through the call
+// sgl_step_h / sgl_step_w make (same DevGraph: its hub segments and partial slab).  X goes into a temporary sized as the
+// fit sizes B; the factors and the graph's own buffer are not touched.
+extern "C" int sgl_op_graph_conv(sgl_ctx* c, const double* X, int32_t k, double* Y) {
+    FIT_GUARD(c);
+    if (c->team) { sgl_set_error("sgl_op_graph_conv: the context is a rank of a native team (its convolution reads a halo the team exchanges)"); return SGL_EINVAL; }
+    if (!c->graph.n) { sgl_set_error("sgl_op_graph_conv: no cell graph is set (sgl_set_graph)"); return SGL_ESTATE; }
+    if (!X || !Y) { sgl_set_error("sgl_op_graph_conv: bad arguments"); return SGL_EINVAL; }
+    if (k != c->k) { sgl_set_error("sgl_op_graph_conv: k = %d, the fit has rank %d (the graph's partial slab is sized by it)", k, c->k); return SGL_EINVAL; }
+    const size_t n = (size_t)c->graph.n;
+    DevBuf<double> dX, dY;
+    SGLCHK(dX.alloc((size_t)k * n + 2));
+    SGLCHK(dY.alloc((size_t)k * n + 2));
+    HIPCHK(hipMemcpyAsync(dX.p, X, sizeof(double) * (size_t)k * n, hipMemcpyHostToDevice, c->stream));
+    int rc = k_graph_conv(c->stream, c->graph, dX.p, dY.p, k);
+    if (rc == SGL_OK && hipMemcpyAsync(Y, dY.p, sizeof(double) * (size_t)k * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = SGL_EHIP;
+    return op_finish(c, rc, "sgl_op_graph_conv");
+}
+
 // --------------------------------------------------------------- timing -----
 extern "C" int sgl_timing_enable(sgl_ctx* c, int on) {
     CTX_GUARD(c);

@@ -120,6 +120,9 @@ def cases():
     # ---- graph-convolutional fit, spatial graph, row-wise compression (restated in numpy under tests/)
     for name, orient, graph in [("lattice_km", "km", "lattice"), ("directed_mk", "mk", "directed"), ("odd_square", "square", "odd")]:
         out.append(("c_gcnmf", name, dict(k=6, orient=orient, graph=graph, maxit=3, L1=0.01, L2=0.0)))
+    # columns of kNN length (20 entries) and one hub of 129: the stored-order sum on columns longer than a lattice's 9
+    for k in (6, 34):
+        out.append(("c_gcnmf", "knn_hub_k%d" % k, dict(k=k, orient="km", graph="knn_hub", side=14, maxit=3, L1=0.01, L2=0.0)))
     out.append(("spatial_graph", "lattice_max_k", dict(kind="lattice", side=9, max_dist=2.5, max_k=7)))
     out.append(("spatial_graph", "coincident", dict(kind="coincident", n=60, max_dist=0.2, max_k=100)))
     out.append(("spatial_graph", "random", dict(kind="random", n=150, max_dist=0.13, max_k=12)))
@@ -180,12 +183,13 @@ def inputs(ora, case):
         return dict(A=A, w=w)
     if entry == "c_gcnmf":
         import gcnmf_restatement as gr
-        side = 8
+        side = p.get("side", 8)
         n = side * side
         m = p["k"] if p["orient"] == "square" else 90
         A = ragged(ora, m, n, 6)
         G = dict(lattice=lambda: gr.lattice_graph(ora, side), directed=lambda: gr.random_directed_graph(ora, n, 4, 9),
-                 odd=lambda: gr.sparse_odd_graph(ora, n, 4))[p["graph"]]()
+                 odd=lambda: gr.sparse_odd_graph(ora, n, 4),
+                 knn_hub=lambda: gr.knn_hub_graph(ora, n, hubs=(77,), hub_len=129, seed=31))[p["graph"]]()
         return dict(A=A, At=A.t(), G=G, w0=ora.synth_winit(p["k"], m), w=_w_oriented(ora.synth_winit(p["k"], m), p["orient"]))
     if entry == "spatial_graph":
         rng = np.random.default_rng(21)

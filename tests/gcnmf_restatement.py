@@ -79,6 +79,44 @@ def hub_graph(ora, n, hub, hub_len, seed):
     return _csc_from_coo(ora, rows, cols, rng.uniform(0.1, 1.0, rows.size), n)
 
 
+EDGE_LENGTHS = [0, 1, 2, 3, 4, 5, 7, 8, 9, 127, 128, 129, 130, 131, 191, 192, 193, 256, 257, 320]
+
+
+def edge_length_graph(ora, n=320, seed=17, weights=None):
+    """Column lengths at every edge of the convolution's loops: the four-deep main loop and its 1 - 3 entry tail, the
+    largest non-hub column (128), the smallest hub (129: segments of 64 + 64 + 1), hubs that are whole multiples of the
+    segment length (192, 256, 320) and one entry either side.  Column c holds EDGE_LENGTHS[c % 20] entries, except: column
+    0 holds 129 and column n - 1 holds n (every row: rows 0 and n - 1 occur), columns 100 and 101 hold 192 and 193
+    (adjacent hubs).  A column of one entry is a self-loop; every other column draws sorted distinct rows.
+    weights = None: entry q (its position in the stored order) weighs s * j / 8 with j = q % 15 + 1, s = -1 where q % 3 ==
+    0, else +1 -- exact in eighths, both signs.  Otherwise weights(nnz) supplies them (same structure)."""
+    rng = np.random.default_rng(seed)
+    lens = np.array([EDGE_LENGTHS[c % len(EDGE_LENGTHS)] for c in range(n)])
+    lens[0], lens[n - 1], lens[100], lens[101] = 129, n, 192, 193
+    assert lens.max() <= n
+    rows = []
+    for c in range(n):
+        rows.append(np.array([c]) if lens[c] == 1 else np.sort(rng.choice(n, size=lens[c], replace=False)))
+    rows = np.concatenate(rows).astype(np.int32)
+    p = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    q = np.arange(rows.size)
+    x = np.where(q % 3 == 0, -1.0, 1.0) * (q % 15 + 1) / 8.0 if weights is None else np.asarray(weights(rows.size), dtype=np.float64)
+    return ora.CSC(x, rows, p, n, n)
+
+
+def knn_hub_graph(ora, n, per_col=20, hubs=(), hub_len=129, seed=23):
+    """A kNN-sized graph: every column holds per_col distinct rows with uniform(0.1, 1.0) weights, the columns listed in
+    `hubs` hold hub_len (> 128: the segment pass sums them)."""
+    rng = np.random.default_rng(seed)
+    rows, cols = [], []
+    for c in range(n):
+        r = rng.choice(n, size=hub_len if c in hubs else per_col, replace=False)
+        rows.append(r)
+        cols.append(np.full(r.size, c))
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    return _csc_from_coo(ora, rows, cols, rng.uniform(0.1, 1.0, rows.size), n)
+
+
 def identity_graph(ora, n):
     return ora.CSC(np.ones(n), np.arange(n, dtype=np.int32), np.arange(n + 1, dtype=np.int32), n, n)
 

@@ -71,3 +71,40 @@ def test_lattice_graph_shape(ora):
     for c in range(16):   # rows ascending within each column, self-loop present
         r = G.i[G.p[c]:G.p[c + 1]]
         assert np.all(np.diff(r) > 0) and c in r
+
+
+def test_edge_length_graph_shape(ora):
+    """what tests/test_gpu_graph_conv.py relies on: the lengths and overrides, sorted distinct rows, self-loops for single
+    entries, rows 0 and n - 1, weights of whole eighths of both signs, 173 columns for the main pass and 147 hubs -- and
+    that its exact test is exact: at k = 3 and k = 1024 the sequential float64 sum equals the int64 sum, below 2^31."""
+    n = 320
+    G = gr.edge_length_graph(ora, n)
+    lens = np.diff(G.p)
+    assert G.nrow == G.ncol == n and lens[0] == 129 and lens[n - 1] == n and lens[100] == 192 and lens[101] == 193
+    assert set(gr.EDGE_LENGTHS) <= set(lens.tolist())
+    assert (lens > 128).sum() == 147 and (lens <= 128).sum() == 173
+    for c in range(n):
+        r = G.i[G.p[c]:G.p[c + 1]]
+        assert np.all(np.diff(r) > 0) and (lens[c] != 1 or r[0] == c)
+    assert G.i.min() == 0 and G.i.max() == n - 1
+    w8 = G.x * 8
+    assert np.array_equal(w8, np.rint(w8)) and np.abs(w8).max() == 15 and np.abs(w8).min() == 1 and w8.min() < 0 < w8.max()
+    N2 = gr.edge_length_graph(ora, n, weights=np.random.default_rng(29).standard_normal)
+    assert np.array_equal(N2.p, G.p) and np.array_equal(N2.i, G.i) and not np.array_equal(N2.x, G.x)
+    for k in (3, 1024):
+        X = 1024.0 * np.arange(n)[:, None] + np.arange(k)[None, :] + 1.0
+        ref8 = np.zeros((n, k), dtype=np.int64)
+        for c in range(n):
+            s = slice(G.p[c], G.p[c + 1])
+            ref8[c] = (w8[s, None].astype(np.int64) * X[G.i[s]].astype(np.int64)).sum(axis=0)
+        assert np.abs(ref8).max() < 2 ** 31
+        assert np.array_equal(gr.convolve(G, X) * 8, ref8)
+
+
+def test_knn_hub_graph_shape(ora):
+    G = gr.knn_hub_graph(ora, 324, hubs=(0, 200, 201, 323), hub_len=129)
+    lens = np.diff(G.p)
+    assert np.array_equal(np.nonzero(lens != 20)[0], [0, 200, 201, 323]) and np.all(lens[[0, 200, 201, 323]] == 129)
+    for c in range(324):
+        assert np.all(np.diff(G.i[G.p[c]:G.p[c + 1]]) > 0)
+    assert G.x.min() >= 0.1 and G.x.max() <= 1.0

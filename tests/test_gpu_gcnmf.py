@@ -57,6 +57,47 @@ def test_c_gcnmf_parity(sa, ora, k, L1, L2, kind, maxit):
     assert np.allclose(got["tol"], ref["tol"], rtol=1e-7, atol=1e-14)
 
 
+KNN_HUBS = (0, 200, 201, 323)   # the first and the last column, two adjacent ones
+
+
+@pytest.mark.parametrize("k", [2, 4, 31, 63, 127, 258])
+def test_c_gcnmf_parity_knn_graph_with_hubs(sa, ora, k):
+    """Columns of kNN length (20 entries: five rounds of the convolution's four-deep loop) and four hubs of 129 (segments of
+    64 + 64 + 1), at the widths test_c_gcnmf_parity leaves out: 16-byte loads with 1 and 2 lanes per column (k = 2, 4), single
+    loads with 32 and 64 lanes and with two passes (k = 31, 63, 127), four passes (k = 258).  tests/test_gpu_graph_conv.py
+    holds the convolution itself to the exact sum at these widths; this is the fit through it."""
+    m, n, maxit, L1, L2 = 210, 324, 3, 0.01, 0.0
+    A = ora.synth_csc(m, n, 12)
+    At = A.t()
+    G = gr.knn_hub_graph(ora, n, hubs=KNN_HUBS, hub_len=129)
+    w0 = ora.synth_winit(k, m)
+    ref = gr.c_gcnmf(ora, A, At, G, 0.0, maxit, L1, L2, w0)
+    got = sa.c_gcnmf(to_dgc(sa, A), to_dgc(sa, At), _dg(sa, G), 0.0, maxit, False, L1, L2, 0, w0.T)
+    assert got["w"].shape == (m, k) and got["h"].shape == (k, n)
+    _check(got, ref)
+    assert got["iter"] == ref["iter"] == maxit
+    assert np.allclose(got["tol"], ref["tol"], rtol=1e-7, atol=1e-14)
+
+
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize("m,n,k", [(700, 800, 513), (1200, 1100, 1024)])
+def test_c_gcnmf_parity_high_rank(sa, ora, m, n, k):
+    """c_gcnmf above 512, sized as tests/test_gpu_high_rank.py::test_c_nmf_parity_high_rank sizes c_nmf so that every factor
+    stays alive: the convolution's 16-pass instance of single loads (k = 513) and its 8-pass instance of 16-byte loads
+    (k = 1024), main pass and hub segments, two iterations (the second convolves a non-zero h on the W side too)."""
+    A = ora.synth_csc(m, n, 20)
+    At = A.t()
+    G = gr.knn_hub_graph(ora, n, hubs=(0, n // 2, n // 2 + 1, n - 1), hub_len=129)
+    w0 = ora.synth_winit(k, m)
+    ref = gr.c_gcnmf(ora, A, At, G, 0.0, 2, 0.0, 0.0, w0, pairwise=False)
+    d = np.asarray(ref["d"])
+    assert d.min() > 1e-8 * d.max() and d.min() > 1e-10, d.min()   # a dead factor would make the case test nothing
+    got = sa.c_gcnmf(to_dgc(sa, A), to_dgc(sa, At), _dg(sa, G), 0.0, 2, False, 0.0, 0.0, 0, w0.T)
+    _check(got, ref)
+    assert got["iter"] == ref["iter"] == 2
+    assert np.allclose(got["tol"], ref["tol"], rtol=1e-7, atol=1e-14)
+
+
 def test_graph_orientation_matters(sa, ora):
     """G and G^T of an asymmetric graph give different fits, each equal to its own restatement."""
     m, n, k = 150, 256, 9
