@@ -18,17 +18,237 @@
 
 #pragma clang fp contract(off)
 
+// ------------------------------------------------------------------------------------------------------ shared plumbing ---
+namespace {
+
+unsigned grid_for(int64_t n, int per_block) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, 65535)); }
+
+int hip_ok(hipError_t e, const char* what) {
+    if (e == hipSuccess) return SGL_OK;
+    (void)hipGetLastError();
+    sgl_set_error("%s failed: %s", what, hipGetErrorString(e));
+    return SGL_EHIP;
+}
+#define NBCHK(expr, what) SGLCHK(hip_ok((expr), what))
+
+// n host elements into a fresh device buffer, and n device elements back (n = 0: nothing is copied).
+template <typename T>
+int upload(hipStream_t s, DevBuf<T>& d, const T* h, size_t n, const char* what) {
+    SGLCHK(d.alloc(n));
+    if (n > 0) NBCHK(hipMemcpyAsync(d.p, h, sizeof(T) * n, hipMemcpyHostToDevice, s), what);
+    return SGL_OK;
+}
+template <typename T>
+int download(hipStream_t s, T* h, const T* d, size_t n, const char* what) {
+    if (n > 0) NBCHK(hipMemcpyAsync(h, d, sizeof(T) * n, hipMemcpyDeviceToHost, s), what);
+    return SGL_OK;
+}
+
+// A hipcub call in its two steps: call(nullptr, bytes) asks for the size of the temporary storage, call(tmp, bytes) runs.
+template <typename F>
+int cub_run(F call, const char* what) {
+    size_t bytes = 0;
+    NBCHK(call(nullptr, bytes), what);
+    DevBuf<char> tmp;
+    SGLCHK(tmp.alloc(bytes));
+    NBCHK(call(tmp.p, bytes), what);
+    return SGL_OK;
+}
+
+// Work lists of LKNN (sorted positions) and SNN (columns): the items of length 1 .. cap sort in LDS, one 64-lane workgroup
+// each (fast); the longer ones go through HBM (slow); those of length 0 have no work.  Both lists on the host and the device.
+struct WorkLists {
+    std::vector<int32_t> fast, slow;
+    DevBuf<int32_t> dfast, dslow;
+};
+int split_work(hipStream_t s, const std::vector<int64_t>& len, int64_t cap, WorkLists& w) {
+    for (size_t e = 0; e < len.size(); ++e)
+        if (len[e] > 0) (len[e] <= cap ? w.fast : w.slow).push_back((int32_t)e);
+    SGLCHK(upload(s, w.dfast, w.fast.data(), w.fast.size(), "upload"));
+    return upload(s, w.dslow, w.slow.data(), w.slow.size(), "upload");
+}
+
+// In-LDS bitonic sort of s[0, P) ascending, P a power of two; one 64-lane workgroup.
+template <typename K>
+__device__ __forceinline__ void bitonic_lds(K* s, int P) {
+    for (int size = 2; size <= P; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < P; t += 64) {
+                const int u = t ^ stride;
+                if (u > t) {
+                    const K x = s[t], y = s[u];
+                    const bool up = (t & size) == 0;
+                    if ((x > y) == up) { s[t] = y; s[u] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// The sum of v over the workgroup, to every thread; *acc is an LDS word of the caller, free again on return.
+__device__ __forceinline__ int block_sum(int* acc, int v) {
+    if (threadIdx.x == 0) *acc = 0;
+    __syncthreads();
+    atomicAdd(acc, v);
+    __syncthreads();
+    const int sum = *acc;
+    __syncthreads();
+    return sum;
+}
+
+// ---- the spatial cell list of LKNN (float coordinates, reach = radius) and spatial_graph (double, reach = max_dist).
+// Points are keyed by their bucket by * W + bx of a W x H grid of square buckets, b = floor((c - cmin) / side) in double, and
+// sorted by key (stable: a bucket's members stay in ascending index order).  Every pair of points that passes the operator's
+// distance test lies in adjacent buckets, so the candidates of a point are the 3 x 3 buckets around it: three runs of sorted
+// positions, one per bucket row.
+//
+// Why the prefilter is conservative.  Let the test be d = fl(sqrt(fl(fl(dx*dx) + fl(dy*dy)))) <= r (spatial_graph: < r) with
+// dx = fl(x1 - x2), in a format of p significand bits whose smallest normal number is 2^e, without contraction.  If
+// |dx| < 2^(e/2), then |x1 - x2| < 2^(e/2 + 1) (a difference that rounds below 2^(e/2) is below it too, or subnormal and exact).
+// Otherwise dx*dx >= 2^e is normal, so fl(dx*dx) >= dx^2 (1 - 2^-p); adding a non-negative fl(dy*dy) and taking the rounded
+// root are monotone, each losing at most a factor (1 - 2^-p), so |dx| <= d (1 + 2^(2-p)) and |x1 - x2| <= |dx| (1 + 2^(1-p)) <=
+// r (1 + 2^(3-p)).  Either way |x1 - x2| <= R = max(r, 2^(e/2 + 1)) (1 + 2^(3-p)), and the same holds for y.  Buckets have side
+// s >= max(r, 2^(e/2 + 1)) (1 + 2^-10), so |x1 - x2| / s < 1 - 2^-11.  The bucket coordinate u = fl(fl(x - xmin) / s) in double is
+// off by at most 2^-52 u <= 2^-21, since s is also raised so that u <= 2^30; so |u1 - u2| < 1 and floor(u1), floor(u2) differ by
+// at most one.  The test itself is then evaluated exactly as the reference does, underflow of dx*dx included.
+//   float  (LKNN):          p = 24, e = -126:  factor 1 + 2^-21, reach floor 2^-62  (radius 0: buckets of side ~2^-62, exact
+//                           coordinates up to the underflow of dx*dx that the reference's test also lets through)
+//   double (spatial_graph): p = 53, e = -1022: factor 1 + 2^-50, reach floor 2^-510; here the quotient (x - xmin) / s can be
+//                           subnormal, which adds 2^-1074 to u's error: still <= 2^-21
+// Both factors sit inside the side's 1 + 2^-10.
+struct CellGrid {
+    double xmin, ymin, side;
+    int64_t W, H;
+};
+
+// The grid over the extent [xmin, xmax] x [ymin, ymax] for a reach and its floor; an extent that overflows double is one
+// bucket (every pair is a candidate).
+CellGrid cell_grid(double xmin, double xmax, double ymin, double ymax, double reach, double reach_floor) {
+    CellGrid g{xmin, ymin, INFINITY, 1, 1};
+    const double ext = std::max(xmax - xmin, ymax - ymin);
+    if (ext < INFINITY) {
+        g.side = std::max(std::max(reach, reach_floor) * (1.0 + ldexp(1.0, -10)), ext * ldexp(1.0, -30));
+        g.W = (int64_t)floor((xmax - xmin) / g.side) + 2;
+        g.H = (int64_t)floor((ymax - ymin) / g.side) + 2;
+    }
+    return g;
+}
+
+template <typename T>
+__global__ void cell_keys_kernel(const T* __restrict__ cx, const T* __restrict__ cy, int64_t n, CellGrid g, uint64_t* __restrict__ keys,
+                                 uint32_t* __restrict__ iota) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        int64_t bx = 0, by = 0;
+        if (g.W > 1) {   // cell_grid's W, H hold every point: the clamps never bind
+            bx = std::min<int64_t>((int64_t)floor(((double)cx[e] - g.xmin) / g.side), g.W - 1);
+            by = std::min<int64_t>((int64_t)floor(((double)cy[e] - g.ymin) / g.side), g.H - 1);
+        }
+        keys[e] = (uint64_t)(by * g.W + bx);
+        iota[e] = (uint32_t)e;
+    }
+}
+
+// The boundary table: bnd[12 pos + 4 q + r] = the sorted position where bucket bx - 1 + r of row by - 1 + q starts (r = 0 .. 3,
+// q = 0 .. 2; a row outside the grid: 0), for the bucket (bx, by) of sorted position pos.  So [bnd[4 q + r], bnd[4 q + r + 1]) is
+// one of the nine buckets and [bnd[4 q], bnd[4 q + 3]) the run of row q.  ncand, unless null: the three runs' total.
+__global__ void cell_bounds_kernel(const uint64_t* __restrict__ skeys, int64_t n, int64_t W, int64_t H, int32_t* __restrict__ bnd,
+                                   int64_t* __restrict__ ncand) {
+    for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t key = (int64_t)skeys[pos], by = key / W, bx = key % W;
+        int64_t tot = 0;
+        for (int q = 0; q < 3; ++q) {
+            const int64_t yy = by - 1 + q;
+            int64_t b[4] = {0, 0, 0, 0};
+            for (int r = 0; r < 4; ++r) {
+                if (yy >= 0 && yy < H) {   // the first sorted position whose key is not below the bucket's
+                    const uint64_t v = (uint64_t)(yy * W + std::min<int64_t>(std::max<int64_t>(bx - 1 + r, 0), W));
+                    int64_t lo = 0, hi = n;
+                    while (lo < hi) {
+                        const int64_t mid = (lo + hi) >> 1;
+                        if (skeys[mid] < v) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    b[r] = lo;
+                }
+                bnd[pos * 12 + q * 4 + r] = (int32_t)b[r];
+            }
+            tot += b[3] - b[0];
+        }
+        if (ncand) ncand[pos] = tot;
+    }
+}
+
+struct CellList {
+    DevBuf<uint32_t> sidx;   // point at each sorted position
+    DevBuf<int32_t> bnd;     // the boundary table, 12 per sorted position
+};
+
+// The cell list of n > 0 device-resident points on grid g; ncand (device, n entries) may be null.
+template <typename T>
+int cell_list_build(hipStream_t s, const T* cx, const T* cy, int64_t n, const CellGrid& g, CellList& cl, int64_t* ncand) {
+    DevBuf<uint64_t> keys, skeys;
+    DevBuf<uint32_t> iota;
+    SGLCHK(keys.alloc((size_t)n));
+    SGLCHK(skeys.alloc((size_t)n));
+    SGLCHK(iota.alloc((size_t)n));
+    SGLCHK(cl.sidx.alloc((size_t)n));
+    SGLCHK(cl.bnd.alloc((size_t)n * 12));
+    cell_keys_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(cx, cy, n, g, keys.p, iota.p);
+    NBCHK(hipGetLastError(), "cell_keys_kernel");
+    int end_bit = 1;
+    while (end_bit < 64 && ((uint64_t)1 << end_bit) <= (uint64_t)(g.W * g.H)) ++end_bit;
+    SGLCHK(cub_run([&](void* tmp, size_t& bytes) {   // LSD radix sort is stable
+        return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys.p, skeys.p, iota.p, cl.sidx.p, (int)n, 0, end_bit, s);
+    }, "radix sort"));
+    cell_bounds_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(skeys.p, n, g.W, g.H, cl.bnd.p, ncand);
+    NBCHK(hipGetLastError(), "cell_bounds_kernel");
+    return SGL_OK;
+}
+
+// ---- the two-call CSC tail of the three entries (api._two_call makes the two calls).
+// Host counts per column -> p_out and *nnz_out; a graph of more than 2^31 - 1 entries is refused with too_many (one %lld).
+template <typename C>
+int csc_pointers(const std::vector<C>& cnt, const char* too_many, int32_t* p_out, int64_t* nnz_out) {
+    int64_t nnz = 0;
+    for (const C c : cnt) nnz += c;
+    if (nnz > INT32_MAX) { sgl_set_error(too_many, (long long)nnz); return SGL_EINVAL; }
+    p_out[0] = 0;
+    for (size_t c = 0; c < cnt.size(); ++c) p_out[c + 1] = p_out[c] + (int32_t)cnt[c];
+    *nnz_out = nnz;
+    return SGL_OK;
+}
+// After csc_pointers: the count-only call (no i_out) ends here, and a capacity below nnz is refused with too_small (two
+// %lld) -- p_out and *nnz_out stay filled, the caller sizes its arrays by them.  Else fill(off, oi, ox) enqueues the
+// operator's kernels that write rows and values at the column offsets off (device, of type OFF), and both come back.
+template <typename OFF, typename F>
+int csc_fill(hipStream_t s, int64_t n, const int32_t* p_out, int64_t nnz, int64_t cap, const char* too_small, int32_t* i_out, double* x_out,
+             F fill) {
+    if (!i_out) return SGL_OK;
+    if (cap < nnz) { sgl_set_error(too_small, (long long)cap, (long long)nnz); return SGL_EINVAL; }
+    const std::vector<OFF> off(p_out, p_out + n + 1);
+    DevBuf<OFF> doff;
+    DevBuf<int32_t> oi;
+    DevBuf<double> ox;
+    SGLCHK(upload(s, doff, off.data(), off.size(), "upload of p"));
+    SGLCHK(oi.alloc((size_t)nnz));
+    SGLCHK(ox.alloc((size_t)nnz));
+    SGLCHK(fill(doff.p, oi.p, ox.p));
+    SGLCHK(download(s, i_out, oi.p, (size_t)nnz, "download of i"));
+    SGLCHK(download(s, x_out, ox.p, (size_t)nnz, "download of x"));
+    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
+    return SGL_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------- LKNN ---
 namespace {
 
 enum { NB_EUCLIDEAN = 0, NB_JACCARD, NB_COSINE, NB_MANHATTAN, NB_HAMMING, NB_KL };
 
 constexpr int LKNN_CAP = 512;    // candidates a point sorts in LDS (one 64-lane workgroup, 4 KB); above: segmented sort in HBM
-constexpr int SNN_CAP = 2048;    // gathered column indices a column sorts in LDS (8 KB); above: dense counters in HBM
 constexpr uint64_t NO_KEY = ~0ull;
 
-unsigned grid_for(int64_t n, int per_block) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per_block - 1) / per_block, 65535)); }
-
-// ---------------------------------------------------------------------------------------------------------------- LKNN ---
 // Order-preserving 32-bit key of a distance: -0 is +0 (they tie and are both dropped), every NaN is one value above +inf.
 // key_dist returns that NaN as x86's default NaN (0xffc00000, sign set), the one the reference's 0/0 gives.
 __device__ __forceinline__ uint32_t dist_key(float d) {
@@ -103,7 +323,7 @@ struct LknnArgs {
     float radius, max_dist;
     int similarity;
     const uint32_t* sidx;    // point at each sorted position
-    const int32_t* rng;      // 6 per sorted position: the three [lo, hi) runs of sorted positions of the 3 x 3 buckets
+    const int32_t* bnd;      // the cell list's boundary table: run q of a position's candidates is [bnd[4 q], bnd[4 q + 3])
     int64_t k;
 };
 
@@ -111,12 +331,12 @@ struct LknnArgs {
 // it is the point itself, outside the radius (the reference's exact test, :1520-1523) or pruned by max_dist (:1541).
 template <int MET>
 __device__ __forceinline__ uint64_t lknn_candidate(const LknnArgs& a, int64_t pos, uint32_t pt, int c) {
-    const int32_t* r = a.rng + pos * 6;
+    const int32_t* r = a.bnd + pos * 12;
     int32_t sp;
-    const int32_t l0 = r[1] - r[0], l1 = r[3] - r[2];
+    const int32_t l0 = r[3] - r[0], l1 = r[7] - r[4];
     if (c < l0) sp = r[0] + c;
-    else if (c < l0 + l1) sp = r[2] + (c - l0);
-    else sp = r[4] + (c - l0 - l1);
+    else if (c < l0 + l1) sp = r[4] + (c - l0);
+    else sp = r[8] + (c - l0 - l1);
     const uint32_t j = a.sidx[sp];
     if (j == pt) return NO_KEY;
     const float dx = a.cx[pt] - a.cx[j], dy = a.cy[pt] - a.cy[j];
@@ -127,20 +347,19 @@ __device__ __forceinline__ uint64_t lknn_candidate(const LknnArgs& a, int64_t po
     return ((uint64_t)dist_key(d12) << 32) | j;
 }
 
-// In-LDS bitonic sort of s[0, P) ascending, P a power of two; one 64-lane workgroup.
-__device__ __forceinline__ void bitonic_lds(uint64_t* s, int P) {
-    for (int size = 2; size <= P; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < P; t += 64) {
-                const int u = t ^ stride;
-                if (u > t) {
-                    const uint64_t x = s[t], y = s[u];
-                    const bool up = (t & size) == 0;
-                    if ((x > y) == up) { s[t] = y; s[u] = x; }
-                }
-            }
-            __syncthreads();
-        }
+// The kk kept neighbours of a point, as sorted index-major keys (index << 32 | distance key), to its staging slots
+// [o, o + kk), zeros included; the calling thread handles every stride-th one and returns how many of its are non-zero.
+__device__ __forceinline__ int lknn_write_kept(const uint64_t* keys, int kk, int stride, int64_t o, int32_t* __restrict__ ti,
+                                               float* __restrict__ tx) {
+    int nz = 0;
+    for (int c = threadIdx.x; c < kk; c += stride) {
+        const uint64_t v = keys[c];
+        const float d = key_dist((uint32_t)v);
+        ti[o + c] = (int32_t)(v >> 32);
+        tx[o + c] = d;
+        nz += d != 0.0f;
+    }
+    return nz;
 }
 
 // Points whose 3 x 3 buckets hold at most LKNN_CAP candidates, one 64-lane workgroup each, in spatial (sorted) order so that
@@ -152,48 +371,30 @@ __global__ __launch_bounds__(64) void lknn_fast_kernel(LknnArgs a, const int32_t
                                                        float* __restrict__ tx, int32_t* __restrict__ kept,
                                                        int32_t* __restrict__ nzc) {
     __shared__ uint64_t s[LKNN_CAP];
-    __shared__ int npass;
+    __shared__ int acc;
     for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
         const int64_t pos = work[w];
         const uint32_t pt = a.sidx[pos];
-        const int32_t* r = a.rng + pos * 6;
-        const int C = (r[1] - r[0]) + (r[3] - r[2]) + (r[5] - r[4]);
+        const int32_t* r = a.bnd + pos * 12;
+        const int C = (r[3] - r[0]) + (r[7] - r[4]) + (r[11] - r[8]);
         int P = 64;
         while (P < C) P <<= 1;
-        if (threadIdx.x == 0) npass = 0;
-        __syncthreads();
         int mine = 0;
         for (int c = threadIdx.x; c < P; c += 64) {
             const uint64_t key = c < C ? lknn_candidate<MET>(a, pos, pt, c) : NO_KEY;
             mine += key != NO_KEY;
             s[c] = key;
         }
-        atomicAdd(&npass, mine);
-        __syncthreads();
+        const int kk = (int)std::min<int64_t>(a.k, (int64_t)block_sum(&acc, mine));
         bitonic_lds(s, P);
-        const int kk = (int)std::min<int64_t>(a.k, (int64_t)npass);
         for (int c = threadIdx.x; c < P; c += 64) {   // the kept ones, index-major
             const uint64_t v = s[c];
             s[c] = c < kk ? (((v & 0xffffffffull) << 32) | (v >> 32)) : NO_KEY;
         }
         __syncthreads();
         bitonic_lds(s, P);
-        int nz = 0;
-        const int64_t o = toff[pt];
-        for (int c = threadIdx.x; c < kk; c += 64) {
-            const uint64_t v = s[c];
-            const float d = key_dist((uint32_t)v);
-            ti[o + c] = (int32_t)(v >> 32);
-            tx[o + c] = d;
-            nz += d != 0.0f;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) npass = 0;
-        __syncthreads();
-        atomicAdd(&npass, nz);
-        __syncthreads();
-        if (threadIdx.x == 0) { kept[pt] = kk; nzc[pt] = npass; }
-        __syncthreads();
+        const int nz = block_sum(&acc, lknn_write_kept(s, kk, 64, toff[pt], ti, tx));
+        if (threadIdx.x == 0) { kept[pt] = kk; nzc[pt] = nz; }
     }
 }
 
@@ -203,23 +404,19 @@ template <int MET>
 __global__ __launch_bounds__(256) void lknn_slow_keys_kernel(LknnArgs a, const int32_t* __restrict__ work, int64_t nwork,
                                                             const int32_t* __restrict__ soff, uint64_t* __restrict__ keys,
                                                             int32_t* __restrict__ npass) {
-    __shared__ int cnt;
+    __shared__ int acc;
     for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
         const int64_t pos = work[w];
-        const uint32_t pt = a.sidx[pos];
+        const uint32_t pt = __builtin_amdgcn_readfirstlane(a.sidx[pos]);   // (one point per workgroup)
         const int C = soff[w + 1] - soff[w];
-        if (threadIdx.x == 0) cnt = 0;
-        __syncthreads();
         int mine = 0;
         for (int c = threadIdx.x; c < C; c += blockDim.x) {
             const uint64_t key = lknn_candidate<MET>(a, pos, pt, c);
             mine += key != NO_KEY;
             keys[soff[w] + c] = key;
         }
-        atomicAdd(&cnt, mine);
-        __syncthreads();
-        if (threadIdx.x == 0) npass[w] = cnt;
-        __syncthreads();
+        const int n = block_sum(&acc, mine);
+        if (threadIdx.x == 0) npass[w] = n;
     }
 }
 
@@ -242,25 +439,12 @@ __global__ void lknn_slow_write_kernel(const uint64_t* __restrict__ sorted2, con
                                        const uint32_t* __restrict__ sidx, const int64_t* __restrict__ toff,
                                        int32_t* __restrict__ ti, float* __restrict__ tx, int32_t* __restrict__ kept,
                                        int32_t* __restrict__ nzc) {
-    __shared__ int cnt;
+    __shared__ int acc;
     for (int64_t w = blockIdx.x; w < nwork; w += gridDim.x) {
-        const uint32_t pt = sidx[work[w]];
+        const uint32_t pt = __builtin_amdgcn_readfirstlane(sidx[work[w]]);
         const int kk = kend[w] - soff[w];
-        const int64_t o = toff[pt];
-        if (threadIdx.x == 0) cnt = 0;
-        __syncthreads();
-        int nz = 0;
-        for (int c = threadIdx.x; c < kk; c += blockDim.x) {
-            const uint64_t v = sorted2[soff[w] + c];
-            const float d = key_dist((uint32_t)v);
-            ti[o + c] = (int32_t)(v >> 32);
-            tx[o + c] = d;
-            nz += d != 0.0f;
-        }
-        atomicAdd(&cnt, nz);
-        __syncthreads();
-        if (threadIdx.x == 0) { kept[pt] = kk; nzc[pt] = cnt; }
-        __syncthreads();
+        const int nz = block_sum(&acc, lknn_write_kept(sorted2 + soff[w], kk, blockDim.x, toff[pt], ti, tx));
+        if (threadIdx.x == 0) { kept[pt] = kk; nzc[pt] = nz; }
     }
 }
 
@@ -278,48 +462,6 @@ __global__ void lknn_to_float_kernel(const double* __restrict__ m, int64_t m_row
     if (bad) atomicOr(flag, 1);
 }
 
-// Bucket key of every point: by * W + bx, with b = floor((c - cmin) / s) computed in double (see lknn_buckets for why this
-// is conservative).
-__global__ void lknn_keys_kernel(const float* __restrict__ cx, const float* __restrict__ cy, int64_t n, double xmin, double ymin,
-                                 double s, int64_t W, uint64_t* __restrict__ keys, uint32_t* __restrict__ iota) {
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t bx = (int64_t)floor(((double)cx[e] - xmin) / s), by = (int64_t)floor(((double)cy[e] - ymin) / s);
-        keys[e] = (uint64_t)(by * W + bx);
-        iota[e] = (uint32_t)e;
-    }
-}
-
-__device__ __forceinline__ int64_t lower_bound_u64(const uint64_t* a, int64_t n, uint64_t v) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// The three runs of sorted positions (buckets bx-1 .. bx+1 of rows by-1 .. by+1 are contiguous in key order) and their total.
-__global__ void lknn_ranges_kernel(const uint64_t* __restrict__ skeys, int64_t n, int64_t W, int64_t H, int32_t* __restrict__ rng,
-                                   int64_t* __restrict__ C) {
-    for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t key = (int64_t)skeys[pos], by = key / W, bx = key % W;
-        int64_t tot = 0;
-        for (int q = 0; q < 3; ++q) {
-            const int64_t yy = by - 1 + q;
-            int64_t lo = 0, hi = 0;
-            if (yy >= 0 && yy < H) {
-                lo = lower_bound_u64(skeys, n, (uint64_t)(yy * W + std::max<int64_t>(bx - 1, 0)));
-                hi = lower_bound_u64(skeys, n, (uint64_t)(yy * W + std::min<int64_t>(bx + 1, W - 1) + 1));
-            }
-            rng[pos * 6 + 2 * q] = (int32_t)lo;
-            rng[pos * 6 + 2 * q + 1] = (int32_t)hi;
-            tot += hi - lo;
-        }
-        C[pos] = tot;
-    }
-}
-
 // Drop the zeros (:1572-1588) and widen to double: point pt's staged entries -> its output column at off[pt].
 __global__ void lknn_compact_kernel(const int64_t* __restrict__ toff, const int32_t* __restrict__ kept, const int64_t* __restrict__ off,
                                     const int32_t* __restrict__ ti, const float* __restrict__ tx, int64_t n,
@@ -335,15 +477,14 @@ __global__ void lknn_compact_kernel(const int64_t* __restrict__ toff, const int3
 template <int MET>
 int lknn_launch_fast(hipStream_t s, const LknnArgs& a, const int32_t* work, int64_t nwork, const int64_t* toff, int32_t* ti, float* tx,
                      int32_t* kept, int32_t* nzc) {
-    if (nwork > 0)
-        lknn_fast_kernel<MET><<<dim3(grid_for(nwork, 1)), dim3(64), 0, s>>>(a, work, nwork, toff, ti, tx, kept, nzc);
-    return hipGetLastError() == hipSuccess ? SGL_OK : SGL_EHIP;
+    if (nwork > 0) lknn_fast_kernel<MET><<<dim3(grid_for(nwork, 1)), dim3(64), 0, s>>>(a, work, nwork, toff, ti, tx, kept, nzc);
+    return hip_ok(hipGetLastError(), "lknn_fast_kernel");
 }
 template <int MET>
 int lknn_launch_slow_keys(hipStream_t s, const LknnArgs& a, const int32_t* work, int64_t nwork, const int32_t* soff, uint64_t* keys,
                           int32_t* npass) {
     lknn_slow_keys_kernel<MET><<<dim3(grid_for(nwork, 1)), dim3(256), 0, s>>>(a, work, nwork, soff, keys, npass);
-    return hipGetLastError() == hipSuccess ? SGL_OK : SGL_EHIP;
+    return hip_ok(hipGetLastError(), "lknn_slow_keys_kernel");
 }
 
 #define NB_DISPATCH(met, fn, ...)                                   \
@@ -353,14 +494,6 @@ int lknn_launch_slow_keys(hipStream_t s, const LknnArgs& a, const int32_t* work,
      : (met) == NB_HAMMING   ? fn<NB_HAMMING>(__VA_ARGS__)          \
      : (met) == NB_KL        ? fn<NB_KL>(__VA_ARGS__)               \
                              : fn<NB_EUCLIDEAN>(__VA_ARGS__))
-
-int hip_ok(hipError_t e, const char* what) {
-    if (e == hipSuccess) return SGL_OK;
-    (void)hipGetLastError();
-    sgl_set_error("%s failed: %s", what, hipGetErrorString(e));
-    return SGL_EHIP;
-}
-#define NBCHK(expr, what) SGLCHK(hip_ok((expr), what))
 
 }  // namespace
 
@@ -422,97 +555,55 @@ extern "C" int sgl_c_lknn(const double* m, int32_t m_rows, int32_t m_cols, const
     DevBuf<double> dm;
     DevBuf<float> mf, dcx, dcy;
     DevBuf<int> flag;
-    SGLCHK(dm.alloc((size_t)(D * n)));
     SGLCHK(mf.alloc((size_t)(D * n)));
-    SGLCHK(dcx.alloc((size_t)n));
-    SGLCHK(dcy.alloc((size_t)n));
     SGLCHK(flag.alloc(1));
     NBCHK(hipMemsetAsync(flag.p, 0, sizeof(int), s), "hipMemsetAsync");
+    SGLCHK(upload(s, dm, m, (size_t)(D * n), "upload of m"));
     if (D > 0) {
-        NBCHK(hipMemcpyAsync(dm.p, m, sizeof(double) * (size_t)(D * n), hipMemcpyHostToDevice, s), "upload of m");
         lknn_to_float_kernel<<<dim3(grid_for(D * n, 256)), dim3(256), 0, s>>>(dm.p, m_rows, transpose ? 1 : 0, D, n, mf.p, flag.p);
         NBCHK(hipGetLastError(), "lknn_to_float_kernel");
     }
-    NBCHK(hipMemcpyAsync(dcx.p, cx.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s), "upload of coord_x");
-    NBCHK(hipMemcpyAsync(dcy.p, cy.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s), "upload of coord_y");
+    SGLCHK(upload(s, dcx, cx.data(), (size_t)n, "upload of coord_x"));
+    SGLCHK(upload(s, dcy, cy.data(), (size_t)n, "upload of coord_y"));
     int hflag = 0;
-    NBCHK(hipMemcpyAsync(&hflag, flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "download of the flag");
+    SGLCHK(download(s, &hflag, flag.p, 1, "download of the flag"));
     NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
     if (hflag) { sgl_set_error("c_LKNN: 'm' holds a NaN or infinite value (or one that overflows float)"); return SGL_EINVAL; }
     { DevBuf<double> tmp; std::swap(tmp.p, dm.p); }   // the double copy is done with
 
-    // --- spatial cell list.  Conservative prefilter: let the float test sqrt(dx*dx + dy*dy) <= r pass with dx = fl(x1 - x2).
-    // If |dx| < 2^-63, then |x1 - x2| < 2^-62.  Otherwise dx*dx >= 2^-126 is normal, so fl(dx*dx) >= dx^2 (1 - 2^-24); adding a
-    // non-negative fl(dy*dy) and taking the rounded root are monotone, each losing at most a factor (1 - 2^-24), so
-    // |x1 - x2| <= r (1 + 2^-21).  Either way |x1 - x2| <= R = max(r, 2^-62) (1 + 2^-21), and the same holds for y.  Buckets have
-    // side s >= max(r, 2^-62) (1 + 2^-10), so |x1 - x2| / s < 1 - 2^-11.  The bucket coordinate u = fl(fl(x - xmin) / s) in
-    // double is off by at most 2^-52 u <= 2^-21 (s is also raised so that u <= 2^30), so |u1 - u2| < 1 and floor(u1), floor(u2)
-    // differ by at most one: every pair that passes the radius test lies in adjacent buckets.  The test itself is then
-    // evaluated exactly as the reference does.  (radius 0 gives buckets of side ~2^-62: exact coordinates, up to the float
-    // underflow of dx*dx that the reference's test also lets through.)
-    const double ext = std::max(xmax - xmin, ymax - ymin);
-    const double side = std::max({std::max((double)radius, ldexp(1.0, -62)) * (1.0 + ldexp(1.0, -10)), ext * ldexp(1.0, -30)});
-    const int64_t W = (int64_t)floor((xmax - xmin) / side) + 2, H = (int64_t)floor((ymax - ymin) / side) + 2;
-    DevBuf<uint64_t> keys, skeys;
-    DevBuf<uint32_t> iota, sidx;
-    SGLCHK(keys.alloc((size_t)n));
-    SGLCHK(skeys.alloc((size_t)n));
-    SGLCHK(iota.alloc((size_t)n));
-    SGLCHK(sidx.alloc((size_t)n));
-    lknn_keys_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(dcx.p, dcy.p, n, xmin, ymin, side, W, keys.p, iota.p);
-    NBCHK(hipGetLastError(), "lknn_keys_kernel");
-    int end_bit = 1;
-    while (end_bit < 64 && ((uint64_t)1 << end_bit) <= (uint64_t)(W * H)) ++end_bit;
-    {
-        size_t tb = 0;
-        NBCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, iota.p, sidx.p, (int)n, 0, end_bit, s), "radix sort");
-        DevBuf<char> tmp;
-        SGLCHK(tmp.alloc(tb));
-        NBCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.p, skeys.p, iota.p, sidx.p, (int)n, 0, end_bit, s), "radix sort");
-    }
-    DevBuf<int32_t> rng;
+    // --- spatial cell list, the candidates of every sorted position
+    CellList cl;
     DevBuf<int64_t> dC;
-    SGLCHK(rng.alloc((size_t)n * 6));
     SGLCHK(dC.alloc((size_t)n));
-    lknn_ranges_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(skeys.p, n, W, H, rng.p, dC.p);
-    NBCHK(hipGetLastError(), "lknn_ranges_kernel");
+    SGLCHK(cell_list_build(s, dcx.p, dcy.p, n, cell_grid(xmin, xmax, ymin, ymax, radius, ldexp(1.0, -62)), cl, dC.p));
     std::vector<int64_t> C((size_t)n);
     std::vector<uint32_t> hsidx((size_t)n);
-    NBCHK(hipMemcpyAsync(C.data(), dC.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download of the candidate counts");
-    NBCHK(hipMemcpyAsync(hsidx.data(), sidx.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download of the order");
+    SGLCHK(download(s, C.data(), dC.p, (size_t)n, "download of the candidate counts"));
+    SGLCHK(download(s, hsidx.data(), cl.sidx.p, (size_t)n, "download of the order"));
     NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
 
     // --- staging slots: min(k, candidates) per point, in point order; work lists in sorted (spatial) order
     std::vector<int64_t> toff((size_t)n + 1);
-    std::vector<int32_t> fast, slow;
     toff[0] = 0;
     {
         std::vector<int64_t> room((size_t)n);
-        for (int64_t pos = 0; pos < n; ++pos) {
-            room[hsidx[pos]] = std::min<int64_t>(k, C[pos]);
-            if (C[pos] <= LKNN_CAP) fast.push_back((int32_t)pos);
-            else slow.push_back((int32_t)pos);
-        }
+        for (int64_t pos = 0; pos < n; ++pos) room[hsidx[pos]] = std::min<int64_t>(k, C[pos]);
         for (int64_t pt = 0; pt < n; ++pt) toff[pt + 1] = toff[pt] + room[pt];
     }
     const int64_t staged = toff[n];
+    WorkLists wl;   // (every position has a candidate: the point itself)
     DevBuf<int64_t> dtoff;
-    DevBuf<int32_t> ti, kept, nzc, dfast;
+    DevBuf<int32_t> ti, kept, nzc;
     DevBuf<float> tx;
-    SGLCHK(dtoff.alloc((size_t)n + 1));
+    SGLCHK(split_work(s, C, LKNN_CAP, wl));
+    SGLCHK(upload(s, dtoff, toff.data(), toff.size(), "upload"));
     SGLCHK(ti.alloc((size_t)staged));
     SGLCHK(tx.alloc((size_t)staged));
     SGLCHK(kept.alloc((size_t)n));
     SGLCHK(nzc.alloc((size_t)n));
-    SGLCHK(dfast.alloc(fast.size()));
-    NBCHK(hipMemcpyAsync(dtoff.p, toff.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload");
-    if (!fast.empty())
-        NBCHK(hipMemcpyAsync(dfast.p, fast.data(), sizeof(int32_t) * fast.size(), hipMemcpyHostToDevice, s), "upload");
-    LknnArgs a{mf.p, (int)D, dcx.p, dcy.p, radius, max_dist, similarity ? 1 : 0, sidx.p, rng.p, k};
-    if (NB_DISPATCH(met, lknn_launch_fast, s, a, dfast.p, (int64_t)fast.size(), dtoff.p, ti.p, tx.p, kept.p, nzc.p) != SGL_OK) {
-        sgl_set_error("lknn_fast_kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-        return SGL_EHIP;
-    }
+    const std::vector<int32_t>& slow = wl.slow;
+    LknnArgs a{mf.p, (int)D, dcx.p, dcy.p, radius, max_dist, similarity ? 1 : 0, cl.sidx.p, cl.bnd.p, k};
+    SGLCHK(NB_DISPATCH(met, lknn_launch_fast, s, a, wl.dfast.p, (int64_t)wl.fast.size(), dtoff.p, ti.p, tx.p, kept.p, nzc.p));
 
     // --- points with more than LKNN_CAP candidates: segmented sorts in HBM, in batches of at most 2^27 candidates
     const int64_t BATCH = (int64_t)1 << 27;
@@ -522,33 +613,28 @@ extern "C" int sgl_c_lknn(const double* m, int32_t m_rows, int32_t m_cols, const
         while (b1 < slow.size() && (b1 == b0 || tot + C[slow[b1]] <= BATCH)) tot += C[slow[b1++]];
         if (tot >= INT32_MAX) { sgl_set_error("c_LKNN: one point has %lld candidates in its 3 x 3 buckets (limit 2^31)", (long long)tot); return SGL_EINVAL; }
         const int64_t nw = (int64_t)(b1 - b0);
+        const int32_t* dwork = wl.dslow.p + b0;
         std::vector<int32_t> hsoff((size_t)nw + 1);
         hsoff[0] = 0;
         for (int64_t w = 0; w < nw; ++w) hsoff[w + 1] = hsoff[w] + (int32_t)C[slow[b0 + w]];
-        DevBuf<int32_t> dwork, dsoff, dnpass, dkend;
+        DevBuf<int32_t> dsoff, dnpass, dkend;
         DevBuf<uint64_t> k1, k2;
-        SGLCHK(dwork.alloc((size_t)nw));
-        SGLCHK(dsoff.alloc((size_t)nw + 1));
+        SGLCHK(upload(s, dsoff, hsoff.data(), hsoff.size(), "upload"));
         SGLCHK(dnpass.alloc((size_t)nw));
         SGLCHK(dkend.alloc((size_t)nw));
         SGLCHK(k1.alloc((size_t)tot));
         SGLCHK(k2.alloc((size_t)tot));
-        NBCHK(hipMemcpyAsync(dwork.p, slow.data() + b0, sizeof(int32_t) * (size_t)nw, hipMemcpyHostToDevice, s), "upload");
-        NBCHK(hipMemcpyAsync(dsoff.p, hsoff.data(), sizeof(int32_t) * ((size_t)nw + 1), hipMemcpyHostToDevice, s), "upload");
-        if (NB_DISPATCH(met, lknn_launch_slow_keys, s, a, dwork.p, nw, dsoff.p, k1.p, dnpass.p) != SGL_OK) {
-            sgl_set_error("lknn_slow_keys_kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-            return SGL_EHIP;
-        }
-        size_t tb = 0, tb2 = 0;
-        NBCHK(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, tb, k1.p, k2.p, (int)tot, (int)nw, dsoff.p, dsoff.p + 1, 0, 64, s), "segmented sort");
-        NBCHK(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, tb2, k1.p, k2.p, (int)tot, (int)nw, dsoff.p, dkend.p, 0, 64, s), "segmented sort");
-        DevBuf<char> tmp;
-        SGLCHK(tmp.alloc(std::max(tb, tb2)));
-        NBCHK(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.p, tb, k1.p, k2.p, (int)tot, (int)nw, dsoff.p, dsoff.p + 1, 0, 64, s), "segmented sort");
+        SGLCHK(NB_DISPATCH(met, lknn_launch_slow_keys, s, a, dwork, nw, dsoff.p, k1.p, dnpass.p));
+        const auto sort_segments = [&](int32_t* ends) {   // k1's segments [soff[w], ends[w]) -> k2
+            return cub_run([&](void* tmp, size_t& bytes) {
+                return hipcub::DeviceSegmentedRadixSort::SortKeys(tmp, bytes, k1.p, k2.p, (int)tot, (int)nw, dsoff.p, ends, 0, 64, s);
+            }, "segmented sort");
+        };
+        SGLCHK(sort_segments(dsoff.p + 1));
         lknn_slow_trim_kernel<<<dim3(grid_for(nw, 1)), dim3(256), 0, s>>>(k2.p, k1.p, dsoff.p, dnpass.p, nw, k, dkend.p);
         NBCHK(hipGetLastError(), "lknn_slow_trim_kernel");
-        NBCHK(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.p, tb2, k1.p, k2.p, (int)tot, (int)nw, dsoff.p, dkend.p, 0, 64, s), "segmented sort");
-        lknn_slow_write_kernel<<<dim3(grid_for(nw, 1)), dim3(256), 0, s>>>(k2.p, dsoff.p, dkend.p, dwork.p, nw, sidx.p, dtoff.p, ti.p, tx.p,
+        SGLCHK(sort_segments(dkend.p));
+        lknn_slow_write_kernel<<<dim3(grid_for(nw, 1)), dim3(256), 0, s>>>(k2.p, dsoff.p, dkend.p, dwork, nw, cl.sidx.p, dtoff.p, ti.p, tx.p,
                                                                             kept.p, nzc.p);
         NBCHK(hipGetLastError(), "lknn_slow_write_kernel");
         NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");   // the batch's buffers go back to the pool
@@ -557,46 +643,29 @@ extern "C" int sgl_c_lknn(const double* m, int32_t m_rows, int32_t m_cols, const
 
     // --- counts, slot overflow, column pointers
     std::vector<int32_t> hkept((size_t)n), hnz((size_t)n);
-    NBCHK(hipMemcpyAsync(hkept.data(), kept.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download");
-    NBCHK(hipMemcpyAsync(hnz.data(), nzc.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download");
+    SGLCHK(download(s, hkept.data(), kept.p, (size_t)n, "download"));
+    SGLCHK(download(s, hnz.data(), nzc.p, (size_t)n, "download"));
     NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
-    std::vector<int64_t> off((size_t)n + 1);
-    off[0] = 0;
-    for (int64_t pt = 0; pt < n; ++pt) {
+    for (int64_t pt = 0; pt < n; ++pt)
         if ((double)hkept[pt] > n_max_edges) {
             sgl_set_error("c_LKNN: point %lld keeps %d neighbours, more than the %.0f slots per point the reference allocates "
                           "(ceil((2 * radius + 1)^2) - 1): the reference would write into the next point's slots",
                           (long long)pt, hkept[pt], n_max_edges);
             return SGL_EINVAL;
         }
-        off[pt + 1] = off[pt] + hnz[pt];
-    }
-    const int64_t nnz = off[n];
-    if (nnz > INT32_MAX) { sgl_set_error("c_LKNN: %lld edges do not fit a dgCMatrix", (long long)nnz); return SGL_EINVAL; }
-    for (int64_t pt = 0; pt <= n; ++pt) p_out[pt] = (int32_t)off[pt];
-    *nnz_out = nnz;
-    if (!i_out) return SGL_OK;
-    if (cap < nnz) { sgl_set_error("sgl_c_lknn: output capacity %lld < %lld edges", (long long)cap, (long long)nnz); return SGL_EINVAL; }
-
-    DevBuf<int64_t> doff;
-    DevBuf<int32_t> oi;
-    DevBuf<double> ox;
-    SGLCHK(doff.alloc((size_t)n + 1));
-    SGLCHK(oi.alloc((size_t)nnz));
-    SGLCHK(ox.alloc((size_t)nnz));
-    NBCHK(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload");
-    lknn_compact_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(dtoff.p, kept.p, doff.p, ti.p, tx.p, n, oi.p, ox.p);
-    NBCHK(hipGetLastError(), "lknn_compact_kernel");
-    if (nnz > 0) {
-        NBCHK(hipMemcpyAsync(i_out, oi.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download");
-        NBCHK(hipMemcpyAsync(x_out, ox.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download");
-    }
-    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
-    return SGL_OK;
+    SGLCHK(csc_pointers(hnz, "c_LKNN: %lld edges do not fit a dgCMatrix", p_out, nnz_out));
+    return csc_fill<int64_t>(s, n, p_out, *nnz_out, cap, "sgl_c_lknn: output capacity %lld < %lld edges", i_out, x_out,
+                             [&](const int64_t* off, int32_t* oi, double* ox) {
+        lknn_compact_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(dtoff.p, kept.p, off, ti.p, tx.p, n, oi, ox);
+        NBCHK(hipGetLastError(), "lknn_compact_kernel");
+        return SGL_OK;
+    });
 }
 
 // ----------------------------------------------------------------------------------------------------------------- SNN ---
 namespace {
+
+constexpr int SNN_CAP = 2048;    // gathered column indices a column sorts in LDS (8 KB); above: dense counters in HBM
 
 __global__ void snn_row_hist_kernel(const int32_t* __restrict__ Gi, int64_t nnz, int64_t* __restrict__ rcnt) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += (int64_t)gridDim.x * blockDim.x)
@@ -632,21 +701,6 @@ __device__ __forceinline__ bool snn_keep(int64_t i, int64_t j, int64_t inter, co
     return *sim > min_sim;
 }
 
-__device__ __forceinline__ void bitonic_lds_u32(uint32_t* s, int P) {
-    for (int size = 2; size <= P; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < P; t += 64) {
-                const int u = t ^ stride;
-                if (u > t) {
-                    const uint32_t x = s[t], y = s[u];
-                    const bool up = (t & size) == 0;
-                    if ((x > y) == up) { s[t] = y; s[u] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
 // Columns whose gathered list fits LDS, one 64-lane workgroup each: sort the list; a run of j of length L means |rows(i) and
 // rows(j)| = L.  FILL = false: count the entries; FILL = true: write them at off[i], ascending j.
 template <bool FILL>
@@ -671,7 +725,7 @@ __global__ __launch_bounds__(64) void snn_fast_kernel(const int32_t* __restrict_
         for (int q = Tn + lane; q < P; q += 64) s[q] = 0xffffffffu;
         if (lane == 0) s[P] = 0xffffffffu;
         __syncthreads();
-        bitonic_lds_u32(s, P);
+        bitonic_lds(s, P);
         int64_t base = FILL ? off[i] : 0;
         for (int q0 = 0; q0 < Tn; q0 += 64) {
             const int q = q0 + lane;
@@ -770,18 +824,16 @@ extern "C" int sgl_c_snn(const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, i
     CtxHolder hd;
     SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
     hipStream_t s = hd.c->stream;
-    DevBuf<int32_t> dGi, Rj, dfast, dslow;
+    DevBuf<int32_t> dGi, Rj;
     DevBuf<int64_t> dGp, Rp, rcnt, T, cnt;
     DevBuf<int> flag;
-    SGLCHK(dGi.alloc((size_t)gnnz));
-    SGLCHK(dGp.alloc((size_t)n + 1));
+    SGLCHK(upload(s, dGi, Gi, (size_t)gnnz, "upload of G@i"));
+    SGLCHK(upload(s, dGp, hp.data(), hp.size(), "upload of G@p"));
     SGLCHK(flag.alloc(1));
-    if (gnnz > 0) NBCHK(hipMemcpyAsync(dGi.p, Gi, sizeof(int32_t) * (size_t)gnnz, hipMemcpyHostToDevice, s), "upload of G@i");
-    NBCHK(hipMemcpyAsync(dGp.p, hp.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload of G@p");
     NBCHK(hipMemsetAsync(flag.p, 0, sizeof(int), s), "hipMemsetAsync");
     SGLCHK(k_validate_csc(s, dGi.p, dGp.p, n, G_nrow, flag.p));
     int hflag = 0;
-    NBCHK(hipMemcpyAsync(&hflag, flag.p, sizeof(int), hipMemcpyDeviceToHost, s), "download of the flag");
+    SGLCHK(download(s, &hflag, flag.p, 1, "download of the flag"));
     NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
     if (hflag) {
         sgl_set_error("c_SNN: G is not a valid dgCMatrix: %s%s", (hflag & 1) ? "row index outside [0, nrow) " : "",
@@ -810,104 +862,70 @@ extern "C" int sgl_c_snn(const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, i
         snn_gather_len_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(dGi.p, dGp.p, Rp.p, n, T.p);
         NBCHK(hipGetLastError(), "snn_gather_len_kernel");
     }
-    std::vector<int64_t> hT((size_t)n);
-    if (n > 0) NBCHK(hipMemcpyAsync(hT.data(), T.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download");
+    std::vector<int64_t> hT((size_t)n), hcnt((size_t)n, 0);
+    SGLCHK(download(s, hT.data(), T.p, (size_t)n, "download"));
     NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
-    std::vector<int32_t> fast, slow;
-    std::vector<int64_t> hcnt((size_t)n, 0);
-    for (int64_t c = 0; c < n; ++c) {
-        if (hT[c] == 0) continue;   // empty column: no entries (:1611)
-        if (hT[c] <= SNN_CAP) fast.push_back((int32_t)c);
-        else slow.push_back((int32_t)c);
-    }
-    SGLCHK(dfast.alloc(fast.size()));
-    SGLCHK(dslow.alloc(slow.size()));
-    if (!fast.empty()) NBCHK(hipMemcpyAsync(dfast.p, fast.data(), sizeof(int32_t) * fast.size(), hipMemcpyHostToDevice, s), "upload");
-    if (!slow.empty()) NBCHK(hipMemcpyAsync(dslow.p, slow.data(), sizeof(int32_t) * slow.size(), hipMemcpyHostToDevice, s), "upload");
+    WorkLists wl;   // (an empty column has no entries, :1611)
+    SGLCHK(split_work(s, hT, SNN_CAP, wl));
+    const int64_t nfast = (int64_t)wl.fast.size(), nslow = (int64_t)wl.slow.size();
     NBCHK(hipMemsetAsync(cnt.p, 0, sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1), s), "hipMemsetAsync");
     DevBuf<uint32_t> counters;
     int64_t nslots = 0;
-    if (!slow.empty()) {   // one counter row of ncol per resident workgroup, at most 256 MB of them
-        nslots = std::max<int64_t>(1, std::min<int64_t>({(int64_t)slow.size(), 1024, ((int64_t)1 << 26) / std::max<int64_t>(n, 1)}));
+    if (nslow > 0) {   // one counter row of ncol per resident workgroup, at most 256 MB of them
+        nslots = std::max<int64_t>(1, std::min<int64_t>({nslow, 1024, ((int64_t)1 << 26) / std::max<int64_t>(n, 1)}));
         SGLCHK(counters.alloc((size_t)(nslots * n)));
         NBCHK(hipMemsetAsync(counters.p, 0, sizeof(uint32_t) * (size_t)(nslots * n), s), "hipMemsetAsync");
     }
 
     // --- count pass
-    if (!fast.empty()) {
-        snn_fast_kernel<false><<<dim3(grid_for((int64_t)fast.size(), 1)), dim3(64), 0, s>>>(
-            dGi.p, dGp.p, Rp.p, Rj.p, dfast.p, (int64_t)fast.size(), T.p, min_similarity, cnt.p, nullptr, nullptr, nullptr);
+    if (nfast > 0) {
+        snn_fast_kernel<false><<<dim3(grid_for(nfast, 1)), dim3(64), 0, s>>>(
+            dGi.p, dGp.p, Rp.p, Rj.p, wl.dfast.p, nfast, T.p, min_similarity, cnt.p, nullptr, nullptr, nullptr);
         NBCHK(hipGetLastError(), "snn_fast_kernel");
     }
-    if (!slow.empty()) {
-        snn_slow_kernel<false><<<dim3((unsigned)nslots), dim3(256), 0, s>>>(dGi.p, dGp.p, Rp.p, Rj.p, dslow.p, (int64_t)slow.size(), n,
-                                                                          counters.p, min_similarity, cnt.p, nullptr, nullptr, nullptr);
+    if (nslow > 0) {
+        snn_slow_kernel<false><<<dim3((unsigned)nslots), dim3(256), 0, s>>>(dGi.p, dGp.p, Rp.p, Rj.p, wl.dslow.p, nslow, n, counters.p,
+                                                                          min_similarity, cnt.p, nullptr, nullptr, nullptr);
         NBCHK(hipGetLastError(), "snn_slow_kernel");
     }
-    if (n > 0) NBCHK(hipMemcpyAsync(hcnt.data(), cnt.p, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download");
+    SGLCHK(download(s, hcnt.data(), cnt.p, (size_t)n, "download"));
     NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
-    std::vector<int64_t> off((size_t)n + 1);
-    off[0] = 0;
-    for (int64_t c = 0; c < n; ++c) off[c + 1] = off[c] + hcnt[c];
-    const int64_t nnz = off[n];
-    if (nnz > INT32_MAX) {
-        sgl_set_error("c_SNN: the graph would hold %lld entries, which a dgCMatrix (32-bit column pointers) cannot hold; "
-                      "raise min_similarity", (long long)nnz);
-        return SGL_EINVAL;
-    }
-    for (int64_t c = 0; c <= n; ++c) p_out[c] = (int32_t)off[c];
-    *nnz_out = nnz;
-    if (!i_out) return SGL_OK;
-    if (cap < nnz) { sgl_set_error("sgl_c_snn: output capacity %lld < %lld entries", (long long)cap, (long long)nnz); return SGL_EINVAL; }
+    SGLCHK(csc_pointers(hcnt, "c_SNN: the graph would hold %lld entries, which a dgCMatrix (32-bit column pointers) cannot hold; "
+                              "raise min_similarity", p_out, nnz_out));
 
     // --- fill pass
-    DevBuf<int64_t> doff;
-    DevBuf<int32_t> oi;
-    DevBuf<double> ox;
-    SGLCHK(doff.alloc((size_t)n + 1));
-    SGLCHK(oi.alloc((size_t)nnz));
-    SGLCHK(ox.alloc((size_t)nnz));
-    NBCHK(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload");
-    if (!fast.empty()) {
-        snn_fast_kernel<true><<<dim3(grid_for((int64_t)fast.size(), 1)), dim3(64), 0, s>>>(
-            dGi.p, dGp.p, Rp.p, Rj.p, dfast.p, (int64_t)fast.size(), T.p, min_similarity, nullptr, doff.p, oi.p, ox.p);
-        NBCHK(hipGetLastError(), "snn_fast_kernel");
-    }
-    if (!slow.empty()) {
-        const int64_t ns = (int64_t)slow.size();
-        std::vector<int64_t> hsoff((size_t)ns + 1);
+    return csc_fill<int64_t>(s, n, p_out, *nnz_out, cap, "sgl_c_snn: output capacity %lld < %lld entries", i_out, x_out,
+                             [&](const int64_t* off, int32_t* oi, double* ox) -> int {
+        if (nfast > 0) {
+            snn_fast_kernel<true><<<dim3(grid_for(nfast, 1)), dim3(64), 0, s>>>(
+                dGi.p, dGp.p, Rp.p, Rj.p, wl.dfast.p, nfast, T.p, min_similarity, nullptr, off, oi, ox);
+            NBCHK(hipGetLastError(), "snn_fast_kernel");
+        }
+        if (nslow == 0) return SGL_OK;
+        std::vector<int64_t> hsoff((size_t)nslow + 1);
         hsoff[0] = 0;
-        for (int64_t w = 0; w < ns; ++w) hsoff[w + 1] = hsoff[w] + hcnt[slow[w]];
-        const int64_t stot = hsoff[ns];
+        for (int64_t w = 0; w < nslow; ++w) hsoff[w + 1] = hsoff[w] + hcnt[wl.slow[w]];
+        const int64_t stot = hsoff[nslow];
         DevBuf<int64_t> dsoff;
         DevBuf<int32_t> si, si2;
         DevBuf<double> sx, sx2;
-        SGLCHK(dsoff.alloc((size_t)ns + 1));
+        SGLCHK(upload(s, dsoff, hsoff.data(), hsoff.size(), "upload"));
         SGLCHK(si.alloc((size_t)stot));
         SGLCHK(si2.alloc((size_t)stot));
         SGLCHK(sx.alloc((size_t)stot));
         SGLCHK(sx2.alloc((size_t)stot));
-        NBCHK(hipMemcpyAsync(dsoff.p, hsoff.data(), sizeof(int64_t) * ((size_t)ns + 1), hipMemcpyHostToDevice, s), "upload");
-        snn_slow_kernel<true><<<dim3((unsigned)nslots), dim3(256), 0, s>>>(dGi.p, dGp.p, Rp.p, Rj.p, dslow.p, ns, n, counters.p,
+        snn_slow_kernel<true><<<dim3((unsigned)nslots), dim3(256), 0, s>>>(dGi.p, dGp.p, Rp.p, Rj.p, wl.dslow.p, nslow, n, counters.p,
                                                                          min_similarity, nullptr, dsoff.p, si.p, sx.p);
         NBCHK(hipGetLastError(), "snn_slow_kernel");
-        size_t tb = 0;
-        NBCHK(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, tb, si.p, si2.p, sx.p, sx2.p, (int)stot, (int)ns, dsoff.p, dsoff.p + 1,
-                                                          0, 32, s), "segmented sort");
-        DevBuf<char> tmp;
-        SGLCHK(tmp.alloc(tb));
-        NBCHK(hipcub::DeviceSegmentedRadixSort::SortPairs(tmp.p, tb, si.p, si2.p, sx.p, sx2.p, (int)stot, (int)ns, dsoff.p, dsoff.p + 1,
-                                                          0, 32, s), "segmented sort");
-        snn_scatter_kernel<<<dim3(grid_for(ns, 1)), dim3(256), 0, s>>>(si2.p, sx2.p, dsoff.p, dslow.p, ns, doff.p, oi.p, ox.p);
+        SGLCHK(cub_run([&](void* tmp, size_t& bytes) {
+            return hipcub::DeviceSegmentedRadixSort::SortPairs(tmp, bytes, si.p, si2.p, sx.p, sx2.p, (int)stot, (int)nslow, dsoff.p, dsoff.p + 1,
+                                                               0, 32, s);
+        }, "segmented sort"));
+        snn_scatter_kernel<<<dim3(grid_for(nslow, 1)), dim3(256), 0, s>>>(si2.p, sx2.p, dsoff.p, wl.dslow.p, nslow, off, oi, ox);
         NBCHK(hipGetLastError(), "snn_scatter_kernel");
         NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
-    }
-    if (nnz > 0) {
-        NBCHK(hipMemcpyAsync(i_out, oi.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download");
-        NBCHK(hipMemcpyAsync(x_out, ox.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download");
-    }
-    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
-    return SGL_OK;
+        return SGL_OK;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------- spatial_graph ---
@@ -935,38 +953,12 @@ struct SgArgs {
     int64_t K;               // min(max_k, n) >= 1
 };
 
-// Bucket key of every point, in double: by * W + bx, b = floor((c - cmin) / side); one bucket when W = H = 1 (an extent that
-// overflows).  See sgl_spatial_graph for why this is conservative.
-__global__ void sg_keys_kernel(const double* __restrict__ c1, const double* __restrict__ c2, int64_t n, double xmin, double ymin,
-                               double side, int64_t W, int64_t H, uint64_t* __restrict__ keys, uint32_t* __restrict__ iota) {
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-        int64_t bx = 0, by = 0;
-        if (W > 1) {   // the host's W, H hold every point: the clamps never bind
-            bx = std::min<int64_t>((int64_t)floor((c1[e] - xmin) / side), W - 1);
-            by = std::min<int64_t>((int64_t)floor((c2[e] - ymin) / side), H - 1);
-        }
-        keys[e] = (uint64_t)(by * W + bx);
-        iota[e] = (uint32_t)e;
-    }
-}
-
-// Coordinates in sorted order, and the bucket boundaries of the 3 x 3 neighbourhood of each sorted position.
-__global__ void sg_ranges_kernel(const uint64_t* __restrict__ skeys, const uint32_t* __restrict__ sidx, const double* __restrict__ c1,
-                                 const double* __restrict__ c2, int64_t n, int64_t W, int64_t H, double* __restrict__ sx,
-                                 double* __restrict__ sy, int32_t* __restrict__ bnd) {
+// Coordinates in sorted order.
+__global__ void sg_gather_kernel(const uint32_t* __restrict__ sidx, const double* __restrict__ c1, const double* __restrict__ c2, int64_t n,
+                                 double* __restrict__ sx, double* __restrict__ sy) {
     for (int64_t pos = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < n; pos += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t pt = sidx[pos];
-        sx[pos] = c1[pt];
-        sy[pos] = c2[pt];
-        const int64_t key = (int64_t)skeys[pos], by = key / W, bx = key % W;
-        for (int q = 0; q < 3; ++q) {
-            const int64_t yy = by - 1 + q;
-            for (int r = 0; r < 4; ++r) {
-                int64_t b = 0;
-                if (yy >= 0 && yy < H) b = lower_bound_u64(skeys, n, (uint64_t)(yy * W + std::min<int64_t>(std::max<int64_t>(bx - 1 + r, 0), W)));
-                bnd[pos * 12 + q * 4 + r] = (int32_t)b;
-            }
-        }
+        sx[pos] = c1[sidx[pos]];
+        sy[pos] = c2[sidx[pos]];
     }
 }
 
@@ -1125,86 +1117,35 @@ extern "C" int sgl_spatial_graph(const double* c1, const double* c2, int32_t n, 
         return SGL_OK;
     }
 
-    // --- spatial cell list.  Conservative prefilter: let d = fl(sqrt(fl(fl(dx*dx) + fl(dy*dy)))) < max_dist pass, with
-    // dx = fl(x1 - x2) (double, no contraction).  If |dx| < 2^-511, then |x1 - x2| < 2^-510 (a difference that rounds below
-    // 2^-511 is below it too, or subnormal and exact).  Otherwise dx*dx >= 2^-1022 is normal, so fl(dx*dx) >= dx^2 (1 - 2^-53);
-    // adding a non-negative fl(dy*dy) and taking the rounded root are monotone, each losing at most a factor (1 - 2^-53), so
-    // |dx| <= d (1 + 2^-51) and |x1 - x2| <= |dx| (1 + 2^-52) < max_dist (1 + 2^-50).  Either way |x1 - x2| < R =
-    // max(max_dist, 2^-510) (1 + 2^-50), and the same holds for y.  Buckets have side s >= max(max_dist, 2^-510) (1 + 2^-10),
-    // so |x1 - x2| / s < 1 - 2^-11.  The bucket coordinate u = fl(fl(x - xmin) / s) is off by at most 2^-52 u (+ 2^-1074 if
-    // the quotient is subnormal) <= 2^-21, since s is also raised so that u <= 2^30; so |u1 - u2| < 1 and floor(u1), floor(u2)
-    // differ by at most one: every pair the reference accepts lies in adjacent buckets, underflow of dx*dx included.  (An extent
-    // that overflows double is one bucket: every pair is a candidate.)
-    const double ext = std::max(xmax - xmin, ymax - ymin);
-    int64_t W = 1, H = 1;
-    double side = INFINITY;
-    if (ext < INFINITY) {
-        side = std::max(std::max(max_dist, ldexp(1.0, -510)) * (1.0 + ldexp(1.0, -10)), ext * ldexp(1.0, -30));
-        W = (int64_t)floor((xmax - xmin) / side) + 2;
-        H = (int64_t)floor((ymax - ymin) / side) + 2;
-    }
+    // --- spatial cell list, coordinates in sorted order
     DevBuf<double> d1, d2, sx, sy, colsum;
-    DevBuf<uint64_t> keys, skeys;
-    DevBuf<uint32_t> iota, sidx;
-    DevBuf<int32_t> bnd, cnt;
-    SGLCHK(d1.alloc((size_t)n));
-    SGLCHK(d2.alloc((size_t)n));
-    NBCHK(hipMemcpyAsync(d1.p, c1, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s), "upload of c1");
-    NBCHK(hipMemcpyAsync(d2.p, c2, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, s), "upload of c2");
-    SGLCHK(keys.alloc((size_t)n));
-    SGLCHK(skeys.alloc((size_t)n));
-    SGLCHK(iota.alloc((size_t)n));
-    SGLCHK(sidx.alloc((size_t)n));
-    sg_keys_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(d1.p, d2.p, n, xmin, ymin, side, W, H, keys.p, iota.p);
-    NBCHK(hipGetLastError(), "sg_keys_kernel");
-    int end_bit = 1;
-    while (end_bit < 64 && ((uint64_t)1 << end_bit) <= (uint64_t)(W * H)) ++end_bit;
-    {   // LSD radix sort is stable: each bucket's members stay in ascending index order
-        size_t tb = 0;
-        NBCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, iota.p, sidx.p, (int)n, 0, end_bit, s), "radix sort");
-        DevBuf<char> tmp;
-        SGLCHK(tmp.alloc(tb));
-        NBCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.p, skeys.p, iota.p, sidx.p, (int)n, 0, end_bit, s), "radix sort");
-    }
+    DevBuf<int32_t> cnt;
+    CellList cl;
+    SGLCHK(upload(s, d1, c1, (size_t)n, "upload of c1"));
+    SGLCHK(upload(s, d2, c2, (size_t)n, "upload of c2"));
+    SGLCHK(cell_list_build(s, d1.p, d2.p, n, cell_grid(xmin, xmax, ymin, ymax, max_dist, ldexp(1.0, -510)), cl, nullptr));
     SGLCHK(sx.alloc((size_t)n));
     SGLCHK(sy.alloc((size_t)n));
-    SGLCHK(bnd.alloc((size_t)n * 12));
-    sg_ranges_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(skeys.p, sidx.p, d1.p, d2.p, n, W, H, sx.p, sy.p, bnd.p);
-    NBCHK(hipGetLastError(), "sg_ranges_kernel");
+    sg_gather_kernel<<<dim3(grid_for(n, 256)), dim3(256), 0, s>>>(cl.sidx.p, d1.p, d2.p, n, sx.p, sy.p);
+    NBCHK(hipGetLastError(), "sg_gather_kernel");
 
     // --- count pass, scan, 2^31 check
     SGLCHK(cnt.alloc((size_t)n));
     SGLCHK(colsum.alloc((size_t)n));
-    const SgArgs a{sx.p, sy.p, sidx.p, bnd.p, n, max_dist, scale, K};
+    const SgArgs a{sx.p, sy.p, cl.sidx.p, cl.bnd.p, n, max_dist, scale, K};
     sg_merge_kernel<false><<<dim3(grid_for(n, 1)), dim3(64), 0, s>>>(a, cnt.p, colsum.p, nullptr, nullptr, nullptr);
     NBCHK(hipGetLastError(), "sg_merge_kernel (count)");
     std::vector<int32_t> hcnt((size_t)n);
-    NBCHK(hipMemcpyAsync(hcnt.data(), cnt.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s), "download of the counts");
+    SGLCHK(download(s, hcnt.data(), cnt.p, (size_t)n, "download of the counts"));
     NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
-    int64_t nnz = 0;
-    for (int64_t c = 0; c < n; ++c) nnz += hcnt[c];
-    if (nnz > INT32_MAX) {
-        sgl_set_error("spatial_graph: the graph would hold %lld entries, which a dgCMatrix (32-bit column pointers) cannot hold; "
-                      "lower max_dist or max_k", (long long)nnz);
-        return SGL_EINVAL;
-    }
-    p_out[0] = 0;
-    for (int64_t c = 0; c < n; ++c) p_out[c + 1] = p_out[c] + hcnt[c];
-    *nnz_out = nnz;
-    if (!i_out) return SGL_OK;
-    if (cap < nnz) { sgl_set_error("sgl_spatial_graph: output capacity %lld < %lld entries", (long long)cap, (long long)nnz); return SGL_EINVAL; }
+    SGLCHK(csc_pointers(hcnt, "spatial_graph: the graph would hold %lld entries, which a dgCMatrix (32-bit column pointers) cannot hold; "
+                              "lower max_dist or max_k", p_out, nnz_out));
 
     // --- fill pass
-    DevBuf<int32_t> doff, oi;
-    DevBuf<double> ox;
-    SGLCHK(doff.alloc((size_t)n + 1));
-    SGLCHK(oi.alloc((size_t)nnz));
-    SGLCHK(ox.alloc((size_t)nnz));
-    NBCHK(hipMemcpyAsync(doff.p, p_out, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s), "upload of p");
-    sg_merge_kernel<true><<<dim3(grid_for(n, 1)), dim3(64), 0, s>>>(a, nullptr, colsum.p, doff.p, oi.p, ox.p);
-    NBCHK(hipGetLastError(), "sg_merge_kernel (fill)");
-    NBCHK(hipMemcpyAsync(i_out, oi.p, sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download of i");
-    NBCHK(hipMemcpyAsync(x_out, ox.p, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, s), "download of x");
-    NBCHK(hipStreamSynchronize(s), "hipStreamSynchronize");
-    return SGL_OK;
+    return csc_fill<int32_t>(s, n, p_out, *nnz_out, cap, "sgl_spatial_graph: output capacity %lld < %lld entries", i_out, x_out,
+                             [&](const int32_t* off, int32_t* oi, double* ox) -> int {
+        sg_merge_kernel<true><<<dim3(grid_for(n, 1)), dim3(64), 0, s>>>(a, nullptr, colsum.p, off, oi, ox);
+        NBCHK(hipGetLastError(), "sg_merge_kernel (fill)");
+        return SGL_OK;
+    });
 }
