@@ -321,7 +321,9 @@ SGL_API int sgl_set_stream(sgl_ctx* ctx, void* hip_stream);
 /* Upload a shard: columns [cell_offset, cell_offset + ncol) of a genes x
  * ncells_total matrix.  At describes the same shard transposed (ncol x nrow,
  * row indices local to the shard); pass NULLs to have it built on the device.
- * Replaces the Rcpp::SparseMatrix views (inst/include/singlet.h:108-127). */
+ * Replaces the Rcpp::SparseMatrix views (inst/include/singlet.h:108-127).
+ * A refused or failed upload (any of the sgl_upload_* entries) leaves NO matrix
+ * resident, the previous one included: sgl_dims reports 0 / 0 / 0. */
 SGL_API int sgl_upload_csc(sgl_ctx* ctx, const double* Ax, const int32_t* Ai, const int32_t* Ap,
                    const double* Atx, const int32_t* Ati, const int32_t* Atp,
                    int32_t nrow, int32_t ncol, int64_t cell_offset, int64_t ncells_total);

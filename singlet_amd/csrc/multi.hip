@@ -1148,7 +1148,14 @@ extern "C" int sgl_multi_upload_csc(sgl_multi* M, const double* Ax, const int32_
         p.resize((size_t)(hi - lo) + 1);
         for (int64_t q = lo; q <= hi; ++q) p[(size_t)(q - lo)] = Ap[q] - Ap[lo];
         // transposes are built on the device (the host's t(A) describes the whole matrix, not a block)
-        SGLCHK(sgl_upload_csc(M->local[r], Ax + Ap[lo], Ai + Ap[lo], p.data(), nullptr, nullptr, nullptr, nrow, (int32_t)(hi - lo), lo, ncol));
+        const int rc = sgl_upload_csc(M->local[r], Ax + Ap[lo], Ai + Ap[lo], p.data(), nullptr, nullptr, nullptr, nrow, (int32_t)(hi - lo), lo, ncol);
+        if (rc != SGL_OK) {   // one rank refused its block: no rank keeps a matrix, and the team's guards (cell_lo) say so
+            for (auto c : M->local) sgl_matrix_clear(c);
+            M->cell_lo.clear();
+            M->nrow = 0;
+            M->ncells_total = 0;
+            return rc;
+        }
     }
     return SGL_OK;
 }

@@ -409,6 +409,7 @@ int k_link_mul(hipStream_t s, double* B, const double* L, int k, int link_rows, 
 int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, double* out);
 int k_raster_dense(hipStream_t s, const double* A, int64_t nrow, int64_t ncol, int64_t n, int64_t nb, double* out);
 // upload of A alone (an empty At) validating the structure only, the values as they are (singlet_hip.hip)
+void sgl_matrix_clear(sgl_ctx* c);   // drops the fit and the resident matrix (the team upload, after one rank refused)
 int sgl_upload_A_structure(sgl_ctx* c, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol);
 
 // graph convolution (kernels_graph.hip): Y = X G, X and Y k x n column-major (Y must not alias X)

@@ -199,6 +199,26 @@ static void free_matrix(sgl_ctx* c) {
     c->dense_input = false;
 }
 
+// A refused or failed upload leaves no matrix resident: the doors allocate the slots and set the dimensions before the
+// validator has spoken, so every failure after their first free_matrix comes back through here (the stream is drained
+// first: a copy or a kernel may still be writing the slots).  sgl_dims then reports 0 / 0 / 0.
+static int drop_matrix(sgl_ctx* c, int rc) {
+    (void)hipStreamSynchronize(c->stream);
+    free_matrix(c);
+    return rc;
+}
+void sgl_matrix_clear(sgl_ctx* c) {
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    free_fit(c);
+    free_matrix(c);
+}
+#define UPLOADCHK(c, expr)                                 \
+    do {                                                   \
+        int r__ = (expr);                                  \
+        if (r__ != SGL_OK) return drop_matrix((c), r__);   \
+    } while (0)
+
 #define CTX_GUARD(c)                                                 \
     do {                                                             \
         if ((c) == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; } \
@@ -420,17 +440,18 @@ extern "C" int sgl_upload_csc(sgl_ctx* c, const double* Ax, const int32_t* Ai, c
     free_matrix(c);
     c->cell_offset = cell_offset;
     c->ncells_total = ncells_total > 0 ? ncells_total : ncol;
-    SGLCHK(upload_one(c, c->A, Ax, Ai, Ap, nrow, ncol));
+    UPLOADCHK(c, upload_one(c, c->A, Ax, Ai, Ap, nrow, ncol));
     if (Atx) {
-        if ((int64_t)Atp[nrow] != c->A.nnz) { sgl_set_error("At has %d non-zeros, A has %lld", Atp[nrow], (long long)c->A.nnz); return SGL_EINVAL; }
-        SGLCHK(upload_one(c, c->At, Atx, Ati, Atp, ncol, nrow));
+        if ((int64_t)Atp[nrow] != c->A.nnz) { sgl_set_error("At has %d non-zeros, A has %lld", Atp[nrow], (long long)c->A.nnz); return drop_matrix(c, SGL_EINVAL); }
+        UPLOADCHK(c, upload_one(c, c->At, Atx, Ati, Atp, ncol, nrow));
     } else {
         const double t0 = wall_now();
-        SGLCHK(sgl_device_transpose(c));
-        HIPCHK(hipStreamSynchronize(c->stream));
+        UPLOADCHK(c, sgl_device_transpose(c));
+        if (hipStreamSynchronize(c->stream) != hipSuccess) { sgl_set_error("sgl_upload_csc: HIP call failed after the transpose"); return drop_matrix(c, SGL_EHIP); }
         g_times.transpose_s += wall_now() - t0;
     }
-    return finish_matrix(c);
+    UPLOADCHK(c, finish_matrix(c));
+    return SGL_OK;
 }
 
 extern "C" int sgl_upload_csc_list(sgl_ctx* c, int32_t n_chunks, const double* const* Ax, const int32_t* const* Ai,
@@ -442,20 +463,21 @@ extern "C" int sgl_upload_csc_list(sgl_ctx* c, int32_t n_chunks, const double* c
     if (n_t_chunks > 0 && (!Atx || !Ati || !Atp || !t_chunk_ncol)) { sgl_set_error("sgl_upload_csc_list: incomplete At chunk list"); return SGL_EINVAL; }
     free_fit(c);
     free_matrix(c);
-    SGLCHK(upload_chunks(c, c->A, n_chunks, Ax, Ai, Ap, chunk_ncol, nrow));
+    UPLOADCHK(c, upload_chunks(c, c->A, n_chunks, Ax, Ai, Ap, chunk_ncol, nrow));
     c->cell_offset = cell_offset;
     c->ncells_total = ncells_total > 0 ? ncells_total : c->A.ncol;
     if (n_t_chunks > 0) {
-        SGLCHK(upload_chunks(c, c->At, n_t_chunks, Atx, Ati, Atp, t_chunk_ncol, c->A.ncol));
+        UPLOADCHK(c, upload_chunks(c, c->At, n_t_chunks, Atx, Ati, Atp, t_chunk_ncol, c->A.ncol));
         if (c->At.ncol != nrow || c->At.nnz != c->A.nnz) {
             sgl_set_error("At list describes a %d-column matrix with %lld non-zeros; t(A) has %d columns and %lld", c->At.ncol,
                           (long long)c->At.nnz, nrow, (long long)c->A.nnz);
-            return SGL_EINVAL;
+            return drop_matrix(c, SGL_EINVAL);
         }
     } else {
-        SGLCHK(sgl_device_transpose(c));
+        UPLOADCHK(c, sgl_device_transpose(c));
     }
-    return finish_matrix(c);
+    UPLOADCHK(c, finish_matrix(c));
+    return SGL_OK;
 }
 
 // A only (c_project_model never walks At): At becomes an empty nrow-column matrix.
@@ -467,14 +489,15 @@ static int sgl_upload_csc_A_only(sgl_ctx* c, const double* Ax, const int32_t* Ai
     free_matrix(c);
     c->cell_offset = 0;
     c->ncells_total = ncol;
-    SGLCHK(upload_one(c, c->A, Ax, Ai, Ap, nrow, ncol, check_finite));
+    UPLOADCHK(c, upload_one(c, c->A, Ax, Ai, Ap, nrow, ncol, check_finite));
     DevCSC& T = c->At;
     T.nrow = ncol; T.ncol = nrow; T.nnz = 0;
-    SGLCHK(dev_alloc(&T.x, 1));
-    SGLCHK(dev_alloc(&T.i, 1));
-    SGLCHK(dev_alloc(&T.p, (size_t)nrow + 1));
-    HIPCHK(hipMemsetAsync(T.p, 0, sizeof(int64_t) * ((size_t)nrow + 1), c->stream));
-    return finish_matrix(c);
+    UPLOADCHK(c, dev_alloc(&T.x, 1));
+    UPLOADCHK(c, dev_alloc(&T.i, 1));
+    UPLOADCHK(c, dev_alloc(&T.p, (size_t)nrow + 1));
+    if (hipMemsetAsync(T.p, 0, sizeof(int64_t) * ((size_t)nrow + 1), c->stream) != hipSuccess) { sgl_set_error("upload: HIP call failed"); return drop_matrix(c, SGL_EHIP); }
+    UPLOADCHK(c, finish_matrix(c));
+    return SGL_OK;
 }
 
 int sgl_upload_A_structure(sgl_ctx* c, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol) {
@@ -545,8 +568,9 @@ extern "C" int sgl_upload_dense(sgl_ctx* c, const double* A, int32_t nrow, int32
     double* dev = nullptr;
     SGLCHK(dev_alloc(&dev, tot));
     c->Adense = dev;
-    HIPCHK(hipMemcpyAsync(dev, A, sizeof(double) * tot, hipMemcpyHostToDevice, c->stream));
-    return ingest_dense(c, dev, nrow, ncol, "sgl_upload_dense");
+    if (hipMemcpyAsync(dev, A, sizeof(double) * tot, hipMemcpyHostToDevice, c->stream) != hipSuccess) { sgl_set_error("sgl_upload_dense: HIP call failed"); return drop_matrix(c, SGL_EHIP); }
+    UPLOADCHK(c, ingest_dense(c, dev, nrow, ncol, "sgl_upload_dense"));
+    return SGL_OK;
 }
 
 extern "C" int sgl_synth_csc(sgl_ctx* c, uint64_t S, uint64_t inv_density, const double* levels16, int32_t ngenes,
@@ -685,7 +709,8 @@ extern "C" int sgl_rasterize_rowwise(sgl_ctx* c, int64_t n) {
     c->dense_input = true;
     c->cell_offset = 0;
     c->ncells_total = ncol;
-    return ingest_dense(c, R, (int32_t)nb, ncol, "sgl_rasterize_rowwise");
+    UPLOADCHK(c, ingest_dense(c, R, (int32_t)nb, ncol, "sgl_rasterize_rowwise"));
+    return SGL_OK;
 }
 
 extern "C" int sgl_weight_by_split(sgl_ctx* c, const int32_t* split_by, int32_t n_groups) {
