@@ -5,7 +5,8 @@
  * R/FindLocalNeighbors.R:95-98 and singlet:::spatial_graph work unchanged.  They need two R API pieces the main shim does not: the string of
  * `metric`, and a new Matrix::dgCMatrix object for the result.
  *
- * Not compiled in this repository's CI (no R here); build it together with singlet_hip_shim.c.
+ * Compiled and executed here against the emulated R C API of tests/r_emul/ together with singlet_hip_shim.c (see its header;
+ * tests/test_r_shim_emulated.py, tests/test_gpu_r_shim.py); a build against R's own headers remains unverified.
  */
 #include <R.h>
 #include <Rinternals.h>
@@ -126,7 +127,8 @@ SEXP _singlet_c_SNN(SEXP G_, SEXP min_similarity_, SEXP threads_) {
     a.p = INTEGER(p);
     a.nrow = INTEGER(dim)[0];
     a.ncol = INTEGER(dim)[1];
-    if (XLENGTH(p) != (R_xlen_t)a.ncol + 1) Rf_error("G: not a dgCMatrix (length(p) != ncol + 1)");
+    if (a.ncol < 0 || XLENGTH(p) != (R_xlen_t)a.ncol + 1) Rf_error("G: not a dgCMatrix (length(p) != ncol + 1)");
+    if ((R_xlen_t)a.p[a.ncol] > XLENGTH(i)) Rf_error("G: not a dgCMatrix (p[ncol] > length(i))");   /* the library reads p[ncol] entries of i */
     a.min_similarity = Rf_asReal(min_similarity_);
     return graph_result(snn_call, &a, a.ncol);
 }

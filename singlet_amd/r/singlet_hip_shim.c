@@ -12,13 +12,15 @@
  * allocates the result objects, and forwards to libsinglet_hip.so
  * (include/singlet_hip.h).  It uses the plain R C API only: no Rcpp, no Eigen.
  *
- * NOT COMPILED IN THIS REPOSITORY'S CI: the build image has neither R nor its
- * headers.  Build where R exists with
+ * The build image has neither R nor its headers.  This file and singlet_hip_graph_shim.c are compiled, unmodified, against
+ * an emulation of the R C API subset they use (tests/r_emul/: objects, protect stack, a collector that runs at every
+ * allocation, Rf_error / interrupts as long jumps, .Call through the table below), and every entry is executed:
+ * tests/test_r_shim_emulated.py (no device: every refusal raised before the library) and tests/test_gpu_r_shim.py (all 16
+ * entries on the GPU, bit for bit against the Python mirror and against the oracle; result layout, protect balance,
+ * library errors and interrupts).  A build against R's own headers remains unverified here; make it where R exists with
  *     R CMD SHLIB -o singlet_hip_shim.so singlet_hip_shim.c singlet_hip_graph_shim.c -I<repo>/include \
  *         -L<repo>/singlet_amd -lsinglet_hip
- * (or add the file to the package's src/ and the two flags to src/Makevars;
- * see INTEGRATION.md).  All numerical testing of the library goes through the
- * same C ABI from Python (tests/).
+ * (or add the file to the package's src/ and the two flags to src/Makevars).
  */
 #include <R.h>
 #include <Rinternals.h>
@@ -52,6 +54,10 @@ static dgc_view view_dgc(SEXP s, const char* what) {
     v.p = INTEGER(p);
     v.nrow = INTEGER(dim)[0];
     v.ncol = INTEGER(dim)[1];
+    /* the library reads p[0..ncol] and p[ncol] entries of i and x from these host vectors; only here are their lengths known */
+    if (v.ncol < 0 || XLENGTH(p) != (R_xlen_t)v.ncol + 1) Rf_error("%s: not a dgCMatrix (length(p) != ncol + 1)", what);
+    if (XLENGTH(i) != XLENGTH(x)) Rf_error("%s: not a dgCMatrix (length(i) != length(x))", what);
+    if ((R_xlen_t)v.p[v.ncol] > XLENGTH(x)) Rf_error("%s: not a dgCMatrix (p[ncol] > length(x))", what);
     return v;
 }
 
