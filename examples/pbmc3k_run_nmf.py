@@ -4,6 +4,8 @@ PreprocessData (LogNormalize, on the device) -> run_nmf(rank = 10) -> project_mo
 libsinglet_hip.so.  Needs an MI355X.
 
   python examples/pbmc3k_run_nmf.py
+  python examples/pbmc3k_run_nmf.py features     the same fit on the 2 000 genes with the most non-zeros, through RunNMF:
+                                                 normalise, subset and fit on one resident matrix
 """
 import os
 import sys
@@ -31,3 +33,14 @@ print("run_nmf(rank=10): %d iterations in %.3f s, d = %s" % (fit["iter"], dt, np
 proj = sa.project_model(A, fit["w"])
 print("project_model: h is %d x %d, relative change vs the fit's h: %.2e"
       % (proj["h"].shape[0], proj["h"].shape[1], np.linalg.norm(proj["h"] - fit["h"]) / np.linalg.norm(fit["h"])))
+
+if "features" in sys.argv[1:]:
+    with sa.Context(0) as ctx:                        # non-zeros per gene, counted on the device
+        ctx.upload(counts, None)
+        per_gene = ctx.col_counts(1)
+    features = np.argsort(-per_gene, kind="stable")[:2000]
+    t0 = time.perf_counter()
+    sub = sa.RunNMF(counts, k=10, features=features, tol=1e-4, maxit=100, verbose=0, L1=0.01, seed=123)
+    dt = time.perf_counter() - t0
+    print("RunNMF(k=10, features = the 2000 genes with the most non-zeros): w is %d x %d, %d iterations in %.3f s, d = %s"
+          % (sub["w"].shape[0], sub["w"].shape[1], sub["iter"], dt, np.round(sub["d"], 1)))

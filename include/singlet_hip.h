@@ -410,6 +410,30 @@ SGL_API int sgl_c_rowwise_compress_dense(const double* A, int32_t nrow, int32_t 
  * sum that overflows) is refused like sgl_upload_dense refuses one, and then no matrix stays resident. */
 SGL_API int sgl_rasterize_rowwise(sgl_ctx* ctx, int64_t n);
 
+/* Subset of the resident matrix by features and cells: R's A[features, ] of RunNMF.Seurat (R/RunNMF.R:72-81, after the
+ * normalisation, before weight_by_split) and the gene alignment of ProjectData.Seurat (R/ProjectData.R:68-69), without
+ * the matrix leaving the device.  The resident A (nrow x ncol) is replaced by A' with A'[r', c'] = A[rows[r'], cols[c']]:
+ *  - indices are 0-based, in any order, duplicates allowed (R's A[c(3, 1, 3), ]).  rows == NULL keeps all rows (n_rows is
+ *    ignored), cols == NULL all columns (n_cols is ignored); both NULL is a no-op that still drops a running fit.
+ *  - data movement only: the stored values move bit for bit, explicit zeros stay stored, nothing is validated for
+ *    finiteness again.  Both orientations end up exactly as sgl_upload_csc(..., At = NULL) leaves the host-side subset:
+ *    row indices strictly ascending within every column of A' and of t(A'), 64-bit offsets.  (A column gather of one
+ *    orientation -- cols on A, rows on t(A) -- and the device transpose for the other: one transpose for one list, two
+ *    for both.  The old images are freed before the transpose allocates.)
+ *  - afterwards: a running fit is dropped, and with it the entry streams, mask lists, graph, links and tiling segments,
+ *    as when the matrix changes by any other door; the per-column counts are those of A'; cell_offset = 0 and
+ *    ncells_total = the new ncol.  A dense copy kept by sgl_upload_dense is released (as sgl_log_normalize releases it);
+ *    the matrix still counts as dense input, so sgl_set_graph stays refused.  A result without a stored entry is
+ *    resident like the empty-but-shaped matrix sgl_upload_csc accepts.
+ *  - refused with the matrix and a running fit untouched: SGL_ESTATE with no matrix resident, on a team member or with
+ *    an all-reduce hook set (the gene-side images would differ across shards), or on a context that holds a shard
+ *    (cell_offset != 0 or ncells_total != ncol); SGL_EINVAL for a non-NULL list with n == 0 (a resident matrix cannot be
+ *    empty) or n > INT32_MAX, and for an index outside [0, nrow) / [0, ncol) -- the message names the list, the
+ *    position and the value of the first offender.  Both lists are checked completely before anything is freed.
+ *  - after that only an allocation or a HIP call can fail, and then no matrix stays resident (sgl_dims: 0 / 0 / 0), as
+ *    after a failed upload. */
+SGL_API int sgl_subset(sgl_ctx* ctx, const int32_t* rows, int64_t n_rows, const int32_t* cols, int64_t n_cols);
+
 /* Start a fit at rank k.  w_init: k x nrow host array, or NULL to fill W on
  * the device with the synthetic init ((rand_{S+2}(f,g) >> 11) + 0.5) * 2^-53.
  * h = 0, d = 1 as in src/singlet.cpp:639-641.
@@ -417,7 +441,7 @@ SGL_API int sgl_rasterize_rowwise(sgl_ctx* ctx, int64_t n);
  * of times, R/ard_nmf.R:95-160): the re-blocked entry streams of the matrix (2 x ~15 bytes per non-zero at
  * k <= 128, + 8 per non-zero once a masked fit has run) are kept between fits -- a fit at an unchanged rank reuses
  * them as they are, another rank rebuilds them in the same allocations -- and are released when the matrix changes
- * (upload, synth, log-normalize, weight_by_split) or the context is destroyed. */
+ * (upload, synth, log-normalize, weight_by_split, rasterize, subset) or the context is destroyed. */
 SGL_API int sgl_fit_init(sgl_ctx* ctx, int32_t k, const double* w_init, uint64_t synth_seed);
 
 /* Link matrices of c_linked_nmf for the current fit (after sgl_fit_init; the

@@ -75,6 +75,7 @@ SIGNATURES = {
     "sgl_c_rowwise_compress_sparse": (C.c_int, _CSC + [C.c_int32, C.c_int32, C.c_int64, f64p]),
     "sgl_c_rowwise_compress_dense": (C.c_int, [f64p, C.c_int32, C.c_int32, C.c_int64, f64p]),
     "sgl_rasterize_rowwise": (C.c_int, [C.c_void_p, C.c_int64]),
+    "sgl_subset": (C.c_int, [C.c_void_p, i32p, C.c_int64, i32p, C.c_int64]),
     "sgl_c_project_model": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                              C.c_uint16, f64p, f64p]),
     "sgl_rcpp_predict": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,

@@ -16,6 +16,7 @@ names, argument order, defaults and return fields:
   cross_validate_nmf                    R/cross_validate_nmf.R:18-105
   GetBestRank                           R/GetBestRank.R:8-46
   project_model                         R/ProjectData.R:11-19
+  RunNMF (matrix steps), subset         R/RunNMF.R:61-151; A[features, ] (:72-81), R/ProjectData.R:68-69
 
 Matrices follow R's orientation: w is returned k x m by c_nmf and m x k by
 run_nmf / ard_nmf (they transpose and sort by d, R/run_nmf.R:65-68); h is
@@ -335,9 +336,16 @@ def _sort_model(model, rn=None, cn=None):
     return model
 
 
-def run_nmf(A, rank, tol=1e-4, maxit=100, verbose=True, L1=0.01, L2=0, threads=0, seed=None):
+def run_nmf(A, rank, tol=1e-4, maxit=100, verbose=True, L1=0.01, L2=0, threads=0, seed=None, _fits=None):
     """R/run_nmf.R:18-77 (sparse, single-matrix branch).  `seed` replaces R's global RNG state
     (stats::runif, l.55): an int or numpy Generator."""
+    if _fits is not None:   # RunNMF: the matrix is staged and resident already (A is not read)
+        if verbose:
+            print("running with sparse optimization")
+        L1, L2 = _pair(L1), _pair(L2)
+        w_init = _rng(seed).random((_fits.nrow, rank)).T
+        model = _fits.c_nmf(tol, maxit, bool(verbose), L1[0], L1[1], L2[0], L2[1], threads, w_init)
+        return _sort_model(model, _fits.Dimnames[0], _fits.Dimnames[1])
     dense_mode = isinstance(A, np.ndarray)   # R/run_nmf.R:41-46: a base matrix stays dense
     if not dense_mode:
         A = as_dgCMatrix(A)
@@ -420,24 +428,83 @@ def run_gcnmf(A, graph, k, split_by=None, tol=1e-5, L1=0.01, L2=0, verbose=2, ma
     return model
 
 
-def _staged(A, op):
-    """Upload A, run a staging operator on the device, return the transformed dgCMatrix."""
+def _staged(A, op, Dimnames=None):
+    """Upload A, run a staging operator on the device, return the transformed dgCMatrix (Dimnames: those of the result
+    when the operator changes the shape)."""
     from .context import Context
     A = as_dgCMatrix(A)
     c = Context(0)
     try:
         c.upload(A, None)
         op(c)
+        nrow, ncol, _ = c.dims()
         x, i, p = c.download(0)
     finally:
         c.close()
-    return dgCMatrix(x, i, p.astype(np.int32), A.Dim, A.Dimnames)
+    return dgCMatrix(x, i, p.astype(np.int32), (nrow, ncol), A.Dimnames if Dimnames is None else Dimnames)
 
 
 def PreprocessData(A, scale_factor=10000.0):
     """PreprocessData.dgCMatrix (R/PreprocessData.R:34-39): Seurat::LogNormalize of a counts matrix,
     log1p(x / colSums * scale_factor), computed on the device; dimnames kept."""
     return _staged(A, lambda c: c.log_normalize(scale_factor))
+
+
+def _subset_index(sel, extent, names, what):
+    """One axis of a subset as the library takes it: None, or a contiguous int32 array of 0-based indices.  sel: 0-based
+    integers (any order, duplicates allowed), a boolean mask of the axis length, or names looked up in `names` (the
+    first match, as R's `[` does).  R's negative "drop" indices are not mirrored: they raise."""
+    if sel is None:
+        return None
+    a = np.asarray(sel)
+    if a.ndim != 1:
+        raise ValueError("subset: %s must be one-dimensional" % what)
+    if a.size == 0:
+        raise ValueError("subset: %s selects nothing (a matrix cannot be empty)" % what)
+    if a.dtype == np.bool_:
+        if a.shape[0] != extent:
+            raise ValueError("subset: the boolean mask for %s has %d entries, the axis has %d" % (what, a.shape[0], extent))
+        idx = np.flatnonzero(a)
+    elif a.dtype.kind in "USO" and a.size and all(isinstance(v, (str, bytes, np.str_)) for v in a.tolist()):
+        if names is None:
+            raise ValueError("subset: %s are given by name, but that axis of A has no names" % what)
+        first = {}
+        for q, nm in enumerate(names):
+            first.setdefault(nm, q)
+        missing = [v for v in a.tolist() if v not in first]
+        if missing:
+            raise ValueError("subset: %d of the %s are not among the names of A (first: %r)" % (len(missing), what, missing[0]))
+        idx = np.array([first[v] for v in a.tolist()], dtype=np.int64)
+    elif a.dtype.kind in "iu":
+        idx = a.astype(np.int64)
+        if idx.size and int(idx.min()) < 0:
+            raise ValueError("subset: negative index %d in %s (indices are 0-based; R's negative 'drop' indices are not "
+                             "supported)" % (int(idx.min()), what))
+        if idx.size and int(idx.max()) >= extent:
+            raise ValueError("subset: index %d in %s is outside [0, %d)" % (int(idx.max()), what, extent))
+    else:
+        raise ValueError("subset: %s must be 0-based integers, a boolean mask or names" % what)
+    if idx.size == 0:
+        raise ValueError("subset: %s selects nothing (a matrix cannot be empty)" % what)
+    return np.ascontiguousarray(idx, dtype=np.int32)
+
+
+def _subset_names(names, idx):
+    if names is None or idx is None:
+        return names
+    return [names[int(q)] for q in idx]
+
+
+def subset(A, rows=None, cols=None):
+    """A[rows, cols] computed on the device (sgl_subset): the A[features, ] of RunNMF.Seurat (R/RunNMF.R:72-81) and the
+    gene alignment of ProjectData.Seurat (R/ProjectData.R:68-69).  rows / cols: 0-based integers in any order (duplicates
+    allowed), a boolean mask of the axis length, names looked up in A.Dimnames, or None to keep the axis.  Returns a
+    dgCMatrix with the selected Dimnames; the stored values, explicit zeros included, move bit for bit."""
+    A = as_dgCMatrix(A)
+    r = _subset_index(rows, A.nrow, A.Dimnames[0], "rows")
+    c = _subset_index(cols, A.ncol, A.Dimnames[1], "cols")
+    names = (_subset_names(A.Dimnames[0], r), _subset_names(A.Dimnames[1], c))
+    return _staged(A, lambda ctx: ctx.subset(r, c), names)
 
 
 def weight_by_split(A_, split_by, n_groups):
@@ -552,18 +619,29 @@ class _ResidentFits:
     R/cross_validate_nmf.R:69-97), without re-uploading, re-transposing and re-validating it per call.
     Same arguments and return lists as c_ard_nmf / c_nmf; results are identical to the one-shot calls."""
 
-    def __init__(self, A, device=0):
+    def __init__(self, A, device=0, ctx=None, Dimnames=(None, None)):
+        """ctx: an already staged Context to adopt instead of uploading A (RunNMF); it stays the caller's to close, and
+        Dimnames are the names of its resident matrix."""
         from .context import Context
-        self.A = as_dgCMatrix(A)
+        self._adopted = ctx is not None
+        if self._adopted:
+            self.ctx = ctx
+            self.nrow = ctx.dims()[0]
+            self.Dimnames = tuple(Dimnames)
+            return
+        A = as_dgCMatrix(A)
+        self.nrow = A.nrow
+        self.Dimnames = A.Dimnames
         self.ctx = Context(device)
         try:
-            self.ctx.upload(self.A, None)
+            self.ctx.upload(A, None)
         except Exception:
             self.ctx.close()
             raise
 
     def close(self):
-        self.ctx.close()
+        if not self._adopted:
+            self.ctx.close()
 
     def __enter__(self):
         return self
@@ -572,7 +650,7 @@ class _ResidentFits:
         self.close()
 
     def c_ard_nmf(self, tol, maxit, verbose, L1, L2, threads, w, seed, inv_density, overfit_threshold, trace_test_mse):
-        wb = _w_in(w, self.A.nrow)
+        wb = _w_in(w, self.nrow)
         k = wb.shape[1]
         self.ctx.fit_init(k, wb)
         r = self.ctx.ard_run(float(tol), int(maxit), L1, L2, int(seed), int(inv_density), float(overfit_threshold),
@@ -582,7 +660,7 @@ class _ResidentFits:
                 "score_overfit": r["score_overfit"]}
 
     def c_nmf(self, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w):
-        wb = _w_in(w, self.A.nrow)
+        wb = _w_in(w, self.nrow)
         k = wb.shape[1]
         self.ctx.fit_init(k, wb)
         n_iter, tr = self.ctx.nmf_run(float(tol), int(maxit), L1_w, L1_h, L2_w, L2_h, log=_verbose_log(verbose))
@@ -736,7 +814,7 @@ def GetBestRank(df, tol_overfit=1e-4):
 
 def ard_nmf(A, k_init=2, k_max=100, k_min=2, n_replicates=1, tol=1e-5, cv_tol=1e-4, maxit=100, verbose=1, L1=0.01,
             L2=0, threads=0, test_density=0.05, learning_rate=1, tol_overfit=1e-3, trace_test_mse=1, seed=None,
-            resident=True):
+            resident=True, _fits=None):
     """R/ard_nmf.R:31-193: automatic rank search, then the final fit -- all three input branches: one dgCMatrix
     (:82-85), a list of dgCMatrix column chunks (:45-76 -> c_*_sparse_list), a dense matrix (:79-86 -> c_*_dense).
     resident = True keeps a single dgCMatrix in HBM across all fits of the search (False, and always for the list and
@@ -747,8 +825,10 @@ def ard_nmf(A, k_init=2, k_max=100, k_min=2, n_replicates=1, tol=1e-5, cv_tol=1e
         k_init = k_min
     if k_min < 2:
         raise ValueError("k_min cannot be less than 2")
-    kind, A = _classify_input(A)
-    if kind == "list":
+    kind, A = ("staged", None) if _fits is not None else _classify_input(A)
+    if kind == "staged":   # RunNMF: the matrix is staged and resident already
+        nrow, (rn, cn), fits = _fits.nrow, _fits.Dimnames, _fits
+    elif kind == "list":
         nrow = A[0].nrow
         rn = A[0].Dimnames[0]
         cns = [c.Dimnames[1] for c in A]
@@ -772,7 +852,7 @@ def ard_nmf(A, k_init=2, k_max=100, k_min=2, n_replicates=1, tol=1e-5, cv_tol=1e
         return _ard_nmf_search(fits, (rn, cn), df, w_init, test_seed, inv_density, k_init, k_max, k_min, n_replicates, tol, cv_tol,
                                maxit, verbose, L1, L2, threads, learning_rate, tol_overfit, trace_test_mse)
     finally:
-        fits.close()
+        fits.close()   # (an adopted context stays open: _ResidentFits.close)
 
 
 def _ard_nmf_search(fits, dimnames, df, w_init, test_seed, inv_density, k_init, k_max, k_min, n_replicates, tol, cv_tol, maxit,
@@ -879,7 +959,8 @@ def _run_grid_on_replicas(A, devices, jobs, run):
 
 
 def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1, L1=0.01, L2=0, threads=0,
-                       test_density=0.05, tol_overfit=1e-4, trace_test_mse=5, seed=None, resident=True, devices=None):
+                       test_density=0.05, tol_overfit=1e-4, trace_test_mse=5, seed=None, resident=True, devices=None,
+                       _fits=None):
     """R/cross_validate_nmf.R:18-105 -> cv table with k, rep, test_error, iter, tol; one dgCMatrix, a list of dgCMatrix
     column chunks (:27-50 -> c_ard_nmf_sparse_list) or a dense matrix (:57-60 -> c_ard_nmf_dense).
     resident = True keeps a single dgCMatrix in HBM across the whole (rank, replicate) grid.  devices (a list, a count, or
@@ -887,8 +968,11 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
     resident copy of A (BASELINE config 5 on one node); the table is the one-device table, row for row."""
     if L1 >= 1:
         raise ValueError("L1 penalty must be strictly in the range (0, 1]")
-    kind, A = _classify_input(A)
-    nrow = A[0].nrow if kind == "list" else (A.shape[0] if kind == "dense" else A.nrow)
+    if _fits is not None:   # RunNMF: the matrix is staged and resident already (A is not read)
+        kind, nrow = "sparse", _fits.nrow
+    else:
+        kind, A = _classify_input(A)
+        nrow = A[0].nrow if kind == "list" else (A.shape[0] if kind == "dense" else A.nrow)
     ranks = [int(r) for r in np.atleast_1d(ranks)]
     rng = _rng(seed)
     w_init = [rng.random((nrow, max(ranks))).T for _ in range(n_replicates)]
@@ -913,11 +997,11 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
         for k, rep in grid:
             rows(k, rep, fit(fits, (k, rep)))
         return df2
-    if resident and len(devs) > 1:
+    if _fits is None and resident and len(devs) > 1:
         for (k, rep), model in zip(grid, _run_grid_on_replicas(A, devs, grid, fit)):
             rows(k, rep, model)
         return df2
-    fits = _ResidentFits(A, devs[0]) if resident else _OneShotFits(A)
+    fits = _fits if _fits is not None else (_ResidentFits(A, devs[0]) if resident else _OneShotFits(A))
     try:
         for q, (k, rep) in enumerate(grid):
             if verbose > 1:
@@ -931,6 +1015,81 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
     finally:
         fits.close()
     return df2
+
+
+def RunNMF(A, k=None, features=None, split_by=None, reps=3, tol=1e-5, L1=0.01, L2=0, verbose=2, maxit=100, test_density=0.05,
+           learning_rate=0.8, tol_overfit=1e-4, trace_test_mse=5, threads=0, seed=None):
+    """The matrix steps of RunNMF.Seurat (R/RunNMF.R:61-151) on a genes x cells matrix, without the Seurat object, on ONE
+    resident context -- the matrix is uploaded once and never comes back between the steps:
+      1. LogNormalize when every value is integral (sum(as.integer(v)) == sum(v), l.66-69);
+      2. A <- A[features, ] (l.72-81): `features` as subset() takes rows -- 0-based integers, names or a mask; the
+         "var.features" of a Seurat object are the caller's to pass;
+      3. weight_by_split when `split_by` (one label per cell, any type) is given (l.86-97);
+      4. k a vector: cross_validate_nmf at tol * 10, GetBestRank, the final run_nmf (l.101-125); k None: ard_nmf with
+         k_max = 1e4 (l.126-145), clipped to the library's rank limit of 1024; k a scalar: run_nmf (l.146-148).
+    `seed` (an int or numpy Generator) replaces R's global RNG state: one stream, drawn from by the drivers in the order
+    they run, each exactly as it draws for a matrix of the subset's shape.  Returns the model of the driver it
+    dispatched to (w m x k, d, h k x n, names) plus "cv_data" (empty for a scalar k)."""
+    from .context import Context
+    A = as_dgCMatrix(A)
+    rn, cn = A.Dimnames
+    rows = None
+    if features is not None:
+        if isinstance(features, str):
+            if features == "var.features":
+                raise ValueError("features = 'var.features' reads a Seurat object's variable features: pass them as names or indices")
+            features = [features]
+        rows = _subset_index(features, A.nrow, rn, "features")
+    sb = None
+    if split_by is not None:
+        sb = np.asarray(split_by)
+        if sb.shape != (A.ncol,):
+            raise ValueError("split_by needs one entry per column of A")
+        groups = np.unique(sb)
+        sb = np.searchsorted(groups, sb).astype(np.int32)   # as.integer(as.numeric(as.factor(.))) - 1
+    scalar_k = k is not None and np.ndim(k) == 0
+    if k is not None and not scalar_k and np.size(k) < 1:
+        raise ValueError("value for 'k' was invalid")
+    rng = _rng(seed)
+    ctx = Context(0)
+    try:
+        ctx.upload(A, None)
+        v = A.x
+        if np.sum(np.trunc(v)) == np.sum(v):   # sum(as.integer(v)) == sum(v)
+            ctx.log_normalize()
+        if rows is not None:
+            ctx.subset(rows=rows)
+            rn = _subset_names(rn, rows)
+        if sb is not None:
+            ctx.weight_by_split(sb, int(groups.size))
+        fits = _ResidentFits(None, ctx=ctx, Dimnames=(rn, cn))
+        if k is not None and not scalar_k and np.size(k) > 1:
+            cv_data = cross_validate_nmf(None, k, n_replicates=reps, tol=tol * 10, maxit=maxit, verbose=verbose, L1=L1, L2=L2,
+                                         threads=threads, test_density=test_density, tol_overfit=tol_overfit,
+                                         trace_test_mse=trace_test_mse, seed=rng, _fits=fits)
+            best_rank = GetBestRank(cv_data, tol_overfit)
+            if verbose >= 1:
+                print("best rank: ", best_rank)
+                print("\nfitting final model:")
+            model = run_nmf(None, best_rank, tol, maxit, verbose > 1, L1, L2, threads, seed=rng, _fits=fits)
+        elif k is None:
+            k_max = 10000
+            if k_max > 1024:
+                if verbose >= 1:
+                    print("k_max = 1e4 is above the library's rank limit: searching up to k = 1024")
+                k_max = 1024
+            model = ard_nmf(None, k_init=None, k_max=k_max, k_min=2, n_replicates=reps, tol=tol, maxit=maxit, verbose=verbose,
+                            L1=L1, L2=L2, threads=threads, test_density=test_density, learning_rate=learning_rate,
+                            tol_overfit=tol_overfit, trace_test_mse=trace_test_mse, seed=rng, _fits=fits)
+            cv_data = model["cv_data"]
+        else:
+            rank = int(k if scalar_k else np.ravel(k)[0])
+            model = run_nmf(None, rank, tol, maxit, verbose > 1, L1, L2, threads, seed=rng, _fits=fits)
+            cv_data = CVData()
+    finally:
+        ctx.close()
+    model["cv_data"] = cv_data
+    return model
 
 
 # ---------------------------------------------------------------------------

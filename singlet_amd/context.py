@@ -248,6 +248,23 @@ class Context:
         check(self._L.sgl_rasterize_rowwise(self._h, _bin_size(n, "rasterize_rowwise")))
         self.k = 0
 
+    def subset(self, rows=None, cols=None):
+        """A <- A[rows, cols] on the resident matrix (sgl_subset): 0-based int32 index lists in any order, duplicates
+        allowed; None keeps the axis.  Both orientations are rebuilt on the device; a running fit is dropped."""
+        def lst(v):
+            if v is None:
+                return None, 0
+            a = np.ascontiguousarray(v, dtype=np.int32)
+            if a.ndim != 1:
+                raise ValueError("subset: an index list must be one-dimensional")
+            n = int(a.shape[0])
+            # an empty list is not None: it goes down as a non-NULL pointer with n = 0, which the library refuses
+            return (a if n else np.zeros(1, dtype=np.int32)), n
+        r, nr = lst(rows)
+        cl, nc = lst(cols)
+        check(self._L.sgl_subset(self._h, ptr(r, i32p), nr, ptr(cl, i32p), nc))
+        self.k = 0
+
     def weight_by_split(self, split_by, n_groups):
         """weight_by_split (src/singlet.cpp:119-144) on the resident shard; split_by: 0-based group per local cell."""
         sb = np.ascontiguousarray(split_by, dtype=np.int32)

@@ -81,13 +81,11 @@ static int talloc(T** p, size_t count) {
     return SGL_OK;
 }
 
-// Fills c->At from c->A, sorting at most max_batch_entries non-zeros at a time (<= 0: the default, 2^31 - 1).  A batch
+// Fills T (empty on entry) with the transpose of A, sorting at most max_batch_entries non-zeros at a time (<= 0: the default, 2^31 - 1).  A batch
 // is a run of whole columns (a column with more entries than the cap is a batch of its own; no column holds 2^31 or
 // more), so the positions the sort carries fit in 32 bits at any nnz and the temporaries stay at one batch.  A matrix
 // that fits one batch takes the single sort and gather.
-int sgl_device_transpose(sgl_ctx* c, int64_t max_batch_entries) {
-    const DevCSC& A = c->A;
-    DevCSC& T = c->At;
+int sgl_device_transpose_into(sgl_ctx* c, const DevCSC& A, DevCSC& T, int64_t max_batch_entries) {
     hipStream_t s = c->stream;
     const int64_t nnz = A.nnz;
     const int64_t cap = (max_batch_entries <= 0 || max_batch_entries > INT32_MAX) ? (int64_t)INT32_MAX : max_batch_entries;
@@ -177,3 +175,6 @@ int sgl_device_transpose(sgl_ctx* c, int64_t max_batch_entries) {
     if (tmp) (void)sgl_pool_free(tmp);
     return rc;
 }
+
+// the resident pair: c->At from c->A
+int sgl_device_transpose(sgl_ctx* c, int64_t max_batch_entries) { return sgl_device_transpose_into(c, c->A, c->At, max_batch_entries); }

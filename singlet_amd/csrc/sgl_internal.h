@@ -408,6 +408,10 @@ int k_link_mul(hipStream_t s, double* B, const double* L, int k, int link_rows, 
 // row-wise rasterisation (kernels_raster.hip): out (nb x ncol, column-major) = means of rows [b n, b n + n), nb >= 1
 int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, double* out);
 int k_raster_dense(hipStream_t s, const double* A, int64_t nrow, int64_t ncol, int64_t n, int64_t nb, double* out);
+// column gather of a CSC (kernels_subset.hip): D = S[:, sel], sel on the device and checked by the caller, D empty on entry
+int k_subset_gather(sgl_ctx* c, const DevCSC& S, const int32_t* sel, int64_t n, DevCSC& D);
+// device transpose (kernels_transpose.hip): T (empty on entry) = t(A), rows ascending; <= 0: the default batch size
+int sgl_device_transpose_into(sgl_ctx* c, const DevCSC& A, DevCSC& T, int64_t max_batch_entries);
 // upload of A alone (an empty At) validating the structure only, the values as they are (singlet_hip.hip)
 void sgl_matrix_clear(sgl_ctx* c);   // drops the fit and the resident matrix (the team upload, after one rank refused)
 int sgl_upload_A_structure(sgl_ctx* c, const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol);

@@ -713,6 +713,90 @@ extern "C" int sgl_rasterize_rowwise(sgl_ctx* c, int64_t n) {
     return SGL_OK;
 }
 
+// ---- sgl_subset: A <- A[rows, cols] on the device (include/singlet_hip.h) ----
+// One list of the call: orientation `which` (0: A, its columns are the cells; 1: At, its columns are the genes) becomes
+// the gather of its columns sel[0 .. n); then both old orientations are freed and the other one is rebuilt as the
+// transpose of the gathered one.  At the peak the two old images and ONE new one are resident; the transpose allocates
+// its result and its sort buffers only after the old images are gone.  For scripts/subset_rate.py the gather is booked
+// under SGL_PH_SCALE ("copies") when timing is enabled, the transpose in sgl_call_times_get's transpose slot.
+static int subset_side(sgl_ctx* c, int which, const int32_t* sel, int64_t n) {
+    DevCSC& S = which ? c->At : c->A;
+    DevCSC& O = which ? c->A : c->At;
+    DevBuf<int32_t> dsel;
+    SGLCHK(dsel.alloc((size_t)n));
+    HIPCHK(hipMemcpyAsync(dsel.p, sel, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    DevCSC G;
+    int rc;
+    {
+        Phase ph(c, SGL_PH_SCALE);
+        rc = k_subset_gather(c, S, dsel.p, n, G);
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == SGL_OK && e != hipSuccess) { sgl_set_error("sgl_subset: %s", hipGetErrorString(e)); rc = SGL_EHIP; }
+    if (rc != SGL_OK) { free_csc(G); return rc; }
+    free_csc(S);
+    free_csc(O);
+    S = G;
+    const double t0 = wall_now();
+    SGLCHK(sgl_device_transpose_into(c, S, O, 0));   // (synchronises the stream)
+    g_times.transpose_s += wall_now() - t0;          // as the transpose of sgl_upload_csc is booked (sgl_call_times_get)
+    return SGL_OK;
+}
+
+static int subset_check_list(const char* name, const int32_t* sel, int64_t n, int32_t extent, const char* extent_name) {
+    if (!sel) return SGL_OK;
+    if (n <= 0 || n > INT32_MAX) {
+        sgl_set_error("sgl_subset: %s holds %lld indices: a list must hold between 1 and 2^31 - 1 (a resident matrix cannot be "
+                      "empty; pass NULL to keep the axis as it is)", name, (long long)n);
+        return SGL_EINVAL;
+    }
+    for (int64_t q = 0; q < n; ++q)
+        if (sel[q] < 0 || sel[q] >= extent) {
+            sgl_set_error("sgl_subset: %s[%lld] = %d is outside [0, %s = %d)", name, (long long)q, sel[q], extent_name, extent);
+            return SGL_EINVAL;
+        }
+    return SGL_OK;
+}
+
+extern "C" int sgl_subset(sgl_ctx* c, const int32_t* rows, int64_t n_rows, const int32_t* cols, int64_t n_cols) {
+    CTX_GUARD(c);
+    if (c->team || c->allreduce) {
+        sgl_set_error("sgl_subset: the context is a shard of a team or has an all-reduce hook; a subset of this shard's "
+                      "genes would leave the shards' gene-side images inconsistent");
+        return SGL_ESTATE;
+    }
+    if (!c->A.p) { sgl_set_error("no matrix resident"); return SGL_ESTATE; }
+    const int32_t nrow = c->A.nrow, ncol = c->A.ncol;
+    if (c->cell_offset != 0 || c->ncells_total != (int64_t)ncol) {
+        sgl_set_error("sgl_subset: the context holds a shard (cells %lld .. %lld of %lld); subset the matrix before it is sharded",
+                      (long long)c->cell_offset, (long long)c->cell_offset + ncol, (long long)c->ncells_total);
+        return SGL_ESTATE;
+    }
+    SGLCHK(subset_check_list("rows", rows, n_rows, nrow, "nrow"));
+    SGLCHK(subset_check_list("cols", cols, n_cols, ncol, "ncol"));
+    free_fit(c);
+    c->k = 0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (!rows && !cols) return SGL_OK;
+    sgl_dense_release(c);   // the dense copy is of the OLD matrix; dense_input stays: the result came through the dense door
+    dev_free(c->col_nnz_A);
+    dev_free(c->col_nnz_At);
+    dev_free(c->col_nnz_At_global);
+    c->gene_nnz_global = false;
+    // the list that keeps the smaller share of its axis goes first: the second gather and both transposes then move less
+    const bool rows_first = rows && (!cols || (double)n_rows * (double)ncol <= (double)n_cols * (double)nrow);
+    for (int step = 0; step < 2; ++step) {
+        const bool do_rows = (step == 0) == rows_first;
+        if (do_rows ? !rows : !cols) continue;
+        UPLOADCHK(c, subset_side(c, do_rows ? 1 : 0, do_rows ? rows : cols, do_rows ? n_rows : n_cols));
+    }
+    c->cell_offset = 0;
+    c->ncells_total = c->A.ncol;
+    UPLOADCHK(c, finish_matrix(c));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { sgl_set_error("sgl_subset: HIP call failed"); return drop_matrix(c, SGL_EHIP); }
+    return SGL_OK;
+}
+
 extern "C" int sgl_weight_by_split(sgl_ctx* c, const int32_t* split_by, int32_t n_groups) {
     CTX_GUARD(c);
     if (!c->A.p) { sgl_set_error("no matrix resident"); return SGL_ESTATE; }
