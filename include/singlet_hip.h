@@ -650,6 +650,26 @@ SGL_API int sgl_op_cor(sgl_ctx* ctx, const double* x, const double* y, int64_t n
 SGL_API int sgl_op_graph_conv(sgl_ctx* ctx, const double* X, int32_t k, double* Y);
 /* mse_test (src/singlet.cpp:536-568) on the resident shard with the current factors. */
 SGL_API int sgl_op_mse_test(sgl_ctx* ctx, uint64_t seed, uint64_t inv_density, double* out);
+/* The three other device stages of one masked half-step (predict_mask, src/singlet.cpp:436-466, and mse_test), each through
+ * the internal entry the fit calls; none touches a fit's factors, right-hand sides, entry streams or stream value arrays. */
+/* Masked right-hand sides (src/singlet.cpp:449-457) for the resident shard: sgl_op_rhs with the entries drawn by the mask
+ * left out.  which = 0 / 1: A / t(A) by the plain CSC kernel hashing every entry; 2 / 3: the same through a temporary entry
+ * stream whose value array has zeros at the drawn entries.  The hash sees draw(cell, gene) with the context's cell_offset
+ * added to the cell (the column of A, the row of t(A)), as the fit's masked steps do.  SGL_EINVAL for inv_density = 0 and,
+ * tiled, at a rank without entry streams. */
+SGL_API int sgl_op_rhs_masked(sgl_ctx* ctx, int which, const double* F, int32_t k, uint64_t seed, uint64_t inv_density, double* B);
+/* nnls on ncols independent columns, each against its OWN Gram: Gcols = ncols blocks of k x k, B / X as in sgl_op_nnls;
+ * col_nnz (int64 [ncols], or NULL): columns with a zero there are skipped -- X keeps its input, no sweeps are counted.
+ * The dispatch of every masked half-step (four columns per wave on LDS triangles or on the Grams in global memory, one
+ * wave per column above), 1 <= k <= 1024. */
+SGL_API int sgl_op_nnls_percol(sgl_ctx* ctx, const double* Gcols, const double* B, double* X, const int64_t* col_nnz, int32_t k,
+                int64_t ncols, double L1, double L2, int32_t* sweeps_out);
+/* mse_test per cell, before the sum: losses[c] = mean over the drawn genes g of cell c of ((W diag(d) h_c)[g] - A(g, c))^2,
+ * 0 for a cell without a drawn gene; ncol doubles.  variant names the kernel family: 0 hashing inside the kernel; 1 from
+ * the cell-side mask lists, the matrix values found through the sliding window; 2 from the lists with the matrix values
+ * listed first.  1 and 2 select (build, when they are not there) the context's cell-side lists for this mask, as a masked
+ * H-update does: SGL_EINVAL above k = 128, SGL_ENOMEM when the lists (or, for 2, the values) are refused.  Needs a fit. */
+SGL_API int sgl_op_mse_test_cells(sgl_ctx* ctx, uint64_t seed, uint64_t inv_density, int variant, double* losses);
 
 /* ------------------------------------------------------------------------
  * 4. Timing (hipEvent based, on the context's stream).

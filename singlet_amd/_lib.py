@@ -146,6 +146,9 @@ SIGNATURES = {
     "sgl_op_cor": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, f64p]),
     "sgl_op_graph_conv": (C.c_int, [C.c_void_p, f64p, C.c_int32, f64p]),
     "sgl_op_mse_test": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, f64p]),
+    "sgl_op_rhs_masked": (C.c_int, [C.c_void_p, C.c_int, f64p, C.c_int32, C.c_uint64, C.c_uint64, f64p]),
+    "sgl_op_nnls_percol": (C.c_int, [C.c_void_p, f64p, f64p, f64p, i64p, C.c_int32, C.c_int64, C.c_double, C.c_double, i32p]),
+    "sgl_op_mse_test_cells": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, f64p]),
     "sgl_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "sgl_timing_get": (C.c_int, [C.c_void_p, f64p, i64p, C.c_int]),
     "sgl_sweeps_get": (C.c_int, [C.c_void_p, i64p, C.c_int]),

@@ -467,6 +467,44 @@ class Context:
         check(self._L.sgl_op_mse_test(self._h, int(seed), int(inv_density), C.byref(out)))
         return out.value
 
+    def op_rhs_masked(self, which, F, seed, inv_density):
+        """op_rhs with the entries the mask (seed, inv_density) draws left out (sgl_op_rhs_masked): which = 0 / 1 hash every
+        entry in the plain kernel, 2 / 3 run the LDS-tiled kernel on a masked value array."""
+        F = _f(F)
+        nr, nc, _ = self.dims()
+        k = F.shape[1]
+        ncol = nr if (which & 1) else nc
+        nrow = nc if (which & 1) else nr
+        if F.shape[0] != nrow:
+            raise ValueError("F must have %d rows" % nrow)
+        B = np.empty((ncol, k))
+        check(self._L.sgl_op_rhs_masked(self._h, int(which), ptr(F, f64p), k, int(seed), int(inv_density), ptr(B, f64p)))
+        return B
+
+    def op_nnls_percol(self, Gcols, B, X, col_nnz=None, L1=0.0, L2=0.0):
+        """nnls of every column against its own Gram (sgl_op_nnls_percol): Gcols (ncols, k, k), B / X (ncols, k); col_nnz:
+        int64 per column, a zero skips the column.  Returns (X, total sweeps)."""
+        Gcols, B = _f(Gcols), _f(B)
+        X = np.array(X, dtype=np.float64, order="C")
+        ncols, k = B.shape
+        if Gcols.shape != (ncols, k, k) or X.shape != (ncols, k):
+            raise ValueError("Gcols must be (ncols, k, k) and X (ncols, k)")
+        nz = None if col_nnz is None else np.ascontiguousarray(col_nnz, dtype=np.int64)
+        if nz is not None and nz.shape != (ncols,):
+            raise ValueError("col_nnz must have one entry per column")
+        sw = C.c_int32()
+        check(self._L.sgl_op_nnls_percol(self._h, ptr(Gcols, f64p), ptr(B, f64p), ptr(X, f64p), ptr(nz, i64p), k, ncols, L1, L2,
+                                         C.byref(sw)))
+        return X, sw.value
+
+    def op_mse_test_cells(self, seed, inv_density, variant=0):
+        """The per-cell losses of mse_test (sgl_op_mse_test_cells) by one kernel family: variant 0 hashing, 1 mask lists with
+        the sliding window, 2 mask lists with listed matrix values."""
+        _, nc, _ = self.dims()
+        out = np.empty(nc)
+        check(self._L.sgl_op_mse_test_cells(self._h, int(seed), int(inv_density), int(variant), ptr(out, f64p)))
+        return out
+
     # -- timing -------------------------------------------------------------
     def timing_enable(self, on=True):
         check(self._L.sgl_timing_enable(self._h, int(bool(on))))

@@ -797,50 +797,52 @@ __global__ void sum_final_kernel(const double* __restrict__ part, int nblocks, d
     out[0] = s;
 }
 
-// out_dev[0] = sum over local cells of the per-cell mean squared test error
-// (the caller divides by the global number of cells, src/singlet.cpp:567).
-int k_mse_test(sgl_ctx* c, const double* Wd, const double* H, int k, uint64_t seed, uint64_t inv_density,
-               double* out_dev) {
+// The matrix values at the listed entries of the cell-side lists Lw, found once per mask (8 B per drawn pair: 12 GB at
+// config 5; not when that is more than a fifth of the free memory: Lw.val_refused, the window kernel then looks them up in
+// every trace).  No-op when they are there or were refused.
+int k_mask_vals(sgl_ctx* c, DevMaskList& Lw) {
+    if (Lw.val_ok || Lw.val_refused) return SGL_OK;
     const int64_t n = c->A.ncol;
-    if (n <= 0) return SGL_OK;
-    int nblocks = (int)((n + 4095) / 4096);
-    if (nblocks > 256) nblocks = 256;
-    if (nblocks < 1) nblocks = 1;
-    SGLCHK(sgl_ws_reserve(c, sizeof(double) * ((size_t)n + (size_t)nblocks)));
-    double* losses = c->ws;
-    double* part = c->ws + n;
     int64_t blocks = (n + 3) / 4;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    // the cell-side mask lists of this fit, when they are there (built by the H-update of the masked iteration)
-    const DevMaskList& L = c->ML[0];
-    const bool lists = k <= 128 && L.mask_t == 0 && L.ptr != nullptr && L.idx != nullptr && L.seed == seed && L.inv == inv_density &&
-                       L.ncol == n && L.nrow == c->A.nrow && L.col_off == c->cell_offset && L.row_off == 0 && !getenv("SGL_MSE_NO_LIST");
-    // ... and the matrix values at the listed entries, found once per mask (8 B per drawn pair: 12 GB at config 5; not when
-    // that is more than a fifth of the free memory, SGL_MSE_NO_VALS=1: the window kernel looks them up in every trace)
-    DevMaskList& Lw = c->ML[0];
-    if (lists && !Lw.val_ok && !Lw.val_refused && !getenv("SGL_MSE_NO_VALS")) {
-        const size_t want = (size_t)Lw.total + 64;
-        if (Lw.cap_val < want) {
-            if (Lw.val) (void)sgl_pool_free(Lw.val);
-            Lw.val = nullptr; Lw.cap_val = 0;
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(sgl_pool_mem_info(&free_b, &total_b));
-            const size_t cap = (size_t)((double)Lw.total * 1.02) + 1024;
-            if (8.0 * (double)cap > 0.2 * (double)free_b || sgl_pool_malloc(&Lw.val, sizeof(double) * cap) != hipSuccess) {
-                (void)hipGetLastError();
-                Lw.val = nullptr;
-                Lw.val_refused = true;
-            } else {
-                Lw.cap_val = cap;
-            }
-        }
-        if (Lw.val) {
-            mask_vals_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(c->A.x, c->A.i, c->A.p, n, Lw.ptr, Lw.idx, Lw.val);
-            HIPCHK(hipGetLastError());
-            Lw.val_ok = true;
+    const size_t want = (size_t)Lw.total + 64;
+    if (Lw.cap_val < want) {
+        if (Lw.val) (void)sgl_pool_free(Lw.val);
+        Lw.val = nullptr; Lw.cap_val = 0;
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(sgl_pool_mem_info(&free_b, &total_b));
+        const size_t cap = (size_t)((double)Lw.total * 1.02) + 1024;
+        if (8.0 * (double)cap > 0.2 * (double)free_b || sgl_pool_malloc(&Lw.val, sizeof(double) * cap) != hipSuccess) {
+            (void)hipGetLastError();
+            Lw.val = nullptr;
+            Lw.val_refused = true;
+        } else {
+            Lw.cap_val = cap;
         }
     }
-    if (lists && Lw.val_ok) {
+    if (Lw.val) {
+        mask_vals_kernel<<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(c->A.x, c->A.i, c->A.p, n, Lw.ptr, Lw.idx, Lw.val);
+        HIPCHK(hipGetLastError());
+        Lw.val_ok = true;
+    }
+    return SGL_OK;
+}
+
+// losses[cell] = the mean squared test error of every local cell, by ONE kernel family: variant 0 mse_test_kernel (hashing;
+// L unused), 1 mse_test_list_kernel (the cell-side lists L, k <= 128), 2 mse_test_vals_kernel (L with its values listed).
+// Shared by the fit (k_mse_test picks the variant) and sgl_op_mse_test_cells (the caller names it).
+int k_mse_test_cells(sgl_ctx* c, const double* Wd, const double* H, int k, uint64_t seed, uint64_t inv_density, int variant,
+                     const DevMaskList* Lp, double* losses) {
+    const int64_t n = c->A.ncol;
+    if (n <= 0) return SGL_OK;
+    int64_t blocks = (n + 3) / 4;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    if (variant != 0 && (Lp == nullptr || k > 128 || Lp->ptr == nullptr || Lp->idx == nullptr || (variant == 2 && !Lp->val_ok))) {
+        sgl_set_error("k_mse_test_cells: variant %d without its lists (k = %d)", variant, k);
+        return SGL_EINVAL;
+    }
+    if (variant == 2) {
+        const DevMaskList& L = *Lp;
 #define SGL_MSEV(NJ_) mse_test_vals_kernel<NJ_><<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(n, L.ptr, L.idx, L.val, Wd, H, k, losses)
         switch ((k + 15) / 16) {
             case 1: SGL_MSEV(1); break;
@@ -853,7 +855,8 @@ int k_mse_test(sgl_ctx* c, const double* Wd, const double* H, int k, uint64_t se
             default: SGL_MSEV(8); break;
         }
 #undef SGL_MSEV
-    } else if (lists) {
+    } else if (variant == 1) {
+        const DevMaskList& L = *Lp;
 #define SGL_MSEL(NJ_) mse_test_list_kernel<NJ_><<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(c->A.x, c->A.i, c->A.p, n, L.ptr, L.idx, Wd, H, k, losses)
         switch ((k + 15) / 16) {
             case 1: SGL_MSEL(1); break;
@@ -879,6 +882,28 @@ int k_mse_test(sgl_ctx* c, const double* Wd, const double* H, int k, uint64_t se
         mse_test_kernel<16><<<dim3((unsigned)blocks), dim3(256), 0, c->stream>>>(c->A.x, c->A.i, c->A.p, c->A.nrow, n, c->cell_offset,
                                                                                  Wd, H, k, seed, sgl_div_make(inv_density), losses);
     HIPCHK(hipGetLastError());
+    return SGL_OK;
+}
+
+// out_dev[0] = sum over local cells of the per-cell mean squared test error
+// (the caller divides by the global number of cells, src/singlet.cpp:567).
+int k_mse_test(sgl_ctx* c, const double* Wd, const double* H, int k, uint64_t seed, uint64_t inv_density,
+               double* out_dev) {
+    const int64_t n = c->A.ncol;
+    if (n <= 0) return SGL_OK;
+    int nblocks = (int)((n + 4095) / 4096);
+    if (nblocks > 256) nblocks = 256;
+    if (nblocks < 1) nblocks = 1;
+    SGLCHK(sgl_ws_reserve(c, sizeof(double) * ((size_t)n + (size_t)nblocks)));
+    double* losses = c->ws;
+    double* part = c->ws + n;
+    // the cell-side mask lists of this fit, when they are there (built by the H-update of the masked iteration)
+    DevMaskList& L = c->ML[0];
+    const bool lists = k <= 128 && L.mask_t == 0 && L.ptr != nullptr && L.idx != nullptr && L.seed == seed && L.inv == inv_density &&
+                       L.ncol == n && L.nrow == c->A.nrow && L.col_off == c->cell_offset && L.row_off == 0 && !getenv("SGL_MSE_NO_LIST");
+    // ... and the matrix values at the listed entries (SGL_MSE_NO_VALS=1: the window kernel looks them up in every trace)
+    if (lists && !getenv("SGL_MSE_NO_VALS")) SGLCHK(k_mask_vals(c, L));
+    SGLCHK(k_mse_test_cells(c, Wd, H, k, seed, inv_density, lists ? (L.val_ok ? 2 : 1) : 0, &L, losses));
     sum_partial_kernel<<<dim3(nblocks), dim3(256), 0, c->stream>>>(losses, n, part);
     HIPCHK(hipGetLastError());
     sum_final_kernel<<<dim3(1), dim3(64), 0, c->stream>>>(part, nblocks, out_dev);

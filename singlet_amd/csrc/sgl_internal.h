@@ -465,6 +465,11 @@ int k_tri_pack(hipStream_t s, const double* S, int k, int64_t ncols, double* tri
 int k_mask_gram_finalize_tri(hipStream_t s, const double* G, const double* tri, int k, int64_t ncols, double* out);
 int k_mse_test(sgl_ctx* c, const double* Wd, const double* H, int k, uint64_t seed, uint64_t inv_density,
                double* out_dev);
+// its two halves, shared with sgl_op_mse_test_cells: the matrix values at the listed entries of the cell-side lists (no-op once
+// there or refused), and the per-cell losses by the named kernel family (0 hashing, 1 lists + window, 2 listed values)
+int k_mask_vals(sgl_ctx* c, DevMaskList& L);
+int k_mse_test_cells(sgl_ctx* c, const double* Wd, const double* H, int k, uint64_t seed, uint64_t inv_density, int variant,
+                     const DevMaskList* L, double* losses);
 int k_wd(hipStream_t s, const double* W, const double* d, int k, int64_t cols, double* Wd);
 
 // ---- device-side hash (rng::rand, src/singlet.cpp:30-64) ------------------

@@ -2026,6 +2026,95 @@ extern "C" int sgl_op_nnls(sgl_ctx* c, const double* G, const double* B, double*
     return rc;
 }
 
+// The masked right-hand sides of sgl_masked_rhs on their own: the same two paths with the same offsets, on temporaries (the
+// plain kernel's tile table as in sgl_op_rhs; an entry stream and its masked value array of its own for the tiled one).
+extern "C" int sgl_op_rhs_masked(sgl_ctx* c, int which, const double* F, int32_t k, uint64_t seed, uint64_t inv_density, double* B) {
+    CTX_GUARD(c);
+    const bool tiled = (which & 2) != 0;
+    const int mask_t = (which & 1) ? 1 : 0;
+    DevCSC& M = mask_t ? c->At : c->A;
+    if (!M.p) { sgl_set_error("no matrix resident"); return SGL_ESTATE; }
+    if (!F || !B || k <= 0 || k > SGL_MAX_K || inv_density == 0 || (tiled && tiled_part_size(k) == 0)) { sgl_set_error("sgl_op_rhs_masked: bad arguments"); return SGL_EINVAL; }
+    const int64_t col_off = mask_t ? 0 : c->cell_offset;
+    const int64_t row_off = mask_t ? c->cell_offset : 0;
+    DevBuf<double> dF, dB;
+    SGLCHK(dF.alloc((size_t)k * M.nrow + 2));
+    SGLCHK(dB.alloc((size_t)k * M.ncol));
+    HIPCHK(hipMemcpyAsync(dF.p, F, sizeof(double) * (size_t)k * M.nrow, hipMemcpyHostToDevice, c->stream));
+    int rc;
+    if (tiled) {
+        DevTiled S;
+        rc = sgl_tiled_build(c, M, tiled_part_size(k), S);
+        if (rc == SGL_OK) rc = sgl_tiled_mask_values(c, M, S, seed, inv_density, mask_t, col_off, row_off);
+        if (rc == SGL_OK) rc = k_acc_tiled_all(c->stream, S, dF.p, dB.p, k, S.xm);
+        if (rc == SGL_OK && hipMemcpyAsync(B, dB.p, sizeof(double) * (size_t)k * M.ncol, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = SGL_EHIP;
+        rc = op_finish(c, rc, "sgl_op_rhs_masked");
+        sgl_tiled_free(S);
+    } else {
+        int64_t* saved = M.seg; int32_t str = M.tile_rows, snt = M.ntiles;
+        M.seg = nullptr;
+        rc = build_tiles(c, M, k);
+        if (rc == SGL_OK) rc = k_acc(c->stream, M, dF.p, k, dB.p, seed, inv_density, mask_t ? 2 : 1, col_off, row_off);
+        if (rc == SGL_OK && hipMemcpyAsync(B, dB.p, sizeof(double) * (size_t)k * M.ncol, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = SGL_EHIP;
+        rc = op_finish(c, rc, "sgl_op_rhs_masked");
+        dev_free(M.seg);
+        M.seg = saved; M.tile_rows = str; M.ntiles = snt;
+    }
+    return rc;
+}
+
+// k_nnls_percol with a Gram per column (gstride = k * k), as every masked half-step calls it
+extern "C" int sgl_op_nnls_percol(sgl_ctx* c, const double* Gcols, const double* B, double* X, const int64_t* col_nnz, int32_t k,
+                                  int64_t ncols, double L1, double L2, int32_t* sweeps_out) {
+    CTX_GUARD(c);
+    if (!Gcols || !B || !X || k <= 0 || k > SGL_MASK_MAX_K || ncols < 0) { sgl_set_error("sgl_op_nnls_percol: bad arguments"); return SGL_EINVAL; }
+    DevBuf<double> dG, dB, dX;
+    DevBuf<int64_t> dN;
+    SGLCHK(dG.alloc((size_t)k * k * ncols));
+    SGLCHK(dB.alloc((size_t)k * ncols));
+    SGLCHK(dX.alloc((size_t)k * ncols));
+    if (col_nnz) SGLCHK(dN.alloc((size_t)ncols));
+    HIPCHK(hipMemcpyAsync(dG.p, Gcols, sizeof(double) * (size_t)k * k * ncols, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dB.p, B, sizeof(double) * (size_t)k * ncols, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dX.p, X, sizeof(double) * (size_t)k * ncols, hipMemcpyHostToDevice, c->stream));
+    if (col_nnz) HIPCHK(hipMemcpyAsync(dN.p, col_nnz, sizeof(int64_t) * (size_t)ncols, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(c->sweep_counters + 4, 0, 4 * sizeof(unsigned long long), c->stream));
+    int rc = k_nnls_percol(c->stream, dG.p, (int64_t)k * k, dB.p, dX.p, col_nnz ? dN.p : nullptr, k, ncols, L1, L2, c->sweep_counters + 4);
+    unsigned long long sw = 0;
+    if (rc == SGL_OK && (hipMemcpyAsync(X, dX.p, sizeof(double) * (size_t)k * ncols, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                         hipMemcpyAsync(&sw, c->sweep_counters + 4, sizeof(sw), hipMemcpyDeviceToHost, c->stream) != hipSuccess)) rc = SGL_EHIP;
+    rc = op_finish(c, rc, "sgl_op_nnls_percol");
+    if (sweeps_out) *sweeps_out = (int32_t)sw;
+    return rc;
+}
+
+// The per-cell losses of mse_test by the kernel family `variant` names (k_mse_test_cells, the launch code of the fit's
+// k_mse_test): W' = W^T diag(d) goes to the fit's own scratch as in sgl_op_mse_test, the losses to a temporary.
+extern "C" int sgl_op_mse_test_cells(sgl_ctx* c, uint64_t seed, uint64_t inv_density, int variant, double* losses) {
+    FIT_GUARD(c);
+    if (!losses || inv_density == 0 || variant < 0 || variant > 2) { sgl_set_error("sgl_op_mse_test_cells: bad arguments"); return SGL_EINVAL; }
+    const int k = c->k;
+    const int64_t n = c->A.ncol;
+    if (variant != 0 && k > 128) { sgl_set_error("sgl_op_mse_test_cells: the mask lists serve ranks up to 128 (k = %d)", k); return SGL_EINVAL; }
+    if (n <= 0) return SGL_OK;
+    SGLCHK(sgl_mask_workspace(c));
+    DevBuf<double> dL;
+    SGLCHK(dL.alloc((size_t)n));
+    DevMaskList& L = c->ML[0];
+    if (variant != 0) {
+        SGLCHK(sgl_mask_list_select(c, 0, n, c->A.nrow, seed, inv_density, 0, c->cell_offset, 0));
+        if (L.mask_t != 0) { sgl_set_error("sgl_op_mse_test_cells: the lists were refused"); return SGL_ENOMEM; }
+    }
+    if (variant == 2) {
+        SGLCHK(k_mask_vals(c, L));
+        if (!L.val_ok) { sgl_set_error("sgl_op_mse_test_cells: the listed values were refused"); return SGL_ENOMEM; }
+    }
+    int rc = k_wd(c->stream, c->W, c->d, k, c->A.nrow, c->Wd);
+    if (rc == SGL_OK) rc = k_mse_test_cells(c, c->Wd, c->H, k, seed, inv_density, variant, &L, dL.p);
+    if (rc == SGL_OK && hipMemcpyAsync(losses, dL.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = SGL_EHIP;
+    return op_finish(c, rc, "sgl_op_mse_test_cells");
+}
+
 extern "C" int sgl_op_transpose(sgl_ctx* c, int64_t max_batch_entries) {
     CTX_GUARD(c);
     if (!c->A.p || !c->col_nnz_A) { sgl_set_error("sgl_op_transpose: no resident matrix"); return SGL_EINVAL; }
