@@ -449,6 +449,49 @@ SGL_API int sgl_fit_init(sgl_ctx* ctx, int32_t k, const double* w_init, uint64_t
 SGL_API int sgl_set_links(sgl_ctx* ctx, const double* link_h, int32_t link_h_rows, int32_t link_h_cols,
                           const double* link_w, int32_t link_w_rows, int32_t link_w_cols);
 
+/* The grouped form of the link matrices, for links whose column is a function of the cell's (gene's) group alone, as
+ * RunLNMF.Seurat builds them (R/RunLNMF.R:146-154).  Behaves exactly as if sgl_set_links had received
+ *   link_h[j, c] = table_h[j, group_h[c]]   (table_h rows_h x groups_h column-major, group_h one id per LOCAL cell) and
+ *   link_w[j, g] = table_w[j, group_w[g]]   (table_w rows_w x groups_w, group_w one id per gene),
+ * without the expanded matrices ever existing: the device holds rows * groups doubles plus 4 bytes per cell / gene.
+ *  - every entry of the right-hand sides gets the same single multiplication as in the dense form (never a select:
+ *    b * 0.0 keeps the sign of b), so a fit gives the same bits either way.  A table of up to 32 KiB (rows * groups * 8)
+ *    is staged in LDS by every workgroup, a larger one is read through the cache; the group id is loaded once per cell.
+ *  - a NULL table (or rows < 1) switches that side off.  A side that is on needs its group list (SGL_EINVAL without).
+ *  - lifetime as sgl_set_links: after sgl_fit_init, dropped by the next one.  sgl_set_links and sgl_set_links_grouped
+ *    each replace everything the other (or an earlier call of itself) set, on both sides.
+ *  - refused like sgl_set_links: with a cell graph set, and when a table has more rows than the rank (SGL_EINVAL; the
+ *    links set before are gone then, as after sgl_set_links' refusal).
+ *  - groups < 1 on a side that is on is SGL_EINVAL; a group id outside [0, groups) is SGL_EINVAL with a message naming
+ *    the list, the position and the value of the first offender.  Both lists are checked completely before anything is
+ *    freed or launched: after such a refusal the links set before are still in force.
+ *  - table values are not checked for finiteness (sgl_set_links does not check its matrices either). */
+SGL_API int sgl_set_links_grouped(sgl_ctx* ctx, const double* table_h, int32_t rows_h, int32_t groups_h, const int32_t* group_h,
+                                  const double* table_w, int32_t rows_w, int32_t groups_w, const int32_t* group_w);
+
+/* Group means of a k x n factor matrix: means[f, g] = mean of F[f, c] over the cells c with group[c] == g -- the k x G table
+ * that RunLNMF.Seurat (R/RunLNMF.R:136-143) and MetadataSummary (R/MetadataSummary.R:18-26) form with k G calls of
+ * mean(h[which(...)]).
+ *  - F: a host k x n array (column-major, one column per cell), or NULL for the H of the current fit, which stays where it
+ *    is; with NULL, k and n must be the fit's rank and the resident matrix's cell count (SGL_EINVAL otherwise).
+ *  - means: k x n_groups column-major; counts: int64_t[n_groups] cells per group.  means[f, g] = sum / (double)counts[g], one
+ *    true division; an empty group gives NaN, the 0.0 / 0.0 of R's mean(numeric(0)).
+ *  - the summation order is a function of (n, group, n_groups) alone -- no floating-point atomics, nothing depends on the
+ *    launch size or the occupancy -- so two calls give the same bits, and the resident, the host-F and the one-shot form
+ *    agree bit for bit.  The order: the cells of a group, in ascending cell index, are cut into chunks of 256; inside a
+ *    chunk, slot s of S = 256 / min(64, k rounded up to a power of two) takes the cells s, s + S, ... in turn and the S slot
+ *    sums are added by a binary tree; the chunk sums are added in chunk order.  |error| <= n_g 2^-53 mean_g |x| to first order.
+ *  - refused: SGL_ESTATE on a team member, with an all-reduce hook set (the shard's means are not the matrix's; a team
+ *    uses sgl_multi_group_means), or with F == NULL and no fit; SGL_EINVAL for n_groups < 1, k outside [1, 1024], n < 0 and
+ *    for a group id outside [0, n_groups), the message naming the list, the position and the value of the first offender
+ *    (the whole list is checked before anything is launched).  The context stays usable after every refusal.
+ *  - values are not checked for finiteness: NaN / Inf propagate through the IEEE sums. */
+SGL_API int sgl_group_means(sgl_ctx* ctx, const double* F, int32_t k, int64_t n, const int32_t* group, int32_t n_groups,
+                            double* means, int64_t* counts);
+/* The one-shot form: its own context on the current device (like sgl_c_rowwise_compress_*); F must not be NULL. */
+SGL_API int sgl_c_group_means(const double* F, int32_t k, int64_t n, const int32_t* group, int32_t n_groups,
+                              double* means, int64_t* counts);
+
 /* Cell graph of c_gcnmf for the current fit (after sgl_fit_init, which drops
  * it again; all-NULL slots clear it).  G is an n x n dgCMatrix, n = the cells of
  * the resident matrix; an invalid G is SGL_EINVAL with a message.  While it is
@@ -552,6 +595,16 @@ SGL_API int sgl_multi_fit_init(sgl_multi* m, int32_t k, const double* w_init, ui
  * the columns of link_h that belong to its cells.) */
 SGL_API int sgl_multi_set_links(sgl_multi* m, const double* link_h, int32_t link_h_rows, int32_t link_h_cols,
                                 const double* link_w, int32_t link_w_rows, int32_t link_w_cols);
+/* sgl_set_links_grouped on the team: group_h holds one id per cell of the WHOLE matrix and is dealt out with the cells, as
+ * sgl_multi_set_links deals out the columns of link_h; the tables and group_w go to every rank, whose gene block reads
+ * group_w from its first gene on.  Both lists are checked before any rank is touched. */
+SGL_API int sgl_multi_set_links_grouped(sgl_multi* m, const double* table_h, int32_t rows_h, int32_t groups_h, const int32_t* group_h,
+                                        const double* table_w, int32_t rows_w, int32_t groups_w, const int32_t* group_w);
+/* sgl_group_means of the H of the team's fit (group: one id per cell of the whole matrix): every rank sums its own cells
+ * in the order sgl_group_means defines for its block, the host adds the rank partials in rank order and divides by the
+ * counts over all ranks.  Equal to the one-context means to the rounding of the different order (same first-order
+ * bound); the counts are exact.  SGL_ESTATE without a fit. */
+SGL_API int sgl_multi_group_means(sgl_multi* m, const int32_t* group, int32_t n_groups, double* means, int64_t* counts);
 /* c_gcnmf on the team (src/singlet.cpp:1668-1730): the cell graph of the WHOLE matrix (arguments, checks and messages as
  * sgl_set_graph; all-NULL slots clear it; sgl_multi_fit_init drops it).  Rank r keeps the columns of its own cells.  The
  * rows of those columns that name another rank's cells are that rank's "exports"; E = the longest export list of the

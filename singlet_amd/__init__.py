@@ -6,7 +6,8 @@ from .context import Context, Multi, comm_unique_id, comm_available, device_coun
 from .api import (c_nmf, c_ard_nmf, c_linked_nmf, c_gcnmf, run_gcnmf, c_nmf_dense, c_nmf_sparse_list, c_ard_nmf_dense, c_ard_nmf_sparse_list, c_project_model, Rcpp_predict, run_nmf, ard_nmf, cross_validate_nmf,  # noqa: F401
                   GetBestRank, project_model, CVData, PreprocessData, weight_by_split, call_times, c_LKNN, c_SNN,
                   find_local_neighbors, rescale_spatial, spatial_graph,
-                  rowwise_compress_sparse, rowwise_compress_dense, RasterizeRowwise, RasterMatrix, subset, RunNMF)
+                  rowwise_compress_sparse, rowwise_compress_dense, RasterizeRowwise, RasterMatrix, subset, RunNMF,
+                  group_means, run_linked_nmf, RunLNMF, MetadataSummary, GetSharedFactors, GetUniqueFactors)
 from ._lib import SingletHipError, LIB_PATH  # noqa: F401
 
 __version__ = "0.1.0"

@@ -17,6 +17,11 @@ names, argument order, defaults and return fields:
   GetBestRank                           R/GetBestRank.R:8-46
   project_model                         R/ProjectData.R:11-19
   RunNMF (matrix steps), subset         R/RunNMF.R:61-151; A[features, ] (:72-81), R/ProjectData.R:68-69
+  run_linked_nmf                        R/RunLNMF.R:18-66
+  RunLNMF (matrix steps)                R/RunLNMF.R:111-159
+  MetadataSummary                       R/MetadataSummary.R:15-36 (without the hclust display order)
+  GetSharedFactors / GetUniqueFactors   R/GetSharedFactors.R:4-10, R/GetUniqueFactors.R:4-10
+  group_means                           the k G calls of mean(h[which(...)]) of R/RunLNMF.R:136-143, R/MetadataSummary.R:18-26
 
 Matrices follow R's orientation: w is returned k x m by c_nmf and m x k by
 run_nmf / ard_nmf (they transpose and sort by d, R/run_nmf.R:65-68); h is
@@ -1090,6 +1095,223 @@ def RunNMF(A, k=None, features=None, split_by=None, reps=3, tol=1e-5, L1=0.01, L
         ctx.close()
     model["cv_data"] = cv_data
     return model
+
+
+# ---------------------------------------------------------------------------
+# Linked NMF (R/RunLNMF.R, R/MetadataSummary.R, R/GetSharedFactors.R, R/GetUniqueFactors.R)
+# ---------------------------------------------------------------------------
+def group_means(F, group, n_groups):
+    """(means, counts) of the columns of F (k x n, one column per cell) per group: means[f, g] = mean(F[f, which(group == g)])
+    as k x n_groups, counts[g] the cells of group g (sgl_c_group_means, on the device).  group holds one 0-based id per
+    column; an empty group gives a NaN column (R's mean(numeric(0))) and a count of 0.  The summation order depends on
+    (n, group, n_groups) alone."""
+    from .context import _group_list
+    Fa = np.asarray(F, dtype=np.float64)
+    if Fa.ndim != 2:
+        raise ValueError("F must be a k x n matrix")
+    k, n = Fa.shape
+    buf = np.ascontiguousarray(Fa.T)   # column-major image
+    g = _group_list(group, n, "group")
+    G = int(n_groups)
+    means = np.empty((max(G, 0), k))
+    counts = np.zeros(max(G, 0), dtype=np.int64)
+    check(_lib.load().sgl_c_group_means(ptr(buf, f64p), int(k), int(n), ptr(g, i32p), G, ptr(means, f64p),
+                                        ptr(counts, C.POINTER(C.c_int64))))
+    return means.T, counts
+
+
+def _shares(means):
+    """apply(m, 1, function(x) x / sum(x)), kept k x G: every factor's group means divided by their sum (added in group
+    order).  A factor whose means are all zero gives a NaN row."""
+    m = np.asarray(means, dtype=np.float64)
+    if m.ndim != 2 or m.shape[1] < 1:
+        raise ValueError("means must be a k x G matrix with at least one group")
+    total = np.zeros(m.shape[0])
+    for g in range(m.shape[1]):
+        total = total + m[:, g]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return m / total[:, None]
+
+
+def _share_table(means):
+    """t(apply(m, 1, function(x) x / sum(x))) * length(levels) of R/RunLNMF.R:143 for the k x G table of group means."""
+    s = _shares(means)
+    return s * s.shape[1]
+
+
+def _link_table(means, link_cutoff):
+    """The k x G link table of R/RunLNMF.R:143-154: 0 where a group's share of a factor (_share_table) is below link_cutoff
+    (strictly: a share equal to the cut-off stays linked), 1 elsewhere.  A NaN share raises, naming the factor: R stops
+    there too, at `if (NA)` (l.149)."""
+    share = _share_table(means)
+    bad = np.flatnonzero(np.isnan(share).any(axis=1))
+    if bad.size:
+        raise ValueError("factor %d (0-based; factor %d of the reference) has no defined share of the groups (its group means "
+                         "are all zero or not finite): the reference stops at `if (NA)` (R/RunLNMF.R:149)"
+                         % (int(bad[0]), int(bad[0]) + 1))
+    return 1.0 - (share < float(link_cutoff)).astype(np.float64)
+
+
+def _dim2(x):
+    return tuple(np.shape(x)) if np.ndim(x) == 2 else None
+
+
+def _linked_checks(nrow_A, ncol_A, w_shape, link_h_shape, link_w_shape, L1):
+    """The stop()s of run_linked_nmf (R/RunLNMF.R:19-53), in its order, with its messages (a shape is (rows, cols) or None)."""
+    if link_h_shape is None and link_w_shape is None:
+        raise ValueError("both link_h and link_w cannot be NULL. Specify at least one linking matrix.")
+    if link_h_shape is not None and link_h_shape[0] != w_shape[1]:
+        raise ValueError("number of rows in 'link_h' must be equal to the nubmer of columns in 'w'")
+    if link_h_shape is not None and link_h_shape[1] != ncol_A:
+        raise ValueError("number of columns in 'link_h' must be equal to the number of columns in 'A'")
+    if link_w_shape is not None and link_w_shape[1] != w_shape[1]:
+        raise ValueError("number of columns in 'link_w' must be equal to the nubmer of columns in 'w'")
+    if link_w_shape is not None and link_w_shape[0] != nrow_A:
+        raise ValueError("number of rows in 'link_w' must be equal to the number of rows in 'A'")
+    if L1 >= 1:
+        raise ValueError("L1 penalty must be strictly in the range (0, 1]")
+    if w_shape[0] != nrow_A:
+        raise ValueError("number of rows in 'w' must be equal to the number of rows in 'A'")
+
+
+def _sort_linked(model):
+    # sort_index <- order(model$d, decreasing = TRUE)   R/RunLNMF.R:61-64, as _sort_model
+    idx = np.argsort(-model["d"], kind="stable")
+    model["d"] = model["d"][idx]
+    model["w"] = model["w"].T[:, idx]
+    model["h"] = model["h"][idx, :]
+    return idx
+
+
+def run_linked_nmf(A, w, link_h=None, link_w=None, tol=1e-4, maxit=100, verbose=True, L1=0.01, L2=0, threads=0):
+    """R/RunLNMF.R:18-66: linked NMF from an initial w (m x k).  link_h is k x n, link_w m x k, as the reference documents
+    them.  The same checks in the same order (ValueError with the reference's messages), then c_linked_nmf on t(w) and the
+    sort by d.  As in the reference, link_w reaches c_linked_nmf as it is, m x k, and is used only when its column count
+    equals nrow(A) (src/singlet.cpp:1065), that is for k == m.  Returns w m x k, d, h k x n (plus "iter" / "tol")."""
+    shp = getattr(A, "shape", None) or (A.nrow, A.ncol)
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim != 2:
+        raise ValueError("w must be a matrix")
+    for name, Lk in (("link_h", link_h), ("link_w", link_w)):
+        if Lk is not None and np.ndim(Lk) != 2:
+            raise ValueError("%s must be a matrix" % name)
+    _linked_checks(int(shp[0]), int(shp[1]), w.shape, None if link_h is None else _dim2(link_h),
+                   None if link_w is None else _dim2(link_w), L1)
+    if link_h is None:
+        link_h = np.zeros((1, 1))
+    if link_w is None:
+        link_w = np.zeros((1, 1))
+    A = as_dgCMatrix(A)
+    model = c_linked_nmf(A, None, tol, maxit, verbose, L1, L2, threads, w.T, link_h, link_w)
+    _sort_linked(model)
+    return model
+
+
+def RunLNMF(A, model, split_by, link_cutoff=0.5, tol=1e-5, maxit=100, L1=0.01, L2=0, verbose=True, threads=0):
+    """The matrix steps of RunLNMF.Seurat (R/RunLNMF.R:111-159) without the Seurat object, on ONE resident context: A is the
+    assay's @data (the normalised genes x cells matrix), model what run_nmf / RunNMF returned (w m x k, h k x n), split_by one
+    label per cell (any type).
+      1. split_by -> as.factor codes (l.120), as RunNMF makes them; A uploaded once; weight_by_split (l.125);
+      2. the k x G group means of model["h"] on the device (l.136-142: sgl_group_means);
+      3. the share table m / rowSums(m) * G < link_cutoff (l.143) and the link table 1 - unlinked (l.146-154), k x G;
+      4. fit_init(k, t(w)), the link set in its grouped form (the k x n matrix of l.146 is never built: column c of it is
+         column codes[c] of the table), nmf_run(tol, maxit, L1, L1, L2, L2) -- what run_linked_nmf -> c_linked_nmf does
+         (l.159), the same bits as with the expanded matrix;
+      5. sort by d (l.61-64), factor names LNMF_i (l.164).
+    link_w: the reference passes matrix(1, m, k) (l.157); c_linked_nmf ignores it unless k == m (src/singlet.cpp:1065), and
+    then it multiplies by one -- no W-side link is set.
+    Returns w m x k, d, h k x n, "iter", "tol", the names, and
+      "link_table"    k x G, rows in the order of the INPUT factors -- the reference's misc$link_matrix (l.174) is not
+                      re-sorted with the model either; the dense link matrix is link_table[:, codes];
+      "levels"        the group levels (sorted unique labels; codes index them);
+      "factor_order"  the sort index: output factor i is input factor factor_order[i].
+    Refused (ValueError): a missing split_by, one of length nrow(A) -- the reference's transposed branch (l.121-123,
+    161-163) hands t(A) to run_linked_nmf, whose own nrow(w) check (l.51) it cannot pass --, any other wrong length, the
+    stop()s of run_linked_nmf, and a factor whose share row is NaN (all group means zero), where R stops at `if (NA)`."""
+    from .context import Context
+    A = as_dgCMatrix(A)
+    rn, cn = A.Dimnames
+    if split_by is None:
+        raise ValueError("no value specified for 'split.by'")
+    sb = np.asarray(split_by)
+    if sb.ndim != 1:
+        raise ValueError("split_by must be a vector")
+    if sb.shape[0] == A.nrow:
+        raise ValueError("split_by has one entry per ROW of A: the reference then factorises t(A) (R/RunLNMF.R:121-123), which its own "
+                         "check of nrow(w) (l.51) refuses; pass one label per cell (column)")
+    if sb.shape[0] != A.ncol:
+        raise ValueError("length of 'split.by' was not equal to one of the dimensions of the input matrix")
+    w = np.asarray(model["w"], dtype=np.float64)
+    h = np.asarray(model["h"], dtype=np.float64)
+    if w.ndim != 2 or h.ndim != 2:
+        raise ValueError("model['w'] must be m x k and model['h'] k x n")
+    # link_h <- matrix(1, ncol(h), nrow(h)) with h the n x k cell embeddings: its shape is that of model["h"]
+    _linked_checks(A.nrow, A.ncol, w.shape, h.shape, (w.shape[0], w.shape[1]), L1)
+    k = w.shape[1]
+    levels = np.unique(sb)
+    codes = np.searchsorted(levels, sb).astype(np.int32)   # as.integer(as.numeric(as.factor(.))) - 1
+    G = int(levels.size)
+    ctx = Context(0)
+    try:
+        ctx.upload(A, None)
+        ctx.weight_by_split(codes, G)
+        means, _ = ctx.group_means(codes, G, F=h)
+        table = _link_table(means, link_cutoff)
+        ctx.fit_init(k, w)
+        ctx.set_links_grouped(table, codes)
+        n_iter, tr = ctx.nmf_run(float(tol), int(maxit), L1, L1, L2, L2, log=_verbose_log(verbose))
+        W, D, H = ctx.get_factors()
+    finally:
+        ctx.close()
+    out = {"w": W.T, "d": D, "h": H.T, "iter": n_iter, "tol": tr}
+    idx = _sort_linked(out)
+    out["factor_names"] = ["LNMF_%d" % (q + 1) for q in range(k)]
+    out["rownames_w"] = rn
+    out["colnames_h"] = cn
+    out["link_table"] = table
+    out["levels"] = levels
+    out["factor_order"] = idx
+    return out
+
+
+def MetadataSummary(h, factor_data):
+    """R/MetadataSummary.R:15-36: the share of every group of cells in every factor.  h is k x n, factor_data one label per
+    column; levels are the sorted unique labels (as.factor).  The k x G group means come from the device (group_means);
+    each factor's means are divided by their sum (l.26).  Returns {"table": G x k, "levels": the row names in row order,
+    "factors": the column names factor1 ... factork (l.17)}.  With two levels the rows are ordered by their share of the
+    first factor, decreasing (l.27-28).  The hclust reordering of more than two levels (l.29-31) is display order only and is
+    not mirrored: rows stay in level order, columns in factor order."""
+    h = np.asarray(h, dtype=np.float64)
+    fd = np.asarray(factor_data)
+    if h.ndim != 2 or fd.shape != (h.shape[1],):
+        raise ValueError("h must be k x n and factor_data hold one label per column of h")
+    levels = np.unique(fd)
+    codes = np.searchsorted(levels, fd).astype(np.int32)
+    G = int(levels.size)
+    means, _ = group_means(h, codes, G)
+    table = _shares(means).T   # G x k: apply(m, 1, function(x) x / sum(x)) returns the transpose
+    if G == 2:
+        order = np.argsort(-table[:, 0], kind="stable")   # m[order(m[, 1], decreasing = TRUE), ]
+        table, levels = table[order], levels[order]
+    return {"table": table, "levels": levels, "factors": ["factor%d" % (q + 1) for q in range(h.shape[0])]}
+
+
+def _unique_mask(h, split_by):
+    t = MetadataSummary(h, split_by)["table"]
+    with np.errstate(invalid="ignore"):
+        return np.min(t, axis=0) == 0   # apply(., 2, function(x) min(x) == 0); NaN compares false, as which() drops NA
+
+
+def GetUniqueFactors(h, split_by):
+    """R/GetUniqueFactors.R:4-10 on a k x n embedding: the 0-based indices of the factors whose smallest share over the groups
+    (MetadataSummary) is exactly 0 -- factors some group does not carry at all."""
+    return np.flatnonzero(_unique_mask(h, split_by))
+
+
+def GetSharedFactors(h, split_by):
+    """R/GetSharedFactors.R:4-10: the 0-based indices of all other factors.  A factor whose shares are NaN counts as shared,
+    as which() drops NA."""
+    return np.flatnonzero(~_unique_mask(h, split_by))
 
 
 # ---------------------------------------------------------------------------

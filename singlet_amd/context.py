@@ -110,6 +110,43 @@ def _chunk_list(chunks):
     return (n, xs, is_, ps, ptr(nc, i32p)), (chunks, xs, is_, ps, nc)
 
 
+def _link_image(Lk):
+    """ctypes image of an R link matrix (rows x cols): (pointer, rows, cols, the buffer to keep alive); None switches the side off."""
+    if Lk is None:
+        return None, 0, 0, None
+    Lk = np.asarray(Lk, dtype=np.float64)
+    if Lk.ndim != 2:
+        raise ValueError("link matrices must be 2-D")
+    buf = np.ascontiguousarray(Lk.T)   # column-major image of the R matrix
+    return ptr(buf, f64p), Lk.shape[0], Lk.shape[1], buf
+
+
+def _group_list(group, n, what):
+    """int32 image of a list of group ids, one per cell (gene); the library checks their range."""
+    g = np.asarray(group)
+    if g.ndim != 1 or (n is not None and g.shape[0] != n):
+        raise ValueError("%s must hold one group id per %s" % (what, "entry" if n is None else "column (%d)" % n))
+    if g.dtype.kind not in "iu" and g.dtype.kind != "b":
+        raise ValueError("%s must hold integer group ids" % what)
+    if g.size and (g.min() < -2**31 or g.max() >= 2**31):
+        raise ValueError("%s holds an id outside the 32-bit range" % what)
+    return np.ascontiguousarray(g, dtype=np.int32)
+
+
+def _grouped_side(table, group, n, side):
+    """(pointer, rows, groups, group pointer, what to keep alive) of one side of set_links_grouped; a None table is off."""
+    if table is None:
+        return None, 0, 0, None, None
+    T = np.asarray(table, dtype=np.float64)
+    if T.ndim != 2:
+        raise ValueError("table_%s must be a rows x groups matrix" % side)
+    if group is None:
+        raise ValueError("table_%s needs group_%s" % (side, side))
+    g = _group_list(group, n, "group_" + side)
+    buf = np.ascontiguousarray(T.T)   # column-major image
+    return ptr(buf, f64p), T.shape[0], T.shape[1], ptr(g, i32p), (buf, g)
+
+
 class Context:
     def __init__(self, device=0, _borrowed=None):
         self._L = _lib.load()
@@ -284,6 +321,45 @@ class Context:
                 raise ValueError("w_init must be k x nrow(A) (got %r for k=%d, nrow=%d)" % (w.shape[::-1], k, nr))
         check(self._L.sgl_fit_init(self._h, int(k), ptr(w, f64p), synth_seed))
         self.k = int(k)
+
+    def set_links(self, link_h=None, link_w=None):
+        """c_linked_nmf's link matrices (sgl_set_links; rows x cols, as R holds them: link_h rows x cells of this shard,
+        link_w rows x genes); a matrix whose column count does not match its side is ignored, None switches a side off.
+        Call after fit_init (which drops them)."""
+        lh, lhr, lhc, k1 = _link_image(link_h)
+        lw, lwr, lwc, k2 = _link_image(link_w)
+        check(self._L.sgl_set_links(self._h, lh, lhr, lhc, lw, lwr, lwc))
+
+    def set_links_grouped(self, table_h, group_h, table_w=None, group_w=None):
+        """The grouped form of the links (sgl_set_links_grouped): exactly set_links(table_h[:, group_h], table_w[:, group_w])
+        without the expanded matrices -- table_* rows x groups, group_* one 0-based id per cell (gene).  Same bits, same
+        lifetime; a None table switches its side off; either call replaces what the other set."""
+        nr, nc, _ = self.dims()
+        th, rh, gh, ph, k1 = _grouped_side(table_h, group_h, nc, "h")
+        tw, rw, gw, pw, k2 = _grouped_side(table_w, group_w, nr, "w")
+        check(self._L.sgl_set_links_grouped(self._h, th, rh, gh, ph, tw, rw, gw, pw))
+
+    def group_means(self, group, n_groups, F=None):
+        """(means k x n_groups, counts) of the columns of F (k x n, R's orientation) per group (sgl_group_means); F = None:
+        of the H of the current fit, read where it is.  An empty group gives a NaN column and a count of 0."""
+        if F is None:
+            _, n, _ = self.dims()
+            k, Fp = self.k, None
+            if k == 0:   # no fit: the library refuses (SGL_ESTATE) before it reads the list
+                n = None
+        else:
+            Fa = np.asarray(F, dtype=np.float64)
+            if Fa.ndim != 2:
+                raise ValueError("F must be a k x n matrix")
+            k, n = Fa.shape
+            buf = np.ascontiguousarray(Fa.T)   # column-major image
+            Fp = ptr(buf, f64p)
+        g = _group_list(group, n, "group")
+        G = int(n_groups)
+        means = np.empty((max(G, 0), k))
+        counts = np.zeros(max(G, 0), dtype=np.int64)
+        check(self._L.sgl_group_means(self._h, Fp, int(k), int(g.shape[0]), ptr(g, i32p), G, ptr(means, f64p), ptr(counts, i64p)))
+        return means.T, counts
 
     def set_graph(self, G):
         """c_gcnmf's cell graph (sgl_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over the resident cells, or None
@@ -602,15 +678,27 @@ class Multi:
 
     def set_links(self, link_h=None, link_w=None):
         """c_linked_nmf's link matrices (rows x cols, as R holds them) for the whole matrix; call after fit_init."""
-        def img(Lk):
-            if Lk is None:
-                return None, 0, 0, None
-            Lk = np.asarray(Lk, dtype=np.float64)
-            buf = np.ascontiguousarray(Lk.T)   # column-major image of the R matrix
-            return ptr(buf, f64p), Lk.shape[0], Lk.shape[1], buf
-        lh, lhr, lhc, k1 = img(link_h)
-        lw, lwr, lwc, k2 = img(link_w)
+        lh, lhr, lhc, k1 = _link_image(link_h)
+        lw, lwr, lwc, k2 = _link_image(link_w)
         check(self._L.sgl_multi_set_links(self._h, lh, lhr, lhc, lw, lwr, lwc))
+
+    def set_links_grouped(self, table_h, group_h, table_w=None, group_w=None):
+        """Context.set_links_grouped for the whole matrix (sgl_multi_set_links_grouped): group_h holds one id per cell of ALL
+        cells and follows them to the ranks; the tables and group_w go to every rank."""
+        nr, nc = self._dims
+        th, rh, gh, ph, k1 = _grouped_side(table_h, group_h, nc, "h")
+        tw, rw, gw, pw, k2 = _grouped_side(table_w, group_w, nr, "w")
+        check(self._L.sgl_multi_set_links_grouped(self._h, th, rh, gh, ph, tw, rw, gw, pw))
+
+    def group_means(self, group, n_groups):
+        """(means k x n_groups, counts) of the H of the team's fit per group of cells (sgl_multi_group_means): every rank sums
+        its cells, the rank partials are added in rank order and divided by the counts over all ranks."""
+        g = _group_list(group, self._dims[1], "group")
+        G = int(n_groups)
+        means = np.empty((max(G, 0), self.k))
+        counts = np.zeros(max(G, 0), dtype=np.int64)
+        check(self._L.sgl_multi_group_means(self._h, ptr(g, i32p), G, ptr(means, f64p), ptr(counts, i64p)))
+        return means.T, counts
 
     def set_graph(self, G):
         """c_gcnmf's cell graph for the team (sgl_multi_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over ALL

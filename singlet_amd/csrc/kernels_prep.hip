@@ -94,3 +94,47 @@ int k_link_mul(hipStream_t s, double* B, const double* L, int k, int link_rows, 
     HIPCHK(hipGetLastError());
     return SGL_OK;
 }
+
+// The same multiplication with the link column looked up by group (sgl_set_links_grouped): B[j, c] *= T[j, group[c]] for
+// j < rows, T rows x n_groups column-major.  ONE multiplication per entry, as link_mul_kernel does it, so a fit gives the
+// same bits as with the expanded matrix -- never a select: b * 0.0 keeps the sign of b, and b * NaN is NaN.
+// FL = min(64, rows rounded up to a power of two) lanes run over the rows of a cell and 256 / FL slots over the cells; a
+// lane loads the group id once per cell and then walks the rows j = lane, lane + FL, ...  With LDS the workgroup first
+// copies the table (rows * n_groups * 8 <= SGL_GLINK_LDS_BYTES) into LDS -- once per workgroup, each of which then serves
+// many rounds of cells -- otherwise the table is read through the cache.
+template <bool LDS>
+__global__ __launch_bounds__(256) void link_mul_grouped_kernel(double* __restrict__ B, const double* __restrict__ T,
+                                                               const int32_t* __restrict__ group, int k, int rows, int n_groups,
+                                                               int64_t ncols, int fl_shift) {
+    extern __shared__ double tab[];
+    if (LDS) {
+        const int total = rows * n_groups;
+        for (int e = threadIdx.x; e < total; e += 256) tab[e] = T[e];
+        __syncthreads();
+    }
+    const int FL = 1 << fl_shift;
+    const int S = 256 >> fl_shift;
+    const int fl = threadIdx.x & (FL - 1);
+    const int slot = threadIdx.x >> fl_shift;
+    for (int64_t c = (int64_t)blockIdx.x * S + slot; c < ncols; c += (int64_t)gridDim.x * S) {
+        const int64_t t0 = (int64_t)group[c] * rows;
+        double* b = B + c * k;
+        for (int j = fl; j < rows; j += FL) b[j] *= LDS ? tab[t0 + j] : T[t0 + j];
+    }
+}
+
+int k_link_mul_grouped(hipStream_t s, double* B, const double* T, const int32_t* group, int k, int rows, int n_groups, int64_t ncols) {
+    if (ncols <= 0 || rows <= 0) return SGL_OK;
+    int fl_shift = 0;
+    while ((1 << fl_shift) < rows && fl_shift < 6) ++fl_shift;
+    const int S = 256 >> fl_shift;
+    int64_t blocks = (ncols + S - 1) / S;
+    if (blocks > 256 * 8) blocks = 256 * 8;   // eight workgroups per CU: the staged table is re-read by 2048 workgroups at most
+    const size_t bytes = sizeof(double) * (size_t)rows * (size_t)n_groups;
+    if (bytes <= SGL_GLINK_LDS_BYTES)
+        link_mul_grouped_kernel<true><<<dim3((unsigned)blocks), dim3(256), bytes, s>>>(B, T, group, k, rows, n_groups, ncols, fl_shift);
+    else
+        link_mul_grouped_kernel<false><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(B, T, group, k, rows, n_groups, ncols, fl_shift);
+    HIPCHK(hipGetLastError());
+    return SGL_OK;
+}

@@ -756,6 +756,7 @@ static int team_iterate(sgl_team* T, double L1_w, double L1_h, double L2_w, doub
             double* Bblk = c->red + (size_t)g0 * k;
             SGLCHK(k_scale_apply(c->stream, Bblk, k, ng, c->d, 0));
             if (c->link_w) SGLCHK(k_link_mul(c->stream, Bblk, c->link_w + (size_t)g0 * c->link_w_rows, k, c->link_w_rows, ng));  // predict_link l.429-430
+            else if (c->glink_w.table) SGLCHK(k_link_mul_grouped(c->stream, Bblk, c->glink_w.table, c->glink_w.group + g0, k, c->glink_w.rows, c->glink_w.groups, ng));
             const int64_t* gene_nnz = (N > 1) ? c->col_nnz_At_global : c->col_nnz_At;
             if (N > 1 && !c->gene_nnz_global) { sgl_set_error("team: global gene counts missing"); return SGL_ESTATE; }
             // (the dense front-end solves every column, src/singlet.cpp:370-381: no skip list)
@@ -1201,6 +1202,46 @@ extern "C" int sgl_multi_set_links(sgl_multi* M, const double* link_h, int32_t l
     return SGL_OK;
 }
 
+// the grouped form (sgl_set_links_grouped) for the whole matrix: group_h follows the cells to the ranks, the tables and
+// group_w go to every rank; both lists are checked over the whole matrix before the first rank is touched
+extern "C" int sgl_multi_set_links_grouped(sgl_multi* M, const double* table_h, int32_t rows_h, int32_t groups_h, const int32_t* group_h,
+                                           const double* table_w, int32_t rows_w, int32_t groups_w, const int32_t* group_w) {
+    TEAM_GUARD(M);
+    if (M->cell_lo.empty()) { sgl_set_error("sgl_multi_set_links_grouped: no matrix resident"); return SGL_ESTATE; }
+    const bool use_h = table_h && rows_h > 0, use_w = table_w && rows_w > 0;
+    if (use_h && group_h && groups_h >= 1) SGLCHK(sgl_group_ids_check("sgl_multi_set_links_grouped", "group_h", group_h, M->ncells_total, groups_h));
+    if (use_w && group_w && groups_w >= 1) SGLCHK(sgl_group_ids_check("sgl_multi_set_links_grouped", "group_w", group_w, M->nrow, groups_w));
+    for (int r = 0; r < M->nranks; ++r)
+        SGLCHK(sgl_set_links_grouped(M->local[r], table_h, rows_h, groups_h, (use_h && group_h) ? group_h + M->cell_lo[r] : nullptr, table_w, rows_w,
+                                     groups_w, group_w));
+    return SGL_OK;
+}
+
+// group means of the team's H (include/singlet_hip.h): rank partials in rank order, one division by the global counts
+extern "C" int sgl_multi_group_means(sgl_multi* M, const int32_t* group, int32_t n_groups, double* means, int64_t* counts) {
+    TEAM_GUARD(M);
+    if (M->cell_lo.empty() || M->local[0]->k == 0) { sgl_set_error("sgl_multi_group_means: no fit initialised (call sgl_multi_fit_init)"); return SGL_ESTATE; }
+    if (n_groups < 1) { sgl_set_error("sgl_multi_group_means: n_groups = %d: at least one group is needed", n_groups); return SGL_EINVAL; }
+    if (!group || !means || !counts) { sgl_set_error("sgl_multi_group_means: NULL group list or output"); return SGL_EINVAL; }
+    SGLCHK(sgl_group_ids_check("sgl_multi_group_means", "group", group, M->ncells_total, n_groups));
+    const int k = M->local[0]->k;
+    const size_t kg = (size_t)k * (size_t)n_groups;
+    std::vector<double> part(kg), total(kg, 0.0);
+    std::vector<int64_t> cnt((size_t)n_groups);
+    for (int32_t g = 0; g < n_groups; ++g) counts[g] = 0;
+    for (int r = 0; r < M->nranks; ++r) {
+        sgl_ctx* c = M->local[r];
+        const int64_t lo = M->cell_lo[r], nloc = M->cell_lo[r + 1] - lo;
+        HIPCHK(hipSetDevice(c->device));
+        SGLCHK(sgl_group_sums_dev(c, c->H, k, nloc, group + lo, n_groups, false, part.data(), cnt.data()));
+        for (size_t e = 0; e < kg; ++e) total[e] += part[e];
+        for (int32_t g = 0; g < n_groups; ++g) counts[g] += cnt[g];
+    }
+    for (int32_t g = 0; g < n_groups; ++g)
+        for (int f = 0; f < k; ++f) means[(size_t)g * k + f] = total[(size_t)g * k + f] / (double)counts[g];
+    return SGL_OK;
+}
+
 // ------------------------------------------------------- c_gcnmf on the team --
 // The halo plan (header, section 2b): which cells every rank exports and the row indices of every rank's columns in terms
 // of [own cells | slab].  Pure host code.
@@ -1266,7 +1307,7 @@ extern "C" int sgl_multi_set_graph(sgl_multi* M, const double* Gx, const int32_t
     if (!Gx || !Gi || !Gp) { sgl_set_error("sgl_multi_set_graph: G must be fully given or fully NULL"); return SGL_EINVAL; }
     for (auto c : M->local) {
         if (c->dense_input) { sgl_set_error("sgl_multi_set_graph: the matrix was uploaded dense (c_gcnmf takes a dgCMatrix)"); return SGL_EINVAL; }
-        if (c->link_h || c->link_w) { sgl_set_error("sgl_multi_set_graph: link matrices are set (the reference has no linked graph-convolutional NMF)"); return SGL_EINVAL; }
+        if (sgl_has_links(c)) { sgl_set_error("sgl_multi_set_graph: link matrices are set (the reference has no linked graph-convolutional NMF)"); return SGL_EINVAL; }
     }
     const int64_t n = M->ncells_total;
     SGLCHK(sgl_graph_check("sgl_multi_set_graph", Gx, Gi, Gp, G_nrow, G_ncol, n));

@@ -184,6 +184,14 @@ struct DevGraph {
     double* halo = nullptr;     // [team size * E * k] block s = the exported columns of rank s (all-gathered in place)
 };
 
+// The grouped form of one side's link matrix (sgl_set_links_grouped): column c of the link is column group[c] of a
+// rows x groups table, so rows * groups doubles and 4 bytes per cell / gene are resident instead of rows x cols doubles.
+struct DevGroupLink {
+    double* table = nullptr;   // rows x groups, column-major (nullptr: this side has no grouped link)
+    int32_t* group = nullptr;  // one id in [0, groups) per local cell (H side) / per gene (W side)
+    int rows = 0, groups = 0;
+};
+
 struct sgl_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -214,6 +222,7 @@ struct sgl_ctx {
     double* link_h = nullptr;  // c_linked_nmf: link_rows x ncol / x nrow multipliers of the right-hand sides
     double* link_w = nullptr;
     int link_h_rows = 0, link_w_rows = 0;
+    DevGroupLink glink_h, glink_w;   // the grouped form: a side holds the dense matrix, the grouped table or nothing
     DevGraph graph;            // c_gcnmf: right-hand sides convolved over the cell graph (sgl_set_graph); dropped with the fit
     bool dense_input = false;  // the resident matrix came from sgl_upload_dense (a graph is refused there)
     DevMaskList ML[2];         // masked path: the drawn rows of every column, per orientation (kernels_mask.hip); live with the entry streams
@@ -259,6 +268,8 @@ int sgl_step_h_solve(sgl_ctx* c, double L1, double L2, bool convolve);
 int sgl_graph_check(const char* who, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t G_nrow, int32_t G_ncol, int64_t n);
 int sgl_graph_upload(sgl_ctx* c, const char* who, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t ncol);
 void sgl_graph_clear(sgl_ctx* c);
+// links of either form on either side (a graph is refused next to them)
+inline bool sgl_has_links(const sgl_ctx* c) { return c->link_h || c->link_w || c->glink_h.table || c->glink_w.table; }
 int sgl_scale_w_enqueue(sgl_ctx* c);            // scale(w, d); cor(w, w_prev) -> device scalar
 int sgl_scale_w_fetch(sgl_ctx* c, double* tol); // copy it out (synchronises the stream)
 // masked path pieces (singlet_hip.hip) used by the team's sharded c_ard_nmf (multi.hip)
@@ -404,6 +415,19 @@ bool sgl_dense_gemm_available();
 int k_colsum(hipStream_t s, const DevCSC& M, double* sums);
 int k_cell_factor(hipStream_t s, DevCSC& A, DevCSC& At, const double* f, int mode, double scale);
 int k_link_mul(hipStream_t s, double* B, const double* L, int k, int link_rows, int64_t ncols);
+// the same multiplication with the link column looked up by group: B[j, c] *= T[j, group[c]], j < rows (T rows x n_groups)
+int k_link_mul_grouped(hipStream_t s, double* B, const double* T, const int32_t* group, int k, int rows, int n_groups, int64_t ncols);
+#define SGL_GLINK_LDS_BYTES (32 * 1024)   // a table of up to this many bytes is staged in LDS; a larger one is read through the cache
+
+// group sums (kernels_group.hip): F k x n column-major on the device, group[c] in [0, n_groups) on the HOST (checked by the
+// caller).  out (k x n_groups, host) = the sums of F's columns per group -- divided by the group's cell count when
+// `divide` (0 / 0 = NaN for an empty group) -- and counts (n_groups, host).  The summation order depends on (n, group,
+// n_groups) alone.  Synchronises the stream.
+#define SGL_GROUP_CHUNK 256   // cells per chunk of a group's cell list
+int sgl_group_sums_dev(sgl_ctx* c, const double* F, int k, int64_t n, const int32_t* group, int32_t n_groups, bool divide,
+                       double* out, int64_t* counts);
+// SGL_EINVAL naming the list, the position and the value of the first id outside [0, n_groups)
+int sgl_group_ids_check(const char* who, const char* name, const int32_t* group, int64_t n, int32_t n_groups);
 
 // row-wise rasterisation (kernels_raster.hip): out (nb x ncol, column-major) = means of rows [b n, b n + n), nb >= 1
 int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, double* out);

@@ -155,6 +155,18 @@ static void free_graph(sgl_ctx* c) {
 }
 void sgl_graph_clear(sgl_ctx* c) { free_graph(c); }
 
+// both forms of the link matrices, both sides
+static void links_clear(sgl_ctx* c) {
+    dev_free(c->link_h);
+    dev_free(c->link_w);
+    c->link_h_rows = c->link_w_rows = 0;
+    for (DevGroupLink* g : {&c->glink_h, &c->glink_w}) {
+        dev_free(g->table);
+        dev_free(g->group);
+        *g = DevGroupLink();
+    }
+}
+
 // keep_streams: the entry streams (and their buffers) survive a re-init of the fit on the SAME matrix -- every
 // path that changes the matrix calls free_fit(c) without it
 static void free_fit(sgl_ctx* c, bool keep_streams = false) {
@@ -172,10 +184,7 @@ static void free_fit(sgl_ctx* c, bool keep_streams = false) {
     dev_free(c->Sbuf);
     dev_free(c->Stri);
     nnls_scratch_free(c->nnls_scr);
-    dev_free(c->link_h);
-    dev_free(c->link_w);
-    c->link_h = c->link_w = nullptr;
-    c->link_h_rows = c->link_w_rows = 0;
+    links_clear(c);
     free_graph(c);
     dev_free(c->A.seg);
     dev_free(c->At.seg);
@@ -1005,6 +1014,7 @@ int sgl_step_h_rhs(sgl_ctx* c, bool convolve) {
       else if (c->use_tiled) SGLCHK(k_acc_tiled_all(c->stream, c->TA, c->W, c->B, k));
       else SGLCHK(k_acc(c->stream, c->A, c->W, k, c->B, 0, 1, 0, 0, 0));
       if (c->link_h) SGLCHK(k_link_mul(c->stream, c->B, c->link_h, k, c->link_h_rows, c->A.ncol));  // predict_link l.429-430
+      else if (c->glink_h.table) SGLCHK(k_link_mul_grouped(c->stream, c->B, c->glink_h.table, c->glink_h.group, k, c->glink_h.rows, c->glink_h.groups, c->A.ncol));
       if (c->graph.n && convolve) SGLCHK(k_graph_conv(c->stream, c->graph, c->B, c->graph.buf, k)); }  // gcnmf_update_h l.1684-1688: Bc = B G
     return SGL_OK;
 }
@@ -1063,6 +1073,7 @@ extern "C" int sgl_step_w(sgl_ctx* c, double L1, double L2) {
       SGLCHK(k_gram_add_diag(c->stream, c->G, k, 1e-15)); }
     { Phase ph(c, SGL_PH_NNLS_W);
       if (c->link_w) SGLCHK(k_link_mul(c->stream, Bw, c->link_w, k, c->link_w_rows, m));  // on the complete (all-reduced) sums
+      else if (c->glink_w.table) SGLCHK(k_link_mul_grouped(c->stream, Bw, c->glink_w.table, c->glink_w.group, k, c->glink_w.rows, c->glink_w.groups, m));
       SGLCHK(sgl_nnls_shared(c, c->G, Bw, c->W, (c->solve_empty || c->graph.n) ? nullptr : gene_nnz, m, L1, L2, c->sweep_counters + 1)); }
     return SGL_OK;
 }
@@ -1578,10 +1589,7 @@ extern "C" int sgl_set_links(sgl_ctx* c, const double* link_h, int32_t link_h_ro
         sgl_set_error("sgl_set_links: a cell graph is set (the reference has no linked graph-convolutional NMF)");
         return SGL_EINVAL;
     }
-    dev_free(c->link_h);
-    dev_free(c->link_w);
-    c->link_h = c->link_w = nullptr;
-    c->link_h_rows = c->link_w_rows = 0;
+    links_clear(c);   // the grouped form too: each of sgl_set_links / sgl_set_links_grouped replaces what the other set
     if (link_h && link_h_cols == c->A.ncol && link_h_rows > 0) {
         if (link_h_rows > c->k) { sgl_set_error("sgl_set_links: link_h has more rows (%d) than the rank (%d)", link_h_rows, c->k); return SGL_EINVAL; }
         SGLCHK(dev_alloc(&c->link_h, (size_t)link_h_rows * link_h_cols));
@@ -1614,6 +1622,91 @@ extern "C" int sgl_c_linked_nmf(const double* Ax, const int32_t* Ai, const int32
     SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, Atx, Ati, Atp, nrow, ncol, 0, ncol));
     return one_shot_fit(hd, {k, w_init, tol, maxit, L1, L1, L2, L2, nullptr, w_out, d_out, h_out, n_iter, tol_trace, cb},
                         [&](sgl_ctx* c) { return sgl_set_links(c, link_h, link_h_rows, link_h_cols, link_w, link_w_rows, link_w_cols); });
+}
+
+// The grouped form of the links (include/singlet_hip.h): as sgl_set_links with link[j, c] = table[j, group[c]].  Everything
+// that can be refused without touching the links set before -- arguments, group ids -- is checked first; from the graph
+// test on the order is sgl_set_links' own.
+static int glink_upload(sgl_ctx* c, DevGroupLink& g, const double* table, int32_t rows, int32_t groups, const int32_t* group, int64_t n) {
+    SGLCHK(dev_alloc(&g.table, (size_t)rows * (size_t)groups));
+    SGLCHK(dev_alloc(&g.group, (size_t)std::max<int64_t>(n, 1)));
+    HIPCHK(hipMemcpyAsync(g.table, table, sizeof(double) * (size_t)rows * (size_t)groups, hipMemcpyHostToDevice, c->stream));
+    if (n > 0) HIPCHK(hipMemcpyAsync(g.group, group, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    g.rows = rows;
+    g.groups = groups;
+    return SGL_OK;
+}
+extern "C" int sgl_set_links_grouped(sgl_ctx* c, const double* table_h, int32_t rows_h, int32_t groups_h, const int32_t* group_h,
+                                     const double* table_w, int32_t rows_w, int32_t groups_w, const int32_t* group_w) {
+    FIT_GUARD(c);
+    const bool use_h = table_h && rows_h > 0, use_w = table_w && rows_w > 0;
+    if ((use_h && groups_h < 1) || (use_w && groups_w < 1)) {
+        sgl_set_error("sgl_set_links_grouped: n_groups = %d: a link table needs at least one group", use_h && groups_h < 1 ? groups_h : groups_w);
+        return SGL_EINVAL;
+    }
+    if ((use_h && !group_h) || (use_w && !group_w)) { sgl_set_error("sgl_set_links_grouped: a link table without its group list"); return SGL_EINVAL; }
+    if (use_h) SGLCHK(sgl_group_ids_check("sgl_set_links_grouped", "group_h", group_h, c->A.ncol, groups_h));
+    if (use_w) SGLCHK(sgl_group_ids_check("sgl_set_links_grouped", "group_w", group_w, c->A.nrow, groups_w));
+    if (c->graph.n && (use_h || use_w)) {
+        sgl_set_error("sgl_set_links_grouped: a cell graph is set (the reference has no linked graph-convolutional NMF)");
+        return SGL_EINVAL;
+    }
+    links_clear(c);
+    int rc = SGL_OK;
+    if (use_h) {
+        if (rows_h > c->k) { sgl_set_error("sgl_set_links_grouped: table_h has more rows (%d) than the rank (%d)", rows_h, c->k); return SGL_EINVAL; }
+        rc = glink_upload(c, c->glink_h, table_h, rows_h, groups_h, group_h, c->A.ncol);
+    }
+    if (rc == SGL_OK && use_w) {
+        if (rows_w > c->k) {
+            links_clear(c);
+            sgl_set_error("sgl_set_links_grouped: table_w has more rows (%d) than the rank (%d)", rows_w, c->k); return SGL_EINVAL;
+        }
+        rc = glink_upload(c, c->glink_w, table_w, rows_w, groups_w, group_w, c->A.nrow);
+    }
+    const hipError_t e = hipStreamSynchronize(c->stream);   // the host arrays are the caller's again on return
+    if (rc == SGL_OK && e != hipSuccess) { sgl_set_error("sgl_set_links_grouped: %s", hipGetErrorString(e)); rc = SGL_EHIP; }
+    if (rc != SGL_OK) links_clear(c);
+    return rc;
+}
+
+// Group means (include/singlet_hip.h; kernels_group.hip): of a host F through a temporary device copy, or of the fit's H in place.
+static int group_means_args(const char* who, int32_t k, int64_t n, const int32_t* group, int32_t n_groups, const double* means,
+                            const int64_t* counts) {
+    if (n_groups < 1) { sgl_set_error("%s: n_groups = %d: at least one group is needed", who, n_groups); return SGL_EINVAL; }
+    if (!group || !means || !counts) { sgl_set_error("%s: NULL group list or output", who); return SGL_EINVAL; }
+    if (n < 0 || n > INT32_MAX) { sgl_set_error("%s: n = %lld cells is outside [0, 2^31)", who, (long long)n); return SGL_EINVAL; }
+    SGLCHK(rank_check(k));
+    return sgl_group_ids_check(who, "group", group, n, n_groups);
+}
+extern "C" int sgl_group_means(sgl_ctx* c, const double* F, int32_t k, int64_t n, const int32_t* group, int32_t n_groups, double* means,
+                               int64_t* counts) {
+    CTX_GUARD(c);
+    if (c->team || c->allreduce) {
+        sgl_set_error("sgl_group_means: the context is a shard of a team or has an all-reduce hook; the means of this shard's cells "
+                      "are not the matrix's (a team: sgl_multi_group_means)");
+        return SGL_ESTATE;
+    }
+    if (!F && c->k == 0) { sgl_set_error("sgl_group_means: F is NULL and no fit is initialised (call sgl_fit_init)"); return SGL_ESTATE; }
+    if (!F && (k != c->k || n != c->A.ncol)) {
+        sgl_set_error("sgl_group_means: F is NULL, but k = %d, n = %lld are not the fit's %d x %d", k, (long long)n, c->k, c->A.ncol);
+        return SGL_EINVAL;
+    }
+    SGLCHK(group_means_args("sgl_group_means", k, n, group, n_groups, means, counts));
+    if (!F) return sgl_group_sums_dev(c, c->H, k, n, group, n_groups, true, means, counts);
+    DevBuf<double> dF;
+    SGLCHK(dF.alloc((size_t)k * (size_t)std::max<int64_t>(n, 1)));
+    if (n > 0) HIPCHK(hipMemcpyAsync(dF.p, F, sizeof(double) * (size_t)k * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    return sgl_group_sums_dev(c, dF.p, k, n, group, n_groups, true, means, counts);   // (synchronises before dF goes)
+}
+
+extern "C" int sgl_c_group_means(const double* F, int32_t k, int64_t n, const int32_t* group, int32_t n_groups, double* means,
+                                 int64_t* counts) {
+    if (!F) { sgl_set_error("sgl_c_group_means: F is NULL"); return SGL_EINVAL; }
+    SGLCHK(group_means_args("sgl_c_group_means", k, n, group, n_groups, means, counts));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    return sgl_group_means(hd.c, F, k, n, group, n_groups, means, counts);
 }
 
 // c_gcnmf's cell graph G (src/singlet.cpp:1668-1730): n x n, n = the cells of the resident matrix, as a dgCMatrix.  Checked
@@ -1706,7 +1799,7 @@ extern "C" int sgl_set_graph(sgl_ctx* c, const double* Gx, const int32_t* Gi, co
     // the reference defines none of these combinations
     if (c->allreduce) { sgl_set_error("sgl_set_graph: an all-reduce hook is installed (graph-convolutional NMF runs on one shard)"); return SGL_EINVAL; }
     if (c->dense_input) { sgl_set_error("sgl_set_graph: the matrix was uploaded dense (c_gcnmf takes a dgCMatrix)"); return SGL_EINVAL; }
-    if (c->link_h || c->link_w) { sgl_set_error("sgl_set_graph: link matrices are set (the reference has no linked graph-convolutional NMF)"); return SGL_EINVAL; }
+    if (sgl_has_links(c)) { sgl_set_error("sgl_set_graph: link matrices are set (the reference has no linked graph-convolutional NMF)"); return SGL_EINVAL; }
     SGLCHK(sgl_graph_check("sgl_set_graph", Gx, Gi, Gp, G_nrow, G_ncol, c->A.ncol));
     return sgl_graph_upload(c, "sgl_set_graph", Gx, Gi, Gp, c->A.ncol);
 }
