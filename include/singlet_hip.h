@@ -335,6 +335,46 @@ SGL_API int sgl_upload_csc_list(sgl_ctx* ctx, int32_t n_chunks, const double* co
                         const int32_t* t_chunk_ncol,
                         int32_t nrow, int64_t cell_offset, int64_t ncells_total);
 
+/* The arrays of a SciPy / AnnData / torch CSR or CSC as the caller holds them: n_major + 1 offsets, and per stored entry
+ * an index below n_minor and a value.  On success the context holds exactly what sgl_upload_csc(ctx, x64, i32, p32,
+ * NULL...) leaves for the same matrix converted, sorted and (major_is_genes = 1) transposed on the host, bit for bit:
+ *  - major_is_genes = 0: a major slice is a cell; the arrays are the CSC of A (= the CSR of t(A)) and fill A, t(A) is
+ *    its device transpose.  major_is_genes = 1: a major slice is a gene; the arrays are the CSC of t(A) (= the CSR of A)
+ *    and fill t(A), A is its device transpose.  A is n_minor x n_major or n_major x n_minor accordingly.
+ *  - values: F32 and I32 widen exactly; an I64 beyond +-2^53 is refused ("inexact"); NaN / Inf is refused like at every
+ *    door; explicit zeros stay stored.
+ *  - indices: an I64 index is range-checked as a 64-bit number before it is narrowed (2^32 + 3 is out of range, never
+ *    row 3).
+ *  - offsets: ptr[0] == 0, non-decreasing; ptr[n_major] is the entry count (above 2^31 - 1 is legal with I64 offsets).
+ *    HOST space: checked on the host.  DEVICE space: checked by a kernel, the count read back; the host never
+ *    dereferences a device pointer.
+ *  - order: without SGL_UP_SORT a slice whose indices are not strictly ascending is refused.  With it the (index, value)
+ *    pairs of every slice that is out of order -- and of no other -- are sorted by index on the device; two equal
+ *    indices in one slice are refused either way (duplicate entries are not summed).
+ *  - space: HOST arrays are pageable host memory, copied once each.  DEVICE arrays must be device memory of the
+ *    context's device (hipPointerGetAttributes, asked for all three before any copy; SGL_EINVAL otherwise); they are
+ *    read on the context's stream and not retained, and the caller guarantees that their producer has finished.
+ *  - n_major / n_minor outside [1, 2^31 - 1], an unknown type code, space, flag bit or major_is_genes: SGL_EINVAL before
+ *    anything is allocated.  Every refusal or failure leaves NO matrix resident.
+ *  - report (NULL or 8 values, written on success): [0] entries, [1] slices sorted in LDS, [2] slices sorted by the long
+ *    path, [3] 1 if every stored value equals its truncation, [4] bytes read from the caller's arrays, [5] the LDS
+ *    sort's capacity in entries, [6], [7] 0. */
+#define SGL_T_F64 0
+#define SGL_T_F32 1
+#define SGL_T_I32 2
+#define SGL_T_I64 3
+#define SGL_SPACE_HOST 0
+#define SGL_SPACE_DEVICE 1
+#define SGL_UP_SORT 1u        /* indices of a major slice may come in any order: sorted on the device */
+SGL_API int sgl_upload_typed(sgl_ctx* ctx, const void* x, int x_type, const void* idx, int idx_type,
+                     const void* ptr, int ptr_type, int64_t n_major, int64_t n_minor, int major_is_genes,
+                     int space, uint32_t flags, int64_t cell_offset, int64_t ncells_total, int64_t* report);
+
+/* Host only (no device): the batches of sgl_upload_typed's long sort path.  The n slices of len[s] >= 0 entries are cut,
+ * in order, into runs [cut[b], cut[b + 1]) of whole slices whose entries sum to at most max_entries >= 1 (a longer
+ * slice is a run of its own); cut has room for n + 1 values, *n_runs receives the number of runs. */
+SGL_API int sgl_ingest_batch_edges(const int64_t* len, int64_t n, int64_t max_entries, int64_t* cut, int64_t* n_runs);
+
 /* A dense matrix (nrow x ncol, column-major doubles, as R / Eigen hold it; what c_nmf_dense and c_ard_nmf_dense take,
  * src/singlet.cpp:1052-1054, 1357-1361): resident as its CSC image (zeros dropped, both orientations, built on the
  * device) and -- when more than half of its entries are non-zero -- as the dense copy itself, on which the plain fit then

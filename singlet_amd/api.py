@@ -37,6 +37,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
 from .context import _chunk_list, make_callbacks
+from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
 
 
@@ -341,9 +342,37 @@ def _sort_model(model, rn=None, cn=None):
     return model
 
 
+class _NativeStage:
+    """A NativeMatrix (native()) staged on one Context through the typed door: `with _NativeStage(N) as st` gives st.ctx,
+    st.report (Context.upload_native) and st.fits, the resident fits the drivers already run on (as RunNMF stages them)."""
+
+    def __init__(self, N, device=0):
+        from .context import Context
+        self.ctx = Context(device)
+        try:
+            self.report = self.ctx.upload_native(N)
+        except Exception:
+            self.ctx.close()
+            raise
+        self.Dimnames = N.Dimnames
+
+    @property
+    def fits(self):
+        return _ResidentFits(None, ctx=self.ctx, Dimnames=self.Dimnames)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.ctx.close()
+
+
 def run_nmf(A, rank, tol=1e-4, maxit=100, verbose=True, L1=0.01, L2=0, threads=0, seed=None, _fits=None):
     """R/run_nmf.R:18-77 (sparse, single-matrix branch).  `seed` replaces R's global RNG state
-    (stats::runif, l.55): an int or numpy Generator."""
+    (stats::runif, l.55): an int or numpy Generator.  A NativeMatrix (native()) is staged on the device as it is."""
+    if _fits is None and isinstance(A, NativeMatrix):
+        with _NativeStage(A) as st:
+            return run_nmf(None, rank, tol, maxit, verbose, L1, L2, threads, seed, _fits=st.fits)
     if _fits is not None:   # RunNMF: the matrix is staged and resident already (A is not read)
         if verbose:
             print("running with sparse optimization")
@@ -504,7 +533,16 @@ def subset(A, rows=None, cols=None):
     """A[rows, cols] computed on the device (sgl_subset): the A[features, ] of RunNMF.Seurat (R/RunNMF.R:72-81) and the
     gene alignment of ProjectData.Seurat (R/ProjectData.R:68-69).  rows / cols: 0-based integers in any order (duplicates
     allowed), a boolean mask of the axis length, names looked up in A.Dimnames, or None to keep the axis.  Returns a
-    dgCMatrix with the selected Dimnames; the stored values, explicit zeros included, move bit for bit."""
+    dgCMatrix with the selected Dimnames; the stored values, explicit zeros included, move bit for bit.  A NativeMatrix
+    (native()) is staged through the typed door; the result is the same dgCMatrix (double values, sorted indices)."""
+    if isinstance(A, NativeMatrix):
+        r = _subset_index(rows, A.nrow, A.Dimnames[0], "rows")
+        c = _subset_index(cols, A.ncol, A.Dimnames[1], "cols")
+        with _NativeStage(A) as st:
+            st.ctx.subset(r, c)
+            nrow, ncol, _ = st.ctx.dims()
+            x, i, p = st.ctx.download(0)
+        return dgCMatrix(x, i, p.astype(np.int32), (nrow, ncol), (_subset_names(A.Dimnames[0], r), _subset_names(A.Dimnames[1], c)))
     A = as_dgCMatrix(A)
     r = _subset_index(rows, A.nrow, A.Dimnames[0], "rows")
     c = _subset_index(cols, A.ncol, A.Dimnames[1], "cols")
@@ -610,7 +648,19 @@ def RasterizeRowwise(A, n=10, threads=0):
 
 
 def project_model(A, w, L1=0.01, L2=0, threads=0):
-    """R/ProjectData.R:11-19."""
+    """R/ProjectData.R:11-19.  A NativeMatrix (native()) is staged through the typed door and projected on that context:
+    scale(w) (Context.op_scale: the kernels of the one-shot call), fit_init(k, w), project_run -- the one-shot call's bits."""
+    if isinstance(A, NativeMatrix):
+        w = np.asarray(w, dtype=np.float64)
+        if w.ndim != 2 or (w.shape[0] != A.nrow and w.shape[1] != A.nrow):
+            raise ValueError("'w' must share a common edge with the rows of 'A'")
+        wb = np.ascontiguousarray(w if w.shape[0] == A.nrow else w.T)   # (m, k), as c_project_model orients it (src/singlet.cpp:406)
+        with _NativeStage(A) as st:
+            wb, _ = st.ctx.op_scale(wb)
+            st.ctx.fit_init(wb.shape[1], wb)
+            st.ctx.project_run(float(L1), float(L2))
+            _, d, H = st.ctx.get_factors(w=False)
+        return {"h": H.T, "d": d}
     A = as_dgCMatrix(A)
     w = np.asarray(w)
     if w.shape[0] != A.nrow and w.shape[1] != A.nrow:
@@ -830,6 +880,10 @@ def ard_nmf(A, k_init=2, k_max=100, k_min=2, n_replicates=1, tol=1e-5, cv_tol=1e
         k_init = k_min
     if k_min < 2:
         raise ValueError("k_min cannot be less than 2")
+    if _fits is None and isinstance(A, NativeMatrix):   # native(): staged through the typed door, then the resident way
+        with _NativeStage(A) as st:
+            return ard_nmf(None, k_init, k_max, k_min, n_replicates, tol, cv_tol, maxit, verbose, L1, L2, threads, test_density,
+                           learning_rate, tol_overfit, trace_test_mse, seed, resident, _fits=st.fits)
     kind, A = ("staged", None) if _fits is not None else _classify_input(A)
     if kind == "staged":   # RunNMF: the matrix is staged and resident already
         nrow, (rn, cn), fits = _fits.nrow, _fits.Dimnames, _fits
@@ -973,6 +1027,10 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
     resident copy of A (BASELINE config 5 on one node); the table is the one-device table, row for row."""
     if L1 >= 1:
         raise ValueError("L1 penalty must be strictly in the range (0, 1]")
+    if _fits is None and isinstance(A, NativeMatrix):   # native(): one staged context (no replica sweep over `devices`)
+        with _NativeStage(A) as st:
+            return cross_validate_nmf(None, ranks, n_replicates, tol, maxit, verbose, L1, L2, threads, test_density, tol_overfit,
+                                      trace_test_mse, seed, resident, devices, _fits=st.fits)
     if _fits is not None:   # RunNMF: the matrix is staged and resident already (A is not read)
         kind, nrow = "sparse", _fits.nrow
     else:
@@ -1034,9 +1092,14 @@ def RunNMF(A, k=None, features=None, split_by=None, reps=3, tol=1e-5, L1=0.01, L
          k_max = 1e4 (l.126-145), clipped to the library's rank limit of 1024; k a scalar: run_nmf (l.146-148).
     `seed` (an int or numpy Generator) replaces R's global RNG state: one stream, drawn from by the drivers in the order
     they run, each exactly as it draws for a matrix of the subset's shape.  Returns the model of the driver it
-    dispatched to (w m x k, d, h k x n, names) plus "cv_data" (empty for a scalar k)."""
+    dispatched to (w m x k, d, h k x n, names) plus "cv_data" (empty for a scalar k).
+    A NativeMatrix (native()) is staged through the typed door; step 1 then takes its decision from the upload's report
+    (`integral`: every stored value equals its truncation, found while the values are converted on the device) instead
+    of scanning a host array -- for non-negative values that is the reference's sum(as.integer(v)) == sum(v)."""
     from .context import Context
-    A = as_dgCMatrix(A)
+    is_native = isinstance(A, NativeMatrix)
+    if not is_native:
+        A = as_dgCMatrix(A)
     rn, cn = A.Dimnames
     rows = None
     if features is not None:
@@ -1058,9 +1121,13 @@ def RunNMF(A, k=None, features=None, split_by=None, reps=3, tol=1e-5, L1=0.01, L
     rng = _rng(seed)
     ctx = Context(0)
     try:
-        ctx.upload(A, None)
-        v = A.x
-        if np.sum(np.trunc(v)) == np.sum(v):   # sum(as.integer(v)) == sum(v)
+        if is_native:
+            integral = bool(ctx.upload_native(A)["integral"])
+        else:
+            ctx.upload(A, None)
+            v = A.x
+            integral = np.sum(np.trunc(v)) == np.sum(v)   # sum(as.integer(v)) == sum(v)
+        if integral:
             ctx.log_normalize()
         if rows is not None:
             ctx.subset(rows=rows)

@@ -153,11 +153,13 @@ class Context:
         if _borrowed is not None:   # a rank of a Multi: owned by it
             self._h = _borrowed
             self._owned = False
+            self.device = None
         else:
             h = C.c_void_p()
             check(self._L.sgl_create(int(device), C.byref(h)))
             self._h = h
             self._owned = True
+            self.device = int(device)
         self._keep = []
         self.k = 0
 
@@ -229,6 +231,36 @@ class Context:
             t, keep_t = (0, None, None, None, None), None
         check(self._L.sgl_upload_csc_list(self._h, *a, *t, nrow, int(cell_offset), int(ncells_total)))
         self.k = 0
+
+    def upload_native(self, N, sort=True, cell_offset=0, ncells_total=0):
+        """sgl_upload_typed: a NativeMatrix (native()) goes in as its owner holds it -- converted, validated, sorted (sort =
+        True: the indices of a slice may come in any order) and transposed on the device; the resident image is bit for
+        bit that of upload(as_dgCMatrix(...)).  A torch GPU tensor is read where it lies (its device must be this
+        context's; its current stream is synchronised first), everything else is copied once from host memory.
+        Returns the report: nnz, sorted_lds / sorted_long (slices sorted by either path), integral (every stored value
+        equals its truncation), bytes_copied, lds_capacity."""
+        from .native import NativeMatrix, REPORT_KEYS, SGL_SPACE_DEVICE, SGL_UP_SORT
+        if not isinstance(N, NativeMatrix):
+            raise TypeError("upload_native takes what native() returns")
+        if N.space == SGL_SPACE_DEVICE:
+            if N.device != self.device:
+                raise ValueError("upload_native: the tensors live on GPU %r, this context on GPU %r" % (N.device, self.device))
+            import torch
+            torch.cuda.current_stream(N.device).synchronize()
+        try:
+            N.check_entry_count()
+        except ValueError:
+            # the library cannot see the arrays' length, so this refusal is made here; like every refused upload it
+            # leaves no matrix resident (a call without arrays is refused by the library after it dropped the matrix)
+            self._L.sgl_upload_typed(self._h, None, 0, None, 0, None, 0, 0, 0, 0, 0, 0, 0, 0, None)
+            self.k = 0
+            raise
+        report = np.zeros(8, dtype=np.int64)
+        x, i, p = (C.c_void_p(a) for a in N.addresses())
+        check(self._L.sgl_upload_typed(self._h, x, N.x_type, i, N.idx_type, p, N.ptr_type, N.n_major, N.n_minor, N.major_is_genes,
+                                       N.space, SGL_UP_SORT if sort else 0, int(cell_offset), int(ncells_total), ptr(report, i64p)))
+        self.k = 0
+        return dict(zip(REPORT_KEYS, (int(v) for v in report)))
 
     def upload_dense(self, A):
         """A: dense (nrow, ncol) array (sgl_upload_dense: CSC image built on the device, GEMM right-hand sides when

@@ -434,6 +434,20 @@ int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, doubl
 int k_raster_dense(hipStream_t s, const double* A, int64_t nrow, int64_t ncol, int64_t n, int64_t nb, double* out);
 // column gather of a CSC (kernels_subset.hip): D = S[:, sel], sel on the device and checked by the caller, D empty on entry
 int k_subset_gather(sgl_ctx* c, const DevCSC& S, const int32_t* sel, int64_t n, DevCSC& D);
+// typed ingest (kernels_ingest.hip, sgl_upload_typed): what a convert kernel ORs into its flag word (RANGE / ORDER / FINITE
+// are the validator's bits), the LDS sort's capacity in entries (8 LDS bytes per entry: four workgroups fit a CU's
+// 160 KiB, two were asked for), and the launchers
+#define SGL_INGEST_RANGE 1
+#define SGL_INGEST_ORDER 2
+#define SGL_INGEST_FINITE 4
+#define SGL_INGEST_INEXACT 8     // an int64 value beyond +-2^53
+#define SGL_INGEST_OFFSETS 16    // ptr[0] != 0 or ptr decreases (device-space offsets)
+#define SGL_INGEST_FRACTION 32   // not a defect: some value has a fraction (report[3] = 0)
+#define SGL_INGEST_LDS_CAP 4096
+int k_ingest_values(hipStream_t s, const void* src, int x_type, double* dst, int64_t n, int* flag);   // src may be dst for F64
+int k_ingest_narrow_index(hipStream_t s, const int64_t* src, int32_t* dst, int64_t n, int64_t extent, int* flag);
+int k_ingest_offsets(hipStream_t s, const void* src, int ptr_type, int64_t n1, int64_t* dst, int check, int* flag);
+int k_ingest_sort_slices(sgl_ctx* c, DevCSC& M, int64_t* n_short, int64_t* n_long);
 // device transpose (kernels_transpose.hip): T (empty on entry) = t(A), rows ascending; <= 0: the default batch size
 int sgl_device_transpose_into(sgl_ctx* c, const DevCSC& A, DevCSC& T, int64_t max_batch_entries);
 // upload of A alone (an empty At) validating the structure only, the values as they are (singlet_hip.hip)

@@ -4,6 +4,7 @@
 // this directory.  No CPU compute path exists here: without a gfx950 device
 // every entry point returns SGL_ENODEV.
 #include "sgl_internal.h"
+#include "ingest_host.h"
 
 #include <math.h>
 #include <string.h>
@@ -486,6 +487,175 @@ extern "C" int sgl_upload_csc_list(sgl_ctx* c, int32_t n_chunks, const double* c
         UPLOADCHK(c, sgl_device_transpose(c));
     }
     UPLOADCHK(c, finish_matrix(c));
+    return SGL_OK;
+}
+
+// ---- sgl_upload_typed: the arrays as a Python caller holds them (include/singlet_hip.h; kernels_ingest.hip) ----
+// Allocation order, per stored entry: the final offsets, x (8 B) and i (4 B) slots first; then, one after the other and
+// each freed before the next is taken, the raw staging of a HOST array whose type is not its slot's (4 B for F32 / I32
+// values, 8 B for I64 values or I64 indices); then the sort's lists and the long path's compact buffers (24 B per entry
+// of a long out-of-order slice); then the transpose's result and sort buffers, as at sgl_upload_csc.
+static const char* ingest_arg_text(IngestArgError e) {
+    switch (e) {
+    case INGEST_ARGS_NULL: return "a NULL array";
+    case INGEST_ARGS_X_TYPE: return "x_type is none of SGL_T_F64 / F32 / I32 / I64";
+    case INGEST_ARGS_IDX_TYPE: return "idx_type is neither SGL_T_I32 nor SGL_T_I64";
+    case INGEST_ARGS_PTR_TYPE: return "ptr_type is neither SGL_T_I32 nor SGL_T_I64";
+    case INGEST_ARGS_EXTENT: return "n_major and n_minor must lie in [1, 2^31 - 1]";
+    case INGEST_ARGS_MAJOR: return "major_is_genes is neither 0 nor 1";
+    case INGEST_ARGS_SPACE: return "space is neither SGL_SPACE_HOST nor SGL_SPACE_DEVICE";
+    case INGEST_ARGS_FLAGS: return "unknown flag bit";
+    default: return "";
+    }
+}
+
+// device memory of the context's device, nothing else
+static bool ingest_on_device(const sgl_ctx* c, const void* ptr) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeDevice && a.device == c->device;
+}
+
+// one caller array of `bytes` into dst (device): pageable host memory or device memory of this device
+static int ingest_copy(sgl_ctx* c, void* dst, const void* src, size_t bytes, int space) {
+    if (bytes == 0) return SGL_OK;
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, space == SGL_SPACE_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+    return SGL_OK;
+}
+
+static void ingest_defect_text(int flag, bool duplicates) {
+    sgl_set_error("not a valid dgCMatrix: %s%s%s%s%s", (flag & SGL_INGEST_RANGE) ? "row index outside [0, nrow) " : "",
+                  (flag & SGL_INGEST_ORDER) ? "row indices not strictly ascending within a column " : "",
+                  (flag & SGL_INGEST_ORDER) && duplicates ? "(two equal indices in one slice: duplicate entries are not summed) " : "",
+                  (flag & SGL_INGEST_FINITE) ? "non-finite value (NA / NaN / Inf) in the x slot -- refused here; singlet's CPU path would return all-NaN factors " : "",
+                  (flag & SGL_INGEST_INEXACT) ? "inexact: a 64-bit integer value beyond +-2^53 has no double of its own" : "");
+}
+
+// M (empty) <- the arrays: converted, validated, sorted where asked; report as in the header (8 values, always written on success).
+static int ingest_fill(sgl_ctx* c, DevCSC& M, const void* x, int x_type, const void* idx, int idx_type, const void* ptr, int ptr_type,
+                       int64_t n_major, int64_t n_minor, int space, uint32_t flags, int64_t* report) {
+    hipStream_t s = c->stream;
+    const bool host = space == SGL_SPACE_HOST;
+    const size_t n1 = (size_t)n_major + 1, pb = (size_t)ingest_type_bytes(ptr_type);
+    DevBuf<int> dflag;   // [0]: the validator's word (it clears it), [1]: the convert kernels'
+    SGLCHK(dflag.alloc(2));
+    HIPCHK(hipMemsetAsync(dflag.p, 0, 2 * sizeof(int), s));
+    M.nrow = (int32_t)n_minor;
+    M.ncol = (int32_t)n_major;
+    double t0 = wall_now();
+    double copied = (double)(n1 * pb);
+
+    // -- offsets: their checks come before the entry count is believed
+    int64_t nnz = 0;
+    SGLCHK(dev_alloc(&M.p, n1));
+    if (host) {
+        const int64_t at = ptr_type == SGL_T_I32 ? ingest_check_offsets(static_cast<const int32_t*>(ptr), n_major, &nnz)
+                                                 : ingest_check_offsets(static_cast<const int64_t*>(ptr), n_major, &nnz);
+        if (at >= 0) { sgl_set_error("invalid offset array: %s at position %lld", at == 0 ? "ptr[0] != 0" : "ptr decreases", (long long)at); return SGL_EINVAL; }
+        if (ptr_type == SGL_T_I64) {
+            SGLCHK(ingest_copy(c, M.p, ptr, n1 * 8, space));
+        } else {
+            DevBuf<char> raw;
+            SGLCHK(raw.alloc(n1 * pb));
+            SGLCHK(ingest_copy(c, raw.p, ptr, n1 * pb, space));
+            SGLCHK(k_ingest_offsets(s, raw.p, ptr_type, (int64_t)n1, M.p, 0, dflag.p + 1));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    } else {
+        int hflag = 0;
+        SGLCHK(k_ingest_offsets(s, ptr, ptr_type, (int64_t)n1, M.p, 1, dflag.p + 1));
+        HIPCHK(hipMemcpyAsync(&hflag, dflag.p + 1, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&nnz, M.p + n_major, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if ((hflag & SGL_INGEST_OFFSETS) || nnz < 0) { sgl_set_error("invalid offset array: ptr[0] != 0 or ptr decreases (device-space offsets)"); return SGL_EINVAL; }
+    }
+    M.nnz = nnz;
+    const size_t xb = (size_t)ingest_type_bytes(x_type), ib = (size_t)ingest_type_bytes(idx_type);
+    copied += (double)nnz * (double)(xb + ib);
+    SGLCHK(dev_alloc(&M.x, (size_t)nnz));
+    SGLCHK(dev_alloc(&M.i, (size_t)nnz));
+
+    // -- values: F64 of a HOST call lands in its slot and is tested there; a device array is converted from where it lies
+    if (host && x_type != SGL_T_F64) {
+        DevBuf<char> raw;
+        SGLCHK(raw.alloc((size_t)nnz * xb));
+        SGLCHK(ingest_copy(c, raw.p, x, (size_t)nnz * xb, space));
+        SGLCHK(k_ingest_values(s, raw.p, x_type, M.x, nnz, dflag.p + 1));
+        HIPCHK(hipStreamSynchronize(s));   // the staging buffer is freed here
+    } else {
+        if (host) SGLCHK(ingest_copy(c, M.x, x, (size_t)nnz * xb, space));
+        SGLCHK(k_ingest_values(s, host ? M.x : x, x_type, M.x, nnz, dflag.p + 1));
+    }
+    // -- indices
+    if (idx_type == SGL_T_I32) {
+        SGLCHK(ingest_copy(c, M.i, idx, (size_t)nnz * ib, space));
+    } else if (host) {
+        DevBuf<char> raw;
+        SGLCHK(raw.alloc((size_t)nnz * ib));
+        SGLCHK(ingest_copy(c, raw.p, idx, (size_t)nnz * ib, space));
+        SGLCHK(k_ingest_narrow_index(s, reinterpret_cast<const int64_t*>(raw.p), M.i, nnz, n_minor, dflag.p + 1));
+        HIPCHK(hipStreamSynchronize(s));
+    } else {
+        SGLCHK(k_ingest_narrow_index(s, static_cast<const int64_t*>(idx), M.i, nnz, n_minor, dflag.p + 1));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    double t1 = wall_now();
+    g_times.h2d_s += t1 - t0;
+    if (host) g_times.h2d_bytes += copied;
+
+    // -- the validator; then, for the order class alone and when asked, the sort and the validator again
+    int hf[2] = {0, 0};
+    SGLCHK(k_validate_csc(s, M.i, M.p, n_major, (int32_t)n_minor, dflag.p));
+    HIPCHK(hipMemcpyAsync(hf, dflag.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    int defects = (hf[0] | hf[1]) & (SGL_INGEST_RANGE | SGL_INGEST_ORDER | SGL_INGEST_FINITE | SGL_INGEST_INEXACT);
+    int64_t n_short = 0, n_long = 0;
+    bool sorted = false;
+    if (defects == SGL_INGEST_ORDER && (flags & SGL_UP_SORT)) {
+        SGLCHK(k_ingest_sort_slices(c, M, &n_short, &n_long));
+        sorted = true;
+        SGLCHK(k_validate_csc(s, M.i, M.p, n_major, (int32_t)n_minor, dflag.p));
+        HIPCHK(hipMemcpyAsync(hf, dflag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        defects = hf[0] & (SGL_INGEST_RANGE | SGL_INGEST_ORDER);
+    }
+    g_times.validate_s += wall_now() - t1;
+    if (defects) { ingest_defect_text(defects, sorted); return SGL_EINVAL; }
+    report[0] = nnz;
+    report[1] = n_short;
+    report[2] = n_long;
+    report[3] = (hf[1] & SGL_INGEST_FRACTION) ? 0 : 1;
+    report[4] = (int64_t)copied;
+    report[5] = SGL_INGEST_LDS_CAP;
+    report[6] = report[7] = 0;
+    return SGL_OK;
+}
+
+extern "C" int sgl_upload_typed(sgl_ctx* c, const void* x, int x_type, const void* idx, int idx_type, const void* ptr, int ptr_type,
+                                int64_t n_major, int64_t n_minor, int major_is_genes, int space, uint32_t flags, int64_t cell_offset,
+                                int64_t ncells_total, int64_t* report) {
+    CTX_GUARD(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    free_fit(c);
+    free_matrix(c);   // whatever follows, the previous matrix is gone
+    const IngestArgError bad = ingest_check_args(x, x_type, idx, idx_type, ptr, ptr_type, n_major, n_minor, major_is_genes, space, flags, SGL_UP_SORT);
+    if (bad != INGEST_ARGS_OK) { sgl_set_error("sgl_upload_typed: %s", ingest_arg_text(bad)); return SGL_EINVAL; }
+    if (space == SGL_SPACE_DEVICE && !(ingest_on_device(c, x) && ingest_on_device(c, idx) && ingest_on_device(c, ptr))) {
+        sgl_set_error("sgl_upload_typed: SGL_SPACE_DEVICE takes device memory of the context's device (%d) only", c->device);
+        return SGL_EINVAL;
+    }
+    const IngestLayout L = ingest_layout(major_is_genes, n_major, n_minor);
+    c->cell_offset = cell_offset;
+    c->ncells_total = ncells_total > 0 ? ncells_total : L.cells;
+    int64_t rep[8];
+    DevCSC& M = L.filled ? c->At : c->A;
+    UPLOADCHK(c, ingest_fill(c, M, x, x_type, idx, idx_type, ptr, ptr_type, n_major, n_minor, space, flags, rep));
+    const double t0 = wall_now();
+    UPLOADCHK(c, L.filled ? sgl_device_transpose_into(c, c->At, c->A, 0) : sgl_device_transpose(c));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) { sgl_set_error("sgl_upload_typed: HIP call failed after the transpose"); return drop_matrix(c, SGL_EHIP); }
+    g_times.transpose_s += wall_now() - t0;
+    UPLOADCHK(c, finish_matrix(c));
+    if (report) memcpy(report, rep, sizeof(rep));
     return SGL_OK;
 }
 
