@@ -30,6 +30,9 @@ t0 = time.perf_counter()
 fit = sa.run_nmf(A, rank=10, tol=1e-4, maxit=100, verbose=False, L1=0.01, seed=123)
 dt = time.perf_counter() - t0
 print("run_nmf(rank=10): %d iterations in %.3f s, d = %s" % (fit["iter"], dt, np.round(fit["d"], 1)))
+err = sa.evaluate(A, fit, cell_loss=True)                # the full-matrix error of the fit, zeros included
+print("evaluate: mse = %.6g over all %d x %d entries; the worst-explained cell carries %.3g of the squared error"
+      % (err["mse"], A.nrow, A.ncol, err["cell_loss"].max() / err["sse"]))
 proj = sa.project_model(A, fit["w"])
 print("project_model: h is %d x %d, relative change vs the fit's h: %.2e"
       % (proj["h"].shape[0], proj["h"].shape[1], np.linalg.norm(proj["h"] - fit["h"]) / np.linalg.norm(fit["h"])))

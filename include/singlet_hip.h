@@ -532,6 +532,42 @@ SGL_API int sgl_group_means(sgl_ctx* ctx, const double* F, int32_t k, int64_t n,
 SGL_API int sgl_c_group_means(const double* F, int32_t k, int64_t n, const int32_t* group, int32_t n_groups,
                               double* means, int64_t* counts);
 
+/* Model error of the current factors against the resident matrix: per cell j and per gene i the sum of the squared
+ * residuals of the plain reconstruction w^T diag(d) h over ALL entries of the column (row), zeros included,
+ *   cell_loss[j] = sum_i (A_ij - sum_f w_fi d_f h_fj)^2 = ||a_j||^2 - 2 h_j . b_j + h_j^T Gw h_j,   b_j = W^ a_j,  Gw = W^ W^^T,
+ * with W^ = diag(d) w, from the sparse structure alone (nnz k + (m + n) k^2 multiply-adds, never m n k); the gene side is
+ * the same over t(A) with H^ = diag(d) h.  b and Gw come from the fit's own accumulate and Gram kernels.
+ *  - cell_loss: ncol doubles; gene_loss: nrow doubles.  Either may be NULL and that side's pass is skipped; with both NULL
+ *    the cell side still runs, for sse.  sse = the sum of the cell losses; mse = sse / ((double)nrow * (double)ncol), one
+ *    true division.  sse and mse may be NULL.
+ *  - what is evaluated is w^T diag(d) h alone: link matrices (either form) and a cell graph set on the fit are ignored.
+ *  - sign: a loss that cancellation leaves at or below zero is returned as +0.0 (the true value is >= 0); NaN and Inf
+ *    propagate.  sse is formed from the clamped cell losses.  |error| of a loss <= (max column nnz + m + k^2 + 4) 2^-53
+ *    (||a_j||^2 + 2 |h_j| . |b_j| + |h_j|^T |Gw| |h_j|) to first order: relative to the TERMS, not to the loss, so a
+ *    near-exact fit keeps few digits of a small loss.
+ *  - the result is a function of (matrix, k, factors) alone -- no floating-point atomics, nothing depends on the launch
+ *    size or the occupancy -- so two calls give the same bits, and the resident and the one-shot form agree bit for bit.
+ *    The orders: ||a_j||^2: lane l of 64 adds the squares of the entries l, l + 64, ... of the column in stored order, the
+ *    lane sums are added by a butterfly (lane ^ 32, 16, ... 1).  t_f = sum_g Gw[f, g] h_g with g ascending; lane l adds
+ *    h_f b_f and h_f t_f over f = l, l + 64, ...; the same butterfly; loss = (||a_j||^2 - 2 dot) + quad.  sse: the cells in
+ *    matrix order are cut into chunks of 1024; thread t of 256 adds the cells t, t + 256, t + 512, t + 768 of its chunk in
+ *    that order, the 256 sums are added by a binary tree (t += t + stride, stride = 128 ... 1), and the chunk sums are added
+ *    in chunk order starting from +0.0.
+ *  - the call uses the fit's scratch (right-hand sides, Gram, workspace) and changes nothing a later step reads: a fit
+ *    continued after it gives the bits it would have given without it.  The kernels' time counts in the existing rhs_h,
+ *    rhs_w and gram phases or in none.
+ *  - refused: SGL_ESTATE without a resident matrix or without a fit; SGL_ESTATE on a team member or with an all-reduce
+ *    hook set (the shard's losses are not the matrix's; a one-process team uses sgl_multi_evaluate).  After
+ *    sgl_upload_dense the call WORKS: it runs over the CSC image that upload keeps next to the dense matrix (the sparse
+ *    accumulate, whatever kernel the fit's own right-hand sides use).  The context stays usable after every refusal. */
+SGL_API int sgl_evaluate(sgl_ctx* ctx, double* sse, double* mse, double* cell_loss, double* gene_loss);
+/* The one-shot form: its own context on the current device (like sgl_c_group_means); A as a dgCMatrix (t(A) is built on
+ * the device), w k x nrow, d k, h k x ncol as sgl_set_factors takes them.  SGL_EINVAL for k outside [1, 1024] and for a
+ * NULL factor, before anything is uploaded; an invalid matrix is refused as by sgl_upload_csc. */
+SGL_API int sgl_c_evaluate(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol,
+                           const double* w, const double* d, const double* h, int32_t k,
+                           double* sse, double* mse, double* cell_loss, double* gene_loss);
+
 /* Cell graph of c_gcnmf for the current fit (after sgl_fit_init, which drops
  * it again; all-NULL slots clear it).  G is an n x n dgCMatrix, n = the cells of
  * the resident matrix; an invalid G is SGL_EINVAL with a message.  While it is
@@ -645,6 +681,14 @@ SGL_API int sgl_multi_set_links_grouped(sgl_multi* m, const double* table_h, int
  * counts over all ranks.  Equal to the one-context means to the rounding of the different order (same first-order
  * bound); the counts are exact.  SGL_ESTATE without a fit. */
 SGL_API int sgl_multi_group_means(sgl_multi* m, const int32_t* group, int32_t n_groups, double* means, int64_t* counts);
+/* sgl_evaluate on the team's fit (cell_loss: all cells of the whole matrix in global order; mse divides by nrow * all
+ * cells).  Every rank, on its own thread, computes the losses of its cells, their sum in sgl_evaluate's order over its
+ * block, and -- when gene_loss is asked for -- the UNCLAMPED partial of every gene over its own cells; no collective is
+ * needed, every rank holds the same w and d.  The host adds the ranks' cell sums in rank order for sse, and adds the gene
+ * partials in rank order, then clamps.  Equal to the one-context result to the rounding of the different order (the same
+ * first-order bound); exact on inputs whose sums are exact.  SGL_ESTATE without a matrix or a fit.  Process-per-GPU
+ * teams (sgl_comm_init_rank) have no such call: sgl_evaluate refuses on their contexts. */
+SGL_API int sgl_multi_evaluate(sgl_multi* m, double* sse, double* mse, double* cell_loss, double* gene_loss);
 /* c_gcnmf on the team (src/singlet.cpp:1668-1730): the cell graph of the WHOLE matrix (arguments, checks and messages as
  * sgl_set_graph; all-NULL slots clear it; sgl_multi_fit_init drops it).  Rank r keeps the columns of its own cells.  The
  * rows of those columns that name another rank's cells are that rank's "exports"; E = the longest export list of the

@@ -101,6 +101,8 @@ SIGNATURES = {
     "sgl_set_links_grouped": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int32, i32p, f64p, C.c_int32, C.c_int32, i32p]),
     "sgl_group_means": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64, i32p, C.c_int32, f64p, i64p]),
     "sgl_c_group_means": (C.c_int, [f64p, C.c_int32, C.c_int64, i32p, C.c_int32, f64p, i64p]),
+    "sgl_evaluate": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p]),
+    "sgl_c_evaluate": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p]),
     "sgl_set_graph": (C.c_int, [C.c_void_p, f64p, i32p, i32p, C.c_int32, C.c_int32]),
     "sgl_set_allreduce": (C.c_int, [C.c_void_p, ALLREDUCE_FN, C.c_void_p]),
     "sgl_step_begin": (C.c_int, [C.c_void_p]),
@@ -126,6 +128,7 @@ SIGNATURES = {
     "sgl_multi_set_links": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32]),
     "sgl_multi_set_links_grouped": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int32, i32p, f64p, C.c_int32, C.c_int32, i32p]),
     "sgl_multi_group_means": (C.c_int, [C.c_void_p, i32p, C.c_int32, f64p, i64p]),
+    "sgl_multi_evaluate": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p]),
     "sgl_multi_set_graph": (C.c_int, [C.c_void_p, f64p, i32p, i32p, C.c_int32, C.c_int32]),
     "sgl_multi_graph_info": (C.c_int, [C.c_void_p, i64p]),
     "sgl_graph_halo_plan": (C.c_int, [i32p, i32p, C.c_int32, C.c_int, i64p, i32p, i64p, i32p, i64p]),

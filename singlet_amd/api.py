@@ -22,6 +22,8 @@ names, argument order, defaults and return fields:
   MetadataSummary                       R/MetadataSummary.R:15-36 (without the hclust display order)
   GetSharedFactors / GetUniqueFactors   R/GetSharedFactors.R:4-10, R/GetUniqueFactors.R:4-10
   group_means                           the k G calls of mean(h[which(...)]) of R/RunLNMF.R:136-143, R/MetadataSummary.R:18-26
+  evaluate                              no R counterpart: the full-matrix error of a model (mse_test, src/singlet.cpp:536-568,
+                                        with every entry drawn), per cell and per gene
 
 Matrices follow R's orientation: w is returned k x m by c_nmf and m x k by
 run_nmf / ard_nmf (they transpose and sort by d, R/run_nmf.R:65-68); h is
@@ -1162,6 +1164,43 @@ def RunNMF(A, k=None, features=None, split_by=None, reps=3, tol=1e-5, L1=0.01, L
         ctx.close()
     model["cv_data"] = cv_data
     return model
+
+
+# ---------------------------------------------------------------------------
+# Model error
+# ---------------------------------------------------------------------------
+def evaluate(A, model, cell_loss=False, gene_loss=False):
+    """Error of a model against the matrix it explains: {"sse", "mse"} and, when asked for, "cell_loss" (one per column of A)
+    and "gene_loss" (one per row) -- the sums of squared residuals of w diag(d) h over every entry, zeros included, formed on
+    the device from the sparse structure (sgl_c_evaluate; include/singlet_hip.h, sgl_evaluate).  A: whatever run_nmf
+    takes -- a dgCMatrix, anything as_dgCMatrix accepts, or a native(...) object, which is staged through the typed door.
+    model: what the drivers return (w m x k, d k, h k x n).  Shapes are checked before anything is uploaded."""
+    is_native = isinstance(A, NativeMatrix)
+    if not is_native:
+        A = as_dgCMatrix(A)
+    w = np.asarray(model["w"], dtype=np.float64)
+    d = np.asarray(model["d"], dtype=np.float64).reshape(-1)
+    h = np.asarray(model["h"], dtype=np.float64)
+    if w.ndim != 2 or h.ndim != 2:
+        raise ValueError("evaluate: model['w'] must be m x k and model['h'] k x n")
+    k = w.shape[1]
+    if w.shape[0] != A.nrow or h.shape[1] != A.ncol or h.shape[0] != k or d.shape[0] != k:
+        raise ValueError("evaluate: A is %d x %d, but w is %r, d %r and h %r (expected m x k, k, k x n)"
+                         % (A.nrow, A.ncol, w.shape, d.shape, h.shape))
+    if k < 1:
+        raise ValueError("evaluate: the model has rank 0")
+    wk = np.ascontiguousarray(w)        # m x k row-major = k x m column-major, the layout of sgl_set_factors
+    hk = np.ascontiguousarray(h.T)
+    dk = np.ascontiguousarray(d)
+    from .context import _evaluate_call
+    if is_native:
+        with _NativeStage(A) as st:
+            st.ctx.fit_init(k)
+            st.ctx.set_factors(wk, dk, hk)
+            return st.ctx.evaluate(cell_loss, gene_loss)
+    L = _lib.load()
+    return _evaluate_call(lambda *o: L.sgl_c_evaluate(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow, A.ncol, ptr(wk, f64p),
+                                                      ptr(dk, f64p), ptr(hk, f64p), int(k), *o), A.nrow, A.ncol, cell_loss, gene_loss)
 
 
 # ---------------------------------------------------------------------------

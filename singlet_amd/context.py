@@ -147,6 +147,20 @@ def _grouped_side(table, group, n, side):
     return ptr(buf, f64p), T.shape[0], T.shape[1], ptr(g, i32p), (buf, g)
 
 
+def _evaluate_call(fn, nrow, ncol, cell_loss, gene_loss):
+    """Shared by Context.evaluate, Multi.evaluate and api.evaluate: fn(sse, mse, cell_loss, gene_loss) is the library call."""
+    sse, mse = np.zeros(1), np.zeros(1)
+    cl = np.empty(max(int(ncol), 1)) if cell_loss else None
+    gl = np.empty(max(int(nrow), 1)) if gene_loss else None
+    check(fn(ptr(sse, f64p), ptr(mse, f64p), ptr(cl, f64p), ptr(gl, f64p)))
+    out = {"sse": float(sse[0]), "mse": float(mse[0])}
+    if cell_loss:
+        out["cell_loss"] = cl[:int(ncol)]
+    if gene_loss:
+        out["gene_loss"] = gl[:int(nrow)]
+    return out
+
+
 class Context:
     def __init__(self, device=0, _borrowed=None):
         self._L = _lib.load()
@@ -392,6 +406,13 @@ class Context:
         counts = np.zeros(max(G, 0), dtype=np.int64)
         check(self._L.sgl_group_means(self._h, Fp, int(k), int(g.shape[0]), ptr(g, i32p), G, ptr(means, f64p), ptr(counts, i64p)))
         return means.T, counts
+
+    def evaluate(self, cell_loss=False, gene_loss=False):
+        """Error of the current factors against the resident matrix (sgl_evaluate): {"sse", "mse"} plus, when asked for,
+        "cell_loss" (one per cell) and "gene_loss" (one per gene) -- sums of squared residuals of w^T diag(d) h over every
+        entry of the column / row, zeros included.  Links and a cell graph on the fit are ignored; the fit is not changed."""
+        nr, nc, _ = self.dims()
+        return _evaluate_call(lambda *o: self._L.sgl_evaluate(self._h, *o), nr, nc, cell_loss, gene_loss)
 
     def set_graph(self, G):
         """c_gcnmf's cell graph (sgl_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over the resident cells, or None
@@ -731,6 +752,12 @@ class Multi:
         counts = np.zeros(max(G, 0), dtype=np.int64)
         check(self._L.sgl_multi_group_means(self._h, ptr(g, i32p), G, ptr(means, f64p), ptr(counts, i64p)))
         return means.T, counts
+
+    def evaluate(self, cell_loss=False, gene_loss=False):
+        """Context.evaluate for the team's fit (sgl_multi_evaluate): cell_loss covers all cells in global order; the ranks'
+        sums and gene partials are added on the host in rank order."""
+        nr, nc = self._dims if self._dims else (0, 0)
+        return _evaluate_call(lambda *o: self._L.sgl_multi_evaluate(self._h, *o), nr, nc, cell_loss, gene_loss)
 
     def set_graph(self, G):
         """c_gcnmf's cell graph for the team (sgl_multi_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over ALL

@@ -1242,6 +1242,32 @@ extern "C" int sgl_multi_group_means(sgl_multi* M, const int32_t* group, int32_t
     return SGL_OK;
 }
 
+// model error of the team's fit (include/singlet_hip.h): every rank evaluates its shard on its own thread; rank sums and
+// unclamped gene partials are added on the host in rank order
+extern "C" int sgl_multi_evaluate(sgl_multi* M, double* sse, double* mse, double* cell_loss, double* gene_loss) {
+    TEAM_GUARD(M);
+    if (M->cell_lo.empty()) { sgl_set_error("sgl_multi_evaluate: no matrix resident"); return SGL_ESTATE; }
+    if (M->local[0]->k == 0) { sgl_set_error("sgl_multi_evaluate: no fit initialised (call sgl_multi_fit_init)"); return SGL_ESTATE; }
+    const int R = (int)M->local.size();
+    const size_t m = (size_t)M->nrow;
+    std::vector<double> sums((size_t)R, 0.0), gpart(gene_loss ? (size_t)R * m : 0);
+    SGLCHK(team_parallel(M, [&](int r) -> int {
+        return sgl_eval_shard(M->local[r], false, &sums[(size_t)r], cell_loss ? cell_loss + M->cell_lo[r] : nullptr,
+                              gene_loss ? gpart.data() + (size_t)r * m : nullptr);
+    }));
+    double s = 0.0;
+    for (int r = 0; r < R; ++r) s += sums[(size_t)r];
+    if (gene_loss)
+        for (size_t i = 0; i < m; ++i) {
+            double g = 0.0;
+            for (int r = 0; r < R; ++r) g += gpart[(size_t)r * m + i];
+            gene_loss[i] = g <= 0.0 ? 0.0 : g;   // NaN <= 0 is false: it propagates
+        }
+    if (sse) *sse = s;
+    if (mse) *mse = s / ((double)M->nrow * (double)M->ncells_total);
+    return SGL_OK;
+}
+
 // ------------------------------------------------------- c_gcnmf on the team --
 // The halo plan (header, section 2b): which cells every rank exports and the row indices of every rank's columns in terms
 // of [own cells | slab].  Pure host code.

@@ -429,6 +429,12 @@ int sgl_group_sums_dev(sgl_ctx* c, const double* F, int k, int64_t n, const int3
 // SGL_EINVAL naming the list, the position and the value of the first id outside [0, n_groups)
 int sgl_group_ids_check(const char* who, const char* name, const int32_t* group, int64_t n, int32_t n_groups);
 
+// model error (kernels_eval.hip; include/singlet_hip.h, sgl_evaluate) of the shard of a context with a fit: *cell_sum (host) = the
+// order-fixed sum of the clamped losses of its cells; cell_loss (host, ncol; may be NULL); gene_loss (host, nrow; NULL: the
+// gene side is skipped) = the losses of the genes over THIS shard's cells, clamped only when `clamp_genes` (a team adds the
+// unclamped rank partials first).  Uses red, B, G and the workspace as scratch; synchronises the stream.
+int sgl_eval_shard(sgl_ctx* c, bool clamp_genes, double* cell_sum, double* cell_loss, double* gene_loss);
+
 // row-wise rasterisation (kernels_raster.hip): out (nb x ncol, column-major) = means of rows [b n, b n + n), nb >= 1
 int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, double* out);
 int k_raster_dense(hipStream_t s, const double* A, int64_t nrow, int64_t ncol, int64_t n, int64_t nb, double* out);

@@ -1879,6 +1879,35 @@ extern "C" int sgl_c_group_means(const double* F, int32_t k, int64_t n, const in
     return sgl_group_means(hd.c, F, k, n, group, n_groups, means, counts);
 }
 
+// Model error (include/singlet_hip.h; kernels_eval.hip): the losses of the resident fit, or of given factors in a context of its own.
+extern "C" int sgl_evaluate(sgl_ctx* c, double* sse, double* mse, double* cell_loss, double* gene_loss) {
+    CTX_GUARD(c);
+    if (c->team || c->allreduce) {
+        sgl_set_error("sgl_evaluate: the context is a shard of a team or has an all-reduce hook; the losses of this shard's cells "
+                      "are not the matrix's (a team: sgl_multi_evaluate)");
+        return SGL_ESTATE;
+    }
+    if (!c->A.p || !c->At.p) { sgl_set_error("sgl_evaluate: no matrix resident"); return SGL_ESTATE; }
+    if (c->k == 0) { sgl_set_error("sgl_evaluate: no fit initialised (call sgl_fit_init)"); return SGL_ESTATE; }
+    double s = 0.0;
+    SGLCHK(sgl_eval_shard(c, true, &s, cell_loss, gene_loss));
+    if (sse) *sse = s;
+    if (mse) *mse = s / ((double)c->A.nrow * (double)c->A.ncol);
+    return SGL_OK;
+}
+
+extern "C" int sgl_c_evaluate(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, const double* w,
+                              const double* d, const double* h, int32_t k, double* sse, double* mse, double* cell_loss, double* gene_loss) {
+    if (!w || !d || !h) { sgl_set_error("sgl_c_evaluate: NULL factor"); return SGL_EINVAL; }
+    SGLCHK(rank_check(k));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, nullptr, nullptr, nullptr, nrow, ncol, 0, ncol));
+    SGLCHK(sgl_fit_init(hd.c, k, nullptr, 0));   // (the factors are not checked for finiteness: NaN / Inf propagate)
+    SGLCHK(sgl_set_factors(hd.c, w, d, h));
+    return sgl_evaluate(hd.c, sse, mse, cell_loss, gene_loss);
+}
+
 // c_gcnmf's cell graph G (src/singlet.cpp:1668-1730): n x n, n = the cells of the resident matrix, as a dgCMatrix.  Checked
 // on the host (the kernels index factor columns by its rows): p[0] = 0 and monotone, rows strictly ascending within a column
 // and in [0, n), values finite.  Columns above SGL_GRAPH_HUB entries get their segment lists here (kernels_graph.hip).
