@@ -568,6 +568,75 @@ SGL_API int sgl_c_evaluate(const double* Ax, const int32_t* Ai, const int32_t* A
                            const double* w, const double* d, const double* h, int32_t k,
                            double* sse, double* mse, double* cell_loss, double* gene_loss);
 
+/* Variable features of the resident COUNTS: the selection Seurat stores in var.features by default,
+ * FindVariableFeatures(selection.method = "vst"), which RunNMF.Seurat reads as features = "var.features"
+ * (R/RunNMF.R:73-74) -- per-gene mean and variance of the counts, a smooth trend of log10(variance) on log10(mean), the
+ * variance of the clipped standardised counts, and the top nfeatures genes by it.  Neither Seurat nor R was at hand:
+ * the rules below are this library's own, stated in full; tests/variable_features_restatement.py restates them.
+ *
+ * The three gene passes run over the gene-side image t(A) (one column per gene, 64-bit offsets).  n = ncol; c_g = the
+ * stored entries of gene g, explicit zeros included.  All sums are in double, without contraction (a product and the
+ * addition that follows are two roundings) and without floating-point atomics; no loop's trip count follows the launch.
+ *  - mean:   S_g = sum of the stored x;  mean_g = S_g / (double)n, one true division;  count_g = c_g.
+ *  - variance, given mu (Seurat's SparseRowVar2):  d = x - mu_g, t = d * d for every stored x;  Q_g = sum of the t;
+ *    Z_g = (double)(n - c_g) * (mu_g * mu_g);  var_g = (Q_g + Z_g) / (double)(n - 1).
+ *  - standardised variance, given mu, sd and vmax (Seurat's SparseRowVarStd):  sd_g == 0 gives +0.0.  Otherwise
+ *    z = (x - mu_g) / sd_g (a true division), z = z > vmax ? vmax : z, t = z * z;  Q_g = sum of the t;
+ *    z0 = (0.0 - mu_g) / sd_g, NOT clipped (as in Seurat);  Z_g = (double)(n - c_g) * (z0 * z0);  the result is
+ *    (Q_g + Z_g) / (double)(n - 1).
+ *  - THE SUMMATION ORDER of S_g and of either Q_g is a function of c_g alone: the gene's entries, in stored order, are cut
+ *    into segments of 8192 (the last one shorter); inside a segment lane l of 64 adds the terms of the segment's entries
+ *    l, l + 64, ... in that order, starting from +0.0, and the 64 lane sums are added by a butterfly (v += v[lane ^ 32],
+ *    then 16, 8, 4, 2, 1); the segment sums are added in ascending segment order starting from +0.0 (a gene without a
+ *    stored entry gives +0.0).  One wave works on one segment, so a gene stored in every cell is not walked by one wave
+ *    alone.  Two calls, the resident and the one-shot form give the same bits.  To first order, for terms that are not
+ *    negative, |error| <= (c_g + 2) 2^-53 of the mean and (3 c_g + 8) 2^-53 of either variance.
+ *  - the trend (sgl_op_loess_direct): x and y of length m, sorted ascending by (x, original index), and a window length
+ *    q, 1 <= q <= m.  For every point i on its own:
+ *      window   the q consecutive sorted positions s .. s + q - 1 containing i (max(0, i - q + 1) <= s <= min(i, m - q))
+ *               whose farthest member is nearest: f(s) = max(x_i - x_s, x_{s + q - 1} - x_i) is least, ties to the lowest s;
+ *               hmax = that f(s).
+ *      weights  u = x_j - x_i, r = |u| / hmax, r3 = (r * r) * r, c = 1 - r3, w = (c * c) * c; every w is 1 when hmax == 0.
+ *      degree   D = the distinct x among the window's members of POSITIVE weight (hmax == 0 or |u| < hmax; the members at
+ *               the distance hmax itself weigh nothing and cannot carry a coefficient): degree 2 for D >= 3, 1 for
+ *               D == 2, 0 for D == 1.
+ *      moments  S0 .. S4 = sum of w, wu = w * u, wu2 = wu * u, wu3 = wu2 * u, wu4 = wu3 * u;  T0, T1, T2 = sum of w * y,
+ *               wu * y, wu2 * y: lane l of 64 adds the members s + l, s + l + 64, ... in that order, then the butterfly above.
+ *      fit      weighted least squares in u; the fitted value is the intercept: degree 0: T0 / S0;  degree 1:
+ *               (S2 T0 - S1 T1) / (S0 S2 - S1 S1);  degree 2, by Cramer's rule with A = S2 S4 - S3 S3:
+ *               (T0 A - S1 (T1 S4 - S3 T2) + S2 (T1 S3 - S2 T2)) / (S0 A - S1 (S1 S4 - S3 S2) + S2 (S1 S3 - S2 S2)).
+ *    This is an exact local fit at EVERY point.  It is NOT R's default loess(surface = "interpolate"), which fits at the
+ *    vertices of a k-d tree and blends them; that code was not at hand and nothing here is pinned to it.  The difference
+ *    is in the trend alone: a caller with R's (or any other) loess at hand passes its expected variances (below) and
+ *    gets exact parity with it for everything else.
+ *
+ * sgl_variable_features: mean and variance (mu = mean) as above; m' = the genes with variance > 0.  expected_var, when
+ * not NULL, holds nrow doubles and IS the expected variance.  Otherwise the expected variance of the m' genes is
+ * 10^fitted, from the trend of y = log10(variance) on x = log10(mean) over them with q = max(min(m', 3), floor(span m')),
+ * and 0 for the constant genes.  sd = sqrt(expected); vmax <= 0 (or NaN) means sqrt((double)n).  The genes are ranked by
+ * standardised variance, descending, ties to the lower gene index (a NaN ranks last).  features receives the first
+ * min(nfeatures, nrow) gene indices (0-based) in rank order -- the order A[var.features, ] puts the rows in -- and *n_out
+ * how many were written.  info, when not NULL, is 4 x nrow column-major: mean, variance, expected, standardised of gene g
+ * at info[4 g .. 4 g + 3].  Host code in the library (nrow doubles): log10, the sort, pow, sqrt and the ranking; device:
+ * the three passes over the stored values and the trend.
+ *  - refused with SGL_EINVAL, nothing changed: nfeatures < 1; span outside (0, 1]; ncol < 2; a NULL features or n_out; a
+ *    negative or non-finite expected_var; a gene of positive variance whose mean is not positive (the message names it).
+ *  - refused with SGL_ESTATE: with no matrix resident, on a team member, with an all-reduce hook set, and on a context
+ *    that holds a shard (cell_offset != 0 or ncells_total != ncol): a shard's moments are not the matrix's, and
+ *    sgl_subset, which follows, is refused there too.  The context stays usable after every refusal.
+ *  - after sgl_upload_dense the call WORKS, over the CSC image that upload keeps.
+ *  - the call only reads: the matrix and a fit in progress stay untouched -- entry streams, mask lists and the packed
+ *    solves' sweep counts included; a fit continued after it gives the bits it would have given without it.  The kernels'
+ *    time counts in the "scale" phase when timing is on.
+ *  - 64-bit indexing throughout; values are not checked again (an upload refuses non-finite ones). */
+SGL_API int sgl_variable_features(sgl_ctx* ctx, int32_t nfeatures, double span, double vmax, const double* expected_var,
+                                  int32_t* features, int32_t* n_out, double* info);
+/* The one-shot form: its own context on the current device, A as a dgCMatrix (t(A) is built on the device); the argument
+ * refusals come before anything is uploaded.  Neither uses nor touches the SINGLET_HIP_CACHE context. */
+SGL_API int sgl_c_variable_features(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol,
+                                    int32_t nfeatures, double span, double vmax, const double* expected_var,
+                                    int32_t* features, int32_t* n_out, double* info);
+
 /* Cell graph of c_gcnmf for the current fit (after sgl_fit_init, which drops
  * it again; all-NULL slots clear it).  G is an n x n dgCMatrix, n = the cells of
  * the resident matrix; an invalid G is SGL_EINVAL with a message.  While it is
@@ -795,6 +864,19 @@ SGL_API int sgl_op_mse_test(sgl_ctx* ctx, uint64_t seed, uint64_t inv_density, d
  * added to the cell (the column of A, the row of t(A)), as the fit's masked steps do.  SGL_EINVAL for inv_density = 0 and,
  * tiled, at a rank without entry streams. */
 SGL_API int sgl_op_rhs_masked(sgl_ctx* ctx, int which, const double* F, int32_t k, uint64_t seed, uint64_t inv_density, double* B);
+/* The stages of sgl_variable_features, one at a time (the rules and the summation order are stated there).  All four only
+ * read the context: they need a resident matrix (SGL_ESTATE without) and run over its gene-side image t(A) whatever it
+ * holds (counts or not, a shard or not); SGL_EINVAL for a NULL array.
+ *  - sgl_op_gene_mean: mean[g] = S_g / (double)ncol and count[g] = c_g, nrow of each.
+ *  - sgl_op_gene_var: var[g] = (Q_g + Z_g) / (double)(ncol - 1) about the given mu (nrow doubles).
+ *  - sgl_op_gene_var_std: the variance of the counts standardised by mu and sd and clipped at vmax (taken as it is:
+ *    only the composite replaces vmax <= 0); +0.0 where sd[g] == 0.
+ *  - sgl_op_loess_direct: fitted[i] = the local fit at x[i] of y on x with windows of q points; x, y, fitted hold n doubles,
+ *    x already sorted.  SGL_EINVAL when x is not ascending (or not finite), for q < 1, q > n and n >= 2^31. */
+SGL_API int sgl_op_gene_mean(sgl_ctx* ctx, double* mean, int64_t* count);
+SGL_API int sgl_op_gene_var(sgl_ctx* ctx, const double* mu, double* var);
+SGL_API int sgl_op_gene_var_std(sgl_ctx* ctx, const double* mu, const double* sd, double vmax, double* out);
+SGL_API int sgl_op_loess_direct(sgl_ctx* ctx, const double* x, const double* y, int64_t n, int64_t q, double* fitted);
 /* nnls on ncols independent columns, each against its OWN Gram: Gcols = ncols blocks of k x k, B / X as in sgl_op_nnls;
  * col_nnz (int64 [ncols], or NULL): columns with a zero there are skipped -- X keeps its input, no sweeps are counted.
  * The dispatch of every masked half-step (four columns per wave on LDS triangles or on the Grams in global memory, one

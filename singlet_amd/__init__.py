@@ -7,7 +7,8 @@ from .api import (c_nmf, c_ard_nmf, c_linked_nmf, c_gcnmf, run_gcnmf, c_nmf_dens
                   GetBestRank, project_model, CVData, PreprocessData, weight_by_split, call_times, c_LKNN, c_SNN,
                   find_local_neighbors, rescale_spatial, spatial_graph,
                   rowwise_compress_sparse, rowwise_compress_dense, RasterizeRowwise, RasterMatrix, subset, RunNMF,
-                  group_means, run_linked_nmf, RunLNMF, MetadataSummary, GetSharedFactors, GetUniqueFactors, evaluate)
+                  group_means, run_linked_nmf, RunLNMF, MetadataSummary, GetSharedFactors, GetUniqueFactors, evaluate,
+                  find_variable_features)
 from .native import native, NativeMatrix  # noqa: F401
 from ._lib import SingletHipError, LIB_PATH  # noqa: F401
 

@@ -103,6 +103,8 @@ SIGNATURES = {
     "sgl_c_group_means": (C.c_int, [f64p, C.c_int32, C.c_int64, i32p, C.c_int32, f64p, i64p]),
     "sgl_evaluate": (C.c_int, [C.c_void_p, f64p, f64p, f64p, f64p]),
     "sgl_c_evaluate": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p]),
+    "sgl_variable_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, f64p, i32p, i32p, f64p]),
+    "sgl_c_variable_features": (C.c_int, _CSC + [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, f64p, i32p, i32p, f64p]),
     "sgl_set_graph": (C.c_int, [C.c_void_p, f64p, i32p, i32p, C.c_int32, C.c_int32]),
     "sgl_set_allreduce": (C.c_int, [C.c_void_p, ALLREDUCE_FN, C.c_void_p]),
     "sgl_step_begin": (C.c_int, [C.c_void_p]),
@@ -158,6 +160,10 @@ SIGNATURES = {
     "sgl_op_graph_conv": (C.c_int, [C.c_void_p, f64p, C.c_int32, f64p]),
     "sgl_op_mse_test": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, f64p]),
     "sgl_op_rhs_masked": (C.c_int, [C.c_void_p, C.c_int, f64p, C.c_int32, C.c_uint64, C.c_uint64, f64p]),
+    "sgl_op_gene_mean": (C.c_int, [C.c_void_p, f64p, i64p]),
+    "sgl_op_gene_var": (C.c_int, [C.c_void_p, f64p, f64p]),
+    "sgl_op_gene_var_std": (C.c_int, [C.c_void_p, f64p, f64p, C.c_double, f64p]),
+    "sgl_op_loess_direct": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int64, C.c_int64, f64p]),
     "sgl_op_nnls_percol": (C.c_int, [C.c_void_p, f64p, f64p, f64p, i64p, C.c_int32, C.c_int64, C.c_double, C.c_double, i32p]),
     "sgl_op_mse_test_cells": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, f64p]),
     "sgl_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),

@@ -22,6 +22,9 @@ names, argument order, defaults and return fields:
   MetadataSummary                       R/MetadataSummary.R:15-36 (without the hclust display order)
   GetSharedFactors / GetUniqueFactors   R/GetSharedFactors.R:4-10, R/GetUniqueFactors.R:4-10
   group_means                           the k G calls of mean(h[which(...)]) of R/RunLNMF.R:136-143, R/MetadataSummary.R:18-26
+  find_variable_features                Seurat::FindVariableFeatures(selection.method = "vst"), what R/RunNMF.R:73-74 reads as
+                                        "var.features", under the rules stated in include/singlet_hip.h (the trend is an
+                                        exact local fit at every gene, not R's interpolated loess)
   evaluate                              no R counterpart: the full-matrix error of a model (mse_test, src/singlet.cpp:536-568,
                                         with every entry drawn), per cell and per gene
 
@@ -1083,12 +1086,15 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
 
 
 def RunNMF(A, k=None, features=None, split_by=None, reps=3, tol=1e-5, L1=0.01, L2=0, verbose=2, maxit=100, test_density=0.05,
-           learning_rate=0.8, tol_overfit=1e-4, trace_test_mse=5, threads=0, seed=None):
+           learning_rate=0.8, tol_overfit=1e-4, trace_test_mse=5, threads=0, seed=None, nfeatures=None):
     """The matrix steps of RunNMF.Seurat (R/RunNMF.R:61-151) on a genes x cells matrix, without the Seurat object, on ONE
     resident context -- the matrix is uploaded once and never comes back between the steps:
       1. LogNormalize when every value is integral (sum(as.integer(v)) == sum(v), l.66-69);
       2. A <- A[features, ] (l.72-81): `features` as subset() takes rows -- 0-based integers, names or a mask; the
-         "var.features" of a Seurat object are the caller's to pass;
+         "var.features" of a Seurat object are the caller's to pass -- or `nfeatures` selects them here: the vst selection
+         (Context.variable_features) runs on the resident COUNTS right after the upload, before step 1, and its genes, in
+         rank order, are the rows of this step; the model then carries them as "var_features" (names, or indices when A
+         has no row names).  Counts only: a matrix that is not integral is refused, and so is `features` next to it;
       3. weight_by_split when `split_by` (one label per cell, any type) is given (l.86-97);
       4. k a vector: cross_validate_nmf at tol * 10, GetBestRank, the final run_nmf (l.101-125); k None: ard_nmf with
          k_max = 1e4 (l.126-145), clipped to the library's rank limit of 1024; k a scalar: run_nmf (l.146-148).
@@ -1104,6 +1110,12 @@ def RunNMF(A, k=None, features=None, split_by=None, reps=3, tol=1e-5, L1=0.01, L
         A = as_dgCMatrix(A)
     rn, cn = A.Dimnames
     rows = None
+    if nfeatures is not None:
+        if features is not None:
+            raise ValueError("pass either features or nfeatures (the variable features selected here), not both")
+        if isinstance(nfeatures, bool) or int(nfeatures) != nfeatures or int(nfeatures) < 1:
+            raise ValueError("nfeatures must be a whole number of at least 1")
+        nfeatures = int(nfeatures)
     if features is not None:
         if isinstance(features, str):
             if features == "var.features":
@@ -1129,6 +1141,12 @@ def RunNMF(A, k=None, features=None, split_by=None, reps=3, tol=1e-5, L1=0.01, L
             ctx.upload(A, None)
             v = A.x
             integral = np.sum(np.trunc(v)) == np.sum(v)   # sum(as.integer(v)) == sum(v)
+        var_features = None
+        if nfeatures is not None:
+            if not integral:
+                raise ValueError("variable features are selected on counts: A is not integral (select them elsewhere and pass features)")
+            rows = ctx.variable_features(nfeatures)["features"]
+            var_features = _subset_names(rn, rows) if rn is not None else rows
         if integral:
             ctx.log_normalize()
         if rows is not None:
@@ -1163,7 +1181,37 @@ def RunNMF(A, k=None, features=None, split_by=None, reps=3, tol=1e-5, L1=0.01, L
     finally:
         ctx.close()
     model["cv_data"] = cv_data
+    if var_features is not None:
+        model["var_features"] = var_features
     return model
+
+
+# ---------------------------------------------------------------------------
+# Variable features
+# ---------------------------------------------------------------------------
+def find_variable_features(A, nfeatures=2000, span=0.3, vmax=None, expected_var=None):
+    """Seurat::FindVariableFeatures(selection.method = "vst") on a genes x cells COUNT matrix, on the device
+    (sgl_c_variable_features; the rules are stated in include/singlet_hip.h, sgl_variable_features): {"features" (int32 gene
+    indices, 0-based, in rank order: the rows of A[var.features, ]), "mean", "variance", "variance_expected",
+    "variance_standardized"} plus "names" (the selected row names) when A has row names.  A: a dgCMatrix, anything
+    as_dgCMatrix accepts, or a native(...) object, which is staged through the typed door.  vmax None: sqrt(ncol).
+    expected_var: one expected variance per gene, used in place of the trend -- the trend here is an exact local fit at
+    every gene, not R's interpolated loess; with R's fitted values passed in, everything else agrees with Seurat's rules."""
+    from .context import _variable_features_call
+    is_native = isinstance(A, NativeMatrix)
+    if not is_native:
+        A = as_dgCMatrix(A)
+    if is_native:
+        with _NativeStage(A) as st:
+            out = st.ctx.variable_features(nfeatures, span, vmax, expected_var)
+    else:
+        L = _lib.load()
+        out = _variable_features_call(lambda *a: L.sgl_c_variable_features(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow,
+                                                                           A.ncol, *a), A.nrow, nfeatures, span, vmax, expected_var)
+    rn = A.Dimnames[0]
+    if rn is not None:
+        out["names"] = _subset_names(rn, out["features"])
+    return out
 
 
 # ---------------------------------------------------------------------------

@@ -161,6 +161,25 @@ def _evaluate_call(fn, nrow, ncol, cell_loss, gene_loss):
     return out
 
 
+def _variable_features_call(fn, nrow, nfeatures, span, vmax, expected_var):
+    """Shared by Context.variable_features and api.find_variable_features: fn(nfeatures, span, vmax, expected_var, features,
+    n_out, info) is the library call."""
+    nrow = int(nrow)
+    ev = None
+    if expected_var is not None:
+        ev = np.ascontiguousarray(expected_var, dtype=np.float64)
+        if ev.shape != (nrow,):
+            raise ValueError("expected_var needs one entry per gene (row) of A")
+    nf = int(nfeatures)
+    feats = np.zeros(max(min(nf, nrow), 1), dtype=np.int32)
+    n_out = C.c_int32()
+    info = np.empty((max(nrow, 1), 4))
+    check(fn(nf, float(span), 0.0 if vmax is None else float(vmax), ptr(ev, f64p), ptr(feats, i32p), C.byref(n_out), ptr(info, f64p)))
+    info = info[:nrow]
+    return {"features": feats[:n_out.value].copy(), "mean": info[:, 0].copy(), "variance": info[:, 1].copy(),
+            "variance_expected": info[:, 2].copy(), "variance_standardized": info[:, 3].copy()}
+
+
 class Context:
     def __init__(self, device=0, _borrowed=None):
         self._L = _lib.load()
@@ -414,6 +433,14 @@ class Context:
         nr, nc, _ = self.dims()
         return _evaluate_call(lambda *o: self._L.sgl_evaluate(self._h, *o), nr, nc, cell_loss, gene_loss)
 
+    def variable_features(self, nfeatures=2000, span=0.3, vmax=None, expected_var=None):
+        """Variable features of the resident counts (sgl_variable_features; Seurat's vst selection under this library's
+        stated rules): {"features" (int32 gene indices in rank order), "mean", "variance", "variance_expected",
+        "variance_standardized"} (one value per gene).  vmax None: sqrt(ncol).  expected_var: one expected variance per
+        gene, used instead of the trend (another loess's, for parity with it).  The matrix and a running fit are only read."""
+        nr, _, _ = self.dims()
+        return _variable_features_call(lambda *a: self._L.sgl_variable_features(self._h, *a), nr, nfeatures, span, vmax, expected_var)
+
     def set_graph(self, G):
         """c_gcnmf's cell graph (sgl_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over the resident cells, or None
         to clear it.  Call after fit_init (which drops it)."""
@@ -595,6 +622,42 @@ class Context:
         out = C.c_double()
         check(self._L.sgl_op_mse_test(self._h, int(seed), int(inv_density), C.byref(out)))
         return out.value
+
+    # the stages of variable_features, one at a time (mu, sd: one value per gene)
+    def _gene_vec(self, v, what):
+        a = np.ascontiguousarray(v, dtype=np.float64)
+        if a.shape != (self.dims()[0],):
+            raise ValueError("%s needs one entry per gene (row) of A" % what)
+        return a
+
+    def op_gene_mean(self):
+        """(mean, count) per gene of the resident matrix (sgl_op_gene_mean): sum of the stored values / ncol, stored entries."""
+        nr = self.dims()[0]
+        mean, count = np.empty(max(nr, 1)), np.zeros(max(nr, 1), dtype=np.int64)
+        check(self._L.sgl_op_gene_mean(self._h, ptr(mean, f64p), ptr(count, i64p)))
+        return mean[:nr], count[:nr]
+
+    def op_gene_var(self, mu):
+        mu = self._gene_vec(mu, "mu")
+        out = np.empty(max(mu.shape[0], 1))
+        check(self._L.sgl_op_gene_var(self._h, ptr(mu, f64p), ptr(out, f64p)))
+        return out[:mu.shape[0]]
+
+    def op_gene_var_std(self, mu, sd, vmax):
+        mu, sd = self._gene_vec(mu, "mu"), self._gene_vec(sd, "sd")
+        out = np.empty(max(mu.shape[0], 1))
+        check(self._L.sgl_op_gene_var_std(self._h, ptr(mu, f64p), ptr(sd, f64p), float(vmax), ptr(out, f64p)))
+        return out[:mu.shape[0]]
+
+    def op_loess_direct(self, x, y, q):
+        """The trend of variable_features (sgl_op_loess_direct): the local fit of y on the ascending x at every x[i], windows of q."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if x.ndim != 1 or x.shape != y.shape:
+            raise ValueError("x and y must be vectors of one length")
+        out = np.empty(max(x.shape[0], 1))
+        check(self._L.sgl_op_loess_direct(self._h, ptr(x, f64p), ptr(y, f64p), x.shape[0], int(q), ptr(out, f64p)))
+        return out[:x.shape[0]]
 
     def op_rhs_masked(self, which, F, seed, inv_density):
         """op_rhs with the entries the mask (seed, inv_density) draws left out (sgl_op_rhs_masked): which = 0 / 1 hash every

@@ -435,6 +435,16 @@ int sgl_group_ids_check(const char* who, const char* name, const int32_t* group,
 // unclamped rank partials first).  Uses red, B, G and the workspace as scratch; synchronises the stream.
 int sgl_eval_shard(sgl_ctx* c, bool clamp_genes, double* cell_sum, double* cell_loss, double* gene_loss);
 
+// variable features (kernels_hvg.hip; include/singlet_hip.h, sgl_variable_features).  All arrays are the HOST's; every call
+// only reads the context, allocates its own temporaries and synchronises the stream before it returns.
+// one gene pass over c->At: mode 0 mean (out = mean, count = c_g), 1 variance about mu, 2 standardised variance (mu, sd, vmax)
+int sgl_hvg_pass(sgl_ctx* c, int mode, const double* mu, const double* sd, double vmax, double* out, int64_t* count);
+int sgl_loess_direct(sgl_ctx* c, const double* x, const double* y, int64_t n, int64_t q, double* fitted);   // arguments checked by the caller
+int sgl_hvg_args_check(const char* who, int32_t nrow, int32_t ncol, int32_t nfeatures, double span, const double* expected_var,
+                       const int32_t* features, const int32_t* n_out);
+int sgl_hvg_select(sgl_ctx* c, int32_t nfeatures, double span, double vmax, const double* expected_var, int32_t* features,
+                   int32_t* n_out, double* info);   // the composite after its refusals
+
 // row-wise rasterisation (kernels_raster.hip): out (nb x ncol, column-major) = means of rows [b n, b n + n), nb >= 1
 int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, double* out);
 int k_raster_dense(hipStream_t s, const double* A, int64_t nrow, int64_t ncol, int64_t n, int64_t nb, double* out);

@@ -1908,6 +1908,35 @@ extern "C" int sgl_c_evaluate(const double* Ax, const int32_t* Ai, const int32_t
     return sgl_evaluate(hd.c, sse, mse, cell_loss, gene_loss);
 }
 
+// Variable features (include/singlet_hip.h; kernels_hvg.hip): the refusals, then the composite that only reads the context.
+extern "C" int sgl_variable_features(sgl_ctx* c, int32_t nfeatures, double span, double vmax, const double* expected_var,
+                                     int32_t* features, int32_t* n_out, double* info) {
+    CTX_GUARD(c);
+    if (c->team || c->allreduce) {
+        sgl_set_error("sgl_variable_features: the context is a shard of a team or has an all-reduce hook; the moments of this "
+                      "shard's cells are not the matrix's");
+        return SGL_ESTATE;
+    }
+    if (!c->A.p || !c->At.p) { sgl_set_error("sgl_variable_features: no matrix resident"); return SGL_ESTATE; }
+    if (c->cell_offset != 0 || c->ncells_total != (int64_t)c->A.ncol) {
+        sgl_set_error("sgl_variable_features: the context holds a shard (cells %lld .. %lld of %lld); select on the whole matrix",
+                      (long long)c->cell_offset, (long long)c->cell_offset + c->A.ncol, (long long)c->ncells_total);
+        return SGL_ESTATE;
+    }
+    SGLCHK(sgl_hvg_args_check("sgl_variable_features", c->A.nrow, c->A.ncol, nfeatures, span, expected_var, features, n_out));
+    return sgl_hvg_select(c, nfeatures, span, vmax, expected_var, features, n_out, info);
+}
+
+extern "C" int sgl_c_variable_features(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol,
+                                       int32_t nfeatures, double span, double vmax, const double* expected_var, int32_t* features,
+                                       int32_t* n_out, double* info) {
+    SGLCHK(sgl_hvg_args_check("sgl_c_variable_features", std::max(nrow, 0), ncol, nfeatures, span, expected_var, features, n_out));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, nullptr, nullptr, nullptr, nrow, ncol, 0, ncol));
+    return sgl_variable_features(hd.c, nfeatures, span, vmax, expected_var, features, n_out, info);
+}
+
 // c_gcnmf's cell graph G (src/singlet.cpp:1668-1730): n x n, n = the cells of the resident matrix, as a dgCMatrix.  Checked
 // on the host (the kernels index factor columns by its rows): p[0] = 0 and monotone, rows strictly ascending within a column
 // and in [0, n), values finite.  Columns above SGL_GRAPH_HUB entries get their segment lists here (kernels_graph.hip).
@@ -2353,6 +2382,33 @@ extern "C" int sgl_op_rhs_masked(sgl_ctx* c, int which, const double* F, int32_t
         M.seg = saved; M.tile_rows = str; M.ntiles = snt;
     }
     return rc;
+}
+
+// The stages of sgl_variable_features one at a time (kernels_hvg.hip)
+static int op_gene_pass(sgl_ctx* c, const char* who, int mode, const double* mu, const double* sd, double vmax, double* out, int64_t* count) {
+    CTX_GUARD(c);
+    if (!c->At.p) { sgl_set_error("%s: no matrix resident", who); return SGL_ESTATE; }
+    if (!out || (mode == 0 && !count) || (mode >= 1 && !mu) || (mode == 2 && !sd)) { sgl_set_error("%s: NULL array", who); return SGL_EINVAL; }
+    return sgl_hvg_pass(c, mode, mu, sd, vmax, out, count);
+}
+extern "C" int sgl_op_gene_mean(sgl_ctx* c, double* mean, int64_t* count) { return op_gene_pass(c, "sgl_op_gene_mean", 0, nullptr, nullptr, 0.0, mean, count); }
+extern "C" int sgl_op_gene_var(sgl_ctx* c, const double* mu, double* var) { return op_gene_pass(c, "sgl_op_gene_var", 1, mu, nullptr, 0.0, var, nullptr); }
+extern "C" int sgl_op_gene_var_std(sgl_ctx* c, const double* mu, const double* sd, double vmax, double* out) {
+    return op_gene_pass(c, "sgl_op_gene_var_std", 2, mu, sd, vmax, out, nullptr);
+}
+extern "C" int sgl_op_loess_direct(sgl_ctx* c, const double* x, const double* y, int64_t n, int64_t q, double* fitted) {
+    CTX_GUARD(c);
+    if (!x || !y || !fitted) { sgl_set_error("sgl_op_loess_direct: NULL array"); return SGL_EINVAL; }
+    if (n < 1 || n > INT32_MAX || q < 1 || q > n) {
+        sgl_set_error("sgl_op_loess_direct: n = %lld, q = %lld: 1 <= q <= n < 2^31 is needed", (long long)n, (long long)q);
+        return SGL_EINVAL;
+    }
+    for (int64_t j = 0; j < n; ++j)
+        if (!std::isfinite(x[j]) || (j > 0 && x[j] < x[j - 1])) {
+            sgl_set_error("sgl_op_loess_direct: x[%lld] = %g: x must be finite and ascending", (long long)j, x[j]);
+            return SGL_EINVAL;
+        }
+    return sgl_loess_direct(c, x, y, n, q, fitted);
 }
 
 // k_nnls_percol with a Gram per column (gstride = k * k), as every masked half-step calls it
