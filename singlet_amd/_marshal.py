@@ -1,0 +1,81 @@
+"""Marshalling shared by the fit calls of api.py and the handles of context.py: pointer triples, column-major images and
+the output buffers of the two fit families, each yielding its trailing ctypes arguments in ABI order."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import f64p, i32p, ptr
+
+
+def csc_ptrs(A):
+    """The (x, i, p) pointers of a dgCMatrix; three NULLs for None."""
+    return (None, None, None) if A is None else (ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p))
+
+
+def colmajor(X, message):
+    """Column-major image of a 2-D array, as the library reads an R matrix: shape (cols, rows), float64, contiguous.
+    message: the caller's ValueError text for anything that is not 2-D."""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError(message)
+    return np.ascontiguousarray(X.T)
+
+
+class _FitOutputs:
+    """shape = (m, n, k): w_out (m, k) -- (k, m) with w_m_by_k, the m x k column-major image c_gcnmf writes --, h_out
+    (n, k) and d_out; shape = None: no factor buffers (the run loops of a handle: get_factors fills w, d, h later)."""
+
+    def __init__(self, shape, w_m_by_k=False):
+        self.w = self.d = self.h = None
+        if shape is not None:
+            m, n, k = shape
+            self.w, self.h, self.d = np.empty((k, m) if w_m_by_k else (m, k)), np.empty((n, k)), np.empty(k)
+
+    def _factor_args(self):
+        return () if self.w is None else (ptr(self.w, f64p), ptr(self.d, f64p), ptr(self.h, f64p))
+
+
+class NmfOutputs(_FitOutputs):
+    """What a fit of the c_nmf family writes: the factors, n_iter and the tol trace of max(maxit, 1) entries."""
+
+    def __init__(self, shape, maxit, w_m_by_k=False):
+        super().__init__(shape, w_m_by_k)
+        self.n_iter = C.c_int32()
+        self.trace = np.zeros(max(int(maxit), 1))
+
+    def args(self):
+        return (*self._factor_args(), C.byref(self.n_iter), ptr(self.trace, f64p))
+
+    def run(self):
+        """(iterations, their tol) as nmf_run returns them."""
+        return self.n_iter.value, self.trace[:self.n_iter.value].copy()
+
+    def result(self):
+        n_iter, tol = self.run()
+        return {"w": self.w.T, "d": self.d, "h": self.h.T, "iter": n_iter, "tol": tol}
+
+
+class ArdOutputs(_FitOutputs):
+    """What a fit of the ARD family writes: the factors, four traces of maxit + 2 entries, nt (the entries written) and,
+    with nit (the run loops), the iterations run."""
+
+    def __init__(self, shape, maxit, nit=False):
+        super().__init__(shape)
+        cap = int(maxit) + 2
+        self.test_mse, self.tol, self.score_overfit = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        self.iter = np.zeros(cap, dtype=np.int32)
+        self.nt = C.c_int32()
+        self.nit = C.c_int32() if nit else None
+
+    def args(self):
+        tail = (C.byref(self.nt),) if self.nit is None else (C.byref(self.nt), C.byref(self.nit))
+        return (*self._factor_args(), ptr(self.test_mse, f64p), ptr(self.iter, i32p), ptr(self.tol, f64p),
+                ptr(self.score_overfit, f64p), *tail)
+
+    def traces(self):
+        q = self.nt.value
+        return {"test_mse": self.test_mse[:q].copy(), "iter": self.iter[:q].copy(), "tol": self.tol[:q].copy(),
+                "score_overfit": self.score_overfit[:q].copy()}
+
+    def result(self):
+        return {"w": self.w.T, "d": self.d, "h": self.h.T, **self.traces()}

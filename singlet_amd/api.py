@@ -41,7 +41,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from .context import _chunk_list, make_callbacks
+from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs
+from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
 
@@ -83,60 +84,55 @@ def call_times():
     return dict(zip(CALL_TIMES_KEYS, (float(v) for v in out)))
 
 
-def c_nmf(A, At, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w):
-    """.Call(`_singlet_c_nmf`, ...) -> list(w = k x m, d = k, h = k x n)  (src/singlet.cpp:665)."""
-    L = _lib.load()
+def _fit(fn, inp, tol, maxit, verbose, penalties, threads, extra=(), ard=False, w_m_by_k=False):
+    """The body the one-shot fits share.  inp: (the matrix arguments, (m, n, k), the w arguments, what must stay alive) as
+    _sparse_in / _dense_in / _list_in spell them; extra: what the entry point takes between k and its outputs.  The log
+    header is printed here, after every check of the inputs."""
+    matrix, shape, w, _keep = inp
+    out = ArdOutputs(shape, maxit) if ard else NmfOutputs(shape, maxit, w_m_by_k)
+    cb = make_callbacks(_verbose_log(verbose, ard))
+    check(fn(*matrix, float(tol), int(maxit), int(bool(verbose)), *penalties, int(threads), *w, *extra, *out.args(), C.byref(cb)))
+    return out.result()
+
+
+def _ard_extra(seed, inv_density, overfit_threshold, trace_test_mse):
+    return int(seed), int(inv_density), float(overfit_threshold), int(trace_test_mse)
+
+
+def _sparse_in(A, At, w):
     A = as_dgCMatrix(A)
     At = None if At is None else as_dgCMatrix(At)
     wb = _w_in(w, A.nrow)
-    m, k = wb.shape
-    n = A.ncol
-    w_out, h_out, d_out = np.empty((m, k)), np.empty((n, k)), np.empty(k)
-    n_iter = C.c_int32()
-    tr = np.zeros(max(int(maxit), 1))
-    cb = make_callbacks(_verbose_log(verbose))
-    t = (ptr(At.x, f64p), ptr(At.i, i32p), ptr(At.p, i32p)) if At is not None else (None, None, None)
-    check(L.sgl_c_nmf(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), *t, A.nrow, A.ncol, float(tol), int(maxit),
-                      int(bool(verbose)), L1_w, L1_h, L2_w, L2_h, int(threads), ptr(wb, f64p), k, ptr(w_out, f64p),
-                      ptr(d_out, f64p), ptr(h_out, f64p), C.byref(n_iter), ptr(tr, f64p), C.byref(cb)))
-    return {"w": w_out.T, "d": d_out, "h": h_out.T, "iter": n_iter.value, "tol": tr[:n_iter.value].copy()}
+    k = wb.shape[1]
+    return (*csc_ptrs(A), *csc_ptrs(At), A.nrow, A.ncol), (A.nrow, A.ncol, k), (ptr(wb, f64p), k), (A, At, wb)
+
+
+def _dense_in(A, w):
+    Af = colmajor(A, "A must be a matrix")
+    n, m = Af.shape
+    wb = _w_in(w, m)
+    k = wb.shape[1]
+    return (ptr(Af, f64p), m, n), (m, n, k), (ptr(wb, f64p), k), (Af, wb)
+
+
+def _list_in(A_, At_, w):
+    a, t, nrow, n, keep = _chunk_lists(A_, At_, "A_ must hold at least one matrix", "all chunks of A_ must have the same number of rows")
+    wb = _w_in(w, nrow)
+    k = wb.shape[1]
+    return (*a, *t, nrow), (nrow, n, k), (ptr(wb, f64p), k), (keep, wb)
+
+
+def c_nmf(A, At, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w):
+    """.Call(`_singlet_c_nmf`, ...) -> list(w = k x m, d = k, h = k x n)  (src/singlet.cpp:665)."""
+    L = _lib.load()
+    return _fit(L.sgl_c_nmf, _sparse_in(A, At, w), tol, maxit, verbose, (L1_w, L1_h, L2_w, L2_h), threads)
 
 
 def c_nmf_dense(A, At, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w):
     """.Call(`_singlet_c_nmf_dense`, ...) -> list(w, d, h)  (src/singlet.cpp:1052-1054).  A: dense m x n
     array; At is accepted for signature parity and ignored (the transpose is built on the device)."""
     L = _lib.load()
-    A = np.asarray(A, dtype=np.float64)
-    if A.ndim != 2:
-        raise ValueError("A must be a matrix")
-    m, n = A.shape
-    Af = np.ascontiguousarray(A.T)   # column-major image
-    wb = _w_in(w, m)
-    k = wb.shape[1]
-    w_out, h_out, d_out = np.empty((m, k)), np.empty((n, k)), np.empty(k)
-    n_iter = C.c_int32()
-    tr = np.zeros(max(int(maxit), 1))
-    cb = make_callbacks(_verbose_log(verbose))
-    check(L.sgl_c_nmf_dense(ptr(Af, f64p), m, n, float(tol), int(maxit), int(bool(verbose)), L1_w, L1_h, L2_w, L2_h,
-                            int(threads), ptr(wb, f64p), k, ptr(w_out, f64p), ptr(d_out, f64p), ptr(h_out, f64p),
-                            C.byref(n_iter), ptr(tr, f64p), C.byref(cb)))
-    return {"w": w_out.T, "d": d_out, "h": h_out.T, "iter": n_iter.value, "tol": tr[:n_iter.value].copy()}
-
-
-def _list_args(A_, At_):
-    A_ = list(A_)
-    if not A_:
-        raise ValueError("A_ must hold at least one matrix")
-    a, keep_a = _chunk_list(A_)
-    nrow = keep_a[0][0].nrow
-    if any(c.nrow != nrow for c in keep_a[0]):
-        raise ValueError("all chunks of A_ must have the same number of rows")
-    if At_ is None or len(At_) == 0:
-        t, keep_t = (0, None, None, None, None), None
-    else:
-        t, keep_t = _chunk_list(At_)
-    n = sum(c.ncol for c in keep_a[0])
-    return a, t, nrow, n, (keep_a, keep_t)
+    return _fit(L.sgl_c_nmf_dense, _dense_in(A, w), tol, maxit, verbose, (L1_w, L1_h, L2_w, L2_h), threads)
 
 
 def c_nmf_sparse_list(A_, At_, tol, maxit, verbose, L1, L2, threads, w):
@@ -144,65 +140,23 @@ def c_nmf_sparse_list(A_, At_, tol, maxit, verbose, L1, L2, threads, w):
     (the predict over chunks carries a running column offset, :384-402), At_ a list of column chunks of t(A)
     (None / empty: the transpose is built on the device).  The chunks are joined on the device."""
     L = _lib.load()
-    a, t, nrow, n, keep = _list_args(A_, At_)
-    wb = _w_in(w, nrow)
-    m, k = wb.shape
-    w_out, h_out, d_out = np.empty((m, k)), np.empty((n, k)), np.empty(k)
-    n_iter = C.c_int32()
-    tr = np.zeros(max(int(maxit), 1))
-    cb = make_callbacks(_verbose_log(verbose))
-    check(L.sgl_c_nmf_sparse_list(*a, *t, nrow, float(tol), int(maxit), int(bool(verbose)), L1, L2, int(threads), ptr(wb, f64p), k,
-                                  ptr(w_out, f64p), ptr(d_out, f64p), ptr(h_out, f64p), C.byref(n_iter), ptr(tr, f64p),
-                                  C.byref(cb)))
-    return {"w": w_out.T, "d": d_out, "h": h_out.T, "iter": n_iter.value, "tol": tr[:n_iter.value].copy()}
+    return _fit(L.sgl_c_nmf_sparse_list, _list_in(A_, At_, w), tol, maxit, verbose, (L1, L2), threads)
 
 
 def c_ard_nmf_sparse_list(A_, At_, tol, maxit, verbose, L1, L2, threads, w, rng_seed, inv_density, overfit_threshold,
                           trace_test_mse):
     """.Call(`_singlet_c_ard_nmf_sparse_list`, ...)  (src/singlet.cpp:1162-1234)."""
     L = _lib.load()
-    a, t, nrow, n, keep = _list_args(A_, At_)
-    wb = _w_in(w, nrow)
-    m, k = wb.shape
-    w_out, h_out, d_out = np.empty((m, k)), np.empty((n, k)), np.empty(k)
-    cap = int(maxit) + 2
-    tm, ft, so = np.zeros(cap), np.zeros(cap), np.zeros(cap)
-    itv = np.zeros(cap, dtype=np.int32)
-    nt = C.c_int32()
-    cb = make_callbacks(_verbose_log(verbose, ard=True))
-    check(L.sgl_c_ard_nmf_sparse_list(*a, *t, nrow, float(tol), int(maxit), int(bool(verbose)), L1, L2, int(threads),
-                                      ptr(wb, f64p), k, int(rng_seed), int(inv_density), float(overfit_threshold),
-                                      int(trace_test_mse), ptr(w_out, f64p), ptr(d_out, f64p), ptr(h_out, f64p), ptr(tm, f64p),
-                                      ptr(itv, i32p), ptr(ft, f64p), ptr(so, f64p), C.byref(nt), C.byref(cb)))
-    q = nt.value
-    return {"w": w_out.T, "d": d_out, "h": h_out.T, "test_mse": tm[:q].copy(), "iter": itv[:q].copy(),
-            "tol": ft[:q].copy(), "score_overfit": so[:q].copy()}
+    return _fit(L.sgl_c_ard_nmf_sparse_list, _list_in(A_, At_, w), tol, maxit, verbose, (L1, L2), threads,
+                _ard_extra(rng_seed, inv_density, overfit_threshold, trace_test_mse), ard=True)
 
 
 def c_ard_nmf_dense(A, At, tol, maxit, verbose, L1, L2, threads, w, seed, inv_density, overfit_threshold, trace_test_mse):
     """.Call(`_singlet_c_ard_nmf_dense`, ...)  (src/singlet.cpp:1357-1361).  A: dense m x n array; At is accepted
     for signature parity and ignored."""
     L = _lib.load()
-    A = np.asarray(A, dtype=np.float64)
-    if A.ndim != 2:
-        raise ValueError("A must be a matrix")
-    m, n = A.shape
-    Af = np.ascontiguousarray(A.T)
-    wb = _w_in(w, m)
-    k = wb.shape[1]
-    w_out, h_out, d_out = np.empty((m, k)), np.empty((n, k)), np.empty(k)
-    cap = int(maxit) + 2
-    tm, ft, so = np.zeros(cap), np.zeros(cap), np.zeros(cap)
-    itv = np.zeros(cap, dtype=np.int32)
-    nt = C.c_int32()
-    cb = make_callbacks(_verbose_log(verbose, ard=True))
-    check(L.sgl_c_ard_nmf_dense(ptr(Af, f64p), m, n, float(tol), int(maxit), int(bool(verbose)), L1, L2, int(threads),
-                                ptr(wb, f64p), k, int(seed), int(inv_density), float(overfit_threshold), int(trace_test_mse),
-                                ptr(w_out, f64p), ptr(d_out, f64p), ptr(h_out, f64p), ptr(tm, f64p), ptr(itv, i32p),
-                                ptr(ft, f64p), ptr(so, f64p), C.byref(nt), C.byref(cb)))
-    q = nt.value
-    return {"w": w_out.T, "d": d_out, "h": h_out.T, "test_mse": tm[:q].copy(), "iter": itv[:q].copy(),
-            "tol": ft[:q].copy(), "score_overfit": so[:q].copy()}
+    return _fit(L.sgl_c_ard_nmf_dense, _dense_in(A, w), tol, maxit, verbose, (L1, L2), threads,
+                _ard_extra(seed, inv_density, overfit_threshold, trace_test_mse), ard=True)
 
 
 def c_linked_nmf(A, At, tol, maxit, verbose, L1, L2, threads, w, link_h, link_w):
@@ -210,32 +164,23 @@ def c_linked_nmf(A, At, tol, maxit, verbose, L1, L2, threads, w, link_h, link_w)
     are R matrices (rows x cols); a link whose column count does not match its side is ignored, as in
     the reference (R/RunLNMF.R passes a 1 x 1 matrix to switch a side off)."""
     L = _lib.load()
-    A = as_dgCMatrix(A)
-    At = None if At is None else as_dgCMatrix(At)
-    wb = _w_in(w, A.nrow)
-    m, k = wb.shape
-    n = A.ncol
-    w_out, h_out, d_out = np.empty((m, k)), np.empty((n, k)), np.empty(k)
-    n_iter = C.c_int32()
-    tr = np.zeros(max(int(maxit), 1))
-    cb = make_callbacks(_verbose_log(verbose))
-    t = (ptr(At.x, f64p), ptr(At.i, i32p), ptr(At.p, i32p)) if At is not None else (None, None, None)
+    inp = _sparse_in(A, At, w)
+    lh, lhr, lhc, keep_h = _link_image(link_h)
+    lw, lwr, lwc, keep_w = _link_image(link_w)
+    return _fit(L.sgl_c_linked_nmf, inp, tol, maxit, verbose, (L1, L2), threads, (lh, lhr, lhc, lw, lwr, lwc))
 
-    def link(Lk):
-        if Lk is None:
-            return None, 0, 0, None
-        Lk = np.asarray(Lk, dtype=np.float64)
-        if Lk.ndim != 2:
-            raise ValueError("link matrices must be 2-D")
-        buf = np.ascontiguousarray(Lk.T)   # column-major image of the R matrix
-        return ptr(buf, f64p), Lk.shape[0], Lk.shape[1], buf
-    lh, lhr, lhc, keep_h = link(link_h)
-    lw, lwr, lwc, keep_w = link(link_w)
-    check(L.sgl_c_linked_nmf(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), *t, A.nrow, A.ncol, float(tol), int(maxit),
-                             int(bool(verbose)), L1, L2, int(threads), ptr(wb, f64p), k, lh, lhr, lhc, lw, lwr, lwc,
-                             ptr(w_out, f64p), ptr(d_out, f64p), ptr(h_out, f64p), C.byref(n_iter), ptr(tr, f64p),
-                             C.byref(cb)))
-    return {"w": w_out.T, "d": d_out, "h": h_out.T, "iter": n_iter.value, "tol": tr[:n_iter.value].copy()}
+
+def _w_either(w, nrow, square_is_k_by_m):
+    """A w that may come k x m or m x k -> (its column-major image, rows, cols, k).  The reference has two rules for which
+    it is, and they stay two: c_project_model (src/singlet.cpp:406) reads w as m x k whenever nrow(w) == nrow(A);
+    c_gcnmf (l.1713) and Rcpp_predict (l.350-367) only when w is not square as well (square_is_k_by_m)."""
+    wf = colmajor(w, "w must be a matrix")
+    w_cols, w_rows = wf.shape
+    return wf, w_rows, w_cols, (w_cols if _w_is_m_by_k(w_rows, w_cols, nrow, square_is_k_by_m) else w_rows)
+
+
+def _w_is_m_by_k(w_rows, w_cols, nrow, square_is_k_by_m):
+    return w_rows == nrow and not (square_is_k_by_m and w_rows == w_cols)
 
 
 def c_gcnmf(A, At, G, tol, maxit, verbose, L1, L2, threads, w):
@@ -246,63 +191,27 @@ def c_gcnmf(A, At, G, tol, maxit, verbose, L1, L2, threads, w):
     A = as_dgCMatrix(A)
     At = None if At is None else as_dgCMatrix(At)
     G = as_dgCMatrix(G)
-    w = np.asarray(w, dtype=np.float64)
-    if w.ndim != 2:
-        raise ValueError("w must be a matrix")
-    w_rows, w_cols = w.shape
-    k = w_cols if (w_rows == A.nrow and w_rows != w_cols) else w_rows
-    wf = np.ascontiguousarray(w.T)   # column-major image of w
-    m, n = A.nrow, A.ncol
-    w_out, h_out, d_out = np.empty((k, m)), np.empty((n, k)), np.empty(k)   # w_out: m x k column-major
-    n_iter = C.c_int32()
-    tr = np.zeros(max(int(maxit), 1))
-    cb = make_callbacks(_verbose_log(verbose))
-    t = (ptr(At.x, f64p), ptr(At.i, i32p), ptr(At.p, i32p)) if At is not None else (None, None, None)
-    check(L.sgl_c_gcnmf(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), *t, m, n, ptr(G.x, f64p), ptr(G.i, i32p),
-                        ptr(G.p, i32p), G.nrow, G.ncol, float(tol), int(maxit), int(bool(verbose)), float(L1), float(L2),
-                        int(threads), ptr(wf, f64p), w_rows, w_cols, k, ptr(w_out, f64p), ptr(d_out, f64p), ptr(h_out, f64p),
-                        C.byref(n_iter), ptr(tr, f64p), C.byref(cb)))
-    return {"w": w_out.T, "d": d_out, "h": h_out.T, "iter": n_iter.value, "tol": tr[:n_iter.value].copy()}
+    wf, w_rows, w_cols, k = _w_either(w, A.nrow, square_is_k_by_m=True)
+    inp = ((*csc_ptrs(A), *csc_ptrs(At), A.nrow, A.ncol, *csc_ptrs(G), G.nrow, G.ncol), (A.nrow, A.ncol, k),
+           (ptr(wf, f64p), w_rows, w_cols, k), (A, At, G, wf))
+    return _fit(L.sgl_c_gcnmf, inp, tol, maxit, verbose, (float(L1), float(L2)), threads, w_m_by_k=True)   # w_out: m x k column-major
 
 
 def c_ard_nmf(A, At, tol, maxit, verbose, L1, L2, threads, w, seed, inv_density, overfit_threshold, trace_test_mse):
     """.Call(`_singlet_c_ard_nmf`, ...) -> list(w, d, h, test_mse, iter, tol, score_overfit) (src/singlet.cpp:1144-1151)."""
     L = _lib.load()
-    A = as_dgCMatrix(A)
-    At = None if At is None else as_dgCMatrix(At)
-    wb = _w_in(w, A.nrow)
-    m, k = wb.shape
-    n = A.ncol
-    w_out, h_out, d_out = np.empty((m, k)), np.empty((n, k)), np.empty(k)
-    cap = int(maxit) + 2
-    tm, ft, so = np.zeros(cap), np.zeros(cap), np.zeros(cap)
-    itv = np.zeros(cap, dtype=np.int32)
-    nt = C.c_int32()
-    cb = make_callbacks(_verbose_log(verbose, ard=True))
-    t = (ptr(At.x, f64p), ptr(At.i, i32p), ptr(At.p, i32p)) if At is not None else (None, None, None)
-    check(L.sgl_c_ard_nmf(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), *t, A.nrow, A.ncol, float(tol), int(maxit),
-                          int(bool(verbose)), L1, L2, int(threads), ptr(wb, f64p), k, int(seed), int(inv_density),
-                          float(overfit_threshold), int(trace_test_mse), ptr(w_out, f64p), ptr(d_out, f64p),
-                          ptr(h_out, f64p), ptr(tm, f64p), ptr(itv, i32p), ptr(ft, f64p), ptr(so, f64p), C.byref(nt),
-                          C.byref(cb)))
-    q = nt.value
-    return {"w": w_out.T, "d": d_out, "h": h_out.T, "test_mse": tm[:q].copy(), "iter": itv[:q].copy(),
-            "tol": ft[:q].copy(), "score_overfit": so[:q].copy()}
+    return _fit(L.sgl_c_ard_nmf, _sparse_in(A, At, w), tol, maxit, verbose, (L1, L2), threads,
+                _ard_extra(seed, inv_density, overfit_threshold, trace_test_mse), ard=True)
 
 
 def c_project_model(A, w, L1, L2, threads):
     """.Call(`_singlet_c_project_model`, ...) -> list(h = k x n, d = k)  (src/singlet.cpp:405-413)."""
     L = _lib.load()
     A = as_dgCMatrix(A)
-    w = np.asarray(w, dtype=np.float64)
-    if w.ndim != 2:
-        raise ValueError("w must be a matrix")
-    w_rows, w_cols = w.shape
-    wf = np.ascontiguousarray(w.T)  # column-major image of w
-    k = w_cols if w_rows == A.nrow else w_rows
+    wf, w_rows, w_cols, k = _w_either(w, A.nrow, square_is_k_by_m=False)
     h_out, d_out = np.empty((A.ncol, k)), np.empty(k)
-    check(L.sgl_c_project_model(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow, A.ncol, ptr(wf, f64p),
-                                w_rows, w_cols, L1, L2, int(threads), ptr(h_out, f64p), ptr(d_out, f64p)))
+    check(L.sgl_c_project_model(*csc_ptrs(A), A.nrow, A.ncol, ptr(wf, f64p), w_rows, w_cols, L1, L2, int(threads),
+                                ptr(h_out, f64p), ptr(d_out, f64p)))
     return {"h": h_out.T, "d": d_out}
 
 
@@ -310,15 +219,9 @@ def Rcpp_predict(A, w, L1, L2, threads):
     """.Call(`_singlet_Rcpp_predict`, ...) -> h (k x n)  (src/singlet.cpp:350-367)."""
     L = _lib.load()
     A = as_dgCMatrix(A)
-    w = np.asarray(w, dtype=np.float64)
-    if w.ndim != 2:
-        raise ValueError("w must be a matrix")
-    w_rows, w_cols = w.shape
-    wf = np.ascontiguousarray(w.T)
-    k = w_cols if (w_rows == A.nrow and w_cols != A.nrow) else w_rows
+    wf, w_rows, w_cols, k = _w_either(w, A.nrow, square_is_k_by_m=True)
     h_out = np.empty((A.ncol, k))
-    check(L.sgl_rcpp_predict(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow, A.ncol, ptr(wf, f64p), w_rows, w_cols,
-                             L1, L2, int(threads), ptr(h_out, f64p)))
+    check(L.sgl_rcpp_predict(*csc_ptrs(A), A.nrow, A.ncol, ptr(wf, f64p), w_rows, w_cols, L1, L2, int(threads), ptr(h_out, f64p)))
     return h_out.T
 
 
@@ -347,37 +250,21 @@ def _sort_model(model, rn=None, cn=None):
     return model
 
 
-class _NativeStage:
-    """A NativeMatrix (native()) staged on one Context through the typed door: `with _NativeStage(N) as st` gives st.ctx,
-    st.report (Context.upload_native) and st.fits, the resident fits the drivers already run on (as RunNMF stages them)."""
-
-    def __init__(self, N, device=0):
-        from .context import Context
-        self.ctx = Context(device)
-        try:
-            self.report = self.ctx.upload_native(N)
-        except Exception:
-            self.ctx.close()
-            raise
-        self.Dimnames = N.Dimnames
-
-    @property
-    def fits(self):
-        return _ResidentFits(None, ctx=self.ctx, Dimnames=self.Dimnames)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.ctx.close()
+def _on_native(N, body):
+    """body(ctx, fits) on one Context that holds the NativeMatrix N (native()), staged through the typed door
+    (Context.upload_native); fits: the resident fits the drivers already run on (as RunNMF stages them).  The NativeMatrix
+    case of every driver; what a driver checks before it stages, it checks before it calls this."""
+    from .context import Context
+    with Context(0) as ctx:
+        ctx.upload_native(N)
+        return body(ctx, _ResidentFits(None, ctx=ctx, Dimnames=N.Dimnames))
 
 
 def run_nmf(A, rank, tol=1e-4, maxit=100, verbose=True, L1=0.01, L2=0, threads=0, seed=None, _fits=None):
     """R/run_nmf.R:18-77 (sparse, single-matrix branch).  `seed` replaces R's global RNG state
     (stats::runif, l.55): an int or numpy Generator.  A NativeMatrix (native()) is staged on the device as it is."""
     if _fits is None and isinstance(A, NativeMatrix):
-        with _NativeStage(A) as st:
-            return run_nmf(None, rank, tol, maxit, verbose, L1, L2, threads, seed, _fits=st.fits)
+        return _on_native(A, lambda ctx, fits: run_nmf(None, rank, tol, maxit, verbose, L1, L2, threads, seed, _fits=fits))
     if _fits is not None:   # RunNMF: the matrix is staged and resident already (A is not read)
         if verbose:
             print("running with sparse optimization")
@@ -412,7 +299,7 @@ def _gcnmf_on_team(A, G, tol, maxit, verbose, L1, L2, w, devices):
     if w.ndim != 2:
         raise ValueError("w must be a matrix")
     given = w.shape
-    if not (w.shape[0] == A.nrow and w.shape[0] != w.shape[1]):   # c_gcnmf's rule (l.1713): such a w is k x m; the team takes m x k
+    if not _w_is_m_by_k(*w.shape, A.nrow, square_is_k_by_m=True):   # c_gcnmf's rule (l.1713): such a w is k x m; the team takes m x k
         w = w.T
     if w.shape[0] != A.nrow:
         raise ValueError("w is %d x %d; expected k x m or m x k with m = %d" % (given[0], given[1], A.nrow))
@@ -468,19 +355,21 @@ def run_gcnmf(A, graph, k, split_by=None, tol=1e-5, L1=0.01, L2=0, verbose=2, ma
 
 
 def _staged(A, op, Dimnames=None):
-    """Upload A, run a staging operator on the device, return the transformed dgCMatrix (Dimnames: those of the result
-    when the operator changes the shape)."""
+    """Upload A (a NativeMatrix: through the typed door), run a staging operator on the device, return the transformed
+    dgCMatrix (Dimnames: those of the result when the operator changes the shape)."""
     from .context import Context
-    A = as_dgCMatrix(A)
-    c = Context(0)
-    try:
-        c.upload(A, None)
+
+    def body(c, fits=None):
         op(c)
         nrow, ncol, _ = c.dims()
         x, i, p = c.download(0)
-    finally:
-        c.close()
-    return dgCMatrix(x, i, p.astype(np.int32), (nrow, ncol), A.Dimnames if Dimnames is None else Dimnames)
+        return dgCMatrix(x, i, p.astype(np.int32), (nrow, ncol), A.Dimnames if Dimnames is None else Dimnames)
+    if isinstance(A, NativeMatrix):
+        return _on_native(A, body)
+    A = as_dgCMatrix(A)
+    with Context(0) as c:
+        c.upload(A, None)
+        return body(c)
 
 
 def PreprocessData(A, scale_factor=10000.0):
@@ -540,15 +429,8 @@ def subset(A, rows=None, cols=None):
     allowed), a boolean mask of the axis length, names looked up in A.Dimnames, or None to keep the axis.  Returns a
     dgCMatrix with the selected Dimnames; the stored values, explicit zeros included, move bit for bit.  A NativeMatrix
     (native()) is staged through the typed door; the result is the same dgCMatrix (double values, sorted indices)."""
-    if isinstance(A, NativeMatrix):
-        r = _subset_index(rows, A.nrow, A.Dimnames[0], "rows")
-        c = _subset_index(cols, A.ncol, A.Dimnames[1], "cols")
-        with _NativeStage(A) as st:
-            st.ctx.subset(r, c)
-            nrow, ncol, _ = st.ctx.dims()
-            x, i, p = st.ctx.download(0)
-        return dgCMatrix(x, i, p.astype(np.int32), (nrow, ncol), (_subset_names(A.Dimnames[0], r), _subset_names(A.Dimnames[1], c)))
-    A = as_dgCMatrix(A)
+    if not isinstance(A, NativeMatrix):
+        A = as_dgCMatrix(A)
     r = _subset_index(rows, A.nrow, A.Dimnames[0], "rows")
     c = _subset_index(cols, A.ncol, A.Dimnames[1], "cols")
     names = (_subset_names(A.Dimnames[0], r), _subset_names(A.Dimnames[1], c))
@@ -563,8 +445,7 @@ def weight_by_split(A_, split_by, n_groups):
     if sb.shape[0] != A.ncol:
         raise ValueError("split_by needs one entry per column of A")
     x = np.empty(A.nnz, dtype=np.float64)
-    check(_lib.load().sgl_c_weight_by_split(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow, A.ncol, ptr(sb, i32p),
-                                            int(n_groups), ptr(x, f64p)))
+    check(_lib.load().sgl_c_weight_by_split(*csc_ptrs(A), A.nrow, A.ncol, ptr(sb, i32p), int(n_groups), ptr(x, f64p)))
     return dgCMatrix(x, A.i, A.p, A.Dim, A.Dimnames)
 
 
@@ -604,8 +485,7 @@ def rowwise_compress_sparse(A, n=10, threads=0):
     A = as_dgCMatrix(A)
     nn = _bin_size(n, "rowwise_compress_sparse")
     out = _raster_out(A.nrow // nn if 1 <= nn <= A.nrow else 0, A.ncol)
-    check(_lib.load().sgl_c_rowwise_compress_sparse(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow, A.ncol, nn,
-                                                    ptr(out, f64p)))
+    check(_lib.load().sgl_c_rowwise_compress_sparse(*csc_ptrs(A), A.nrow, A.ncol, nn, ptr(out, f64p)))
     return out
 
 
@@ -660,12 +540,13 @@ def project_model(A, w, L1=0.01, L2=0, threads=0):
         if w.ndim != 2 or (w.shape[0] != A.nrow and w.shape[1] != A.nrow):
             raise ValueError("'w' must share a common edge with the rows of 'A'")
         wb = np.ascontiguousarray(w if w.shape[0] == A.nrow else w.T)   # (m, k), as c_project_model orients it (src/singlet.cpp:406)
-        with _NativeStage(A) as st:
-            wb, _ = st.ctx.op_scale(wb)
-            st.ctx.fit_init(wb.shape[1], wb)
-            st.ctx.project_run(float(L1), float(L2))
-            _, d, H = st.ctx.get_factors(w=False)
-        return {"h": H.T, "d": d}
+        def body(ctx, fits):
+            ws, _ = ctx.op_scale(wb)
+            ctx.fit_init(ws.shape[1], ws)
+            ctx.project_run(float(L1), float(L2))
+            _, d, H = ctx.get_factors(w=False)
+            return {"h": H.T, "d": d}
+        return _on_native(A, body)
     A = as_dgCMatrix(A)
     w = np.asarray(w)
     if w.shape[0] != A.nrow and w.shape[1] != A.nrow:
@@ -673,7 +554,21 @@ def project_model(A, w, L1=0.01, L2=0, threads=0):
     return c_project_model(A, w, L1, L2, threads)
 
 
-class _ResidentFits:
+class _Fits:
+    """What the drivers fit through: c_ard_nmf / c_nmf without their two matrix arguments, and close(), also as a context
+    manager."""
+
+    def close(self):
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class _ResidentFits(_Fits):
     """One matrix kept in HBM across many fits (include/singlet_hip.h section 2): what R's ard_nmf /
     cross_validate_nmf do by calling c_ard_nmf / c_nmf again and again on the same A (R/ard_nmf.R:95-160,
     R/cross_validate_nmf.R:69-97), without re-uploading, re-transposing and re-validating it per call.
@@ -703,103 +598,51 @@ class _ResidentFits:
         if not self._adopted:
             self.ctx.close()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    def _run(self, w, run, verbose, ard, *args):
+        wb = _w_in(w, self.nrow)
+        self.ctx.fit_init(wb.shape[1], wb)
+        out = run(*args, log=_verbose_log(verbose, ard))
+        out.w, out.d, out.h = self.ctx.get_factors()
+        return out.result()
 
     def c_ard_nmf(self, tol, maxit, verbose, L1, L2, threads, w, seed, inv_density, overfit_threshold, trace_test_mse):
-        wb = _w_in(w, self.nrow)
-        k = wb.shape[1]
-        self.ctx.fit_init(k, wb)
-        r = self.ctx.ard_run(float(tol), int(maxit), L1, L2, int(seed), int(inv_density), float(overfit_threshold),
-                             int(trace_test_mse), log=_verbose_log(verbose, ard=True))
-        W, d, H = self.ctx.get_factors()
-        return {"w": W.T, "d": d, "h": H.T, "test_mse": r["test_mse"], "iter": r["iter"], "tol": r["tol"],
-                "score_overfit": r["score_overfit"]}
+        return self._run(w, self.ctx._ard_run, verbose, True, float(tol), int(maxit), L1, L2, int(seed), int(inv_density),
+                         float(overfit_threshold), int(trace_test_mse))
 
     def c_nmf(self, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w):
-        wb = _w_in(w, self.nrow)
-        k = wb.shape[1]
-        self.ctx.fit_init(k, wb)
-        n_iter, tr = self.ctx.nmf_run(float(tol), int(maxit), L1_w, L1_h, L2_w, L2_h, log=_verbose_log(verbose))
-        W, d, H = self.ctx.get_factors()
-        return {"w": W.T, "d": d, "h": H.T, "iter": n_iter, "tol": tr}
+        return self._run(w, self.ctx._nmf_run, verbose, False, float(tol), int(maxit), L1_w, L1_h, L2_w, L2_h)
 
 
-class _OneShotFits:
-    """The same interface through the one-shot entry points (every call uploads A again)."""
-
-    def __init__(self, A):
-        self.A = as_dgCMatrix(A)
-
-    def close(self):
-        pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        pass
-
-    def c_ard_nmf(self, *args):
-        return c_ard_nmf(self.A, None, *args)
-
-    def c_nmf(self, *args):
-        return c_nmf(self.A, None, *args)
+_ONE_SHOT = {"sparse": ("c_ard_nmf", "c_nmf"), "list": ("c_ard_nmf_sparse_list", "c_nmf_sparse_list"),
+             "dense": ("c_ard_nmf_dense", "c_nmf_dense")}
 
 
-class _OneShotListFits:
-    """R's list branch (R/ard_nmf.R:45-76, 109-110, 176-178; R/cross_validate_nmf.R:27-50, 76-77): A is a list of
-    column chunks (dgCMatrix, same rows); every fit goes through c_ard_nmf_sparse_list / c_nmf_sparse_list.  R builds a
-    "distributed transpose" At on the host first (a list of row-block transposes); here At_ = None: the library joins
-    the chunks into one resident matrix with 64-bit column pointers and builds t(A) on the device."""
+class _OneShotFits(_Fits):
+    """The same interface through the one-shot entry points of one branch of _classify_input (every call uploads A again):
+      "sparse"  a dgCMatrix: c_ard_nmf / c_nmf;
+      "list"    R's list branch (R/ard_nmf.R:45-76, 109-110, 176-178; R/cross_validate_nmf.R:27-50, 76-77): column chunks
+                (dgCMatrix, same rows) through c_ard_nmf_sparse_list / c_nmf_sparse_list.  R builds a "distributed
+                transpose" At on the host first (a list of row-block transposes); here At_ = None: the library joins the
+                chunks into one resident matrix with 64-bit column pointers and builds t(A) on the device;
+      "dense"   R's dense branch (class(A)[[1]] == "matrix": R/ard_nmf.R:79-86, 105-106, 172-173): c_ard_nmf_dense /
+                c_nmf_dense (every column is solved, all-zero ones included: src/singlet.cpp:370-381).
+    The entry points are looked up by name in this module when a fit is made, not when this object is."""
 
-    def __init__(self, chunks):
-        self.chunks = [as_dgCMatrix(a) for a in chunks]
-
-    def close(self):
-        pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        pass
+    def __init__(self, kind, A):
+        self.A = A
+        self.ard, self.nmf = _ONE_SHOT[kind]
 
     def c_ard_nmf(self, *args):
-        return c_ard_nmf_sparse_list(self.chunks, None, *args)
+        return globals()[self.ard](self.A, None, *args)
 
     def c_nmf(self, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w):
-        # c_nmf_sparse_list(A, At, tol, maxit, verbose > 2, L1, L2, threads, w_init_this)   R/ard_nmf.R:178
-        return c_nmf_sparse_list(self.chunks, None, tol, maxit, verbose, L1_w, L2_w, threads, w)
-
-
-class _OneShotDenseFits:
-    """R's dense branch (class(A)[[1]] == "matrix": R/ard_nmf.R:79-86, 105-106, 172-173): c_ard_nmf_dense /
-    c_nmf_dense on the dense matrix (every column is solved, all-zero ones included: src/singlet.cpp:370-381)."""
-
-    def __init__(self, A):
-        self.A = np.asarray(A, dtype=np.float64)
-
-    def close(self):
-        pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        pass
-
-    def c_ard_nmf(self, *args):
-        return c_ard_nmf_dense(self.A, None, *args)
-
-    def c_nmf(self, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w):
+        if self.nmf == "c_nmf_sparse_list":
+            # c_nmf_sparse_list(A, At, tol, maxit, verbose > 2, L1, L2, threads, w_init_this)   R/ard_nmf.R:178
+            return globals()[self.nmf](self.A, None, tol, maxit, verbose, L1_w, L2_w, threads, w)
         # R/ard_nmf.R:173 calls c_nmf_dense(A, At, tol, maxit, verbose > 2, L1, L2, threads, w_init_this): nine arguments
         # for an eleven-argument wrapper (R/RcppExports.R: L1_w, L1_h, L2_w, L2_h) -- an error in R; mirrored as the call
         # the sparse branch makes (L1, L1, L2, L2), the only reading under which the dense branch returns a model
-        return c_nmf_dense(self.A, None, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w)
+        return globals()[self.nmf](self.A, None, tol, maxit, verbose, L1_w, L1_h, L2_w, L2_h, threads, w)
 
 
 def _classify_input(A):
@@ -886,9 +729,9 @@ def ard_nmf(A, k_init=2, k_max=100, k_min=2, n_replicates=1, tol=1e-5, cv_tol=1e
     if k_min < 2:
         raise ValueError("k_min cannot be less than 2")
     if _fits is None and isinstance(A, NativeMatrix):   # native(): staged through the typed door, then the resident way
-        with _NativeStage(A) as st:
-            return ard_nmf(None, k_init, k_max, k_min, n_replicates, tol, cv_tol, maxit, verbose, L1, L2, threads, test_density,
-                           learning_rate, tol_overfit, trace_test_mse, seed, resident, _fits=st.fits)
+        return _on_native(A, lambda ctx, fits: ard_nmf(None, k_init, k_max, k_min, n_replicates, tol, cv_tol, maxit, verbose, L1, L2,
+                                                       threads, test_density, learning_rate, tol_overfit, trace_test_mse, seed,
+                                                       resident, _fits=fits))
     kind, A = ("staged", None) if _fits is not None else _classify_input(A)
     if kind == "staged":   # RunNMF: the matrix is staged and resident already
         nrow, (rn, cn), fits = _fits.nrow, _fits.Dimnames, _fits
@@ -897,13 +740,13 @@ def ard_nmf(A, k_init=2, k_max=100, k_min=2, n_replicates=1, tol=1e-5, cv_tol=1e
         rn = A[0].Dimnames[0]
         cns = [c.Dimnames[1] for c in A]
         cn = None if any(c is None for c in cns) else [name for c in cns for name in c]   # rownames(At[[1]]): all cells
-        fits = _OneShotListFits(A)
+        fits = _OneShotFits(kind, A)
     elif kind == "dense":
         nrow, rn, cn = A.shape[0], None, None
-        fits = _OneShotDenseFits(A)
+        fits = _OneShotFits(kind, A)
     else:
         nrow, (rn, cn) = A.nrow, A.Dimnames
-        fits = _ResidentFits(A) if resident else _OneShotFits(A)
+        fits = _ResidentFits(A) if resident else _OneShotFits(kind, A)
     if verbose > 0:
         print("running with dense optimization" if kind == "dense" else "running with sparse optimization")
     rng = _rng(seed)
@@ -1033,9 +876,9 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
     if L1 >= 1:
         raise ValueError("L1 penalty must be strictly in the range (0, 1]")
     if _fits is None and isinstance(A, NativeMatrix):   # native(): one staged context (no replica sweep over `devices`)
-        with _NativeStage(A) as st:
-            return cross_validate_nmf(None, ranks, n_replicates, tol, maxit, verbose, L1, L2, threads, test_density, tol_overfit,
-                                      trace_test_mse, seed, resident, devices, _fits=st.fits)
+        return _on_native(A, lambda ctx, fits: cross_validate_nmf(None, ranks, n_replicates, tol, maxit, verbose, L1, L2, threads,
+                                                                  test_density, tol_overfit, trace_test_mse, seed, resident, devices,
+                                                                  _fits=fits))
     if _fits is not None:   # RunNMF: the matrix is staged and resident already (A is not read)
         kind, nrow = "sparse", _fits.nrow
     else:
@@ -1061,7 +904,7 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
 
     devs = _replica_devices(devices)
     if kind != "sparse":
-        fits = _OneShotListFits(A) if kind == "list" else _OneShotDenseFits(A)
+        fits = _OneShotFits(kind, A)
         for k, rep in grid:
             rows(k, rep, fit(fits, (k, rep)))
         return df2
@@ -1069,7 +912,7 @@ def cross_validate_nmf(A, ranks, n_replicates=3, tol=1e-4, maxit=100, verbose=1,
         for (k, rep), model in zip(grid, _run_grid_on_replicas(A, devs, grid, fit)):
             rows(k, rep, model)
         return df2
-    fits = _fits if _fits is not None else (_ResidentFits(A, devs[0]) if resident else _OneShotFits(A))
+    fits = _fits if _fits is not None else (_ResidentFits(A, devs[0]) if resident else _OneShotFits(kind, A))
     try:
         for q, (k, rep) in enumerate(grid):
             if verbose > 1:
@@ -1202,12 +1045,11 @@ def find_variable_features(A, nfeatures=2000, span=0.3, vmax=None, expected_var=
     if not is_native:
         A = as_dgCMatrix(A)
     if is_native:
-        with _NativeStage(A) as st:
-            out = st.ctx.variable_features(nfeatures, span, vmax, expected_var)
+        out = _on_native(A, lambda ctx, fits: ctx.variable_features(nfeatures, span, vmax, expected_var))
     else:
         L = _lib.load()
-        out = _variable_features_call(lambda *a: L.sgl_c_variable_features(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow,
-                                                                           A.ncol, *a), A.nrow, nfeatures, span, vmax, expected_var)
+        out = _variable_features_call(lambda *a: L.sgl_c_variable_features(*csc_ptrs(A), A.nrow, A.ncol, *a), A.nrow, nfeatures, span,
+                                      vmax, expected_var)
     rn = A.Dimnames[0]
     if rn is not None:
         out["names"] = _subset_names(rn, out["features"])
@@ -1242,13 +1084,14 @@ def evaluate(A, model, cell_loss=False, gene_loss=False):
     dk = np.ascontiguousarray(d)
     from .context import _evaluate_call
     if is_native:
-        with _NativeStage(A) as st:
-            st.ctx.fit_init(k)
-            st.ctx.set_factors(wk, dk, hk)
-            return st.ctx.evaluate(cell_loss, gene_loss)
+        def body(ctx, fits):
+            ctx.fit_init(k)
+            ctx.set_factors(wk, dk, hk)
+            return ctx.evaluate(cell_loss, gene_loss)
+        return _on_native(A, body)
     L = _lib.load()
-    return _evaluate_call(lambda *o: L.sgl_c_evaluate(ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow, A.ncol, ptr(wk, f64p),
-                                                      ptr(dk, f64p), ptr(hk, f64p), int(k), *o), A.nrow, A.ncol, cell_loss, gene_loss)
+    return _evaluate_call(lambda *o: L.sgl_c_evaluate(*csc_ptrs(A), A.nrow, A.ncol, ptr(wk, f64p), ptr(dk, f64p), ptr(hk, f64p),
+                                                      int(k), *o), A.nrow, A.ncol, cell_loss, gene_loss)
 
 
 # ---------------------------------------------------------------------------
@@ -1259,19 +1102,11 @@ def group_means(F, group, n_groups):
     as k x n_groups, counts[g] the cells of group g (sgl_c_group_means, on the device).  group holds one 0-based id per
     column; an empty group gives a NaN column (R's mean(numeric(0))) and a count of 0.  The summation order depends on
     (n, group, n_groups) alone."""
-    from .context import _group_list
-    Fa = np.asarray(F, dtype=np.float64)
-    if Fa.ndim != 2:
-        raise ValueError("F must be a k x n matrix")
-    k, n = Fa.shape
-    buf = np.ascontiguousarray(Fa.T)   # column-major image
+    from .context import _group_list, _group_means_call
+    buf = colmajor(F, "F must be a k x n matrix")
+    n, k = buf.shape
     g = _group_list(group, n, "group")
-    G = int(n_groups)
-    means = np.empty((max(G, 0), k))
-    counts = np.zeros(max(G, 0), dtype=np.int64)
-    check(_lib.load().sgl_c_group_means(ptr(buf, f64p), int(k), int(n), ptr(g, i32p), G, ptr(means, f64p),
-                                        ptr(counts, C.POINTER(C.c_int64))))
-    return means.T, counts
+    return _group_means_call(lambda *o: _lib.load().sgl_c_group_means(ptr(buf, f64p), int(k), int(n), *o), g, n_groups, k)
 
 
 def _shares(means):

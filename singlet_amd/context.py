@@ -6,6 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
+from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs
 from .sparse import as_dgCMatrix
 
 SYNTH_SEED = 0x5EED
@@ -110,15 +111,29 @@ def _chunk_list(chunks):
     return (n, xs, is_, ps, ptr(nc, i32p)), (chunks, xs, is_, ps, nc)
 
 
+def _chunk_lists(chunks, t_chunks, empty_message, rows_message):
+    """The images of the column chunks of A and of t(A) (None / empty: the transpose is built on the device) for the list
+    entry points: (a, t, nrow, total columns, what must stay alive).  The caller words the two refusals."""
+    chunks = list(chunks)
+    if not chunks:
+        raise ValueError(empty_message)
+    a, keep_a = _chunk_list(chunks)
+    nrow = keep_a[0][0].nrow
+    if any(c.nrow != nrow for c in keep_a[0]):
+        raise ValueError(rows_message)
+    if t_chunks is None or len(t_chunks) == 0:
+        t, keep_t = (0, None, None, None, None), None
+    else:
+        t, keep_t = _chunk_list(t_chunks)
+    return a, t, nrow, sum(c.ncol for c in keep_a[0]), (keep_a, keep_t)
+
+
 def _link_image(Lk):
     """ctypes image of an R link matrix (rows x cols): (pointer, rows, cols, the buffer to keep alive); None switches the side off."""
     if Lk is None:
         return None, 0, 0, None
-    Lk = np.asarray(Lk, dtype=np.float64)
-    if Lk.ndim != 2:
-        raise ValueError("link matrices must be 2-D")
-    buf = np.ascontiguousarray(Lk.T)   # column-major image of the R matrix
-    return ptr(buf, f64p), Lk.shape[0], Lk.shape[1], buf
+    buf = colmajor(Lk, "link matrices must be 2-D")
+    return ptr(buf, f64p), buf.shape[1], buf.shape[0], buf
 
 
 def _group_list(group, n, what):
@@ -137,14 +152,21 @@ def _grouped_side(table, group, n, side):
     """(pointer, rows, groups, group pointer, what to keep alive) of one side of set_links_grouped; a None table is off."""
     if table is None:
         return None, 0, 0, None, None
-    T = np.asarray(table, dtype=np.float64)
-    if T.ndim != 2:
-        raise ValueError("table_%s must be a rows x groups matrix" % side)
+    buf = colmajor(table, "table_%s must be a rows x groups matrix" % side)
     if group is None:
         raise ValueError("table_%s needs group_%s" % (side, side))
     g = _group_list(group, n, "group_" + side)
-    buf = np.ascontiguousarray(T.T)   # column-major image
-    return ptr(buf, f64p), T.shape[0], T.shape[1], ptr(g, i32p), (buf, g)
+    return ptr(buf, f64p), buf.shape[1], buf.shape[0], ptr(g, i32p), (buf, g)
+
+
+def _group_means_call(fn, g, n_groups, k):
+    """Shared by Context.group_means, Multi.group_means and api.group_means: fn(group, n_groups, means, counts) is the
+    library call; g the int32 group list (_group_list)."""
+    G = int(n_groups)
+    means = np.empty((max(G, 0), k))
+    counts = np.zeros(max(G, 0), dtype=np.int64)
+    check(fn(ptr(g, i32p), G, ptr(means, f64p), ptr(counts, i64p)))
+    return means.T, counts
 
 
 def _evaluate_call(fn, nrow, ncol, cell_loss, gene_loss):
@@ -180,7 +202,90 @@ def _variable_features_call(fn, nrow, nfeatures, span, vmax, expected_var):
             "variance_expected": info[:, 2].copy(), "variance_standardized": info[:, 3].copy()}
 
 
-class Context:
+class _Handle:
+    """One handle of the library -- a context (sgl_*) or a team (sgl_multi_*) -- its lifetime, and the calls both take
+    alike: _fn picks the symbol by the class's prefix, _shape gives (nrow, ncol) of the whole resident matrix."""
+    _PREFIX = "sgl_"
+    _owned = True
+
+    def _fn(self, name):
+        return getattr(self._L, self._PREFIX + name)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if self._owned:
+                self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def set_links(self, link_h=None, link_w=None):
+        """c_linked_nmf's link matrices (sgl_set_links; rows x cols, as R holds them: link_h rows x cells -- of this shard
+        on a Context, of the whole matrix on a Multi --, link_w rows x genes); a matrix whose column count does not match
+        its side is ignored, None switches a side off.  Call after fit_init (which drops them)."""
+        lh, lhr, lhc, k1 = _link_image(link_h)
+        lw, lwr, lwc, k2 = _link_image(link_w)
+        check(self._fn("set_links")(self._h, lh, lhr, lhc, lw, lwr, lwc))
+
+    def set_links_grouped(self, table_h, group_h, table_w=None, group_w=None):
+        """The grouped form of the links (sgl_set_links_grouped): exactly set_links(table_h[:, group_h], table_w[:, group_w])
+        without the expanded matrices -- table_* rows x groups, group_* one 0-based id per cell (gene).  Same bits, same
+        lifetime; a None table switches its side off; either call replaces what the other set.  On a Multi group_h holds
+        one id per cell of ALL cells and follows them to the ranks; the tables and group_w go to every rank."""
+        nr, nc = self._shape()
+        th, rh, gh, ph, k1 = _grouped_side(table_h, group_h, nc, "h")
+        tw, rw, gw, pw, k2 = _grouped_side(table_w, group_w, nr, "w")
+        check(self._fn("set_links_grouped")(self._h, th, rh, gh, ph, tw, rw, gw, pw))
+
+    def set_graph(self, G):
+        """c_gcnmf's cell graph (sgl_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over the resident cells (on
+        a Multi: over ALL cells), or None to clear it.  Call after fit_init (which drops it).  On a Multi every rank keeps
+        the columns of its cells; the columns of B and h that other ranks read travel in a halo exchange per
+        half-iteration (graph_info())."""
+        G = None if G is None else as_dgCMatrix(G)
+        check(self._fn("set_graph")(self._h, *csc_ptrs(G), *((0, 0) if G is None else (G.nrow, G.ncol))))
+
+    def evaluate(self, cell_loss=False, gene_loss=False):
+        """Error of the current factors against the resident matrix (sgl_evaluate): {"sse", "mse"} plus, when asked for,
+        "cell_loss" (one per cell) and "gene_loss" (one per gene) -- sums of squared residuals of w^T diag(d) h over every
+        entry of the column / row, zeros included.  Links and a cell graph on the fit are ignored; the fit is not changed.
+        On a Multi cell_loss covers all cells in global order; the ranks' sums and gene partials are added on the host in
+        rank order."""
+        nr, nc = self._shape() or (0, 0)
+        return _evaluate_call(lambda *o: self._fn("evaluate")(self._h, *o), nr, nc, cell_loss, gene_loss)
+
+    def _nmf_run(self, tol, maxit, L1_w, L1_h, L2_w, L2_h, log=None, poll=None):
+        out = NmfOutputs(None, maxit)
+        cb = make_callbacks(log, poll)
+        check(self._fn("nmf_run")(self._h, tol, int(maxit), L1_w, L1_h, L2_w, L2_h, *out.args(), C.byref(cb)))
+        return out
+
+    def nmf_run(self, tol, maxit, L1_w, L1_h, L2_w, L2_h, log=None, poll=None):
+        return self._nmf_run(tol, maxit, L1_w, L1_h, L2_w, L2_h, log, poll).run()
+
+    def _ard_run(self, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, log=None, poll=None):
+        out = ArdOutputs(None, maxit, nit=True)
+        cb = make_callbacks(log, poll)
+        check(self._fn("ard_run")(self._h, tol, int(maxit), L1, L2, int(seed), int(inv_density), overfit_threshold,
+                                  int(trace_test_mse), *out.args(), C.byref(cb)))
+        return out
+
+    def ard_run(self, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, log=None, poll=None):
+        out = self._ard_run(tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, log, poll)
+        return dict(out.traces(), n_iter=out.nit.value)
+
+
+class Context(_Handle):
     def __init__(self, device=0, _borrowed=None):
         self._L = _lib.load()
         if _borrowed is not None:   # a rank of a Multi: owned by it
@@ -196,12 +301,8 @@ class Context:
         self._keep = []
         self.k = 0
 
-    # -- lifetime ---------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            if self._owned:
-                self._L.sgl_destroy(self._h)
-            self._h = None
+    def _shape(self):
+        return self.dims()[:2]
 
     def comm_init_rank(self, nranks, rank, comm_id):
         """Join the native team of `nranks` processes (one per GPU) with the id rank 0 made
@@ -224,44 +325,18 @@ class Context:
         check(self._L.sgl_nmf_iterate(self._h, L1_w, L1_h, L2_w, L2_h, C.byref(t)))
         return t.value
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
     # -- matrix -----------------------------------------------------------
     def upload(self, A, At=None, cell_offset=0, ncells_total=0):
-        a = (ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p))
-        if At is not None:
-            if At.Dim != (A.Dim[1], A.Dim[0]):
-                raise ValueError("At must be the transpose of A")
-            t = (ptr(At.x, f64p), ptr(At.i, i32p), ptr(At.p, i32p))
-        else:
-            t = (None, None, None)
-        check(self._L.sgl_upload_csc(self._h, *a, *t, A.nrow, A.ncol, int(cell_offset), int(ncells_total)))
+        if At is not None and At.Dim != (A.Dim[1], A.Dim[0]):
+            raise ValueError("At must be the transpose of A")
+        check(self._L.sgl_upload_csc(self._h, *csc_ptrs(A), *csc_ptrs(At), A.nrow, A.ncol, int(cell_offset), int(ncells_total)))
         self.k = 0
 
     def upload_list(self, chunks, t_chunks=None, cell_offset=0, ncells_total=0):
         """sgl_upload_csc_list: a list of column chunks of A joined into one resident shard (64-bit column pointers);
         t_chunks: the column chunks of t(A), or None / empty to build the transpose on the device."""
-        chunks = list(chunks)
-        if not chunks:
-            raise ValueError("the chunk list must hold at least one matrix")
-        a, keep_a = _chunk_list(chunks)
-        nrow = keep_a[0][0].nrow
-        if any(q.nrow != nrow for q in keep_a[0]):
-            raise ValueError("all chunks must have the same number of rows")
-        if t_chunks is not None and len(t_chunks) > 0:
-            t, keep_t = _chunk_list(t_chunks)
-        else:
-            t, keep_t = (0, None, None, None, None), None
+        a, t, nrow, _, keep = _chunk_lists(chunks, t_chunks, "the chunk list must hold at least one matrix",
+                                           "all chunks must have the same number of rows")
         check(self._L.sgl_upload_csc_list(self._h, *a, *t, nrow, int(cell_offset), int(ncells_total)))
         self.k = 0
 
@@ -387,23 +462,6 @@ class Context:
         check(self._L.sgl_fit_init(self._h, int(k), ptr(w, f64p), synth_seed))
         self.k = int(k)
 
-    def set_links(self, link_h=None, link_w=None):
-        """c_linked_nmf's link matrices (sgl_set_links; rows x cols, as R holds them: link_h rows x cells of this shard,
-        link_w rows x genes); a matrix whose column count does not match its side is ignored, None switches a side off.
-        Call after fit_init (which drops them)."""
-        lh, lhr, lhc, k1 = _link_image(link_h)
-        lw, lwr, lwc, k2 = _link_image(link_w)
-        check(self._L.sgl_set_links(self._h, lh, lhr, lhc, lw, lwr, lwc))
-
-    def set_links_grouped(self, table_h, group_h, table_w=None, group_w=None):
-        """The grouped form of the links (sgl_set_links_grouped): exactly set_links(table_h[:, group_h], table_w[:, group_w])
-        without the expanded matrices -- table_* rows x groups, group_* one 0-based id per cell (gene).  Same bits, same
-        lifetime; a None table switches its side off; either call replaces what the other set."""
-        nr, nc, _ = self.dims()
-        th, rh, gh, ph, k1 = _grouped_side(table_h, group_h, nc, "h")
-        tw, rw, gw, pw, k2 = _grouped_side(table_w, group_w, nr, "w")
-        check(self._L.sgl_set_links_grouped(self._h, th, rh, gh, ph, tw, rw, gw, pw))
-
     def group_means(self, group, n_groups, F=None):
         """(means k x n_groups, counts) of the columns of F (k x n, R's orientation) per group (sgl_group_means); F = None:
         of the H of the current fit, read where it is.  An empty group gives a NaN column and a count of 0."""
@@ -413,25 +471,11 @@ class Context:
             if k == 0:   # no fit: the library refuses (SGL_ESTATE) before it reads the list
                 n = None
         else:
-            Fa = np.asarray(F, dtype=np.float64)
-            if Fa.ndim != 2:
-                raise ValueError("F must be a k x n matrix")
-            k, n = Fa.shape
-            buf = np.ascontiguousarray(Fa.T)   # column-major image
+            buf = colmajor(F, "F must be a k x n matrix")
+            n, k = buf.shape
             Fp = ptr(buf, f64p)
         g = _group_list(group, n, "group")
-        G = int(n_groups)
-        means = np.empty((max(G, 0), k))
-        counts = np.zeros(max(G, 0), dtype=np.int64)
-        check(self._L.sgl_group_means(self._h, Fp, int(k), int(g.shape[0]), ptr(g, i32p), G, ptr(means, f64p), ptr(counts, i64p)))
-        return means.T, counts
-
-    def evaluate(self, cell_loss=False, gene_loss=False):
-        """Error of the current factors against the resident matrix (sgl_evaluate): {"sse", "mse"} plus, when asked for,
-        "cell_loss" (one per cell) and "gene_loss" (one per gene) -- sums of squared residuals of w^T diag(d) h over every
-        entry of the column / row, zeros included.  Links and a cell graph on the fit are ignored; the fit is not changed."""
-        nr, nc, _ = self.dims()
-        return _evaluate_call(lambda *o: self._L.sgl_evaluate(self._h, *o), nr, nc, cell_loss, gene_loss)
+        return _group_means_call(lambda *o: self._L.sgl_group_means(self._h, Fp, int(k), int(g.shape[0]), *o), g, n_groups, k)
 
     def variable_features(self, nfeatures=2000, span=0.3, vmax=None, expected_var=None):
         """Variable features of the resident counts (sgl_variable_features; Seurat's vst selection under this library's
@@ -440,16 +484,6 @@ class Context:
         gene, used instead of the trend (another loess's, for parity with it).  The matrix and a running fit are only read."""
         nr, _, _ = self.dims()
         return _variable_features_call(lambda *a: self._L.sgl_variable_features(self._h, *a), nr, nfeatures, span, vmax, expected_var)
-
-    def set_graph(self, G):
-        """c_gcnmf's cell graph (sgl_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over the resident cells, or None
-        to clear it.  Call after fit_init (which drops it)."""
-        if G is None:
-            check(self._L.sgl_set_graph(self._h, None, None, None, 0, 0))
-            return
-        from .sparse import as_dgCMatrix
-        G = as_dgCMatrix(G)
-        check(self._L.sgl_set_graph(self._h, ptr(G.x, f64p), ptr(G.i, i32p), ptr(G.p, i32p), G.nrow, G.ncol))
 
     def set_stream(self, stream_ptr):
         check(self._L.sgl_set_stream(self._h, C.c_void_p(stream_ptr) if stream_ptr else None))
@@ -496,27 +530,6 @@ class Context:
         check(self._L.sgl_step_scale_w(self._h, C.byref(t)))
         return t.value
 
-    def nmf_run(self, tol, maxit, L1_w, L1_h, L2_w, L2_h, log=None, poll=None):
-        n_iter = C.c_int32()
-        tr = np.zeros(max(int(maxit), 1))
-        cb = make_callbacks(log, poll)
-        check(self._L.sgl_nmf_run(self._h, tol, int(maxit), L1_w, L1_h, L2_w, L2_h, C.byref(n_iter), ptr(tr, f64p),
-                                  C.byref(cb)))
-        return n_iter.value, tr[:n_iter.value].copy()
-
-    def ard_run(self, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, log=None, poll=None):
-        cap = int(maxit) + 2
-        tm, ft, so = np.zeros(cap), np.zeros(cap), np.zeros(cap)
-        itv = np.zeros(cap, dtype=np.int32)
-        nt, nit = C.c_int32(), C.c_int32()
-        cb = make_callbacks(log, poll)
-        check(self._L.sgl_ard_run(self._h, tol, int(maxit), L1, L2, int(seed), int(inv_density), overfit_threshold,
-                                  int(trace_test_mse), ptr(tm, f64p), ptr(itv, i32p), ptr(ft, f64p), ptr(so, f64p),
-                                  C.byref(nt), C.byref(nit), C.byref(cb)))
-        q = nt.value
-        return dict(test_mse=tm[:q].copy(), iter=itv[:q].copy(), tol=ft[:q].copy(), score_overfit=so[:q].copy(),
-                    n_iter=nit.value)
-
     def project_run(self, L1, L2):
         check(self._L.sgl_project_run(self._h, L1, L2))
 
@@ -555,15 +568,17 @@ class Context:
         check(self._L.sgl_op_gram(self._h, ptr(F, f64p), k, cols, ptr(G, f64p)))
         return G
 
-    def op_rhs(self, which, F):
+    def _rhs_buffers(self, which, F):
+        """(F, k, B) of op_rhs / op_rhs_masked: which & 1 selects t(A); which & 2 the LDS-tiled kernel."""
         F = _f(F)
         nr, nc, _ = self.dims()
-        k = F.shape[1]
-        ncol = nr if (which & 1) else nc   # which & 2 selects the LDS-tiled kernel
-        nrow = nc if (which & 1) else nr
+        ncol, nrow = (nr, nc) if (which & 1) else (nc, nr)
         if F.shape[0] != nrow:
             raise ValueError("F must have %d rows" % nrow)
-        B = np.empty((ncol, k))
+        return F, F.shape[1], np.empty((ncol, F.shape[1]))
+
+    def op_rhs(self, which, F):
+        F, k, B = self._rhs_buffers(which, F)
         check(self._L.sgl_op_rhs(self._h, int(which), ptr(F, f64p), k, ptr(B, f64p)))
         return B
 
@@ -662,14 +677,7 @@ class Context:
     def op_rhs_masked(self, which, F, seed, inv_density):
         """op_rhs with the entries the mask (seed, inv_density) draws left out (sgl_op_rhs_masked): which = 0 / 1 hash every
         entry in the plain kernel, 2 / 3 run the LDS-tiled kernel on a masked value array."""
-        F = _f(F)
-        nr, nc, _ = self.dims()
-        k = F.shape[1]
-        ncol = nr if (which & 1) else nc
-        nrow = nc if (which & 1) else nr
-        if F.shape[0] != nrow:
-            raise ValueError("F must have %d rows" % nrow)
-        B = np.empty((ncol, k))
+        F, k, B = self._rhs_buffers(which, F)
         check(self._L.sgl_op_rhs_masked(self._h, int(which), ptr(F, f64p), k, int(seed), int(inv_density), ptr(B, f64p)))
         return B
 
@@ -733,10 +741,11 @@ class Context:
         return tuple(int(v) for v in out)
 
 
-class Multi:
+class Multi(_Handle):
     """sgl_multi: ONE process driving several devices, cells sharded, exchange over RCCL inside the
     library (include/singlet_hip.h section 2b).  devices: list of device ids -- all distinct (RCCL) or
     all equal (ranks share one device and exchange through a HIP kernel: the test configuration)."""
+    _PREFIX = "sgl_multi_"
 
     def __init__(self, devices):
         self._L = _lib.load()
@@ -748,22 +757,8 @@ class Multi:
         self.k = 0
         self._dims = None
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.sgl_multi_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
+    def _shape(self):
+        return self._dims
 
     def rank_ctx(self, r):
         h = C.c_void_p()
@@ -773,7 +768,7 @@ class Multi:
         return c
 
     def upload(self, A):
-        check(self._L.sgl_multi_upload_csc(self._h, ptr(A.x, f64p), ptr(A.i, i32p), ptr(A.p, i32p), A.nrow, A.ncol))
+        check(self._L.sgl_multi_upload_csc(self._h, *csc_ptrs(A), A.nrow, A.ncol))
         self._dims = (A.nrow, A.ncol)
         self.k = 0
 
@@ -792,45 +787,11 @@ class Multi:
         check(self._L.sgl_multi_fit_init(self._h, int(k), ptr(w, f64p), synth_seed))
         self.k = int(k)
 
-    def set_links(self, link_h=None, link_w=None):
-        """c_linked_nmf's link matrices (rows x cols, as R holds them) for the whole matrix; call after fit_init."""
-        lh, lhr, lhc, k1 = _link_image(link_h)
-        lw, lwr, lwc, k2 = _link_image(link_w)
-        check(self._L.sgl_multi_set_links(self._h, lh, lhr, lhc, lw, lwr, lwc))
-
-    def set_links_grouped(self, table_h, group_h, table_w=None, group_w=None):
-        """Context.set_links_grouped for the whole matrix (sgl_multi_set_links_grouped): group_h holds one id per cell of ALL
-        cells and follows them to the ranks; the tables and group_w go to every rank."""
-        nr, nc = self._dims
-        th, rh, gh, ph, k1 = _grouped_side(table_h, group_h, nc, "h")
-        tw, rw, gw, pw, k2 = _grouped_side(table_w, group_w, nr, "w")
-        check(self._L.sgl_multi_set_links_grouped(self._h, th, rh, gh, ph, tw, rw, gw, pw))
-
     def group_means(self, group, n_groups):
         """(means k x n_groups, counts) of the H of the team's fit per group of cells (sgl_multi_group_means): every rank sums
         its cells, the rank partials are added in rank order and divided by the counts over all ranks."""
         g = _group_list(group, self._dims[1], "group")
-        G = int(n_groups)
-        means = np.empty((max(G, 0), self.k))
-        counts = np.zeros(max(G, 0), dtype=np.int64)
-        check(self._L.sgl_multi_group_means(self._h, ptr(g, i32p), G, ptr(means, f64p), ptr(counts, i64p)))
-        return means.T, counts
-
-    def evaluate(self, cell_loss=False, gene_loss=False):
-        """Context.evaluate for the team's fit (sgl_multi_evaluate): cell_loss covers all cells in global order; the ranks'
-        sums and gene partials are added on the host in rank order."""
-        nr, nc = self._dims if self._dims else (0, 0)
-        return _evaluate_call(lambda *o: self._L.sgl_multi_evaluate(self._h, *o), nr, nc, cell_loss, gene_loss)
-
-    def set_graph(self, G):
-        """c_gcnmf's cell graph for the team (sgl_multi_set_graph): an n x n dgCMatrix-like or scipy sparse matrix over ALL
-        cells, or None to clear it.  Call after fit_init (which drops it).  Every rank keeps the columns of its cells; the
-        columns of B and h that other ranks read travel in a halo exchange per half-iteration (graph_info())."""
-        if G is None:
-            check(self._L.sgl_multi_set_graph(self._h, None, None, None, 0, 0))
-            return
-        G = as_dgCMatrix(G)
-        check(self._L.sgl_multi_set_graph(self._h, ptr(G.x, f64p), ptr(G.i, i32p), ptr(G.p, i32p), G.nrow, G.ncol))
+        return _group_means_call(lambda *o: self._L.sgl_multi_group_means(self._h, *o), g, n_groups, self.k)
 
     def graph_info(self):
         """dict(edges, crossing, E, exported, halo_bytes) of the graph set by set_graph (all 0 without one): entries of G,
@@ -844,27 +805,6 @@ class Multi:
         t = C.c_double()
         check(self._L.sgl_multi_iterate(self._h, L1_w, L1_h, L2_w, L2_h, C.byref(t)))
         return t.value
-
-    def nmf_run(self, tol, maxit, L1_w, L1_h, L2_w, L2_h, log=None, poll=None):
-        n_iter = C.c_int32()
-        tr = np.zeros(max(int(maxit), 1))
-        cb = make_callbacks(log, poll)
-        check(self._L.sgl_multi_nmf_run(self._h, tol, int(maxit), L1_w, L1_h, L2_w, L2_h, C.byref(n_iter), ptr(tr, f64p),
-                                        C.byref(cb)))
-        return n_iter.value, tr[:n_iter.value].copy()
-
-    def ard_run(self, tol, maxit, L1, L2, seed, inv_density, overfit_threshold, trace_test_mse, log=None, poll=None):
-        cap = int(maxit) + 2
-        tm, ft, so = np.zeros(cap), np.zeros(cap), np.zeros(cap)
-        itv = np.zeros(cap, dtype=np.int32)
-        nt, nit = C.c_int32(), C.c_int32()
-        cb = make_callbacks(log, poll)
-        check(self._L.sgl_multi_ard_run(self._h, tol, int(maxit), L1, L2, int(seed), int(inv_density), overfit_threshold,
-                                        int(trace_test_mse), ptr(tm, f64p), ptr(itv, i32p), ptr(ft, f64p), ptr(so, f64p),
-                                        C.byref(nt), C.byref(nit), C.byref(cb)))
-        q = nt.value
-        return dict(test_mse=tm[:q].copy(), iter=itv[:q].copy(), tol=ft[:q].copy(), score_overfit=so[:q].copy(),
-                    n_iter=nit.value)
 
     def get_factors(self):
         nr, nc = self._dims
