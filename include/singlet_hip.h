@@ -637,6 +637,57 @@ SGL_API int sgl_c_variable_features(const double* Ax, const int32_t* Ai, const i
                                     int32_t nfeatures, double span, double vmax, const double* expected_var,
                                     int32_t* features, int32_t* n_out, double* info);
 
+/* Embedding neighbours: the EXACT n_neighbors nearest reference columns of every query column of a k x n embedding, by
+ * brute force in FP64 -- the k-NN step of Seurat's FindNeighbors on the `nmf` reduction (its Jaccard step is sgl_c_snn), and
+ * of label transfer after a projection.  The reference's package has no such function (it hands the embedding to Seurat);
+ * the rules below are this library's own, stated in full; tests/embedding_knn_restatement.py restates them in numpy.
+ *
+ * R is k x n_ref and Q is k x n_query, column-major on the host (one column per cell).  R == NULL: the H of the current
+ * fit, read where it lies on the device (k and n_ref must then be the fit's rank and cell count: SGL_EINVAL otherwise), in
+ * the fit's stored factor order.  Q == NULL: the queries are the references themselves (n_query is not used beyond its sign).
+ *  - distance: for query column q and reference column r, over the selected dimensions f in the listed order,
+ *        s = +0.0;  for f:  t = q_f - r_f;  s = s + t * t
+ *    in double, sequentially, without contraction (the product and the addition are two roundings).  s is a function of
+ *    the two columns alone: it does not depend on tiling, on the launch or on which form of the call computed it.
+ *  - ranking: by (s, reference index) ascending; ties go to the lower index.  The ranking is on the squared sum, not on its
+ *    root (sqrt can merge two different sums).  With finite inputs no s is NaN; a sum that overflows to +Inf ties with every
+ *    other +Inf and ranks by index.  This is a total order, so the result is the same however the references are cut into
+ *    segments and merged.
+ *  - output: idx_out int32, dist_out double, both n_neighbors x n_query column-major: column j holds the n_neighbors best
+ *    references of query j in rank order, and __builtin_sqrt(s) of each (the IEEE root, as sgl_spatial_graph).  Either may
+ *    be NULL.
+ *  - self: with Q == NULL nothing is special-cased.  A cell is its own candidate at s = +0.0; it is in its result (first,
+ *    unless identical columns of lower index tie with it) EXCEPT when n_neighbors or more identical columns precede it in
+ *    index order: those fill the list at s = +0.0 before it.
+ *  - dims: int32[n_dims], 0-based rows of R and Q, each in [0, k), no duplicates; NULL: all k rows in stored order (n_dims is
+ *    not read).  One gather kernel writes the packed operands.
+ *  - refused with SGL_EINVAL and a message, before anything is launched for the search: n_neighbors < 1, > 256 or > n_ref;
+ *    k outside [1, 1024]; n_ref < 1 or >= 2^31; n_query < 0; n_dims outside [1, k], a dims entry out of range or repeated
+ *    (named by position and value); a non-finite value in R, Q or the resident H: a device pass finds it, and the message
+ *    names the array, the column and the row of the first one in column-major order.
+ *  - refused with SGL_ESTATE: on a team member or with an all-reduce hook set (the shard's H is not the embedding; refused
+ *    whatever R is); R == NULL without a fit.  The context stays usable after every refusal.
+ *  - the call only reads the context; its temporaries are its own (the operands it uploads or gathers, and
+ *    segments x n_neighbors x n_query candidates of 12 bytes).  A plain, a masked or a grouped-link fit continued after a
+ *    call in mid-fit gives the bits it would have given without it.  The kernels' time counts in the "scale" phase when
+ *    timing is on.
+ *  - kernels (singlet_amd/csrc/kernels_knn.hip): a lane owns its queries; the references stream in ascending index and
+ *    their coordinates reach the FP64 vector instructions as scalar operands.  n_dims <= 64 keeps the queries' coordinates
+ *    in registers (instances 0 .. 3: n_dims up to 8, 16, 32 with two queries per lane, up to 64 with one); instance 4 serves
+ *    every rank above.  The candidate lists live in LDS up to n_neighbors = 32, above in global scratch.  With fewer than
+ *    1024 workgroups of queries the references are cut into up to 64 segments of at least max(1024, 4 n_neighbors)
+ *    references, and a merge pass ranks the segments' candidates by (s, index).  64-bit offsets; no floating-point atomics. */
+SGL_API int sgl_knn(sgl_ctx* ctx, const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query,
+                    const int32_t* dims, int32_t n_dims, int32_t n_neighbors, int32_t* idx_out, double* dist_out);
+/* The one-shot form: its own context on the current device; R must not be NULL (SGL_EINVAL).  The argument refusals come
+ * before a context is made. */
+SGL_API int sgl_c_knn(const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query,
+                      const int32_t* dims, int32_t n_dims, int32_t n_neighbors, int32_t* idx_out, double* dist_out);
+/* What the last sgl_knn on this context ran (read-only, in the spirit of sgl_layout_get; all 0 before the first search):
+ * out[0] the kernel instance (0 .. 4 above), [1] the reference segments, [2] the queries per workgroup, [3] 0 when the
+ * candidate lists lay in LDS, 1 in global scratch.  A refused call leaves it as it was. */
+SGL_API int sgl_knn_info(sgl_ctx* ctx, int64_t out[4]);
+
 /* Cell graph of c_gcnmf for the current fit (after sgl_fit_init, which drops
  * it again; all-NULL slots clear it).  G is an n x n dgCMatrix, n = the cells of
  * the resident matrix; an invalid G is SGL_EINVAL with a message.  While it is

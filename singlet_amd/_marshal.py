@@ -1,10 +1,11 @@
 """Marshalling shared by the fit calls of api.py and the handles of context.py: pointer triples, column-major images and
-the output buffers of the two fit families, each yielding its trailing ctypes arguments in ABI order."""
+the output buffers of the two fit families, each yielding its trailing ctypes arguments in ABI order, and the one call of the
+embedding k-NN."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import f64p, i32p, ptr
+from ._lib import check, f64p, i32p, ptr
 
 
 def csc_ptrs(A):
@@ -79,3 +80,38 @@ class ArdOutputs(_FitOutputs):
 
     def result(self):
         return {"w": self.w.T, "d": self.d, "h": self.h.T, **self.traces()}
+
+
+def knn_call(fn, reference, query, dims, n_neighbors, resident=None):
+    """Shared by Context.knn and api.knn: fn(R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, idx_out, dist_out) is the
+    library call.  reference / query: k x n matrices (R's orientation, one column per cell); a None reference stands for the
+    H of a fit of shape resident = (k, n), a None query for the references themselves; dims: 0-based rows or None.
+    Returns (idx, dist), each n_query x n_neighbors: row j holds the neighbours of query j in rank order."""
+    if reference is None:
+        if resident is None:
+            raise ValueError("reference must be a k x n matrix")
+        k, n_ref = resident
+        Rb = None
+    else:
+        Rb = colmajor(reference, "reference must be a k x n matrix")
+        n_ref, k = Rb.shape
+    Qb, nq = None, n_ref
+    if query is not None:
+        Qb = colmajor(query, "query must be a k x n matrix")
+        nq = Qb.shape[0]
+        if Qb.shape[1] != k:
+            raise ValueError("query has %d rows, the reference has %d" % (Qb.shape[1], k))
+    d, nd = None, 0
+    if dims is not None:
+        d = np.asarray(dims)
+        if d.size == 0:   # (an empty list has no integer type of its own; the library refuses it by name)
+            d = np.zeros(0, dtype=np.int32)
+        if d.ndim != 1 or d.dtype.kind not in "iu" or (d.size and (d.min() < -2**31 or d.max() >= 2**31)):
+            raise ValueError("dims must be a list of 32-bit row indices")
+        d = np.ascontiguousarray(d, dtype=np.int32)
+        nd = int(d.size)
+    K = int(n_neighbors)
+    shape = (int(nq), K) if 1 <= K <= 256 else (1, 1)   # outside it the library refuses before it writes
+    idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
+    check(fn(ptr(Rb, f64p), int(k), int(n_ref), ptr(Qb, f64p), int(nq), ptr(d, i32p), nd, K, ptr(idx, i32p), ptr(dist, f64p)))
+    return idx, dist

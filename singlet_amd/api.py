@@ -41,7 +41,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs
+from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, knn_call
 from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
@@ -1439,3 +1439,63 @@ def find_local_neighbors(h, spatial, k_param=20, spatial_radius=4, nn_metric="ja
         knn.x = np.ones_like(knn.x)
     snn = c_SNN(knn, prune_snn, threads) if compute_snn else None
     return {"knn": knn, "snn": snn}
+
+
+# ---------------------------------------------------------------------------
+# Embedding neighbours (Seurat's FindNeighbors on the nmf reduction)
+# ---------------------------------------------------------------------------
+def knn(reference, query=None, n_neighbors=20, dims=None):
+    """Exact nearest neighbours in an embedding, one-shot (sgl_c_knn): reference k x n, query k x n_query (R's orientation, one
+    column per cell; None: the references themselves), dims 0-based rows -> (idx, dist), each n_query x n_neighbors, as
+    Context.knn returns them.  The rules -- the sequential FP64 sum, the ranking by (squared distance, index) -- are in
+    include/singlet_hip.h, sgl_knn."""
+    return knn_call(_lib.load().sgl_c_knn, reference, query, dims, n_neighbors)
+
+
+def find_neighbors(embedding, k_param=20, dims=None, compute_snn=True, prune_snn=1 / 15, return_dist=False):
+    """The numeric steps of Seurat's FindNeighbors on a reduction: the exact k.param nearest neighbours of every cell (itself
+    included) in the embedding, and the shared-nearest-neighbour graph of them.  `embedding` is cells x factors (as
+    cell.embeddings), or a Context with a fit, whose H is searched where it lies, in the fit's stored factor order; `dims`
+    are 1-based, as in R.  Returns {"nn", "snn", "idx", "dist"}: idx / dist n x k.param as Context.knn returns them; nn the
+    n x n dgCMatrix whose column j holds the neighbours of cell j (rows ascending; x = 1, or the distances with return_dist:
+    the self entry is then an explicit 0); snn = c_SNN(nn, nextafter(prune_snn, -inf), 0) or None.
+
+    Seurat's SNN zeroes the entries below prune.SNN and keeps equality; c_SNN keeps > strictly.  With k.param neighbours in
+    every column, inter / (2 k.param - inter) is Seurat's Jaccard index and the diagonal 1 its k.param / k.param, and the
+    next double below prune_snn as the strict threshold keeps exactly the entries >= prune_snn."""
+    from .context import Context
+    if prune_snn >= 1:
+        raise ValueError("prune.snn must be less than 1. You are currently asking to prune everything.")
+    if isinstance(embedding, Context):
+        ctx, E = embedding, None
+        _, n, _ = ctx.dims()
+        k = ctx.k
+    else:
+        ctx, E = None, np.asarray(embedding, dtype=np.float64)
+        if E.ndim != 2:
+            raise ValueError("embedding must be a cells x factors matrix")
+        n, k = E.shape
+    d0 = None
+    if dims is not None:
+        d = np.atleast_1d(np.asarray(dims))
+        if d.ndim != 1 or d.dtype.kind not in "iu":
+            raise ValueError("dims must be a list of 1-based dimensions")
+        d = d.astype(np.int64)
+        if d.size and np.max(d) > k:
+            raise ValueError("you requested up to %d dims but there are only %d dimensions in reduction" % (np.max(d), k))
+        if d.size == 0 or np.min(d) < 1:
+            raise ValueError("dims are 1-based: at least one, none below 1")
+        d0 = d - 1
+    K = int(k_param)
+    if n * max(K, 0) > 2**31 - 1:
+        raise ValueError("%d cells x %d neighbours do not fit a dgCMatrix" % (n, K))
+    if ctx is not None:
+        idx, dist = ctx.knn(K, dims=d0)
+    else:
+        idx, dist = knn(E.T, None, K, d0)
+    order = np.argsort(idx, axis=1, kind="stable")
+    rows = np.take_along_axis(idx, order, axis=1).ravel()
+    x = np.take_along_axis(dist, order, axis=1).ravel() if return_dist else np.ones(rows.size)
+    nn = dgCMatrix(x, rows, np.arange(n + 1, dtype=np.int64) * K, (n, n))
+    snn = c_SNN(nn, np.nextafter(prune_snn, -np.inf), 0) if compute_snn else None
+    return {"nn": nn, "snn": snn, "idx": idx, "dist": dist}

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
-from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs
+from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, knn_call
 from .sparse import as_dgCMatrix
 
 SYNTH_SEED = 0x5EED
@@ -484,6 +484,27 @@ class Context(_Handle):
         gene, used instead of the trend (another loess's, for parity with it).  The matrix and a running fit are only read."""
         nr, _, _ = self.dims()
         return _variable_features_call(lambda *a: self._L.sgl_variable_features(self._h, *a), nr, nfeatures, span, vmax, expected_var)
+
+    def knn(self, n_neighbors=20, reference=None, query=None, dims=None):
+        """Exact nearest neighbours in an embedding (sgl_knn): (idx, dist), each n_query x n_neighbors, row j = the
+        n_neighbors nearest reference columns of query column j in rank order -- by (squared distance, index), ties to
+        the lower index -- and their Euclidean distances.  reference: k x n (R's orientation); None: the H of the current
+        fit, read where it is, in the fit's stored factor order.  query: k x n_query; None: the references themselves (a
+        cell is then its own first neighbour unless n_neighbors identical columns precede it).  dims: 0-based rows.  The
+        context and a running fit are only read."""
+        resident = None
+        if reference is None:
+            _, n, _ = self.dims()
+            resident = (self.k, n)
+        return knn_call(lambda *a: self._L.sgl_knn(self._h, *a), reference, query, dims, n_neighbors, resident)
+
+    def knn_info(self):
+        """What the last knn() on this context ran (sgl_knn_info): {"instance" (0 .. 3: coordinates in registers up to 8,
+        16, 32, 64 dimensions; 4: the generic kernel), "segments" (pieces of the references, merged afterwards),
+        "queries_per_workgroup", "lists_global" (0: candidate lists in LDS, 1: in global scratch)}."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._L.sgl_knn_info(self._h, ptr(out, i64p)))
+        return dict(zip(("instance", "segments", "queries_per_workgroup", "lists_global"), (int(v) for v in out)))
 
     def set_stream(self, stream_ptr):
         check(self._L.sgl_set_stream(self._h, C.c_void_p(stream_ptr) if stream_ptr else None))

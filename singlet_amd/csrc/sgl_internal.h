@@ -242,6 +242,7 @@ struct sgl_ctx {
     int64_t sweeps_acc[4] = {0, 0, 0, 0};
     int64_t wave_sweeps_acc[2] = {0, 0};
     double* pinned = nullptr;        // host pinned scratch (8 doubles)
+    int64_t knn_last[4] = {0, 0, 0, 0};   // sgl_knn_info: instance, segments, queries per workgroup, list home of the last sgl_knn
 
     sgl_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
