@@ -688,6 +688,85 @@ SGL_API int sgl_c_knn(const double* R, int32_t k, int64_t n_ref, const double* Q
  * candidate lists lay in LDS, 1 in global scratch.  A refused call leaves it as it was. */
 SGL_API int sgl_knn_info(sgl_ctx* ctx, int64_t out[4]);
 
+/* Clustering: a deterministic multi-level Louvain modularity optimiser on a neighbour graph -- the step after
+ * find_neighbors (Seurat's FindClusters on the SNN graph).  The reference's package has no clustering code (it hands the
+ * graph to Seurat, whose optimiser visits the vertices in a seeded random order), so the rules below are this library's own,
+ * stated in full; tests/louvain_restatement.py restates them in numpy and the device holds them bit for bit.  No parity of
+ * labels with Seurat is claimed.  One-shot on the current device; no team form, no R shim entry.
+ *
+ * Input: G is an n x n dgCMatrix (Gx, Gi, Gp): rows ascending within a column, weights finite and >= 0, pattern and values
+ * symmetric (A_ij and A_ji both stored, with the same bits; the output of sgl_c_snn qualifies: its Jaccard index is one
+ * division of commutative integer sums).  A diagonal entry is a self-loop, counted once.
+ *  - refused with SGL_EINVAL and a message, before anything is uploaded: n < 0; n_res < 1 or a NULL resolutions; a resolution
+ *    that is not finite or not > 0 (named by position); tol < 0 or NaN; max_sweeps outside [1, 1024]; max_levels outside
+ *    [1, 32]; Gp[0] != 0 or a decreasing Gp (the column is named); a NULL array of a graph with entries.
+ *  - refused with SGL_EINVAL by a device pass, with a message that names the column and the row of the first defective entry
+ *    in column-major order: a row outside [0, n), a row not above the one before it in its column, a weight that is not
+ *    finite, a negative weight.  A graph without such an entry goes through a second pass that names the first entry in
+ *    column-major order whose mirror A_ji is missing or differs in its bits.  Then S (below) is computed: S = 0 (an all-zero
+ *    graph, one without entries included) and an S that overflows are refused.  The library stays usable after every refusal.
+ *  - n = 0: an empty result and no levels, nothing is read.
+ *  - the graph is uploaded and validated once for all n_res resolutions; the outputs of resolution r lie at labels + r n,
+ *    n_clusters + r, n_levels + r, q_levels + 32 r, sweeps_levels + 32 r.  Any output may be NULL.
+ *
+ * Quantities of one level (its graph A with n vertices, labels comm[], gamma = the resolution), every sum in ONE order that
+ * depends on the graph and the labels alone -- never on the launch shape, never on a floating-point atomic -- every product
+ * and addition its own rounding (the unit is compiled with -ffp-contract=off):
+ *  - "sequential": from +0.0, the terms one after the other.  "blocked": the terms in their stated order are cut into blocks
+ *    of 1024 consecutive terms; every block is summed sequentially, and the block sums are summed sequentially in ascending
+ *    block order (so a million-term sum is not one serial chain, and up to 1024 terms it IS the sequential sum).
+ *  - k_v = the sequential sum of column v in ascending row, the diagonal included.  S = the blocked sum of k_v, v ascending.
+ *    Every level computes k and S from its own graph.
+ *  - own_v = the sequential sum, in ascending row, of the entries A_jv of column v with comm[j] == comm[v] (the diagonal
+ *    is one of them).  tot_c = the blocked sum of k_v, in_c = the blocked sum of own_v, over the members v of c ascending.
+ *  - term_c = in_c / S - (gamma * (tot_c / S)) * (tot_c / S), evaluated in that order (+0.0 for an id without members), and
+ *    Q = the blocked sum of term_c over the ids c = 0 .. n-1 ascending.
+ *
+ * One synchronous sweep: every vertex reads the labels, tot and the community sizes of the sweep's start.  For vertex v
+ * with own community o = comm[v] the candidates are o and every community among its off-diagonal neighbours; for each,
+ *     w_c  = the sequential sum of A_jv over j != v with comm[j] == c, in ascending j (w_o = +0.0 without such a j),
+ *     g(c) = w_c - ((gamma * k_v) * (c == o ? tot_c - k_v : tot_c)) / S,       evaluated in that order.
+ * best = the candidate of maximal g, ties to the lowest id.  v moves to best only if best != o and g(best) > g(o) strictly,
+ * and -- the swap rule -- not when o and best both hold a single vertex and best > o (of two singletons that prefer each
+ * other only the higher-numbered moves; without the rule they would swap for ever).  A vertex with no off-diagonal
+ * neighbour never moves.
+ *
+ * One level: the labels start as comm[v] = v, Q is computed, then sweeps follow under the guard.  After a sweep Q' is
+ * computed from the new labels: Q' <= Q (a sweep that moved nothing included): the sweep is discarded and the level's moving
+ * phase ends; Q' - Q <= tol: the sweep is kept and the phase ends; otherwise it is kept and the phase continues, up to
+ * max_sweeps sweeps.  So Q never decreases and the number of sweeps is bounded whatever the data.  (Synchronous moves can
+ * lower Q where many gains tie, as on unweighted lattices: the guard then ends the phase early -- DESIGN.md "Clustering".)
+ *
+ * Aggregation: the ids that survive a level are renumbered in ascending order; the next level's graph has one vertex per
+ * community and A'_cd = the blocked sum of A_uv over u in c, v in d in column-major order of the fine entries (v ascending,
+ * then u); self-loops carry the intra-community weight.  A coarse graph need not be bitwise symmetric: nothing reads a row.
+ * The optimiser stops after a level that kept no sweep, or after max_levels levels.
+ *
+ * Output per resolution: labels int32[n], clusters numbered by descending size, ties by smallest member, 0 the largest;
+ * n_clusters; n_levels = the levels run (the last one that kept no sweep included); q_levels[32]: Q at the end of each
+ * level's moving phase; sweeps_levels[32]: the sweeps KEPT at each level; entries past n_levels are 0.
+ *
+ * Kernels (singlet_amd/csrc/kernels_cluster.hip; the host logic without HIP in cluster_host.h): the sweep sorts the keys
+ * (community << 32 | position in the column) of a vertex so that a community's entries become one run in ascending row --
+ * one wave per vertex in LDS for columns of up to 512 stored entries (the fast path), a segmented radix sort in HBM and one
+ * 256-thread workgroup per vertex above (the slow path; coarse levels produce such hubs).  tot, in, Q and the member lists
+ * come from a stable radix sort of the vertices by label; the coarse graph from a stable radix sort of the entries by
+ * (column community, row community).  64-bit offsets; integer atomics only (the move count, the first defect). */
+SGL_API int sgl_c_louvain(const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const double* resolutions,
+                          int32_t n_res, double tol, int32_t max_sweeps, int32_t max_levels, int32_t* labels,
+                          int32_t* n_clusters, int32_t* n_levels, double* q_levels, int32_t* sweeps_levels);
+/* Stage operator: ONE sweep on G from labels_in (each in [0, n); any partition, not only a level's start) at one
+ * resolution -> labels_out, Q of labels_in, Q of labels_out, the number of moved vertices.  It makes no guard decision.  G
+ * goes through the first validation pass and the S rule only: a coarse graph, which need not be symmetric, is a valid
+ * input.  Outputs may be NULL. */
+SGL_API int sgl_op_louvain_sweep(const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* labels_in,
+                                 double resolution, int32_t* labels_out, double* q_in, double* q_out, int64_t* moved_out);
+/* What the last sgl_c_louvain or sgl_op_louvain_sweep of this process ran: out[0] the widest column (stored entries) of the
+ * fast path in this build; [1] the vertices that took the slow path at level 0, [2] at later levels (each summed over the
+ * call's resolutions); [3] the coarse-graph build path: 0 none was built, 1 the global radix sort.  A call refused before
+ * its first sweep leaves [1] .. [3] as they were. */
+SGL_API int sgl_louvain_info(int64_t out[4]);
+
 /* Cell graph of c_gcnmf for the current fit (after sgl_fit_init, which drops
  * it again; all-NULL slots clear it).  G is an n x n dgCMatrix, n = the cells of
  * the resident matrix; an invalid G is SGL_EINVAL with a message.  While it is

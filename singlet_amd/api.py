@@ -1499,3 +1499,87 @@ def find_neighbors(embedding, k_param=20, dims=None, compute_snn=True, prune_snn
     nn = dgCMatrix(x, rows, np.arange(n + 1, dtype=np.int64) * K, (n, n))
     snn = c_SNN(nn, np.nextafter(prune_snn, -np.inf), 0) if compute_snn else None
     return {"nn": nn, "snn": snn, "idx": idx, "dist": dist}
+
+
+# ---------------------------------------------------------------------------
+# Clustering (Seurat's FindClusters on the SNN graph; the rules are this library's own: include/singlet_hip.h, "Clustering")
+# ---------------------------------------------------------------------------
+LOUVAIN_MAX_LEVELS = 32
+
+
+def _square_graph(G, what):
+    G = as_dgCMatrix(G)
+    if G.nrow != G.ncol:
+        raise ValueError("%s: the graph must be square, not %d x %d" % (what, G.nrow, G.ncol))
+    return G
+
+
+def c_louvain(G, resolutions, tol=1e-7, max_sweeps=64, max_levels=32):
+    """sgl_c_louvain: deterministic multi-level Louvain on the symmetric n x n graph G for every resolution of the list ->
+    {"labels": n_res x n int32 (clusters numbered by descending size), "n_clusters", "n_levels": n_res, "q_levels",
+    "sweeps_levels": n_res x 32}.  The graph is uploaded and validated once."""
+    G = _square_graph(G, "c_louvain")
+    res = np.ascontiguousarray(np.atleast_1d(np.asarray(resolutions, dtype=np.float64)).ravel())
+    n, R = G.ncol, int(res.size)
+    labels = np.zeros((max(R, 1), n), dtype=np.int32)
+    ncl, nlev = np.zeros(max(R, 1), dtype=np.int32), np.zeros(max(R, 1), dtype=np.int32)
+    q = np.zeros((max(R, 1), LOUVAIN_MAX_LEVELS))
+    sw = np.zeros((max(R, 1), LOUVAIN_MAX_LEVELS), dtype=np.int32)
+    check(_lib.load().sgl_c_louvain(ptr(G.x, f64p), ptr(G.i, i32p), ptr(G.p, i32p), n, ptr(res, f64p), R, float(tol), int(max_sweeps),
+                                    int(max_levels), ptr(labels, i32p), ptr(ncl, i32p), ptr(nlev, i32p), ptr(q, f64p), ptr(sw, i32p)))
+    return {"labels": labels[:R], "n_clusters": ncl[:R], "n_levels": nlev[:R], "q_levels": q[:R], "sweeps_levels": sw[:R]}
+
+
+def op_louvain_sweep(G, labels, resolution=1.0):
+    """sgl_op_louvain_sweep: one synchronous sweep on G from `labels` -> (labels_out, Q of labels, Q of labels_out, moved).
+    No guard decision; G need not be symmetric (a coarse graph is a valid input)."""
+    G = _square_graph(G, "op_louvain_sweep")
+    n = G.ncol
+    lab = np.ascontiguousarray(labels, dtype=np.int32).ravel()
+    if lab.size != n:
+        raise ValueError("op_louvain_sweep: %d labels for %d vertices" % (lab.size, n))
+    out = np.zeros(n, dtype=np.int32)
+    q0, q1, moved = C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
+    check(_lib.load().sgl_op_louvain_sweep(ptr(G.x, f64p), ptr(G.i, i32p), ptr(G.p, i32p), n, ptr(lab, i32p), float(resolution),
+                                           ptr(out, i32p), C.byref(q0), C.byref(q1), C.byref(moved)))
+    return out, q0.value, q1.value, int(moved.value)
+
+
+def louvain_info():
+    """sgl_louvain_info: what the last clustering call of this process ran."""
+    out = np.zeros(4, dtype=np.int64)
+    check(_lib.load().sgl_louvain_info(ptr(out, _lib.i64p)))
+    return dict(zip(("fast_degree", "slow_level0", "slow_coarse", "coarse_build"), (int(v) for v in out)))
+
+
+def _without_diagonal(G):
+    col = np.repeat(np.arange(G.ncol, dtype=np.int64), np.diff(G.p))
+    keep = G.i != col
+    p = np.concatenate(([0], np.cumsum(np.bincount(col[keep], minlength=G.ncol))))
+    return dgCMatrix(G.x[keep], G.i[keep], p, G.Dim)
+
+
+def find_clusters(graph, resolution=0.8, drop_diagonal=True, tol=1e-7, max_sweeps=64, max_levels=32):
+    """The numeric step of Seurat's FindClusters on a neighbour graph: modularity clusters of the cells at every resolution
+    asked for.  `graph` is a symmetric n x n dgCMatrix / SciPy matrix, or the dict find_neighbors returns (its "snn" is
+    used); `resolution` a number or a list; drop_diagonal removes the stored diagonal first (the unit diagonal of an SNN
+    graph says nothing about communities and only damps the moves).  Returns {"clusters": n x n_res int32, column r the
+    clusters at resolution r numbered by descending size (0 the largest), "modularity": n_res, the Q reached,
+    "n_clusters": n_res, "levels": n_res}.  The optimiser is this library's deterministic synchronous Louvain, not
+    Seurat's seeded one: no parity of labels is claimed (include/singlet_hip.h, "Clustering")."""
+    if isinstance(graph, dict):
+        if graph.get("snn") is None:
+            raise ValueError("find_clusters: the neighbours were computed without an SNN graph (compute_snn=False)")
+        graph = graph["snn"]
+    G = _square_graph(graph, "find_clusters")
+    res = np.atleast_1d(np.asarray(resolution, dtype=np.float64))
+    if res.ndim != 1 or res.size < 1:
+        raise ValueError("find_clusters: resolution must be a number or a list of numbers")
+    if not np.all(np.isfinite(res) & (res > 0)):
+        raise ValueError("find_clusters: every resolution must be finite and > 0")
+    if drop_diagonal:
+        G = _without_diagonal(G)
+    out = c_louvain(G, res, tol, max_sweeps, max_levels)
+    last = np.maximum(out["n_levels"], 1) - 1
+    return {"clusters": np.ascontiguousarray(out["labels"].T), "modularity": out["q_levels"][np.arange(res.size), last],
+            "n_clusters": out["n_clusters"], "levels": out["n_levels"]}
