@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Host model of the entry-stream layout (kernels_tiled.hip: tiled_count_kernel) -- the sliding-window schedule, stored entries
-per non-zero for a CSC matrix.  `stream_counts` returns the same group counts the device writes; `entries` their total in
-stored entries, which is what sgl_layout_get reports.  Usage: layout_emulate.py [pbmc3k | iid M N INV] k"""
+per non-zero for a CSC matrix.  `stream_counts` returns the same group counts the device writes (balance=True: the device
+default, the eight wave blocks of a workgroup level their chunks of a stage; balance=False: SGL_TILED_NO_BALANCE=1, the
+rule before it); `entries` their total in stored entries, which is what sgl_layout_get reports.  Usage: layout_emulate.py [pbmc3k | iid M N INV] k"""
 import sys
 import os
 import numpy as np
@@ -26,15 +27,34 @@ def block_ranges(T, nb, nr):
     return [(2 * (y * T // nr), min(2 * ((y + 1) * T // nr), nb)) for y in range(nr)]
 
 
-def stream_counts(p, i, nrow, TR, nsl, ranges=1, order="sorted", tail_wg0=-1, tail_R=1, trace=None):
+def level_spread(f, E):
+    """Run-ahead groups of the balance rule: spread E groups level over units that can take f[..., p] of them.  t = the largest
+    level with sum(min(f, t)) <= E; unit p gets min(f_p, t), what is left goes one each to the highest-numbered units with
+    f_p > t.  Where sum(f) <= E every unit gets f_p.  f: (waves, 32), E: (waves,)"""
+    ts = np.arange(256, dtype=np.int64)
+    S = np.minimum(f[:, None, :], ts[None, :, None]).sum(axis=2)          # S[w, t], non-decreasing in t
+    t = (S <= E[:, None]).sum(axis=1) - 1
+    add = np.minimum(f, t[:, None])
+    left = E - add.sum(axis=1)
+    hot = f > t[:, None]
+    above = np.cumsum(hot[:, ::-1], axis=1)[:, ::-1] - hot                # hot units numbered higher than p
+    return add + (hot & (above < left[:, None]))
+
+
+def stream_counts(p, i, nrow, TR, nsl, ranges=1, order="sorted", tail_wg0=-1, tail_R=1, trace=None, balance=True):
     """Group counts cnt[wb, b, pair] of the sliding-window stream (b = row block of D = TR / 2 rows = the stage).
 
     In stage b the LDS holds blocks b and b + 1 of the range; every column finishes its entries in block b and may run ahead
     into block b + 1.  Per pair: n = the larger number of entries left in block b over its nsl columns, rounded up to
-    groups of four; every column takes min(n, entries left in the window) real entries, pads for the rest.  The chunk
-    (wave block, stage) is rounded up to whole 64-slot sets by extra groups on the last pairs, each taking as many as
-    its columns still have run-ahead entries for; what is left goes on pair 31 as pads.
-    trace: a list that receives (col, first entry, entries, b) for every run of real entries, in stream order."""
+    groups of four; every column takes min(n, entries left in the window) real entries, pads for the rest.
+    balance (the device default; False = SGL_TILED_NO_BALANCE=1, the rule before it): the eight wave blocks of a workgroup
+    meet at a barrier after every stage, so the stage lasts as long as its longest chunk.  target = the largest of their
+    chunks of must groups, in whole sets; a wave block short of it takes the difference as run-ahead, but only groups that
+    hold real entries for every present column of the unit (f = floor(least window entries left / 4) - must), spread level
+    over the units (level_spread).  A wave block that cannot reach the target stays short.
+    The chunk (wave block, stage) is then rounded up to whole 64-slot sets by extra groups on the last pairs, each taking
+    as many as its columns still have run-ahead entries for; what is left goes on pair 31 as pads.
+    trace: a list that receives (col, first entry, entries, b) for every run of real entries."""
     p = np.asarray(p, dtype=np.int64)
     i = np.asarray(i, dtype=np.int64)
     ncol = p.size - 1
@@ -57,12 +77,11 @@ def stream_counts(p, i, nrow, TR, nsl, ranges=1, order="sorted", tail_wg0=-1, ta
     present = slot >= 0
     sc = np.where(present, slot, 0)
     cnt = np.zeros((nwb, nb, 32), dtype=np.int64)
-    nwg = (nwb + 7) // 8
-    for wb in range(nwb):
-        wg = wb // 8
+    for wg in range((nwb + 7) // 8):            # a workgroup: eight consecutive wave blocks (fewer in the last one)
+        w0, w1 = 8 * wg, min(8 * wg + 8, nwb)
         nr = tail_R if (tail_R > 1 and tail_wg0 >= 0 and wg >= tail_wg0) else ranges
         nr = max(1, min(nr, T))
-        cols, pres = sc[wb], present[wb]
+        cols, pres = sc[w0:w1], present[w0:w1]
         for b0, b1 in block_ranges(T, nb, nr):
             if b0 >= b1:
                 continue
@@ -71,25 +90,31 @@ def stream_counts(p, i, nrow, TR, nsl, ranges=1, order="sorted", tail_wg0=-1, ta
                 hi = min(b + 2, b1)
                 end_b = np.where(pres, seg[b + 1][cols], 0)
                 end_w = np.where(pres, seg[hi][cols], 0)
-                g = (np.max(end_b - pos, axis=1) + 3) // 4
-                cap = (np.max(end_w - pos, axis=1) + 3) // 4 - g
-                rem = (-int(g.sum())) % gps
-                for q in range(31, -1, -1):
-                    if rem == 0:
-                        break
-                    e = min(int(cap[q]), rem)
-                    g[q] += e
-                    rem -= e
-                g[31] += rem
-                take = np.minimum(4 * g[:, None], end_w - pos)
+                g = (np.max(end_b - pos, axis=2) + 3) // 4
+                if balance:
+                    tot = g.sum(axis=1)
+                    target = gps * np.max((tot + gps - 1) // gps)
+                    fmin = np.min(np.where(pres, end_w - pos, np.iinfo(np.int64).max), axis=2) // 4
+                    f = np.where(pres.any(axis=2), np.maximum(fmin - g, 0), 0)
+                    g = g + level_spread(f, target - tot)
+                cap = (np.max(end_w - pos, axis=2) + 3) // 4 - g
+                for w in range(w1 - w0):
+                    rem = (-int(g[w].sum())) % gps
+                    for q in range(31, -1, -1):
+                        if rem == 0:
+                            break
+                        e = min(int(cap[w, q]), rem)
+                        g[w, q] += e
+                        rem -= e
+                    g[w, 31] += rem
+                take = np.minimum(4 * g[:, :, None], end_w - pos)
                 if trace is not None:
-                    for q in range(32):
-                        for h in range(nsl):
-                            if pres[q, h] and take[q, h] > 0:
-                                trace.append((int(cols[q, h]), int(pos[q, h]), int(take[q, h]), b))
+                    for w, q, h in zip(*np.nonzero(pres & (take > 0))):
+                        trace.append((int(cols[w, q, h]), int(pos[w, q, h]), int(take[w, q, h]), b))
                 pos = pos + take
-                cnt[wb, b] = g
+                cnt[w0:w1, b] = g
             assert np.array_equal(pos[pres], seg[b1][cols][pres]), "a column left entries behind"
+    assert cnt.max(initial=0) <= 255, "a unit's groups must fit the byte of cnt"
     return cnt
 
 

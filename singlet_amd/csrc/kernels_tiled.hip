@@ -25,7 +25,12 @@
 //     columns are stored as two half-streams that advance in lockstep.  Sliding window (round 7): in stage b every
 //     column finishes its entries of block b and may run ahead into block b + 1 -- the pair takes n = the most
 //     block-b entries either column has left, rounded up to 4, and each column fills those n steps with its own
-//     next entries of the window (x = 0 pads only where it has none left; tiled_count_kernel).  The chunk is
+//     next entries of the window (x = 0 pads only where it has none left; tiled_count_kernel).  Balanced chunks:
+//     the workgroup's eight waves meet at a barrier after every stage, so a stage lasts as long as its longest
+//     chunk; a wave block whose chunk is shorter than the longest of the eight takes the difference as further
+//     run-ahead, spread level over its pairs and only in groups that hold real entries for both columns -- the
+//     waves' chunks of a stage come out within ~1 % of each other instead of ~9 % (i.i.d. columns), for slightly
+//     fewer stored entries (SGL_TILED_NO_BALANCE=1: the rule before).  The chunk is
 //     rounded up to a multiple of 32 entries per half the same way, by extra groups on the last pairs.  64
 //     consecutive stream slots hold 32 entries of the A half then 32 of the B half, so one coalesced
 //     64-lane load fetches a "set".  Two arrays: roff (byte offset of the row inside the LDS ring: slot
@@ -87,64 +92,105 @@ __device__ __forceinline__ int tiled_range_end(int b, int T, int NB, int nr) {
 // blocks b and b + 1.  In the chunk (wb, b) every column finishes its entries of block b and may run ahead into block b + 1:
 // a column unit (pair / quad) takes n = the most entries any of its columns has left in block b, rounded up to groups of
 // four, and each of its columns fills those n steps with its own next entries of the window -- pads (x = 0) only where a
-// column has none left.  The chunk is rounded up to whole 64-slot sets by extra groups on the last units, each taking as
-// many as its columns still have window entries for; what no unit can fill goes on unit 31 as pads.
-// One wave per wave block, lane p = unit p (lanes 32-63 mirror 0-31), walking the stages of each of its ranges in order.
-// cnt = groups per (chunk, unit) -- at most D / 4 + D / 4 + 7 <= 253: a byte; ahead = entries of block b a column took in
+// column has none left.
+// Balance: the eight waves of an accumulate workgroup meet at a barrier after every stage, so a stage lasts as long as
+// the longest of their chunks.  With tot = a wave block's must groups, target = the largest tot of the workgroup's wave
+// blocks in whole sets: no stage can be shorter.  A wave block below it takes E = target - tot further groups as run-ahead
+// now -- work it would otherwise do in stage b + 1 -- but only groups that hold a real entry for every present column of
+// the unit: f = floor(the least window entries left over those columns / 4) - must groups a unit can give.  They are
+// spread level: t = the largest level with sum(min(f, t)) <= E, unit p gets min(f_p, t), what is left goes one each to
+// the highest-numbered units with f_p > t.  A wave block whose units cannot give E takes all they can and stays short:
+// it is never padded up to the target.  (SGL_TILED_NO_BALANCE=1: no such groups, the rule before.)
+// The chunk is then rounded up to whole 64-slot sets by extra groups on the last units, each taking as many as its
+// columns still have window entries for; what no unit can fill goes on unit 31 as pads.
+// One workgroup of eight waves per (accumulate workgroup, tile range) -- a range starts over at its first block, so the
+// ranges are independent -- one wave per wave block, lane p = unit p (lanes 32-63 mirror 0-31), walking the stages of the
+// range in order; the eight tot are exchanged through LDS.  The wave blocks of a workgroup share their range count.
+// cnt = groups per (chunk, unit) -- at most 2 D / 4 + 7 <= 253: a byte; ahead = entries of block b a column took in
 // stage b - 1 (<= D); chunk_entries = stored entries of the chunk (all slots).
-__global__ __launch_bounds__(256) void tiled_count_kernel(const int64_t* __restrict__ seg, const int32_t* __restrict__ perm, int64_t ncol,
-                                                          int T, int NB, int64_t nwb, int R, int64_t tail_wg0, int tail_R,
-                                                          uint8_t* __restrict__ cnt, uint16_t* __restrict__ ahead,
-                                                          int64_t* __restrict__ chunk_entries, int nsl) {
-    const int lane = threadIdx.x & 63, p = lane & 31;
-    const int64_t wb = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (wb >= nwb) return;   // wave-uniform
-    const int gps = 16 / nsl;   // groups (of 4 entries per slot) in a 64-slot set
-    int64_t col[4];
-    for (int h = 0; h < 4; ++h) col[h] = h < nsl ? tiled_slot_col(perm, ncol, wb, h, p, nsl) : -1;
-    const int nr = tiled_ranges_of(wb, R, tail_wg0, tail_R);
-    for (int b0 = 0; b0 < NB;) {
-        const int b1 = tiled_range_end(b0, T, NB, nr);
-        int64_t pos[4];
-        for (int h = 0; h < 4; ++h) pos[h] = col[h] >= 0 ? seg[(int64_t)b0 * ncol + col[h]] : 0;
-        for (int b = b0; b < b1; ++b) {
-            const int hi = b + 2 < b1 ? b + 2 : b1;
-            int64_t must = 0, avail = 0, ew[4];
-            for (int h = 0; h < 4; ++h) {
-                ew[h] = 0;
-                if (col[h] >= 0) {
-                    const int64_t eb = seg[(int64_t)(b + 1) * ncol + col[h]];
-                    ew[h] = seg[(int64_t)hi * ncol + col[h]];
-                    must = eb - pos[h] > must ? eb - pos[h] : must;
-                    avail = ew[h] - pos[h] > avail ? ew[h] - pos[h] : avail;
-                }
+__device__ __forceinline__ int tiled_sum32(int v) {
+    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 32);
+    return v;
+}
+// sum of v over the units above this one (p + 1 .. 31)
+__device__ __forceinline__ int tiled_sum_above(int v, int p) {
+    int suf = v;
+    for (int o = 1; o < 32; o <<= 1) {
+        const int w = __shfl_down(suf, o, 32);
+        if (p + o < 32) suf += w;
+    }
+    return suf - v;
+}
+
+__global__ __launch_bounds__(64 * TILED_NW) void tiled_count_kernel(const int64_t* __restrict__ seg, const int32_t* __restrict__ perm,
+                                                                    int64_t ncol, int T, int NB, int64_t nwb, int R, int64_t tail_wg0,
+                                                                    int tail_R, uint8_t* __restrict__ cnt, uint16_t* __restrict__ ahead,
+                                                                    int64_t* __restrict__ chunk_entries, int nsl, int balance) {
+    __shared__ int wtot[TILED_NW];
+    const int lane = threadIdx.x & 63, p = lane & 31, wave = (int)(threadIdx.x >> 6);
+    const int64_t wb = (int64_t)blockIdx.x * TILED_NW + wave;
+    const bool wact = wb < nwb;   // wave-uniform; a wave without a wave block still goes through the barriers
+    const int gps = 16 / nsl;     // groups (of 4 entries per slot) in a 64-slot set
+    // tile range blockIdx.y of the workgroup's nr (<= T: none is empty), the ranges of tiled_range_end
+    const int nr = tiled_ranges_of((int64_t)blockIdx.x * TILED_NW, R, tail_wg0, tail_R);
+    if ((int)blockIdx.y >= nr) return;   // workgroup-uniform
+    const int b0 = 2 * (int)(((int64_t)blockIdx.y * T) / nr);
+    const int e1 = 2 * (int)((((int64_t)blockIdx.y + 1) * T) / nr);
+    const int b1 = e1 < NB ? e1 : NB;
+    int64_t col[4], pos[4];
+    for (int h = 0; h < 4; ++h) col[h] = (wact && h < nsl) ? tiled_slot_col(perm, ncol, wb, h, p, nsl) : -1;
+    for (int h = 0; h < 4; ++h) pos[h] = (col[h] >= 0 && b0 < b1) ? seg[(int64_t)b0 * ncol + col[h]] : 0;
+    for (int b = b0; b < b1; ++b) {
+        const int hi = b + 2 < b1 ? b + 2 : b1;
+        int64_t must = 0, avail = 0, least = INT64_MAX, ew[4];
+        for (int h = 0; h < 4; ++h) {
+            ew[h] = 0;
+            if (col[h] >= 0) {
+                const int64_t eb = seg[(int64_t)(b + 1) * ncol + col[h]];
+                ew[h] = seg[(int64_t)hi * ncol + col[h]];
+                must = eb - pos[h] > must ? eb - pos[h] : must;
+                avail = ew[h] - pos[h] > avail ? ew[h] - pos[h] : avail;
+                least = ew[h] - pos[h] < least ? ew[h] - pos[h] : least;
             }
-            int g = (int)((must + 3) >> 2);
-            const int cap = (int)((avail + 3) >> 2) - g;
-            int tot = g;
-            for (int o = 16; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 32);
-            const int rem = (gps - (tot & (gps - 1))) & (gps - 1);
-            int suf = cap;   // run-ahead groups units p .. 31 can fill
-            for (int o = 1; o < 32; o <<= 1) {
-                const int v = __shfl_down(suf, o, 32);
-                if (p + o < 32) suf += v;
-            }
-            const int above = suf - cap;
-            int extra = rem - above < cap ? rem - above : cap;
-            if (extra < 0) extra = 0;
-            const int all = __shfl(suf, 0, 32);
-            if (p == TILED_NP - 1 && rem > all) extra += rem - all;
-            g += extra;
-            const int64_t u = wb * NB + b;
-            if (lane < 32) {
-                cnt[u * TILED_NP + p] = (uint8_t)g;
-                for (int h = 0; h < nsl; ++h)
-                    ahead[u * (TILED_NP * nsl) + nsl * p + h] = col[h] >= 0 ? (uint16_t)(pos[h] - seg[(int64_t)b * ncol + col[h]]) : (uint16_t)0;
-            }
-            if (lane == 0) chunk_entries[u] = (int64_t)(tot + rem) * 4 * nsl;
-            for (int h = 0; h < 4; ++h) pos[h] += (4 * (int64_t)g < ew[h] - pos[h]) ? 4 * (int64_t)g : ew[h] - pos[h];
         }
-        b0 = b1;
+        int g = (int)((must + 3) >> 2);
+        int tot = tiled_sum32(g);
+        if (balance) {
+            if (lane == 0) wtot[wave] = tot;   // 0 for a wave without a wave block
+            __syncthreads();
+            int sets = 0;
+            for (int w = 0; w < TILED_NW; ++w) sets = max(sets, (wtot[w] + gps - 1) / gps);
+            __syncthreads();   // everyone has read wtot: the next stage may write it
+            const int E = sets * gps - tot;
+            int f = least == INT64_MAX ? 0 : (int)(least >> 2) - g;
+            if (f < 0) f = 0;
+            int t = 0;   // the largest level in [0, 255] with sum(min(f, t)) <= E (f <= 2 D / 4 <= 246)
+            for (int step = 128; step > 0; step >>= 1)
+                if (tiled_sum32(min(f, t + step)) <= E) t += step;
+            int add = min(f, t);
+            const int left = E - tiled_sum32(add);
+            const int hot = f > t ? 1 : 0;
+            const int hot_above = tiled_sum_above(hot, p);   // (every lane takes part in the shuffles)
+            if (hot && hot_above < left) ++add;
+            g += add;
+            tot = tiled_sum32(g);
+        }
+        const int cap = (int)((avail + 3) >> 2) - g;
+        const int rem = (gps - (tot & (gps - 1))) & (gps - 1);
+        const int above = tiled_sum_above(cap, p);   // run-ahead groups units p + 1 .. 31 can fill
+        int extra = rem - above < cap ? rem - above : cap;
+        if (extra < 0) extra = 0;
+        const int all = __shfl(above + cap, 0, 32);
+        if (p == TILED_NP - 1 && rem > all) extra += rem - all;
+        g += extra;
+        const int64_t u = wb * NB + b;
+        if (wact && lane < 32) {
+            cnt[u * TILED_NP + p] = (uint8_t)g;
+            for (int h = 0; h < nsl; ++h)
+                ahead[u * (TILED_NP * nsl) + nsl * p + h] = col[h] >= 0 ? (uint16_t)(pos[h] - seg[(int64_t)b * ncol + col[h]]) : (uint16_t)0;
+        }
+        if (wact && lane == 0) chunk_entries[u] = (int64_t)(tot + rem) * 4 * nsl;
+        for (int h = 0; h < 4; ++h) pos[h] += (4 * (int64_t)g < ew[h] - pos[h]) ? 4 * (int64_t)g : ew[h] - pos[h];
     }
 }
 
@@ -267,6 +313,12 @@ static bool tiled_sort_columns() {
     const char* e = getenv("SGL_TILED_SORT");
     return !(e && *e == '0');
 }
+// SGL_TILED_NO_BALANCE=1 leaves the waves' chunks of a stage as unequal as their must groups are (the rule before the
+// balance of tiled_count_kernel; kept for A/B measurements and the tests)
+static bool tiled_balance_chunks() {
+    const char* e = getenv("SGL_TILED_NO_BALANCE");
+    return !(e && *e && *e != '0');
+}
 
 __global__ void tiled_col_keys_kernel(const int64_t* __restrict__ p, int64_t ncol, uint32_t* __restrict__ keys, int32_t* __restrict__ iota) {
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < ncol; c += (int64_t)gridDim.x * blockDim.x) {
@@ -328,9 +380,12 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
     // ranks up to 32: four columns per LDS instruction (SGL_TILED_NO_QUAD=1: the pair layout at every rank; A/B, tests)
     const int nsl = (k <= 32 && !getenv("SGL_TILED_NO_QUAD")) ? 4 : 2;
     // same matrix (any change of it frees the streams), same part size: the stream is still valid
-    if (S.built && S.k == k && S.NSL == nsl && S.ncol == M.ncol && S.nrow == M.nrow && S.src_nnz == M.nnz && (S.perm != nullptr) == tiled_sort_columns())
+    const bool balance = tiled_balance_chunks();
+    if (S.built && S.k == k && S.NSL == nsl && S.ncol == M.ncol && S.nrow == M.nrow && S.src_nnz == M.nnz &&
+        (S.perm != nullptr) == tiled_sort_columns() && S.balance == balance)
         return SGL_OK;
     S.built = false;
+    S.balance = balance;
     S.xm_mask_t = -1;   // the masked value array follows the stream layout
     S.k = k;
     S.NSL = nsl;
@@ -342,6 +397,7 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
     int TR = TILED_LDS_BYTES / (KS * 8);
     TR = TR / 8 * 8;
     if (TR > 984) TR = 984;  // groups per pair (+ <= 7 chunk-padding groups) must fit a byte
+    static_assert(984 / 4 + 7 <= 255, "cnt: a unit's groups of one stage -- at most its window of TR rows in fours, + 7 pads -- in a byte");
     if (TR < 8 || k > 64) { sgl_set_error("tiled accumulate: k=%d unsupported", k); return SGL_EINVAL; }
     S.nwb = ((int64_t)M.ncol + S.CW - 1) / S.CW;
     // A small matrix cannot fill the chip with LDS-sized tiles even when every tile is a range of its own (pbmc3k: 3 column
@@ -469,8 +525,9 @@ int sgl_tiled_build(sgl_ctx* c, const DevCSC& M, int k, DevTiled& S) {
     if (rc == SGL_OK) rc = t_reserve(&S.ahead, &S.cap_ahead, (size_t)nchunks * (size_t)S.CW);
     if (rc == SGL_OK) rc = t_reserve(&S.cstart, &S.cap_cstart, (size_t)nchunks + 1);
     if (rc == SGL_OK && S.nwb > 0) {
-        tiled_count_kernel<<<dim3((unsigned)((S.nwb + 3) / 4)), dim3(256), 0, s>>>(S.seg, S.perm, M.ncol, S.T, S.NB, S.nwb, S.R,
-                                                                                   S.tail_wg0, S.tail_R, S.cnt, S.ahead, chunk_entries, nsl);
+        // one workgroup per (accumulate workgroup, tile range); a workgroup with fewer ranges than the grid has leaves the rest
+        tiled_count_kernel<<<dim3((unsigned)nwg_x, (unsigned)std::max(S.R, S.tail_R)), dim3(64 * TILED_NW), 0, s>>>(
+            S.seg, S.perm, M.ncol, S.T, S.NB, S.nwb, S.R, S.tail_wg0, S.tail_R, S.cnt, S.ahead, chunk_entries, nsl, balance ? 1 : 0);
         if (hipGetLastError() != hipSuccess) { sgl_set_error("tiled build: count kernel launch failed"); rc = SGL_EHIP; }
     }
     if (rc == SGL_OK) rc = k_exclusive_scan(c, chunk_entries, S.cstart, nchunks);

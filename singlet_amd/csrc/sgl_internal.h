@@ -87,6 +87,7 @@ struct DevTiled {
     int32_t* perm = nullptr;    // [ncol] column at position pos of the descending-non-zero-count order (nullptr: matrix order)
     size_t cap_perm = 0;
     int64_t perm_nnz = -1;      // the matrix (by its non-zero count) perm was computed for
+    bool balance = true;        // the waves' chunks of a stage levelled by run-ahead (tiled_count_kernel; SGL_TILED_NO_BALANCE)
     bool range_fastest = false; // work units ordered (column group, tile range) instead of (tile range, column group)
     double top_share = 0.0;     // share of the non-zeros in the first 512 columns of that order (the heaviest workgroup)
     double top_share4 = 0.0;    // ... in the first 1024 (the heaviest workgroup of the quad layout)
