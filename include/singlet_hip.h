@@ -637,6 +637,71 @@ SGL_API int sgl_c_variable_features(const double* Ax, const int32_t* Ai, const i
                                     int32_t nfeatures, double span, double vmax, const double* expected_var,
                                     int32_t* features, int32_t* n_out, double* info);
 
+/* Marker genes: which genes mark each cluster -- Seurat's FindAllMarkers / FindMarkers with the default Wilcoxon rank-sum
+ * test, one-vs-rest, for every gene and every cluster from ONE ordering of the gene's values over the resident matrix.  The
+ * reference's package has no such function (it hands the object to Seurat); the rules below are this library's own, stated
+ * in full; tests/markers_restatement.py restates them in numpy and scipy.stats.mannwhitneyu is the independent yardstick.
+ *
+ * Inputs.  The resident matrix, m genes x n cells, values as they are (normally after sgl_log_normalize).  labels[n], int32
+ * in [-1, G): a cell labelled -1 is left out of everything; every other cell is included.  N = the included cells, n_c = the
+ * size of cluster c (group_n).  FindMarkers(ident.1, ident.2) is the case labels in {0, 1, -1}.  1 <= G <= 1024;
+ * ncol <= 2^21, so that the tie term fits 64 bits (N^3 - N < 2^63).
+ *
+ * Entry classes, per gene g, over the gene's stored entries in included cells: x == 0.0 (either sign) is a zero and joins
+ * the gene's implicit zeros; pos[g, c] = the stored x > 0 in cluster c; nz[g, c] = the stored x != 0 in cluster c.
+ *
+ * Ranks.  The N values of the gene are ordered: the negatives ascending, the zero block of N - sum_c nz[g, c] values, the
+ * positives ascending.  A tie run is a maximal set of equal doubles; the zero block is one run.  A run at the 0-based
+ * positions [a, b) gives each member the DOUBLED midrank a + b + 1.  rank2[g, c] (int64) = the sum of the doubled midranks
+ * of the members in cluster c (the zero block has n_c - nz[g, c] members of c); tie[g] (uint64) = the sum over the runs of
+ * t^3 - t, t = b - a.  sum_c rank2[g, c] = N (N + 1).  All integers: any correct kernel gives the same bits, whatever its
+ * tiling, and the batching of the long path cannot change one.
+ *
+ * Group sums.  sum[g, c] = the sum of f(x) over the gene's stored entries in cluster c; transform 0: f = identity, 1:
+ * f = expm1 (Seurat's mean function of log-normalised data), evaluated on the device.  THE SUMMATION ORDER is a function
+ * of the gene's entries and the labels alone: the entries in stored order -- those of excluded cells included, as members of
+ * no cluster -- are cut into segments of 8192; a segment into blocks of 64 consecutive entries; the block partial of cluster
+ * c is the butterfly sum (v += v[lane ^ 32], then 16, 8, 4, 2, 1) of 64 lane values, +0.0 for a lane that holds no member of
+ * c or lies past the end; the block partials are added in ascending block order from +0.0 within a segment, the segment
+ * partials in ascending segment order from +0.0.  A block without a member of c may be skipped: the bits do not change.
+ * No floating-point atomics, no contraction, no loop whose trip count follows the launch size.
+ *
+ * Derived statistics, on the host inside the library, once per (g, c), with n1 = n_c and n2 = N - n_c:
+ *   pct_in = pos / n1;  pct_out = (sum over c' != c of pos) / n2;  mean_in = sum / n1;  S_out = the sum[g, c'] of c' != c
+ *   added in ascending c' from +0.0;  mean_out = S_out / n2;  log2fc = log2(mean_in + pseudocount) - log2(mean_out +
+ *   pseudocount);  U2 = rank2 - n1 (n1 + 1) and D = U2 - n1 n2 in int64;
+ *   var = ((double)n1 * (double)n2 / 12.0) * (((double)N + 1.0) - (double)tie / ((double)N * ((double)N - 1.0))).
+ *   With n1 or n2 zero, or !(var > 0): the ratios of the empty side are NaN (0 / 0), z and p are NaN.  Otherwise
+ *   a = |D| / 2.0 - 0.5, raised to 0 when negative (the continuity correction); zz = a / sqrt(var); z = D < 0 ? -zz : zz;
+ *   p = erfc(zz * M_SQRT1_2), two-sided: R's wilcox.test(exact = FALSE, correct = TRUE), scipy's asymptotic method.
+ *
+ * sgl_markers: the per-(g, c) arrays are m x G column-major, gene fastest (a cluster's column is contiguous); group_n has G
+ * values, tie m.  ANY output pointer may be NULL.
+ *  - refused with SGL_EINVAL, nothing launched: NULL labels; n_groups outside [1, 1024]; a transform outside {0, 1}; a
+ *    pseudocount that is negative or not finite; ncol > 2^21; a label outside [-1, G) -- the whole list is checked first,
+ *    the message names position and value.
+ *  - refused with SGL_ESTATE: with no matrix resident, on a team member, with an all-reduce hook set, and on a context that
+ *    holds a shard.  The context stays usable after every refusal.
+ *  - after sgl_upload_dense the call WORKS, over the CSC image that upload keeps.
+ *  - the call only reads: the matrix, a running fit, entry streams and mask lists stay untouched; a fit continued after it
+ *    gives the bits it would have given without it.  The kernels' time counts in the "scale" phase when timing is on.
+ *  - two rank paths: a gene with at most CAP = 2048 included non-zero entries is sorted in LDS by one workgroup; a longer
+ *    one goes through scratch and a segmented radix sort, in batches of whole genes in ascending order (each below 2^31
+ *    entries and the scratch budget, 24 bytes per entry; a gene above the budget is a batch of its own), and is then walked
+ *    in chunks of 1024 positions with the run start and end carried across chunk edges.  64-bit indexing throughout.
+ *  - there is NO team form and NO R shim entry: a team's shards hold different cells, and a gene's ranks need them all. */
+SGL_API int sgl_markers(sgl_ctx* ctx, const int32_t* labels, int32_t n_groups, int transform, double pseudocount, int64_t* group_n,
+                        int64_t* pos, double* sum, int64_t* rank2, uint64_t* tie, double* pct_in, double* pct_out, double* log2fc,
+                        double* z, double* p);
+/* The one-shot form: its own context on the current device, A as a dgCMatrix (t(A) is built on the device); the argument
+ * refusals come before anything is uploaded.  Neither uses nor touches the SINGLET_HIP_CACHE context. */
+SGL_API int sgl_c_markers(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, const int32_t* labels,
+                          int32_t n_groups, int transform, double pseudocount, int64_t* group_n, int64_t* pos, double* sum,
+                          int64_t* rank2, uint64_t* tie, double* pct_in, double* pct_out, double* log2fc, double* z, double* p);
+/* What the last rank pass on this context ran: out[0] the genes sorted in LDS, out[1] the genes on the long path, out[2]
+ * the batches of the long path, out[3] the LDS cap (included non-zero entries). */
+SGL_API int sgl_markers_info(sgl_ctx* ctx, int64_t out[4]);
+
 /* Embedding neighbours: the EXACT n_neighbors nearest reference columns of every query column of a k x n embedding, by
  * brute force in FP64 -- the k-NN step of Seurat's FindNeighbors on the `nmf` reduction (its Jaccard step is sgl_c_snn), and
  * of label transfer after a projection.  The reference's package has no such function (it hands the embedding to Seurat);
@@ -1007,6 +1072,13 @@ SGL_API int sgl_op_gene_mean(sgl_ctx* ctx, double* mean, int64_t* count);
 SGL_API int sgl_op_gene_var(sgl_ctx* ctx, const double* mu, double* var);
 SGL_API int sgl_op_gene_var_std(sgl_ctx* ctx, const double* mu, const double* sd, double vmax, double* out);
 SGL_API int sgl_op_loess_direct(sgl_ctx* ctx, const double* x, const double* y, int64_t n, int64_t q, double* fitted);
+/* The stages of sgl_markers, one at a time (the rules are stated there; the same refusals, the same read-only contract).
+ *  - sgl_op_marker_sums: pos, nz (int64) and sum (double), each nrow x n_groups column-major; any may be NULL.
+ *  - sgl_op_marker_ranks: rank2 (int64, nrow x n_groups) and tie (uint64, nrow); max_batch_entries = the entries of a batch
+ *    of the long path, 0: the default (2^27), negative: SGL_EINVAL.  The results do not depend on it. */
+SGL_API int sgl_op_marker_sums(sgl_ctx* ctx, const int32_t* labels, int32_t n_groups, int transform, int64_t* pos, int64_t* nz, double* sum);
+SGL_API int sgl_op_marker_ranks(sgl_ctx* ctx, const int32_t* labels, int32_t n_groups, int64_t max_batch_entries, int64_t* rank2,
+                                uint64_t* tie);
 /* nnls on ncols independent columns, each against its OWN Gram: Gcols = ncols blocks of k x k, B / X as in sgl_op_nnls;
  * col_nnz (int64 [ncols], or NULL): columns with a zero there are skipped -- X keeps its input, no sweeps are counted.
  * The dispatch of every masked half-step (four columns per wave on LDS triangles or on the Grams in global memory, one

@@ -105,6 +105,13 @@ SIGNATURES = {
     "sgl_c_evaluate": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, f64p, f64p, C.c_int32, f64p, f64p, f64p, f64p]),
     "sgl_variable_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, f64p, i32p, i32p, f64p]),
     "sgl_c_variable_features": (C.c_int, _CSC + [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, f64p, i32p, i32p, f64p]),
+    "sgl_markers": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int, C.c_double, i64p, i64p, f64p, i64p, u64p, f64p, f64p, f64p,
+                              f64p, f64p]),
+    "sgl_c_markers": (C.c_int, _CSC + [C.c_int32, C.c_int32, i32p, C.c_int32, C.c_int, C.c_double, i64p, i64p, f64p, i64p, u64p,
+                                       f64p, f64p, f64p, f64p, f64p]),
+    "sgl_markers_info": (C.c_int, [C.c_void_p, i64p]),
+    "sgl_op_marker_sums": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int, i64p, i64p, f64p]),
+    "sgl_op_marker_ranks": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int64, i64p, u64p]),
     "sgl_knn": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64, f64p, C.c_int64, i32p, C.c_int32, C.c_int32, i32p, f64p]),
     "sgl_c_knn": (C.c_int, [f64p, C.c_int32, C.c_int64, f64p, C.c_int64, i32p, C.c_int32, C.c_int32, i32p, f64p]),
     "sgl_knn_info": (C.c_int, [C.c_void_p, i64p]),

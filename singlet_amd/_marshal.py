@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, f64p, i32p, ptr
+from ._lib import check, f64p, i32p, i64p, ptr, u64p
 
 
 def csc_ptrs(A):
@@ -80,6 +80,44 @@ class ArdOutputs(_FitOutputs):
 
     def result(self):
         return {"w": self.w.T, "d": self.d, "h": self.h.T, **self.traces()}
+
+
+MARKER_TRANSFORMS = {"identity": 0, "expm1": 1, 0: 0, 1: 1}
+
+
+def label_list(labels, n, n_groups):
+    """(int32 labels, G) of sgl_markers: one label in [-1, G) per cell; n_groups None: 1 + the largest label (at least 1).
+    The library checks the range."""
+    g = np.asarray(labels)
+    if g.ndim != 1 or (n is not None and g.shape[0] != n):
+        raise ValueError("labels must hold one cluster id per cell" + ("" if n is None else " (%d)" % n))
+    if g.dtype.kind not in "iub":
+        raise ValueError("labels must hold integer cluster ids (-1: the cell is left out)")
+    if g.size and (g.min() < -2**31 or g.max() >= 2**31):
+        raise ValueError("labels holds an id outside the 32-bit range")
+    g = np.ascontiguousarray(g, dtype=np.int32)
+    G = int(n_groups) if n_groups is not None else max(int(g.max()) + 1 if g.size else 1, 1)
+    return g, G
+
+
+def markers_call(fn, nrow, labels, G, transform, pseudocount):
+    """Shared by Context.markers and api.c_markers: fn(labels, n_groups, transform, pseudocount, group_n, pos, sum, rank2, tie,
+    pct_in, pct_out, log2fc, z, p) is the library call.  Returns the dict of the arrays, the per-(gene, cluster) ones as
+    nrow x G."""
+    if transform not in MARKER_TRANSFORMS:
+        raise ValueError("transform must be 'expm1' or 'identity'")
+    m, Gs = max(int(nrow), 1), max(min(G, 1024), 1)   # outside [1, 1024] the library refuses before it writes
+    group_n = np.zeros(Gs, dtype=np.int64)
+    i64s = {k: np.zeros((Gs, m), dtype=np.int64) for k in ("pos", "rank2")}
+    f64s = {k: np.empty((Gs, m)) for k in ("sum", "pct_in", "pct_out", "log2fc", "z", "p")}
+    tie = np.zeros(m, dtype=np.uint64)
+    check(fn(ptr(labels, i32p), int(G), MARKER_TRANSFORMS[transform], float(pseudocount), ptr(group_n, i64p), ptr(i64s["pos"], i64p),
+             ptr(f64s["sum"], f64p), ptr(i64s["rank2"], i64p), ptr(tie, u64p), ptr(f64s["pct_in"], f64p), ptr(f64s["pct_out"], f64p),
+             ptr(f64s["log2fc"], f64p), ptr(f64s["z"], f64p), ptr(f64s["p"], f64p)))
+    out = {"group_n": group_n, "tie": tie[:int(nrow)]}
+    for k, a in {**i64s, **f64s}.items():
+        out[k] = a[:, :int(nrow)].T
+    return out
 
 
 def knn_call(fn, reference, query, dims, n_neighbors, resident=None):

@@ -27,6 +27,8 @@ names, argument order, defaults and return fields:
                                         exact local fit at every gene, not R's interpolated loess)
   evaluate                              no R counterpart: the full-matrix error of a model (mse_test, src/singlet.cpp:536-568,
                                         with every entry drawn), per cell and per gene
+  find_all_markers / find_markers       Seurat::FindAllMarkers / FindMarkers(test.use = "wilcox") under the rules stated in
+                                        include/singlet_hip.h, "Marker genes" (the filters are applied after the test)
 
 Matrices follow R's orientation: w is returned k x m by c_nmf and m x k by
 run_nmf / ard_nmf (they transpose and sort by d, R/run_nmf.R:65-68); h is
@@ -41,7 +43,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, knn_call
+from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, knn_call, label_list, markers_call
 from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
@@ -1583,3 +1585,96 @@ def find_clusters(graph, resolution=0.8, drop_diagonal=True, tol=1e-7, max_sweep
     last = np.maximum(out["n_levels"], 1) - 1
     return {"clusters": np.ascontiguousarray(out["labels"].T), "modularity": out["q_levels"][np.arange(res.size), last],
             "n_clusters": out["n_clusters"], "levels": out["n_levels"]}
+
+
+# ---------------------------------------------------------------------------
+# Marker genes (Seurat's FindAllMarkers / FindMarkers, Wilcoxon rank-sum test)
+# ---------------------------------------------------------------------------
+def c_markers(A, labels, n_groups=None, transform="expm1", pseudocount=1.0):
+    """The one-shot form of Context.markers (sgl_c_markers): A a dgCMatrix or anything as_dgCMatrix accepts, in a context of
+    its own.  Returns the same dict of arrays."""
+    A = as_dgCMatrix(A)
+    g, G = label_list(labels, A.ncol, n_groups)
+    L = _lib.load()
+    return markers_call(lambda *a: L.sgl_c_markers(*csc_ptrs(A), A.nrow, A.ncol, *a), A.nrow, g, G, transform, pseudocount)
+
+
+def _markers_of(A, labels, n_groups, transform, pseudocount):
+    """(the dict of Context.markers, the row names or None) for whatever find_all_markers takes."""
+    from .context import Context
+    if isinstance(A, Context):
+        return A.markers(labels, n_groups, transform, pseudocount), None
+    if isinstance(A, NativeMatrix):
+        return _on_native(A, lambda ctx, fits: ctx.markers(labels, n_groups, transform, pseudocount)), A.Dimnames[0]
+    A = as_dgCMatrix(A)
+    return c_markers(A, labels, n_groups, transform, pseudocount), A.Dimnames[0]
+
+
+def _marker_table(st, c, names, min_pct, logfc_threshold, only_pos, return_thresh):
+    """The rows of cluster c that pass the filters, in the stated order."""
+    m = st["p"].shape[0]
+    p, fc, p1, p2 = st["p"][:, c], st["log2fc"][:, c], st["pct_in"][:, c], st["pct_out"][:, c]
+    with np.errstate(invalid="ignore"):
+        keep = np.fmax(p1, p2) >= min_pct
+        keep &= (fc >= logfc_threshold) if only_pos else (np.abs(fc) >= logfc_threshold)
+        keep &= p < return_thresh
+    genes = np.nonzero(keep)[0]
+    genes = genes[np.lexsort((genes, -fc[genes], p[genes]))]   # (p_val asc, avg_log2FC desc, gene asc)
+    out = {"gene": genes.astype(np.int32), "p_val": p[genes], "avg_log2FC": fc[genes], "pct_1": p1[genes], "pct_2": p2[genes],
+           "p_val_adj": np.minimum(1.0, p[genes] * m)}
+    if names is not None:
+        out["names"] = _subset_names(names, out["gene"])
+    return out
+
+
+def find_all_markers(A, clusters, min_pct=0.1, logfc_threshold=0.25, only_pos=False, return_thresh=0.01, transform="expm1",
+                     pseudocount=1.0):
+    """Seurat::FindAllMarkers(test.use = "wilcox") on the device: for every cluster, the genes that mark it against all other
+    cells (sgl_markers; the rules are stated in include/singlet_hip.h, "Marker genes").  A: a dgCMatrix, anything
+    as_dgCMatrix accepts, a native(...) object, or a Context that holds the (normally log-normalised) matrix.  clusters: one
+    id >= 0 per cell, -1 leaves the cell out.  Returns a list with one dict per cluster: "cluster", "gene" (int32 row
+    indices), "names" (when A has row names), "p_val", "avg_log2FC", "pct_1", "pct_2", "p_val_adj" = min(1, p * nrow).
+    The filters -- max(pct_1, pct_2) >= min_pct; |avg_log2FC| >= logfc_threshold (avg_log2FC >= it with only_pos);
+    p_val < return_thresh -- are applied AFTER the test, to all genes; Seurat filters by pct and fold change BEFORE it tests:
+    the retained rows are the same.  Rows are ordered by (p_val ascending, avg_log2FC descending, gene ascending)."""
+    st, names = _markers_of(A, clusters, None, transform, pseudocount)
+    out = []
+    for c in range(st["group_n"].shape[0]):
+        t = _marker_table(st, c, names, min_pct, logfc_threshold, only_pos, return_thresh)
+        t["cluster"] = c
+        out.append(t)
+    return out
+
+
+def find_markers(A, cells_1, cells_2=None, min_pct=0.1, logfc_threshold=0.25, only_pos=False, return_thresh=0.01,
+                 transform="expm1", pseudocount=1.0):
+    """Seurat::FindMarkers(ident.1, ident.2): the cells cells_1 (indices or a boolean mask) against cells_2 (None: all other
+    cells), through the labels {0, 1, -1} of sgl_markers.  Returns the table of group 0 as find_all_markers lays it out."""
+    from .context import Context
+    if isinstance(A, Context):
+        n = A.dims()[1]
+    else:
+        if not isinstance(A, NativeMatrix):
+            A = as_dgCMatrix(A)
+        n = A.ncol
+
+    def mask(cells, what):
+        c = np.asarray(cells)
+        if c.dtype.kind == "b":
+            if c.shape != (n,):
+                raise ValueError("find_markers: a boolean %s needs one entry per cell (%d)" % (what, n))
+            return c.copy()
+        if c.ndim != 1 or c.dtype.kind not in "iu" or (c.size and (c.min() < 0 or c.max() >= n)):
+            raise ValueError("find_markers: %s must hold cell indices in [0, %d)" % (what, n))
+        mk = np.zeros(n, dtype=bool)
+        mk[c] = True
+        return mk
+    m1 = mask(cells_1, "cells_1")
+    m2 = ~m1 if cells_2 is None else mask(cells_2, "cells_2")
+    if np.any(m1 & m2):
+        raise ValueError("find_markers: a cell is in both groups")
+    labels = np.full(n, -1, dtype=np.int32)
+    labels[m2] = 1
+    labels[m1] = 0
+    st, names = _markers_of(A, labels, 2, transform, pseudocount)
+    return _marker_table(st, 0, names, min_pct, logfc_threshold, only_pos, return_thresh)

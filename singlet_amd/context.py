@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
-from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, knn_call
+from ._marshal import MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, knn_call, label_list, markers_call
 from .sparse import as_dgCMatrix
 
 SYNTH_SEED = 0x5EED
@@ -485,6 +485,22 @@ class Context(_Handle):
         nr, _, _ = self.dims()
         return _variable_features_call(lambda *a: self._L.sgl_variable_features(self._h, *a), nr, nfeatures, span, vmax, expected_var)
 
+    def markers(self, labels, n_groups=None, transform="expm1", pseudocount=1.0):
+        """The one-vs-rest Wilcoxon rank-sum test of every gene against every cluster of the resident matrix (sgl_markers;
+        the rules are stated in include/singlet_hip.h, "Marker genes").  labels: one cluster id in [-1, G) per cell, -1
+        leaves the cell out; n_groups None: 1 + the largest label.  transform: "expm1" (Seurat's mean of log-normalised
+        data) or "identity".  Returns {"group_n" (G), "tie" (m), and m x G arrays "pos", "sum", "rank2", "pct_in",
+        "pct_out", "log2fc", "z", "p"}.  The matrix and a running fit are only read."""
+        nr, nc, _ = self.dims()
+        g, G = label_list(labels, nc or None, n_groups)   # (no matrix: the library refuses)
+        return markers_call(lambda *a: self._L.sgl_markers(self._h, *a), nr, g, G, transform, pseudocount)
+
+    def markers_info(self):
+        """What the last rank pass on this context ran (sgl_markers_info): {"lds_genes", "long_genes", "batches", "lds_cap"}."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._L.sgl_markers_info(self._h, ptr(out, i64p)))
+        return dict(zip(("lds_genes", "long_genes", "batches", "lds_cap"), (int(v) for v in out)))
+
     def knn(self, n_neighbors=20, reference=None, query=None, dims=None):
         """Exact nearest neighbours in an embedding (sgl_knn): (idx, dist), each n_query x n_neighbors, row j = the
         n_neighbors nearest reference columns of query column j in rank order -- by (squared distance, index), ties to
@@ -694,6 +710,27 @@ class Context(_Handle):
         out = np.empty(max(x.shape[0], 1))
         check(self._L.sgl_op_loess_direct(self._h, ptr(x, f64p), ptr(y, f64p), x.shape[0], int(q), ptr(out, f64p)))
         return out[:x.shape[0]]
+
+    # the stages of markers, one at a time
+    def op_marker_sums(self, labels, n_groups=None, transform="expm1"):
+        """(pos, nz, sum), each m x G, of the resident matrix under the labels (sgl_op_marker_sums)."""
+        nr, nc, _ = self.dims()
+        g, G = label_list(labels, nc or None, n_groups)   # (no matrix: the library refuses)
+        if transform not in MARKER_TRANSFORMS:
+            raise ValueError("transform must be 'expm1' or 'identity'")
+        shape = (max(min(G, 1024), 1), max(nr, 1))
+        pos, nz, s = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64), np.empty(shape)
+        check(self._L.sgl_op_marker_sums(self._h, ptr(g, i32p), G, MARKER_TRANSFORMS[transform], ptr(pos, i64p), ptr(nz, i64p), ptr(s, f64p)))
+        return pos[:, :nr].T, nz[:, :nr].T, s[:, :nr].T
+
+    def op_marker_ranks(self, labels, n_groups=None, max_batch_entries=0):
+        """(rank2 m x G, tie m) of the resident matrix under the labels (sgl_op_marker_ranks); max_batch_entries 0: the default."""
+        nr, nc, _ = self.dims()
+        g, G = label_list(labels, nc or None, n_groups)   # (no matrix: the library refuses)
+        rank2 = np.zeros((max(min(G, 1024), 1), max(nr, 1)), dtype=np.int64)
+        tie = np.zeros(max(nr, 1), dtype=np.uint64)
+        check(self._L.sgl_op_marker_ranks(self._h, ptr(g, i32p), G, int(max_batch_entries), ptr(rank2, i64p), ptr(tie, u64p)))
+        return rank2[:, :nr].T, tie[:nr]
 
     def op_rhs_masked(self, which, F, seed, inv_density):
         """op_rhs with the entries the mask (seed, inv_density) draws left out (sgl_op_rhs_masked): which = 0 / 1 hash every

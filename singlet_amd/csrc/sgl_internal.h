@@ -244,6 +244,7 @@ struct sgl_ctx {
     int64_t wave_sweeps_acc[2] = {0, 0};
     double* pinned = nullptr;        // host pinned scratch (8 doubles)
     int64_t knn_last[4] = {0, 0, 0, 0};   // sgl_knn_info: instance, segments, queries per workgroup, list home of the last sgl_knn
+    int64_t markers_last[4] = {0, 0, 0, 0};   // sgl_markers_info: genes sorted in LDS, long genes, batches, the LDS cap of the last rank pass
 
     sgl_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
@@ -446,6 +447,17 @@ int sgl_hvg_args_check(const char* who, int32_t nrow, int32_t ncol, int32_t nfea
                        const int32_t* features, const int32_t* n_out);
 int sgl_hvg_select(sgl_ctx* c, int32_t nfeatures, double span, double vmax, const double* expected_var, int32_t* features,
                    int32_t* n_out, double* info);   // the composite after its refusals
+
+// marker genes (kernels_markers.hip; include/singlet_hip.h, "Marker genes").  All arrays are the HOST's; every call only reads the
+// context, allocates its own temporaries and synchronises the stream before it returns.
+int sgl_markers_args_check(const char* who, const int32_t* labels, int64_t ncol, int32_t n_groups, int transform, double pseudocount);
+// the device passes over c->At (labels checked before): the group sums with their counts (`sums`) and / or the rank pass
+// (`ranks`; max_batch_entries <= 0: the default); m x G column-major outputs, any may be NULL
+int sgl_markers_core(sgl_ctx* c, const int32_t* labels, int32_t G, int transform, int64_t max_batch_entries, bool sums, bool ranks,
+                     int64_t* group_n, int64_t* pos, int64_t* nz, double* sum, int64_t* rank2, uint64_t* tie);
+// both passes and the derived statistics (markers_host.h)
+int sgl_markers_all(sgl_ctx* c, const int32_t* labels, int32_t G, int transform, double pseudocount, int64_t* group_n, int64_t* pos,
+                    double* sum, int64_t* rank2, uint64_t* tie, double* pct_in, double* pct_out, double* log2fc, double* z, double* p);
 
 // row-wise rasterisation (kernels_raster.hip): out (nb x ncol, column-major) = means of rows [b n, b n + n), nb >= 1
 int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, double* out);

@@ -1937,6 +1937,46 @@ extern "C" int sgl_c_variable_features(const double* Ax, const int32_t* Ai, cons
     return sgl_variable_features(hd.c, nfeatures, span, vmax, expected_var, features, n_out, info);
 }
 
+// Marker genes (include/singlet_hip.h; kernels_markers.hip): the refusals, then passes that only read the context.
+static int markers_state(sgl_ctx* c, const char* who) {
+    if (c->team || c->allreduce) {
+        sgl_set_error("%s: the context is a shard of a team or has an all-reduce hook; the ranks of this shard's cells are not the matrix's", who);
+        return SGL_ESTATE;
+    }
+    if (!c->A.p || !c->At.p) { sgl_set_error("%s: no matrix resident", who); return SGL_ESTATE; }
+    if (c->cell_offset != 0 || c->ncells_total != (int64_t)c->A.ncol) {
+        sgl_set_error("%s: the context holds a shard (cells %lld .. %lld of %lld); test on the whole matrix", who,
+                      (long long)c->cell_offset, (long long)c->cell_offset + c->A.ncol, (long long)c->ncells_total);
+        return SGL_ESTATE;
+    }
+    return SGL_OK;
+}
+extern "C" int sgl_markers(sgl_ctx* c, const int32_t* labels, int32_t n_groups, int transform, double pseudocount, int64_t* group_n,
+                           int64_t* pos, double* sum, int64_t* rank2, uint64_t* tie, double* pct_in, double* pct_out, double* log2fc,
+                           double* z, double* p) {
+    CTX_GUARD(c);
+    SGLCHK(markers_state(c, "sgl_markers"));
+    SGLCHK(sgl_markers_args_check("sgl_markers", labels, c->A.ncol, n_groups, transform, pseudocount));
+    return sgl_markers_all(c, labels, n_groups, transform, pseudocount, group_n, pos, sum, rank2, tie, pct_in, pct_out, log2fc, z, p);
+}
+
+extern "C" int sgl_c_markers(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, const int32_t* labels,
+                             int32_t n_groups, int transform, double pseudocount, int64_t* group_n, int64_t* pos, double* sum,
+                             int64_t* rank2, uint64_t* tie, double* pct_in, double* pct_out, double* log2fc, double* z, double* p) {
+    SGLCHK(sgl_markers_args_check("sgl_c_markers", labels, std::max(ncol, 0), n_groups, transform, pseudocount));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, nullptr, nullptr, nullptr, nrow, ncol, 0, ncol));
+    return sgl_markers(hd.c, labels, n_groups, transform, pseudocount, group_n, pos, sum, rank2, tie, pct_in, pct_out, log2fc, z, p);
+}
+
+extern "C" int sgl_markers_info(sgl_ctx* c, int64_t out[4]) {
+    CTX_GUARD(c);
+    if (!out) { sgl_set_error("sgl_markers_info: NULL out"); return SGL_EINVAL; }
+    std::copy(c->markers_last, c->markers_last + 4, out);
+    return SGL_OK;
+}
+
 // c_gcnmf's cell graph G (src/singlet.cpp:1668-1730): n x n, n = the cells of the resident matrix, as a dgCMatrix.  Checked
 // on the host (the kernels index factor columns by its rows): p[0] = 0 and monotone, rows strictly ascending within a column
 // and in [0, n), values finite.  Columns above SGL_GRAPH_HUB entries get their segment lists here (kernels_graph.hip).
@@ -2409,6 +2449,22 @@ extern "C" int sgl_op_loess_direct(sgl_ctx* c, const double* x, const double* y,
             return SGL_EINVAL;
         }
     return sgl_loess_direct(c, x, y, n, q, fitted);
+}
+
+// The stages of sgl_markers one at a time (kernels_markers.hip)
+extern "C" int sgl_op_marker_sums(sgl_ctx* c, const int32_t* labels, int32_t n_groups, int transform, int64_t* pos, int64_t* nz, double* sum) {
+    CTX_GUARD(c);
+    SGLCHK(markers_state(c, "sgl_op_marker_sums"));
+    SGLCHK(sgl_markers_args_check("sgl_op_marker_sums", labels, c->A.ncol, n_groups, transform, 0.0));
+    return sgl_markers_core(c, labels, n_groups, transform, 0, true, false, nullptr, pos, nz, sum, nullptr, nullptr);
+}
+extern "C" int sgl_op_marker_ranks(sgl_ctx* c, const int32_t* labels, int32_t n_groups, int64_t max_batch_entries, int64_t* rank2,
+                                   uint64_t* tie) {
+    CTX_GUARD(c);
+    SGLCHK(markers_state(c, "sgl_op_marker_ranks"));
+    SGLCHK(sgl_markers_args_check("sgl_op_marker_ranks", labels, c->A.ncol, n_groups, 0, 0.0));
+    if (max_batch_entries < 0) { sgl_set_error("sgl_op_marker_ranks: max_batch_entries = %lld is negative", (long long)max_batch_entries); return SGL_EINVAL; }
+    return sgl_markers_core(c, labels, n_groups, 0, max_batch_entries, false, true, nullptr, nullptr, nullptr, nullptr, rank2, tie);
 }
 
 // k_nnls_percol with a Gram per column (gstride = k * k), as every masked half-step calls it
