@@ -832,6 +832,82 @@ SGL_API int sgl_op_louvain_sweep(const double* Gx, const int32_t* Gi, const int3
  * its first sweep leaves [1] .. [3] as they were. */
 SGL_API int sgl_louvain_info(int64_t out[4]);
 
+/* Layout: the 2-D (or up to 8-D) picture of the cells -- the last step of the vignette's pipe, RunUMAP(reduction = "nmf"):
+ * the fuzzy neighbour graph of the k-NN lists, then a force-directed layout of it.  The reference's package has no layout
+ * code (it hands the embedding to Seurat / uwot), and the published optimiser is racy (hogwild SGD) and sequential per edge,
+ * so the rules below are this library's own: a SYNCHRONOUS, OWNER-COMPUTES form of it, stated in full;
+ * tests/umap_restatement.py restates them in numpy.  Every result is one function of its inputs.  No parity of coordinates
+ * with uwot or umap-learn is claimed (DESIGN.md "Layout").  One-shot on the current device; no team form, no R shim entry.
+ * All arithmetic is FP64, every product and addition its own rounding (the unit is compiled with -ffp-contract=off).
+ *
+ * 1. sgl_c_fuzzy_graph.  Input: what sgl_knn returns for n cells: idx int32 and dist double (the roots), both K x n
+ * column-major (the list of cell j at idx + j K, ranked ascending).  The cell itself is usually first in its list, but not
+ * when K identical columns precede it.  Output: an n x n dgCMatrix, rows ascending within a column, no diagonal, pattern and
+ * values bitwise symmetric (what sgl_c_louvain demands), in the two calls of sgl_c_snn: i_out == NULL counts (p_out and
+ * *nnz_out are filled), the second call gets i_out / x_out of at least cap >= *nnz_out entries.  rho_out / sigma_out
+ * (double[n], may be NULL) receive rho and sigma.
+ *  - own list of cell j: its K candidates without the one whose index is j, if present, in list order.
+ *  - rho_j = the smallest distance > 0 of the own list, 0 when there is none.
+ *  - sigma_j: bisection on psum(s) = the sum over the own list, in list order from +0.0, of
+ *    (d - rho_j > 0 ? exp(-(d - rho_j) / s) : 1.0), against log2(K).  lo = 0, hi = +Inf, mid = 1; a step: psum(mid) > log2(K)
+ *    sets hi = mid and mid = (lo + hi) / 2; otherwise lo = mid, and mid = 2 mid while hi is infinite, else (lo + hi) / 2.
+ *    EXACTLY 64 steps, no early exit (the bracket is then below an ulp, so an ulp of exp cannot send two implementations
+ *    down different branches for long).  Then sigma_j = max(mid, 1e-3 * mean), mean = (the sum of the own list's distances in
+ *    list order from +0.0) / (their number) when rho_j > 0, else the mean of all n K input distances: their blocked sum in
+ *    memory order (blocks of 1024 consecutive terms, as in Clustering) / (n K).
+ *  - membership p_ji = 1.0 when d_ji - rho_j <= 0, else exp(-(d_ji - rho_j) / sigma_j).
+ *  - w_ij = (p_ij + p_ji) - p_ij * p_ji with an absent direction read as +0.0: the sum and the product commute, so the
+ *    result is bitwise symmetric.  Entries equal to 0 are dropped.
+ *  - refused with SGL_EINVAL and a message, on the host, before anything is launched and with every output untouched: K
+ *    outside [2, 256]; n outside [1, 2^31); and, named by cell and place, the first of: an index outside [0, n), an index
+ *    repeated in its list, a distance that is not finite, a negative distance, a distance below the one before it.  A graph of
+ *    2^31 entries or more is refused after the count, outputs untouched.
+ *  - kernels (singlet_amd/csrc/kernels_umap.hip; the host logic without HIP in umap_host.h): one thread per cell computes
+ *    rho, sigma and the memberships; the incoming lists come from a counting transpose (integer histogram, scan, cursor
+ *    fill); one wave per vertex sorts the keys of its own and incoming entries in LDS, up to 512 keys per vertex (the LDS
+ *    merge); a vertex with more (a hub: the in-degree is unbounded) takes the fallback, a segmented radix sort in HBM.
+ *    Integer atomics only.
+ *
+ * 2. sgl_c_umap_layout.  Input: a graph G as above -- validated on the host: rows in [0, n) and ascending within a column,
+ * weights finite and >= 0; symmetry is NOT required; a diagonal entry is skipped (it never fires) -- Y0 (dim x n
+ * column-major, finite, dim in [1, 8]); a, b finite and > 0; n_epochs in [1, 2^20]; alpha0 finite and > 0; neg_rate in
+ * [0, 255]; seed.  n in [1, 2^31).  Anything else is SGL_EINVAL with a message, before anything is launched.  Output: Y
+ * (dim x n).  The positions live in two buffers that swap per epoch: an epoch reads the positions of its start only.
+ *  - firing: r_e = w_e / w_max, one division, w_max the exact maximum stored weight.  Entry e fires in epoch t (1-based) iff
+ *    floor(t * r_e) > floor((t - 1) * r_e): stateless, and an edge below w_max / n_epochs never fires.  w_max == 0: Y = Y0.
+ *  - head and tail: column j is the head, the stored row i the tail; only the head moves (a symmetric graph stores the other
+ *    direction too).
+ *  - a term of head j against a point o: d_f = y_j,f - y_o,f; d2 = the sum of d_f * d_f over f ascending from +0.0;
+ *    p = d2 when b == 1.0 exactly, else pow(d2, b).  Attractive (o = the tail): c = (m2ab * (p / d2)) / (a * p + 1.0) with
+ *    m2ab = -2.0 * a * b, when d2 > 0; else the term is +0.0.  Repulsive (o = a negative sample m):
+ *    c = tb / ((0.001 + d2) * (a * p + 1.0)) with tb = 2.0 * b.  Component f of the term is fmin(fmax(c * d_f, -4.0), 4.0).
+ *    A repulsive term with d2 == 0 and m != j has all components +4.0; a sample with m == j contributes +0.0.
+ *  - negative samples of a firing entry: for s = 0 .. neg_rate - 1, u = rand(seed, e, 256 t + s) -- the hash of the mask,
+ *    e the entry's position in Gx -- and m = ((u >> 32) * (uint64) n) >> 32: integers only.
+ *  - orders: g_e = attractive + neg_0 + ... + neg_last, sequentially; delta_j = the sequential sum of g_e over the firing
+ *    entries of column j in stored order, from +0.0; y_j' = y_j + alpha_t * delta_j, a product then an addition, with
+ *    alpha_t = alpha0 * (1.0 - (t - 1) / n_epochs).  A vertex without a firing entry keeps the bits of y_j.
+ *  - kernel: one launch per epoch, one wave per vertex; the column is taken in steps of 64 stored entries, a ballot compacts
+ *    the firing entries and the (entry, term) pairs are spread over the lanes, so only firing entries pay for pow; lane
+ *    f < dim adds component f in the stated order and carries the sums from step to step (no slow path for wide columns).
+ *    Instances: 2 * (0: dim 2, 1: dim 3, 2: the generic loop up to 8) + (1 when b == 1.0).  Each y is written once; no
+ *    floating-point atomics.
+ *  - what holds: with b == 1.0 no transcendental is left and the device equals the restatement bit for bit; otherwise the
+ *    two differ by the ulps of pow. */
+SGL_API int sgl_c_fuzzy_graph(const int32_t* idx, const double* dist, int64_t n, int32_t K, int32_t* p_out, int64_t* nnz_out,
+                              int32_t* i_out, double* x_out, int64_t cap, double* rho_out, double* sigma_out);
+SGL_API int sgl_c_umap_layout(const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const double* Y0, int32_t dim,
+                              double a, double b, int32_t n_epochs, double alpha0, int32_t neg_rate, uint64_t seed, double* Y);
+/* Stage operator: ONE epoch t in [1, n_epochs] from the positions Yin -> Y, with the layout's validation and rules. */
+SGL_API int sgl_op_umap_epoch(const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const double* Yin, int32_t dim,
+                              double a, double b, int32_t n_epochs, double alpha0, int32_t neg_rate, uint64_t seed, int32_t t,
+                              double* Y);
+/* What the last calls of this process ran: out[0] the layout's kernel instance (-1 before the first layout), [1] the widest
+ * column (stored entries) and [2] the vertices that needed more than one step of 64 entries in the last sgl_c_umap_layout
+ * or sgl_op_umap_epoch; [3] the vertices of the last sgl_c_fuzzy_graph that took the LDS merge's fallback.  A refused call
+ * leaves them as they were. */
+SGL_API int sgl_umap_info(int64_t out[4]);
+
 /* Cell graph of c_gcnmf for the current fit (after sgl_fit_init, which drops
  * it again; all-NULL slots clear it).  G is an n x n dgCMatrix, n = the cells of
  * the resident matrix; an invalid G is SGL_EINVAL with a message.  While it is

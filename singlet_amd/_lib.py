@@ -118,6 +118,12 @@ SIGNATURES = {
     "sgl_c_louvain": (C.c_int, _CSC + [C.c_int32, f64p, C.c_int32, C.c_double, C.c_int32, C.c_int32, i32p, i32p, i32p, f64p, i32p]),
     "sgl_op_louvain_sweep": (C.c_int, _CSC + [C.c_int32, i32p, C.c_double, i32p, f64p, f64p, i64p]),
     "sgl_louvain_info": (C.c_int, [i64p]),
+    "sgl_c_fuzzy_graph": (C.c_int, [i32p, f64p, C.c_int64, C.c_int32, i32p, i64p, i32p, f64p, C.c_int64, f64p, f64p]),
+    "sgl_c_umap_layout": (C.c_int, _CSC + [C.c_int32, f64p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32,
+                                           C.c_uint64, f64p]),
+    "sgl_op_umap_epoch": (C.c_int, _CSC + [C.c_int32, f64p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32,
+                                           C.c_uint64, C.c_int32, f64p]),
+    "sgl_umap_info": (C.c_int, [i64p]),
     "sgl_set_graph": (C.c_int, [C.c_void_p, f64p, i32p, i32p, C.c_int32, C.c_int32]),
     "sgl_set_allreduce": (C.c_int, [C.c_void_p, ALLREDUCE_FN, C.c_void_p]),
     "sgl_step_begin": (C.c_int, [C.c_void_p]),

@@ -1588,6 +1588,185 @@ def find_clusters(graph, resolution=0.8, drop_diagonal=True, tol=1e-7, max_sweep
 
 
 # ---------------------------------------------------------------------------
+# Layout (Seurat's RunUMAP on the nmf reduction; the rules are this library's own: include/singlet_hip.h, "Layout")
+# ---------------------------------------------------------------------------
+def fuzzy_simplicial_set(idx, dist, return_sigmas=False):
+    """sgl_c_fuzzy_graph: the fuzzy neighbour graph of k-NN lists as knn returns them (idx, dist: n x K, row j the candidates
+    of cell j in rank order) -> the symmetric n x n dgCMatrix (rows ascending, no diagonal, bitwise symmetric: what c_louvain
+    and umap_layout take); with return_sigmas also (rho, sigma)."""
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    dist = np.ascontiguousarray(dist, dtype=np.float64)
+    if idx.ndim != 2 or idx.shape != dist.shape:
+        raise ValueError("fuzzy_simplicial_set: idx and dist must both be n x K")
+    n, K = idx.shape
+    L = _lib.load()
+    rho, sigma = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    p, i, x = _two_call(lambda po, no, io, xo, cap: L.sgl_c_fuzzy_graph(ptr(idx, i32p), ptr(dist, f64p), n, K, po, no, io, xo, cap,
+                                                                         ptr(rho, f64p), ptr(sigma, f64p)), n)
+    G = dgCMatrix(x, i, p, (n, n))
+    return (G, rho[:n], sigma[:n]) if return_sigmas else G
+
+
+def _layout_args(G, Y, what):
+    G = _square_graph(G, what)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if Y.ndim != 2 or Y.shape[0] != G.ncol:
+        raise ValueError("%s: the positions must be n x dim with one row per vertex of the graph" % what)
+    return G, Y
+
+
+def umap_layout(G, Y0, a, b, n_epochs, alpha0=1.0, neg_rate=5, seed=42):
+    """sgl_c_umap_layout: n_epochs synchronous epochs on the graph G from the positions Y0 (n x dim) -> Y (n x dim)."""
+    G, Y0 = _layout_args(G, Y0, "umap_layout")
+    Y = np.empty_like(Y0)
+    check(_lib.load().sgl_c_umap_layout(ptr(G.x, f64p), ptr(G.i, i32p), ptr(G.p, i32p), G.ncol, ptr(Y0, f64p), Y0.shape[1], float(a),
+                                        float(b), int(n_epochs), float(alpha0), int(neg_rate), int(seed), ptr(Y, f64p)))
+    return Y
+
+
+def op_umap_epoch(G, Y, a, b, n_epochs, t, alpha0=1.0, neg_rate=5, seed=42):
+    """sgl_op_umap_epoch: the ONE epoch t (1-based) of a layout of n_epochs epochs, from the positions Y -> the new positions."""
+    G, Y = _layout_args(G, Y, "op_umap_epoch")
+    out = np.empty_like(Y)
+    check(_lib.load().sgl_op_umap_epoch(ptr(G.x, f64p), ptr(G.i, i32p), ptr(G.p, i32p), G.ncol, ptr(Y, f64p), Y.shape[1], float(a),
+                                        float(b), int(n_epochs), float(alpha0), int(neg_rate), int(seed), int(t), ptr(out, f64p)))
+    return out
+
+
+def umap_info():
+    """sgl_umap_info: what the last layout and the last fuzzy graph of this process ran."""
+    out = np.zeros(4, dtype=np.int64)
+    check(_lib.load().sgl_umap_info(ptr(out, _lib.i64p)))
+    return dict(zip(("instance", "widest_column", "multi_chunk", "merge_fallback"), (int(v) for v in out)))
+
+
+def find_ab_params(spread=1.0, min_dist=0.3):
+    """(a, b) of the layout's curve 1 / (1 + a x^(2b)): the least-squares fit to umap-learn's target -- 1 up to min_dist,
+    exp(-(x - min_dist) / spread) beyond -- on linspace(0, 3 spread, 300), by Levenberg-Marquardt from (1, 1)."""
+    spread, min_dist = float(spread), float(min_dist)
+    if not (spread > 0 and np.isfinite(spread)) or not (min_dist >= 0 and np.isfinite(min_dist)):
+        raise ValueError("find_ab_params: spread must be > 0 and min_dist >= 0")
+    x = np.linspace(0.0, 3.0 * spread, 300)
+    y = np.where(x < min_dist, 1.0, np.exp(-(x - min_dist) / spread))
+    lx = np.log(np.where(x > 0, x, 1.0))
+
+    def model(q):
+        u = np.where(x > 0, np.exp(2.0 * q[1] * lx), 0.0)   # x^(2b)
+        return u, 1.0 / (1.0 + q[0] * u)
+
+    q = np.array([1.0, 1.0])
+    u, f = model(q)
+    r = f - y
+    ss, lam = float(r @ r), 1e-3
+    for _ in range(500):
+        J = np.stack([-u * f * f, -q[0] * u * 2.0 * lx * f * f], axis=1)
+        A, g = J.T @ J, J.T @ r
+        step = np.linalg.solve(A + lam * np.diag(np.diag(A)), -g)
+        q2 = q + step
+        if q2[0] > 0 and q2[1] > 0:
+            u2, f2 = model(q2)
+            r2 = f2 - y
+            ss2 = float(r2 @ r2)
+        else:
+            ss2 = np.inf
+        if ss2 <= ss:
+            small = np.max(np.abs(step) / np.abs(q2)) < 1e-14
+            q, u, f, r, ss, lam = q2, u2, f2, r2, ss2, max(lam / 10.0, 1e-12)
+            if small:
+                break
+        else:
+            lam *= 10.0
+            if lam > 1e12:
+                break
+    return float(q[0]), float(q[1])
+
+
+def _rand2(state, i, j):
+    """The library's counter hash (sgl_op_rand) on numpy uint64 arrays: the bits the device and the oracle give."""
+    M = np.uint64
+    with np.errstate(over="ignore"):
+        i = np.asarray(i, dtype=M).copy()
+        j = np.asarray(j, dtype=M).copy()
+        i ^= i << M(19)
+        i ^= i >> M(7)
+        i ^= i << M(36)
+        x = M(state) + i
+        x ^= x << M(38)
+        x ^= x >> M(13)
+        x ^= x << M(23)
+        j ^= j >> M(7)
+        j ^= j << M(23)
+        j ^= j >> M(8)
+        x = x + j
+        x ^= x >> M(7)
+        x ^= x << M(53)
+        x ^= x >> M(4)
+    return x
+
+
+def _umap_init(E, n_components, init, seed):
+    """The start positions (n x n_components) of run_umap from the k x n embedding E."""
+    k, n = E.shape
+    if isinstance(init, str):
+        if init == "pca":
+            if n_components > k:
+                raise ValueError("run_umap: init='pca' gives at most %d components" % k)
+            Ec = E - E.mean(axis=1, keepdims=True)
+            lam, V = np.linalg.eigh(Ec @ Ec.T)                   # the k x k Gram on the host
+            V = V[:, np.argsort(-lam, kind="stable")[:n_components]]
+            top = np.argmax(np.abs(V), axis=0)
+            V = V * np.where(V[top, np.arange(V.shape[1])] < 0, -1.0, 1.0)   # the largest-magnitude loading is positive
+            Y = (V.T @ Ec).T
+            m = np.max(np.abs(Y)) if Y.size else 0.0
+            return np.ascontiguousarray(Y * (10.0 / m)) if m > 0 else np.ascontiguousarray(Y)
+        if init == "random":
+            c, f = np.meshgrid(np.arange(n, dtype=np.uint64), np.arange(n_components, dtype=np.uint64), indexing="ij")
+            u = _rand2(int(seed) & (2**64 - 1), c, f)
+            return (u >> np.uint64(11)).astype(np.float64) * (20.0 / 2.0**53) - 10.0
+        raise ValueError("run_umap: init must be 'pca', 'random' or an n x n_components array")
+    Y = np.ascontiguousarray(init, dtype=np.float64)
+    if Y.shape != (n, n_components):
+        raise ValueError("run_umap: the init array must be %d x %d" % (n, n_components))
+    return Y
+
+
+def run_umap(embedding, n_neighbors=30, n_components=2, min_dist=0.3, spread=1.0, n_epochs=None, learning_rate=1.0,
+             negative_sample_rate=5, init="pca", seed=42, dims=None, return_graph=False):
+    """The numeric steps of Seurat's RunUMAP(reduction = "nmf") on the device: exact k-NN, the fuzzy neighbour graph, and
+    the synchronous layout (include/singlet_hip.h, "Layout").  `embedding` is k x n (R's orientation, one column per cell, as
+    knn takes it) or a Context with a fit, whose H is searched where it lies; dims: 0-based rows.  n_epochs None: 500 up to
+    10 000 cells, 200 above.  init: "pca" (the top components of the centred embedding, each signed so that its
+    largest-magnitude loading is positive, scaled to max |y| = 10), "random" (uniform in [-10, 10) from the hash of
+    (seed, cell, component)) or an n x n_components array.  Returns the n x n_components positions, with return_graph
+    (positions, graph).  Euclidean only; no parity of coordinates with uwot or umap-learn is claimed."""
+    from .context import Context
+    if isinstance(embedding, Context):
+        ctx = embedding
+        E = np.ascontiguousarray(ctx.get_factors(w=False, d=False, h=True)[2].T)
+    else:
+        ctx, E = None, np.asarray(embedding, dtype=np.float64)
+        if E.ndim != 2:
+            raise ValueError("run_umap: embedding must be a k x n matrix or a Context")
+    d0 = None
+    if dims is not None:
+        d0 = np.atleast_1d(np.asarray(dims))
+        if d0.ndim != 1 or d0.dtype.kind not in "iu" or d0.size == 0 or d0.min() < 0 or d0.max() >= E.shape[0]:
+            raise ValueError("run_umap: dims must be 0-based rows of the embedding")
+    n = E.shape[1]
+    n_components = int(n_components)
+    if not 1 <= n_components <= 8:
+        raise ValueError("run_umap: n_components must lie in [1, 8]")
+    if n_epochs is None:
+        n_epochs = 500 if n <= 10000 else 200
+    a, b = find_ab_params(spread, min_dist)
+    Y0 = _umap_init(E if d0 is None else E[d0], n_components, init, seed)
+    idx, dist = ctx.knn(int(n_neighbors), dims=d0) if ctx is not None else knn(E, None, int(n_neighbors), d0)
+    G = fuzzy_simplicial_set(idx, dist)
+    Y = umap_layout(G, Y0, a, b, n_epochs, learning_rate, negative_sample_rate, int(seed) & (2**64 - 1))
+    return (Y, G) if return_graph else Y
+
+
+# ---------------------------------------------------------------------------
 # Marker genes (Seurat's FindAllMarkers / FindMarkers, Wilcoxon rank-sum test)
 # ---------------------------------------------------------------------------
 def c_markers(A, labels, n_groups=None, transform="expm1", pseudocount=1.0):
