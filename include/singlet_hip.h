@@ -315,7 +315,11 @@ SGL_API int sgl_create(int device, sgl_ctx** out);
 SGL_API int sgl_destroy(sgl_ctx* ctx);
 /* Launch all work of this context on `hip_stream` (a hipStream_t; NULL = the
  * context's own stream).  Lets a host that owns a stream (torch's current
- * stream) order collectives against the kernels without host syncs. */
+ * stream) order collectives against the kernels without host syncs.
+ * Handle 0 / NULL = the private stream: the null stream (torch's default
+ * stream) cannot be chosen, and the private stream is created non-blocking,
+ * so it is not ordered against the null stream either.  A hook on the private
+ * stream must have finished its writes when it returns (sgl_allreduce_fn). */
 SGL_API int sgl_set_stream(sgl_ctx* ctx, void* hip_stream);
 
 /* Upload a shard: columns [cell_offset, cell_offset + ncol) of a genes x

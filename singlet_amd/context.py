@@ -523,6 +523,10 @@ class Context(_Handle):
         return dict(zip(("instance", "segments", "queries_per_workgroup", "lists_global"), (int(v) for v in out)))
 
     def set_stream(self, stream_ptr):
+        """Launch all work of this context on the HIP stream with this handle (sgl_set_stream; e.g. the cuda_stream of a
+        torch.cuda.Stream); host reads wait for it, and an all-reduce hook enqueues on it without a host sync.  Handle 0 /
+        None = the context's private stream -- torch's default stream, whose handle is 0, cannot be chosen --, and a hook
+        on the private stream must have finished its writes when it returns."""
         check(self._L.sgl_set_stream(self._h, C.c_void_p(stream_ptr) if stream_ptr else None))
 
     def set_allreduce(self, fn):

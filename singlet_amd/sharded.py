@@ -70,7 +70,13 @@ def torch_allreduce_hook(dist, device, group=None):
     """All-reduce hook for singlet_amd.Context.set_allreduce: sums `count` doubles at a device
     pointer over the default process group (RCCL when the backend is "nccl").  The context must
     launch on torch's current stream (Context.set_stream) so the collective is ordered after the
-    kernels that produced the buffer and before the ones that consume it, with no host sync."""
+    kernels that produced the buffer and before the ones that consume it, with no host sync.
+
+    That needs a stream of torch's own making (torch.cuda.Stream).  torch's default stream has
+    handle 0, and handle 0 / None mean the context's private stream to set_stream: the context
+    cannot be on the default stream, and its private stream is not ordered against it.  The rule of
+    the private stream then applies -- a hook on it must have finished when it returns -- so with
+    torch on its default stream the hook waits for the collective before it returns."""
     import torch
     views = {}
 
@@ -80,5 +86,8 @@ def torch_allreduce_hook(dist, device, group=None):
             t = torch.as_tensor(DevView(ptr, count), device=device)
             views[(ptr, count)] = t
         dist.all_reduce(t, group=group)
+        stream = torch.cuda.current_stream(device)
+        if stream.cuda_stream == 0:
+            stream.synchronize()
 
     return hook
