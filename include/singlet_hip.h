@@ -912,6 +912,70 @@ SGL_API int sgl_op_umap_epoch(const double* Gx, const int32_t* Gi, const int32_t
  * leaves them as they were. */
 SGL_API int sgl_umap_info(int64_t out[4]);
 
+/* Gene set enrichment: which gene sets are enriched at the top of each factor's loadings -- the reference's RunGSEA
+ * (R/RunGSEA.R), one pre-ranked enrichment test per factor and gene set.  The enrichment score is the weighted
+ * Kolmogorov-Smirnov statistic of GSEA in the form fgsea's calcGseaStat computes it (exponent 1); the p-values come from a
+ * permutation null of random gene sets of the same size (the scheme of fgseaSimple), drawn from the library's counter hash.
+ * The rules below are stated in full; tests/gsea_restatement.py restates them in numpy, the textbook walk over all genes and
+ * a calibration on random sets are the independent yardsticks.  NO parity with fgseaMultilevel's seeded sampler is
+ * claimed, and p-values below 1 / (nperm + 1) are not resolved.  The result is one function of (w, sets, score type, nperm,
+ * seed): tiling, batching and device do not change one bit.
+ *
+ * Inputs.  w: m genes x k factors, column-major doubles, finite, any sign.  The P gene sets as set_ptr[P + 1] (int64,
+ * set_ptr[0] = 0) and set_genes[] (int32, 0-based): set j holds set_genes[set_ptr[j] .. set_ptr[j + 1]).  score_type: 0 pos
+ * (RunGSEA's default), 1 neg, 2 std.  nperm >= 1.  seed (uint64).
+ *
+ * Ranking of factor f.  The genes are ordered by w[g, f] descending; ties (the zeros an L1 fit leaves; -0.0 counts as 0.0)
+ * go by gene index ascending.  pos_f[g] = the 0-based position of gene g.  This tie rule replaces RunGSEA's add.noise.
+ *
+ * Score of a set S of s genes in factor f.  The hits are taken in position order, p_0 < ... < p_{s-1}, with the weights
+ * a_i = |w| of the gene at p_i.  THE PREFIX SUMS cum_i follow one order: the hits are cut into blocks of 64 consecutive
+ * hits; within a block the Kogge-Stone ladder: for d = 1, 2, 4, 8, 16, 32 every lane l >= d adds the previous step's value
+ * of lane l - d, all lanes at once (a lane past the last hit holds +0.0), giving L_l; the block carry C starts at +0.0;
+ * cum of lane l = C + L_l; then C = C + L_63 (the block's last prefix).  NR = cum_{s-1}.
+ *   top_i = cum_i / NR - (double)(p_i - i) / (double)(m - s);   bottom_i = top_i - a_i / NR;
+ * IEEE divisions, no contraction.  When NR == 0 (every hit has weight zero) fgsea's rule holds: cum_i / NR becomes
+ * (double)(i + 1) / (double)s and a_i / NR becomes 1.0 / (double)s.  ES_pos = max top (>= 0), ES_neg = min bottom (<= 0);
+ * std gives the one larger in magnitude, and +0.0 when they are equal in magnitude.
+ *
+ * Null.  key(r, g) = rand(seed, r, g), the reference's hash (src/singlet.cpp:30-64), r in [0, nperm).  The null set of size
+ * s of permutation r = the s genes smallest by (key, g): the sets of one permutation are nested and the same for every
+ * factor.  null[f, s, r] = the score (of the call's score type) of that set in factor f, for every distinct size s among
+ * the tested sets.
+ *
+ * Tallies (integers) and statistics (on the host inside the library, gsea_host.h).  For every (set j, factor f), over the
+ * nulls of its size: n_ge = #{null >= ES}, n_le = #{null <= ES}; per (size, factor): #{null >= 0}, #{null <= 0} and the
+ * sums of the nulls >= 0 and of the nulls <= 0, each added in ascending r, sequentially, from +0.0 -- the running sum is
+ * carried across the batches.  The side of a score: the nulls >= 0 for pos, the nulls <= 0 for neg, for std those >= 0
+ * when ES >= 0 and those <= 0 otherwise; n_side = their number.
+ *   p:  pos (1 + n_ge) / (1 + nperm);  neg (1 + n_le) / (1 + nperm);  std (1 + n_ge or n_le of the side) / (1 + n_side).
+ *   NES = ES / |sum of the side / n_side|, NaN when the side is empty or its mean is 0.
+ *   padj: Benjamini-Hochberg per factor over its P sets: the p in ascending order, rank i = 1 .. n;
+ *         padj of rank i = min(1, min over i' >= i of ((double)n / (double)i') * p of rank i'); a NaN p is left out.
+ *
+ * sgl_c_gsea: one-shot, its own context on the current device; neither uses nor touches the SINGLET_HIP_CACHE context.
+ * Outputs, P x k column-major (set fastest), ANY pointer may be NULL: es, nes, pval, padj, n_ge, n_le, n_side; set_size[P];
+ * info[5] as sgl_gsea_info lays it out; stage_ms[5] = the device time of the five stages (rankings, observed scores, null
+ * sample, null scores, tallies) by events, which costs a wait per stage and batch.  batch: permutations per batch, 0 = by
+ * the memory budget of k x sizes x batch x 8 bytes (256 MiB); the results do not depend on it.
+ *  - refused with SGL_EINVAL before anything is uploaded or launched, the message names the offender: a NULL w, set_ptr or
+ *    set_genes; k outside [1, 1024]; m < 2; n_sets < 1; a score type outside {0, 1, 2}; nperm outside [1, 2^20]; a
+ *    negative batch; a non-finite w; set_ptr not starting at 0 or not ascending; an empty set; a set of size >= m; a set
+ *    above the LDS cap of 4096 genes (RunGSEA's max.size is 500); a gene outside [0, m); a gene twice in one set.
+ *  - the kernels: a segmented radix sort per factor for the rankings; ONE WAVE per (set, factor) sorts the set's positions
+ *    in LDS and scores them; a segmented radix sort of the m keys of every permutation, of which the s_max smallest are
+ *    kept; ONE WAVE per (permutation, factor) sorts the s_max sampled positions once and, for every distinct size,
+ *    compacts the members by a ballot and scores them; integer tallies per (set, factor) and (size, factor).
+ *  - there is NO team form and NO R shim entry; fgseaMultilevel, leading-edge genes and exponents other than 1 are not
+ *    offered. */
+SGL_API int sgl_c_gsea(const double* w, int32_t m, int32_t k, const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets,
+                       int score_type, int32_t nperm, uint64_t seed, int32_t batch, double* es, double* nes, double* pval,
+                       double* padj, int64_t* n_ge, int64_t* n_le, int64_t* n_side, int32_t* set_size, int64_t* info,
+                       double* stage_ms);
+/* What the last enrichment call on this context ran: out[0] the sets, out[1] the distinct sizes, out[2] s_max, out[3] the
+ * batches of permutations, out[4] the permutations per batch (sgl_op_gsea_es: sets and s_max; sgl_op_gsea_null: the rest). */
+SGL_API int sgl_gsea_info(sgl_ctx* ctx, int64_t out[5]);
+
 /* Cell graph of c_gcnmf for the current fit (after sgl_fit_init, which drops
  * it again; all-NULL slots clear it).  G is an n x n dgCMatrix, n = the cells of
  * the resident matrix; an invalid G is SGL_EINVAL with a message.  While it is
@@ -1159,6 +1223,20 @@ SGL_API int sgl_op_loess_direct(sgl_ctx* ctx, const double* x, const double* y, 
 SGL_API int sgl_op_marker_sums(sgl_ctx* ctx, const int32_t* labels, int32_t n_groups, int transform, int64_t* pos, int64_t* nz, double* sum);
 SGL_API int sgl_op_marker_ranks(sgl_ctx* ctx, const int32_t* labels, int32_t n_groups, int64_t max_batch_entries, int64_t* rank2,
                                 uint64_t* tie);
+/* The stages of sgl_c_gsea, one at a time (the rules and the refusals are stated there).  They use the context's device,
+ * stream and pool only: no resident matrix is needed, nothing of the context changes but what sgl_gsea_info reports.
+ *  - sgl_op_gsea_es: the observed scores of the given sets under all three score types, each n_sets x k column-major; any
+ *    may be NULL.
+ *  - sgl_op_gsea_null: the null scores of the given sizes (strictly ascending, each in [1, min(m - 1, 4096)]) for the
+ *    permutations [r0, r1), 0 <= r0 < r1 <= 2^20, in batches of `batch` permutations (0: by the memory budget; negative:
+ *    SGL_EINVAL): null_out[(f n_sizes + si) (r1 - r0) + (r - r0)], and sample[(r - r0) s_max + t] = the gene at place t of
+ *    permutation r's order by (key, gene), s_max = the largest size; either may be NULL.  The results do not depend on
+ *    `batch`. */
+SGL_API int sgl_op_gsea_es(sgl_ctx* ctx, const double* w, int32_t m, int32_t k, const int64_t* set_ptr, const int32_t* set_genes,
+                           int32_t n_sets, double* es_pos, double* es_neg, double* es_std);
+SGL_API int sgl_op_gsea_null(sgl_ctx* ctx, const double* w, int32_t m, int32_t k, const int32_t* sizes, int32_t n_sizes,
+                             int score_type, uint64_t seed, int32_t r0, int32_t r1, int32_t batch, double* null_out,
+                             int32_t* sample);
 /* nnls on ncols independent columns, each against its OWN Gram: Gcols = ncols blocks of k x k, B / X as in sgl_op_nnls;
  * col_nnz (int64 [ncols], or NULL): columns with a zero there are skipped -- X keeps its input, no sweeps are counted.
  * The dispatch of every masked half-step (four columns per wave on LDS triangles or on the Grams in global memory, one

@@ -10,7 +10,7 @@ from .api import (c_nmf, c_ard_nmf, c_linked_nmf, c_gcnmf, run_gcnmf, c_nmf_dens
                   group_means, run_linked_nmf, RunLNMF, MetadataSummary, GetSharedFactors, GetUniqueFactors, evaluate,
                   find_variable_features, knn, find_neighbors, c_louvain, op_louvain_sweep,
                   louvain_info, find_clusters, c_markers, find_all_markers, find_markers, fuzzy_simplicial_set, umap_layout,
-                  op_umap_epoch, umap_info, find_ab_params, run_umap)
+                  op_umap_epoch, umap_info, find_ab_params, run_umap, c_gsea, read_gmt, run_gsea)
 from .native import native, NativeMatrix  # noqa: F401
 from ._lib import SingletHipError, LIB_PATH  # noqa: F401
 

@@ -112,6 +112,12 @@ SIGNATURES = {
     "sgl_markers_info": (C.c_int, [C.c_void_p, i64p]),
     "sgl_op_marker_sums": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int, i64p, i64p, f64p]),
     "sgl_op_marker_ranks": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int64, i64p, u64p]),
+    "sgl_c_gsea": (C.c_int, [f64p, C.c_int32, C.c_int32, i64p, i32p, C.c_int32, C.c_int, C.c_int32, C.c_uint64, C.c_int32, f64p, f64p,
+                             f64p, f64p, i64p, i64p, i64p, i32p, i64p, f64p]),
+    "sgl_gsea_info": (C.c_int, [C.c_void_p, i64p]),
+    "sgl_op_gsea_es": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int32, i64p, i32p, C.c_int32, f64p, f64p, f64p]),
+    "sgl_op_gsea_null": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int32, i32p, C.c_int32, C.c_int, C.c_uint64, C.c_int32, C.c_int32,
+                                   C.c_int32, f64p, i32p]),
     "sgl_knn": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64, f64p, C.c_int64, i32p, C.c_int32, C.c_int32, i32p, f64p]),
     "sgl_c_knn": (C.c_int, [f64p, C.c_int32, C.c_int64, f64p, C.c_int64, i32p, C.c_int32, C.c_int32, i32p, f64p]),
     "sgl_knn_info": (C.c_int, [C.c_void_p, i64p]),

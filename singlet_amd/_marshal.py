@@ -120,6 +120,34 @@ def markers_call(fn, nrow, labels, G, transform, pseudocount):
     return out
 
 
+GSEA_SCORE_TYPES = {"pos": 0, "neg": 1, "std": 2, 0: 0, 1: 1, 2: 2}
+
+
+def gsea_inputs(w, set_ptr, set_genes):
+    """(w column-major as its (k, m) image, m, k, int64 set_ptr, int32 set_genes) of the enrichment calls.  w: m genes x k
+    factors.  The library checks the content; only what cannot be marshalled is refused here."""
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim != 2:
+        raise ValueError("w must be a matrix, m genes x k factors")
+    sp, sg = np.asarray(set_ptr), np.asarray(set_genes)
+    if sg.size == 0:
+        sg = np.zeros(0, dtype=np.int32)
+    if sp.ndim != 1 or sp.size < 1 or sp.dtype.kind not in "iu":
+        raise ValueError("set_ptr must hold the n_sets + 1 integer offsets of the gene sets")
+    if sg.ndim != 1 or sg.dtype.kind not in "iu" or (sg.size and (sg.min() < -2**31 or sg.max() >= 2**31)):
+        raise ValueError("set_genes must hold 0-based integer gene indices")
+    sp = np.ascontiguousarray(sp, dtype=np.int64)
+    if sp[-1] > sg.size or (sp.size > 1 and sp.max() > sg.size):
+        raise ValueError("set_ptr points past the end of set_genes (%d entries)" % sg.size)
+    return np.ascontiguousarray(w.T), w.shape[0], w.shape[1], sp, np.ascontiguousarray(sg, dtype=np.int32)
+
+
+def gsea_score_type(score_type):
+    if score_type not in GSEA_SCORE_TYPES:
+        raise ValueError("score_type must be 'pos', 'neg' or 'std'")
+    return GSEA_SCORE_TYPES[score_type]
+
+
 def knn_call(fn, reference, query, dims, n_neighbors, resident=None):
     """Shared by Context.knn and api.knn: fn(R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, idx_out, dist_out) is the
     library call.  reference / query: k x n matrices (R's orientation, one column per cell); a None reference stands for the

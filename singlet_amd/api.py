@@ -27,6 +27,8 @@ names, argument order, defaults and return fields:
                                         exact local fit at every gene, not R's interpolated loess)
   evaluate                              no R counterpart: the full-matrix error of a model (mse_test, src/singlet.cpp:536-568,
                                         with every entry drawn), per cell and per gene
+  run_gsea                              RunGSEA (R/RunGSEA.R:27-138) with the gene sets given by the caller and a permutation
+                                        null in place of fgseaMultilevel (include/singlet_hip.h, "Gene set enrichment")
   find_all_markers / find_markers       Seurat::FindAllMarkers / FindMarkers(test.use = "wilcox") under the rules stated in
                                         include/singlet_hip.h, "Marker genes" (the filters are applied after the test)
 
@@ -43,7 +45,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, knn_call, label_list, markers_call
+from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, label_list, markers_call
 from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
@@ -1857,3 +1859,114 @@ def find_markers(A, cells_1, cells_2=None, min_pct=0.1, logfc_threshold=0.25, on
     labels[m1] = 0
     st, names = _markers_of(A, labels, 2, transform, pseudocount)
     return _marker_table(st, 0, names, min_pct, logfc_threshold, only_pos, return_thresh)
+
+
+# ---------------------------------------------------------------------------
+# Gene set enrichment of the factors (RunGSEA, R/RunGSEA.R)
+# ---------------------------------------------------------------------------
+GSEA_SEED = 0x65EA
+
+
+def c_gsea(w, set_ptr, set_genes, score_type="pos", nperm=1000, seed=GSEA_SEED, batch=0, timing=False):
+    """The pre-ranked enrichment test of every gene set in every factor (sgl_c_gsea; the rules are stated in
+    include/singlet_hip.h, "Gene set enrichment").  w: m genes x k factors; the sets as set_ptr (n_sets + 1 offsets) and
+    set_genes (0-based gene indices).  Returns a dict of n_sets x k arrays "es", "nes", "pval", "padj", "n_ge", "n_le",
+    "n_side", with "set_size" (n_sets), "info" ({"sets", "sizes", "s_max", "batches", "batch"}) and, with timing, "stage_ms"
+    (rankings, observed scores, null sample, null scores, tallies).  batch: permutations per batch, 0 = by the memory budget;
+    the results do not depend on it."""
+    wt, m, k, sp, sg = gsea_inputs(w, set_ptr, set_genes)
+    st = gsea_score_type(score_type)
+    P = sp.shape[0] - 1
+    shape = (max(k, 1), max(P, 1))
+    f64s = {n: np.empty(shape) for n in ("es", "nes", "pval", "padj")}
+    i64s = {n: np.zeros(shape, dtype=np.int64) for n in ("n_ge", "n_le", "n_side")}
+    set_size = np.zeros(max(P, 1), dtype=np.int32)
+    info = np.zeros(5, dtype=np.int64)
+    stage_ms = np.zeros(5) if timing else None
+    i64p = _lib.i64p
+    check(_lib.load().sgl_c_gsea(ptr(wt, f64p), m, k, ptr(sp, i64p), ptr(sg, i32p), P, st, int(nperm), int(seed), int(batch),
+                                 ptr(f64s["es"], f64p), ptr(f64s["nes"], f64p), ptr(f64s["pval"], f64p), ptr(f64s["padj"], f64p),
+                                 ptr(i64s["n_ge"], i64p), ptr(i64s["n_le"], i64p), ptr(i64s["n_side"], i64p), ptr(set_size, i32p),
+                                 ptr(info, i64p), ptr(stage_ms, f64p)))
+    out = {n: a[:k, :P].T for n, a in {**f64s, **i64s}.items()}
+    out["set_size"] = set_size[:P]
+    out["info"] = dict(zip(("sets", "sizes", "s_max", "batches", "batch"), (int(v) for v in info)))
+    if timing:
+        out["stage_ms"] = stage_ms
+    return out
+
+
+def read_gmt(path):
+    """A GMT file (one gene set per line: name, description, genes, tab-separated) as a dict name -> list of gene names, in
+    file order; empty fields are dropped, a name that occurs twice keeps the genes of both lines.  Pure host."""
+    sets = {}
+    with open(path) as f:
+        for line in f:
+            cells = line.rstrip("\r\n").split("\t")
+            if len(cells) < 2 or not cells[0]:
+                continue
+            sets.setdefault(cells[0], []).extend(g for g in cells[2:] if g)
+    return sets
+
+
+def gsea_filter(pathways, gene_names, w, min_size=10, max_size=500):
+    """The filters of RunGSEA (R/RunGSEA.R:36-64) and of fgsea's own preparation, in their order.  pathways: dict name ->
+    gene names; gene_names: the row names of w (m x k).  Returns (names, rows, sets, tested): the names of the sets RunGSEA
+    hands to fgsea, the rows of w that stay (ascending), each set as indices into those rows (duplicates dropped, in order
+    of first occurrence), and tested[j] = fgsea's own inclusive size filter min_size <= size <= max_size on what is left."""
+    w = np.asarray(w)
+    paths = {n: list(v) for n, v in pathways.items() if len(v) > min_size}                 # l.36: strictly longer
+    in_paths = set(g for v in paths.values() for g in v)                                     # l.39
+    keep = np.array([g in in_paths for g in gene_names], dtype=bool)                         # l.54
+    kept_names = set(g for g, kk in zip(gene_names, keep) if kk)
+    paths = {n: [g for g in v if g in kept_names] for n, v in paths.items()}                 # l.55
+    paths = {n: v for n, v in paths.items() if min_size < len(v) < max_size}                 # l.56-57: both strict
+    keep &= w.sum(axis=1) != 0                                                               # l.60-64: rows whose sum is 0 go
+    rows = np.nonzero(keep)[0]
+    index = {gene_names[g]: q for q, g in enumerate(rows.tolist())}
+    names, sets, tested = [], [], []
+    for n, v in paths.items():
+        ids = list(dict.fromkeys(index[g] for g in v if g in index))                         # fgsea: unique genes of the ranking
+        names.append(n)
+        sets.append(np.asarray(ids, dtype=np.int32))
+        tested.append(min_size <= len(ids) <= max_size)
+    return names, rows, sets, np.asarray(tested, dtype=bool)
+
+
+def run_gsea(w, pathways, gene_names, min_size=10, max_size=500, dims=None, score_type="pos", nperm=1000, seed=GSEA_SEED,
+             padj_sig=0.01):
+    """RunGSEA (R/RunGSEA.R:27-138) on the device: which gene sets are enriched in each factor.  w: m genes x k factors (a
+    model's w); pathways: a dict name -> gene names, or the path of a GMT file (the reference fetches them from msigdbr, which
+    needs a download); gene_names: the m row names of w; dims: the factors to test (0-based), None = all.  The filters are
+    the reference's, in its order: keep the sets longer than min_size; restrict w to the genes of any kept set and the sets
+    to those genes; keep the sets with min_size < size < max_size; drop the genes whose row of w sums to zero; then fgsea's
+    own inclusive size filter on what is left -- a set failing it is a row of NaN, as padData leaves it.  Returns {"pval",
+    "padj" (both as -log10), "es", "nes"}: sets x factors, with "pathways" (the row names), "dims", "significant" (the rows
+    with a padj below padj_sig in some factor) and "genes" (the rows of w the test ran on).
+    The test is the library's permutation test (sgl_c_gsea): ties of a factor go by gene index, the null is nperm random
+    sets of each size.  NOT offered: the hclust display order of the rows and columns (as MetadataSummary leaves it out);
+    add.noise (the tie rule removes its cause); remove.zeros.per.factor (a per-factor universe); fgseaMultilevel's p-values
+    below 1 / (nperm + 1) -- the floor of this test is 1 / (nperm + 1): raise nperm to resolve smaller ones."""
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim != 2 or len(gene_names) != w.shape[0]:
+        raise ValueError("run_gsea: gene_names must name the %s rows of w" % (w.shape[0] if w.ndim == 2 else "m"))
+    if isinstance(pathways, (str, bytes)) or hasattr(pathways, "__fspath__"):
+        pathways = read_gmt(pathways)
+    st = gsea_score_type(score_type)
+    gene_names = list(gene_names)
+    dims = np.arange(w.shape[1]) if dims is None else np.asarray(dims, dtype=np.int64).ravel()
+    w = w[:, dims]                                                                           # l.47
+    names, rows, sets, tested = gsea_filter(pathways, gene_names, w, min_size, max_size)
+    P, k = len(names), w.shape[1]
+    out = {n: np.full((P, k), np.nan) for n in ("pval", "padj", "es", "nes")}
+    run = np.nonzero(tested)[0]
+    if run.size:
+        set_ptr = np.concatenate([[0], np.cumsum([sets[j].size for j in run])]).astype(np.int64)
+        res = c_gsea(w[rows], set_ptr, np.concatenate([sets[j] for j in run]), st, nperm, seed)
+        for n in out:
+            out[n][run] = res[n]
+    with np.errstate(invalid="ignore"):
+        sig = np.nonzero(np.nanmin(np.where(np.isnan(out["padj"]), np.inf, out["padj"]), axis=1, initial=np.inf) < padj_sig)[0]
+        out["pval"], out["padj"] = -np.log10(out["pval"]), -np.log10(out["padj"])
+    out.update(pathways=names, dims=dims, significant=sig, genes=rows)
+    return out

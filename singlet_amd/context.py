@@ -6,7 +6,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
-from ._marshal import MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, knn_call, label_list, markers_call
+from ._marshal import (MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, label_list,
+                       markers_call)
 from .sparse import as_dgCMatrix
 
 SYNTH_SEED = 0x5EED
@@ -735,6 +736,37 @@ class Context(_Handle):
         tie = np.zeros(max(nr, 1), dtype=np.uint64)
         check(self._L.sgl_op_marker_ranks(self._h, ptr(g, i32p), G, int(max_batch_entries), ptr(rank2, i64p), ptr(tie, u64p)))
         return rank2[:, :nr].T, tie[:nr]
+
+    # the stages of the gene set enrichment test, one at a time (no resident matrix is needed)
+    def op_gsea_es(self, w, set_ptr, set_genes):
+        """(es_pos, es_neg, es_std), each n_sets x k: the observed enrichment scores of the gene sets in every column of w (m genes
+        x k factors) under the three score types (sgl_op_gsea_es; the rules: include/singlet_hip.h, "Gene set enrichment")."""
+        wt, m, k, sp, sg = gsea_inputs(w, set_ptr, set_genes)
+        P = sp.shape[0] - 1
+        out = [np.empty((max(k, 1), max(P, 1))) for _ in range(3)]
+        check(self._L.sgl_op_gsea_es(self._h, ptr(wt, f64p), m, k, ptr(sp, i64p), ptr(sg, i32p), P, *(ptr(o, f64p) for o in out)))
+        return tuple(o[:k, :P].T for o in out)
+
+    def op_gsea_null(self, w, sizes, score_type="pos", seed=0, r0=0, r1=1, batch=0, return_sample=False):
+        """null (k x n_sizes x (r1 - r0)): the scores of the null sets of the given sizes (strictly ascending) for the permutations
+        [r0, r1) in batches of `batch` permutations (0: by the memory budget); with return_sample also the (r1 - r0) x s_max
+        genes of every permutation in their order by (key, gene) (sgl_op_gsea_null)."""
+        wt, m, k, _, _ = gsea_inputs(w, [0], [])
+        sz = np.ascontiguousarray(np.asarray(sizes).ravel(), dtype=np.int32)
+        st, n = gsea_score_type(score_type), max(int(r1) - int(r0), 1)
+        s_max = int(min(max(int(sz.max()) if sz.size else 1, 1), 4096))   # (outside the range the library refuses before it writes)
+        null = np.empty((max(k, 1), max(sz.size, 1), n))
+        sample = np.zeros((n, s_max), dtype=np.int32) if return_sample else None
+        check(self._L.sgl_op_gsea_null(self._h, ptr(wt, f64p), m, k, ptr(sz, i32p), sz.size, st, int(seed), int(r0), int(r1), int(batch),
+                                       ptr(null, f64p), ptr(sample, i32p)))
+        null = null[:k, :sz.size]
+        return (null, sample) if return_sample else null
+
+    def gsea_info(self):
+        """What the last enrichment call on this context ran (sgl_gsea_info): {"sets", "sizes", "s_max", "batches", "batch"}."""
+        out = np.zeros(5, dtype=np.int64)
+        check(self._L.sgl_gsea_info(self._h, ptr(out, i64p)))
+        return dict(zip(("sets", "sizes", "s_max", "batches", "batch"), (int(v) for v in out)))
 
     def op_rhs_masked(self, which, F, seed, inv_density):
         """op_rhs with the entries the mask (seed, inv_density) draws left out (sgl_op_rhs_masked): which = 0 / 1 hash every

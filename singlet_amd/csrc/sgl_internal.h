@@ -245,6 +245,7 @@ struct sgl_ctx {
     double* pinned = nullptr;        // host pinned scratch (8 doubles)
     int64_t knn_last[4] = {0, 0, 0, 0};   // sgl_knn_info: instance, segments, queries per workgroup, list home of the last sgl_knn
     int64_t markers_last[4] = {0, 0, 0, 0};   // sgl_markers_info: genes sorted in LDS, long genes, batches, the LDS cap of the last rank pass
+    int64_t gsea_last[5] = {0, 0, 0, 0, 0};   // sgl_gsea_info: sets, distinct sizes, s_max, batches, batch size of the last enrichment call
 
     sgl_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
@@ -458,6 +459,23 @@ int sgl_markers_core(sgl_ctx* c, const int32_t* labels, int32_t G, int transform
 // both passes and the derived statistics (markers_host.h)
 int sgl_markers_all(sgl_ctx* c, const int32_t* labels, int32_t G, int transform, double pseudocount, int64_t* group_n, int64_t* pos,
                     double* sum, int64_t* rank2, uint64_t* tie, double* pct_in, double* pct_out, double* log2fc, double* z, double* p);
+
+// gene set enrichment (kernels_gsea.hip; include/singlet_hip.h, "Gene set enrichment").  All arrays are the HOST's; every call
+// only reads the context (it records what it ran in gsea_last), allocates its own temporaries and synchronises the stream
+// before it returns.  The *_args_check functions hold every refusal and launch nothing.
+int sgl_gsea_args_check(const char* who, const double* w, int64_t m, int64_t k, const int64_t* set_ptr, const int32_t* set_genes, int64_t P,
+                        int score_type, int64_t nperm, int64_t batch);
+int sgl_gsea_null_args_check(const char* who, const double* w, int64_t m, int64_t k, const int32_t* sizes, int64_t n_sizes, int score_type,
+                             int64_t r0, int64_t r1, int64_t batch);
+// es3: the three planes (pos, neg, std) of P x k observed scores
+int sgl_gsea_es(sgl_ctx* c, const double* w, int64_t m, int64_t k, const int64_t* set_ptr, const int32_t* set_genes, int64_t P, double* es3);
+// null_out[(f S + si) (r1 - r0) + (r - r0)]; sample[(r - r0) s_max + t]; either may be NULL; batch 0: by the memory budget
+int sgl_gsea_null(sgl_ctx* c, const double* w, int64_t m, int64_t k, const int32_t* sizes, int64_t S, int score_type, uint64_t seed, int64_t r0,
+                  int64_t r1, int64_t batch, double* null_out, int32_t* sample);
+// the five stages and the derived statistics (gsea_host.h); stage_ms (5 values, may be NULL): the stages timed by events
+int sgl_gsea_all(sgl_ctx* c, const double* w, int64_t m, int64_t k, const int64_t* set_ptr, const int32_t* set_genes, int64_t P, int score_type,
+                 int64_t nperm, uint64_t seed, int64_t batch, double* es, double* nes, double* pval, double* padj, int64_t* n_ge, int64_t* n_le,
+                 int64_t* n_side, int32_t* set_size, double* stage_ms);
 
 // row-wise rasterisation (kernels_raster.hip): out (nb x ncol, column-major) = means of rows [b n, b n + n), nb >= 1
 int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, double* out);

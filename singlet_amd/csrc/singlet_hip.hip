@@ -1977,6 +1977,26 @@ extern "C" int sgl_markers_info(sgl_ctx* c, int64_t out[4]) {
     return SGL_OK;
 }
 
+// Gene set enrichment (include/singlet_hip.h; kernels_gsea.hip): the refusals before a context is made, then its own context.
+extern "C" int sgl_c_gsea(const double* w, int32_t m, int32_t k, const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets, int score_type,
+                          int32_t nperm, uint64_t seed, int32_t batch, double* es, double* nes, double* pval, double* padj, int64_t* n_ge,
+                          int64_t* n_le, int64_t* n_side, int32_t* set_size, int64_t* info, double* stage_ms) {
+    SGLCHK(sgl_gsea_args_check("sgl_c_gsea", w, m, k, set_ptr, set_genes, n_sets, score_type, nperm, batch));
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    SGLCHK(sgl_gsea_all(hd.c, w, m, k, set_ptr, set_genes, n_sets, score_type, nperm, seed, batch, es, nes, pval, padj, n_ge, n_le, n_side, set_size,
+                        stage_ms));
+    if (info) std::copy(hd.c->gsea_last, hd.c->gsea_last + 5, info);
+    return SGL_OK;
+}
+
+extern "C" int sgl_gsea_info(sgl_ctx* c, int64_t out[5]) {
+    CTX_GUARD(c);
+    if (!out) { sgl_set_error("sgl_gsea_info: NULL out"); return SGL_EINVAL; }
+    std::copy(c->gsea_last, c->gsea_last + 5, out);
+    return SGL_OK;
+}
+
 // c_gcnmf's cell graph G (src/singlet.cpp:1668-1730): n x n, n = the cells of the resident matrix, as a dgCMatrix.  Checked
 // on the host (the kernels index factor columns by its rows): p[0] = 0 and monotone, rows strictly ascending within a column
 // and in [0, n), values finite.  Columns above SGL_GRAPH_HUB entries get their segment lists here (kernels_graph.hip).
@@ -2465,6 +2485,26 @@ extern "C" int sgl_op_marker_ranks(sgl_ctx* c, const int32_t* labels, int32_t n_
     SGLCHK(sgl_markers_args_check("sgl_op_marker_ranks", labels, c->A.ncol, n_groups, 0, 0.0));
     if (max_batch_entries < 0) { sgl_set_error("sgl_op_marker_ranks: max_batch_entries = %lld is negative", (long long)max_batch_entries); return SGL_EINVAL; }
     return sgl_markers_core(c, labels, n_groups, 0, max_batch_entries, false, true, nullptr, nullptr, nullptr, nullptr, rank2, tie);
+}
+
+// The stages of sgl_c_gsea one at a time (kernels_gsea.hip); they read nothing of the context but its stream
+extern "C" int sgl_op_gsea_es(sgl_ctx* c, const double* w, int32_t m, int32_t k, const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets,
+                              double* es_pos, double* es_neg, double* es_std) {
+    CTX_GUARD(c);
+    SGLCHK(sgl_gsea_args_check("sgl_op_gsea_es", w, m, k, set_ptr, set_genes, n_sets, 0, 1, 0));
+    const size_t pk = (size_t)n_sets * (size_t)k;
+    std::vector<double> es3(3 * pk);
+    SGLCHK(sgl_gsea_es(c, w, m, k, set_ptr, set_genes, n_sets, es3.data()));
+    if (es_pos) std::copy(es3.begin(), es3.begin() + pk, es_pos);
+    if (es_neg) std::copy(es3.begin() + pk, es3.begin() + 2 * pk, es_neg);
+    if (es_std) std::copy(es3.begin() + 2 * pk, es3.end(), es_std);
+    return SGL_OK;
+}
+extern "C" int sgl_op_gsea_null(sgl_ctx* c, const double* w, int32_t m, int32_t k, const int32_t* sizes, int32_t n_sizes, int score_type,
+                                uint64_t seed, int32_t r0, int32_t r1, int32_t batch, double* null_out, int32_t* sample) {
+    CTX_GUARD(c);
+    SGLCHK(sgl_gsea_null_args_check("sgl_op_gsea_null", w, m, k, sizes, n_sizes, score_type, r0, r1, batch));
+    return sgl_gsea_null(c, w, m, k, sizes, n_sizes, score_type, seed, r0, r1, batch, null_out, sample);
 }
 
 // k_nnls_percol with a Gram per column (gstride = k * k), as every masked half-step calls it
