@@ -62,14 +62,33 @@ def plan(KP):
                 WAVES=max(1, min(8, 512 // ((total + 7) // 8 * 8))))
 
 
+EPS_RCP = 2.0 ** -13   # relative error of v_rcp_f64 assumed throughout: two Newton steps must reach a correctly rounded quotient
+
+
+def band(KP):
+    """delta of the bounded variant: its running tol S and the exact kernel's T obey |S - T| <= delta / 2 * T ("The
+    bounded tol"; the factor 2 covers the roundings of S (1 -+ delta) and the second-order terms).  nnls_lane_asm_bounded_band
+    (kernels_nnls_asm_bounded.hip) is the same expression."""
+    return 2.0 * (EPS_RCP ** 2 + (KP + 4) * 2.0 ** -52)
+
+
 def r2(b):
     return f"v[{b}:{b + 1}]"
 
 
 class Sweep:
-    def __init__(self, KP):
+    def __init__(self, KP, bounded=False):
+        """bounded: the variant whose tol term is a quotient with a PROVEN error bound instead of the correctly rounded one
+        (v_rcp_f64 and ONE Newton step: 4 instructions fewer per coordinate), for L2 = 0 and L1 >= 0 (the L2 term is not
+        issued, the gate and L1 are one FMA: 2 fewer).  x, b and the steps are the same bits; the running tol S is within a
+        relative delta of the exact one ("The bounded tol"), and the kernel body decides the stop test on both ends
+        of that interval.  Same register plan: the remainder E shares DEN's pair (DEN is dead once E is formed), which frees a
+        pair for L1G = L1 * GM."""
         p = plan(KP)
         self.__dict__.update(p)
+        self.bounded = bounded
+        if bounded and self.XA:
+            raise SystemExit("gen_nnls_lane.py: the bounded variant has no accumulator-register plan (KP = %d)" % KP)
         T = self.V_T
         self.A, self.E2 = T, T + 2          # head temporaries
         self.ND = [T + 4, T + 6]            # nd by coordinate parity
@@ -78,6 +97,8 @@ class Sweep:
         self.GM = T + 18                    # 1.0 / 0.0: the stopped-column gate of this sweep
         self.XH = [T + 20, T + 22]          # XA: x_i as the chain reads it (by coordinate parity), XN its new value
         self.XN = T + 24
+        if bounded:
+            self.E, self.L1G = self.DEN, T + 12   # L1 where the column iterates, 0 where it has stopped
         self.L = []
 
     def b(self, j):
@@ -104,10 +125,15 @@ class Sweep:
         ]
         if i + 1 < self.KP:   # D is free: the pair of the next coordinate
             ops.append(f"ds_read_b128 v[{self.V_D}:{self.V_D + 3}], %[dl] offset:{16 * (i + 1)}")
+        if self.bounded:   # (A - L1) * GM in one rounding for GM in {0, 1}: the bits of the two instructions but for the sign of a zero step
+            ops.append(f"v_fma_f64 {r2(A)}, {r2(A)}, {r2(self.GM)}, -{r2(self.L1G)}")
+        else:
+            ops += [
+                f"v_add_f64 {r2(A)}, {r2(A)}, -%[l1]",
+                f"v_fma_f64 {r2(A)}, %[l2], {r2(x)}, {r2(A)}",
+                f"v_mul_f64 {r2(A)}, {r2(A)}, {r2(self.GM)}",            # a stopped column takes a zero step
+            ]
         ops += [
-            f"v_add_f64 {r2(A)}, {r2(A)}, -%[l1]",
-            f"v_fma_f64 {r2(A)}, %[l2], {r2(x)}, {r2(A)}",
-            f"v_mul_f64 {r2(A)}, {r2(A)}, {r2(self.GM)}",            # a stopped column takes a zero step
             f"v_min_f64 {r2(ND)}, -{r2(A)}, {r2(x)}",                # nd = min(-diff, x_i)
             f"v_cmp_lt_f64_e64 s[{{c0}}:{{c0p}}], {r2(x)}, -{r2(A)}",  # -diff > x_i ...
             f"v_cmp_neq_f64_e32 vcc, 0, {r2(x)}",                    # ... and x_i != 0: the clamp from a positive value
@@ -124,6 +150,16 @@ class Sweep:
         else:
             x = self.x(i)
             first = [f"v_add_f64 {r2(x)}, {r2(x)}, -{r2(ND)}"]
+        if self.bounded:
+            return first + [
+                f"v_add_f64 {r2(DEN)}, {r2(x)}, %[eps]",
+                f"v_rcp_f64 {r2(R)}, {r2(DEN)}",
+                f"v_fma_f64 {r2(E)}, -{r2(DEN)}, {r2(R)}, 1.0",       # (E overwrites DEN)
+                f"v_fma_f64 {r2(R)}, {r2(R)}, {r2(E)}, {r2(R)}",       # one Newton step: relative error <= eps_r^2 + 2^-52
+                f"v_mul_f64 {r2(Q)}, {r2(ND)}, {r2(R)}",
+                f"v_add_f64 {r2(Q)}, {r2(self.TOL)}, |{r2(Q)}|",
+                "TOLSEL",
+            ]
         return first + [
             f"v_add_f64 {r2(DEN)}, {r2(x)}, %[eps]",
             f"v_rcp_f64 {r2(R)}, {r2(DEN)}",
@@ -208,11 +244,15 @@ class Sweep:
         return " \\\n".join(f'    "{ins}\\n\\t"' for ins in (L if L is not None else self.L))
 
 
-def kernel_body(KP):
+def kernel_body(KP, bounded=False):
     """Everything between the staging of the Gram and the epilogue bookkeeping as ONE asm statement: b and x then are plain
     clobbers of that statement (hipcc offers no way to keep it out of a register range ACROSS statements below 64 registers:
-    amdgpu_num_vgpr is not honoured, waves_per_eu caps at 64).  Operands: see kernels_nnls_asm.hip."""
-    s = Sweep(KP)
+    amdgpu_num_vgpr is not honoured, waves_per_eu caps at 64).  Operands: see kernels_nnls_asm.hip.
+    bounded: the sweep of Sweep(KP, bounded=True) and the two-sided stop test.  The running tol S is within a relative %[dlt]
+    of the exact tol, and the stop test is monotone in tol: where it says the same for S (1 - dlt) and S (1 + dlt), that is what
+    the exact kernel decides.  Where it does not, the lane is TAINTED (%[tn], in / out): it stops, nothing of it is stored, and
+    the exact kernel solves the column again from the state it entered this pass with (kernels_nnls_asm_bounded.hip)."""
+    s = Sweep(KP, bounded=bounded)
     s.build()
     sweep = s.L
     L = []
@@ -238,6 +278,34 @@ def kernel_body(KP):
         A("s_nop 3")
         A(f"s_and_b64 {go}, vcc, {c1}")
         A(f"s_and_b64 {go}, {go}, %[valid]")
+
+    def go_mask_bounded():
+        lo_go, hi_go, S, E = "s[40:41]", "s[42:43]", s.A, s.E     # (the compare slots and the head's temporaries are free between sweeps)
+        A(f"v_rcp_f64 {r2(R)}, %[kd]")
+        A("s_nop 1")
+        A(f"v_fma_f64 {r2(E)}, -%[kd], {r2(R)}, 1.0")
+        A(f"v_fma_f64 {r2(R)}, {r2(R)}, {r2(E)}, {r2(R)}")
+        A(f"v_fma_f64 {r2(E)}, -%[kd], {r2(R)}, 1.0")
+        A(f"v_fma_f64 {r2(R)}, {r2(R)}, {r2(E)}, {r2(R)}")       # RN(1 / k), as in the exact test
+        for end, sign in ((lo_go, "-"), (hi_go, "")):
+            A(f"v_fma_f64 {r2(S)}, {sign}{r2(TOL)}, %[dlt], {r2(TOL)}")   # S (1 -+ dlt)
+            A(f"v_mul_f64 {r2(Q)}, {r2(S)}, {r2(R)}")
+            A(f"v_fma_f64 {r2(E)}, -%[kd], {r2(Q)}, {r2(S)}")
+            A(f"v_fma_f64 {r2(Q)}, {r2(E)}, {r2(R)}, {r2(Q)}")
+            A(f"v_cmp_lt_f64_e64 {end}, %[thr], {r2(Q)}")
+        A("v_cmp_gt_u32_e32 vcc, 100, %[it]")
+        A("s_nop 3")
+        A(f"s_xor_b64 {c1}, {lo_go}, {hi_go}")                    # the two ends disagree, and the sweep limit does not decide anyway
+        A(f"s_and_b64 {c1}, {c1}, vcc")
+        A(f"s_and_b64 {c1}, {c1}, %[valid]")
+        A(f"s_or_b64 %[tn], %[tn], {c1}")
+        A(f"s_and_b64 {go}, {lo_go}, {hi_go}")
+        A(f"s_and_b64 {go}, {go}, vcc")
+        A(f"s_and_b64 {go}, {go}, %[valid]")
+        A(f"s_andn2_b64 {go}, {go}, %[tn]")                       # a tainted lane has stopped for good
+
+    if bounded:
+        go_mask = go_mask_bounded
 
     def masked(mask, body, last):
         A(f"s_mov_b64 {sv}, exec")
@@ -282,6 +350,8 @@ def kernel_body(KP):
     A(f"v_cndmask_b32_e64 v{TOL + 1}, v{TOL + 1}, 0, {go}")
     A(f"v_mov_b32 v{GM}, 0")
     A(f"v_cndmask_b32_e64 v{GM + 1}, 0, %[one_hi], {go}")    # gm = 1.0 / 0.0
+    if bounded:
+        A(f"v_mul_f64 {r2(s.L1G)}, {r2(GM)}, %[l1]")
     L.extend(sweep)
     A(f"v_cndmask_b32_e64 v{s.A}, 0, 1, {go}")
     A(f"v_add_u32 %[it], %[it], v{s.A}")
@@ -289,7 +359,11 @@ def kernel_body(KP):
     A("3:")                                      # ---- {go} = the columns left unfinished (only when the pass re-packs)
     A(f"v_mov_b32 %[lo], v{TOL}")
     A(f"v_mov_b32 %[hi], v{TOL + 1}")
-    masked("%[valid]", [f"global_store_dwordx2 %[xp], {xr(q)}, off offset:{8 * q}" for q in range(KP - 1)],
+    xm = "%[valid]"
+    if bounded:   # x of a tainted lane stays as the pass found it
+        xm = c1
+        A(f"s_andn2_b64 {c1}, %[valid], %[tn]")
+    masked(xm, [f"global_store_dwordx2 %[xp], {xr(q)}, off offset:{8 * q}" for q in range(KP - 1)],
            f"global_store_dwordx2 %[xp], {xr(j)}, off offset:{8 * j}")
     masked(go, [f"global_store_dwordx2 %[bp], {r2(s.b(q))}, off offset:{8 * q}" for q in range(KP - 1)],
            f"global_store_dwordx2 %[bp], {r2(s.b(j))}, off offset:{8 * j}")
@@ -301,9 +375,14 @@ def kernel_body(KP):
 def main():
     out = ["// generated by gen_nnls_lane.py -- do not edit", "#pragma once",
            "#define SGL_NNLS_ASM_INSTANCES(X_) " + " ".join(f"X_({KP})" for KP in KPS)]
+    out.append("// the bounded-tol variant: the ranks whose x lives in the vector registers")
+    out.append("#define SGL_NNLS_ASMB_INSTANCES(X_) " + " ".join(f"X_({KP})" for KP in KPS if not plan(KP)["XA"]))
     for KP in KPS:
         s, L = kernel_body(KP)
         p = plan(KP)
+        if not p["XA"]:   # same registers, same waves per SIMD: NNLS_ASM_VT_ / _NGP_ / _WAVES_ / _VCLOB_ serve both
+            sb, Lb = kernel_body(KP, bounded=True)
+            out.append(f"#define NNLS_ASMB_BODY_{KP} \\\n{sb.text(Lb)}")
         out.append(f"// ---- KP = {KP}: T v{p['V_T']}, D v{p['V_D']}, G v{p['V_G']}, B v{p['V_B']}, X v{p['V_X']}")
         out.append(f"#define NNLS_ASM_VT_{KP} {p['V_T']}")
         out.append(f"#define NNLS_ASM_NGP_{KP} {p['NGP']}")

@@ -41,6 +41,11 @@ int k_nnls_half_launch_asm(hipStream_t s, const double* Gpad, int KP, double* B,
 bool nnls_lane_asm_has(int KP, double L1, int64_t ncols);
 int k_nnls_lane_launch_asm(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
                            int64_t ncols, double L1, double L2, unsigned long long* sweep_counter, const NnlsPass& ps, dim3 g, dim3 b);
+// the generated sweep with the bounded tol (kernels_nnls_asm_bounded.hip): whether it serves this solve, its band delta, its launch
+bool nnls_lane_asm_bounded_has(int KP, double L1, double L2, int64_t ncols);
+double nnls_lane_asm_bounded_band(int KP);
+int k_nnls_lane_launch_asm_bounded(hipStream_t s, const double* Gpad, int KP, double* B, double* X, const int64_t* col_nnz, int k,
+                                   int64_t ncols, double L1, double dlt, unsigned long long* sweep_counter, const NnlsPass& ps, dim3 g, dim3 b);
 
 // The two-lane solves put 32 columns in a wave: the chip is as full at half the columns, and re-packing pays from there --
 // nnls_h per 200 000 columns k = 100 6.56 -> 6.16 ms, k = 128 11.44 -> 10.27 (scripts/r5/r5_step26.sh).
@@ -66,6 +71,16 @@ int nnls_lane_kp(int k, double L1) {
 
 int nnls_scratch_alloc(NnlsScratch& sc, int64_t cap, int k) {
     nnls_scratch_free(sc);
+    // the redo list of the bounded-tol solve (one-lane ranks; k_nnls_lane runs the exact kernels without it)
+    if (k <= 64 && cap > 0) {
+        if (sgl_pool_malloc(&sc.redo_list, sizeof(int32_t) * cap) != hipSuccess || sgl_pool_malloc(&sc.redo_count, sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            nnls_scratch_free(sc);
+            sgl_set_error("NNLS scratch: out of device memory");
+            return SGL_ENOMEM;
+        }
+        sc.redo_cap = cap;
+    }
     // lists / per-column state only where re-packing is used (k_nnls_lane)
     if (cap < nnls_repack_min_cols(k > 64)) return SGL_OK;
     if (sgl_pool_malloc(&sc.list[0], sizeof(int32_t) * cap) != hipSuccess || sgl_pool_malloc(&sc.list[1], sizeof(int32_t) * cap) != hipSuccess ||
@@ -86,6 +101,8 @@ void nnls_scratch_free(NnlsScratch& sc) {
     if (sc.counts) (void)sgl_pool_free(sc.counts);
     if (sc.it_state) (void)sgl_pool_free(sc.it_state);
     if (sc.tol_state) (void)sgl_pool_free(sc.tol_state);
+    if (sc.redo_list) (void)sgl_pool_free(sc.redo_list);
+    if (sc.redo_count) (void)sgl_pool_free(sc.redo_count);
     if (sc.prev_it) (void)sgl_pool_free(sc.prev_it);
     if (sc.packed) (void)sgl_pool_free(sc.packed);
     if (sc.sort_ws) (void)sgl_pool_free(sc.sort_ws);
@@ -206,7 +223,13 @@ int k_nnls_lane(hipStream_t s, const double* Gpad, int KP, double* B, double* X,
     const bool half_asm = two_lane && nnls_half_asm_has(KP, L1);
     auto launch_lane = nnls_lane_asm_has(KP, L1, ncols) ? k_nnls_lane_launch_asm : (KP <= 40) ? k_nnls_lane_launch1 : k_nnls_lane_launch2;
     const dim3 g((unsigned)((ncols + 255) / 256)), b(256);
+    // The bounded tol (one-lane generated sweep, L2 = 0): the passes run the variant whose tol term costs 4 instructions less
+    // and whose stop test is decided on both ends of the tol's error band; the few columns it cannot decide are left as the
+    // pass found them and listed, and the exact kernel resumes them after the last pass (SGL_NNLS_EXACT_TOL=1: exact kernels only).
+    const bool bounded = !two_lane && scr != nullptr && scr->redo_list != nullptr && scr->redo_cap >= ncols && nnls_lane_asm_bounded_has(KP, L1, L2, ncols);
+    const double dlt = bounded ? nnls_lane_asm_bounded_band(KP) : 0.0;
     auto launch = [&](const NnlsPass& ps) {
+        if (bounded && ps.redo_list != nullptr) return k_nnls_lane_launch_asm_bounded(s, Gpad, KP, B, X, col_nnz, k, ncols, L1, dlt, sweep_counter, ps, g, b);
         return half_asm ? k_nnls_half_launch_asm(s, Gpad, KP, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps)
                : two_lane ? k_nnls_half_launch(s, Gpad, KP, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps)
                           : launch_lane(s, Gpad, KP, B, X, col_nnz, k, ncols, L1, L2, sweep_counter, ps, g, b);
@@ -221,6 +244,28 @@ int k_nnls_lane(hipStream_t s, const double* Gpad, int KP, double* B, double* X,
     const int32_t* list0 = nullptr;
     const uint32_t* count0 = nullptr;
     if (prev_it != nullptr && ncols >= 65536 && !getenv("SGL_NNLS_NO_PACK")) SGLCHK(nnls_pack_order(s, *scr, ncols, &list0, &count0));
+    if (bounded) HIPCHK(hipMemsetAsync(scr->redo_count, 0, sizeof(uint32_t), s));
+    // after the last pass: the exact kernel over the redo list, every column from the state its pass found it in and to the end
+    // (launched for the worst case like the later passes: workgroups beyond the list return at once)
+    auto redo = [&](bool resume) {
+        if (!bounded) return (int)SGL_OK;
+        NnlsPass rd = {};
+        rd.list = scr->redo_list;
+        rd.count = scr->redo_count;
+        rd.fresh = resume ? 0 : 1;
+        rd.prev_it = prev_it;
+        rd.it_state = scr->it_state;
+        rd.tol_state = scr->tol_state;
+        SGLCHK(launch(rd));
+        HIPCHK(hipGetLastError());
+        if (getenv("SGL_NNLS_TRACE_REDO")) {   // (A/B runs: synchronises)
+            uint32_t n = 0;
+            HIPCHK(hipMemcpyAsync(&n, scr->redo_count, sizeof(n), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            fprintf(stderr, "nnls redo: %u of %lld columns (k = %d, band %.3g)\n", n, (long long)ncols, k, dlt);
+        }
+        return (int)SGL_OK;
+    };
     if (!repack) {
         NnlsPass one = {};
         one.list = list0;
@@ -228,9 +273,10 @@ int k_nnls_lane(hipStream_t s, const double* Gpad, int KP, double* B, double* X,
         // fresh = 2: a packed single pass of one to two workgroups per CU may pair the longest waves with the shortest (kernels_nnls_asm.hip)
         one.fresh = (list0 != nullptr && !getenv("SGL_NNLS_NO_SNAKE")) ? 2 : 1;
         one.prev_it = prev_it;
+        if (bounded) { one.redo_list = scr->redo_list; one.redo_count = scr->redo_count; }
         SGLCHK(launch(one));
         HIPCHK(hipGetLastError());
-        return SGL_OK;
+        return redo(false);
     }
     // Passes over ever shorter lists; how many columns survive a pass is only known on the device, so
     // every pass is launched for the worst case and workgroups beyond the list return at once.  The
@@ -238,7 +284,8 @@ int k_nnls_lane(hipStream_t s, const double* Gpad, int KP, double* B, double* X,
     HIPCHK(hipMemsetAsync(scr->counts, 0, sizeof(uint32_t) * (SGL_NNLS_MAX_PASSES + 1), s));
     for (int p = 0; p < SGL_NNLS_MAX_PASSES; ++p) {
         const bool last = (p == SGL_NNLS_MAX_PASSES - 1);
-        NnlsPass ps;
+        NnlsPass ps = {};
+        if (bounded) { ps.redo_list = scr->redo_list; ps.redo_count = scr->redo_count; }
         ps.list = p ? scr->list[(p - 1) & 1] : list0;
         ps.count = p ? scr->counts + p : count0;
         ps.fresh = p ? 0 : 1;
@@ -251,7 +298,7 @@ int k_nnls_lane(hipStream_t s, const double* Gpad, int KP, double* B, double* X,
         SGLCHK(launch(ps));
         HIPCHK(hipGetLastError());
     }
-    return SGL_OK;
+    return redo(true);
 }
 
 // ---------------------------------------------------------------------------

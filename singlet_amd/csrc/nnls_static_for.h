@@ -201,3 +201,23 @@ __device__ __forceinline__ void sgl_nnls_pass_exit(const NnlsPass& ps, const Sgl
     }
     sgl_nnls_book_sweeps(sweep_counter, (pc.valid && !unfinished && speaks) ? it : 0, ran);
 }
+// The bounded-tol solve (kernels_nnls_asm_bounded.hip): a lane whose stop test the bounded tol could not decide is TAINTED.  The
+// kernel has stored nothing of it -- B, X, tol_state and it_state hold the state the column entered the pass with -- and
+// sgl_nnls_pass_exit has seen it as a lane without a column (no packing key, no sweeps booked).  It is appended to the redo list
+// (wave-aggregated, like next_list), which the exact kernel runs over after the last pass, resuming every column; a column of
+// a first pass has no saved state yet and gets the one every column starts with.
+__device__ __forceinline__ void sgl_nnls_pass_redo(const NnlsPass& ps, const SglNnlsPassCol& pc, bool tainted) {
+    const unsigned long long tm = __ballot(tainted);
+    if (tm == 0ull) return;
+    const int lane = threadIdx.x & 63;
+    unsigned base = 0;
+    if (lane == 0) base = atomicAdd(ps.redo_count, (unsigned)__popcll(tm));
+    base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+    if (tainted) {
+        ps.redo_list[base + (unsigned)__popcll(tm & ((1ull << lane) - 1ull))] = (int32_t)pc.col;
+        if (!pc.resume && ps.tol_state != nullptr) {
+            ps.tol_state[pc.col] = 1.0;
+            ps.it_state[pc.col] = 0;
+        }
+    }
+}

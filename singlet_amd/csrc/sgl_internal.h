@@ -124,6 +124,9 @@ struct NnlsPass {
     int32_t final_below;  // a pass over at most this many columns runs them to the end
     int32_t fresh;        // list != nullptr but nothing to resume: a first pass over columns given in packing order (below)
     uint8_t* prev_it;     // sweeps a column needed, written when it stops: the packing key of the NEXT solve (nullptr: not kept)
+    // the bounded-tol solve (kernels_nnls_asm_bounded.hip): the columns whose stop test it could not decide, for the exact kernel
+    int32_t* redo_list;
+    uint32_t* redo_count;
 };
 // device scratch of the multi-pass solve, sized for `cap` columns (owned by the caller)
 struct NnlsScratch {
@@ -138,6 +141,10 @@ struct NnlsScratch {
     int32_t* packed = nullptr;
     uint32_t* sort_ws = nullptr;  // [128 * nblocks + 2]
     int64_t pack_cap = 0;
+    // the redo list of the bounded-tol solve and its length (a device word)
+    int32_t* redo_list = nullptr;
+    uint32_t* redo_count = nullptr;
+    int64_t redo_cap = 0;
 };
 
 // The cross-validation mask of one orientation as lists: idx[ptr[c] .. ptr[c + 1]) = the rows r (ascending) with
