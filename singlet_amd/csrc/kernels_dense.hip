@@ -79,6 +79,139 @@ __global__ __launch_bounds__(256) void gram_mfma_kernel(const double* __restrict
         }
 }
 
+// scale(h, d) and AAt(h) in ONE pass over F (the H side of an iteration, k <= 64): gram_mfma_kernel with the division of
+// scale_kernel in front of its MFMAs.  Every element of F is an MFMA operand of exactly one lane, exactly once (wave w of a
+// block owns the columns c = c_begin + 4 w (mod 16), lane (r16, kk) row b * 16 + r16 of column c + kk), so that lane forms
+// the quotient f / d[row], stores it back in place and feeds it to the MFMAs: the quotient is scale_kernel's, and column
+// ownership, tile order, LDS reduction and partial layout are gram_mfma_kernel's, so F and the partials come out bit for
+// bit as from the two kernels, with 800 MB moved at config 3 instead of 1200 and one launch less.
+// The operands of the next SG_DEPTH - 1 steps are loaded before a step's divisions and MFMAs issue, which takes the pass
+// off its load latency (gram_mfma_kernel has nothing in flight across its steps).  At NT = 4: 188 VGPRs (accumulators
+// included), two waves per SIMD like gram_mfma_kernel<4> (184); 0.157 ms at 1 000 000 x 50 against 0.130 + 0.191 ms.
+#define SG_DEPTH 4
+template <int NT>
+__global__ __launch_bounds__(256, 2) void scale_gram_mfma_kernel(double* __restrict__ F, int k, int64_t cols, int64_t cols_per_block,
+                                                              const double* __restrict__ d, double* __restrict__ part) {
+    constexpr int NTILES = NT * (NT + 1) / 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r16 = lane & 15, kk = lane >> 4;
+    const int64_t c_begin = (int64_t)blockIdx.x * cols_per_block;
+    int64_t c_end = c_begin + cols_per_block;
+    if (c_end > cols) c_end = cols;
+
+    d4 acc[NTILES];
+#pragma unroll
+    for (int t = 0; t < NTILES; ++t) acc[t] = d4{0, 0, 0, 0};
+    // Rows: the blocks b < NT - 1 lie inside k whole; in the last one the lanes past row k - 1 read row k - 1 along (an
+    // address inside F, a quotient nobody uses), store nothing and hand 0.0 to the MFMAs: the loads of a full step carry no
+    // lane-dependent branch, which is what lets the compiler count them down (s_waitcnt vmcnt(n)) instead of draining them.
+    int roff[NT];   // this lane's row in block b (clamped)
+    double dv[NT];
+#pragma unroll
+    for (int b = 0; b < NT; ++b) {
+        const int row = b * 16 + r16;
+        roff[b] = (row < k) ? row : k - 1;
+        dv[b] = d[roff[b]];
+    }
+    const bool last_row_in = (NT - 1) * 16 + r16 < k;
+
+    auto mfmas = [&](const double (&v)[NT]) {
+        int t = 0;
+#pragma unroll
+        for (int bi = 0; bi < NT; ++bi)
+#pragma unroll
+            for (int bj = 0; bj <= bi; ++bj) {
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(v[bi], v[bj], acc[t], 0, 0, 0);
+                ++t;
+            }
+    };
+    // a FULL step (its four columns c .. c + 3 all below c_end): this lane's NT elements loaded ...
+    auto load = [&](int64_t c, double (&f)[NT]) {
+        const double* col = F + (c + kk) * k;
+#pragma unroll
+        for (int b = 0; b < NT; ++b) f[b] = col[roff[b]];
+    };
+    // ... divided, stored back and multiplied into the tiles
+    auto step = [&](int64_t c, const double (&f)[NT]) {
+        double* col = F + (c + kk) * k;
+        double v[NT];
+#pragma unroll
+        for (int b = 0; b < NT; ++b) v[b] = f[b] / dv[b];
+#pragma unroll
+        for (int b = 0; b < NT - 1; ++b) col[roff[b]] = v[b];
+        if (last_row_in) col[roff[NT - 1]] = v[NT - 1];
+        else v[NT - 1] = 0.0;
+        mfmas(v);
+    };
+
+    // The wave's full steps c_first, c_first + 16, ...: the loads of the next SG_DEPTH - 1 steps are in flight while a step
+    // divides and multiplies.  A turn of the loop takes SG_DEPTH steps so that every buffer index is static (a copy from
+    // buffer to buffer would wait for the load); past the last full step the look-ahead loads that step again (no
+    // branch, a line in cache, never used), and the steps left over after the last whole turn find their loads made.
+    const int64_t c_first = c_begin + 4 * wave;
+    const int64_t nfull = (c_end - c_first >= 4) ? (c_end - c_first - 4) / 16 + 1 : 0;
+    if (nfull > 0) {
+        double f[SG_DEPTH][NT];
+        auto at = [&](int64_t i) { return c_first + 16 * ((i < nfull) ? i : nfull - 1); };
+#pragma unroll
+        for (int j = 0; j < SG_DEPTH - 1; ++j) load(at(j), f[j]);
+        int64_t i = 0;
+        for (; i + SG_DEPTH <= nfull; i += SG_DEPTH) {
+#pragma unroll
+            for (int j = 0; j < SG_DEPTH; ++j) {
+                load(at(i + j + SG_DEPTH - 1), f[(j + SG_DEPTH - 1) % SG_DEPTH]);
+                step(c_first + 16 * (i + j), f[j]);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < SG_DEPTH - 1; ++j)
+            if (i + j < nfull) step(c_first + 16 * (i + j), f[j]);
+    }
+    // the ragged step at the end of F (one to three columns; only the last block has one): gram_mfma_kernel's guarded form
+    const int64_t c_tail = c_first + 16 * nfull;
+    if (c_tail < c_end) {
+        const int64_t cc = c_tail + kk;
+        double v[NT];
+#pragma unroll
+        for (int b = 0; b < NT; ++b) {
+            const int row = b * 16 + r16;
+            v[b] = 0.0;
+            if (cc < c_end && row < k) {
+                v[b] = F[cc * k + row] / dv[b];
+                F[cc * k + row] = v[b];
+            }
+        }
+        mfmas(v);
+    }
+
+    // reduce the 4 waves through LDS, then write the block's partial: gram_mfma_kernel's epilogue
+    __shared__ double sm[4][64 * 4];
+    double* out = part + (size_t)blockIdx.x * k * k;
+    int t = 0;
+#pragma unroll
+    for (int bi = 0; bi < NT; ++bi)
+#pragma unroll
+        for (int bj = 0; bj <= bi; ++bj) {
+            __syncthreads();
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sm[wave][lane * 4 + r] = acc[t][r];
+            __syncthreads();
+            if (wave == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double v = ((sm[0][lane * 4 + r] + sm[1][lane * 4 + r]) + sm[2][lane * 4 + r]) + sm[3][lane * 4 + r];
+                    const int row = bi * 16 + kk + 4 * r;  // D row (lane>>4) + 4r
+                    const int col = bj * 16 + r16;         // D col lane & 15
+                    if (row < k && col < k) {
+                        out[(size_t)col * k + row] = v;
+                        if (bi != bj) out[(size_t)row * k + col] = v;
+                    }
+                }
+            }
+            ++t;
+        }
+}
+
 // 64 < k <= 128 (NT = 5 .. 8): all NT (NT + 1) / 2 tiles no longer fit one wave's registers, so the tiles
 // are dealt out to the 4 waves of the workgroup (tile t to wave t % 4) and every wave walks ALL columns of
 // the block's chunk (the operand loads of the 4 waves hit the same cache lines).  No cross-wave reduction:
@@ -266,17 +399,25 @@ static int sgl_partial_sum(sgl_ctx* c, int nblocks, int n, int diag_k, double di
 
 int k_gram_big_partials(hipStream_t s, const double* F, int k, int64_t cols, int64_t cols_per_block, int nblocks, double* part);   // kernels_gram_big.hip
 
-int k_gram(sgl_ctx* c, const double* F, int k, int64_t cols, double* G, double diag_add) {
-    if (k <= 0 || k > SGL_MAX_K) { sgl_set_error("k_gram: k=%d out of range", k); return SGL_EINVAL; }
+// the column chunks of a Gram pass: at most max_blocks blocks of whole 16-column steps
+static void gram_chunks(int64_t cols, int max_blocks, int* nblocks_out, int64_t* cpb_out) {
     int nblocks = (int)((cols + 255) / 256);        // (at least 16 columns per block; fills the chip from ~65 000 columns on)
-    if (nblocks > 1024) nblocks = 1024;
-    const bool big_mfma = k > 128 && k <= 256 && !getenv("SGL_GRAM_BIG_VALU");   // ranks 129 - 256 on the matrix cores (kernels_gram_big.hip)
-    if (k > 128 && nblocks > (big_mfma ? 512 : 128)) nblocks = big_mfma ? 512 : 128;   // k x k doubles of workspace per block
+    if (nblocks > max_blocks) nblocks = max_blocks;
     if (nblocks < 1) nblocks = 1;
     int64_t cpb = (cols + nblocks - 1) / nblocks;
     cpb = (cpb + 15) / 16 * 16;  // whole 16-column steps per block
     nblocks = (int)((cols + cpb - 1) / cpb);
     if (nblocks < 1) nblocks = 1;
+    *nblocks_out = nblocks;
+    *cpb_out = cpb;
+}
+
+int k_gram(sgl_ctx* c, const double* F, int k, int64_t cols, double* G, double diag_add) {
+    if (k <= 0 || k > SGL_MAX_K) { sgl_set_error("k_gram: k=%d out of range", k); return SGL_EINVAL; }
+    const bool big_mfma = k > 128 && k <= 256 && !getenv("SGL_GRAM_BIG_VALU");   // ranks 129 - 256 on the matrix cores (kernels_gram_big.hip)
+    int nblocks;
+    int64_t cpb;
+    gram_chunks(cols, k <= 128 ? 1024 : big_mfma ? 512 : 128, &nblocks, &cpb);   // (above 128: k x k doubles of workspace per block)
     SGLCHK(sgl_ws_reserve(c, sizeof(double) * sgl_partial_ws(nblocks, k * k)));
     hipStream_t s = c->stream;
     const int NT = (k + 15) / 16;
@@ -296,6 +437,29 @@ int k_gram(sgl_ctx* c, const double* F, int k, int64_t cols, double* G, double d
             gram_valu_kernel<<<dim3(nblocks), dim3(256), lds, s>>>(F, k, cols, cpb, c->ws, pair0);
     }
     HIPCHK(hipGetLastError());
+    return sgl_partial_sum(c, nblocks, k * k, k, diag_add, G);
+}
+
+// F[i, c] /= d[i] in place and G = F F^T (+ diag_add on the diagonal) of the quotients, k <= 64: the blocks and the columns
+// per block of k_gram at these ranks, scale_gram_mfma_kernel, the partial sum of k_gram.  d carries its + 1e-15 already.
+// The timings count the pass as scale and the sum of its partials as Gram.
+int k_scale_gram(sgl_ctx* c, double* F, int k, int64_t cols, const double* d, double* G, double diag_add) {
+    if (k <= 0 || k > 64) { sgl_set_error("k_scale_gram: k=%d out of range", k); return SGL_EINVAL; }
+    int nblocks;
+    int64_t cpb;
+    gram_chunks(cols, 1024, &nblocks, &cpb);
+    SGLCHK(sgl_ws_reserve(c, sizeof(double) * sgl_partial_ws(nblocks, k * k)));
+    {
+        Phase ph(c, SGL_PH_SCALE);
+        hipStream_t s = c->stream;
+        const int NT = (k + 15) / 16;
+        if (NT == 1) scale_gram_mfma_kernel<1><<<dim3(nblocks), dim3(256), 0, s>>>(F, k, cols, cpb, d, c->ws);
+        else if (NT == 2) scale_gram_mfma_kernel<2><<<dim3(nblocks), dim3(256), 0, s>>>(F, k, cols, cpb, d, c->ws);
+        else if (NT == 3) scale_gram_mfma_kernel<3><<<dim3(nblocks), dim3(256), 0, s>>>(F, k, cols, cpb, d, c->ws);
+        else scale_gram_mfma_kernel<4><<<dim3(nblocks), dim3(256), 0, s>>>(F, k, cols, cpb, d, c->ws);
+        HIPCHK(hipGetLastError());
+    }
+    Phase ph(c, SGL_PH_GRAM);
     return sgl_partial_sum(c, nblocks, k * k, k, diag_add, G);
 }
 
@@ -380,11 +544,14 @@ __global__ void scale_kernel(double* __restrict__ F, int k, int64_t n, const dou
         F[t] = F[t] / d[t % k];
 }
 
+int k_add_eps(hipStream_t s, double* d, int k) {
+    add_eps_kernel<<<dim3((k + 63) / 64), dim3(64), 0, s>>>(d, k);
+    HIPCHK(hipGetLastError());
+    return SGL_OK;
+}
+
 int k_scale_apply(hipStream_t s, double* F, int k, int64_t cols, double* d, int add_eps) {
-    if (add_eps) {
-        add_eps_kernel<<<dim3((k + 63) / 64), dim3(64), 0, s>>>(d, k);
-        HIPCHK(hipGetLastError());
-    }
+    if (add_eps) SGLCHK(k_add_eps(s, d, k));
     const int64_t n = (int64_t)k * cols;
     if (n <= 0) return SGL_OK;
     int64_t blocks = (n + 255) / 256;

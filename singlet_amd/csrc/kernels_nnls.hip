@@ -131,49 +131,46 @@ __global__ __launch_bounds__(256) void nnls_pack_hist_kernel(const uint8_t* __re
     // bin-major, longest first: entry (bin b, block) at [(BINS - 1 - b) * nblocks + block]
     if (threadIdx.x < SGL_PACK_BINS) hist[(size_t)(SGL_PACK_BINS - 1 - threadIdx.x) * nblocks + blockIdx.x] = h[threadIdx.x];
 }
-// exclusive scan of the BINS * nblocks counts in place (one workgroup; <= 128 * 512 entries at a million columns)
-__global__ __launch_bounds__(1024) void nnls_pack_scan_kernel(uint32_t* __restrict__ hist, int total, uint32_t* __restrict__ n_out) {
-    __shared__ unsigned part[1024];
-    const int per = (total + 1023) / 1024;
-    const int a = threadIdx.x * per, b = (a + per < total) ? a + per : total;
+// The exclusive scan of the BINS * nblocks counts, spread over the chip (one workgroup walking all of them took 33 us per
+// solve at a million columns): workgroup r scans row r -- one key's counts over the blocks -- in place and leaves the row's sum
+// in tot[r]; the 128 row sums are scanned by every workgroup of the scatter kernel for itself, which adds its rows' bases.
+// The offsets a column sees are those of the one flat scan: bin-major, the longest bin first.
+__global__ __launch_bounds__(256) void nnls_pack_scan_kernel(uint32_t* __restrict__ hist, int nblocks, uint32_t* __restrict__ tot) {
+    __shared__ unsigned part[256];
+    uint32_t* row = hist + (size_t)blockIdx.x * nblocks;
+    const int per = (nblocks + 255) / 256;
+    const int a = (threadIdx.x * per < (unsigned)nblocks) ? threadIdx.x * per : nblocks, b = (a + per < nblocks) ? a + per : nblocks;
     unsigned s = 0;
-    {   // (eight independent loads per step: one at a time the thread's ~60 strided reads were 90 us of pure latency per solve)
-        int e = a;
-        for (; e + 8 <= b; e += 8) {
-            unsigned v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = hist[e + q];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) s += v[q];
-        }
-        for (; e < b; ++e) s += hist[e];
-    }
+    for (int e = a; e < b; ++e) s += row[e];
     part[threadIdx.x] = s;
     __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
+    for (int off = 1; off < 256; off <<= 1) {
         const unsigned v = (threadIdx.x >= (unsigned)off) ? part[threadIdx.x - off] : 0u;
         __syncthreads();
         part[threadIdx.x] += v;
         __syncthreads();
     }
     unsigned run = part[threadIdx.x] - s;
-    {
-        int e = a;
-        for (; e + 8 <= b; e += 8) {
-            unsigned v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = hist[e + q];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { hist[e + q] = run; run += v[q]; }
-        }
-        for (; e < b; ++e) { const unsigned c = hist[e]; hist[e] = run; run += c; }
-    }
-    if (threadIdx.x == 1023) *n_out = part[1023];
+    for (int e = a; e < b; ++e) { const unsigned c = row[e]; row[e] = run; run += c; }
+    if (threadIdx.x == 255) tot[blockIdx.x] = part[255];
 }
 __global__ __launch_bounds__(256) void nnls_pack_scatter_kernel(const uint8_t* __restrict__ key, int64_t n, int nblocks,
-                                                                const uint32_t* __restrict__ offs, int32_t* __restrict__ packed) {
+                                                                const uint32_t* __restrict__ offs, const uint32_t* __restrict__ tot,
+                                                                uint32_t* __restrict__ n_out, int32_t* __restrict__ packed) {
     __shared__ unsigned cur[SGL_PACK_BINS];
-    if (threadIdx.x < SGL_PACK_BINS) cur[threadIdx.x] = offs[(size_t)(SGL_PACK_BINS - 1 - threadIdx.x) * nblocks + blockIdx.x];
+    __shared__ unsigned base[SGL_PACK_BINS];   // inclusive scan of the row sums
+    const unsigned mine = (threadIdx.x < SGL_PACK_BINS) ? tot[threadIdx.x] : 0u;
+    if (threadIdx.x < SGL_PACK_BINS) base[threadIdx.x] = mine;
+    __syncthreads();
+    for (int off = 1; off < SGL_PACK_BINS; off <<= 1) {
+        const unsigned v = (threadIdx.x < SGL_PACK_BINS && threadIdx.x >= (unsigned)off) ? base[threadIdx.x - off] : 0u;
+        __syncthreads();
+        if (threadIdx.x < SGL_PACK_BINS) base[threadIdx.x] += v;
+        __syncthreads();
+    }
+    // thread r holds row r = the key BINS - 1 - r
+    if (threadIdx.x < SGL_PACK_BINS) cur[SGL_PACK_BINS - 1 - threadIdx.x] = offs[(size_t)threadIdx.x * nblocks + blockIdx.x] + (base[threadIdx.x] - mine);
+    if (blockIdx.x == 0 && threadIdx.x == SGL_PACK_BINS - 1) *n_out = base[SGL_PACK_BINS - 1];
     __syncthreads();
     const int64_t c0 = (int64_t)blockIdx.x * SGL_PACK_CPB;
     for (int q = threadIdx.x; q < SGL_PACK_CPB; q += 256) {
@@ -190,7 +187,7 @@ int nnls_pack_alloc(NnlsScratch& sc, int64_t ncols) {
     sc.prev_it = nullptr; sc.packed = nullptr; sc.sort_ws = nullptr; sc.pack_cap = 0;
     const int64_t nblocks = (ncols + SGL_PACK_CPB - 1) / SGL_PACK_CPB;
     if (sgl_pool_malloc(&sc.prev_it, (size_t)ncols) != hipSuccess || sgl_pool_malloc(&sc.packed, sizeof(int32_t) * (size_t)ncols) != hipSuccess ||
-        sgl_pool_malloc(&sc.sort_ws, sizeof(uint32_t) * ((size_t)SGL_PACK_BINS * nblocks + 4)) != hipSuccess ||
+        sgl_pool_malloc(&sc.sort_ws, sizeof(uint32_t) * ((size_t)SGL_PACK_BINS * nblocks + 4 + SGL_PACK_BINS)) != hipSuccess ||
         hipMemset(sc.prev_it, 0, (size_t)ncols) != hipSuccess) {
         (void)hipGetLastError();
         sgl_set_error("NNLS packing scratch: out of device memory");
@@ -206,8 +203,9 @@ static int nnls_pack_order(hipStream_t s, const NnlsScratch& scr, int64_t ncols,
     const int nblocks = (int)((ncols + SGL_PACK_CPB - 1) / SGL_PACK_CPB);
     uint32_t* n_dev = scr.sort_ws + (size_t)SGL_PACK_BINS * nblocks;
     nnls_pack_hist_kernel<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(scr.prev_it, ncols, nblocks, scr.sort_ws);
-    nnls_pack_scan_kernel<<<dim3(1), dim3(1024), 0, s>>>(scr.sort_ws, SGL_PACK_BINS * nblocks, n_dev);
-    nnls_pack_scatter_kernel<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(scr.prev_it, ncols, nblocks, scr.sort_ws, scr.packed);
+    uint32_t* tot = n_dev + 4;   // the SGL_PACK_BINS row sums
+    nnls_pack_scan_kernel<<<dim3(SGL_PACK_BINS), dim3(256), 0, s>>>(scr.sort_ws, nblocks, tot);
+    nnls_pack_scatter_kernel<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(scr.prev_it, ncols, nblocks, scr.sort_ws, tot, n_dev, scr.packed);
     HIPCHK(hipGetLastError());
     *order = scr.packed;
     if (count) *count = n_dev;

@@ -139,7 +139,7 @@ struct NnlsScratch {
     // order of it, and the counting sort's workspace
     uint8_t* prev_it = nullptr;
     int32_t* packed = nullptr;
-    uint32_t* sort_ws = nullptr;  // [128 * nblocks + 2]
+    uint32_t* sort_ws = nullptr;  // [128 * nblocks + 4 + 128]: counts / offsets, the list length, the 128 bin totals
     int64_t pack_cap = 0;
     // the redo list of the bounded-tol solve and its length (a device word)
     int32_t* redo_list = nullptr;
@@ -393,6 +393,9 @@ int k_gram_add_diag(hipStream_t s, double* G, int k, double v);
 int k_rowsum(sgl_ctx* c, const double* F, int k, int64_t cols, double* d_out, int add_eps = 0);  // add_eps: + 1e-15 in the final stage
 bool k_rowsum_can_add_eps(int k, int64_t cols);
 int k_scale_apply(hipStream_t s, double* F, int k, int64_t cols, double* d, int add_eps);
+int k_add_eps(hipStream_t s, double* d, int k);   // d += 1e-15, the kernel of k_scale_apply(add_eps = 1)
+// k_scale_apply(add_eps = 0) and k_gram of the scaled F in one pass over F, bit for bit (k <= 64)
+int k_scale_gram(sgl_ctx* c, double* F, int k, int64_t cols, const double* d, double* G, double diag_add);
 int k_cor(sgl_ctx* c, const double* x, const double* y, int64_t n, double* out_dev);
 int k_pad_gram(hipStream_t s, const double* G, int k, int KP, int GS, double* Gpad);
 int k_gram_rescale(hipStream_t s, double* G, int k, const double* d, double diag_add);  // G[i,j] = G[i,j] / d_i / d_j (+ diag_add)

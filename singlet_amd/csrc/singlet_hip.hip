@@ -1205,21 +1205,40 @@ extern "C" int sgl_step_h(sgl_ctx* c, double L1, double L2) {
     return sgl_step_h_solve(c, L1, L2, false);
 }
 
+// What the scale step of an iteration hands to its W step: the Gram of the scaled H, formed in the pass that scaled it
+// (k_scale_gram).  It travels as an argument inside sgl_iterate_shard only -- the context keeps no flag, so nothing outside
+// one iteration can meet a stale Gram, and the public step entries run the separate kernels.
+enum HGram {
+    HGRAM_NONE = 0,   // not formed: the W step runs k_gram
+    HGRAM_LOCAL,      // this shard's sum in c->G, without the ridge: to be all-reduced with the right-hand sides
+    HGRAM_DONE        // c->G is complete, ridge included (one shard, no hook)
+};
+
 // scale(h, d): src/singlet.cpp:219-225; row sums are global over all shards
-extern "C" int sgl_step_scale_h(sgl_ctx* c) {
+static int scale_h(sgl_ctx* c, HGram* gram) {
     FIT_GUARD(c);
     if (c->team && sgl_team_size(c) > 1) { sgl_set_error("step API on a native team: use sgl_nmf_iterate / sgl_multi_iterate"); return SGL_ESTATE; }
     // (one shard: the + 1e-15 of l.221 rides in the row sums' final stage; with a hook the sums are all-reduced first)
     const int eps_in_sum = (!c->allreduce && k_rowsum_can_add_eps(c->k, c->A.ncol)) ? 1 : 0;
     { Phase ph(c, SGL_PH_SCALE); SGLCHK(k_rowsum(c, c->H, c->k, c->A.ncol, c->d, eps_in_sum)); }
     SGLCHK(do_allreduce(c, c->d, c->k));
+    if (gram != nullptr && c->k <= 64) {
+        // the W step's Gram in the same pass; c->G (the Gram of W the H solve is done with) is free until the W solve.
+        // One shard: the ridge of AAt (l.204) in the partial sum, the one addition k_gram_add_diag makes
+        if (!eps_in_sum) { Phase ph(c, SGL_PH_SCALE); SGLCHK(k_add_eps(c->stream, c->d, c->k)); }
+        SGLCHK(k_scale_gram(c, c->H, c->k, c->A.ncol, c->d, c->G, c->allreduce ? 0.0 : 1e-15));
+        *gram = c->allreduce ? HGRAM_LOCAL : HGRAM_DONE;
+        return SGL_OK;
+    }
     { Phase ph(c, SGL_PH_SCALE); SGLCHK(k_scale_apply(c->stream, c->H, c->k, c->A.ncol, c->d, eps_in_sum ? 0 : 1)); }
     return SGL_OK;
 }
 
+extern "C" int sgl_step_scale_h(sgl_ctx* c) { return scale_h(c, nullptr); }
+
 // predict(At, h, w, L1, L2): right-hand sides and Gram are sums over cells ->
 // one all-reduce of [k*m | k*k] doubles when sharded.
-extern "C" int sgl_step_w(sgl_ctx* c, double L1, double L2) {
+static int update_w(sgl_ctx* c, double L1, double L2, HGram gram) {
     FIT_GUARD(c);
     if (c->team && sgl_team_size(c) > 1) { sgl_set_error("step API on a native team: use sgl_nmf_iterate / sgl_multi_iterate"); return SGL_ESTATE; }
     const int k = c->k;
@@ -1235,18 +1254,24 @@ extern "C" int sgl_step_w(sgl_ctx* c, double L1, double L2) {
       if (c->dense_gemm) SGLCHK(k_dense_rhs(c, 1, F, k, Bw));
       else if (c->use_tiled && c->TAt.roff) SGLCHK(k_acc_tiled_all(c->stream, c->TAt, F, Bw, k));
       else SGLCHK(k_acc(c->stream, c->At, F, k, Bw, 0, 1, 0, 0, 0)); }
-    { Phase ph(c, SGL_PH_GRAM); SGLCHK(k_gram(c, c->H, k, c->A.ncol, Gh, 0.0)); }
-    SGLCHK(do_allreduce(c, c->red, (int64_t)k * m + (int64_t)k * k));
-    { Phase ph(c, SGL_PH_GRAM);
-      // G = Gh + 1e-15 I (AAt, src/singlet.cpp:204) -- reuse the scale kernel family: tiny
-      HIPCHK(hipMemcpyAsync(c->G, Gh, sizeof(double) * k * k, hipMemcpyDeviceToDevice, c->stream));
-      SGLCHK(k_gram_add_diag(c->stream, c->G, k, 1e-15)); }
+    if (gram != HGRAM_DONE) {
+        { Phase ph(c, SGL_PH_GRAM);
+          if (gram == HGRAM_LOCAL) HIPCHK(hipMemcpyAsync(Gh, c->G, sizeof(double) * k * k, hipMemcpyDeviceToDevice, c->stream));   // behind the right-hand sides, as k_gram puts it
+          else SGLCHK(k_gram(c, c->H, k, c->A.ncol, Gh, 0.0)); }
+        SGLCHK(do_allreduce(c, c->red, (int64_t)k * m + (int64_t)k * k));
+        { Phase ph(c, SGL_PH_GRAM);
+          // G = Gh + 1e-15 I (AAt, src/singlet.cpp:204) -- reuse the scale kernel family: tiny
+          HIPCHK(hipMemcpyAsync(c->G, Gh, sizeof(double) * k * k, hipMemcpyDeviceToDevice, c->stream));
+          SGLCHK(k_gram_add_diag(c->stream, c->G, k, 1e-15)); }
+    }
     { Phase ph(c, SGL_PH_NNLS_W);
       if (c->link_w) SGLCHK(k_link_mul(c->stream, Bw, c->link_w, k, c->link_w_rows, m));  // on the complete (all-reduced) sums
       else if (c->glink_w.table) SGLCHK(k_link_mul_grouped(c->stream, Bw, c->glink_w.table, c->glink_w.group, k, c->glink_w.rows, c->glink_w.groups, m));
       SGLCHK(sgl_nnls_shared(c, c->G, Bw, c->W, (c->solve_empty || c->graph.n) ? nullptr : gene_nnz, m, L1, L2, c->sweep_counters + 1)); }
     return SGL_OK;
 }
+
+extern "C" int sgl_step_w(sgl_ctx* c, double L1, double L2) { return update_w(c, L1, L2, HGRAM_NONE); }
 
 // scale(w, d); tol = cor(w, w_it): src/singlet.cpp:655-659
 int sgl_scale_w_enqueue(sgl_ctx* c) {
@@ -1295,9 +1320,11 @@ int sgl_iterate_shard(sgl_ctx* c, double L1_w, double L1_h, double L2_w, double 
                       double* tol) {
     SGLCHK(sgl_step_begin(c));
     SGLCHK(mask ? sgl_step_h_masked(c, L1_h, L2_h, mask->seed, mask->inv_density) : sgl_step_h(c, L1_h, L2_h));
-    SGLCHK(sgl_step_scale_h(c));
+    // the plain fit off a native team: H is scaled and its Gram formed in one pass, handed from the scale step to the W step
+    HGram gram = HGRAM_NONE;
+    SGLCHK(scale_h(c, (mask == nullptr && c->team == nullptr) ? &gram : nullptr));
     if (interrupted(cb)) return SGL_EINTR;
-    SGLCHK(mask ? sgl_step_w_masked(c, L1_w, L2_w, mask->seed, mask->inv_density) : sgl_step_w(c, L1_w, L2_w));
+    SGLCHK(mask ? sgl_step_w_masked(c, L1_w, L2_w, mask->seed, mask->inv_density) : update_w(c, L1_w, L2_w, gram));
     return sgl_step_scale_w(c, tol);
 }
 
