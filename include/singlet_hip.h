@@ -757,6 +757,56 @@ SGL_API int sgl_c_knn(const double* R, int32_t k, int64_t n_ref, const double* Q
  * candidate lists lay in LDS, 1 in global scratch.  A refused call leaves it as it was. */
 SGL_API int sgl_knn_info(sgl_ctx* ctx, int64_t out[4]);
 
+/* The same search under a metric: 0 Euclidean -- sgl_knn's own code, bit for bit --, 1 cosine, 2 correlation (Seurat's
+ * RunUMAP defaults to metric = "cosine", and FindNeighbors offers it as annoy.metric: a column of H scales with the cell's
+ * total signal, and Euclidean neighbours group cells by magnitude as much as by programme).  Everything not stated here is
+ * as in sgl_knn: R / Q / dims, the refusals, the finiteness pass on the RAW operands with the same messages, the team and
+ * hook refusal, the segments and their merge, and that the call only reads the context.  tests/knn_metric_restatement.py
+ * restates the rules in numpy.  All arithmetic is FP64, every product and every addition its own rounding, everything
+ * sequential in the listed order of the selected dimensions.
+ *
+ *  1. unit columns -- per column x of R and of Q, after dims has been applied, over the nd selected rows:
+ *       correlation:  m = +0.0;  for f: m = m + x_f;  m = m / (double)nd;  y_f = x_f - m          cosine:  y = x
+ *       s2 = +0.0;  for f: s2 = s2 + y_f * y_f;   nrm = sqrt(s2) (the IEEE root)
+ *       u_f = y_f / nrm (an IEEE division, not a reciprocal multiply) when nrm != 0;   u_f = +0.0 for every f when nrm == 0
+ *     Nothing else is special-cased.  An s2 that overflows gives nrm = +Inf and u_f = +-0; an s2 that underflows to 0 gives
+ *     the zero column.  Such a column -- nrm == 0 or nrm == +Inf -- "has no direction"; it is not refused (cells with an
+ *     all-zero h exist, and a constant column has no correlation), it is counted (sgl_knn_metric_info).  (Correlation only:
+ *     a column whose plain sum overflows has m = +-Inf and a NaN unit column; its keys are NaN and its rank is not defined.
+ *     That takes values above about 1.8e308 / nd.)
+ *  2. key of a pair:  dot = +0.0;  for f: dot = dot + uq_f * ur_f;   key = 1.0 - dot;   key < 2^-40  ->  key = +0.0.
+ *     The snap: for two bitwise-equal unit columns with a direction, |1 - dot| is the rounding of the rule itself, at most
+ *     about (2 nd + 4) 2^-53 <= 2^-42 at nd = 1024 (measured on the CPU over nd = 1 .. 1024: 22 ulp of 1 for cosine, 182 for
+ *     correlation, against the 4096 of the limit).  So a cell is at exactly +0.0 from itself, from its exact duplicates and
+ *     from its copies scaled by a power of two; such pairs rank by index, as under sgl_knn, and the fuzzy graph's rho (the
+ *     smallest distance > 0) skips them.  The guarantee covers bitwise-equal unit columns only: a pair that is parallel up
+ *     to rounding gets what the rule gives (a correlation pair x, 3.7 x can land above the limit through the cancellation
+ *     in the mean).  key is never negative and at most 2 + eps; a column without direction has key 1.0 to every column,
+ *     itself included.
+ *  3. ranking by (key, reference index) ascending, a total order; dist_out receives the key itself, not a root (uwot and
+ *     umap-learn report 1 - cos the same way).  With Q == NULL nothing is special-cased by index.
+ *
+ *  - metric outside [0, 2]: SGL_EINVAL, "<entry>: metric = 7 is outside [0, 2]", after the argument refusals of sgl_knn and
+ *    before anything is launched (sgl_c_knn_metric: before a context is made).
+ *  - the unit columns are the call's own buffers (2 x 8 x nd x n bytes moved per operand); the resident H is never written.
+ *  - kernels: knn_unit writes the packed unit operands in place of the gather, one sequential lane per column, the tile
+ *    staged through LDS so that global memory is read and written in runs of 32 doubles; it counts the columns without
+ *    direction with an integer atomic.  The scan kernels of sgl_knn have a second inner form: per (pair, dimension) v_mul_f64
+ *    and v_add_f64 with the reference coordinate as the scalar operand -- two FP64 vector instructions where the Euclidean
+ *    form issues three --, the key once per pair; candidates, lists, segments and merge are shared, and the merge takes no
+ *    root.  A fused multiply-add form is deliberately not built: the rule is uncontracted arithmetic.  With timing on, the
+ *    scan and merge count in the "scale" phase as under sgl_knn, and knn_unit alone in the "gram" phase. */
+SGL_API int sgl_knn_metric(sgl_ctx* ctx, const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query,
+                           const int32_t* dims, int32_t n_dims, int32_t n_neighbors, int32_t metric, int32_t* idx_out,
+                           double* dist_out);
+SGL_API int sgl_c_knn_metric(const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query,
+                             const int32_t* dims, int32_t n_dims, int32_t n_neighbors, int32_t metric, int32_t* idx_out,
+                             double* dist_out);
+/* out[0 .. 3] as sgl_knn_info; [4] the metric of the last search on this context (a plain sgl_knn: 0); [5] the number of
+ * columns without direction among its operands -- the columns of R, plus those of Q when Q was given; 0 for Euclidean.  A
+ * refused call leaves it as it was. */
+SGL_API int sgl_knn_metric_info(sgl_ctx* ctx, int64_t out[6]);
+
 /* Clustering: a deterministic multi-level Louvain modularity optimiser on a neighbour graph -- the step after
  * find_neighbors (Seurat's FindClusters on the SNN graph).  The reference's package has no clustering code (it hands the
  * graph to Seurat, whose optimiser visits the vertices in a seeded random order), so the rules below are this library's own,
@@ -844,7 +894,7 @@ SGL_API int sgl_louvain_info(int64_t out[4]);
  * with uwot or umap-learn is claimed (DESIGN.md "Layout").  One-shot on the current device; no team form, no R shim entry.
  * All arithmetic is FP64, every product and addition its own rounding (the unit is compiled with -ffp-contract=off).
  *
- * 1. sgl_c_fuzzy_graph.  Input: what sgl_knn returns for n cells: idx int32 and dist double (the roots), both K x n
+ * 1. sgl_c_fuzzy_graph.  Input: what sgl_knn returns for n cells: idx int32 and dist double (the roots; or the keys of sgl_knn_metric), both K x n
  * column-major (the list of cell j at idx + j K, ranked ascending).  The cell itself is usually first in its list, but not
  * when K identical columns precede it.  Output: an n x n dgCMatrix, rows ascending within a column, no diagonal, pattern and
  * values bitwise symmetric (what sgl_c_louvain demands), in the two calls of sgl_c_snn: i_out == NULL counts (p_out and

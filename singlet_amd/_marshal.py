@@ -148,9 +148,19 @@ def gsea_score_type(score_type):
     return GSEA_SCORE_TYPES[score_type]
 
 
-def knn_call(fn, reference, query, dims, n_neighbors, resident=None):
+KNN_METRICS = {"euclidean": 0, "cosine": 1, "correlation": 2}
+
+
+def knn_metric(metric):
+    """The metric code of sgl_knn_metric for a name; anything else is refused here, by name."""
+    if not isinstance(metric, str) or metric not in KNN_METRICS:
+        raise ValueError("metric must be 'euclidean', 'cosine' or 'correlation'")
+    return KNN_METRICS[metric]
+
+
+def knn_call(fn, reference, query, dims, n_neighbors, resident=None, metric=None):
     """Shared by Context.knn and api.knn: fn(R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, idx_out, dist_out) is the
-    library call.  reference / query: k x n matrices (R's orientation, one column per cell); a None reference stands for the
+    library call -- with a metric code, fn(..., n_neighbors, metric, idx_out, dist_out), the sgl_knn_metric form.  reference / query: k x n matrices (R's orientation, one column per cell); a None reference stands for the
     H of a fit of shape resident = (k, n), a None query for the references themselves; dims: 0-based rows or None.
     Returns (idx, dist), each n_query x n_neighbors: row j holds the neighbours of query j in rank order."""
     if reference is None:
@@ -179,5 +189,6 @@ def knn_call(fn, reference, query, dims, n_neighbors, resident=None):
     K = int(n_neighbors)
     shape = (int(nq), K) if 1 <= K <= 256 else (1, 1)   # outside it the library refuses before it writes
     idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
-    check(fn(ptr(Rb, f64p), int(k), int(n_ref), ptr(Qb, f64p), int(nq), ptr(d, i32p), nd, K, ptr(idx, i32p), ptr(dist, f64p)))
+    code = () if metric is None else (int(metric),)
+    check(fn(ptr(Rb, f64p), int(k), int(n_ref), ptr(Qb, f64p), int(nq), ptr(d, i32p), nd, K, *code, ptr(idx, i32p), ptr(dist, f64p)))
     return idx, dist

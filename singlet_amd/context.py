@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
-from ._marshal import (MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, label_list,
+from ._marshal import (MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_metric, label_list,
                        markers_call)
 from .sparse import as_dgCMatrix
 
@@ -502,17 +502,22 @@ class Context(_Handle):
         check(self._L.sgl_markers_info(self._h, ptr(out, i64p)))
         return dict(zip(("lds_genes", "long_genes", "batches", "lds_cap"), (int(v) for v in out)))
 
-    def knn(self, n_neighbors=20, reference=None, query=None, dims=None):
+    def knn(self, n_neighbors=20, reference=None, query=None, dims=None, metric="euclidean"):
         """Exact nearest neighbours in an embedding (sgl_knn): (idx, dist), each n_query x n_neighbors, row j = the
         n_neighbors nearest reference columns of query column j in rank order -- by (squared distance, index), ties to
         the lower index -- and their Euclidean distances.  reference: k x n (R's orientation); None: the H of the current
         fit, read where it is, in the fit's stored factor order.  query: k x n_query; None: the references themselves (a
         cell is then its own first neighbour unless n_neighbors identical columns precede it).  dims: 0-based rows.  The
-        context and a running fit are only read."""
+        context and a running fit are only read.  metric: "euclidean"; "cosine" or "correlation" (sgl_knn_metric) rank by
+        1 - the dot of the unit columns (for correlation of the columns centred by their own mean) and return that key as
+        the distance, exactly +0.0 between a cell and its duplicates or power-of-two multiples."""
+        code = knn_metric(metric)
         resident = None
         if reference is None:
             _, n, _ = self.dims()
             resident = (self.k, n)
+        if code:
+            return knn_call(lambda *a: self._L.sgl_knn_metric(self._h, *a), reference, query, dims, n_neighbors, resident, code)
         return knn_call(lambda *a: self._L.sgl_knn(self._h, *a), reference, query, dims, n_neighbors, resident)
 
     def knn_info(self):
@@ -522,6 +527,14 @@ class Context(_Handle):
         out = np.zeros(4, dtype=np.int64)
         check(self._L.sgl_knn_info(self._h, ptr(out, i64p)))
         return dict(zip(("instance", "segments", "queries_per_workgroup", "lists_global"), (int(v) for v in out)))
+
+    def knn_metric_info(self):
+        """knn_info() of the last search on this context (sgl_knn_metric_info) with "metric" (0 euclidean, 1 cosine,
+        2 correlation) and "no_direction": the columns among its operands whose unit column is all zeros (a zero or a
+        constant column, a norm that overflows or underflows); 0 for euclidean."""
+        out = np.zeros(6, dtype=np.int64)
+        check(self._L.sgl_knn_metric_info(self._h, ptr(out, i64p)))
+        return dict(zip(("instance", "segments", "queries_per_workgroup", "lists_global", "metric", "no_direction"), (int(v) for v in out)))
 
     def set_stream(self, stream_ptr):
         """Launch all work of this context on the HIP stream with this handle (sgl_set_stream; e.g. the cuda_stream of a

@@ -1,11 +1,13 @@
-// Exact k-nearest neighbours of query columns among reference columns of a k x n embedding (include/singlet_hip.h, sgl_knn).
-// gfx950 only.  This unit is compiled with -ffp-contract=off: s = s + t * t is a product and an addition, two roundings.
+// Exact k-nearest neighbours of query columns among reference columns of a k x n embedding (include/singlet_hip.h, sgl_knn
+// and sgl_knn_metric).  gfx950 only.  This unit is compiled with -ffp-contract=off: s = s + t * t is a product and an
+// addition, two roundings.
 //
 //   knn_first_nonfinite   the first NaN / Inf of an operand in column-major order (the refusal names it)
 //   knn_gather            the rows `dims` of an operand, packed n_dims x n -- or, for the generic scan's queries, n x n_dims
+//   knn_unit              cosine / correlation: in place of the gather, the unit columns of an operand in the same two layouts
 //   knn_scan_reg          n_dims <= 64: a lane owns one or two queries and keeps their coordinates in registers
 //   knn_scan_generic      every rank above: a lane owns one query, eight references at a time keep their running sums
-//   knn_finish            merges the segments' candidates by (s, index), takes the root, writes the result
+//   knn_finish            merges the segments' candidates by (s, index), takes the root (Euclidean only), writes the result
 //
 // The scan.  One workgroup is one wave; grid = (query blocks, reference segments).  The references of the segment stream in
 // ascending index.  A reference coordinate is the same for all 64 lanes: its address depends on the loop counter and the
@@ -18,6 +20,11 @@
 // entry with an equal s: no index is compared.  The list lives in LDS, slot-major ([slot][query of the workgroup]: the
 // lanes of a wave hit 64 consecutive doubles), up to K = 32 -- 48 KiB for the 128 queries of a workgroup -- and above in
 // the global candidate array the merge reads anyway.  Insertions are divergent and rare: K (1 + ln(n / K)) per query.
+//
+// Cosine and correlation (DOT = true).  The operands are unit columns (knn_unit) and the inner form is dot = dot + q_f * r_f:
+// v_mul, v_add with the reference coordinate as the scalar operand, two FP64 VALU instructions per (pair, dimension) where the
+// Euclidean form issues three.  The key 1 - dot, snapped to +0.0 below 2^-40, is formed once per pair (knn_key) and is what
+// the lists, the segments and the merge rank exactly as they rank s; knn_finish takes no root of it.
 //
 // Merge.  Every segment leaves K candidates per query, (+Inf, INT32_MAX) where it had fewer than K references.  (s, index)
 // is a total order and no real index is INT32_MAX, so the K least of their union are the K least of all references,
@@ -48,6 +55,99 @@ __global__ __launch_bounds__(256) void knn_gather(const double* __restrict__ X, 
     const int64_t j = transposed ? e % n : e / nd;
     const int f = (int)(transposed ? e / n : e % nd);
     out[e] = X[j * k + (dims ? dims[f] : f)];
+}
+
+// Unit columns (include/singlet_hip.h, sgl_knn_metric, rule 1).  One workgroup is one wave and owns 64 columns; lane l walks
+// column l sequentially -- the rule's shape -- three times: the mean (correlation only), the sum of squares, the division.
+// Each walk goes in chunks of KNN_UNIT_ROWS rows that the wave stages through LDS: in global memory a lane group reads
+// (writes) 32 consecutive doubles of one column, in LDS lane l reads row l of the tile, whose stride of 33 doubles spreads
+// the 32 lanes of a group over all banks.  The second and third walk find the tile's columns in L2.
+// out: nd x n packed (out[j * nd + f]); out_t: n x nd (out_t[f * n + j]); either may be nullptr.  no_direction counts the
+// columns whose norm is 0 or +Inf: every coordinate of their unit column is a zero.
+constexpr int KNN_UNIT_ROWS = 32;
+constexpr int KNN_UNIT_STRIDE = KNN_UNIT_ROWS + 1;
+
+__global__ __launch_bounds__(64) void knn_unit(const double* __restrict__ X, int k, int64_t n, const int32_t* __restrict__ dims, int nd, int centre,
+                                               double* __restrict__ out, double* __restrict__ out_t, unsigned long long* no_direction) {
+    __shared__ double tile[64 * KNN_UNIT_STRIDE];
+    const int lane = threadIdx.x;
+    const int64_t j0 = (int64_t)blockIdx.x * 64;
+    const int64_t j = j0 + lane;
+    const bool mine = j < n;
+    double* row = tile + lane * KNN_UNIT_STRIDE;
+    // rows [f0, f0 + KNN_UNIT_ROWS) of the 64 columns into the tile; element e of the tile is (column e / 32, row e % 32)
+    auto stage = [&](int f0) {
+        __syncthreads();
+        for (int e = lane; e < 64 * KNN_UNIT_ROWS; e += 64) {
+            const int c = e / KNN_UNIT_ROWS, f = f0 + e % KNN_UNIT_ROWS;
+            if (j0 + c < n && f < nd) tile[c * KNN_UNIT_STRIDE + e % KNN_UNIT_ROWS] = X[(j0 + c) * k + (dims ? dims[f] : f)];
+        }
+        __syncthreads();
+    };
+    double m = 0.0;
+    if (centre) {
+        for (int f0 = 0; f0 < nd; f0 += KNN_UNIT_ROWS) {
+            stage(f0);
+            const int len = nd - f0 < KNN_UNIT_ROWS ? nd - f0 : KNN_UNIT_ROWS;
+            if (mine)
+                for (int f = 0; f < len; ++f) m = m + row[f];
+        }
+        m = m / (double)nd;
+    }
+    double s2 = 0.0;
+    for (int f0 = 0; f0 < nd; f0 += KNN_UNIT_ROWS) {
+        stage(f0);
+        const int len = nd - f0 < KNN_UNIT_ROWS ? nd - f0 : KNN_UNIT_ROWS;
+        if (mine)
+            for (int f = 0; f < len; ++f) {
+                const double y = centre ? row[f] - m : row[f];
+                s2 = s2 + y * y;
+            }
+    }
+    const double nrm = __builtin_sqrt(s2);
+    if (mine && (nrm == 0.0 || nrm == std::numeric_limits<double>::infinity())) atomicAdd(no_direction, 1ull);
+    for (int f0 = 0; f0 < nd; f0 += KNN_UNIT_ROWS) {
+        stage(f0);
+        const int len = nd - f0 < KNN_UNIT_ROWS ? nd - f0 : KNN_UNIT_ROWS;
+        if (mine)
+            for (int f = 0; f < len; ++f) {
+                const double y = centre ? row[f] - m : row[f];
+                const double u = nrm != 0.0 ? y / nrm : 0.0;
+                if (out_t) out_t[(int64_t)(f0 + f) * n + j] = u;
+                row[f] = u;   // the lane's own row: nobody else reads it before the barrier
+            }
+        if (out) {
+            __syncthreads();
+            for (int e = lane; e < 64 * KNN_UNIT_ROWS; e += 64) {
+                const int c = e / KNN_UNIT_ROWS, f = f0 + e % KNN_UNIT_ROWS;
+                if (j0 + c < n && f < nd) out[(j0 + c) * nd + f] = tile[c * KNN_UNIT_STRIDE + e % KNN_UNIT_ROWS];
+            }
+        }
+    }
+}
+
+// One (pair, dimension) of the scan.  Euclidean: the three instructions of the unit's head comment.  DOT: the product and the
+// addition of the dot of two unit columns.
+template <bool DOT>
+__device__ __forceinline__ double knn_step(double s, double q, double r) {
+    if constexpr (DOT) {
+        return s + q * r;
+    } else {
+        const double t = q - r;
+        return s + t * t;
+    }
+}
+
+// What a pair is ranked by, once per pair.  Euclidean: the sum itself.  DOT: 1 - dot, and +0.0 below 2^-40 -- two bitwise
+// equal unit columns with a direction give a dot within rounding of 1, and the snap puts them at exactly +0.0.
+template <bool DOT>
+__device__ __forceinline__ double knn_key(double s) {
+    if constexpr (DOT) {
+        const double key = 1.0 - s;
+        return key < 0x1p-40 ? 0.0 : key;
+    } else {
+        return s;
+    }
 }
 
 // The candidate enters the list sorted by (s, index) whose slot t is ld[t * stride], li[t * stride]: behind every entry
@@ -124,7 +224,9 @@ struct KnnLists {
 // one wave-uniform test per chunk: a whole chunk is CH contiguous doubles of the reference column (one wide scalar load),
 // and the one partial chunk reads the column's last coordinate in place of those past it and replaces them by +0.0 -- the
 // query's registers hold +0.0 there, t = +0.0 and s + t * t = s, bit for bit (s is never -0.0).  Chunks past n_dims are skipped.
-template <int NDLO, int NDHI, int CH, int QPL, bool LISTS_GLOBAL>
+// DOT: the padded product is +0.0 * +0.0 = +0.0, and dot + (+0.0) = dot for every dot that can occur: dot starts at +0.0 and
+// a sum is -0.0 only when both terms are, so dot is never -0.0 either.
+template <int NDLO, int NDHI, int CH, int QPL, bool LISTS_GLOBAL, bool DOT = false>
 __global__ __launch_bounds__(64) void knn_scan_reg(const double* __restrict__ R, const double* __restrict__ Q, int nd, int64_t nq, int64_t n_ref,
                                                    int64_t segment_refs, int K, double* __restrict__ cs, int32_t* __restrict__ ci) {
     static_assert(NDHI % CH == 0, "whole chunks");
@@ -154,10 +256,7 @@ __global__ __launch_bounds__(64) void knn_scan_reg(const double* __restrict__ R,
                 for (int e = 0; e < CH; ++e) {
                     const double rf = rp[c + e];
 #pragma unroll
-                    for (int u = 0; u < QPL; ++u) {
-                        const double t = q[u][c + e] - rf;
-                        s[u] = s[u] + t * t;
-                    }
+                    for (int u = 0; u < QPL; ++u) s[u] = knn_step<DOT>(s[u], q[u][c + e], rf);
                 }
             } else if (c < nd) {
                 double rf[CH];
@@ -167,15 +266,12 @@ __global__ __launch_bounds__(64) void knn_scan_reg(const double* __restrict__ R,
                 for (int e = 0; e < CH; ++e) {
                     const double re = c + e < nd ? rf[e] : 0.0;
 #pragma unroll
-                    for (int u = 0; u < QPL; ++u) {
-                        const double t = q[u][c + e] - re;
-                        s[u] = s[u] + t * t;
-                    }
+                    for (int u = 0; u < QPL; ++u) s[u] = knn_step<DOT>(s[u], q[u][c + e], re);
                 }
             }
         }
 #pragma unroll
-        for (int u = 0; u < QPL; ++u) L.offer(u, K, s[u], (int32_t)r);
+        for (int u = 0; u < QPL; ++u) L.offer(u, K, knn_key<DOT>(s[u]), (int32_t)r);
     }
     L.flush(K, nq);
 }
@@ -183,7 +279,7 @@ __global__ __launch_bounds__(64) void knn_scan_reg(const double* __restrict__ R,
 // Qt is n_dims x nq transposed (Qt[f * nq + j]: the lanes of a wave read consecutive doubles).  The running sums of a tile
 // of KNN_TILE references stay in registers over the whole loop over f, which goes four dimensions at a time (four contiguous
 // doubles of each reference column: one scalar load) and ends with the partial chunk of knn_scan_reg.
-template <bool LISTS_GLOBAL>
+template <bool LISTS_GLOBAL, bool DOT = false>
 __global__ __launch_bounds__(64) void knn_scan_generic(const double* __restrict__ R, const double* __restrict__ Qt, int nd, int64_t nq, int64_t n_ref,
                                                        int64_t segment_refs, int K, double* __restrict__ cs, int32_t* __restrict__ ci) {
     constexpr int CH = 4;
@@ -210,10 +306,7 @@ __global__ __launch_bounds__(64) void knn_scan_generic(const double* __restrict_
 #pragma unroll
             for (int i = 0; i < KNN_TILE; ++i) {
 #pragma unroll
-                for (int e = 0; e < CH; ++e) {
-                    const double t = qf[e] - rp[i][f + e];
-                    s[i] = s[i] + t * t;
-                }
+                for (int e = 0; e < CH; ++e) s[i] = knn_step<DOT>(s[i], qf[e], rp[i][f + e]);
             }
         }
         if (f < nd) {
@@ -228,19 +321,20 @@ __global__ __launch_bounds__(64) void knn_scan_generic(const double* __restrict_
 #pragma unroll
                 for (int e = 0; e < CH; ++e) {
                     const double v = rp[i][f + e < nd ? f + e : nd - 1];
-                    const double t = qf[e] - (f + e < nd ? v : 0.0);
-                    s[i] = s[i] + t * t;
+                    s[i] = knn_step<DOT>(s[i], qf[e], f + e < nd ? v : 0.0);
                 }
             }
         }
 #pragma unroll
         for (int i = 0; i < KNN_TILE; ++i)
-            if (r0 + i < hi) L.offer(0, K, s[i], (int32_t)(r0 + i));
+            if (r0 + i < hi) L.offer(0, K, knn_key<DOT>(s[i]), (int32_t)(r0 + i));
     }
     L.flush(K, nq);
 }
 
-// One thread per query: K times the least head of the segments' sorted lists by (s, index).
+// One thread per query: K times the least head of the segments' sorted lists by (s, index).  ROOT: the distance is the root
+// of the Euclidean sum; a cosine or correlation key goes out as it is.
+template <bool ROOT>
 __global__ __launch_bounds__(256) void knn_finish(const double* __restrict__ cs, const int32_t* __restrict__ ci, int nseg, int K, int64_t nq,
                                                   int32_t* __restrict__ idx_out, double* __restrict__ dist_out) {
     __shared__ uint16_t head[KNN_MAX_SEGMENTS][256];
@@ -262,18 +356,41 @@ __global__ __launch_bounds__(256) void knn_finish(const double* __restrict__ cs,
         }
         head[best][tid] = (uint16_t)(head[best][tid] + 1);   // nseg * K >= K slots: a head is always left
         if (idx_out) idx_out[j * K + t] = bi;
-        if (dist_out) dist_out[j * K + t] = __builtin_sqrt(bd);
+        if (dist_out) dist_out[j * K + t] = ROOT ? __builtin_sqrt(bd) : bd;
     }
 }
 
-template <int NDLO, int NDHI, int CH, int QPL>
+template <int NDLO, int NDHI, int CH, int QPL, bool DOT>
 int launch_reg(hipStream_t s, const KnnPlan& P, const double* R, const double* Q, int nd, int64_t nq, int64_t n_ref, int K, double* cs,
                int32_t* ci) {
     const dim3 grid((unsigned)P.query_blocks, (unsigned)P.segments);
     if (P.lists_global)
-        knn_scan_reg<NDLO, NDHI, CH, QPL, true><<<grid, dim3(64), 0, s>>>(R, Q, nd, nq, n_ref, P.segment_refs, K, cs, ci);
+        knn_scan_reg<NDLO, NDHI, CH, QPL, true, DOT><<<grid, dim3(64), 0, s>>>(R, Q, nd, nq, n_ref, P.segment_refs, K, cs, ci);
     else
-        knn_scan_reg<NDLO, NDHI, CH, QPL, false><<<grid, dim3(64), (size_t)P.lds_bytes, s>>>(R, Q, nd, nq, n_ref, P.segment_refs, K, cs, ci);
+        knn_scan_reg<NDLO, NDHI, CH, QPL, false, DOT><<<grid, dim3(64), (size_t)P.lds_bytes, s>>>(R, Q, nd, nq, n_ref, P.segment_refs, K, cs, ci);
+    HIPCHK(hipGetLastError());
+    return SGL_OK;
+}
+
+// The scan of plan P and the merge.  DOT = false is sgl_knn's code, DOT = true the cosine / correlation form of every instance.
+template <bool DOT>
+int launch_scan(hipStream_t s, const KnnPlan& P, const double* Rs, const double* Qs, int nd, int64_t nq, int64_t n_ref, int K, double* cs,
+                int32_t* ci, int32_t* idx, double* dist) {
+    switch (P.instance) {
+    case 0: SGLCHK((launch_reg<1, 8, 2, 2, DOT>(s, P, Rs, Qs, nd, nq, n_ref, K, cs, ci))); break;
+    case 1: SGLCHK((launch_reg<9, 16, 4, 2, DOT>(s, P, Rs, Qs, nd, nq, n_ref, K, cs, ci))); break;
+    case 2: SGLCHK((launch_reg<17, 32, 8, 2, DOT>(s, P, Rs, Qs, nd, nq, n_ref, K, cs, ci))); break;
+    case 3: SGLCHK((launch_reg<33, 64, 8, 1, DOT>(s, P, Rs, Qs, nd, nq, n_ref, K, cs, ci))); break;
+    default: {
+        const dim3 grid((unsigned)P.query_blocks, (unsigned)P.segments);
+        if (P.lists_global)
+            knn_scan_generic<true, DOT><<<grid, dim3(64), 0, s>>>(Rs, Qs, nd, nq, n_ref, P.segment_refs, K, cs, ci);
+        else
+            knn_scan_generic<false, DOT><<<grid, dim3(64), (size_t)P.lds_bytes, s>>>(Rs, Qs, nd, nq, n_ref, P.segment_refs, K, cs, ci);
+        HIPCHK(hipGetLastError());
+    }
+    }
+    knn_finish<!DOT><<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s>>>(cs, ci, P.segments, K, nq, idx, dist);
     HIPCHK(hipGetLastError());
     return SGL_OK;
 }
@@ -307,12 +424,12 @@ int knn_check_finite(sgl_ctx* c, const char* who, const char* name, const double
 struct KnnBuffers {
     DevBuf<double> R, Q, Rp, Qp, cs, dist;
     DevBuf<int32_t> dims, ci, idx;
-    DevBuf<unsigned long long> first;
+    DevBuf<unsigned long long> first, no_direction;
 };
 
 // Rdev: the k x n_ref references on the device (the fit's H, or B.R).  Arguments checked by the caller.
 int knn_body(sgl_ctx* c, const char* who, KnnBuffers& B, const double* Rdev, const char* Rname, int32_t k, int64_t n_ref, const double* Q,
-             int64_t n_query, const int32_t* dims, int32_t n_dims, int32_t K, int32_t* idx_out, double* dist_out) {
+             int64_t n_query, const int32_t* dims, int32_t n_dims, int32_t K, int32_t metric, int32_t* idx_out, double* dist_out) {
     const int nd = dims ? n_dims : k;
     const double* Qdev = Rdev;
     int64_t nq = n_ref;
@@ -334,13 +451,34 @@ int knn_body(sgl_ctx* c, const char* who, KnnBuffers& B, const double* Rdev, con
     if (dims) {
         SGLCHK(B.dims.alloc((size_t)nd));
         HIPCHK(hipMemcpyAsync(B.dims.p, dims, sizeof(int32_t) * (size_t)nd, hipMemcpyHostToDevice, c->stream));
+    }
+    if (metric != KNN_METRIC_EUCLIDEAN) {
+        // the unit columns of both operands, in the call's own buffers (the resident H is only read), in the layouts of the gather
+        const int centre = metric == KNN_METRIC_CORRELATION ? 1 : 0;
+        const int32_t* dd = dims ? B.dims.p : nullptr;
+        SGLCHK(B.no_direction.alloc(1));
+        HIPCHK(hipMemsetAsync(B.no_direction.p, 0, sizeof(unsigned long long), c->stream));
+        SGLCHK(B.Rp.alloc((size_t)nd * (size_t)n_ref));
+        if (Q || generic) SGLCHK(B.Qp.alloc((size_t)nd * (size_t)nq));
+        Phase ph(c, SGL_PH_GRAM);   // the pass alone, apart from the scan's "scale": the call books nothing else here
+        knn_unit<<<dim3((unsigned)((n_ref + 63) / 64)), dim3(64), 0, c->stream>>>(Rdev, k, n_ref, dd, nd, centre, B.Rp.p,
+                                                                                   !Q && generic ? B.Qp.p : nullptr, B.no_direction.p);
+        HIPCHK(hipGetLastError());
+        if (Q) {
+            knn_unit<<<dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, c->stream>>>(Qdev, k, nq, dd, nd, centre, generic ? nullptr : B.Qp.p,
+                                                                                generic ? B.Qp.p : nullptr, B.no_direction.p);
+            HIPCHK(hipGetLastError());
+        }
+        Rs = B.Rp.p;
+        Qs = Q || generic ? B.Qp.p : B.Rp.p;
+    } else if (dims) {
         SGLCHK(B.Rp.alloc((size_t)nd * (size_t)n_ref));
         knn_gather<<<dim3((unsigned)(((int64_t)nd * n_ref + 255) / 256)), dim3(256), 0, c->stream>>>(Rdev, k, n_ref, B.dims.p, nd, 0, B.Rp.p);
         HIPCHK(hipGetLastError());
         Rs = B.Rp.p;
         if (!Q && !generic) Qs = Rs;
     }
-    if (generic || (dims && Qs != Rs)) {
+    if (metric == KNN_METRIC_EUCLIDEAN && (generic || (dims && Qs != Rs))) {
         SGLCHK(B.Qp.alloc((size_t)nd * (size_t)nq));
         knn_gather<<<dim3((unsigned)(((int64_t)nd * nq + 255) / 256)), dim3(256), 0, c->stream>>>(Qdev, k, nq, dims ? B.dims.p : nullptr, nd,
                                                                                               generic ? 1 : 0, B.Qp.p);
@@ -354,23 +492,14 @@ int knn_body(sgl_ctx* c, const char* who, KnnBuffers& B, const double* Rdev, con
     if (dist_out) SGLCHK(B.dist.alloc((size_t)K * (size_t)nq));
     {
         Phase ph(c, SGL_PH_SCALE);   // where scripts/knn_rate.py reads the kernels' time
-        switch (P.instance) {
-        case 0: SGLCHK((launch_reg<1, 8, 2, 2>(c->stream, P, Rs, Qs, nd, nq, n_ref, K, B.cs.p, B.ci.p))); break;
-        case 1: SGLCHK((launch_reg<9, 16, 4, 2>(c->stream, P, Rs, Qs, nd, nq, n_ref, K, B.cs.p, B.ci.p))); break;
-        case 2: SGLCHK((launch_reg<17, 32, 8, 2>(c->stream, P, Rs, Qs, nd, nq, n_ref, K, B.cs.p, B.ci.p))); break;
-        case 3: SGLCHK((launch_reg<33, 64, 8, 1>(c->stream, P, Rs, Qs, nd, nq, n_ref, K, B.cs.p, B.ci.p))); break;
-        default: {
-            const dim3 grid((unsigned)P.query_blocks, (unsigned)P.segments);
-            if (P.lists_global)
-                knn_scan_generic<true><<<grid, dim3(64), 0, c->stream>>>(Rs, Qs, nd, nq, n_ref, P.segment_refs, K, B.cs.p, B.ci.p);
-            else
-                knn_scan_generic<false><<<grid, dim3(64), (size_t)P.lds_bytes, c->stream>>>(Rs, Qs, nd, nq, n_ref, P.segment_refs, K, B.cs.p, B.ci.p);
-            HIPCHK(hipGetLastError());
-        }
-        }
-        knn_finish<<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, c->stream>>>(B.cs.p, B.ci.p, P.segments, K, nq, B.idx.p, B.dist.p);
-        HIPCHK(hipGetLastError());
+        if (metric == KNN_METRIC_EUCLIDEAN)
+            SGLCHK(launch_scan<false>(c->stream, P, Rs, Qs, nd, nq, n_ref, K, B.cs.p, B.ci.p, B.idx.p, B.dist.p));
+        else
+            SGLCHK(launch_scan<true>(c->stream, P, Rs, Qs, nd, nq, n_ref, K, B.cs.p, B.ci.p, B.idx.p, B.dist.p));
     }
+    unsigned long long no_direction = 0;
+    if (metric != KNN_METRIC_EUCLIDEAN)
+        HIPCHK(hipMemcpyAsync(&no_direction, B.no_direction.p, sizeof(no_direction), hipMemcpyDeviceToHost, c->stream));
     if (idx_out) HIPCHK(hipMemcpyAsync(idx_out, B.idx.p, sizeof(int32_t) * (size_t)K * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
     if (dist_out) HIPCHK(hipMemcpyAsync(dist_out, B.dist.p, sizeof(double) * (size_t)K * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -378,6 +507,8 @@ int knn_body(sgl_ctx* c, const char* who, KnnBuffers& B, const double* Rdev, con
     c->knn_last[1] = P.segments;
     c->knn_last[2] = P.queries_per_wg;
     c->knn_last[3] = P.lists_global;
+    c->knn_last[4] = metric;
+    c->knn_last[5] = (int64_t)no_direction;
     return SGL_OK;
 }
 
@@ -398,8 +529,14 @@ int knn_args(const char* who, int32_t k, int64_t n_ref, int64_t n_query, const i
     return SGL_EINVAL;
 }
 
+int knn_metric_arg(const char* who, int32_t metric) {
+    if (knn_metric_ok(metric)) return SGL_OK;
+    sgl_set_error("%s: metric = %d is outside [0, %d]", who, metric, KNN_METRIC_MAX);
+    return SGL_EINVAL;
+}
+
 int knn_entry(sgl_ctx* c, const char* who, const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query, const int32_t* dims,
-              int32_t n_dims, int32_t n_neighbors, int32_t* idx_out, double* dist_out) {
+              int32_t n_dims, int32_t n_neighbors, int32_t metric, int32_t* idx_out, double* dist_out) {
     if (c->team || c->allreduce) {
         sgl_set_error("%s: the context is a shard of a team or has an all-reduce hook; the H of this shard's cells is not the embedding", who);
         return SGL_ESTATE;
@@ -410,6 +547,7 @@ int knn_entry(sgl_ctx* c, const char* who, const double* R, int32_t k, int64_t n
         return SGL_EINVAL;
     }
     SGLCHK(knn_args(who, k, n_ref, n_query, dims, n_dims, n_neighbors));
+    SGLCHK(knn_metric_arg(who, metric));
     KnnBuffers B;
     int rc = SGL_OK;
     const double* Rdev = c->H;
@@ -422,7 +560,7 @@ int knn_entry(sgl_ctx* c, const char* who, const double* R, int32_t k, int64_t n
         }
         Rdev = B.R.p;
     }
-    if (rc == SGL_OK) rc = knn_body(c, who, B, Rdev, R ? "R" : "H", k, n_ref, Q, n_query, dims, n_dims, n_neighbors, idx_out, dist_out);
+    if (rc == SGL_OK) rc = knn_body(c, who, B, Rdev, R ? "R" : "H", k, n_ref, Q, n_query, dims, n_dims, n_neighbors, metric, idx_out, dist_out);
     return knn_drain(c, rc, who);
 }
 
@@ -432,7 +570,7 @@ extern "C" int sgl_knn(sgl_ctx* c, const double* R, int32_t k, int64_t n_ref, co
                        int32_t n_dims, int32_t n_neighbors, int32_t* idx_out, double* dist_out) {
     if (c == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; }
     HIPCHK(hipSetDevice(c->device));
-    return knn_entry(c, "sgl_knn", R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, idx_out, dist_out);
+    return knn_entry(c, "sgl_knn", R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, KNN_METRIC_EUCLIDEAN, idx_out, dist_out);
 }
 
 extern "C" int sgl_c_knn(const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query, const int32_t* dims, int32_t n_dims,
@@ -441,11 +579,34 @@ extern "C" int sgl_c_knn(const double* R, int32_t k, int64_t n_ref, const double
     SGLCHK(knn_args("sgl_c_knn", k, n_ref, n_query, dims, n_dims, n_neighbors));   // before a context is made
     CtxHolder hd;
     SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
-    return knn_entry(hd.c, "sgl_c_knn", R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, idx_out, dist_out);
+    return knn_entry(hd.c, "sgl_c_knn", R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, KNN_METRIC_EUCLIDEAN, idx_out, dist_out);
 }
 
 extern "C" int sgl_knn_info(sgl_ctx* c, int64_t out[4]) {
     if (c == nullptr || out == nullptr) { sgl_set_error("sgl_knn_info: NULL context or output"); return SGL_EINVAL; }
     for (int q = 0; q < 4; ++q) out[q] = c->knn_last[q];
+    return SGL_OK;
+}
+
+extern "C" int sgl_knn_metric(sgl_ctx* c, const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query, const int32_t* dims,
+                              int32_t n_dims, int32_t n_neighbors, int32_t metric, int32_t* idx_out, double* dist_out) {
+    if (c == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    return knn_entry(c, "sgl_knn_metric", R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, metric, idx_out, dist_out);
+}
+
+extern "C" int sgl_c_knn_metric(const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query, const int32_t* dims, int32_t n_dims,
+                                int32_t n_neighbors, int32_t metric, int32_t* idx_out, double* dist_out) {
+    if (!R) { sgl_set_error("sgl_c_knn_metric: R is NULL"); return SGL_EINVAL; }
+    SGLCHK(knn_args("sgl_c_knn_metric", k, n_ref, n_query, dims, n_dims, n_neighbors));   // before a context is made
+    SGLCHK(knn_metric_arg("sgl_c_knn_metric", metric));
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    return knn_entry(hd.c, "sgl_c_knn_metric", R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, metric, idx_out, dist_out);
+}
+
+extern "C" int sgl_knn_metric_info(sgl_ctx* c, int64_t out[6]) {
+    if (c == nullptr || out == nullptr) { sgl_set_error("sgl_knn_metric_info: NULL context or output"); return SGL_EINVAL; }
+    for (int q = 0; q < 6; ++q) out[q] = c->knn_last[q];
     return SGL_OK;
 }

@@ -1,6 +1,7 @@
-// Host logic of sgl_knn (include/singlet_hip.h) that makes no HIP call: the argument rules, the check of `dims` and the
-// launch plan -- kernel instance, queries per workgroup, reference segments, where the candidate lists live.  Plain C++
-// over plain pointers, so tests/knn_host_main.cpp compiles it alone under -fsanitize=address,undefined and runs it on the CPU.
+// Host logic of sgl_knn and sgl_knn_metric (include/singlet_hip.h) that makes no HIP call: the argument rules, the check of
+// `dims`, the metric's rule and the launch plan -- kernel instance, queries per workgroup, reference segments, where the
+// candidate lists live.  Plain C++ over plain pointers, so tests/knn_host_main.cpp and tests/knn_metric_host_main.cpp compile
+// it alone under -fsanitize=address,undefined and run it on the CPU.
 #pragma once
 #include <stdint.h>
 
@@ -50,6 +51,16 @@ inline KnnArgError knn_check_args(int32_t k, int64_t n_ref, int64_t n_query, con
     *value = 0;
     return KNN_ARGS_OK;
 }
+
+// The metric of sgl_knn_metric: 0 is sgl_knn's own code, 1 and 2 rank by 1 - the dot of the unit columns.
+#define KNN_METRIC_EUCLIDEAN 0
+#define KNN_METRIC_COSINE 1
+#define KNN_METRIC_CORRELATION 2   // cosine of the columns centred by their own mean
+#define KNN_METRIC_MAX 2
+
+// The one refusal sgl_knn_metric adds: it comes after knn_check_args and before anything is launched (for the one-shot
+// form before a context is made); the message names the value and [0, KNN_METRIC_MAX].
+inline bool knn_metric_ok(int32_t metric) { return metric >= KNN_METRIC_EUCLIDEAN && metric <= KNN_METRIC_MAX; }
 
 // One workgroup is one wave; lane l owns queries_per_lane queries.  Instances 0 .. 3 keep the coordinates in registers for
 // n_dims in [1, 8], [9, 16], [17, 32] (two queries per lane) and [33, 64] (one: two would need 256 VGPRs for the

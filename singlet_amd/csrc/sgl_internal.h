@@ -250,7 +250,9 @@ struct sgl_ctx {
     int64_t sweeps_acc[4] = {0, 0, 0, 0};
     int64_t wave_sweeps_acc[2] = {0, 0};
     double* pinned = nullptr;        // host pinned scratch (8 doubles)
-    int64_t knn_last[4] = {0, 0, 0, 0};   // sgl_knn_info: instance, segments, queries per workgroup, list home of the last sgl_knn
+    // sgl_knn_info / sgl_knn_metric_info: instance, segments, queries per workgroup, list home, metric and columns without
+    // direction of the last search
+    int64_t knn_last[6] = {0, 0, 0, 0, 0, 0};
     int64_t markers_last[4] = {0, 0, 0, 0};   // sgl_markers_info: genes sorted in LDS, long genes, batches, the LDS cap of the last rank pass
     int64_t gsea_last[5] = {0, 0, 0, 0, 0};   // sgl_gsea_info: sets, distinct sizes, s_max, batches, batch size of the last enrichment call
 
