@@ -28,7 +28,8 @@ fit = sa.run_nmf(A, rank=10, tol=1e-4, maxit=100, verbose=False, L1=0.01, seed=1
 print("run_nmf(rank=10): %d iterations" % fit["iter"])
 
 t0 = time.perf_counter()
-graph = sa.find_neighbors(fit["h"].T, k_param=20)     # cells x factors, as cell.embeddings
+graph = sa.find_neighbors(fit["h"].T, k_param=20)     # cells x factors, as cell.embeddings; exact.  At 10^5 cells and more:
+#                                                       nn_method="ivf" (approximate, as Seurat's annoy; n_lists=, n_probe=)
 t1 = time.perf_counter()
 resolutions = [float(a) for a in sys.argv[1:]] or [0.4, 0.8, 1.2]
 out = sa.find_clusters(graph, resolution=resolutions)

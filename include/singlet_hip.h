@@ -807,6 +807,82 @@ SGL_API int sgl_c_knn_metric(const double* R, int32_t k, int64_t n_ref, const do
  * refused call leaves it as it was. */
 SGL_API int sgl_knn_metric_info(sgl_ctx* ctx, int64_t out[6]);
 
+/* Approximate embedding neighbours: an inverted-file search.  A coarse k-means over the embedding cuts the references into
+ * n_lists lists, and every query scans only the n_probe lists whose centroids are nearest to it; inside those lists the sums,
+ * the keys and the ranking are exactly sgl_knn's / sgl_knn_metric's.  (Seurat's FindNeighbors and RunUMAP default to annoy, an
+ * approximate index; the exact scan is quadratic in the cells.)  The exact search stays the default everywhere.  Every sum
+ * below has one stated order, so the result is one function of the inputs; tests/knn_ivf_restatement.py restates the rules in
+ * numpy.  The rules are this library's own.
+ *
+ *  - operands: exactly those of sgl_knn_metric.  R, Q and dims are gathered to packed columns; the finiteness pass runs on the
+ *    RAW operands with sgl_knn's messages; for metric 1 and 2 the operands are the unit columns of sgl_knn_metric, rule 1.
+ *    R == NULL: the resident H (k, n_ref must be the fit's); Q == NULL: the queries are the references themselves.
+ *  - the coarse quantiser always works on these operands with the EUCLIDEAN sum of sgl_knn, s = +0.0; s = s + t * t with
+ *    t = x_f - c_f, sequential over the dimensions, uncontracted -- for every metric.  Only the final ranking uses the
+ *    metric's key.  "Nearest centroid" is the least (s, centroid index): sgl_knn's ranking with the centroids as references.
+ *  - training set: T = min(n_ref, 64 n_lists) training cells; training cell t is reference floor(t n_ref / T) in 64-bit
+ *    integers (every cell trains when n_ref <= 64 n_lists).  No seed, no hash.
+ *  - seeds: centroid g starts as training cell floor(g T / n_lists).
+ *  - Lloyd step, n_iter times (0 allowed): every training cell goes to its nearest centroid; every centroid becomes the mean
+ *    of its cells in the summation order sgl_group_means documents (group = list, over the training positions in ascending
+ *    order, rank = n_dims): the sum, then one division by the count.  A centroid that received no cell keeps its value.
+ *    Empty lists are legal: two equal seeds leave the one of higher index empty for as long as the two centroids stay equal
+ *    (always with n_iter = 0; through every step when the cells of the lower one are all copies of it and their mean is exact).
+ *  - lists: after training every reference -- all n_ref, not only the training cells -- goes to its nearest centroid.  A list
+ *    holds its members in ascending cell index.
+ *  - probes: a query probes the n_probe centroids nearest to it.
+ *  - result: among the members of the probed lists, the n_neighbors best by the metric's own (key, cell index) rule --
+ *    sgl_knn's sum for metric 0, sgl_knn_metric's 1 - dot with its snap to +0.0 for 1 and 2.  Layout, and the root for
+ *    metric 0, as in sgl_knn.  A query whose probed lists hold fewer than n_neighbors cells gets idx = -1, dist = +Inf in the
+ *    remaining slots; such queries are counted (sgl_knn_ivf_info).
+ *  - consequences: the result does not depend on tiling, on batching or on which form of the call computed it; with
+ *    n_probe == n_lists it equals sgl_knn / sgl_knn_metric bit for bit (a list streams in ascending cell index, a candidate
+ *    goes behind every entry whose key is not greater, and the merge of the probe slots ranks by (key, cell index)).
+ *  - refused with SGL_EINVAL and a message naming the value and its range, after sgl_knn's own argument refusals and before
+ *    anything is launched (the one-shot form: before a context is made), in this order: n_lists outside
+ *    [1, min(n_ref, 65536)]; n_probe outside [1, min(n_lists, 64)] (64 is the width of the merge pass); n_iter outside
+ *    [0, 1000]; metric outside [0, 2].  SGL_ESTATE exactly where sgl_knn gives it.  The context stays usable after every
+ *    refusal.  The call only reads the context: a fit continued after a search in mid-fit gives the bits it would have given.
+ *  - kernels (singlet_amd/csrc/kernels_knn_ivf.hip; host rules in knn_ivf_host.h): operands, assignment passes and probe
+ *    selection are the kernels of sgl_knn with the centroids as references; the centroid update is sgl_group_means' kernel
+ *    pair; the list offsets, the table from list position to cell and the task table -- the (query, probe slot) pairs sorted
+ *    stably by probed list, cut into blocks of 64 x queries-per-lane pairs that never cross a list edge -- are built on the
+ *    host, one kernel copies the packed references into list order; knn_scan_lists gives one wave a block of pairs that share
+ *    a list: a lane owns its pairs' queries (registers up to n_dims = 64, the instance families of sgl_knn), the list's
+ *    members stream in stored order with their coordinates and cell index as scalar operands, candidate lists in LDS up to 32
+ *    neighbours and in global scratch above; a sibling of knn_finish merges the n_probe slots and writes the padding as
+ *    -1 / +Inf.  The candidates are n_probe x n_neighbors x queries x 12 bytes: the queries go in batches that keep them
+ *    below 1 GiB, and batching cannot change a bit.  No floating-point atomics; 64-bit offsets.  With timing on the list
+ *    scan, its merge and the centroid updates (as sgl_group_means books them) count in the "scale" phase, knn_unit in "gram". */
+SGL_API int sgl_knn_ivf(sgl_ctx* ctx, const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query,
+                        const int32_t* dims, int32_t n_dims, int32_t n_neighbors, int32_t metric, int32_t n_lists,
+                        int32_t n_probe, int32_t n_iter, int32_t* idx_out, double* dist_out);
+/* The one-shot form: its own context on the current device; R must not be NULL (SGL_EINVAL). */
+SGL_API int sgl_c_knn_ivf(const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query, const int32_t* dims,
+                          int32_t n_dims, int32_t n_neighbors, int32_t metric, int32_t n_lists, int32_t n_probe,
+                          int32_t n_iter, int32_t* idx_out, double* dist_out);
+/* What the last inverted-list search on this context ran (sgl_knn_ivf or sgl_op_ivf_search; all 0 before the first; a
+ * refused call leaves it as it was): out[0] n_lists, [1] n_probe, [2] the training cells T (0 after sgl_op_ivf_search, which
+ * trains nothing), [3] the shortest and [4] the longest list, [5] the empty lists, [6] the queries that came back short,
+ * [7] the kernel instance of the list scan (0 .. 4 as sgl_knn_info). */
+SGL_API int sgl_knn_ivf_info(sgl_ctx* ctx, int64_t out[8]);
+/* With timing on (sgl_set_timing), the milliseconds the stages of the last inverted-list call took: out[0] operands, [1]
+ * Lloyd steps, [2] final assignment, [3] bucketing, [4] probes, [5] task table, [6] list scan, [7] merge.  [5] is host work
+ * and read from the host clock; the others lie between two events on the stream and include the copies of their stage. */
+SGL_API int sgl_knn_ivf_stage_ms(sgl_ctx* ctx, double out[8]);
+/* The training alone: centroids_out n_dims x n_lists column-major, assign_out int32[n_ref] the list of every reference.
+ * Refusals as sgl_knn_ivf (there is no n_probe, no n_neighbors and no Q). */
+SGL_API int sgl_op_ivf_train(sgl_ctx* ctx, const double* R, int32_t k, int64_t n_ref, const int32_t* dims, int32_t n_dims,
+                             int32_t metric, int32_t n_lists, int32_t n_iter, double* centroids_out, int32_t* assign_out);
+/* The search under the caller's centroids (n_dims x n_lists, finite) and assignment.  Any assignment with entries in
+ * [0, n_lists) is valid, including ones no training produces; the first offender is refused with position and value
+ * (SGL_EINVAL), after the argument refusals above.  query_batch = 0: the automatic batches; positive: that many queries per
+ * pass; negative: SGL_EINVAL. */
+SGL_API int sgl_op_ivf_search(sgl_ctx* ctx, const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query,
+                              const int32_t* dims, int32_t n_dims, int32_t n_neighbors, int32_t metric,
+                              const double* centroids, int32_t n_lists, const int32_t* assign, int32_t n_probe,
+                              int64_t query_batch, int32_t* idx_out, double* dist_out);
+
 /* Clustering: a deterministic multi-level Louvain modularity optimiser on a neighbour graph -- the step after
  * find_neighbors (Seurat's FindClusters on the SNN graph).  The reference's package has no clustering code (it hands the
  * graph to Seurat, whose optimiser visits the vertices in a seeded random order), so the rules below are this library's own,

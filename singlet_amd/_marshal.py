@@ -2,6 +2,7 @@
 the output buffers of the two fit families, each yielding its trailing ctypes arguments in ABI order, and the one call of the
 embedding k-NN."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -158,9 +159,46 @@ def knn_metric(metric):
     return KNN_METRICS[metric]
 
 
-def knn_call(fn, reference, query, dims, n_neighbors, resident=None, metric=None):
+KNN_IVF_DEFAULT_PROBES = 8   # KNN_IVF_DEFAULT_PROBES of csrc/knn_ivf_host.h (tests/test_knn_ivf_restatement.py holds the two together)
+KNN_METHODS = ("exact", "ivf")
+
+
+def knn_method(method):
+    """True for the inverted-list search, False for the exact one; anything else is refused here, by name."""
+    if not isinstance(method, str) or method not in KNN_METHODS:
+        raise ValueError("method must be 'exact' or 'ivf'")
+    return method == "ivf"
+
+
+def knn_ivf_shape(n_ref, n_lists=None, n_probe=None):
+    """(n_lists, n_probe) of an inverted-list search.  n_lists None: ceil(sqrt(n_ref)) clamped to the legal [1, min(n_ref,
+    65536)]; n_probe None: the default of knn_ivf_host.h clamped to min(n_lists, 64).  A given value goes to the library as it
+    is, which refuses what is out of range."""
+    n_ref = int(n_ref)
+    if n_lists is None:
+        r = math.isqrt(max(n_ref, 0))
+        n_lists = max(1, min(r + (r * r < n_ref), n_ref, 65536))
+    if n_probe is None:
+        n_probe = max(1, min(KNN_IVF_DEFAULT_PROBES, int(n_lists), 64))
+    return int(n_lists), int(n_probe)
+
+
+def knn_recall(idx, idx_exact):
+    """The mean, over the rows, of the share of a row's exact neighbours (idx_exact, n x K) that the same row of idx holds;
+    entries of -1 (a short result) match nothing."""
+    a, b = np.asarray(idx), np.asarray(idx_exact)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[0] != b.shape[0]:
+        raise ValueError("idx and idx_exact must be matrices with one row per query")
+    if b.size == 0:
+        raise ValueError("idx_exact is empty")
+    hit = (b[:, :, None] == a[:, None, :]) & (b[:, :, None] >= 0)
+    return float(hit.any(axis=2).mean(axis=1).mean())
+
+
+def knn_call(fn, reference, query, dims, n_neighbors, resident=None, metric=None, extra=None):
     """Shared by Context.knn and api.knn: fn(R, k, n_ref, Q, n_query, dims, n_dims, n_neighbors, idx_out, dist_out) is the
-    library call -- with a metric code, fn(..., n_neighbors, metric, idx_out, dist_out), the sgl_knn_metric form.  reference / query: k x n matrices (R's orientation, one column per cell); a None reference stands for the
+    library call -- with a metric code, fn(..., n_neighbors, metric, idx_out, dist_out), the sgl_knn_metric form; extra: a
+    function of n_ref giving the arguments between the metric and idx_out (the inverted-list forms).  reference / query: k x n matrices (R's orientation, one column per cell); a None reference stands for the
     H of a fit of shape resident = (k, n), a None query for the references themselves; dims: 0-based rows or None.
     Returns (idx, dist), each n_query x n_neighbors: row j holds the neighbours of query j in rank order."""
     if reference is None:
@@ -190,5 +228,6 @@ def knn_call(fn, reference, query, dims, n_neighbors, resident=None, metric=None
     shape = (int(nq), K) if 1 <= K <= 256 else (1, 1)   # outside it the library refuses before it writes
     idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
     code = () if metric is None else (int(metric),)
-    check(fn(ptr(Rb, f64p), int(k), int(n_ref), ptr(Qb, f64p), int(nq), ptr(d, i32p), nd, K, *code, ptr(idx, i32p), ptr(dist, f64p)))
+    more = () if extra is None else tuple(extra(int(n_ref), nd if d is not None else int(k)))
+    check(fn(ptr(Rb, f64p), int(k), int(n_ref), ptr(Qb, f64p), int(nq), ptr(d, i32p), nd, K, *code, *more, ptr(idx, i32p), ptr(dist, f64p)))
     return idx, dist

@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_metric, label_list, markers_call
+from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, label_list, markers_call
 from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
@@ -1448,13 +1448,17 @@ def find_local_neighbors(h, spatial, k_param=20, spatial_radius=4, nn_metric="ja
 # ---------------------------------------------------------------------------
 # Embedding neighbours (Seurat's FindNeighbors on the nmf reduction)
 # ---------------------------------------------------------------------------
-def knn(reference, query=None, n_neighbors=20, dims=None, metric="euclidean"):
+def knn(reference, query=None, n_neighbors=20, dims=None, metric="euclidean", method="exact", n_lists=None, n_probe=None, n_iter=10):
     """Exact nearest neighbours in an embedding, one-shot (sgl_c_knn): reference k x n, query k x n_query (R's orientation, one
     column per cell; None: the references themselves), dims 0-based rows -> (idx, dist), each n_query x n_neighbors, as
     Context.knn returns them.  The rules -- the sequential FP64 sum, the ranking by (squared distance, index) -- are in
     include/singlet_hip.h, sgl_knn.  metric "cosine" or "correlation" (sgl_c_knn_metric): as Context.knn; the rules are at
-    sgl_knn_metric."""
+    sgl_knn_metric.  method "ivf" (sgl_c_knn_ivf): the approximate inverted-list search with n_lists, n_probe and n_iter as
+    Context.knn takes them."""
     code = knn_metric(metric)
+    if knn_method(method):
+        return knn_call(_lib.load().sgl_c_knn_ivf, reference, query, dims, n_neighbors, metric=code,
+                        extra=lambda n_ref, nd: (*knn_ivf_shape(n_ref, n_lists, n_probe), int(n_iter)))
     if code:
         return knn_call(_lib.load().sgl_c_knn_metric, reference, query, dims, n_neighbors, metric=code)
     return knn_call(_lib.load().sgl_c_knn, reference, query, dims, n_neighbors)
@@ -1465,7 +1469,21 @@ def _metric_kw(metric):
     return {"metric": metric} if knn_metric(metric) else {}
 
 
-def find_neighbors(embedding, k_param=20, dims=None, compute_snn=True, prune_snn=1 / 15, return_dist=False, metric="euclidean"):
+def _nn_method_kw(nn_method, n_lists, n_probe):
+    """The same for the search method: nothing for "exact"."""
+    return {"method": nn_method, "n_lists": n_lists, "n_probe": n_probe} if knn_method(nn_method) else {}
+
+
+def _refuse_short(who, idx):
+    """A -1 of a short inverted-list result must not reach c_SNN or the fuzzy graph."""
+    short = int((np.asarray(idx) < 0).any(axis=1).sum())
+    if short:
+        raise ValueError("%s: %d cells came back with fewer neighbours than asked for: the lists their n_probe probes reach hold too few "
+                         "cells; raise n_probe (or lower n_lists)" % (who, short))
+
+
+def find_neighbors(embedding, k_param=20, dims=None, compute_snn=True, prune_snn=1 / 15, return_dist=False, metric="euclidean",
+                   nn_method="exact", n_lists=None, n_probe=None):
     """The numeric steps of Seurat's FindNeighbors on a reduction: the exact k.param nearest neighbours of every cell (itself
     included) in the embedding, and the shared-nearest-neighbour graph of them.  `embedding` is cells x factors (as
     cell.embeddings), or a Context with a fit, whose H is searched where it lies, in the fit's stored factor order; `dims`
@@ -1473,12 +1491,14 @@ def find_neighbors(embedding, k_param=20, dims=None, compute_snn=True, prune_snn
     n x n dgCMatrix whose column j holds the neighbours of cell j (rows ascending; x = 1, or the distances with return_dist:
     the self entry is then an explicit 0); snn = c_SNN(nn, nextafter(prune_snn, -inf), 0) or None.  metric: Seurat's
     annoy.metric, "euclidean" (its default and ours), "cosine" or "correlation" as knn takes it; dist is then 1 - cos.
+    nn_method "ivf": the approximate inverted-list search of knn (Seurat's own default, annoy, is approximate too) with n_lists
+    and n_probe as knn takes them; a cell that comes back with fewer than k.param neighbours raises ValueError naming n_probe.
 
     Seurat's SNN zeroes the entries below prune.SNN and keeps equality; c_SNN keeps > strictly.  With k.param neighbours in
     every column, inter / (2 k.param - inter) is Seurat's Jaccard index and the diagonal 1 its k.param / k.param, and the
     next double below prune_snn as the strict threshold keeps exactly the entries >= prune_snn."""
     from .context import Context
-    mkw = _metric_kw(metric)
+    mkw = {**_metric_kw(metric), **_nn_method_kw(nn_method, n_lists, n_probe)}
     if prune_snn >= 1:
         raise ValueError("prune.snn must be less than 1. You are currently asking to prune everything.")
     if isinstance(embedding, Context):
@@ -1508,6 +1528,7 @@ def find_neighbors(embedding, k_param=20, dims=None, compute_snn=True, prune_snn
         idx, dist = ctx.knn(K, dims=d0, **mkw)
     else:
         idx, dist = knn(E.T, None, K, d0, **mkw)
+    _refuse_short("find_neighbors", idx)
     order = np.argsort(idx, axis=1, kind="stable")
     rows = np.take_along_axis(idx, order, axis=1).ravel()
     x = np.take_along_axis(dist, order, axis=1).ravel() if return_dist else np.ones(rows.size)
@@ -1744,7 +1765,8 @@ def _umap_init(E, n_components, init, seed):
 
 
 def run_umap(embedding, n_neighbors=30, n_components=2, min_dist=0.3, spread=1.0, n_epochs=None, learning_rate=1.0,
-             negative_sample_rate=5, init="pca", seed=42, dims=None, return_graph=False, metric="euclidean"):
+             negative_sample_rate=5, init="pca", seed=42, dims=None, return_graph=False, metric="euclidean", nn_method="exact", n_lists=None,
+             n_probe=None):
     """The numeric steps of Seurat's RunUMAP(reduction = "nmf") on the device: exact k-NN, the fuzzy neighbour graph, and
     the synchronous layout (include/singlet_hip.h, "Layout").  `embedding` is k x n (R's orientation, one column per cell, as
     knn takes it) or a Context with a fit, whose H is searched where it lies; dims: 0-based rows.  n_epochs None: 500 up to
@@ -1753,9 +1775,10 @@ def run_umap(embedding, n_neighbors=30, n_components=2, min_dist=0.3, spread=1.0
     (seed, cell, component)) or an n x n_components array.  Returns the n x n_components positions, with return_graph
     (positions, graph).  metric: "euclidean", "cosine" or "correlation", the metric of the neighbour search as knn takes it
     (the graph is then built on 1 - cos).  Seurat's RunUMAP defaults to metric = "cosine"; ours stays "euclidean", so that
-    existing results stay.  No parity of coordinates with uwot or umap-learn is claimed."""
+    existing results stay.  nn_method "ivf", n_lists, n_probe: the approximate search, as find_neighbors takes them (a short
+    result raises ValueError naming n_probe).  No parity of coordinates with uwot or umap-learn is claimed."""
     from .context import Context
-    mkw = _metric_kw(metric)
+    mkw = {**_metric_kw(metric), **_nn_method_kw(nn_method, n_lists, n_probe)}
     if isinstance(embedding, Context):
         ctx = embedding
         E = np.ascontiguousarray(ctx.get_factors(w=False, d=False, h=True)[2].T)
@@ -1777,6 +1800,7 @@ def run_umap(embedding, n_neighbors=30, n_components=2, min_dist=0.3, spread=1.0
     a, b = find_ab_params(spread, min_dist)
     Y0 = _umap_init(E if d0 is None else E[d0], n_components, init, seed)
     idx, dist = ctx.knn(int(n_neighbors), dims=d0, **mkw) if ctx is not None else knn(E, None, int(n_neighbors), d0, **mkw)
+    _refuse_short("run_umap", idx)
     G = fuzzy_simplicial_set(idx, dist)
     Y = umap_layout(G, Y0, a, b, n_epochs, learning_rate, negative_sample_rate, int(seed) & (2**64 - 1))
     return (Y, G) if return_graph else Y

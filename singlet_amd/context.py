@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
-from ._marshal import (MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_metric, label_list,
+from ._marshal import (MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, label_list,
                        markers_call)
 from .sparse import as_dgCMatrix
 
@@ -502,7 +502,8 @@ class Context(_Handle):
         check(self._L.sgl_markers_info(self._h, ptr(out, i64p)))
         return dict(zip(("lds_genes", "long_genes", "batches", "lds_cap"), (int(v) for v in out)))
 
-    def knn(self, n_neighbors=20, reference=None, query=None, dims=None, metric="euclidean"):
+    def knn(self, n_neighbors=20, reference=None, query=None, dims=None, metric="euclidean", method="exact", n_lists=None, n_probe=None,
+            n_iter=10):
         """Exact nearest neighbours in an embedding (sgl_knn): (idx, dist), each n_query x n_neighbors, row j = the
         n_neighbors nearest reference columns of query column j in rank order -- by (squared distance, index), ties to
         the lower index -- and their Euclidean distances.  reference: k x n (R's orientation); None: the H of the current
@@ -510,12 +511,19 @@ class Context(_Handle):
         cell is then its own first neighbour unless n_neighbors identical columns precede it).  dims: 0-based rows.  The
         context and a running fit are only read.  metric: "euclidean"; "cosine" or "correlation" (sgl_knn_metric) rank by
         1 - the dot of the unit columns (for correlation of the columns centred by their own mean) and return that key as
-        the distance, exactly +0.0 between a cell and its duplicates or power-of-two multiples."""
+        the distance, exactly +0.0 between a cell and its duplicates or power-of-two multiples.  method "ivf" (sgl_knn_ivf):
+        the approximate inverted-list search -- n_lists lists from n_iter Lloyd steps of a coarse k-means (None:
+        ceil(sqrt(n_ref))), of which a query scans the n_probe nearest (None: the default of knn_ivf_host.h); a query whose
+        probed lists hold fewer than n_neighbors cells has -1 / +Inf in its last slots (knn_ivf_info counts them), and
+        n_probe == n_lists is the exact search bit for bit.  The rules are in include/singlet_hip.h."""
         code = knn_metric(metric)
         resident = None
         if reference is None:
             _, n, _ = self.dims()
             resident = (self.k, n)
+        if knn_method(method):
+            return knn_call(lambda *a: self._L.sgl_knn_ivf(self._h, *a), reference, query, dims, n_neighbors, resident, code,
+                            lambda n_ref, nd: (*knn_ivf_shape(n_ref, n_lists, n_probe), int(n_iter)))
         if code:
             return knn_call(lambda *a: self._L.sgl_knn_metric(self._h, *a), reference, query, dims, n_neighbors, resident, code)
         return knn_call(lambda *a: self._L.sgl_knn(self._h, *a), reference, query, dims, n_neighbors, resident)
@@ -527,6 +535,61 @@ class Context(_Handle):
         out = np.zeros(4, dtype=np.int64)
         check(self._L.sgl_knn_info(self._h, ptr(out, i64p)))
         return dict(zip(("instance", "segments", "queries_per_workgroup", "lists_global"), (int(v) for v in out)))
+
+    def knn_ivf_info(self):
+        """What the last inverted-list search on this context ran (sgl_knn_ivf_info): {"n_lists", "n_probe", "train_cells" (0
+        after op_ivf_search), "shortest_list", "longest_list", "empty_lists", "short_queries" (queries with -1 / +Inf slots),
+        "instance" (of the list scan, as knn_info)}."""
+        out = np.zeros(8, dtype=np.int64)
+        check(self._L.sgl_knn_ivf_info(self._h, ptr(out, i64p)))
+        return dict(zip(("n_lists", "n_probe", "train_cells", "shortest_list", "longest_list", "empty_lists", "short_queries", "instance"),
+                        (int(v) for v in out)))
+
+    def knn_ivf_stage_ms(self):
+        """With timing on, the milliseconds of the stages of the last inverted-list call (sgl_knn_ivf_stage_ms)."""
+        out = np.zeros(8)
+        check(self._L.sgl_knn_ivf_stage_ms(self._h, ptr(out, f64p)))
+        return dict(zip(("operands", "lloyd", "assign", "bucket", "probes", "tasks", "scan", "merge"), (float(v) for v in out)))
+
+    def op_ivf_train(self, n_lists, reference=None, dims=None, metric="euclidean", n_iter=10):
+        """The training of the inverted-list search alone (sgl_op_ivf_train): (centroids n_dims x n_lists, assign int32[n_ref],
+        the list of every reference).  reference / dims / metric as knn."""
+        code = knn_metric(metric)
+        if reference is None:
+            _, n_ref, _ = self.dims()
+            k, Rb = self.k, None
+        else:
+            Rb = colmajor(reference, "reference must be a k x n matrix")
+            n_ref, k = Rb.shape
+        d = None if dims is None else np.ascontiguousarray(np.asarray(dims), dtype=np.int32)
+        nd = int(k) if d is None else int(d.size)
+        L = int(n_lists)
+        cent = np.empty((max(L, 1), max(nd, 1)))
+        assign = np.empty(max(int(n_ref), 1), dtype=np.int32)
+        check(self._L.sgl_op_ivf_train(self._h, ptr(Rb, f64p), int(k), int(n_ref), ptr(d, i32p), 0 if d is None else nd, code, L, int(n_iter),
+                                       ptr(cent, f64p), ptr(assign, i32p)))
+        return cent[:L, :nd].T, assign[:int(n_ref)]
+
+    def op_ivf_search(self, centroids, assign, n_probe, n_neighbors=20, reference=None, query=None, dims=None, metric="euclidean",
+                      query_batch=0):
+        """The inverted-list search under the caller's centroids (n_dims x n_lists) and assignment (one list per reference,
+        any value in [0, n_lists)) (sgl_op_ivf_search): (idx, dist) as knn.  query_batch: 0 automatic, positive: that many
+        queries per pass -- the result does not depend on it."""
+        code = knn_metric(metric)
+        cent = colmajor(centroids, "centroids must be an n_dims x n_lists matrix")
+        a = np.ascontiguousarray(np.asarray(assign), dtype=np.int32)
+        resident = None
+        if reference is None:
+            _, n, _ = self.dims()
+            resident = (self.k, n)
+
+        def extra(n_ref, nd):
+            if cent.shape[1] != nd:
+                raise ValueError("centroids has %d rows, the search has %d dimensions" % (cent.shape[1], nd))
+            if a.ndim != 1 or a.shape[0] != n_ref:
+                raise ValueError("assign must hold one list per reference (%d)" % n_ref)
+            return (ptr(cent, f64p), int(cent.shape[0]), ptr(a, i32p), int(n_probe), int(query_batch))
+        return knn_call(lambda *x: self._L.sgl_op_ivf_search(self._h, *x), reference, query, dims, n_neighbors, resident, code, extra)
 
     def knn_metric_info(self):
         """knn_info() of the last search on this context (sgl_knn_metric_info) with "metric" (0 euclidean, 1 cosine,

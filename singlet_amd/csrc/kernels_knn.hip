@@ -31,6 +31,7 @@
 // however the references were cut.
 #include "sgl_internal.h"
 #include "knn_host.h"
+#include "knn_device.h"   // knn_step, knn_key, knn_insert: shared with the inverted-list scan
 
 #include <limits>
 
@@ -124,48 +125,6 @@ __global__ __launch_bounds__(64) void knn_unit(const double* __restrict__ X, int
             }
         }
     }
-}
-
-// One (pair, dimension) of the scan.  Euclidean: the three instructions of the unit's head comment.  DOT: the product and the
-// addition of the dot of two unit columns.
-template <bool DOT>
-__device__ __forceinline__ double knn_step(double s, double q, double r) {
-    if constexpr (DOT) {
-        return s + q * r;
-    } else {
-        const double t = q - r;
-        return s + t * t;
-    }
-}
-
-// What a pair is ranked by, once per pair.  Euclidean: the sum itself.  DOT: 1 - dot, and +0.0 below 2^-40 -- two bitwise
-// equal unit columns with a direction give a dot within rounding of 1, and the snap puts them at exactly +0.0.
-template <bool DOT>
-__device__ __forceinline__ double knn_key(double s) {
-    if constexpr (DOT) {
-        const double key = 1.0 - s;
-        return key < 0x1p-40 ? 0.0 : key;
-    } else {
-        return s;
-    }
-}
-
-// The candidate enters the list sorted by (s, index) whose slot t is ld[t * stride], li[t * stride]: behind every entry
-// whose s is not greater.  cnt = the slots filled; worst = the K-th s once the list is full.
-__device__ __forceinline__ void knn_insert(double* __restrict__ ld, int32_t* __restrict__ li, int64_t stride, int K, int& cnt, double& worst,
-                                           double s, int32_t r) {
-    int t = cnt < K ? cnt : K - 1;   // the slot that opens: the end of a list still filling, the last of a full one
-    while (t > 0) {
-        const double p = ld[(int64_t)(t - 1) * stride];
-        if (!(p > s)) break;
-        ld[(int64_t)t * stride] = p;
-        li[(int64_t)t * stride] = li[(int64_t)(t - 1) * stride];
-        --t;
-    }
-    ld[(int64_t)t * stride] = s;
-    li[(int64_t)t * stride] = r;
-    if (cnt < K) ++cnt;
-    if (cnt == K) worst = ld[(int64_t)(K - 1) * stride];
 }
 
 // The lists of one lane's QPL queries: where they live, and what the scan leaves in cs / ci when it ends.
@@ -565,6 +524,40 @@ int knn_entry(sgl_ctx* c, const char* who, const double* R, int32_t k, int64_t n
 }
 
 }  // namespace
+
+// ---- what the inverted-list search (kernels_knn_ivf.hip) calls: knn_device.h --------------------------------------------
+int sgl_knn_args(const char* who, int32_t k, int64_t n_ref, int64_t n_query, const int32_t* dims, int32_t n_dims, int32_t n_neighbors) {
+    return knn_args(who, k, n_ref, n_query, dims, n_dims, n_neighbors);
+}
+int sgl_knn_metric_arg(const char* who, int32_t metric) { return knn_metric_arg(who, metric); }
+int sgl_knn_check_finite(sgl_ctx* c, const char* who, const char* name, const double* X, int32_t k, int64_t n, unsigned long long* first_dev) {
+    return knn_check_finite(c, who, name, X, k, n, first_dev);
+}
+int sgl_knn_operand(sgl_ctx* c, const double* X, int32_t k, int64_t n, const int32_t* dims_dev, int nd, int32_t metric, double* packed,
+                    double* transposed, unsigned long long* no_direction) {
+    if (n == 0) return SGL_OK;
+    if (metric != KNN_METRIC_EUCLIDEAN) {
+        knn_unit<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream>>>(X, k, n, dims_dev, nd, metric == KNN_METRIC_CORRELATION ? 1 : 0,
+                                                                              packed, transposed, no_direction);
+        HIPCHK(hipGetLastError());
+        return SGL_OK;
+    }
+    const dim3 grid((unsigned)(((int64_t)nd * n + 255) / 256));
+    if (packed) {
+        knn_gather<<<grid, dim3(256), 0, c->stream>>>(X, k, n, dims_dev, nd, 0, packed);
+        HIPCHK(hipGetLastError());
+    }
+    if (transposed) {
+        knn_gather<<<grid, dim3(256), 0, c->stream>>>(X, k, n, dims_dev, nd, 1, transposed);
+        HIPCHK(hipGetLastError());
+    }
+    return SGL_OK;
+}
+int sgl_knn_scan(hipStream_t s, const KnnPlan& P, bool dot, const double* Rs, const double* Qs, int nd, int64_t nq, int64_t n_ref, int K,
+                 double* cs, int32_t* ci, int32_t* idx, double* dist) {
+    return dot ? launch_scan<true>(s, P, Rs, Qs, nd, nq, n_ref, K, cs, ci, idx, dist)
+               : launch_scan<false>(s, P, Rs, Qs, nd, nq, n_ref, K, cs, ci, idx, dist);
+}
 
 extern "C" int sgl_knn(sgl_ctx* c, const double* R, int32_t k, int64_t n_ref, const double* Q, int64_t n_query, const int32_t* dims,
                        int32_t n_dims, int32_t n_neighbors, int32_t* idx_out, double* dist_out) {

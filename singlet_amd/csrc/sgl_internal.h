@@ -253,6 +253,10 @@ struct sgl_ctx {
     // sgl_knn_info / sgl_knn_metric_info: instance, segments, queries per workgroup, list home, metric and columns without
     // direction of the last search
     int64_t knn_last[6] = {0, 0, 0, 0, 0, 0};
+    // sgl_knn_ivf_info: lists, probes, training cells, shortest and longest list, empty lists, short queries, scan instance of
+    // the last inverted-list search; sgl_knn_ivf_stage_ms: its stage times (timing on)
+    int64_t knn_ivf_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double knn_ivf_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t markers_last[4] = {0, 0, 0, 0};   // sgl_markers_info: genes sorted in LDS, long genes, batches, the LDS cap of the last rank pass
     int64_t gsea_last[5] = {0, 0, 0, 0, 0};   // sgl_gsea_info: sets, distinct sizes, s_max, batches, batch size of the last enrichment call
 
