@@ -883,6 +883,90 @@ SGL_API int sgl_op_ivf_search(sgl_ctx* ctx, const double* R, int32_t k, int64_t 
                               const double* centroids, int32_t n_lists, const int32_t* assign, int32_t n_probe,
                               int64_t query_batch, int32_t* idx_out, double* dist_out);
 
+/* Neighbour index and transfer: the references of a search kept on the device between calls, and the step that consumes a
+ * search of new cells against them -- labels and values of the reference cells transferred to the query cells (projection of
+ * new cells onto a trained w, then "what are they": the counterpart of ProjectData followed by Seurat's TransferData /
+ * MapQuery).  The one-shot searches upload, pack, train and bucket the references in every call; the index pays that once.
+ * One index per context; no team form, no R shim entry.
+ *
+ * The index is what sgl_knn_ivf has after its bucketing stage, kept instead of dropped:
+ *  - method 1 (inverted lists) keeps the packed references in list order, the table from list position to cell, the list
+ *    offsets, the centroids, the dims, the metric and n_dims; method 0 (exact) keeps the packed (unit) references of
+ *    sgl_knn_metric.  Everything else the build allocates -- the raw upload, for method 1 the packed references in stored
+ *    order and the training buffers -- is released before it returns.
+ *  - build: R, k, n_ref, dims, n_dims and metric are exactly sgl_knn_metric's, with its refusals and messages; R == NULL takes
+ *    the resident H.  The index is a SNAPSHOT: it holds its own packed copy; a fit continued afterwards, a new upload or a
+ *    subset neither changes it nor is changed by it.  method outside [0, 1]: SGL_EINVAL.  n_lists and n_iter follow
+ *    sgl_knn_ivf's rules and refusals; method 0 does not read them.  A second build replaces the first (a refused one leaves
+ *    it); the annotations of the replaced index go with it.  sgl_destroy frees the slot.  Team members and contexts with an
+ *    all-reduce hook are refused as by sgl_knn (SGL_ESTATE).
+ *  - search: Q is k x n_query with the build's k, and the build's dims are applied to it.  Q == NULL: SGL_EINVAL (a search of the
+ *    references among themselves stays with the one-shot calls).  The finiteness pass runs on the raw Q with sgl_knn's message.
+ *    n_neighbors in [1, min(256, n_ref)]; for method 1 n_probe in [1, min(n_lists, 64)], free to differ from search to search,
+ *    and query_batch as in sgl_op_ivf_search; method 0 reads neither.  n_query == 0: SGL_OK, nothing is written.  Without an
+ *    index: SGL_ESTATE.  The scan and merge count in the "scale" phase and knn_unit in "gram"; sgl_knn_info,
+ *    sgl_knn_metric_info, sgl_knn_ivf_info and sgl_knn_ivf_stage_ms stay as they were.
+ *  - the contract: for method 1 the result is bit for bit that of sgl_knn_ivf with the same R, Q, dims, metric, n_lists,
+ *    n_probe, n_iter and n_neighbors; for method 0 bit for bit that of sgl_knn / sgl_knn_metric -- for any number of searches
+ *    in any order against one index, whatever the batching.
+ *  - info: out[0] 1 when an index is present (all 0 otherwise), [1] method, [2] metric, [3] k, [4] n_dims, [5] n_ref, [6] n_lists,
+ *    [7] training cells, [8] shortest and [9] longest list, [10] empty lists ([6] .. [10]: 0 for method 0), [11] bytes resident
+ *    (the kept arrays above plus the annotations), [12] searches served since the build (sgl_knn_index_search and
+ *    sgl_knn_index_map calls that returned SGL_OK, those with n_query == 0 included), [13] the queries and [14] the short
+ *    queries of the last of them, [15] the kernel instance of its scan (0 .. 4 as sgl_knn_info).  A refused call leaves the
+ *    report as it was. */
+SGL_API int sgl_knn_index_build(sgl_ctx* ctx, const double* R, int32_t k, int64_t n_ref, const int32_t* dims, int32_t n_dims,
+                                int32_t metric, int32_t method, int32_t n_lists, int32_t n_iter);
+SGL_API int sgl_knn_index_search(sgl_ctx* ctx, const double* Q, int64_t n_query, int32_t n_neighbors, int32_t n_probe,
+                                 int64_t query_batch, int32_t* idx_out, double* dist_out);
+/* Releases the index and its annotations; SGL_OK also when there is none. */
+SGL_API int sgl_knn_index_drop(sgl_ctx* ctx);
+SGL_API int sgl_knn_index_info(sgl_ctx* ctx, int64_t out[16]);
+
+/* The transfer.  The rules are this library's own; tests/knn_transfer_restatement.py restates them in numpy and the device
+ * holds them bit for bit.  Everything is FP64; every product, quotient and sum is its own rounding (the unit is compiled with
+ * -ffp-contract=off); every sum is sequential over the slots in rank order, from +0.0.
+ *
+ * For one query, the slots i = 0 .. n_neighbors - 1 of its neighbour list (idx_i, d_i) are valid where idx_i >= 0; the
+ * padding (-1 / +Inf) follows the valid slots.
+ *  - weights.  weighting 0: w_i = 1.0.  weighting 1, the distance-weighted vote of Dudani (1976): with d_first and d_last the
+ *    distances of the first and of the last valid slot, w_i = (d_last - d_i) / (d_last - d_first) when d_last is finite and
+ *    d_last > d_first; otherwise every w_i = 1.0.  The nearest neighbour weighs 1 and the farthest 0; a single neighbour, or
+ *    neighbours all at one distance, vote equally.
+ *  - labels.  s_c = the sum of w_i over the valid slots whose reference has label c; W = the sum over the valid slots whose
+ *    reference has any label (>= 0).  With W > 0: scores[c] = s_c / W, pred = the class of the largest score, ties to the
+ *    lowest class, best = that score.  Otherwise -- no valid slot, none labelled, only zero-weight slots labelled --: every
+ *    score +0.0, pred = -1, best = +0.0.  scores_out is n_classes x n_query column-major, pred_out int32[n_query],
+ *    best_out double[n_query].
+ *  - values.  Wv = the sum of w_i over all valid slots; values[f] = (the sum over the valid slots of w_i * V[f, idx_i]) / Wv;
+ *    with no valid slot a quiet NaN.  values_out is n_values x n_query column-major.
+ *
+ * sgl_knn_index_annotate puts onto the index labels (int32[n_ref], every entry in [-1, n_classes), -1: the cell has no label;
+ * n_classes in [1, 65536]) and / or V (n_values x n_ref column-major, finite; n_values in [1, 1024]: layout coordinates, any
+ * per-cell covariate).  Either may be NULL and is then left as it is.  The arrays stay resident with the index.
+ * sgl_knn_index_map is one search, in batches, with the transfer of every batch run on the device: the neighbour lists do not
+ * travel to the host and back.  Q, n_neighbors and n_probe as sgl_knn_index_search.  Any output may be NULL; asking for
+ * pred / best / scores without labels on the index, or for values without V, is SGL_ESTATE.  It equals sgl_knn_index_search
+ * followed by sgl_op_knn_transfer bit for bit.
+ * sgl_op_knn_transfer is the stage operator on the caller's idx / dist (n_neighbors x n_query column-major, as the searches
+ * write them; n_neighbors in [1, 256]) and the caller's annotations (an output asked for without its annotation: SGL_EINVAL).
+ *  - refused with SGL_EINVAL and a message naming the value and its range, before anything is launched: weighting outside
+ *    [0, 1]; n_classes or n_values out of range; a label out of range (position and value); a non-finite V (column and row of
+ *    the first one in column-major order); for the operator an idx entry outside [-1, n_ref), or a valid slot behind a padding
+ *    slot (column, slot and value).  After every refusal the index and the context stay usable and no output has been written.
+ *  - kernel (singlet_amd/csrc/kernels_knn_transfer.hip; host rules in knn_transfer_host.h): one wave per query; the wave
+ *    stages the query's slots (cell, label, weight) in LDS once; lanes own the classes lane, lane + 64, ... and walk the slots
+ *    in rank order, so every sum is owned by one lane from start to end; the arg-max is a wave reduction on (score, class) by
+ *    comparisons alone; for the values lanes own the rows and read 64 consecutive doubles of column idx_i at a time.  No
+ *    floating-point atomics; 64-bit offsets; the time counts in the "scale" phase. */
+SGL_API int sgl_knn_index_annotate(sgl_ctx* ctx, const int32_t* labels, int32_t n_classes, const double* V, int32_t n_values);
+SGL_API int sgl_knn_index_map(sgl_ctx* ctx, const double* Q, int64_t n_query, int32_t n_neighbors, int32_t n_probe,
+                              int32_t weighting, int32_t* idx_out, double* dist_out, int32_t* pred_out, double* best_out,
+                              double* scores_out, double* values_out);
+SGL_API int sgl_op_knn_transfer(sgl_ctx* ctx, const int32_t* idx, const double* dist, int32_t n_neighbors, int64_t n_query,
+                                int64_t n_ref, const int32_t* labels, int32_t n_classes, const double* V, int32_t n_values,
+                                int32_t weighting, int32_t* pred_out, double* best_out, double* scores_out, double* values_out);
+
 /* Clustering: a deterministic multi-level Louvain modularity optimiser on a neighbour graph -- the step after
  * find_neighbors (Seurat's FindClusters on the SNN graph).  The reference's package has no clustering code (it hands the
  * graph to Seurat, whose optimiser visits the vertices in a seeded random order), so the rules below are this library's own,

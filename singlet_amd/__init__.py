@@ -8,7 +8,7 @@ from .api import (c_nmf, c_ard_nmf, c_linked_nmf, c_gcnmf, run_gcnmf, c_nmf_dens
                   find_local_neighbors, rescale_spatial, spatial_graph,
                   rowwise_compress_sparse, rowwise_compress_dense, RasterizeRowwise, RasterMatrix, subset, RunNMF,
                   group_means, run_linked_nmf, RunLNMF, MetadataSummary, GetSharedFactors, GetUniqueFactors, evaluate,
-                  find_variable_features, knn, knn_recall, find_neighbors, c_louvain, op_louvain_sweep,
+                  find_variable_features, knn, knn_recall, find_neighbors, ReferenceIndex, transfer_labels, transfer_values, map_query, c_louvain, op_louvain_sweep,
                   louvain_info, find_clusters, c_markers, find_all_markers, find_markers, fuzzy_simplicial_set, umap_layout,
                   op_umap_epoch, umap_info, find_ab_params, run_umap, c_gsea, read_gmt, run_gsea)
 from .native import native, NativeMatrix  # noqa: F401

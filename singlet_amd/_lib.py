@@ -134,6 +134,14 @@ SIGNATURES = {
     "sgl_op_ivf_train": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f64p, i32p]),
     "sgl_op_ivf_search": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64, f64p, C.c_int64, i32p, C.c_int32, C.c_int32, C.c_int32, f64p,
                                     C.c_int32, i32p, C.c_int32, C.c_int64, i32p, f64p]),
+    "sgl_knn_index_build": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64, i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "sgl_knn_index_search": (C.c_int, [C.c_void_p, f64p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, i32p, f64p]),
+    "sgl_knn_index_drop": (C.c_int, [C.c_void_p]),
+    "sgl_knn_index_info": (C.c_int, [C.c_void_p, i64p]),
+    "sgl_knn_index_annotate": (C.c_int, [C.c_void_p, i32p, C.c_int32, f64p, C.c_int32]),
+    "sgl_knn_index_map": (C.c_int, [C.c_void_p, f64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, i32p, f64p, i32p, f64p, f64p, f64p]),
+    "sgl_op_knn_transfer": (C.c_int, [C.c_void_p, i32p, f64p, C.c_int32, C.c_int64, C.c_int64, i32p, C.c_int32, f64p, C.c_int32, C.c_int32,
+                                      i32p, f64p, f64p, f64p]),
     "sgl_c_louvain": (C.c_int, _CSC + [C.c_int32, f64p, C.c_int32, C.c_double, C.c_int32, C.c_int32, i32p, i32p, i32p, f64p, i32p]),
     "sgl_op_louvain_sweep": (C.c_int, _CSC + [C.c_int32, i32p, C.c_double, i32p, f64p, f64p, i64p]),
     "sgl_louvain_info": (C.c_int, [i64p]),

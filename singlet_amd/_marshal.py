@@ -231,3 +231,39 @@ def knn_call(fn, reference, query, dims, n_neighbors, resident=None, metric=None
     more = () if extra is None else tuple(extra(int(n_ref), nd if d is not None else int(k)))
     check(fn(ptr(Rb, f64p), int(k), int(n_ref), ptr(Qb, f64p), int(nq), ptr(d, i32p), nd, K, *code, *more, ptr(idx, i32p), ptr(dist, f64p)))
     return idx, dist
+
+
+KNN_WEIGHTINGS = {"uniform": 0, "distance": 1}
+KNN_INDEX_FIELDS = ("present", "method", "metric", "k", "n_dims", "n_ref", "n_lists", "train_cells", "shortest_list", "longest_list",
+                    "empty_lists", "bytes", "searches", "last_queries", "last_short_queries", "instance")
+
+
+def knn_weighting(weighting):
+    """The weighting code of the transfer for a name: "uniform" (every neighbour votes 1) or "distance" (Dudani's weights)."""
+    if not isinstance(weighting, str) or weighting not in KNN_WEIGHTINGS:
+        raise ValueError("weighting must be 'uniform' or 'distance'")
+    return KNN_WEIGHTINGS[weighting]
+
+
+def knn_lists_in(idx, dist):
+    """(idx int32, dist float64, n_query, n_neighbors) of neighbour lists as the searches return them, n_query x n_neighbors: in
+    memory the n_neighbors x n_query column-major image the library reads."""
+    i, d = np.asarray(idx), np.asarray(dist, dtype=np.float64)
+    if i.ndim != 2 or d.shape != i.shape:
+        raise ValueError("idx and dist must be matrices of one shape, n_query x n_neighbors")
+    if i.dtype.kind not in "iu" or (i.size and (i.min() < -2**31 or i.max() >= 2**31)):
+        raise ValueError("idx must hold 32-bit reference indices (-1: padding)")
+    return np.ascontiguousarray(i, dtype=np.int32), np.ascontiguousarray(d), int(i.shape[0]), int(i.shape[1])
+
+
+def transfer_call(fn, nq, labelled, n_classes, n_values):
+    """Shared by Context.knn_index_map and Context.op_knn_transfer: fn(pred_out, best_out, scores_out, values_out) is the
+    library call with everything before the outputs bound.  labelled: the label outputs are asked for; n_values 0: no values.
+    Returns {"predicted", "score", "scores" (n_query x n_classes), "values" (n_query x n_values)}, None where not asked for."""
+    nq = max(int(nq), 0)
+    pred = np.empty(nq, dtype=np.int32) if labelled else None
+    best = np.empty(nq) if labelled else None
+    scores = np.empty((nq, int(n_classes))) if labelled and 1 <= int(n_classes) <= 65536 else None
+    values = np.empty((nq, int(n_values))) if 1 <= int(n_values) <= 1024 else None
+    check(fn(ptr(pred, i32p), ptr(best, f64p), ptr(scores, f64p), ptr(values, f64p)))
+    return {"predicted": pred, "score": best, "scores": scores, "values": values}

@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, label_list, markers_call
+from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, knn_weighting, label_list, markers_call
 from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
@@ -1535,6 +1535,115 @@ def find_neighbors(embedding, k_param=20, dims=None, compute_snn=True, prune_snn
     nn = dgCMatrix(x, rows, np.arange(n + 1, dtype=np.int64) * K, (n, n))
     snn = c_SNN(nn, np.nextafter(prune_snn, -np.inf), 0) if compute_snn else None
     return {"nn": nn, "snn": snn, "idx": idx, "dist": dist}
+
+
+# ---------------------------------------------------------------------------
+# A neighbour index kept on the GPU, and label / value transfer to query cells (ProjectData followed by Seurat's TransferData /
+# MapQuery; the rules are this library's own: include/singlet_hip.h, "Neighbour index and transfer")
+# ---------------------------------------------------------------------------
+class ReferenceIndex:
+    """The reference cells of an embedding kept on the device for any number of searches (Context.knn_index_build), with the
+    labels and values that are transferred to query cells.  `embedding_or_context` is cells x factors, or a Context with a fit,
+    whose H is snapshotted (a fit continued afterwards does not change the index), as in find_neighbors; from an array the
+    index owns a context of its own.  labels: one class in [-1, n_classes) per reference cell (-1: none); values: cells x
+    n_values (layout coordinates, any covariate).  dims are 1-based, as in find_neighbors, and are applied to every query.
+    method "ivf" (n_lists, n_iter as knn) or "exact".  A context manager; close() drops the index."""
+
+    def __init__(self, embedding_or_context, labels=None, values=None, dims=None, metric="euclidean", method="ivf", n_lists=None, n_iter=10):
+        from .context import Context
+        knn_metric(metric)
+        knn_method(method)
+        self._own = not isinstance(embedding_or_context, Context)
+        E = None
+        if self._own:
+            E = np.asarray(embedding_or_context, dtype=np.float64)
+            if E.ndim != 2:
+                raise ValueError("embedding must be a cells x factors matrix")
+        d0 = None
+        if dims is not None:
+            d = np.atleast_1d(np.asarray(dims))
+            if d.ndim != 1 or d.dtype.kind not in "iu" or d.size == 0 or np.min(d) < 1:
+                raise ValueError("dims are 1-based: at least one, none below 1")
+            d0 = d.astype(np.int64) - 1
+        self._ctx = Context(0) if self._own else embedding_or_context
+        try:
+            self._ctx.knn_index_build(None if E is None else E.T, d0, metric, method, n_lists, n_iter)
+            if labels is not None or values is not None:
+                V = None
+                if values is not None:
+                    V = np.asarray(values, dtype=np.float64)
+                    V = (V[:, None] if V.ndim == 1 else V).T
+                self._ctx.knn_index_annotate(labels, None, V)
+        except Exception:
+            self.close()
+            raise
+
+    def search(self, query, n_neighbors=20, n_probe=None, query_batch=0):
+        """(idx, dist) of the query cells (cells x factors), as knn returns them."""
+        return self._ctx.knn_index_search(np.asarray(query, dtype=np.float64).T, n_neighbors, n_probe, query_batch)
+
+    def map(self, query, n_neighbors=20, n_probe=None, weighting="distance"):
+        """Context.knn_index_map of the query cells (cells x factors); a query that comes back with fewer neighbours than
+        asked for raises ValueError naming n_probe."""
+        out = self._ctx.knn_index_map(np.asarray(query, dtype=np.float64).T, n_neighbors, n_probe, weighting)
+        _refuse_short("ReferenceIndex.map", out["idx"])
+        return out
+
+    def info(self):
+        return self._ctx.knn_index_info()
+
+    def close(self):
+        ctx, self._ctx = self._ctx, None
+        if ctx is None:
+            return
+        if self._own:
+            ctx.close()
+        else:
+            ctx.knn_index_drop()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _transfer(idx, dist, labels, n_classes, values, weighting):
+    from .context import Context
+    n_ref = np.asarray(labels).shape[0] if labels is not None else values.shape[1]
+    with Context(0) as c:
+        return c.op_knn_transfer(idx, dist, n_ref, labels, n_classes, values, weighting)
+
+
+def transfer_labels(idx, dist, labels, n_classes=None, weighting="distance"):
+    """The labels of the reference cells voted onto the query cells along their neighbour lists (sgl_op_knn_transfer): idx /
+    dist n_query x n_neighbors as a search returns them, labels one class in [-1, n_classes) per reference cell ->
+    {"predicted", "score", "scores"} as Context.knn_index_map returns them."""
+    if labels is None:
+        raise ValueError("labels must hold one class per reference cell")
+    out = _transfer(idx, dist, labels, n_classes, None, weighting)
+    return {k: out[k] for k in ("predicted", "score", "scores")}
+
+
+def transfer_values(idx, dist, values, weighting="distance"):
+    """The neighbour-weighted means of the reference cells' values (cells x n_values) for the query cells: n_query x
+    n_values (sgl_op_knn_transfer)."""
+    V = np.asarray(values, dtype=np.float64)
+    if V.ndim not in (1, 2):
+        raise ValueError("values must be a cells x n_values matrix")
+    return _transfer(idx, dist, None, None, (V[:, None] if V.ndim == 1 else V).T, weighting)["values"]
+
+
+def map_query(A, w, index, L1=0.01, L2=0, n_neighbors=20, n_probe=None, weighting="distance"):
+    """New cells mapped onto a reference: project_model(A, w, L1, L2) and its h handed to index.map (a ReferenceIndex built on
+    the reference's embedding in the same factor order).  A: anything project_model takes, native(...) included.  Returns
+    {"h", "d", "idx", "dist", "predicted", "score", "scores", "values"}; a query that comes back short raises ValueError."""
+    if not isinstance(index, ReferenceIndex):
+        raise ValueError("index must be a ReferenceIndex")
+    knn_weighting(weighting)
+    m = project_model(A, w, L1, L2)
+    out = index.map(np.asarray(m["h"]).T, n_neighbors, n_probe, weighting)
+    return {"h": m["h"], "d": m["d"], **out}
 
 
 # ---------------------------------------------------------------------------

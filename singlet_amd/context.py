@@ -6,8 +6,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
-from ._marshal import (MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, label_list,
-                       markers_call)
+from ._marshal import (KNN_INDEX_FIELDS, MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call,
+                       knn_ivf_shape, knn_lists_in, knn_method, knn_metric, knn_weighting, label_list, markers_call, transfer_call)
 from .sparse import as_dgCMatrix
 
 SYNTH_SEED = 0x5EED
@@ -590,6 +590,115 @@ class Context(_Handle):
                 raise ValueError("assign must hold one list per reference (%d)" % n_ref)
             return (ptr(cent, f64p), int(cent.shape[0]), ptr(a, i32p), int(n_probe), int(query_batch))
         return knn_call(lambda *x: self._L.sgl_op_ivf_search(self._h, *x), reference, query, dims, n_neighbors, resident, code, extra)
+
+    def knn_index_build(self, reference=None, dims=None, metric="euclidean", method="ivf", n_lists=None, n_iter=10):
+        """Builds the neighbour index of this context and keeps it on the device (sgl_knn_index_build): the packed references
+        of knn() -- for method "ivf" trained and cut into n_lists lists (None: ceil(sqrt(n_ref))) by n_iter Lloyd steps, for
+        "exact" as they are.  reference: k x n (R's orientation); None: a snapshot of the H of the current fit.  dims / metric
+        as knn; the dims are applied to every later query.  A second build replaces the first and its annotations."""
+        code = knn_metric(metric)
+        ivf = knn_method(method)
+        if reference is None:
+            _, n_ref, _ = self.dims()
+            k, Rb = self.k, None
+        else:
+            Rb = colmajor(reference, "reference must be a k x n matrix")
+            n_ref, k = Rb.shape
+        d, nd = None, 0
+        if dims is not None:
+            d = np.ascontiguousarray(np.asarray(dims), dtype=np.int32)
+            nd = int(d.size)
+        L = knn_ivf_shape(n_ref, n_lists, None)[0] if ivf else 0
+        check(self._L.sgl_knn_index_build(self._h, ptr(Rb, f64p), int(k), int(n_ref), ptr(d, i32p), nd, code, int(ivf), L, int(n_iter)))
+        self._knn_annotations = [0, 0]
+
+    def _knn_index_query(self, query, n_probe):
+        """(the k x n_query image of the query, n_query, n_probe as the library takes it) for a call against the index."""
+        info = self.knn_index_info()
+        Qb = colmajor(query, "query must be a k x n matrix")
+        if info["present"] and Qb.shape[1] != info["k"]:
+            raise ValueError("query has %d rows, the index was built on %d" % (Qb.shape[1], info["k"]))
+        if n_probe is None:
+            n_probe = knn_ivf_shape(info["n_ref"], info["n_lists"], None)[1] if info["method"] == 1 else 0
+        nq = int(Qb.shape[0])
+        if nq == 0:
+            Qb = np.zeros((1, Qb.shape[1]))   # (no query: a buffer that is there, so that the pointer is not NULL)
+        return Qb, nq, int(n_probe)
+
+    def knn_index_search(self, query, n_neighbors=20, n_probe=None, query_batch=0):
+        """The neighbours of the query columns (k x n_query) among the references of the index (sgl_knn_index_search): (idx,
+        dist) as knn returns them -- bit for bit what knn(method=...) gives for the same references and queries.  n_probe
+        (inverted lists only; None: the default of knn) may differ from search to search; query_batch as op_ivf_search."""
+        Qb, nq, n_probe = self._knn_index_query(query, n_probe)
+        K = int(n_neighbors)
+        shape = (nq, K) if 1 <= K <= 256 else (1, 1)   # outside it the library refuses before it writes
+        idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
+        check(self._L.sgl_knn_index_search(self._h, ptr(Qb, f64p), nq, K, n_probe, int(query_batch), ptr(idx, i32p), ptr(dist, f64p)))
+        return idx, dist
+
+    def knn_index_annotate(self, labels=None, n_classes=None, values=None):
+        """Puts labels (one class in [-1, n_classes) per reference cell, -1: none; n_classes None: 1 + the largest) and / or
+        values (n_values x n_ref, R's orientation: one column per reference cell) onto the index (sgl_knn_index_annotate);
+        what is None stays as it is."""
+        n_ref = self.knn_index_info()["n_ref"]
+        g, G, Vb, nv = None, 0, None, 0
+        if labels is not None:
+            g, G = label_list(labels, n_ref or None, n_classes)
+        if values is not None:
+            Vb = colmajor(values, "values must be an n_values x n_ref matrix")
+            if n_ref and Vb.shape[0] != n_ref:
+                raise ValueError("values has %d columns, the index has %d references" % (Vb.shape[0], n_ref))
+            nv = int(Vb.shape[1])
+        check(self._L.sgl_knn_index_annotate(self._h, ptr(g, i32p), int(G), ptr(Vb, f64p), nv))
+        a = getattr(self, "_knn_annotations", [0, 0])
+        self._knn_annotations = [G if g is not None else a[0], nv if Vb is not None else a[1]]
+
+    def knn_index_map(self, query, n_neighbors=20, n_probe=None, weighting="distance"):
+        """One search against the index with the transfer of its annotations run on the device (sgl_knn_index_map): {"idx",
+        "dist"} as knn_index_search, and for the annotations the index holds {"predicted" (int32 per query, -1: no vote),
+        "score" (the winning share), "scores" (n_query x n_classes), "values" (n_query x n_values)}, None for what it does
+        not hold.  weighting: "distance" (Dudani's weights: the nearest neighbour votes 1, the farthest 0) or "uniform"."""
+        w = knn_weighting(weighting)
+        Qb, nq, n_probe = self._knn_index_query(query, n_probe)
+        K = int(n_neighbors)
+        shape = (nq, K) if 1 <= K <= 256 else (1, 1)
+        idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
+        G, nv = getattr(self, "_knn_annotations", [0, 0])
+        out = transfer_call(lambda *o: self._L.sgl_knn_index_map(self._h, ptr(Qb, f64p), nq, K, n_probe, w, ptr(idx, i32p), ptr(dist, f64p), *o),
+                            nq, G > 0, G, nv)
+        return {"idx": idx, "dist": dist, **out}
+
+    def knn_index_drop(self):
+        """Releases the index and its annotations (sgl_knn_index_drop); nothing happens without one."""
+        check(self._L.sgl_knn_index_drop(self._h))
+        self._knn_annotations = [0, 0]
+
+    def knn_index_info(self):
+        """The index of this context (sgl_knn_index_info): {"present" (0 / 1), "method" (0 exact, 1 ivf), "metric", "k",
+        "n_dims", "n_ref", "n_lists", "train_cells", "shortest_list", "longest_list", "empty_lists", "bytes" (resident),
+        "searches" (served since the build), "last_queries", "last_short_queries" (of the last search), "instance" (of its
+        scan, as knn_info)}."""
+        out = np.zeros(16, dtype=np.int64)
+        check(self._L.sgl_knn_index_info(self._h, ptr(out, i64p)))
+        return dict(zip(KNN_INDEX_FIELDS, (int(v) for v in out)))
+
+    def op_knn_transfer(self, idx, dist, n_ref, labels=None, n_classes=None, values=None, weighting="distance"):
+        """The transfer stage alone on the caller's neighbour lists (sgl_op_knn_transfer): idx / dist n_query x n_neighbors as
+        the searches return them, labels and values as knn_index_annotate takes them -> the transfer outputs of
+        knn_index_map."""
+        w = knn_weighting(weighting)
+        i, d, nq, K = knn_lists_in(idx, dist)
+        g, G, Vb, nv = None, 0, None, 0
+        if labels is not None:
+            g, G = label_list(labels, None, n_classes)
+        if values is not None:
+            Vb = colmajor(values, "values must be an n_values x n_ref matrix")
+            nv = int(Vb.shape[1])
+        for name, a in (("labels", g), ("values", Vb)):
+            if a is not None and a.shape[0] != int(n_ref):
+                raise ValueError("%s must hold one entry per reference cell (%d)" % (name, int(n_ref)))
+        return transfer_call(lambda *o: self._L.sgl_op_knn_transfer(self._h, ptr(i, i32p), ptr(d, f64p), K, nq, int(n_ref), ptr(g, i32p), int(G),
+                                                                    ptr(Vb, f64p), nv, w, *o), nq, g is not None, G, nv)
 
     def knn_metric_info(self):
         """knn_info() of the last search on this context (sgl_knn_metric_info) with "metric" (0 euclidean, 1 cosine,

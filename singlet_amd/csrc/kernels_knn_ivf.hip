@@ -25,10 +25,12 @@
 // the batch, exactly the segments knn_finish merges.  No floating-point atomics; 64-bit offsets.
 #include "sgl_internal.h"
 #include "knn_ivf_host.h"
+#include "knn_transfer_host.h"
 #include "knn_device.h"
 
 #include <chrono>
 #include <cmath>
+#include <functional>
 #include <limits>
 #include <vector>
 
@@ -336,8 +338,8 @@ struct StageClock {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     bool on = false;
     std::chrono::steady_clock::time_point h0;
-    explicit StageClock(sgl_ctx* c_) : c(c_) {
-        on = c->timing && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    explicit StageClock(sgl_ctx* c_, bool enabled = true) : c(c_) {   // enabled false: the calls on a kept index, which time no stage
+        on = enabled && c->timing && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
         if (!on) (void)hipGetLastError();
     }
     ~StageClock() {
@@ -498,13 +500,23 @@ int ivf_train(sgl_ctx* c, IvfBuffers& B, StageClock& clk, int64_t n_ref, int32_t
     return SGL_OK;
 }
 
-// The search under the centroids B.C (device) and a checked assignment.  info: what sgl_knn_ivf_info reports, filled here
-// except the training cells.
-int ivf_search(sgl_ctx* c, IvfBuffers& B, StageClock& clk, int64_t n_ref, int32_t K, int32_t metric, int32_t n_lists, const int32_t* assign,
-               int32_t n_probe, int64_t query_batch, int32_t* idx_out, double* dist_out, int64_t info[8]) {
+// What a search reads of the lists (device pointers): the one-shot calls point it at their own buffers, a kept index at its own.
+struct IvfResident {
+    const double* Rl;      // the packed references in list order
+    const double* C;       // the centroids
+    const int64_t* off;
+    const int32_t* cell;
+    int32_t n_lists;
+};
+
+// Called once per batch of queries with the batch's result still on the device: idx / dist are n_neighbors x nb (B.idx, B.dist).
+// The stream has been synchronised when it returns.
+typedef std::function<int(int64_t q0, int64_t nb, const int32_t* idx_dev, const double* dist_dev)> IvfAfterBatch;
+
+// Bucketing under a checked assignment: list offsets and the table from position to cell on the host, the packed references
+// in list order on the device (B.off, B.cell, B.Rl).  info: the lists' part of what sgl_knn_ivf_info reports.
+int ivf_bucket(sgl_ctx* c, IvfBuffers& B, StageClock& clk, int64_t n_ref, int32_t n_lists, const int32_t* assign, int64_t info[8]) {
     const int nd = B.nd;
-    const int64_t nq = B.nq;
-    // bucketing: list offsets and the table from position to cell on the host, the packed references in list order on the device
     clk.begin();
     std::vector<int64_t> off((size_t)n_lists + 1);
     std::vector<int32_t> cell((size_t)n_ref);
@@ -512,20 +524,32 @@ int ivf_search(sgl_ctx* c, IvfBuffers& B, StageClock& clk, int64_t n_ref, int32_
     SGLCHK(B.off.alloc(off.size()));
     SGLCHK(B.cell.alloc(cell.size()));
     SGLCHK(B.Rl.alloc((size_t)nd * (size_t)n_ref));
-    SGLCHK(B.short_queries.alloc(1));
     HIPCHK(hipMemcpyAsync(B.off.p, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(B.cell.p, cell.data(), sizeof(int32_t) * cell.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(B.short_queries.p, 0, sizeof(unsigned long long), c->stream));
     ivf_reorder<<<dim3((unsigned)(((int64_t)nd * n_ref + 255) / 256)), dim3(256), 0, c->stream>>>(B.Rs, nd, B.cell.p, n_ref, B.Rl.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     clk.end(ST_BUCKET);
     info[0] = n_lists;
-    info[1] = n_probe;
     knn_ivf_list_stats(off.data(), n_lists, &info[3], &info[4], &info[5]);
     info[6] = 0;
     info[7] = knn_instance(nd);
+    return SGL_OK;
+}
+
+// The queries B.Qs (packed, nd x B.nq) against the lists S: probes, task table, list scan and merge, in batches.  info[1], [6]
+// and [7] are filled here.  after: see IvfAfterBatch (may be empty).
+int ivf_query(sgl_ctx* c, IvfBuffers& B, StageClock& clk, const IvfResident& S, int32_t K, int32_t metric, int32_t n_probe, int64_t query_batch,
+              int32_t* idx_out, double* dist_out, int64_t info[8], const IvfAfterBatch& after) {
+    const int nd = B.nd;
+    const int64_t nq = B.nq;
+    const int32_t n_lists = S.n_lists;
+    info[1] = n_probe;
+    info[6] = 0;
+    info[7] = knn_instance(nd);
     if (nq == 0) return SGL_OK;
+    SGLCHK(B.short_queries.alloc(1));
+    HIPCHK(hipMemsetAsync(B.short_queries.p, 0, sizeof(unsigned long long), c->stream));
 
     const int ppb = knn_ivf_pairs_per_block(nd);
     const int64_t batch = knn_ivf_batch(nq, n_probe, K, query_batch, KNN_IVF_SCRATCH_BYTES);
@@ -536,7 +560,7 @@ int ivf_search(sgl_ctx* c, IvfBuffers& B, StageClock& clk, int64_t n_ref, int32_
         const int64_t n_pairs = nb * n_probe;
         const double* Xb = B.Qs + q0 * nd;
         clk.begin();
-        SGLCHK(ivf_nearest(c, B, B.C.p, n_lists, Xb, nb, n_probe));
+        SGLCHK(ivf_nearest(c, B, S.C, n_lists, Xb, nb, n_probe));
         probes.resize((size_t)n_pairs);
         HIPCHK(hipMemcpyAsync(probes.data(), B.near.p(), sizeof(int32_t) * (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -563,13 +587,13 @@ int ivf_search(sgl_ctx* c, IvfBuffers& B, StageClock& clk, int64_t n_ref, int32_
         HIPCHK(hipMemcpyAsync(B.pair_slot.p(), pair_slot.data(), sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(B.block_list.p(), block_list.data(), sizeof(int32_t) * (size_t)blocks, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(B.block_begin.p(), block_begin.data(), sizeof(int64_t) * ((size_t)blocks + 1), hipMemcpyHostToDevice, c->stream));
-        const IvfTasks T = {B.pair_query.p(), B.pair_slot.p(), B.block_list.p(), B.block_begin.p(), B.off.p, B.cell.p};
+        const IvfTasks T = {B.pair_query.p(), B.pair_slot.p(), B.block_list.p(), B.block_begin.p(), S.off, S.cell};
         const bool dot = metric != KNN_METRIC_EUCLIDEAN;
         {
             Phase ph(c, SGL_PH_SCALE);   // scan and merge, as under sgl_knn
             clk.begin();
-            if (dot) SGLCHK(launch_lists<true>(c->stream, (int)info[7], blocks, B.Rl.p, Xb, nd, nb, T, K, B.cs.p(), B.ci.p()));
-            else SGLCHK(launch_lists<false>(c->stream, (int)info[7], blocks, B.Rl.p, Xb, nd, nb, T, K, B.cs.p(), B.ci.p()));
+            if (dot) SGLCHK(launch_lists<true>(c->stream, (int)info[7], blocks, S.Rl, Xb, nd, nb, T, K, B.cs.p(), B.ci.p()));
+            else SGLCHK(launch_lists<false>(c->stream, (int)info[7], blocks, S.Rl, Xb, nd, nb, T, K, B.cs.p(), B.ci.p()));
             clk.end(ST_SCAN);
             clk.begin();
             const dim3 grid((unsigned)((nb + 255) / 256));
@@ -582,6 +606,7 @@ int ivf_search(sgl_ctx* c, IvfBuffers& B, StageClock& clk, int64_t n_ref, int32_
         }
         if (idx_out) HIPCHK(hipMemcpyAsync(idx_out + q0 * K, B.idx.p(), sizeof(int32_t) * (size_t)K * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
         if (dist_out) HIPCHK(hipMemcpyAsync(dist_out + q0 * K, B.dist.p(), sizeof(double) * (size_t)K * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+        if (after) SGLCHK(after(q0, nb, B.idx.p(), B.dist.p()));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     unsigned long long short_queries = 0;
@@ -589,6 +614,15 @@ int ivf_search(sgl_ctx* c, IvfBuffers& B, StageClock& clk, int64_t n_ref, int32_
     HIPCHK(hipStreamSynchronize(c->stream));
     info[6] = (int64_t)short_queries;
     return SGL_OK;
+}
+
+// The search under the centroids B.C (device) and a checked assignment.  info: what sgl_knn_ivf_info reports, filled here
+// except the training cells.
+int ivf_search(sgl_ctx* c, IvfBuffers& B, StageClock& clk, int64_t n_ref, int32_t K, int32_t metric, int32_t n_lists, const int32_t* assign,
+               int32_t n_probe, int64_t query_batch, int32_t* idx_out, double* dist_out, int64_t info[8]) {
+    SGLCHK(ivf_bucket(c, B, clk, n_ref, n_lists, assign, info));
+    const IvfResident S = {B.Rl.p, B.C.p, B.off.p, B.cell.p, n_lists};
+    return ivf_query(c, B, clk, S, K, metric, n_probe, query_batch, idx_out, dist_out, info, IvfAfterBatch());
 }
 
 void ivf_clock_reset(sgl_ctx* c) {
@@ -721,4 +755,311 @@ extern "C" int sgl_op_ivf_search(sgl_ctx* c, const double* R, int32_t k, int64_t
     if (rc == SGL_OK)
         for (int q = 0; q < 8; ++q) c->knn_ivf_last[q] = info[q];
     return rc;
+}
+
+// ---- the neighbour index kept on the device (include/singlet_hip.h, "Neighbour index and transfer") ----------------------
+// What ivf_search has after its bucketing stage, kept instead of dropped -- or, for the exact method, the packed references of
+// sgl_knn_metric -- with the annotations sgl_knn_index_annotate puts onto it.  One per context (sgl_ctx::knn_index).
+struct KnnIndex {
+    int32_t method = 0, metric = 0, k = 0, nd = 0, n_lists = 0;
+    int64_t n_ref = 0;
+    DevBuf<double> Rx;        // the packed references: in list order (method 1), in stored order (method 0)
+    DevBuf<double> C;         // method 1: the centroids, the table from position to cell, the list offsets
+    DevBuf<int32_t> cell;
+    DevBuf<int64_t> off;
+    DevBuf<int32_t> dims;     // the build's dims (p == nullptr: all k rows)
+    int64_t train_cells = 0, shortest = 0, longest = 0, empty = 0;
+    DevBuf<int32_t> labels;   // int32[n_ref] in [-1, n_classes)
+    DevBuf<double> V;         // n_values x n_ref
+    int32_t n_classes = 0, n_values = 0;
+    int64_t searches = 0, last_queries = 0, last_short = 0, instance = 0;
+
+    int64_t bytes() const {
+        int64_t b = 8 * (int64_t)nd * n_ref;
+        if (method == 1) b += 8 * (int64_t)nd * n_lists + 4 * n_ref + 8 * ((int64_t)n_lists + 1);
+        if (dims.p) b += 4 * (int64_t)nd;
+        if (labels.p) b += 4 * n_ref;
+        if (V.p) b += 8 * (int64_t)n_values * n_ref;
+        return b;
+    }
+};
+
+void sgl_knn_index_free(sgl_ctx* c) {
+    delete c->knn_index;
+    c->knn_index = nullptr;
+}
+
+namespace {
+
+template <typename T>
+void take(DevBuf<T>& to, DevBuf<T>& from) { std::swap(to.p, from.p); }
+
+int index_method_arg(const char* who, int32_t method) {
+    if (method == 0 || method == 1) return SGL_OK;
+    sgl_set_error("%s: method = %d is outside [0, 1]", who, method);
+    return SGL_EINVAL;
+}
+
+KnnIndex* index_of(sgl_ctx* c, const char* who) {
+    if (!c->knn_index) sgl_set_error("%s: the context holds no neighbour index (call sgl_knn_index_build)", who);
+    return c->knn_index;
+}
+
+// The refusals of a search against the index ix, before anything is uploaded.
+int index_search_args(const char* who, const KnnIndex* ix, const double* Q, int64_t n_query, int32_t K, int32_t n_probe, int64_t query_batch) {
+    if (!Q) { sgl_set_error("%s: Q is NULL (a search of the references among themselves is sgl_knn's, sgl_knn_ivf's)", who); return SGL_EINVAL; }
+    if (n_query < 0) { sgl_set_error("%s: n_query = %lld is negative", who, (long long)n_query); return SGL_EINVAL; }
+    if (K < 1 || K > KNN_MAX_NEIGHBORS || (int64_t)K > ix->n_ref) {
+        sgl_set_error("%s: n_neighbors = %d is outside [1, min(%d, n_ref = %lld)]", who, K, KNN_MAX_NEIGHBORS, (long long)ix->n_ref);
+        return SGL_EINVAL;
+    }
+    if (ix->method == 1 && (n_probe < 1 || n_probe > knn_ivf_max_probes(ix->n_lists))) {
+        sgl_set_error("%s: n_probe = %d is outside [1, min(n_lists = %d, %d)]", who, n_probe, ix->n_lists, KNN_IVF_MAX_PROBES);
+        return SGL_EINVAL;
+    }
+    if (ix->method == 1 && query_batch < 0) { sgl_set_error("%s: query_batch = %lld is negative", who, (long long)query_batch); return SGL_EINVAL; }
+    return SGL_OK;
+}
+
+// One search of the k x nq host columns Q against the index: the upload, the finiteness pass on the raw Q, the packed queries
+// under the build's dims and metric, and the scan of the index's method.  exact_batch: queries per pass of method 0 (0: all).
+int index_query(sgl_ctx* c, const char* who, KnnIndex* ix, IvfBuffers& B, const double* Q, int64_t nq, int32_t K, int32_t n_probe,
+                int64_t query_batch, int64_t exact_batch, int32_t* idx_out, double* dist_out, const IvfAfterBatch& after, int64_t* short_out) {
+    const int nd = ix->nd;
+    const int32_t k = ix->k;
+    StageClock clk(c, false);
+    SGLCHK(B.Q.alloc((size_t)k * (size_t)nq));
+    HIPCHK(hipMemcpyAsync(B.Q.p, Q, sizeof(double) * (size_t)k * (size_t)nq, hipMemcpyHostToDevice, c->stream));
+    SGLCHK(B.first.alloc(1));
+    SGLCHK(sgl_knn_check_finite(c, who, "Q", B.Q.p, k, nq, B.first.p));
+    SGLCHK(B.no_direction.alloc(1));
+    HIPCHK(hipMemsetAsync(B.no_direction.p, 0, sizeof(unsigned long long), c->stream));
+    SGLCHK(B.Qp.alloc((size_t)nd * (size_t)nq));
+    {
+        Phase ph(c, SGL_PH_GRAM);   // as sgl_knn_metric books knn_unit
+        SGLCHK(sgl_knn_operand(c, B.Q.p, k, nq, ix->dims.p, nd, ix->metric, B.Qp.p, nullptr, B.no_direction.p));
+    }
+    B.nd = nd;
+    B.nq = nq;
+    B.Qs = B.Qp.p;
+    *short_out = 0;
+    if (ix->method == 1) {
+        int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        const IvfResident S = {ix->Rx.p, ix->C.p, ix->off.p, ix->cell.p, ix->n_lists};
+        SGLCHK(ivf_query(c, B, clk, S, K, ix->metric, n_probe, query_batch, idx_out, dist_out, info, after));
+        *short_out = info[6];
+        return SGL_OK;
+    }
+    // the exact scan of sgl_knn_metric over the kept references; the merge makes the result independent of the cut
+    const int64_t batch = exact_batch > 0 && exact_batch < nq ? exact_batch : nq;
+    const bool dot = ix->metric != KNN_METRIC_EUCLIDEAN;
+    for (int64_t q0 = 0; q0 < nq; q0 += batch) {
+        const int64_t nb = std::min(batch, nq - q0);
+        const KnnPlan P = knn_plan(nb, ix->n_ref, nd, K);
+        const double* Xb = B.Qs + q0 * nd;
+        if (P.instance == KNN_GENERIC_INSTANCE) {
+            SGLCHK(B.Xt.need((size_t)nd * (size_t)nb));
+            SGLCHK(sgl_knn_operand(c, Xb, nd, nb, nullptr, nd, KNN_METRIC_EUCLIDEAN, nullptr, B.Xt.p(), nullptr));
+            Xb = B.Xt.p();
+        }
+        const size_t slots = (size_t)P.segments * (size_t)K * (size_t)nb;
+        SGLCHK(B.cs.need(slots));
+        SGLCHK(B.ci.need(slots));
+        SGLCHK(B.idx.need((size_t)K * (size_t)nb));
+        SGLCHK(B.dist.need((size_t)K * (size_t)nb));
+        {
+            Phase ph(c, SGL_PH_SCALE);
+            SGLCHK(sgl_knn_scan(c->stream, P, dot, ix->Rx.p, Xb, nd, nb, ix->n_ref, K, B.cs.p(), B.ci.p(), B.idx.p(), B.dist.p()));
+        }
+        if (idx_out) HIPCHK(hipMemcpyAsync(idx_out + q0 * K, B.idx.p(), sizeof(int32_t) * (size_t)K * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+        if (dist_out) HIPCHK(hipMemcpyAsync(dist_out + q0 * K, B.dist.p(), sizeof(double) * (size_t)K * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+        if (after) SGLCHK(after(q0, nb, B.idx.p(), B.dist.p()));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return SGL_OK;
+}
+
+void index_served(KnnIndex* ix, int64_t nq, int64_t short_queries) {
+    ++ix->searches;
+    ix->last_queries = nq;
+    ix->last_short = short_queries;
+}
+
+}  // namespace
+
+extern "C" int sgl_knn_index_build(sgl_ctx* c, const double* R, int32_t k, int64_t n_ref, const int32_t* dims, int32_t n_dims, int32_t metric,
+                                   int32_t method, int32_t n_lists, int32_t n_iter) {
+    const char* who = "sgl_knn_index_build";
+    if (c == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    SGLCHK(ivf_state(c, who, R, k, n_ref));
+    SGLCHK(sgl_knn_args(who, k, n_ref, 0, dims, n_dims, 1));
+    SGLCHK(index_method_arg(who, method));
+    if (method == 1) SGLCHK(ivf_args(who, n_ref, n_lists, 1, n_iter, metric));
+    else SGLCHK(sgl_knn_metric_arg(who, metric));
+    IvfBuffers B;
+    StageClock clk(c, false);
+    std::vector<double> Chost;
+    std::vector<int32_t> assign;
+    int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long no_direction = 0;
+    int rc = ivf_operands(c, who, B, R, k, n_ref, false, nullptr, 0, dims, n_dims, metric, &no_direction);
+    if (rc == SGL_OK && method == 1) rc = ivf_train(c, B, clk, n_ref, n_lists, n_iter, Chost, assign, &info[2]);
+    if (rc == SGL_OK && method == 1) rc = ivf_bucket(c, B, clk, n_ref, n_lists, assign.data(), info);
+    rc = ivf_drain(c, rc, who);
+    if (rc != SGL_OK) return rc;
+    KnnIndex* ix = new KnnIndex;
+    ix->method = method;
+    ix->metric = metric;
+    ix->k = k;
+    ix->nd = B.nd;
+    ix->n_ref = n_ref;
+    ix->instance = knn_instance(B.nd);
+    take(ix->dims, B.dims);
+    if (method == 1) {
+        ix->n_lists = n_lists;
+        ix->train_cells = info[2];
+        ix->shortest = info[3];
+        ix->longest = info[4];
+        ix->empty = info[5];
+        take(ix->Rx, B.Rl);
+        take(ix->C, B.C);
+        take(ix->cell, B.cell);
+        take(ix->off, B.off);
+    } else {
+        take(ix->Rx, B.Rp);
+    }
+    sgl_knn_index_free(c);   // a second build replaces the first
+    c->knn_index = ix;
+    return SGL_OK;            // B releases everything else: the raw upload, and for method 1 Rp and the training buffers
+}
+
+extern "C" int sgl_knn_index_search(sgl_ctx* c, const double* Q, int64_t n_query, int32_t n_neighbors, int32_t n_probe, int64_t query_batch,
+                                    int32_t* idx_out, double* dist_out) {
+    const char* who = "sgl_knn_index_search";
+    if (c == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    KnnIndex* ix = index_of(c, who);
+    if (!ix) return SGL_ESTATE;
+    SGLCHK(index_search_args(who, ix, Q, n_query, n_neighbors, n_probe, query_batch));
+    int64_t short_queries = 0;
+    if (n_query > 0) {
+        IvfBuffers B;
+        const int rc = ivf_drain(c, index_query(c, who, ix, B, Q, n_query, n_neighbors, n_probe, query_batch, 0, idx_out, dist_out, IvfAfterBatch(),
+                                                &short_queries), who);
+        if (rc != SGL_OK) return rc;
+    }
+    index_served(ix, n_query, short_queries);
+    return SGL_OK;
+}
+
+extern "C" int sgl_knn_index_drop(sgl_ctx* c) {
+    if (c == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    sgl_knn_index_free(c);
+    return SGL_OK;
+}
+
+extern "C" int sgl_knn_index_info(sgl_ctx* c, int64_t out[16]) {
+    if (c == nullptr || out == nullptr) { sgl_set_error("sgl_knn_index_info: NULL context or output"); return SGL_EINVAL; }
+    for (int q = 0; q < 16; ++q) out[q] = 0;
+    const KnnIndex* ix = c->knn_index;
+    if (!ix) return SGL_OK;
+    const int64_t v[16] = {1, ix->method, ix->metric, ix->k, ix->nd, ix->n_ref, ix->n_lists, ix->train_cells, ix->shortest, ix->longest,
+                           ix->empty, ix->bytes(), ix->searches, ix->last_queries, ix->last_short, ix->instance};
+    for (int q = 0; q < 16; ++q) out[q] = v[q];
+    return SGL_OK;
+}
+
+extern "C" int sgl_knn_index_annotate(sgl_ctx* c, const int32_t* labels, int32_t n_classes, const double* V, int32_t n_values) {
+    const char* who = "sgl_knn_index_annotate";
+    if (c == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    KnnIndex* ix = index_of(c, who);
+    if (!ix) return SGL_ESTATE;
+    SGLCHK(sgl_knn_transfer_args(who, 0, 1, 0, ix->n_ref, labels != nullptr, n_classes, V != nullptr, n_values));
+    if (labels) SGLCHK(sgl_knn_transfer_labels_check(who, labels, ix->n_ref, n_classes));
+    DevBuf<int32_t> lab;
+    DevBuf<double> val;
+    DevBuf<unsigned long long> first;
+    int rc = SGL_OK;
+    auto stage = [&]() -> int {
+        if (V) {
+            SGLCHK(val.alloc((size_t)n_values * (size_t)ix->n_ref));
+            SGLCHK(first.alloc(1));
+            HIPCHK(hipMemcpyAsync(val.p, V, sizeof(double) * (size_t)n_values * (size_t)ix->n_ref, hipMemcpyHostToDevice, c->stream));
+            SGLCHK(sgl_knn_check_finite(c, who, "V", val.p, n_values, ix->n_ref, first.p));
+        }
+        if (labels) {
+            SGLCHK(lab.alloc((size_t)ix->n_ref));
+            HIPCHK(hipMemcpyAsync(lab.p, labels, sizeof(int32_t) * (size_t)ix->n_ref, hipMemcpyHostToDevice, c->stream));
+        }
+        return SGL_OK;
+    };
+    rc = ivf_drain(c, stage(), who);
+    if (rc != SGL_OK) return rc;   // the index keeps what it had
+    if (labels) { take(ix->labels, lab); ix->n_classes = n_classes; }
+    if (V) { take(ix->V, val); ix->n_values = n_values; }
+    return SGL_OK;   // lab / val release what they replaced
+}
+
+extern "C" int sgl_knn_index_map(sgl_ctx* c, const double* Q, int64_t n_query, int32_t n_neighbors, int32_t n_probe, int32_t weighting,
+                                 int32_t* idx_out, double* dist_out, int32_t* pred_out, double* best_out, double* scores_out,
+                                 double* values_out) {
+    const char* who = "sgl_knn_index_map";
+    if (c == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    KnnIndex* ix = index_of(c, who);
+    if (!ix) return SGL_ESTATE;
+    if (weighting < 0 || weighting > KNN_TRANSFER_WEIGHTING_MAX) {
+        sgl_set_error("%s: weighting = %d is outside [0, %d]", who, weighting, KNN_TRANSFER_WEIGHTING_MAX);
+        return SGL_EINVAL;
+    }
+    SGLCHK(index_search_args(who, ix, Q, n_query, n_neighbors, n_probe, 0));
+    const bool want_labels = pred_out || best_out || scores_out;
+    if (want_labels && !ix->labels.p) {
+        sgl_set_error("%s: pred_out, best_out or scores_out is asked for, but the index holds no labels (call sgl_knn_index_annotate)", who);
+        return SGL_ESTATE;
+    }
+    if (values_out && !ix->V.p) {
+        sgl_set_error("%s: values_out is asked for, but the index holds no values (call sgl_knn_index_annotate)", who);
+        return SGL_ESTATE;
+    }
+    int64_t short_queries = 0;
+    if (n_query > 0) {
+        const int32_t n_classes = ix->n_classes, n_values = ix->n_values;
+        const int64_t per_query = knn_transfer_query_bytes(ix->method == 1 ? n_probe : KNN_MAX_SEGMENTS, n_neighbors, scores_out ? n_classes : 0,
+                                                           values_out ? n_values : 0);
+        const int64_t batch = knn_transfer_batch(n_query, per_query, KNN_TRANSFER_SCRATCH_BYTES);
+        IvfBuffers B;
+        DevBuf<int32_t> pred;
+        DevBuf<double> best, scores, values;
+        auto body = [&]() -> int {
+            if (pred_out) SGLCHK(pred.alloc((size_t)batch));
+            if (best_out) SGLCHK(best.alloc((size_t)batch));
+            if (scores_out) SGLCHK(scores.alloc((size_t)n_classes * (size_t)batch));
+            if (values_out) SGLCHK(values.alloc((size_t)n_values * (size_t)batch));
+            // the transfer of a batch on the device: the neighbour lists do not travel to the host and back
+            const IvfAfterBatch after = [&](int64_t q0, int64_t nb, const int32_t* idx_dev, const double* dist_dev) -> int {
+                if (!want_labels && !values_out) return SGL_OK;
+                SGLCHK(sgl_knn_transfer_dev(c, idx_dev, dist_dev, n_neighbors, nb, want_labels ? ix->labels.p : nullptr, n_classes,
+                                            values_out ? ix->V.p : nullptr, n_values, weighting, pred.p, best.p, scores.p, values.p));
+                if (pred_out) HIPCHK(hipMemcpyAsync(pred_out + q0, pred.p, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+                if (best_out) HIPCHK(hipMemcpyAsync(best_out + q0, best.p, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+                if (scores_out)
+                    HIPCHK(hipMemcpyAsync(scores_out + q0 * n_classes, scores.p, sizeof(double) * (size_t)n_classes * (size_t)nb,
+                                          hipMemcpyDeviceToHost, c->stream));
+                if (values_out)
+                    HIPCHK(hipMemcpyAsync(values_out + q0 * n_values, values.p, sizeof(double) * (size_t)n_values * (size_t)nb,
+                                          hipMemcpyDeviceToHost, c->stream));
+                return SGL_OK;
+            };
+            return index_query(c, who, ix, B, Q, n_query, n_neighbors, n_probe, batch, batch, idx_out, dist_out, after, &short_queries);
+        };
+        const int rc = ivf_drain(c, body(), who);
+        if (rc != SGL_OK) return rc;
+    }
+    index_served(ix, n_query, short_queries);
+    return SGL_OK;
 }

@@ -257,6 +257,7 @@ struct sgl_ctx {
     // the last inverted-list search; sgl_knn_ivf_stage_ms: its stage times (timing on)
     int64_t knn_ivf_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     double knn_ivf_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    struct KnnIndex* knn_index = nullptr;   // the neighbour index kept on the device (kernels_knn_ivf.hip: sgl_knn_index_build); one per context
     int64_t markers_last[4] = {0, 0, 0, 0};   // sgl_markers_info: genes sorted in LDS, long genes, batches, the LDS cap of the last rank pass
     int64_t gsea_last[5] = {0, 0, 0, 0, 0};   // sgl_gsea_info: sets, distinct sizes, s_max, batches, batch size of the last enrichment call
 
@@ -297,6 +298,7 @@ int sgl_predict_mask_dev(sgl_ctx* c, const DevCSC& M, const int64_t* col_nnz, co
 int sgl_mse_test_enqueue(sgl_ctx* c, uint64_t seed, uint64_t inv_density);   // local loss sum -> c->scalars[1]
 #define SGL_MASK_MAX_K SGL_MAX_K   // the masked (ARD) path: MFMA Gram downdates up to k = 128, the generic VALU kernel above
 void sgl_team_detach(sgl_ctx* c);               // called by sgl_destroy
+void sgl_knn_index_free(sgl_ctx* c);            // called by sgl_destroy and sgl_knn_index_drop (kernels_knn_ivf.hip)
 
 // RAII-free phase timer helpers (driver side).
 int sgl_phase_begin(sgl_ctx* c, int phase, PhaseEvent* pe);
@@ -492,6 +494,16 @@ int sgl_gsea_null(sgl_ctx* c, const double* w, int64_t m, int64_t k, const int32
 int sgl_gsea_all(sgl_ctx* c, const double* w, int64_t m, int64_t k, const int64_t* set_ptr, const int32_t* set_genes, int64_t P, int score_type,
                  int64_t nperm, uint64_t seed, int64_t batch, double* es, double* nes, double* pval, double* padj, int64_t* n_ge, int64_t* n_le,
                  int64_t* n_side, int32_t* set_size, double* stage_ms);
+
+// label / value transfer along neighbour lists (kernels_knn_transfer.hip; include/singlet_hip.h, "Neighbour index and transfer").
+// The refusals of the arguments and of a label list under the caller's name (host arrays), and the transfer itself: every
+// pointer is the DEVICE's, idx / dist n_neighbors x nq, any output may be nullptr (labels nullptr: no label outputs; V nullptr:
+// no values); it only launches, in the "scale" phase.
+int sgl_knn_transfer_args(const char* who, int32_t weighting, int32_t n_neighbors, int64_t n_query, int64_t n_ref, bool has_labels,
+                          int32_t n_classes, bool has_values, int32_t n_values);
+int sgl_knn_transfer_labels_check(const char* who, const int32_t* labels, int64_t n_ref, int32_t n_classes);
+int sgl_knn_transfer_dev(sgl_ctx* c, const int32_t* idx, const double* dist, int K, int64_t nq, const int32_t* labels, int n_classes,
+                         const double* V, int n_values, int weighting, int32_t* pred, double* best, double* scores, double* values);
 
 // row-wise rasterisation (kernels_raster.hip): out (nb x ncol, column-major) = means of rows [b n, b n + n), nb >= 1
 int k_raster_sparse(hipStream_t s, const DevCSC& A, int64_t n, int64_t nb, double* out);

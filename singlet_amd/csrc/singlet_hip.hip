@@ -277,6 +277,7 @@ extern "C" int sgl_destroy(sgl_ctx* c) {
     (void)drain_timing(c);
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     sgl_team_detach(c);
+    sgl_knn_index_free(c);
     free_fit(c);
     free_matrix(c);
     dev_free(c->ws);
