@@ -706,6 +706,117 @@ SGL_API int sgl_c_markers(const double* Ax, const int32_t* Ai, const int32_t* Ap
  * the batches of the long path, out[3] the LDS cap (included non-zero entries). */
 SGL_API int sgl_markers_info(sgl_ctx* ctx, int64_t out[4]);
 
+/* Factor annotation: which factors of a fit represent which levels of a metadata column (cell types, batches, donors) --
+ * the reference's AnnotateNMF (R/AnnotateNMF.R:29-41, R/getDesigns.R, R/getModelMatrix.R, R/getModelFit.R,
+ * R/getModelResults.R): for a factor-typed column the means model ~ 0 + column over the cells whose value is not NA, fitted
+ * to every row of the embedding (or to every gene of the resident matrix, R/getModelFit.R:27), with the moderated t and the
+ * log-odds of Smyth (2004, "Linear models and empirical Bayes methods for assessing differential expression in microarray
+ * experiments").  The rules below are this library's own, stated in full; NO parity with limma is claimed (nothing here was
+ * compared with it).  tests/annotate_restatement.py restates them in numpy and scipy.  OUT OF SCOPE: limma's robust = TRUE
+ * (fitFDistRobustly) and trend = TRUE, arbitrary design matrices (designs =, ova = FALSE), a team form and an R shim entry.
+ *
+ * Labels.  labels[n], int32 in [-1, G), 1 <= G <= 1024: a cell labelled -1 is NA and left out of everything.  N = the
+ * included cells, group_n[g] = the size of group g.  For a means model the fit needs three families of moments only.
+ *
+ * Embedding moments (sgl_group_moments).  F is k x n column-major on the host, or NULL for the H of the current fit, read in
+ * place and untouched (k and n must then be the fit's); 1 <= k <= 1024.
+ *  - sum[f, g], k x G column-major: the sum of F[f, c] over the cells of group g in EXACTLY sgl_group_means' summation order
+ *    (the included cells of the group in ascending index, chunks of 256, slots, the binary tree, the chunk sums in chunk
+ *    order; the same kernels run).  An empty group has sum = +0.0.
+ *  - mean[f, g] = sum[f, g] / (double)group_n[g], one true division.
+ *  - rss[f], k values: the sum over the included cells j of d * d, d = F[f, j] - mean[f, labels[j]]: one subtraction and one
+ *    multiplication per cell, not contracted.  Order: inside a chunk as the group sums (slot s of S takes the positions
+ *    s, s + S, ..., then the tree); then the chunk sums of ALL groups are added in ascending chunk order from +0.0 -- group
+ *    0's chunks, then group 1's, and so on.  An empty group contributes nothing.
+ *  - to first order, with u = 2^-53: |sum error| <= n_g u sum_g |x| (and far below it: chunks and trees shorten the chains to
+ *    n_g / 256 + 256 / S + log2 S additions); |rss error| <= (N + 3) u rss + 2 sqrt(rss) sqrt(sum_j e_j^2), where e_j, the
+ *    error of the mean the cell is compared with, is at most (n_g + 1) u mean_g |x|.
+ *
+ * Gene moments (sgl_gene_group_moments), over t(A) of the resident matrix, m genes:
+ *  - nz[g, c] and sum[g, c], m x G column-major: exactly sgl_op_marker_sums with transform 0 (its code runs); a stored
+ *    x == 0.0 of either sign joins the gene's implicit zeros, as it does there.  mean[g, c] = sum / (double)group_n[c].
+ *  - rss[g] = E[g] + Z[g].  E[g]: the sum over the gene's stored non-zero entries in included cells of d * d,
+ *    d = x - mean[g, c], in the segment / block order of the marker sums for a single accumulator: the entries in stored order
+ *    are cut into segments of 8192, a segment into blocks of 64; a lane holds +0.0 for an excluded cell, a stored zero or a
+ *    place past the end; ONE butterfly (v += v[lane ^ 32], 16, 8, 4, 2, 1) per block; the block sums are added in ascending
+ *    order from +0.0 within a segment, the segment sums in ascending order from +0.0.  Skipping a block of zeros changes no bit.
+ *    Z[g] = the sum over the non-empty groups c ascending, from +0.0, of (double)(group_n[c] - nz[g, c]) * (mean * mean): formed
+ *    on the HOST inside the library.
+ *  - 64-bit entry indexing; no 2^21-cell limit (nothing is cubed).  After sgl_upload_dense the call works, over the CSC image.
+ *  - |E error| <= (8192 / 64 + 7 + segments + 2) u E + the mean term above; Z adds G + 2 roundings.
+ *
+ * Refusals and contract (both sides, and the whole calls below).  SGL_EINVAL, the whole list checked before anything is
+ * launched: NULL labels; n_groups outside [1, 1024]; k outside [1, 1024]; a label outside [-1, G), the message naming
+ * position and value; n outside [0, 2^31); F == NULL with k, n not the fit's.  SGL_ESTATE: on a team member, with an
+ * all-reduce hook, on a context that holds a shard (gene side; embedding side with F == NULL), F == NULL without a fit, the
+ * gene side without a resident matrix.  The context stays usable after every refusal.  Every call only reads: a fit continued
+ * afterwards gives the bits it would have given without the call.  The kernels' time counts in the "scale" phase.  Any
+ * output pointer may be NULL. */
+SGL_API int sgl_group_moments(sgl_ctx* ctx, const double* F, int32_t k, int64_t n, const int32_t* labels, int32_t n_groups,
+                              int64_t* group_n, double* sum, double* rss);
+/* The one-shot form: its own context on the current device; F must not be NULL. */
+SGL_API int sgl_c_group_moments(const double* F, int32_t k, int64_t n, const int32_t* labels, int32_t n_groups,
+                                int64_t* group_n, double* sum, double* rss);
+/* Keeps a copy of a host embedding F (k x n column-major) on the device for the annotation calls: while one is held,
+ * F == NULL in sgl_group_moments and sgl_annotate reads IT (k and n must be its; it goes before the H of a fit), so the labels of
+ * many metadata columns go against one upload.  F == NULL here drops it; a new call replaces it; sgl_destroy frees it.  The
+ * fit and the matrix are not touched.  SGL_EINVAL for k outside [1, 1024] or n outside [1, 2^31) (nothing is held then). */
+SGL_API int sgl_annotate_hold(sgl_ctx* ctx, const double* F, int32_t k, int64_t n);
+SGL_API int sgl_gene_group_moments(sgl_ctx* ctx, const int32_t* labels, int32_t n_groups, int64_t* group_n, int64_t* nz,
+                                   double* sum, double* rss);
+
+/* The fit and the moderated statistics from the moments; host code (singlet_amd/csrc/annotate_host.h), needs no context and no
+ * device.  sum is rows x G column-major (row fastest), rss has `rows` values.  Outputs, any may be NULL: coef, t, p_raw, p_adj,
+ * lods rows x G; amean, sigma, s2_post `rows`; stdev_unscaled, var_prior G; scalars[4] = df_residual, s2_prior, df_prior, df_total.
+ *
+ * Fit.  G' = the non-empty groups; df = N - G', the same for every row.  grand[r] = the sum[r, g] added over g ascending from
+ * +0.0; amean = grand / N; coef[r, g] = mean[r, g] - (center ? amean[r] : 0), one subtraction; stdev_unscaled[g] =
+ * 1 / sqrt((double)group_n[g]); s2[r] = rss[r] / df; sigma = sqrt(s2).  With scale: tss[r] = rss[r] + the n_g (mean - amean)^2
+ * added over the non-empty g ascending; sd = sqrt(tss / (N - 1)); coef /= sd; s2 /= sd * sd.  An empty group gives NaN in every
+ * per-(r, g) output (and in its stdev_unscaled and var_prior) and is not counted by Benjamini-Hochberg.  df <= 0: NaN everywhere.
+ *
+ * Prior (Smyth 2004, section 6.2).  The usable rows have a finite s2 >= 0.  x = max(s2, 1e-5 median(s2)), a median of 0
+ * replaced by 1; e = log x - digamma(df / 2) + log(df / 2); evar = the sample variance of e - trigamma(df / 2).  evar > 0:
+ * df_prior = 2 trigamma^-1(evar), s2_prior = exp(mean e + digamma(df_prior / 2) - log(df_prior / 2)); otherwise df_prior = +Inf
+ * and s2_prior = exp(mean e).  Fewer than two usable rows: df_prior = 0, s2_prior = NaN, no shrinkage.  s2_post = (df s2 +
+ * df_prior s2_prior) / (df + df_prior), s2_prior when df_prior is infinite, s2 when it is 0 (NaN for a row that is not usable).
+ * df_total = min(df + df_prior, usable rows * df).
+ *
+ * Moderated t and p.  t = coef / (stdev_unscaled * sqrt(s2_post)).  p_raw by tail: 0 (pos) P(T > t), 1 (neg) P(T < t), 2 (std)
+ * 2 P(T > |t|), T Student's t with df_total degrees of freedom (real-valued; +Inf: the normal distribution).
+ *
+ * Log-odds (the B statistic with `proportion`, and coefficient standard deviation limits 0.1 and 4).  Per group g, over
+ * the rows whose t is a number (rows' below is their count): the ntarget = ceil(proportion / 2 * rows') rows of largest |t|,
+ * ties by row index, ranked i = 1 .. ntarget; pp = max(ntarget / rows', proportion); p0 = 2 P(T > |t|); ptarget_i =
+ * ((i - 0.5) / rows' - (1 - pp) p0) / pp; where ptarget > p0, v0 = stdev_unscaled^2 ((|t| / q)^2 - 1) with q the upper
+ * ptarget / 2 quantile of T, otherwise v0 = 0; v0 is clamped to [0.01, 16]; var_prior[g] = the mean of the ntarget values.
+ * r = (stdev_unscaled^2 + var_prior) / stdev_unscaled^2; kernel = t^2 (1 - 1 / r) / 2 when df_prior > 1e6, else
+ * (1 + df_total) / 2 * log((t^2 + df_total) / (t^2 / r + df_total)); lods = log(proportion / (1 - proportion)) - log(r) / 2 + kernel.
+ *
+ * p_adj: Benjamini-Hochberg over all values of p_raw that are not NaN, jointly over the table (before any filter).
+ * The special functions are defined mathematically, not by an algorithm; tests/test_annotate_restatement.py holds them
+ * against scipy, p_raw RELATIVELY down to 1e-300.  SGL_EINVAL: rows < 0, n_groups outside [1, 1024], a NULL input, a negative
+ * group_n, proportion outside (0, 1), tail outside {0, 1, 2}. */
+SGL_API int sgl_annotate_stats(int64_t rows, int32_t n_groups, const int64_t* group_n, const double* sum, const double* rss,
+                               int center, int scale, double proportion, int tail, double* coef, double* stdev_unscaled,
+                               double* amean, double* sigma, double* s2_post, double* scalars, double* var_prior, double* t,
+                               double* p_raw, double* p_adj, double* lods);
+/* The whole call: sgl_group_moments, then sgl_annotate_stats over the k rows.  F == NULL: the resident H. */
+SGL_API int sgl_annotate(sgl_ctx* ctx, const double* F, int32_t k, int64_t n, const int32_t* labels, int32_t n_groups, int center,
+                         int scale, double proportion, int tail, int64_t* group_n, double* sum, double* rss, double* coef,
+                         double* stdev_unscaled, double* amean, double* sigma, double* s2_post, double* scalars,
+                         double* var_prior, double* t, double* p_raw, double* p_adj, double* lods);
+/* The one-shot form for a host F: its own context on the current device; the refusals come before a context is made. */
+SGL_API int sgl_c_annotate(const double* F, int32_t k, int64_t n, const int32_t* labels, int32_t n_groups, int center, int scale,
+                           double proportion, int tail, int64_t* group_n, double* sum, double* rss, double* coef,
+                           double* stdev_unscaled, double* amean, double* sigma, double* s2_post, double* scalars,
+                           double* var_prior, double* t, double* p_raw, double* p_adj, double* lods);
+/* The same over the genes of the resident matrix: sgl_gene_group_moments, then sgl_annotate_stats over the m rows. */
+SGL_API int sgl_annotate_genes(sgl_ctx* ctx, const int32_t* labels, int32_t n_groups, int center, int scale, double proportion,
+                               int tail, int64_t* group_n, int64_t* nz, double* sum, double* rss, double* coef,
+                               double* stdev_unscaled, double* amean, double* sigma, double* s2_post, double* scalars,
+                               double* var_prior, double* t, double* p_raw, double* p_adj, double* lods);
+
 /* Embedding neighbours: the EXACT n_neighbors nearest reference columns of every query column of a k x n embedding, by
  * brute force in FP64 -- the k-NN step of Seurat's FindNeighbors on the `nmf` reduction (its Jaccard step is sgl_c_snn), and
  * of label transfer after a projection.  The reference's package has no such function (it hands the embedding to Seurat);

@@ -112,6 +112,17 @@ SIGNATURES = {
     "sgl_markers_info": (C.c_int, [C.c_void_p, i64p]),
     "sgl_op_marker_sums": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int, i64p, i64p, f64p]),
     "sgl_op_marker_ranks": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int64, i64p, u64p]),
+    "sgl_group_moments": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64, i32p, C.c_int32, i64p, f64p, f64p]),
+    "sgl_c_group_moments": (C.c_int, [f64p, C.c_int32, C.c_int64, i32p, C.c_int32, i64p, f64p, f64p]),
+    "sgl_annotate_hold": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64]),
+    "sgl_gene_group_moments": (C.c_int, [C.c_void_p, i32p, C.c_int32, i64p, i64p, f64p, f64p]),
+    "sgl_annotate_stats": (C.c_int, [C.c_int64, C.c_int32, i64p, f64p, f64p, C.c_int, C.c_int, C.c_double, C.c_int] + [f64p] * 11),
+    "sgl_annotate": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64, i32p, C.c_int32, C.c_int, C.c_int, C.c_double, C.c_int, i64p, f64p,
+                               f64p] + [f64p] * 11),
+    "sgl_c_annotate": (C.c_int, [f64p, C.c_int32, C.c_int64, i32p, C.c_int32, C.c_int, C.c_int, C.c_double, C.c_int, i64p, f64p, f64p]
+                       + [f64p] * 11),
+    "sgl_annotate_genes": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int, C.c_int, C.c_double, C.c_int, i64p, i64p, f64p, f64p]
+                           + [f64p] * 11),
     "sgl_c_gsea": (C.c_int, [f64p, C.c_int32, C.c_int32, i64p, i32p, C.c_int32, C.c_int, C.c_int32, C.c_uint64, C.c_int32, f64p, f64p,
                              f64p, f64p, i64p, i64p, i64p, i32p, i64p, f64p]),
     "sgl_gsea_info": (C.c_int, [C.c_void_p, i64p]),

@@ -121,6 +121,64 @@ def markers_call(fn, nrow, labels, G, transform, pseudocount):
     return out
 
 
+ANNOTATE_TAILS = {"pos": 0, "neg": 1, "std": 2}
+ANNOTATE_ROW_GROUP = ("coefficients", "t", "p_raw", "p_adj", "lods")      # rows x G
+ANNOTATE_ROW = ("Amean", "sigma", "s2_post")                              # rows
+ANNOTATE_GROUP = ("stdev_unscaled", "var_prior")                          # G
+ANNOTATE_SCALARS = ("df_residual", "s2_prior", "df_prior", "df_total")
+
+
+def annotate_tail(tail):
+    if tail not in ANNOTATE_TAILS:
+        raise ValueError("Invalid tail selection. Choose 'pos','neg', or 'std'")
+    return ANNOTATE_TAILS[tail]
+
+
+def annotate_call(fn, rows, G, center, scale, proportion, tail, moments=None, with_nz=False):
+    """Shared by annotate_stats, Context.annotate, Context.annotate_genes and api.c_annotate: fn(center, scale, proportion, tail,
+    [group_n, (nz,) sum, rss,] the eleven outputs) is the library call.  moments: (group_n, sum rows x G, rss) when the call
+    takes them as inputs (sgl_annotate_stats), else they are outputs.  Returns the dict of the arrays, the per-(row, group)
+    ones as rows x G, with the moments among them."""
+    r, Gs = max(int(rows), 1), max(min(int(G), 1024), 1)   # outside [1, 1024] the library refuses before it writes
+    tl = annotate_tail(tail)
+    rg = {k: np.full((Gs, r), np.nan) for k in ANNOTATE_ROW_GROUP}
+    rw = {k: np.full(r, np.nan) for k in ANNOTATE_ROW}
+    gr = {k: np.full(Gs, np.nan) for k in ANNOTATE_GROUP}
+    sc = np.full(4, np.nan)
+    outs = [ptr(rg["coefficients"], f64p), ptr(gr["stdev_unscaled"], f64p), ptr(rw["Amean"], f64p), ptr(rw["sigma"], f64p),
+            ptr(rw["s2_post"], f64p), ptr(sc, f64p), ptr(gr["var_prior"], f64p), ptr(rg["t"], f64p), ptr(rg["p_raw"], f64p),
+            ptr(rg["p_adj"], f64p), ptr(rg["lods"], f64p)]
+    nz = None
+    if moments is None:
+        group_n, s, rss = np.zeros(Gs, dtype=np.int64), np.zeros((Gs, r)), np.zeros(r)
+        mom = [ptr(group_n, i64p)]
+        if with_nz:
+            nz = np.zeros((Gs, r), dtype=np.int64)
+            mom.append(ptr(nz, i64p))
+        mom += [ptr(s, f64p), ptr(rss, f64p)]
+        check(fn(int(bool(center)), int(bool(scale)), float(proportion), tl, *mom, *outs))
+    else:
+        group_n = np.ascontiguousarray(moments[0], dtype=np.int64)
+        given = np.asarray(moments[1], dtype=np.float64)
+        rss = np.ascontiguousarray(moments[2], dtype=np.float64) if rows else np.zeros(r)
+        if group_n.shape != (int(G),) or given.shape != (int(rows), int(G)) or (rows and rss.shape != (int(rows),)):
+            raise ValueError("group_n must hold G counts, sum rows x G values and rss one value per row")
+        s = np.ascontiguousarray(given.T) if rows else np.zeros((max(int(G), 1), r))   # (G outside [1, 1024]: the library refuses)
+        check(fn(ptr(group_n, i64p), ptr(s, f64p), ptr(rss, f64p), int(bool(center)), int(bool(scale)), float(proportion), tl, *outs))
+    n = int(rows)
+    out = {"group_n": group_n, "sum": s[:, :n].T, "rss": rss[:n], "centered": bool(center), "scaled": bool(scale),
+           "proportion": float(proportion), "tail": tail}
+    if nz is not None:
+        out["nz"] = nz[:, :n].T
+    for k, a in rg.items():
+        out[k] = a[:, :n].T
+    for k, a in rw.items():
+        out[k] = a[:n]
+    out.update(gr)
+    out.update(dict(zip(ANNOTATE_SCALARS, (float(v) for v in sc))))
+    return out
+
+
 GSEA_SCORE_TYPES = {"pos": 0, "neg": 1, "std": 2, 0: 0, 1: 1, 2: 2}
 
 

@@ -45,7 +45,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from ._marshal import ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, knn_weighting, label_list, markers_call
+from ._marshal import ArdOutputs, NmfOutputs, annotate_call, annotate_tail, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, knn_weighting, label_list, markers_call
 from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
@@ -2117,3 +2117,207 @@ def run_gsea(w, pathways, gene_names, min_size=10, max_size=500, dims=None, scor
         out["pval"], out["padj"] = -np.log10(out["pval"]), -np.log10(out["padj"])
     out.update(pathways=names, dims=dims, significant=sig, genes=rows)
     return out
+
+
+# ---------------------------------------------------------------------------
+# Factor annotation (R/AnnotateNMF.R, R/checkColumns.R, R/getDesigns.R, R/getModelMatrix.R, R/getModelFit.R, R/getModelResults.R)
+# ---------------------------------------------------------------------------
+def _meta_columns(meta):
+    """{name: column} of a dict of arrays or a pandas DataFrame (recognised by its interface; pandas is not imported here)."""
+    if isinstance(meta, dict):
+        return dict(meta)
+    if hasattr(meta, "columns") and hasattr(meta, "__getitem__"):
+        return {c: meta[c] for c in meta.columns}
+    raise ValueError("meta must be a dict of arrays or a pandas DataFrame, one value per cell in every column")
+
+
+def _column_codes(col):
+    """(int32 codes with -1 for a missing value, the level names) of one metadata column, or None when the column is not
+    factor-like: a pandas Categorical (its categories, unused ones included, as nlevels counts them), strings / objects, booleans
+    or integers -- levels: the sorted distinct values that are not missing (None, NaN, pandas NA), as as.factor orders them."""
+    cat = getattr(col, "cat", None)
+    if cat is None and hasattr(col, "categories") and hasattr(col, "codes"):
+        cat = col
+    if cat is not None:
+        return np.asarray(cat.codes, dtype=np.int32), [c for c in cat.categories]
+    a = np.asarray(col)
+    if a.ndim != 1:
+        return None
+    if a.dtype.kind in "iub":
+        levels, codes = np.unique(a, return_inverse=True)
+        return codes.astype(np.int32), levels.tolist()
+    if a.dtype.kind in "US":
+        levels, codes = np.unique(a, return_inverse=True)
+        return codes.astype(np.int32), levels.tolist()
+    if a.dtype.kind == "O":
+        missing = np.array([v is None or (isinstance(v, float) and v != v) or type(v).__name__ in ("NAType", "NaTType") for v in a], dtype=bool)
+        vals = a[~missing]
+        if any(isinstance(v, float) for v in vals):
+            return None   # a numeric column that merely arrived as objects
+        try:
+            levels = sorted(set(vals.tolist()))
+        except TypeError:
+            return None
+        index = {v: q for q, v in enumerate(levels)}
+        codes = np.full(a.shape[0], -1, dtype=np.int32)
+        codes[~missing] = [index[v] for v in vals.tolist()]
+        return codes, levels
+    return None   # floating point and everything else: not a factor
+
+
+def check_columns(meta, columns=None, max_levels=200):
+    """R/checkColumns.R: the names of the metadata columns an annotation can use -- present in meta, factor-like (categorical,
+    string or integer-coded) and with 2 to max_levels levels.  The message about the discarded ones appears only when
+    `columns` was given (l.10-19)."""
+    cols = _meta_columns(meta)
+    verbose = columns is not None
+    if columns is None:
+        columns = list(cols)
+    elif isinstance(columns, str):
+        columns = [columns]
+    keep = []
+    for name in columns:
+        if name not in cols:
+            continue
+        coded = _column_codes(cols[name])
+        if coded is None or len(coded[1]) < 2 or len(coded[1]) > max_levels:
+            continue
+        keep.append(name)
+    discard = [c for c in columns if c not in keep]
+    if verbose and discard:
+        print("Some columns are not factors, or have only one level, or have more than max.levels levels.")
+        print("Skipping `" + "`, `".join(str(c) for c in discard) + "`.")
+    return keep
+
+
+def get_designs(meta, columns=None, max_levels=200):
+    """R/getDesigns.R + R/getModelMatrix.R in grouped form: {column: (labels, levels)} for every column check_columns keeps --
+    labels int32, one per cell, the 0-based level of the cell or -1 where the value is missing (model.matrix drops those
+    rows); levels the level names in code order.  A label list is to model.matrix(~ 0 + column) what set_links_grouped's
+    group list is to a link matrix: column g of the design is labels == g."""
+    cols = _meta_columns(meta)
+    return {name: _column_codes(cols[name]) for name in check_columns(meta, columns, max_levels)}
+
+
+def c_group_moments(F, labels, n_groups=None):
+    """The one-shot form of Context.group_moments (sgl_c_group_moments): (group_n, sum k x G, rss k) of the means model over the
+    columns of F (k x n on the host) under the labels, in a context of its own."""
+    buf = colmajor(F, "F must be a k x n matrix")
+    n, k = buf.shape
+    g, G = label_list(labels, n, n_groups)
+    kk, Gs = max(int(k), 1), max(min(G, 1024), 1)   # outside [1, 1024] the library refuses before it writes
+    group_n, s, rss = np.zeros(Gs, dtype=np.int64), np.zeros((Gs, kk)), np.zeros(kk)
+    check(_lib.load().sgl_c_group_moments(ptr(buf, f64p), int(k), int(n), ptr(g, i32p), G, ptr(group_n, _lib.i64p), ptr(s, f64p),
+                                          ptr(rss, f64p)))
+    return group_n, s[:, :k].T, rss[:k]
+
+
+def annotate_stats(group_n, sums, rss, center=True, scale=False, proportion=0.01, tail="pos"):
+    """The fit and the moderated statistics of a means model from its group moments (sgl_annotate_stats; host code of the
+    library, no device needed): group_n G counts, sums rows x G, rss one value per row.  Returns the dict of the arrays:
+    coefficients, t, p_raw, p_adj, lods (rows x G); Amean, sigma, s2_post (rows); stdev_unscaled, var_prior (G);
+    df_residual, s2_prior, df_prior, df_total; the moments themselves."""
+    s = np.asarray(sums, dtype=np.float64)
+    if s.ndim != 2:
+        raise ValueError("sums must be a rows x G matrix")
+    L = _lib.load()
+    return annotate_call(lambda *a: L.sgl_annotate_stats(s.shape[0], s.shape[1], *a), s.shape[0], s.shape[1], center, scale, proportion,
+                         tail, moments=(group_n, s, rss))
+
+
+def c_annotate(F, labels, n_groups=None, center=True, scale=False, proportion=0.01, tail="pos"):
+    """The one-shot form of Context.annotate (sgl_c_annotate): F k x n on the host, in a context of its own."""
+    buf = colmajor(F, "F must be a k x n matrix")
+    n, k = buf.shape
+    g, G = label_list(labels, n, n_groups)
+    L = _lib.load()
+    return annotate_call(lambda *a: L.sgl_c_annotate(ptr(buf, f64p), int(k), int(n), ptr(g, i32p), G, *a), k, G, center, scale,
+                         proportion, tail)
+
+
+def get_model_fit(labels, n_levels, obj, center=True, scale=False, genes=False):
+    """R/getModelFit.R for the means model of one label list (get_designs): eBayes(lmFit(obj, design), proportion = 0.01) under
+    the rules of include/singlet_hip.h ("Factor annotation"; not limma's robust = TRUE).  obj: a k x n array (transposed when
+    it arrives n x k, l.36), a model dict (its "h"), a Context (its held embedding or the H of its fit; with genes = True the
+    genes of its resident matrix), or a sparse matrix / native(...) object for the fit of every gene (l.27).  Returns a dict
+    with limma's field names where they exist -- coefficients, stdev_unscaled, sigma, df_residual, Amean, s2_prior, df_prior,
+    s2_post, df_total, t, p_value (two-sided), lods, var_prior, centered -- and the group moments the statistics came from."""
+    from .context import Context
+    labels = np.asarray(labels)
+    kw = dict(center=center, scale=scale, proportion=0.01, tail="std")
+    if isinstance(obj, Context):
+        fit = obj.annotate_genes(labels, n_levels, **kw) if genes else obj.annotate(labels, n_levels, None, **kw)
+    elif isinstance(obj, NativeMatrix):
+        fit = _on_native(obj, lambda ctx, fits: ctx.annotate_genes(labels, n_levels, **kw))
+    elif isinstance(obj, dgCMatrix) or hasattr(obj, "tocsc"):
+        with Context(0) as ctx:
+            ctx.upload(as_dgCMatrix(obj))
+            fit = ctx.annotate_genes(labels, n_levels, **kw)
+    else:
+        F = np.asarray(obj["h"] if isinstance(obj, dict) else obj, dtype=np.float64)
+        if F.ndim != 2:
+            raise ValueError("obj must be a k x n matrix, a model, a Context or a sparse matrix")
+        if F.shape[1] < labels.shape[0]:
+            F = F.T   # if (ncol(dat) < nrow(design)) dat <- t(dat)
+        fit = c_annotate(F, labels, n_levels, **kw)
+    fit["p_value"] = fit.pop("p_raw")
+    fit["_p_adj_std"] = fit.pop("p_adj")   # the two-sided table's adjusted p: get_model_results(tail = "std") reads it
+    del fit["tail"]
+    return fit
+
+
+def get_model_results(fit, noneg=True, noint=True, tail="pos", names=None):
+    """R/getModelResults.R:23-55: the long table (group, factor, fc, p) of a fit -- fc the log-odds, p the one-sided moderated p
+    of `tail` ("pos", "neg" or "std": two-sided) adjusted by Benjamini-Hochberg over the WHOLE table before any filter; rows
+    with lods <= 0 are dropped when noneg, a group named "(Intercept)" when noint (a means model has none).  Rows run over the
+    groups, the factors ascending within a group (melt's order).  names: (group names, factor names), either may be None;
+    they are added as "group_names" and "factor_names".  Returns a dict of equally long arrays."""
+    annotate_tail(tail)   # "Invalid tail selection. Choose 'pos','neg', or 'std'"
+    if tail == "std" and "_p_adj_std" in fit:   # the fit holds the two-sided p already; a one-sided tail is formed from the moments
+        lods, p = fit["lods"], fit["_p_adj_std"]
+    else:
+        st = annotate_stats(fit["group_n"], fit["sum"], fit["rss"], fit["centered"], fit["scaled"], fit["proportion"], tail)
+        lods, p = st["lods"], st["p_adj"]
+    rows, G = lods.shape
+    group, factor = np.repeat(np.arange(G), rows), np.tile(np.arange(rows), G)
+    keep = np.ones(rows * G, dtype=bool)
+    fc, pv = lods.T.reshape(-1), p.T.reshape(-1)
+    if noneg:
+        with np.errstate(invalid="ignore"):
+            keep &= fc > 0
+    gnames, fnames = names if names is not None else (None, None)
+    if noint and gnames is not None:
+        keep &= np.array([gnames[g] != "(Intercept)" for g in group], dtype=bool)
+    if not keep.any():
+        print("No associations after filtering.")
+    out = {"group": group[keep].astype(np.int32), "factor": factor[keep].astype(np.int32), "fc": fc[keep], "p": pv[keep]}
+    if gnames is not None:
+        out["group_names"] = [gnames[g] for g in out["group"]]
+    if fnames is not None:
+        out["factor_names"] = [fnames[f] for f in out["factor"]]
+    return out
+
+
+def AnnotateNMF(model_or_context, meta, columns=None, center=True, scale=False, max_levels=200, tail="pos"):
+    """R/AnnotateNMF.R:29-41 without the object around it: {column: table}, the content of misc$annotations -- for every usable
+    metadata column (check_columns) the table get_model_results gives for the means-model fit of the factors against it.
+    model_or_context: a model dict (its "h", k x n, uploaded ONCE and held on the device for all columns) or a Context (its
+    held embedding or the H of its fit, read in place)."""
+    from .context import Context
+    annotate_tail(tail)
+    designs = get_designs(meta, columns, max_levels)
+
+    def run(ctx, fnames):
+        out = {}
+        for name, (labels, levels) in designs.items():
+            fit = get_model_fit(labels, len(levels), ctx, center, scale)
+            out[name] = get_model_results(fit, tail=tail, names=(levels, fnames))
+        return out
+
+    if isinstance(model_or_context, Context):
+        return run(model_or_context, None)
+    h = np.asarray(model_or_context["h"], dtype=np.float64)
+    fnames = model_or_context.get("factor_names") if isinstance(model_or_context, dict) else None
+    with Context(0) as ctx:
+        ctx.hold_embedding(h)
+        return run(ctx, fnames)

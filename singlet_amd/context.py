@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
-from ._marshal import (KNN_INDEX_FIELDS, MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call,
+from ._marshal import (KNN_INDEX_FIELDS, MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, annotate_call, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call,
                        knn_ivf_shape, knn_lists_in, knn_method, knn_metric, knn_weighting, label_list, markers_call, transfer_call)
 from .sparse import as_dgCMatrix
 
@@ -477,6 +477,64 @@ class Context(_Handle):
             Fp = ptr(buf, f64p)
         g = _group_list(group, n, "group")
         return _group_means_call(lambda *o: self._L.sgl_group_means(self._h, Fp, int(k), int(g.shape[0]), *o), g, n_groups, k)
+
+    def _embedding_in(self, F):
+        """(the column-major image kept alive or None, its pointer or None, k, n) of the embedding argument of the annotation
+        calls; F = None: the held embedding, else the H of the current fit."""
+        if F is None:
+            held = getattr(self, "_held_embedding", None)
+            if held is not None:
+                return None, None, held[0], held[1]
+            _, n, _ = self.dims()
+            return None, None, self.k, (n if self.k else None)   # no fit: the library refuses (SGL_ESTATE) before it reads the list
+        buf = colmajor(F, "F must be a k x n matrix")
+        return buf, ptr(buf, f64p), buf.shape[1], buf.shape[0]
+
+    def hold_embedding(self, F):
+        """Keeps a device copy of F (k x n) for the annotation calls, which read it when their F is None (sgl_annotate_hold);
+        F = None drops it."""
+        if F is None:
+            check(self._L.sgl_annotate_hold(self._h, None, 0, 0))
+            self._held_embedding = None
+            return
+        buf = colmajor(F, "F must be a k x n matrix")
+        self._held_embedding = None
+        check(self._L.sgl_annotate_hold(self._h, ptr(buf, f64p), buf.shape[1], buf.shape[0]))
+        self._held_embedding = (buf.shape[1], buf.shape[0])
+
+    def group_moments(self, labels, n_groups=None, F=None):
+        """(group_n, sum k x G, rss k) of a means model over the columns of F (k x n, R's orientation) under the labels (one in
+        [-1, G) per cell, -1: left out) (sgl_group_moments); F = None: of the H of the current fit, read where it is."""
+        _buf, Fp, k, n = self._embedding_in(F)
+        g, G = label_list(labels, n, n_groups)
+        kk, Gs = max(int(k), 1), max(min(G, 1024), 1)
+        group_n, s, rss = np.zeros(Gs, dtype=np.int64), np.zeros((Gs, kk)), np.zeros(kk)
+        check(self._L.sgl_group_moments(self._h, Fp, int(k), int(g.shape[0]), ptr(g, i32p), G, ptr(group_n, i64p), ptr(s, f64p), ptr(rss, f64p)))
+        return group_n, s[:, :k].T, rss[:k]
+
+    def gene_group_moments(self, labels, n_groups=None):
+        """(group_n, nz m x G, sum m x G, rss m) of the same model over the genes of the resident matrix (sgl_gene_group_moments)."""
+        nr, nc, _ = self.dims()
+        g, G = label_list(labels, nc or None, n_groups)   # (no matrix: the library refuses)
+        m, Gs = max(nr, 1), max(min(G, 1024), 1)
+        group_n, nz, s, rss = np.zeros(Gs, dtype=np.int64), np.zeros((Gs, m), dtype=np.int64), np.zeros((Gs, m)), np.zeros(m)
+        check(self._L.sgl_gene_group_moments(self._h, ptr(g, i32p), G, ptr(group_n, i64p), ptr(nz, i64p), ptr(s, f64p), ptr(rss, f64p)))
+        return group_n, nz[:, :nr].T, s[:, :nr].T, rss[:nr]
+
+    def annotate(self, labels, n_groups=None, F=None, center=True, scale=False, proportion=0.01, tail="pos"):
+        """The means-model fit of every row of F (k x n; None: the resident H) against the labels with the moderated statistics
+        (sgl_annotate; the rules: include/singlet_hip.h, "Factor annotation"): the dict of annotate_stats."""
+        _buf, Fp, k, n = self._embedding_in(F)
+        g, G = label_list(labels, n, n_groups)
+        return annotate_call(lambda *a: self._L.sgl_annotate(self._h, Fp, int(k), int(g.shape[0]), ptr(g, i32p), G, *a), k, G, center, scale,
+                             proportion, tail)
+
+    def annotate_genes(self, labels, n_groups=None, center=True, scale=False, proportion=0.01, tail="pos"):
+        """The same fit of every gene of the resident matrix (sgl_annotate_genes); the dict also holds "nz"."""
+        nr, nc, _ = self.dims()
+        g, G = label_list(labels, nc or None, n_groups)   # (no matrix: the library refuses)
+        return annotate_call(lambda *a: self._L.sgl_annotate_genes(self._h, ptr(g, i32p), G, *a), nr, G, center, scale, proportion, tail,
+                             with_nz=True)
 
     def variable_features(self, nfeatures=2000, span=0.3, vmax=None, expected_var=None):
         """Variable features of the resident counts (sgl_variable_features; Seurat's vst selection under this library's

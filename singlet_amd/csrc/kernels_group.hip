@@ -89,62 +89,84 @@ int sgl_group_ids_check(const char* who, const char* name, const int32_t* group,
     return SGL_OK;
 }
 
-int sgl_group_sums_dev(sgl_ctx* c, const double* F, int k, int64_t n, const int32_t* group, int32_t n_groups, bool divide,
-                       double* out, int64_t* counts) {
+int sgl_group_plan(sgl_ctx* c, GroupPlan& P, int64_t n, const int32_t* group, int32_t n_groups) {
     if (n > INT32_MAX) { sgl_set_error("sgl_group_sums: %lld cells: the cell list holds 32-bit indices", (long long)n); return SGL_EINVAL; }
-    // stable counting sort of the cells by group, and the chunk boundaries
-    std::vector<int64_t> goff((size_t)n_groups + 1, 0), gfirst((size_t)n_groups + 1, 0);
-    for (int64_t q = 0; q < n; ++q) ++goff[(size_t)group[q] + 1];
+    // stable counting sort of the cells by group (a negative id leaves its cell out), and the chunk boundaries
+    std::vector<int64_t>&goff = P.h_goff, &gfirst = P.h_gfirst, &cbeg = P.h_cbeg;
+    std::vector<int32_t>&perm = P.h_perm, &cgroup = P.h_cgroup;
+    goff.assign((size_t)n_groups + 1, 0);
+    gfirst.assign((size_t)n_groups + 1, 0);
+    for (int64_t q = 0; q < n; ++q)
+        if (group[q] >= 0) ++goff[(size_t)group[q] + 1];
+    P.counts.assign((size_t)n_groups, 0);
     for (int32_t g = 0; g < n_groups; ++g) {
-        counts[g] = goff[(size_t)g + 1];
+        P.counts[g] = goff[(size_t)g + 1];
         gfirst[(size_t)g + 1] = gfirst[g] + (goff[(size_t)g + 1] + SGL_GROUP_CHUNK - 1) / SGL_GROUP_CHUNK;
         goff[(size_t)g + 1] += goff[g];
     }
-    const int64_t nchunks = gfirst[n_groups];
-    std::vector<int32_t> perm((size_t)std::max<int64_t>(n, 1));
+    const int64_t nchunks = gfirst[n_groups], n_in = goff[n_groups];
+    P.nchunks = nchunks;
+    P.n_in = n_in;
+    perm.assign((size_t)std::max<int64_t>(n_in, 1), 0);
     {
         std::vector<int64_t> at(goff.begin(), goff.end() - 1);
-        for (int64_t q = 0; q < n; ++q) perm[(size_t)at[group[q]]++] = (int32_t)q;
+        for (int64_t q = 0; q < n; ++q)
+            if (group[q] >= 0) perm[(size_t)at[group[q]]++] = (int32_t)q;
     }
-    std::vector<int64_t> cbeg((size_t)nchunks + 1, 0);
+    cbeg.assign((size_t)nchunks + 1, 0);
+    cgroup.assign((size_t)std::max<int64_t>(nchunks, 1), 0);
     for (int32_t g = 0; g < n_groups; ++g)
-        for (int64_t ch = gfirst[g]; ch < gfirst[(size_t)g + 1]; ++ch) cbeg[(size_t)ch] = goff[g] + (ch - gfirst[g]) * SGL_GROUP_CHUNK;
-    cbeg[(size_t)nchunks] = n;
+        for (int64_t ch = gfirst[g]; ch < gfirst[(size_t)g + 1]; ++ch) {
+            cbeg[(size_t)ch] = goff[g] + (ch - gfirst[g]) * SGL_GROUP_CHUNK;
+            cgroup[(size_t)ch] = g;
+        }
+    cbeg[(size_t)nchunks] = n_in;
     // (chunk ch ends where chunk ch + 1 begins: the next chunk of its group, or the first cell of the next non-empty group)
 
-    DevBuf<int32_t> dperm;
-    DevBuf<int64_t> dcbeg, dgfirst, dgoff;
-    DevBuf<double> dpart, dout;
-    SGLCHK(dperm.alloc(perm.size()));
-    SGLCHK(dcbeg.alloc(cbeg.size()));
-    SGLCHK(dgfirst.alloc(gfirst.size()));
-    SGLCHK(dgoff.alloc(goff.size()));
-    SGLCHK(dpart.alloc((size_t)std::max<int64_t>(nchunks, 1) * (size_t)k));
-    SGLCHK(dout.alloc((size_t)k * (size_t)n_groups));
-    HIPCHK(hipMemcpyAsync(dperm.p, perm.data(), sizeof(int32_t) * perm.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dcbeg.p, cbeg.data(), sizeof(int64_t) * cbeg.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dgfirst.p, gfirst.data(), sizeof(int64_t) * gfirst.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dgoff.p, goff.data(), sizeof(int64_t) * goff.size(), hipMemcpyHostToDevice, c->stream));
+    SGLCHK(P.perm.alloc(perm.size()));
+    SGLCHK(P.cgroup.alloc(cgroup.size()));
+    SGLCHK(P.cbeg.alloc(cbeg.size()));
+    SGLCHK(P.gfirst.alloc(gfirst.size()));
+    SGLCHK(P.goff.alloc(goff.size()));
+    // the uploads are asynchronous and read the plan's own host vectors: the caller synchronises before the plan goes
+    HIPCHK(hipMemcpyAsync(P.perm.p, perm.data(), sizeof(int32_t) * perm.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(P.cgroup.p, cgroup.data(), sizeof(int32_t) * cgroup.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(P.cbeg.p, cbeg.data(), sizeof(int64_t) * cbeg.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(P.gfirst.p, gfirst.data(), sizeof(int64_t) * gfirst.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(P.goff.p, goff.data(), sizeof(int64_t) * goff.size(), hipMemcpyHostToDevice, c->stream));
+    return SGL_OK;
+}
+
+int sgl_group_sums_on(sgl_ctx* c, GroupPlan& P, const double* F, int k, int32_t n_groups, bool divide, double* part, double* out) {
     int fl_shift = 0;
     while ((1 << fl_shift) < k && fl_shift < 6) ++fl_shift;
-    int rc = SGL_OK;
-    {
-        Phase ph(c, SGL_PH_SCALE);   // "row sums, scale, cor, copies": where scripts/linked_grouped_rate.py reads the kernels' time
-        if (nchunks > 0) {
-            group_chunk_kernel<<<dim3((unsigned)nchunks), dim3(GROUP_THREADS), 0, c->stream>>>(F, k, dperm.p, dcbeg.p, fl_shift, dpart.p);
-            if (hipGetLastError() != hipSuccess) rc = SGL_EHIP;
-        }
-        if (rc == SGL_OK) {
-            const int64_t total = (int64_t)k * n_groups;
-            group_finish_kernel<<<dim3((unsigned)((total + GROUP_THREADS - 1) / GROUP_THREADS)), dim3(GROUP_THREADS), 0, c->stream>>>(
-                dpart.p, k, n_groups, dgfirst.p, dgoff.p, divide ? 1 : 0, dout.p);
-            if (hipGetLastError() != hipSuccess) rc = SGL_EHIP;
-        }
+    Phase ph(c, SGL_PH_SCALE);   // "row sums, scale, cor, copies": where scripts/linked_grouped_rate.py reads the kernels' time
+    if (P.nchunks > 0) {
+        group_chunk_kernel<<<dim3((unsigned)P.nchunks), dim3(GROUP_THREADS), 0, c->stream>>>(F, k, P.perm.p, P.cbeg.p, fl_shift, part);
+        if (hipGetLastError() != hipSuccess) return SGL_EHIP;
     }
+    const int64_t total = (int64_t)k * n_groups;
+    group_finish_kernel<<<dim3((unsigned)((total + GROUP_THREADS - 1) / GROUP_THREADS)), dim3(GROUP_THREADS), 0, c->stream>>>(
+        part, k, n_groups, P.gfirst.p, P.goff.p, divide ? 1 : 0, out);
+    if (hipGetLastError() != hipSuccess) return SGL_EHIP;
+    return SGL_OK;
+}
+
+int sgl_group_sums_dev(sgl_ctx* c, const double* F, int k, int64_t n, const int32_t* group, int32_t n_groups, bool divide,
+                       double* out, int64_t* counts) {
+    GroupPlan P;   // (outlives the synchronisation below on every path: its uploads and the kernels read it)
+    DevBuf<double> dpart, dout;
+    int rc = sgl_group_plan(c, P, n, group, n_groups);
+    if (rc == SGL_EINVAL) return rc;   // refused before anything was queued
+    if (rc == SGL_OK) std::copy(P.counts.begin(), P.counts.end(), counts);
+    if (rc == SGL_OK) rc = dpart.alloc((size_t)std::max<int64_t>(P.nchunks, 1) * (size_t)k);
+    if (rc == SGL_OK) rc = dout.alloc((size_t)k * (size_t)n_groups);
+    if (rc == SGL_OK) rc = sgl_group_sums_on(c, P, F, k, n_groups, divide, dpart.p, dout.p);
     if (rc == SGL_OK && hipMemcpyAsync(out, dout.p, sizeof(double) * (size_t)k * (size_t)n_groups, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
         rc = SGL_EHIP;
     // the host vectors and the device buffers above are released on return: nothing may still be in flight then
     const hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == SGL_ENOMEM) return rc;
     if (rc != SGL_OK || e != hipSuccess) { sgl_set_error("sgl_group_sums: HIP call failed: %s", hipGetErrorString(e)); return SGL_EHIP; }
     return SGL_OK;
 }

@@ -259,6 +259,9 @@ struct sgl_ctx {
     double knn_ivf_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     struct KnnIndex* knn_index = nullptr;   // the neighbour index kept on the device (kernels_knn_ivf.hip: sgl_knn_index_build); one per context
     int64_t markers_last[4] = {0, 0, 0, 0};   // sgl_markers_info: genes sorted in LDS, long genes, batches, the LDS cap of the last rank pass
+    double* ann_F = nullptr;   // sgl_annotate_hold: a k x n embedding kept for the annotation calls (F == NULL reads it)
+    int32_t ann_k = 0;
+    int64_t ann_n = 0;
     int64_t gsea_last[5] = {0, 0, 0, 0, 0};   // sgl_gsea_info: sets, distinct sizes, s_max, batches, batch size of the last enrichment call
 
     sgl_allreduce_fn allreduce = nullptr;
@@ -448,6 +451,20 @@ int k_link_mul_grouped(hipStream_t s, double* B, const double* T, const int32_t*
 #define SGL_GROUP_CHUNK 256   // cells per chunk of a group's cell list
 int sgl_group_sums_dev(sgl_ctx* c, const double* F, int k, int64_t n, const int32_t* group, int32_t n_groups, bool divide,
                        double* out, int64_t* counts);
+// its two halves, for a caller that makes a second pass over the same cell lists (kernels_annotate.hip): the plan -- the
+// cells by group in ascending index (a NEGATIVE id leaves its cell out), cut into chunks -- and the two kernels, launched in
+// the "scale" phase on device arrays (part: nchunks x k, out: k x n_groups); NEITHER half synchronises: as before the split,
+// one call queues the uploads, the kernels and the copy back, and waits once at its end
+struct GroupPlan {
+    DevBuf<int32_t> perm, cgroup;       // the included cells by group; the group of every chunk
+    DevBuf<int64_t> cbeg, gfirst, goff; // chunk -> first position; group -> first chunk; group -> first position
+    std::vector<int64_t> counts;        // host: cells per group
+    std::vector<int32_t> h_perm, h_cgroup;          // the host images the asynchronous uploads read: they live as long as the
+    std::vector<int64_t> h_cbeg, h_gfirst, h_goff;  // plan, and the caller synchronises the stream before the plan goes
+    int64_t nchunks = 0, n_in = 0;
+};
+int sgl_group_plan(sgl_ctx* c, GroupPlan& P, int64_t n, const int32_t* group, int32_t n_groups);
+int sgl_group_sums_on(sgl_ctx* c, GroupPlan& P, const double* F, int k, int32_t n_groups, bool divide, double* part, double* out);
 // SGL_EINVAL naming the list, the position and the value of the first id outside [0, n_groups)
 int sgl_group_ids_check(const char* who, const char* name, const int32_t* group, int64_t n, int32_t n_groups);
 
@@ -477,6 +494,15 @@ int sgl_markers_core(sgl_ctx* c, const int32_t* labels, int32_t G, int transform
 // both passes and the derived statistics (markers_host.h)
 int sgl_markers_all(sgl_ctx* c, const int32_t* labels, int32_t G, int transform, double pseudocount, int64_t* group_n, int64_t* pos,
                     double* sum, int64_t* rank2, uint64_t* tie, double* pct_in, double* pct_out, double* log2fc, double* z, double* p);
+
+// factor annotation (kernels_annotate.hip; include/singlet_hip.h, "Factor annotation").  Host arrays except F, which is the
+// DEVICE's (k x n column-major); every call only reads the context, allocates its own temporaries and synchronises the stream
+// before it returns.  k = 1 on the gene side, which has no rank to refuse.
+int sgl_annotate_args_check(const char* who, const int32_t* labels, int64_t n, int32_t n_groups, int32_t k);
+int sgl_group_moments_dev(sgl_ctx* c, const double* F, int k, int64_t n, const int32_t* labels, int32_t G, int64_t* group_n, double* sum,
+                          double* rss);
+// over c->At: nz and sum from sgl_markers_core (transform 0), rss = E + Z; m x G column-major, rss m values; any may be NULL
+int sgl_gene_moments_core(sgl_ctx* c, const int32_t* labels, int32_t G, int64_t* group_n, int64_t* nz, double* sum, double* rss);
 
 // gene set enrichment (kernels_gsea.hip; include/singlet_hip.h, "Gene set enrichment").  All arrays are the HOST's; every call
 // only reads the context (it records what it ran in gsea_last), allocates its own temporaries and synchronises the stream

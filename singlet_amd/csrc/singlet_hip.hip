@@ -5,6 +5,7 @@
 // every entry point returns SGL_ENODEV.
 #include "sgl_internal.h"
 #include "ingest_host.h"
+#include "annotate_host.h"
 
 #include <math.h>
 #include <string.h>
@@ -278,6 +279,7 @@ extern "C" int sgl_destroy(sgl_ctx* c) {
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     sgl_team_detach(c);
     sgl_knn_index_free(c);
+    dev_free(c->ann_F);
     free_fit(c);
     free_matrix(c);
     dev_free(c->ws);
@@ -2002,6 +2004,171 @@ extern "C" int sgl_markers_info(sgl_ctx* c, int64_t out[4]) {
     CTX_GUARD(c);
     if (!out) { sgl_set_error("sgl_markers_info: NULL out"); return SGL_EINVAL; }
     std::copy(c->markers_last, c->markers_last + 4, out);
+    return SGL_OK;
+}
+
+// Factor annotation (include/singlet_hip.h; kernels_annotate.hip, annotate_host.h): the refusals, then passes that only read.
+#define ANN_OUT_PARAMS double *coef, double *stdev_unscaled, double *amean, double *sigma, double *s2_post, double *scalars, \
+                       double *var_prior, double *t, double *p_raw, double *p_adj, double *lods
+#define ANN_OUT_ARGS coef, stdev_unscaled, amean, sigma, s2_post, scalars, var_prior, t, p_raw, p_adj, lods
+static int annotate_model_args(const char* who, double proportion, int tail) {
+    if (!(proportion > 0.0 && proportion < 1.0)) { sgl_set_error("%s: proportion = %g is outside (0, 1)", who, proportion); return SGL_EINVAL; }
+    if (tail < 0 || tail > 2) { sgl_set_error("%s: tail = %d is none of 0 (pos), 1 (neg), 2 (std)", who, tail); return SGL_EINVAL; }
+    return SGL_OK;
+}
+static int annotate_embedding_state(sgl_ctx* c, const char* who, const double* F, int32_t k, int64_t n) {
+    if (c->team || c->allreduce) {
+        sgl_set_error("%s: the context is a shard of a team or has an all-reduce hook; the moments of this shard's cells are not the matrix's", who);
+        return SGL_ESTATE;
+    }
+    if (F) return SGL_OK;
+    if (c->ann_F) {
+        if (k != c->ann_k || n != c->ann_n) {
+            sgl_set_error("%s: F is NULL, but k = %d, n = %lld are not the held embedding's %d x %lld", who, k, (long long)n, c->ann_k, (long long)c->ann_n);
+            return SGL_EINVAL;
+        }
+        return SGL_OK;
+    }
+    if (c->k == 0) { sgl_set_error("%s: F is NULL and no fit is initialised (call sgl_fit_init)", who); return SGL_ESTATE; }
+    if (c->cell_offset != 0 || c->ncells_total != (int64_t)c->A.ncol) {
+        sgl_set_error("%s: the context holds a shard (cells %lld .. %lld of %lld); annotate the whole embedding", who,
+                      (long long)c->cell_offset, (long long)c->cell_offset + c->A.ncol, (long long)c->ncells_total);
+        return SGL_ESTATE;
+    }
+    if (k != c->k || n != c->A.ncol) {
+        sgl_set_error("%s: F is NULL, but k = %d, n = %lld are not the fit's %d x %d", who, k, (long long)n, c->k, c->A.ncol);
+        return SGL_EINVAL;
+    }
+    return SGL_OK;
+}
+static int annotate_embedding_args(const char* who, int32_t k, int64_t n, const int32_t* labels, int32_t n_groups) {
+    if (n < 0 || n > INT32_MAX) { sgl_set_error("%s: n = %lld cells is outside [0, 2^31)", who, (long long)n); return SGL_EINVAL; }
+    return sgl_annotate_args_check(who, labels, n, n_groups, k);
+}
+// the moments of a host F through a temporary device copy, or of the fit's H in place
+static int annotate_embedding_moments(sgl_ctx* c, const double* F, int32_t k, int64_t n, const int32_t* labels, int32_t G, int64_t* group_n,
+                                      double* sum, double* rss) {
+    if (!F) return sgl_group_moments_dev(c, c->ann_F ? c->ann_F : c->H, k, n, labels, G, group_n, sum, rss);
+    DevBuf<double> dF;
+    SGLCHK(dF.alloc((size_t)k * (size_t)std::max<int64_t>(n, 1)));
+    if (n > 0) HIPCHK(hipMemcpyAsync(dF.p, F, sizeof(double) * (size_t)k * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    return sgl_group_moments_dev(c, dF.p, k, n, labels, G, group_n, sum, rss);   // (synchronises before dF goes)
+}
+static int annotate_gene_state(sgl_ctx* c, const char* who) {
+    if (c->team || c->allreduce) {
+        sgl_set_error("%s: the context is a shard of a team or has an all-reduce hook; the moments of this shard's cells are not the matrix's", who);
+        return SGL_ESTATE;
+    }
+    if (!c->A.p || !c->At.p) { sgl_set_error("%s: no matrix resident", who); return SGL_ESTATE; }
+    if (c->cell_offset != 0 || c->ncells_total != (int64_t)c->A.ncol) {
+        sgl_set_error("%s: the context holds a shard (cells %lld .. %lld of %lld); annotate the whole matrix", who,
+                      (long long)c->cell_offset, (long long)c->cell_offset + c->A.ncol, (long long)c->ncells_total);
+        return SGL_ESTATE;
+    }
+    return SGL_OK;
+}
+
+extern "C" int sgl_annotate_hold(sgl_ctx* c, const double* F, int32_t k, int64_t n) {
+    CTX_GUARD(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    dev_free(c->ann_F);
+    c->ann_F = nullptr;
+    c->ann_k = 0;
+    c->ann_n = 0;
+    if (!F) return SGL_OK;
+    if (k < 1 || k > ANNOTATE_MAX_K) { sgl_set_error("sgl_annotate_hold: k = %d is outside [1, %d]", k, ANNOTATE_MAX_K); return SGL_EINVAL; }
+    if (n < 1 || n > INT32_MAX) { sgl_set_error("sgl_annotate_hold: n = %lld cells is outside [1, 2^31)", (long long)n); return SGL_EINVAL; }
+    SGLCHK(dev_alloc(&c->ann_F, (size_t)k * (size_t)n));
+    const hipError_t e = hipMemcpy(c->ann_F, F, sizeof(double) * (size_t)k * (size_t)n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        dev_free(c->ann_F);
+        c->ann_F = nullptr;
+        sgl_set_error("sgl_annotate_hold: the upload failed: %s", hipGetErrorString(e));
+        return SGL_EHIP;
+    }
+    c->ann_k = k;
+    c->ann_n = n;
+    return SGL_OK;
+}
+
+extern "C" int sgl_group_moments(sgl_ctx* c, const double* F, int32_t k, int64_t n, const int32_t* labels, int32_t n_groups, int64_t* group_n,
+                                 double* sum, double* rss) {
+    CTX_GUARD(c);
+    SGLCHK(annotate_embedding_state(c, "sgl_group_moments", F, k, n));
+    SGLCHK(annotate_embedding_args("sgl_group_moments", k, n, labels, n_groups));
+    return annotate_embedding_moments(c, F, k, n, labels, n_groups, group_n, sum, rss);
+}
+
+extern "C" int sgl_c_group_moments(const double* F, int32_t k, int64_t n, const int32_t* labels, int32_t n_groups, int64_t* group_n, double* sum,
+                                   double* rss) {
+    if (!F) { sgl_set_error("sgl_c_group_moments: F is NULL"); return SGL_EINVAL; }
+    SGLCHK(annotate_embedding_args("sgl_c_group_moments", k, n, labels, n_groups));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    return sgl_group_moments(hd.c, F, k, n, labels, n_groups, group_n, sum, rss);
+}
+
+extern "C" int sgl_gene_group_moments(sgl_ctx* c, const int32_t* labels, int32_t n_groups, int64_t* group_n, int64_t* nz, double* sum, double* rss) {
+    CTX_GUARD(c);
+    SGLCHK(annotate_gene_state(c, "sgl_gene_group_moments"));
+    SGLCHK(sgl_annotate_args_check("sgl_gene_group_moments", labels, c->A.ncol, n_groups, 1));
+    return sgl_gene_moments_core(c, labels, n_groups, group_n, nz, sum, rss);
+}
+
+extern "C" int sgl_annotate_stats(int64_t rows, int32_t n_groups, const int64_t* group_n, const double* sum, const double* rss, int center, int scale,
+                                  double proportion, int tail, ANN_OUT_PARAMS) {
+    if (rows < 0 || n_groups < 1 || n_groups > ANNOTATE_MAX_GROUPS) {
+        sgl_set_error("sgl_annotate_stats: rows = %lld, n_groups = %d: rows >= 0 and n_groups in [1, %d]", (long long)rows, n_groups, ANNOTATE_MAX_GROUPS);
+        return SGL_EINVAL;
+    }
+    if (!group_n || !sum || !rss) { sgl_set_error("sgl_annotate_stats: NULL group_n, sum or rss"); return SGL_EINVAL; }
+    for (int32_t g = 0; g < n_groups; ++g)
+        if (group_n[g] < 0) { sgl_set_error("sgl_annotate_stats: group_n[%d] = %lld is negative", g, (long long)group_n[g]); return SGL_EINVAL; }
+    SGLCHK(annotate_model_args("sgl_annotate_stats", proportion, tail));
+    annotate_stats(rows, n_groups, group_n, sum, rss, center, scale, proportion, tail, ANN_OUT_ARGS);
+    return SGL_OK;
+}
+
+extern "C" int sgl_annotate(sgl_ctx* c, const double* F, int32_t k, int64_t n, const int32_t* labels, int32_t n_groups, int center, int scale,
+                            double proportion, int tail, int64_t* group_n, double* sum, double* rss, ANN_OUT_PARAMS) {
+    CTX_GUARD(c);
+    SGLCHK(annotate_embedding_state(c, "sgl_annotate", F, k, n));
+    SGLCHK(annotate_embedding_args("sgl_annotate", k, n, labels, n_groups));
+    SGLCHK(annotate_model_args("sgl_annotate", proportion, tail));
+    std::vector<int64_t> gn((size_t)n_groups);
+    std::vector<double> hsum((size_t)k * (size_t)n_groups), hrss((size_t)k);
+    SGLCHK(annotate_embedding_moments(c, F, k, n, labels, n_groups, gn.data(), hsum.data(), hrss.data()));
+    annotate_stats(k, n_groups, gn.data(), hsum.data(), hrss.data(), center, scale, proportion, tail, ANN_OUT_ARGS);
+    if (group_n) std::copy(gn.begin(), gn.end(), group_n);
+    if (sum) std::copy(hsum.begin(), hsum.end(), sum);
+    if (rss) std::copy(hrss.begin(), hrss.end(), rss);
+    return SGL_OK;
+}
+
+extern "C" int sgl_c_annotate(const double* F, int32_t k, int64_t n, const int32_t* labels, int32_t n_groups, int center, int scale, double proportion,
+                              int tail, int64_t* group_n, double* sum, double* rss, ANN_OUT_PARAMS) {
+    if (!F) { sgl_set_error("sgl_c_annotate: F is NULL"); return SGL_EINVAL; }
+    SGLCHK(annotate_embedding_args("sgl_c_annotate", k, n, labels, n_groups));   // before a context is made
+    SGLCHK(annotate_model_args("sgl_c_annotate", proportion, tail));
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    return sgl_annotate(hd.c, F, k, n, labels, n_groups, center, scale, proportion, tail, group_n, sum, rss, ANN_OUT_ARGS);
+}
+
+extern "C" int sgl_annotate_genes(sgl_ctx* c, const int32_t* labels, int32_t n_groups, int center, int scale, double proportion, int tail,
+                                  int64_t* group_n, int64_t* nz, double* sum, double* rss, ANN_OUT_PARAMS) {
+    CTX_GUARD(c);
+    SGLCHK(annotate_gene_state(c, "sgl_annotate_genes"));
+    SGLCHK(sgl_annotate_args_check("sgl_annotate_genes", labels, c->A.ncol, n_groups, 1));
+    SGLCHK(annotate_model_args("sgl_annotate_genes", proportion, tail));
+    const int32_t m = c->A.nrow;
+    std::vector<int64_t> gn((size_t)n_groups);
+    std::vector<double> hsum((size_t)m * (size_t)n_groups), hrss((size_t)m);
+    SGLCHK(sgl_gene_moments_core(c, labels, n_groups, gn.data(), nz, hsum.data(), hrss.data()));
+    annotate_stats(m, n_groups, gn.data(), hsum.data(), hrss.data(), center, scale, proportion, tail, ANN_OUT_ARGS);
+    if (group_n) std::copy(gn.begin(), gn.end(), group_n);
+    if (sum) std::copy(hsum.begin(), hsum.end(), sum);
+    if (rss) std::copy(hrss.begin(), hrss.end(), rss);
     return SGL_OK;
 }
 
