@@ -706,6 +706,65 @@ SGL_API int sgl_c_markers(const double* Ax, const int32_t* Ai, const int32_t* Ap
  * the batches of the long path, out[3] the LDS cap (included non-zero entries). */
 SGL_API int sgl_markers_info(sgl_ctx* ctx, int64_t out[4]);
 
+/* Signature scores: how strongly every cell expresses every gene signature -- the rank-based UCell score (Andreatta &
+ * Carmona 2021, "UCell: robust and scalable single-cell gene signature scoring"): the Mann-Whitney U of the signature's genes
+ * within ONE descending ordering of the cell's values.  The reference's package has no such function; the rules below are this
+ * library's own statement of UCell's published definition, in full; tests/signature_restatement.py restates them in numpy
+ * and scipy.stats.rankdata is the independent yardstick.  NO parity run against the R package is claimed.
+ *
+ * Inputs.  The resident matrix A, m genes x n cells, values as they are (non-finite values are refused at upload).  The
+ * score depends only on the order of the values within a cell: raw counts, the log-normalised matrix and a
+ * sgl_weight_by_split matrix give the same scores.  max_rank R, 1 <= R <= m.  n_sets >= 1 gene sets as set_ptr (int64,
+ * n_sets + 1 offsets from 0, ascending) and set_genes (int32, 0-based gene indices in [0, m)), the layout sgl_c_gsea takes.
+ * No gene twice within a set; the size n_s of a set satisfies 1 <= n_s <= R; a gene may be in any number of sets.
+ *
+ * Order within cell c.  Descending by value: the P stored entries x > 0, then ONE zero block of Z = m - P - N genes, then
+ * the N stored entries x < 0.  The zero block holds the implicit zeros and the stored zeros of either sign.  A tie run is a
+ * maximal set of equal doubles; a run at the 0-based positions [a, b) gives each member the DOUBLED midrank r2 = a + b + 1.
+ * The zero block is never materialised: it is the run a = P, b = P + Z, and the positions of the negatives are shifted by Z.
+ *
+ * Cap.  r2' = r2 when r2 <= 2 R, else 2 R + 2: UCell's "ranks above maxRank become maxRank + 1".  A midrank of exactly R is
+ * kept, a midrank of R + 0.5 is capped.
+ *
+ * Per (set s, cell c).  rank2[s, c] (uint64) = the sum of r2' over the genes of the set.
+ *   score[s, c] = 1.0 - (double)(rank2 - n_s (n_s + 1)) / (2.0 * n_s * R)
+ * which is 1 - U / (n_s R) with U = rank sum - n_s (n_s + 1) / 2: one conversion (exact), one division and one subtraction,
+ * both correctly rounded; the score lies in [(n_s - 1) / (2 R), 1].  rank2 is all integers: any correct kernel gives the same
+ * bits, whatever its paths, batches or passes, and the score is the same expression in numpy, bit for bit.  No floating-point
+ * atomics; integer atomics in any order cannot change a bit; no contraction.
+ *
+ * sgl_signature_scores: both outputs hold n_sets x ncol values, column-major with the SET fastest: out[s + n_sets * c] (a
+ * cell's scores are contiguous; read as a C array it is ncol x n_sets).  EITHER output may be NULL.
+ *  - refused with SGL_EINVAL, nothing launched, with a message that names the FIRST defect in this order: no matrix
+ *    resident; a context that is a rank of a team; NULL set_ptr or set_genes; n_sets < 1; max_rank outside [1, m]; a
+ *    negative knob (the operator forms below); then set_ptr over all sets -- an offset that does not start at 0 or
+ *    descends, an empty set, a set with n_s > max_rank; then the genes set by set -- a gene outside [0, m), a gene twice in
+ *    one set.  The context stays usable after every refusal.
+ *  - works after sgl_upload_dense (over the CSC image that upload keeps) and after the typed / native upload.
+ *  - the call only reads the context: the matrix, a running fit, entry streams and mask lists stay untouched; a fit
+ *    continued after it gives the bits it would have given without it.  Its kernels count in the "scale" phase.
+ *  - paths: a count pass gives every cell its P and N, L = P + N.  A cell with L <= 1024 is gathered into LDS as (key, gene)
+ *    pairs -- the key the order-preserving 64-bit image of the double, descending -- sorted there by one workgroup and
+ *    walked once; one with L <= CAP = 4096 goes to the second instance of the same kernel; a longer one (a dense upload
+ *    makes L = m) goes through scratch and a segmented radix sort, in batches of whole cells in ascending order (each below
+ *    2^31 entries and the scratch budget of 2^27 entries, 24 bytes each; a cell above the budget is a batch of its own).
+ *    The walk finds both ends of a position's run at once, by binary search over the sorted keys, only for a gene that is
+ *    in a set: the gene -> sets table (the transpose of the sets, built per call) is looked up first.
+ *  - sets beyond the 1024 whose accumulators one pass holds in LDS are scored in further passes over the sorted cell.
+ *  - there is NO team form and NO R shim entry. */
+SGL_API int sgl_signature_scores(sgl_ctx* ctx, const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets, int32_t max_rank,
+                                 uint64_t* rank2_out, double* score_out);
+/* The one-shot form: its own context on the current device, A as a dgCMatrix; the argument refusals come before anything is
+ * uploaded.  Neither uses nor touches the SINGLET_HIP_CACHE context. */
+SGL_API int sgl_c_signature_scores(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol,
+                                   const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets, int32_t max_rank,
+                                   uint64_t* rank2_out, double* score_out);
+/* What the last signature call (scores or sgl_op_cell_ranks) on this context ran: out[0] the cells sorted by the 1024-entry
+ * LDS instance, out[1] by the 4096-entry one, out[2] the cells on the long path, out[3] the batches of the long path,
+ * out[4] the set passes (0 for sgl_op_cell_ranks), and the caps in force: out[5] the LDS cap (stored non-zero entries),
+ * out[6] the entries of a batch, out[7] the sets of a pass (0 for sgl_op_cell_ranks). */
+SGL_API int sgl_signature_info(sgl_ctx* ctx, int64_t out[8]);
+
 /* Factor annotation: which factors of a fit represent which levels of a metadata column (cell types, batches, donors) --
  * the reference's AnnotateNMF (R/AnnotateNMF.R:29-41, R/getDesigns.R, R/getModelMatrix.R, R/getModelFit.R,
  * R/getModelResults.R): for a factor-typed column the means model ~ 0 + column over the cells whose value is not NA, fitted
@@ -1544,6 +1603,21 @@ SGL_API int sgl_op_loess_direct(sgl_ctx* ctx, const double* x, const double* y, 
 SGL_API int sgl_op_marker_sums(sgl_ctx* ctx, const int32_t* labels, int32_t n_groups, int transform, int64_t* pos, int64_t* nz, double* sum);
 SGL_API int sgl_op_marker_ranks(sgl_ctx* ctx, const int32_t* labels, int32_t n_groups, int64_t max_batch_entries, int64_t* rank2,
                                 uint64_t* tie);
+/* The stages of sgl_signature_scores (the rules are stated there; the same refusals, the same read-only contract), with the
+ * knobs that force every path at small shapes.  A knob of 0 means the default, a negative one is SGL_EINVAL, one above the
+ * default is the default; the results do not depend on any of them.
+ *  - lds_cap: the stored non-zero entries up to which a cell is sorted in LDS (default 4096; the small instance takes the
+ *    cells up to min(lds_cap, 1024)); max_batch_entries: the entries of a batch of the long path (default 2^27);
+ *    pass_sets: the sets of one pass (default 1024).
+ *  - sgl_op_cell_ranks: rank2_entry_out[q] (uint64, one per stored entry, in storage order) = the doubled capped midrank
+ *    r2' of stored entry q within its cell; a stored zero gets the zero block's value.  zero2_out[c] (uint64, ncol) = the
+ *    zero block's value of cell c, or 0 when Z = 0.  Either may be NULL.
+ *  - sgl_op_signature_scores: sgl_signature_scores with the three knobs before the outputs. */
+SGL_API int sgl_op_cell_ranks(sgl_ctx* ctx, int32_t max_rank, int64_t lds_cap, int64_t max_batch_entries, uint64_t* rank2_entry_out,
+                              uint64_t* zero2_out);
+SGL_API int sgl_op_signature_scores(sgl_ctx* ctx, const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets, int32_t max_rank,
+                                    int64_t lds_cap, int64_t max_batch_entries, int32_t pass_sets, uint64_t* rank2_out,
+                                    double* score_out);
 /* The stages of sgl_c_gsea, one at a time (the rules and the refusals are stated there).  They use the context's device,
  * stream and pool only: no resident matrix is needed, nothing of the context changes but what sgl_gsea_info reports.
  *  - sgl_op_gsea_es: the observed scores of the given sets under all three score types, each n_sets x k column-major; any

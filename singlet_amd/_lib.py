@@ -110,6 +110,11 @@ SIGNATURES = {
     "sgl_c_markers": (C.c_int, _CSC + [C.c_int32, C.c_int32, i32p, C.c_int32, C.c_int, C.c_double, i64p, i64p, f64p, i64p, u64p,
                                        f64p, f64p, f64p, f64p, f64p]),
     "sgl_markers_info": (C.c_int, [C.c_void_p, i64p]),
+    "sgl_signature_scores": (C.c_int, [C.c_void_p, i64p, i32p, C.c_int32, C.c_int32, u64p, f64p]),
+    "sgl_c_signature_scores": (C.c_int, _CSC + [C.c_int32, C.c_int32, i64p, i32p, C.c_int32, C.c_int32, u64p, f64p]),
+    "sgl_signature_info": (C.c_int, [C.c_void_p, i64p]),
+    "sgl_op_cell_ranks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, u64p, u64p]),
+    "sgl_op_signature_scores": (C.c_int, [C.c_void_p, i64p, i32p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, u64p, f64p]),
     "sgl_op_marker_sums": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int, i64p, i64p, f64p]),
     "sgl_op_marker_ranks": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int64, i64p, u64p]),
     "sgl_group_moments": (C.c_int, [C.c_void_p, f64p, C.c_int32, C.c_int64, i32p, C.c_int32, i64p, f64p, f64p]),

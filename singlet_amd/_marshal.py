@@ -207,6 +207,43 @@ def gsea_score_type(score_type):
     return GSEA_SCORE_TYPES[score_type]
 
 
+def signature_sets(sets):
+    """(int64 set_ptr, int32 set_genes) of the signature calls from a list of gene-index sequences, one per set.  The library
+    checks the content; only what cannot be marshalled is refused here."""
+    if isinstance(sets, np.ndarray) and sets.ndim == 1 and sets.dtype.kind in "iu":
+        sets = [sets]
+    rows = []
+    for j, v in enumerate(sets):
+        a = np.asarray(v)
+        if a.size == 0:
+            a = np.zeros(0, dtype=np.int32)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (a.min() < -2**31 or a.max() >= 2**31)):
+            raise ValueError("set %d must hold 0-based integer gene indices" % j)
+        rows.append(a.astype(np.int32))
+    sp = np.zeros(len(rows) + 1, dtype=np.int64)
+    if rows:
+        sp[1:] = np.cumsum([r.size for r in rows])
+    sg = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0), dtype=np.int32)
+    if sg.size == 0:
+        sg = np.zeros(1, dtype=np.int32)[:0]
+    return sp, sg
+
+
+def signature_call(fn, ncol, sets, max_rank, return_rank2):
+    """Shared by Context.signature_scores, Context.op_signature_scores and api.c_signature_scores: fn(set_ptr, set_genes,
+    n_sets, max_rank, rank2, score) is the library call.  Returns score (n_sets x ncol), with return_rank2 (rank2, score)."""
+    sp, sg = signature_sets(sets)
+    P, n = sp.shape[0] - 1, max(int(ncol), 1)
+    if not -2**31 <= int(max_rank) < 2**31:
+        raise ValueError("max_rank is outside the 32-bit range")
+    score = np.empty((n, max(P, 1)))
+    rank2 = np.zeros((n, max(P, 1)), dtype=np.uint64) if return_rank2 else None
+    keep = sg if sg.size else np.zeros(1, dtype=np.int32)   # (an empty list still needs an address: the library names the defect)
+    check(fn(ptr(sp, i64p), ptr(keep, i32p), P, int(max_rank), ptr(rank2, u64p), ptr(score, f64p)))
+    score = score[:int(ncol), :P].T
+    return (rank2[:int(ncol), :P].T, score) if return_rank2 else score
+
+
 KNN_METRICS = {"euclidean": 0, "cosine": 1, "correlation": 2}
 
 

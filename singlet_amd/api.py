@@ -29,6 +29,8 @@ names, argument order, defaults and return fields:
                                         with every entry drawn), per cell and per gene
   run_gsea                              RunGSEA (R/RunGSEA.R:27-138) with the gene sets given by the caller and a permutation
                                         null in place of fgseaMultilevel (include/singlet_hip.h, "Gene set enrichment")
+  score_signatures                      UCell's ScoreSignatures_UCell: the rank-based score of gene signatures in every cell
+                                        (include/singlet_hip.h, "Signature scores")
   find_all_markers / find_markers       Seurat::FindAllMarkers / FindMarkers(test.use = "wilcox") under the rules stated in
                                         include/singlet_hip.h, "Marker genes" (the filters are applied after the test)
 
@@ -45,7 +47,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from ._marshal import ArdOutputs, NmfOutputs, annotate_call, annotate_tail, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, knn_weighting, label_list, markers_call
+from ._marshal import ArdOutputs, NmfOutputs, annotate_call, annotate_tail, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, knn_weighting, label_list, markers_call, signature_call
 from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
@@ -2006,6 +2008,113 @@ def find_markers(A, cells_1, cells_2=None, min_pct=0.1, logfc_threshold=0.25, on
     labels[m1] = 0
     st, names = _markers_of(A, labels, 2, transform, pseudocount)
     return _marker_table(st, 0, names, min_pct, logfc_threshold, only_pos, return_thresh)
+
+
+# ---------------------------------------------------------------------------
+# Signature scores of the cells (UCell's ScoreSignatures_UCell)
+# ---------------------------------------------------------------------------
+def c_signature_scores(A, sets, max_rank=1500, return_rank2=False):
+    """The one-shot form of Context.signature_scores (sgl_c_signature_scores): A a dgCMatrix or anything as_dgCMatrix accepts,
+    in a context of its own; the sets are checked before anything is uploaded.  Returns the same arrays."""
+    A = as_dgCMatrix(A)
+    L = _lib.load()
+    return signature_call(lambda *a: L.sgl_c_signature_scores(*csc_ptrs(A), A.nrow, A.ncol, *a), A.ncol, sets, max_rank, return_rank2)
+
+
+def signature_parse(signatures, gene_names=None, nrow=None, max_rank=1500, missing="skip"):
+    """The host half of score_signatures.  signatures: dict name -> genes.  With gene_names the genes are names: a trailing
+    "+" is stripped, a trailing "-" puts the gene into the signature's negative set; a name absent from gene_names is
+    dropped and reported (missing="skip") or refused (missing="error").  Without gene_names they are 0-based int rows in
+    [0, nrow), all positive.  Duplicates within a signature are dropped, the first occurrence kept.  A signature without a
+    positive gene, or with more than max_rank genes on a side, is refused.  Returns (names, pos, neg, dropped): per
+    signature its positive and negative rows as int32 arrays (neg may be empty), and dropped: dict name -> the names left
+    out.  Pure host."""
+    if missing not in ("skip", "error"):
+        raise ValueError("score_signatures: missing must be 'skip' or 'error'")
+    if not isinstance(signatures, dict) or not signatures:
+        raise ValueError("score_signatures: signatures must be a dict name -> genes with at least one signature")
+    index = None
+    if gene_names is not None:
+        index = {}
+        for r, g in enumerate(gene_names):
+            index.setdefault(g.decode() if isinstance(g, bytes) else str(g), r)   # a name that occurs twice: its first row
+        nrow = len(gene_names)
+    names, pos, neg, dropped = [], [], [], {}
+    for name, genes in signatures.items():
+        sides, gone = ([], []), []
+        for g in ([genes] if isinstance(genes, (str, bytes)) else genes):
+            side = 0
+            if index is not None:
+                g = g.decode() if isinstance(g, bytes) else str(g)
+                if g.endswith("-"):
+                    g, side = g[:-1], 1
+                elif g.endswith("+"):
+                    g = g[:-1]
+                if g not in index:
+                    if missing == "error":
+                        raise ValueError("score_signatures: gene %r of signature %r is not among gene_names" % (g, name))
+                    gone.append(g)
+                    continue
+                r = index[g]
+            else:
+                if isinstance(g, (str, bytes)) or int(g) != g:
+                    raise ValueError("score_signatures: signature %r holds %r; without gene_names the genes are int rows" % (name, g))
+                r = int(g)
+                if nrow is not None and not 0 <= r < nrow:
+                    raise ValueError("score_signatures: row %d of signature %r is outside [0, %d)" % (r, name, nrow))
+            if r not in sides[0] and r not in sides[1]:
+                sides[side].append(r)
+        if not sides[0]:
+            raise ValueError("score_signatures: signature %r has no positive gene%s" % (name, " left" if gone else ""))
+        for what, side in zip(("", "negative "), sides):
+            if len(side) > max_rank:
+                raise ValueError("score_signatures: signature %r holds %d %sgenes, more than max_rank = %d" % (name, len(side), what, max_rank))
+        names.append(name)
+        pos.append(np.asarray(sides[0], dtype=np.int32))
+        neg.append(np.asarray(sides[1], dtype=np.int32))
+        if gone:
+            dropped[name] = gone
+    return names, pos, neg, dropped
+
+
+def score_signatures(A, signatures, gene_names=None, max_rank=1500, w_neg=1.0, missing="skip"):
+    """UCell's ScoreSignatures_UCell on the device: the rank-based score of every signature in every cell (sgl_signature_scores;
+    the rules are stated in include/singlet_hip.h, "Signature scores").  A: a dgCMatrix, anything as_dgCMatrix accepts, a
+    native(...) object, or a Context that holds the matrix (counts or normalised: only the order within a cell matters).
+    signatures: a dict name -> gene names (int rows when gene_names is None), or the path of a GMT file (read_gmt).
+    gene_names None: the row names of A when it has them.  A trailing "+" on a gene name is stripped, a trailing "-" puts
+    the gene into the signature's negative set, scored as a device set of its own; the score is max(0, pos - w_neg * neg),
+    computed on the host.  missing: "skip" drops the genes absent from gene_names and reports them, "error" refuses them.
+    Everything is checked before anything is uploaded.  Returns {"scores" (n cells x S signatures), "names", "dropped"}."""
+    from .context import Context
+    if isinstance(signatures, (str, bytes, os.PathLike)):
+        signatures = read_gmt(signatures)
+    is_ctx, is_native = isinstance(A, Context), isinstance(A, NativeMatrix)
+    if not is_ctx and not is_native:
+        A = as_dgCMatrix(A)
+    if gene_names is None and not is_ctx and A.Dimnames[0] is not None and isinstance(signatures, dict) and any(
+            isinstance(g, (str, bytes)) for v in signatures.values() for g in ([v] if isinstance(v, (str, bytes)) else v)):
+        gene_names = A.Dimnames[0]
+    nrow = A.dims()[0] if is_ctx else A.nrow
+    if gene_names is not None and len(gene_names) != nrow:
+        raise ValueError("score_signatures: gene_names must name the %d rows of the matrix" % nrow)
+    max_rank = int(max_rank)
+    if not 1 <= max_rank <= nrow:
+        raise ValueError("score_signatures: max_rank = %d is outside [1, %d] (the genes of the matrix)" % (max_rank, nrow))
+    names, pos, neg, dropped = signature_parse(signatures, gene_names, nrow, max_rank, missing)
+    has_neg = [j for j in range(len(names)) if neg[j].size]
+    sets = pos + [neg[j] for j in has_neg]
+    if is_ctx:
+        sc = A.signature_scores(sets, max_rank)
+    elif is_native:
+        sc = _on_native(A, lambda ctx, fits: ctx.signature_scores(sets, max_rank))
+    else:
+        sc = c_signature_scores(A, sets, max_rank)
+    S = len(names)
+    scores = np.array(sc[:S].T)
+    for t, j in enumerate(has_neg):
+        scores[:, j] = np.maximum(0.0, scores[:, j] - float(w_neg) * sc[S + t])
+    return {"scores": scores, "names": names, "dropped": dropped}
 
 
 # ---------------------------------------------------------------------------

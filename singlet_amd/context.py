@@ -7,7 +7,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
 from ._marshal import (KNN_INDEX_FIELDS, MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, annotate_call, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call,
-                       knn_ivf_shape, knn_lists_in, knn_method, knn_metric, knn_weighting, label_list, markers_call, transfer_call)
+                       knn_ivf_shape, knn_lists_in, knn_method, knn_metric, knn_weighting, label_list, markers_call, signature_call, transfer_call)
 from .sparse import as_dgCMatrix
 
 SYNTH_SEED = 0x5EED
@@ -560,6 +560,21 @@ class Context(_Handle):
         check(self._L.sgl_markers_info(self._h, ptr(out, i64p)))
         return dict(zip(("lds_genes", "long_genes", "batches", "lds_cap"), (int(v) for v in out)))
 
+    def signature_scores(self, sets, max_rank=1500, return_rank2=False):
+        """The rank-based UCell score of every gene set in every cell of the resident matrix (sgl_signature_scores; the rules
+        are stated in include/singlet_hip.h, "Signature scores").  sets: a list of sequences of 0-based gene indices, one per
+        set (no gene twice in a set, at most max_rank genes).  Returns score, n_sets x ncol; with return_rank2 (rank2, score),
+        rank2 the uint64 sums of the doubled capped midranks.  The matrix and a running fit are only read."""
+        _, nc, _ = self.dims()
+        return signature_call(lambda *a: self._L.sgl_signature_scores(self._h, *a), nc, sets, max_rank, return_rank2)
+
+    def signature_info(self):
+        """What the last signature call on this context ran (sgl_signature_info): {"lds_small", "lds_large", "long_cells",
+        "batches", "passes", "lds_cap", "batch_cap", "pass_sets"}."""
+        out = np.zeros(8, dtype=np.int64)
+        check(self._L.sgl_signature_info(self._h, ptr(out, i64p)))
+        return dict(zip(("lds_small", "lds_large", "long_cells", "batches", "passes", "lds_cap", "batch_cap", "pass_sets"), (int(v) for v in out)))
+
     def knn(self, n_neighbors=20, reference=None, query=None, dims=None, metric="euclidean", method="exact", n_lists=None, n_probe=None,
             n_iter=10):
         """Exact nearest neighbours in an embedding (sgl_knn): (idx, dist), each n_query x n_neighbors, row j = the
@@ -979,6 +994,22 @@ class Context(_Handle):
         tie = np.zeros(max(nr, 1), dtype=np.uint64)
         check(self._L.sgl_op_marker_ranks(self._h, ptr(g, i32p), G, int(max_batch_entries), ptr(rank2, i64p), ptr(tie, u64p)))
         return rank2[:, :nr].T, tie[:nr]
+
+    # the stages of signature_scores, with the knobs that force every path (0: the default)
+    def op_cell_ranks(self, max_rank=1500, lds_cap=0, max_batch_entries=0):
+        """(rank2_entry, zero2): the doubled capped midrank of every stored entry of the resident matrix within its cell, in
+        storage order, and of every cell's zero block (0: the cell has none) (sgl_op_cell_ranks)."""
+        _, nc, nnz = self.dims()
+        entry, zero2 = np.zeros(max(nnz, 1), dtype=np.uint64), np.zeros(max(nc, 1), dtype=np.uint64)
+        check(self._L.sgl_op_cell_ranks(self._h, int(max_rank), int(lds_cap), int(max_batch_entries), ptr(entry, u64p), ptr(zero2, u64p)))
+        return entry[:nnz], zero2[:nc]
+
+    def op_signature_scores(self, sets, max_rank=1500, lds_cap=0, max_batch_entries=0, pass_sets=0):
+        """(rank2, score), each n_sets x ncol, as signature_scores gives them, with the LDS cap, the batch size of the long
+        path and the sets of a pass forced (sgl_op_signature_scores); the results do not depend on them."""
+        _, nc, _ = self.dims()
+        return signature_call(lambda sp, sg, P, R, r2, sc: self._L.sgl_op_signature_scores(
+            self._h, sp, sg, P, R, int(lds_cap), int(max_batch_entries), int(pass_sets), r2, sc), nc, sets, max_rank, True)
 
     # the stages of the gene set enrichment test, one at a time (no resident matrix is needed)
     def op_gsea_es(self, w, set_ptr, set_genes):

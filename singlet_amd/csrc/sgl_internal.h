@@ -263,6 +263,9 @@ struct sgl_ctx {
     int32_t ann_k = 0;
     int64_t ann_n = 0;
     int64_t gsea_last[5] = {0, 0, 0, 0, 0};   // sgl_gsea_info: sets, distinct sizes, s_max, batches, batch size of the last enrichment call
+    // sgl_signature_info: cells sorted by the small and by the large LDS instance, long cells, batches, set passes, and the
+    // caps in force (LDS entries, batch entries, sets per pass) of the last signature call
+    int64_t signature_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     sgl_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
@@ -503,6 +506,17 @@ int sgl_group_moments_dev(sgl_ctx* c, const double* F, int k, int64_t n, const i
                           double* rss);
 // over c->At: nz and sum from sgl_markers_core (transform 0), rss = E + Z; m x G column-major, rss m values; any may be NULL
 int sgl_gene_moments_core(sgl_ctx* c, const int32_t* labels, int32_t G, int64_t* group_n, int64_t* nz, double* sum, double* rss);
+
+// signature scores (kernels_signature.hip; include/singlet_hip.h, "Signature scores").  All arrays are the HOST's; every call only
+// reads the context (it records what it ran in signature_last), allocates its own temporaries and synchronises the stream
+// before it returns.  The args check holds every refusal of the arguments and launches nothing (m = the genes of the matrix).
+int sgl_signature_args_check(const char* who, const int64_t* set_ptr, const int32_t* set_genes, int64_t n_sets, int64_t m, int64_t max_rank,
+                             int64_t lds_cap, int64_t max_batch_entries, int64_t pass_sets);
+// over c->A (arguments checked before): rank2 / score n_sets x ncol, set fastest; either may be NULL; a knob of 0: the default
+int sgl_signature_scores_core(sgl_ctx* c, const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets, int64_t max_rank, int64_t lds_cap,
+                              int64_t max_batch_entries, int64_t pass_sets, uint64_t* rank2_out, double* score_out);
+// the doubled capped midrank of every stored entry (nnz values) and of every cell's zero block (ncol values; 0: no zero block)
+int sgl_cell_ranks_core(sgl_ctx* c, int64_t max_rank, int64_t lds_cap, int64_t max_batch_entries, uint64_t* entry_out, uint64_t* zero2_out);
 
 // gene set enrichment (kernels_gsea.hip; include/singlet_hip.h, "Gene set enrichment").  All arrays are the HOST's; every call
 // only reads the context (it records what it ran in gsea_last), allocates its own temporaries and synchronises the stream

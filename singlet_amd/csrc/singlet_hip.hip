@@ -2007,6 +2007,50 @@ extern "C" int sgl_markers_info(sgl_ctx* c, int64_t out[4]) {
     return SGL_OK;
 }
 
+// Signature scores (include/singlet_hip.h; kernels_signature.hip, signature_host.h): the refusals, then passes that only read.
+static int signature_state(sgl_ctx* c, const char* who) {
+    if (!c->A.p) { sgl_set_error("%s: no matrix resident", who); return SGL_EINVAL; }
+    if (c->team) { sgl_set_error("%s: the context is a rank of a team; score the cells on a context of its own", who); return SGL_EINVAL; }
+    return SGL_OK;
+}
+extern "C" int sgl_op_signature_scores(sgl_ctx* c, const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets, int32_t max_rank,
+                                       int64_t lds_cap, int64_t max_batch_entries, int32_t pass_sets, uint64_t* rank2_out, double* score_out) {
+    CTX_GUARD(c);
+    SGLCHK(signature_state(c, "sgl_op_signature_scores"));
+    SGLCHK(sgl_signature_args_check("sgl_op_signature_scores", set_ptr, set_genes, n_sets, c->A.nrow, max_rank, lds_cap, max_batch_entries, pass_sets));
+    return sgl_signature_scores_core(c, set_ptr, set_genes, n_sets, max_rank, lds_cap, max_batch_entries, pass_sets, rank2_out, score_out);
+}
+extern "C" int sgl_signature_scores(sgl_ctx* c, const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets, int32_t max_rank,
+                                    uint64_t* rank2_out, double* score_out) {
+    CTX_GUARD(c);
+    SGLCHK(signature_state(c, "sgl_signature_scores"));
+    SGLCHK(sgl_signature_args_check("sgl_signature_scores", set_ptr, set_genes, n_sets, c->A.nrow, max_rank, 0, 0, 0));
+    return sgl_signature_scores_core(c, set_ptr, set_genes, n_sets, max_rank, 0, 0, 0, rank2_out, score_out);
+}
+extern "C" int sgl_c_signature_scores(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, const int64_t* set_ptr,
+                                      const int32_t* set_genes, int32_t n_sets, int32_t max_rank, uint64_t* rank2_out, double* score_out) {
+    SGLCHK(sgl_signature_args_check("sgl_c_signature_scores", set_ptr, set_genes, n_sets, std::max(nrow, 0), max_rank, 0, 0, 0));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, nullptr, nullptr, nullptr, nrow, ncol, 0, ncol));
+    return sgl_signature_scores(hd.c, set_ptr, set_genes, n_sets, max_rank, rank2_out, score_out);
+}
+extern "C" int sgl_op_cell_ranks(sgl_ctx* c, int32_t max_rank, int64_t lds_cap, int64_t max_batch_entries, uint64_t* rank2_entry_out,
+                                 uint64_t* zero2_out) {
+    CTX_GUARD(c);
+    SGLCHK(signature_state(c, "sgl_op_cell_ranks"));
+    static const int64_t one_ptr[2] = {0, 1};   // the rules of max_rank and the knobs, through one set of one gene
+    static const int32_t one_gene[1] = {0};
+    SGLCHK(sgl_signature_args_check("sgl_op_cell_ranks", one_ptr, one_gene, 1, c->A.nrow, max_rank, lds_cap, max_batch_entries, 0));
+    return sgl_cell_ranks_core(c, max_rank, lds_cap, max_batch_entries, rank2_entry_out, zero2_out);
+}
+extern "C" int sgl_signature_info(sgl_ctx* c, int64_t out[8]) {
+    CTX_GUARD(c);
+    if (!out) { sgl_set_error("sgl_signature_info: NULL out"); return SGL_EINVAL; }
+    std::copy(c->signature_last, c->signature_last + 8, out);
+    return SGL_OK;
+}
+
 // Factor annotation (include/singlet_hip.h; kernels_annotate.hip, annotate_host.h): the refusals, then passes that only read.
 #define ANN_OUT_PARAMS double *coef, double *stdev_unscaled, double *amean, double *sigma, double *s2_post, double *scalars, \
                        double *var_prior, double *t, double *p_raw, double *p_adj, double *lods
