@@ -1292,6 +1292,93 @@ SGL_API int sgl_op_umap_epoch(const double* Gx, const int32_t* Gi, const int32_t
  * leaves them as they were. */
 SGL_API int sgl_umap_info(int64_t out[4]);
 
+/* Layout transform: query cells placed in the FIXED layout of a reference -- the picture of Seurat's MapQuery / ProjectUMAP,
+ * umap-learn's transform, uwot's umap_transform.  The reference positions do not move, negative samples are reference points,
+ * only the query moves: a query's trajectory depends on that query and the reference alone, never on another query.  So the
+ * result is ONE function of (query, reference), bit for bit, whatever the batching, and all epochs of a query run inside one
+ * kernel launch with the position in registers.  The rules are this library's own, stated in full below and restated in numpy
+ * in tests/umap_transform_restatement.py; no parity of coordinates with uwot or umap-learn is claimed (DESIGN.md "Layout
+ * transform").  FP64 throughout, every product, quotient and sum its own rounding (the unit is compiled with
+ * -ffp-contract=off); no floating-point atomics.
+ *
+ * Input of one query q: its neighbour list against the reference, (idx_s, d_s) for s = 0 .. K-1, as the searches write it:
+ * idx int32 and dist double, both K x n_query column-major (the list of query q at idx + q K), ascending, padding -1 / +Inf
+ * behind the valid slots (a slot is padding iff its index is -1; its distance is not read).  K in [1, 256].  The own list is
+ * the valid slots, ALL of them: a query is not a reference, so nothing is removed.
+ *  - memberships: rho and sigma follow sgl_c_fuzzy_graph's rules on the own list, word for word -- rho = the smallest
+ *    distance > 0, else 0; the bisection of EXACTLY 64 steps against log2(K); psum sequential in list order from +0.0 -- with
+ *    one difference: sigma = max(mid, 1e-3 * mean) with mean ALWAYS the own list's mean (the sum of its distances in list order
+ *    from +0.0 / their number).  There is no global mean: it would make one query depend on the others.  (When rho == 0 every
+ *    distance is 0, every membership is 1.0 and sigma is never read.)  w_s = 1.0 when d_s - rho <= 0, else
+ *    exp(-(d_s - rho) / sigma); a padding slot gets +0.0.  There is no symmetrisation: the graph is bipartite.  Consequence:
+ *    every non-empty list holds a membership of exactly 1.0 (its first slot: d_0 <= rho).
+ *  - start: y0_f = (sum_s w_s * Yref[f, idx_s]) / (sum_s w_s), both sums sequential in slot order over the valid slots from
+ *    +0.0.
+ *  - firing: r_s = w_s (the list's maximum is exactly 1.0, so sgl_c_umap_layout's division by w_max is the identity and is
+ *    not performed).  Slot s fires in epoch t (1-based) iff floor(t * w_s) > floor((t - 1) * w_s).
+ *  - terms: the layout's attractive and repulsive terms, clip and constants unchanged; the head is the query's position, the
+ *    other point a reference position: Yref[:, idx_s] for the attractive term, Yref[:, m] for a negative sample.  There is
+ *    no m == j exclusion: a sample is a reference and never the query.  A repulsive term with d2 == 0 has every component
+ *    +4.0; b == 1.0 exactly skips pow.
+ *  - negative samples of firing slot s: for i = 0 .. neg_rate - 1, u = rand(seed, 256 * (query_offset + q) + s, 256 * t + i)
+ *    -- the hash of the mask -- and m = ((u >> 32) * (uint64) n_ref) >> 32.  query_offset is the global index of the call's
+ *    first query (the same device as the global cell index in the mask hash of the sharded fit): with it, a batch cut out of
+ *    a larger call reproduces that call's rows.
+ *  - orders and update: the layout's.  g_s = attractive + the samples in order; delta = the g_s of the firing slots in slot
+ *    order from +0.0; y' = y + alpha_t * delta, alpha_t = alpha0 * (1.0 - (t - 1) / n_epochs).  A query without a firing slot
+ *    in an epoch keeps the bits of y.
+ *  - a query with no valid slot: rho = sigma = +0.0, y0 and y are a quiet NaN (the transfer's rule for values); it is counted
+ *    in sgl_umap_transform_info.  The stage operator does not read (or check) its column of Yin.
+ *  - refused on the host, before anything is launched, with a message naming value and range and every output untouched
+ *    (SGL_EINVAL): K outside [1, 256]; dim outside [1, 8]; n_epochs outside [1, 2^20]; neg_rate outside [0, 255]; alpha0, a
+ *    or b not finite or not > 0; n_ref outside [1, 2^31); n_query < 0; not 1 <= t_first <= t_last <= n_epochs; query_offset
+ *    < 0 or query_offset + n_query above 2^55; and, named by query and slot, the first of: an index outside [-1, n_ref), a
+ *    valid slot behind a padding slot, an index repeated in its list, a distance of a valid slot that is not finite, negative
+ *    or below the one before it; a non-finite Yref or Yin; a W of a valid slot outside [0, 1].  n_query == 0 returns SGL_OK
+ *    and writes nothing.
+ *  - kernels (singlet_amd/csrc/kernels_umap_transform.hip; the host logic without HIP in umap_transform_host.h).  Memberships:
+ *    one thread per query (the serial order of psum forbids a wave reduction).  Transform: one wave per query; the wave
+ *    stages its slots (reference index, membership) in LDS once and keeps y in registers, every lane holding the current y;
+ *    per epoch a ballot compacts the firing slots in steps of 64, the (slot, term) pairs are spread over the lanes, the
+ *    clipped terms go through LDS to lane f < dim, which adds them in the stated order, and y' is published to the wave; y
+ *    is written to memory once, at the end of the launch.  The host cuts the epochs of a call into launches of at most 128
+ *    epochs (the profiling switch SGL_UMAP_TRANSFORM_EPOCHS_PER_LAUNCH in the environment asks for fewer, 1 .. 128); the
+ *    result does not depend on the cut.  Instances as the layout's: 2 * (0: dim 2, 1: dim 3, 2: the generic
+ *    loop up to 8) + (1 when b == 1.0).
+ *  - what holds: rho is bit for bit the restatement's; sigma and W differ from it by the ulps of the device's exp; from
+ *    given W the epochs with b == 1.0 equal the restatement bit for bit, otherwise to the ulps of pow.
+ *
+ * sgl_c_fuzzy_query: the lists -> W (K x n_query), rho, sigma (double[n_query]); any output may be NULL.
+ * sgl_c_umap_transform: the lists and Yref (dim x n_ref column-major, finite) -> Y0_out (the start) and Y_out (after n_epochs
+ * epochs), each dim x n_query; either may be NULL.
+ * sgl_op_umap_transform_epochs, the stage operator: the epochs t_first .. t_last from the caller's W (K x n_query) and Yin
+ * (dim x n_query) -> Y_out.  Epochs 1 .. s followed by s + 1 .. n from its result equal 1 .. n.
+ * sgl_knn_index_set_layout puts Yref (dim x n_ref of the index, finite) onto the neighbour index of the context, resident
+ * with it: replaced by a second call, dropped with the index and by a rebuild, counted in sgl_knn_index_info's resident
+ * bytes.  SGL_ESTATE without an index.
+ * sgl_knn_index_project is one search in batches (Q, n_neighbors, n_probe, query_batch as sgl_knn_index_search), with
+ * memberships, start and transform run on the device for every batch: the lists do not travel to the host and back.  It
+ * equals sgl_knn_index_search followed by sgl_c_umap_transform (query_offset 0) bit for bit, for both index methods and any
+ * query_batch.  Outputs idx, dist (K x n_query), Y0, Y (dim x n_query); any may be NULL.  SGL_ESTATE without an index or
+ * without a layout.
+ * sgl_umap_transform_info: what the last sgl_c_umap_transform, sgl_op_umap_transform_epochs or sgl_knn_index_project of this
+ * process ran: out[0] the transform kernel's instance (-1 before the first), [1] the widest list (valid slots), [2] the
+ * queries without a valid slot, [3] the launches of the transform kernel.  A refused call leaves them as they were. */
+SGL_API int sgl_c_fuzzy_query(const int32_t* idx, const double* dist, int64_t n_query, int32_t K, int64_t n_ref, double* W_out,
+                              double* rho_out, double* sigma_out);
+SGL_API int sgl_c_umap_transform(const int32_t* idx, const double* dist, int64_t n_query, int32_t K, const double* Yref, int32_t dim,
+                                 int64_t n_ref, double a, double b, int32_t n_epochs, double alpha0, int32_t neg_rate, uint64_t seed,
+                                 int64_t query_offset, double* Y0_out, double* Y_out);
+SGL_API int sgl_op_umap_transform_epochs(const int32_t* idx, const double* W, int64_t n_query, int32_t K, const double* Yref, int32_t dim,
+                                         int64_t n_ref, const double* Yin, double a, double b, int32_t n_epochs, double alpha0,
+                                         int32_t neg_rate, uint64_t seed, int64_t query_offset, int32_t t_first, int32_t t_last,
+                                         double* Y_out);
+SGL_API int sgl_knn_index_set_layout(sgl_ctx* ctx, const double* Yref, int32_t dim);
+SGL_API int sgl_knn_index_project(sgl_ctx* ctx, const double* Q, int64_t n_query, int32_t n_neighbors, int32_t n_probe,
+                                  int64_t query_batch, double a, double b, int32_t n_epochs, double alpha0, int32_t neg_rate,
+                                  uint64_t seed, int32_t* idx_out, double* dist_out, double* Y0_out, double* Y_out);
+SGL_API int sgl_umap_transform_info(int64_t out[4]);
+
 /* Gene set enrichment: which gene sets are enriched at the top of each factor's loadings -- the reference's RunGSEA
  * (R/RunGSEA.R), one pre-ranked enrichment test per factor and gene set.  The enrichment score is the weighted
  * Kolmogorov-Smirnov statistic of GSEA in the form fgsea's calcGseaStat computes it (exponent 1); the p-values come from a

@@ -10,7 +10,8 @@ from .api import (c_nmf, c_ard_nmf, c_linked_nmf, c_gcnmf, run_gcnmf, c_nmf_dens
                   group_means, run_linked_nmf, RunLNMF, MetadataSummary, GetSharedFactors, GetUniqueFactors, evaluate,
                   find_variable_features, knn, knn_recall, find_neighbors, ReferenceIndex, transfer_labels, transfer_values, map_query, c_louvain, op_louvain_sweep,
                   louvain_info, find_clusters, c_markers, find_all_markers, find_markers, fuzzy_simplicial_set, umap_layout,
-                  op_umap_epoch, umap_info, find_ab_params, run_umap, c_gsea, read_gmt, run_gsea, check_columns, get_designs, annotate_stats,
+                  op_umap_epoch, umap_info, find_ab_params, run_umap, fuzzy_query, umap_transform, op_umap_transform_epochs,
+                  umap_transform_info, project_umap, UmapModel, c_gsea, read_gmt, run_gsea, check_columns, get_designs, annotate_stats,
                   c_annotate, c_group_moments, get_model_fit, get_model_results, AnnotateNMF, c_signature_scores, signature_parse,
                   score_signatures)
 from .native import native, NativeMatrix  # noqa: F401

@@ -167,6 +167,15 @@ SIGNATURES = {
     "sgl_op_umap_epoch": (C.c_int, _CSC + [C.c_int32, f64p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32,
                                            C.c_uint64, C.c_int32, f64p]),
     "sgl_umap_info": (C.c_int, [i64p]),
+    "sgl_c_fuzzy_query": (C.c_int, [i32p, f64p, C.c_int64, C.c_int32, C.c_int64, f64p, f64p, f64p]),
+    "sgl_c_umap_transform": (C.c_int, [i32p, f64p, C.c_int64, C.c_int32, f64p, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_int32,
+                                       C.c_double, C.c_int32, C.c_uint64, C.c_int64, f64p, f64p]),
+    "sgl_op_umap_transform_epochs": (C.c_int, [i32p, f64p, C.c_int64, C.c_int32, f64p, C.c_int32, C.c_int64, f64p, C.c_double, C.c_double,
+                                               C.c_int32, C.c_double, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, f64p]),
+    "sgl_knn_index_set_layout": (C.c_int, [C.c_void_p, f64p, C.c_int32]),
+    "sgl_knn_index_project": (C.c_int, [C.c_void_p, f64p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_int32,
+                                        C.c_double, C.c_int32, C.c_uint64, i32p, f64p, f64p, f64p]),
+    "sgl_umap_transform_info": (C.c_int, [i64p]),
     "sgl_set_graph": (C.c_int, [C.c_void_p, f64p, i32p, i32p, C.c_int32, C.c_int32]),
     "sgl_set_allreduce": (C.c_int, [C.c_void_p, ALLREDUCE_FN, C.c_void_p]),
     "sgl_step_begin": (C.c_int, [C.c_void_p]),

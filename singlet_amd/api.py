@@ -1551,7 +1551,8 @@ class ReferenceIndex:
     n_values (layout coordinates, any covariate).  dims are 1-based, as in find_neighbors, and are applied to every query.
     method "ivf" (n_lists, n_iter as knn) or "exact".  A context manager; close() drops the index."""
 
-    def __init__(self, embedding_or_context, labels=None, values=None, dims=None, metric="euclidean", method="ivf", n_lists=None, n_iter=10):
+    def __init__(self, embedding_or_context, labels=None, values=None, dims=None, metric="euclidean", method="ivf", n_lists=None, n_iter=10,
+                 layout=None):
         from .context import Context
         knn_metric(metric)
         knn_method(method)
@@ -1576,6 +1577,9 @@ class ReferenceIndex:
                     V = np.asarray(values, dtype=np.float64)
                     V = (V[:, None] if V.ndim == 1 else V).T
                 self._ctx.knn_index_annotate(labels, None, V)
+            self.has_layout = False
+            if layout is not None:
+                self.set_layout(layout)
         except Exception:
             self.close()
             raise
@@ -1589,6 +1593,19 @@ class ReferenceIndex:
         asked for raises ValueError naming n_probe."""
         out = self._ctx.knn_index_map(np.asarray(query, dtype=np.float64).T, n_neighbors, n_probe, weighting)
         _refuse_short("ReferenceIndex.map", out["idx"])
+        return out
+
+    def set_layout(self, layout):
+        """The layout of the reference cells (cells x dim, run_umap's positions), kept on the device with the index."""
+        self._ctx.knn_index_set_layout(np.asarray(layout, dtype=np.float64).T)
+        self.has_layout = True
+
+    def project(self, query, a, b, n_neighbors=20, n_probe=None, n_epochs=None, alpha0=0.25, neg_rate=5, seed=42, query_batch=0):
+        """Context.knn_index_project of the query cells (cells x factors): they are drawn in the reference's layout; a query
+        that comes back with fewer neighbours than asked for raises ValueError naming n_probe, as map does."""
+        out = self._ctx.knn_index_project(np.asarray(query, dtype=np.float64).T, a, b, n_neighbors, n_probe, n_epochs, alpha0, neg_rate, seed,
+                                          query_batch)
+        _refuse_short("ReferenceIndex.project", out["idx"])
         return out
 
     def info(self):
@@ -1636,16 +1653,27 @@ def transfer_values(idx, dist, values, weighting="distance"):
     return _transfer(idx, dist, None, None, (V[:, None] if V.ndim == 1 else V).T, weighting)["values"]
 
 
-def map_query(A, w, index, L1=0.01, L2=0, n_neighbors=20, n_probe=None, weighting="distance"):
+def map_query(A, w, index, L1=0.01, L2=0, n_neighbors=20, n_probe=None, weighting="distance", layout=False, a=None, b=None, n_epochs=None,
+              alpha0=0.25, neg_rate=5, seed=42):
     """New cells mapped onto a reference: project_model(A, w, L1, L2) and its h handed to index.map (a ReferenceIndex built on
     the reference's embedding in the same factor order).  A: anything project_model takes, native(...) included.  Returns
-    {"h", "d", "idx", "dist", "predicted", "score", "scores", "values"}; a query that comes back short raises ValueError."""
+    {"h", "d", "idx", "dist", "predicted", "score", "scores", "values"}; a query that comes back short raises ValueError.
+    layout=True (the index holds a layout; a, b the curve of the reference's run_umap, or a UmapModel as `a`) adds "layout"
+    and "layout_init": index.project of the same h, the query cells drawn in the reference's picture."""
     if not isinstance(index, ReferenceIndex):
         raise ValueError("index must be a ReferenceIndex")
     knn_weighting(weighting)
     m = project_model(A, w, L1, L2)
     out = index.map(np.asarray(m["h"]).T, n_neighbors, n_probe, weighting)
-    return {"h": m["h"], "d": m["d"], **out}
+    res = {"h": m["h"], "d": m["d"], **out}
+    if layout:
+        if isinstance(a, UmapModel):
+            a, b = a.a, a.b
+        if a is None or b is None:
+            raise ValueError("map_query: layout=True needs the curve (a, b) of the reference's layout")
+        pr = index.project(np.asarray(m["h"]).T, a, b, n_neighbors, n_probe, n_epochs, alpha0, neg_rate, seed)
+        res["layout"], res["layout_init"] = pr["layout"], pr["layout_init"]
+    return res
 
 
 # ---------------------------------------------------------------------------
@@ -1877,7 +1905,7 @@ def _umap_init(E, n_components, init, seed):
 
 def run_umap(embedding, n_neighbors=30, n_components=2, min_dist=0.3, spread=1.0, n_epochs=None, learning_rate=1.0,
              negative_sample_rate=5, init="pca", seed=42, dims=None, return_graph=False, metric="euclidean", nn_method="exact", n_lists=None,
-             n_probe=None):
+             n_probe=None, return_model=False):
     """The numeric steps of Seurat's RunUMAP(reduction = "nmf") on the device: exact k-NN, the fuzzy neighbour graph, and
     the synchronous layout (include/singlet_hip.h, "Layout").  `embedding` is k x n (R's orientation, one column per cell, as
     knn takes it) or a Context with a fit, whose H is searched where it lies; dims: 0-based rows.  n_epochs None: 500 up to
@@ -1887,7 +1915,8 @@ def run_umap(embedding, n_neighbors=30, n_components=2, min_dist=0.3, spread=1.0
     (positions, graph).  metric: "euclidean", "cosine" or "correlation", the metric of the neighbour search as knn takes it
     (the graph is then built on 1 - cos).  Seurat's RunUMAP defaults to metric = "cosine"; ours stays "euclidean", so that
     existing results stay.  nn_method "ivf", n_lists, n_probe: the approximate search, as find_neighbors takes them (a short
-    result raises ValueError naming n_probe).  No parity of coordinates with uwot or umap-learn is claimed."""
+    result raises ValueError naming n_probe).  return_model: also a UmapModel, what project_umap needs to draw new cells into
+    this picture (returned last).  No parity of coordinates with uwot or umap-learn is claimed."""
     from .context import Context
     mkw = {**_metric_kw(metric), **_nn_method_kw(nn_method, n_lists, n_probe)}
     if isinstance(embedding, Context):
@@ -1914,7 +1943,115 @@ def run_umap(embedding, n_neighbors=30, n_components=2, min_dist=0.3, spread=1.0
     _refuse_short("run_umap", idx)
     G = fuzzy_simplicial_set(idx, dist)
     Y = umap_layout(G, Y0, a, b, n_epochs, learning_rate, negative_sample_rate, int(seed) & (2**64 - 1))
+    if return_model:
+        model = UmapModel(a, b, int(n_neighbors), metric, None if d0 is None else d0.astype(np.int64), Y, float(learning_rate),
+                          int(negative_sample_rate), int(seed) & (2**64 - 1))
+        return (Y, G, model) if return_graph else (Y, model)
     return (Y, G) if return_graph else Y
+
+
+# ---------------------------------------------------------------------------
+# Layout transform (Seurat's ProjectUMAP / MapQuery picture, umap-learn's transform; the rules are this library's own:
+# include/singlet_hip.h, "Layout transform")
+# ---------------------------------------------------------------------------
+class UmapModel:
+    """What a later projection needs of a run_umap(..., return_model=True): the curve (a, b), n_neighbors, the metric and the
+    dims (0-based rows of the embedding, or None) of its neighbour search, the positions (n x n_components), the learning
+    rate, the negative sample rate and the seed."""
+
+    def __init__(self, a, b, n_neighbors, metric, dims, positions, learning_rate=1.0, negative_sample_rate=5, seed=42):
+        self.a, self.b, self.n_neighbors, self.metric, self.dims = float(a), float(b), int(n_neighbors), metric, dims
+        self.positions = np.ascontiguousarray(positions, dtype=np.float64)
+        self.learning_rate, self.negative_sample_rate, self.seed = float(learning_rate), int(negative_sample_rate), int(seed)
+
+
+def _transform_epochs(n_query, n_epochs):
+    """umap-learn's transform: 100 epochs up to 10 000 queries, 30 above."""
+    return int(n_epochs) if n_epochs is not None else (100 if n_query <= 10000 else 30)
+
+
+def _query_lists(idx, second, what, name):
+    from ._marshal import knn_lists_in
+    i, d, nq, K = knn_lists_in(idx, second)
+    if not 1 <= K <= 256:
+        raise ValueError("%s: idx and %s must be n_query x K with K in [1, 256]" % (what, name))
+    return i, d, nq, K
+
+
+def _positions(Y, rows, what, name):
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    if Y.ndim != 2 or (rows is not None and Y.shape[0] != rows) or not 1 <= Y.shape[1] <= 8:
+        raise ValueError("%s: %s must be %s x dim with dim in [1, 8]" % (what, name, "n" if rows is None else rows))
+    return Y
+
+
+def fuzzy_query(idx, dist, n_ref):
+    """sgl_c_fuzzy_query: the memberships of query cells' neighbour lists against a reference of n_ref cells (idx, dist:
+    n_query x K as the searches return them, padding -1 / +Inf behind the valid slots) -> (W n_query x K, rho, sigma)."""
+    i, d, nq, K = _query_lists(idx, dist, "fuzzy_query", "dist")
+    W, rho, sigma = np.zeros((max(nq, 1), K)), np.zeros(max(nq, 1)), np.zeros(max(nq, 1))
+    check(_lib.load().sgl_c_fuzzy_query(ptr(i, i32p), ptr(d, f64p), nq, K, int(n_ref), ptr(W, f64p), ptr(rho, f64p), ptr(sigma, f64p)))
+    return W[:nq], rho[:nq], sigma[:nq]
+
+
+def umap_transform(idx, dist, layout, a, b, n_epochs=None, alpha0=0.25, neg_rate=5, seed=42, query_offset=0, return_init=False):
+    """sgl_c_umap_transform: query cells placed in the fixed layout of the reference (n_ref x dim) from their neighbour lists
+    against it (idx, dist: n_query x K) -> their positions (n_query x dim); with return_init (start, positions).  n_epochs
+    None: 100 up to 10 000 queries, 30 above.  query_offset: the global index of the first query, with which a slice of a
+    larger call reproduces that call's rows."""
+    i, d, nq, K = _query_lists(idx, dist, "umap_transform", "dist")
+    Yr = _positions(layout, None, "umap_transform", "layout")
+    Y0, Y = np.empty((max(nq, 1), Yr.shape[1])), np.empty((max(nq, 1), Yr.shape[1]))
+    check(_lib.load().sgl_c_umap_transform(ptr(i, i32p), ptr(d, f64p), nq, K, ptr(Yr, f64p), Yr.shape[1], Yr.shape[0], float(a), float(b),
+                                           _transform_epochs(nq, n_epochs), float(alpha0), int(neg_rate), int(seed) & (2**64 - 1),
+                                           int(query_offset), ptr(Y0, f64p), ptr(Y, f64p)))
+    return (Y0[:nq], Y[:nq]) if return_init else Y[:nq]
+
+
+def op_umap_transform_epochs(idx, W, layout, Y, a, b, n_epochs, t_first, t_last, alpha0=0.25, neg_rate=5, seed=42, query_offset=0):
+    """sgl_op_umap_transform_epochs: the epochs t_first .. t_last (1-based) of a transform of n_epochs epochs from the
+    caller's memberships W (n_query x K) and positions Y (n_query x dim) -> the new positions."""
+    i, Wc, nq, K = _query_lists(idx, W, "op_umap_transform_epochs", "W")
+    Yr = _positions(layout, None, "op_umap_transform_epochs", "layout")
+    Yin = _positions(Y, nq, "op_umap_transform_epochs", "Y")
+    if Yin.shape[1] != Yr.shape[1]:
+        raise ValueError("op_umap_transform_epochs: Y and layout must have the same dim")
+    out = np.empty((max(nq, 1), Yr.shape[1]))
+    check(_lib.load().sgl_op_umap_transform_epochs(ptr(i, i32p), ptr(Wc, f64p), nq, K, ptr(Yr, f64p), Yr.shape[1], Yr.shape[0],
+                                                   ptr(Yin if nq else out, f64p), float(a), float(b), int(n_epochs), float(alpha0), int(neg_rate),
+                                                   int(seed) & (2**64 - 1), int(query_offset), int(t_first), int(t_last), ptr(out, f64p)))
+    return out[:nq]
+
+
+def umap_transform_info():
+    """sgl_umap_transform_info: what the last layout transform of this process ran."""
+    out = np.zeros(4, dtype=np.int64)
+    check(_lib.load().sgl_umap_transform_info(ptr(out, _lib.i64p)))
+    return dict(zip(("instance", "widest_list", "empty_queries", "launches"), (int(v) for v in out)))
+
+
+def project_umap(model, index_or_reference_embedding, query_embedding, n_epochs=None, n_probe=None, return_init=False, query_batch=0):
+    """The ProjectUMAP mirror: query cells (cells x factors) drawn in the picture of a run_umap(..., return_model=True).
+    `index_or_reference_embedding`: a ReferenceIndex on the reference's embedding (it receives the model's positions as its
+    layout when it holds none), or the reference embedding itself (cells x factors), on which an exact index is built for the
+    call under the model's metric and dims.  alpha0 is a quarter of the model's learning rate.  -> positions (n_query x
+    n_components); with return_init (start, positions)."""
+    if not isinstance(model, UmapModel):
+        raise ValueError("project_umap: model must come from run_umap(..., return_model=True)")
+    own = not isinstance(index_or_reference_embedding, ReferenceIndex)
+    index = index_or_reference_embedding
+    if own:
+        dims1 = None if model.dims is None else np.asarray(model.dims) + 1
+        index = ReferenceIndex(index_or_reference_embedding, dims=dims1, metric=model.metric, method="exact", layout=model.positions)
+    try:
+        if not index.has_layout:
+            index.set_layout(model.positions)
+        out = index.project(query_embedding, model.a, model.b, model.n_neighbors, n_probe, n_epochs, 0.25 * model.learning_rate,
+                            model.negative_sample_rate, model.seed, query_batch)
+    finally:
+        if own:
+            index.close()
+    return (out["layout_init"], out["layout"]) if return_init else out["layout"]
 
 
 # ---------------------------------------------------------------------------

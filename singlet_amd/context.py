@@ -684,6 +684,7 @@ class Context(_Handle):
         L = knn_ivf_shape(n_ref, n_lists, None)[0] if ivf else 0
         check(self._L.sgl_knn_index_build(self._h, ptr(Rb, f64p), int(k), int(n_ref), ptr(d, i32p), nd, code, int(ivf), L, int(n_iter)))
         self._knn_annotations = [0, 0]
+        self._knn_layout_dim = 0
 
     def _knn_index_query(self, query, n_probe):
         """(the k x n_query image of the query, n_query, n_probe as the library takes it) for a call against the index."""
@@ -741,10 +742,40 @@ class Context(_Handle):
                             nq, G > 0, G, nv)
         return {"idx": idx, "dist": dist, **out}
 
+    def knn_index_set_layout(self, layout):
+        """Puts the layout of the reference cells (dim x n_ref, R's orientation: one column per reference cell; finite, dim in
+        [1, 8]) onto the index, resident with it (sgl_knn_index_set_layout).  A second call replaces it; a rebuild and
+        knn_index_drop release it."""
+        Yb = colmajor(layout, "layout must be a dim x n_ref matrix")
+        n_ref = self.knn_index_info()["n_ref"]
+        if n_ref and Yb.shape[0] != n_ref:
+            raise ValueError("layout has %d columns, the index has %d references" % (Yb.shape[0], n_ref))
+        check(self._L.sgl_knn_index_set_layout(self._h, ptr(Yb, f64p), int(Yb.shape[1])))
+        self._knn_layout_dim = int(Yb.shape[1])
+
+    def knn_index_project(self, query, a, b, n_neighbors=20, n_probe=None, n_epochs=None, alpha0=0.25, neg_rate=5, seed=42, query_batch=0):
+        """One search against the index with the memberships, the start and the layout transform of every batch run on the
+        device (sgl_knn_index_project): {"idx", "dist"} as knn_index_search, "layout_init" (the start) and "layout" (after
+        n_epochs epochs), each n_query x dim.  Bit for bit knn_index_search followed by umap_transform.  n_epochs None: 100
+        up to 10 000 queries, 30 above."""
+        Qb, nq, n_probe = self._knn_index_query(query, n_probe)
+        K = int(n_neighbors)
+        dim = getattr(self, "_knn_layout_dim", 0)
+        shape = (nq, K) if 1 <= K <= 256 else (1, 1)   # outside it the library refuses before it writes
+        idx, dist = np.empty(shape, dtype=np.int32), np.empty(shape)
+        Y0, Y = np.empty((max(nq, 1), max(dim, 1))), np.empty((max(nq, 1), max(dim, 1)))
+        if n_epochs is None:
+            n_epochs = 100 if nq <= 10000 else 30
+        check(self._L.sgl_knn_index_project(self._h, ptr(Qb, f64p), nq, K, n_probe, int(query_batch), float(a), float(b), int(n_epochs),
+                                            float(alpha0), int(neg_rate), int(seed) & (2**64 - 1), ptr(idx, i32p), ptr(dist, f64p),
+                                            ptr(Y0, f64p), ptr(Y, f64p)))
+        return {"idx": idx, "dist": dist, "layout_init": Y0[:nq], "layout": Y[:nq]}
+
     def knn_index_drop(self):
         """Releases the index and its annotations (sgl_knn_index_drop); nothing happens without one."""
         check(self._L.sgl_knn_index_drop(self._h))
         self._knn_annotations = [0, 0]
+        self._knn_layout_dim = 0
 
     def knn_index_info(self):
         """The index of this context (sgl_knn_index_info): {"present" (0 / 1), "method" (0 exact, 1 ivf), "metric", "k",

@@ -27,6 +27,7 @@
 #include "knn_ivf_host.h"
 #include "knn_transfer_host.h"
 #include "knn_device.h"
+#include "umap_transform_dev.h"
 
 #include <chrono>
 #include <cmath>
@@ -772,6 +773,8 @@ struct KnnIndex {
     DevBuf<int32_t> labels;   // int32[n_ref] in [-1, n_classes)
     DevBuf<double> V;         // n_values x n_ref
     int32_t n_classes = 0, n_values = 0;
+    DevBuf<double> Y;         // the layout of the reference cells, ydim x n_ref (sgl_knn_index_set_layout)
+    int32_t ydim = 0;
     int64_t searches = 0, last_queries = 0, last_short = 0, instance = 0;
 
     int64_t bytes() const {
@@ -780,6 +783,7 @@ struct KnnIndex {
         if (dims.p) b += 4 * (int64_t)nd;
         if (labels.p) b += 4 * n_ref;
         if (V.p) b += 8 * (int64_t)n_values * n_ref;
+        if (Y.p) b += 8 * (int64_t)ydim * n_ref;
         return b;
     }
 };
@@ -1060,6 +1064,90 @@ extern "C" int sgl_knn_index_map(sgl_ctx* c, const double* Q, int64_t n_query, i
         const int rc = ivf_drain(c, body(), who);
         if (rc != SGL_OK) return rc;
     }
+    index_served(ix, n_query, short_queries);
+    return SGL_OK;
+}
+
+// ---- the layout on the index, and query cells placed in it (include/singlet_hip.h, "Layout transform") -------------------
+extern "C" int sgl_knn_index_set_layout(sgl_ctx* c, const double* Yref, int32_t dim) {
+    const char* who = "sgl_knn_index_set_layout";
+    if (c == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    KnnIndex* ix = index_of(c, who);
+    if (!ix) return SGL_ESTATE;
+    if (!Yref) { sgl_set_error("%s: Yref is NULL", who); return SGL_EINVAL; }
+    if (dim < 1 || dim > 8) { sgl_set_error("%s: dim = %d is outside [1, 8]", who, dim); return SGL_EINVAL; }
+    DevBuf<double> val;
+    DevBuf<unsigned long long> first;
+    auto stage = [&]() -> int {
+        SGLCHK(val.alloc((size_t)dim * (size_t)ix->n_ref));
+        SGLCHK(first.alloc(1));
+        HIPCHK(hipMemcpyAsync(val.p, Yref, sizeof(double) * (size_t)dim * (size_t)ix->n_ref, hipMemcpyHostToDevice, c->stream));
+        SGLCHK(sgl_knn_check_finite(c, who, "Yref", val.p, dim, ix->n_ref, first.p));
+        return SGL_OK;
+    };
+    const int rc = ivf_drain(c, stage(), who);
+    if (rc != SGL_OK) return rc;   // the index keeps what it had
+    take(ix->Y, val);
+    ix->ydim = dim;
+    return SGL_OK;                 // val releases what it replaced
+}
+
+extern "C" int sgl_knn_index_project(sgl_ctx* c, const double* Q, int64_t n_query, int32_t n_neighbors, int32_t n_probe, int64_t query_batch,
+                                     double a, double b, int32_t n_epochs, double alpha0, int32_t neg_rate, uint64_t seed, int32_t* idx_out,
+                                     double* dist_out, double* Y0_out, double* Y_out) {
+    const char* who = "sgl_knn_index_project";
+    if (c == nullptr) { sgl_set_error("null context"); return SGL_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    KnnIndex* ix = index_of(c, who);
+    if (!ix) return SGL_ESTATE;
+    if (!ix->Y.p) {
+        sgl_set_error("%s: the index holds no layout (call sgl_knn_index_set_layout)", who);
+        return SGL_ESTATE;
+    }
+    SGLCHK(index_search_args(who, ix, Q, n_query, n_neighbors, n_probe, query_batch));
+    if (query_batch < 0) { sgl_set_error("%s: query_batch = %lld is negative", who, (long long)query_batch); return SGL_EINVAL; }
+    const int32_t dim = ix->ydim;
+    SGLCHK(sgl_umap_transform_args(who, n_query, n_neighbors, ix->n_ref, dim, a, b, n_epochs, alpha0, neg_rate));
+    int64_t short_queries = 0, launches = 0;
+    unsigned long long hstats[2] = {0, 0};
+    if (n_query > 0) {
+        // the batch: the caller's, or as many queries as the map's budget keeps (the lists, the memberships, two positions)
+        const int64_t per_query = knn_transfer_query_bytes(ix->method == 1 ? n_probe : KNN_MAX_SEGMENTS, n_neighbors, n_neighbors, 2 * dim);
+        const int64_t batch = query_batch > 0 ? std::min(query_batch, n_query) : knn_transfer_batch(n_query, per_query, KNN_TRANSFER_SCRATCH_BYTES);
+        IvfBuffers B;
+        DevBuf<double> W, Y0, Y;
+        DevBuf<unsigned long long> stats;
+        int64_t cap = 0;
+        auto body = [&]() -> int {
+            SGLCHK(stats.alloc(2));
+            HIPCHK(hipMemsetAsync(stats.p, 0, 2 * sizeof(unsigned long long), c->stream));
+            // memberships, start and transform of a batch on the device: the neighbour lists do not travel to the host and back
+            const IvfAfterBatch after = [&](int64_t q0, int64_t nb, const int32_t* idx_dev, const double* dist_dev) -> int {
+                if (nb > cap) {
+                    SGLCHK(W.alloc((size_t)n_neighbors * (size_t)nb));
+                    SGLCHK(Y0.alloc((size_t)dim * (size_t)nb));
+                    SGLCHK(Y.alloc((size_t)dim * (size_t)nb));
+                    cap = nb;
+                }
+                int64_t issued = 0;
+                SGLCHK(sgl_umap_transform_dev(c->stream, idx_dev, dist_dev, n_neighbors, nb, ix->Y.p, dim, ix->n_ref, a, b, n_epochs, alpha0,
+                                              neg_rate, seed, q0, W.p, Y0_out ? Y0.p : nullptr, Y.p, stats.p, &issued));
+                launches += issued;
+                if (Y0_out) HIPCHK(hipMemcpyAsync(Y0_out + q0 * dim, Y0.p, sizeof(double) * (size_t)dim * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+                if (Y_out) HIPCHK(hipMemcpyAsync(Y_out + q0 * dim, Y.p, sizeof(double) * (size_t)dim * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipStreamSynchronize(c->stream));   // the scratch is free for the next batch, a fault surfaces here
+                return SGL_OK;
+            };
+            SGLCHK(index_query(c, who, ix, B, Q, n_query, n_neighbors, n_probe, batch, batch, idx_out, dist_out, after, &short_queries));
+            HIPCHK(hipMemcpyAsync(hstats, stats.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));
+            return SGL_OK;
+        };
+        const int rc = ivf_drain(c, body(), who);
+        if (rc != SGL_OK) return rc;
+    }
+    sgl_umap_transform_note(dim, b, (int64_t)hstats[0], (int64_t)hstats[1], launches);
     index_served(ix, n_query, short_queries);
     return SGL_OK;
 }
