@@ -478,6 +478,49 @@ SGL_API int sgl_rasterize_rowwise(sgl_ctx* ctx, int64_t n);
  *    after a failed upload. */
 SGL_API int sgl_subset(sgl_ctx* ctx, const int32_t* rows, int64_t n_rows, const int32_t* cols, int64_t n_cols);
 
+/* Simulated doublets: the first step of every doublet detector of the Scrublet kind (Wolock, Lopez & Klein 2019; also
+ * DoubletFinder, scDblFinder) -- artificial doublets as the sums of the raw counts of pairs of cells -- made on the device
+ * from the resident counts, so that no matrix of two or three times the original's size is merged on the host and
+ * uploaded.  The reference's package has no such function; the rules below are this library's own, in full;
+ * tests/doublet_restatement.py restates them in numpy.  The simulation needs COUNTS, and sgl_log_normalize rewrites the
+ * matrix in place, so the call reads one context and writes another.
+ *
+ * sgl_simulate_doublets: the resident matrix of dst becomes S, nrow x n_sim, S[:, s] = A[:, parent_a[s]] + A[:, parent_b[s]],
+ * A the resident CSC image of src, which is only read.
+ *  - stored rows: the stored rows of column s are the union of the two parents' stored rows, ascending.  A row stored in
+ *    one parent carries that value's bits; a row stored in both carries x_a + x_b, ONE IEEE addition (commutative: the order
+ *    of the parents changes nothing).  An explicit zero stays stored; a sum that cancels stays stored as the zero it rounds
+ *    to.  parent_a[s] == parent_b[s] is allowed and gives 2 x.  Parents may repeat and come in any order.
+ *  - the image: dst ends up exactly as sgl_upload_csc(dst, S, At = NULL) would leave it -- both orientations, the
+ *    transposed one through the device transpose, 64-bit offsets, cell_offset = 0, ncells_total = n_sim.  A fit of dst and
+ *    everything that hangs on its matrix (entry streams, mask lists, graph, links, a dense copy) is dropped, as by any
+ *    other door.  src keeps its matrix, its fit and its bits.
+ *  - a non-finite sum (an overflow: the parents' values are finite) is refused as sgl_rasterize_rowwise refuses one:
+ *    SGL_EINVAL, dst is left without a matrix, and the message names the lowest simulated column that holds one.
+ *  - device and streams: both contexts must be on one device.  The kernels run on dst's stream.  First dst's stream waits
+ *    for an event recorded on src's stream (what src still has queued -- a sgl_log_normalize, a sgl_synth_csc -- ends
+ *    before its matrix is read); at the end src's stream waits for an event recorded on dst's stream, so a
+ *    sgl_log_normalize of src issued right after cannot overtake the read.  The call returns with dst's stream
+ *    synchronised (it needs the entry count of S on the host), on the private stream and on a caller's.
+ *  - refused with BOTH contexts untouched: SGL_ESTATE for src == dst, src without a matrix, either context a member of a
+ *    team or with an all-reduce hook, either context holding a shard (cell_offset != 0 or ncells_total != ncol);
+ *    SGL_EINVAL for contexts on different devices, n_sim < 1 or > INT32_MAX, a NULL list, a parent outside [0, ncol) --
+ *    the message names the list, the position and the value of the first offender (position by position, parent_a before
+ *    parent_b).  The lists are checked completely before anything is freed.
+ *  - after that only an allocation or a HIP call can fail, and then dst holds no matrix (sgl_dims: 0 / 0 / 0), as after a
+ *    failed upload.
+ *  - paths: one wave per simulated column, no sort, no atomics on the data, vector stores only.  Entry j of a parent
+ *    goes to slot j + (entries of the other parent below its row) - (rows among them stored in both); the a-side writes
+ *    the sum at a shared row, the b-side skips it.  A pair whose la + lb row indices fit 4096 is staged in LDS and
+ *    searched there (the LDS path), a longer one (a dense upload has columns of nrow entries) is searched in global
+ *    memory (the long path).  Both give the same bits.
+ *  - there is NO team form and NO R shim entry. */
+SGL_API int sgl_simulate_doublets(sgl_ctx* src, sgl_ctx* dst, const int32_t* parent_a, const int32_t* parent_b, int64_t n_sim);
+/* What the last sgl_simulate_doublets INTO this context, or the last sgl_op_pair_columns on it, ran: out[0] the pairs merged
+ * on the LDS path, out[1] on the long path, out[2] the stored entries of S, out[3] the rows stored in both parents, summed
+ * over the pairs (out[2] + out[3] = the parents' entries together). */
+SGL_API int sgl_doublets_info(sgl_ctx* ctx, int64_t out[4]);
+
 /* Start a fit at rank k.  w_init: k x nrow host array, or NULL to fill W on
  * the device with the synthetic init ((rand_{S+2}(f,g) >> 11) + 0.5) * 2^-53.
  * h = 0, d = 1 as in src/singlet.cpp:639-641.
@@ -1705,6 +1748,16 @@ SGL_API int sgl_op_cell_ranks(sgl_ctx* ctx, int32_t max_rank, int64_t lds_cap, i
 SGL_API int sgl_op_signature_scores(sgl_ctx* ctx, const int64_t* set_ptr, const int32_t* set_genes, int32_t n_sets, int32_t max_rank,
                                     int64_t lds_cap, int64_t max_batch_entries, int32_t pass_sets, uint64_t* rank2_out,
                                     double* score_out);
+/* The merge of sgl_simulate_doublets alone (the rules are stated there), over the matrix of ctx, which is only read: S comes
+ * back as CSC slots -- p_out n_sim + 1 offsets (int64), i_out / x_out p_out[n_sim] entries.  With i_out == NULL and
+ * x_out == NULL only p_out is written: the caller sizes the second call from p_out[n_sim] (the two-call pattern of the
+ * neighbour graphs).  lds_cap forces the path split: a pair goes to the LDS path when la + lb <= lds_cap; 0 is the default
+ * of 4096, a larger value is the default, a negative one SGL_EINVAL; the result does not depend on it, and
+ * sgl_doublets_info says what ran.  The refusals of sgl_simulate_doublets that concern one context apply (SGL_ESTATE: no
+ * matrix, a team member, a hook, a shard; SGL_EINVAL: n_sim, a NULL list, a parent out of range, NULL p_out, one of i_out /
+ * x_out without the other).  A non-finite sum is NOT refused here: it comes back as it is. */
+SGL_API int sgl_op_pair_columns(sgl_ctx* ctx, const int32_t* parent_a, const int32_t* parent_b, int64_t n_sim, int64_t lds_cap,
+                                int64_t* p_out, int32_t* i_out, double* x_out);
 /* The stages of sgl_c_gsea, one at a time (the rules and the refusals are stated there).  They use the context's device,
  * stream and pool only: no resident matrix is needed, nothing of the context changes but what sgl_gsea_info reports.
  *  - sgl_op_gsea_es: the observed scores of the given sets under all three score types, each n_sets x k column-major; any

@@ -31,6 +31,8 @@ names, argument order, defaults and return fields:
                                         null in place of fgseaMultilevel (include/singlet_hip.h, "Gene set enrichment")
   score_signatures                      UCell's ScoreSignatures_UCell: the rank-based score of gene signatures in every cell
                                         (include/singlet_hip.h, "Signature scores")
+  score_doublets                        no R counterpart in the reference (it hands the object to Seurat): the scheme of Scrublet
+                                        with the simulator on the device (include/singlet_hip.h, "Simulated doublets")
   find_all_markers / find_markers       Seurat::FindAllMarkers / FindMarkers(test.use = "wilcox") under the rules stated in
                                         include/singlet_hip.h, "Marker genes" (the filters are applied after the test)
 
@@ -2252,6 +2254,227 @@ def score_signatures(A, signatures, gene_names=None, max_rank=1500, w_neg=1.0, m
     for t, j in enumerate(has_neg):
         scores[:, j] = np.maximum(0.0, scores[:, j] - float(w_neg) * sc[S + t])
     return {"scores": scores, "names": names, "dropped": dropped}
+
+
+# ---------------------------------------------------------------------------
+# Doublet scores (the scheme of Scrublet, Wolock, Lopez & Klein 2019; the rules are this library's own:
+# include/singlet_hip.h, "Simulated doublets", DESIGN.md "Doublet scores")
+# ---------------------------------------------------------------------------
+DOUBLET_KNN_LIMIT = 256   # the neighbours one search returns (sgl_knn)
+
+
+def doublet_parents(n_obs, n_sim, seed=0):
+    """(parent_a, parent_b), int32, n_sim each: a = rng.integers(0, n_obs) and b = (a + 1 + rng.integers(0, n_obs - 1)) % n_obs
+    from np.random.default_rng(seed), so the parents of a simulated cell are two DIFFERENT observed cells."""
+    n_obs, n_sim = int(n_obs), int(n_sim)
+    if n_obs < 2 or n_sim < 1:
+        raise ValueError("doublet_parents: at least 2 observed cells and 1 simulated cell are needed")
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, n_obs, size=n_sim)
+    b = (a + 1 + rng.integers(0, n_obs - 1, size=n_sim)) % n_obs
+    return a.astype(np.int32), b.astype(np.int32)
+
+
+def doublet_scores(idx, n_obs, n_sim, expected_rate=0.1, stdev_rate=0.02):
+    """Scrublet's doublet likelihood of every cell of the joint embedding [observed | simulated] from its neighbour lists:
+    idx is (n_obs + n_sim) x (k_adj + 1), the search of the joint embedding against itself.  A cell's own index is removed from
+    its list wherever it stands; when it is absent (duplicates pushed it out) the last entry is removed.  nd = the remaining
+    entries >= n_obs (simulated neighbours); q = (nd + 1) / (k_adj + 2); r = n_sim / n_obs; rho = expected_rate;
+      Ld = q rho / r / (1 - rho - q (1 - rho - rho / r));  se_q = sqrt(q (1 - q) / (k_adj + 3));
+      se_Ld = q rho / r / (1 - rho - q (1 - rho - rho / r))^2 sqrt((se_q / q (1 - rho))^2 + (stdev_rate / rho (1 - q))^2).
+    Host arithmetic.  Returns {"nd", "score", "se"} for the observed and {"sim_nd", "sim_score", "sim_se"} for the simulated."""
+    idx = np.asarray(idx)
+    n_obs, n_sim = int(n_obs), int(n_sim)
+    if idx.ndim != 2 or idx.shape[0] != n_obs + n_sim or idx.shape[1] < 2 or n_obs < 1 or n_sim < 1:
+        raise ValueError("doublet_scores: idx must be (n_obs + n_sim) x (k_adj + 1) with k_adj >= 1")
+    rho, se_rho = float(expected_rate), float(stdev_rate)
+    if not 0.0 < rho < 1.0 or not se_rho >= 0.0:
+        raise ValueError("doublet_scores: expected_rate must lie in (0, 1) and stdev_rate must not be negative")
+    n, k1 = idx.shape
+    k_adj = k1 - 1
+    own = idx == np.arange(n)[:, None]
+    drop = np.where(own.any(axis=1), own.argmax(axis=1), k1 - 1)
+    keep = np.ones((n, k1), dtype=bool)
+    keep[np.arange(n), drop] = False
+    nd = ((idx >= n_obs) & keep).sum(axis=1).astype(np.int64)
+    q = (nd + 1) / float(k_adj + 2)
+    r = n_sim / float(n_obs)
+    den = 1 - rho - q * (1 - rho - rho / r)
+    Ld = q * rho / r / den
+    se_q = np.sqrt(q * (1 - q) / (k_adj + 3))
+    se_Ld = q * rho / r / den ** 2 * np.sqrt((se_q / q * (1 - rho)) ** 2 + (se_rho / rho * (1 - q)) ** 2)
+    return {"nd": nd[:n_obs], "score": Ld[:n_obs], "se": se_Ld[:n_obs], "sim_nd": nd[n_obs:], "sim_score": Ld[n_obs:], "sim_se": se_Ld[n_obs:]}
+
+
+def _local_maxima(h):
+    """Bins above their left neighbour and not below their right one, with empty bins beyond both ends: one per plateau, none
+    among empty bins."""
+    left, right = np.concatenate([[0.0], h[:-1]]), np.concatenate([h[1:], [0.0]])
+    return np.flatnonzero((h > left) & (h >= right))
+
+
+def doublet_threshold(sim_scores, bins=100):
+    """The score that separates the two humps of the simulated cells' scores (doublets of two cell states against doublets
+    within one): a histogram of `bins` bins on [0, max], smoothed by a 3-bin mean (empty bins beyond the ends) until at most
+    two local maxima remain, at most 10 000 rounds; the threshold is the centre of the lowest bin between the two maxima (the
+    first of several).  ValueError when two maxima are not there: the caller then passes a threshold."""
+    s = np.asarray(sim_scores, dtype=np.float64).ravel()
+    bins = int(bins)
+    if s.size < 1 or bins < 3 or not np.all(np.isfinite(s)) or s.min() < 0 or not s.max() > 0:
+        raise ValueError("doublet_threshold: needs finite non-negative scores with a positive maximum and at least 3 bins")
+    top = float(s.max())
+    h = np.histogram(s, bins=bins, range=(0.0, top))[0].astype(np.float64)
+    peaks = _local_maxima(h)
+    rounds = 0
+    while peaks.size > 2 and rounds < 10000:
+        h = (np.concatenate([[0.0], h[:-1]]) + h + np.concatenate([h[1:], [0.0]])) / 3.0
+        peaks = _local_maxima(h)
+        rounds += 1
+    if peaks.size != 2:
+        raise ValueError("doublet_threshold: the simulated scores show %d local maxima, not two; pass a threshold" % peaks.size)
+    lo = int(peaks[0]) + 1 + int(np.argmin(h[peaks[0] + 1:peaks[1]]))
+    return (lo + 0.5) * top / bins
+
+
+def _whole(v, lo, what):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer, float, np.floating)) or int(v) != v or int(v) < lo:
+        raise ValueError("score_doublets: %s must be a whole number of at least %d" % (what, lo))
+    return int(v)
+
+
+def score_doublets(A, w=None, rank=None, features=None, sim_ratio=2.0, n_neighbors=None, expected_rate=0.1, stdev_rate=0.02,
+                   threshold=None, metric="euclidean", nn_method="exact", seed=0, sim_batch=0, L1=0.01, L2=0, scale_factor=1e4,
+                   nfeatures=None, n_lists=None, n_probe=None, tol=1e-4, maxit=100, bins=100):
+    """Doublet scores of the cells of a genes x cells COUNT matrix by the scheme of Scrublet, with the NMF projection as the
+    reduction and every matrix step on the device.  A: anything RunNMF takes, native(...) included.
+      1. one context holds the counts; `features` (as subset() takes rows) or `nfeatures` (Context.variable_features on the
+         counts) selects the genes of the model;
+      2. w None: the model is fitted first, run_nmf at `rank` (tol, maxit, L1, L2, seed) on the normalised observed matrix,
+         and the counts are uploaded again; else w is the model (genes x k or k x genes, the selected genes in order);
+      3. doublet_parents(n_obs, round(sim_ratio n_obs), seed); a second context receives the simulated cells in batches of
+         sim_batch (0: all at once) through Context.simulate_doublets; each batch goes through log_normalize(scale_factor),
+         subset(rows), fit_init(k, scale(w)) and the H-update of a projection (step_h; the row scaling of project_run is
+         left out: it is taken over the cells of a batch, so it would tie a cell's coordinates to its batch and put the
+         observed and the simulated cells on different scales);
+      4. the first context is normalised, subset and projected the same way;
+      5. Context.knn on [H_obs | H_sim] against itself with k_adj + 1 neighbours, k = n_neighbors (None:
+         round(0.5 sqrt(n_obs))), k_adj = round(k (1 + n_sim / n_obs)); doublet_scores; the threshold (None:
+         doublet_threshold of the simulated scores).
+    Every argument is checked before the first upload; k_adj + 1 above the search's limit of 256 is refused there.  Returns
+    {"scores", "se", "predicted", "threshold", "parent_a", "parent_b", "sim_scores", "sim_se", "nd", "sim_nd", "k_adj",
+    "h_obs", "h_sim" (cells x k), "w"}."""
+    from .context import Context
+    is_native = isinstance(A, NativeMatrix)
+    if not is_native:
+        A = as_dgCMatrix(A)
+    n_obs, nrow = int(A.ncol), int(A.nrow)
+    if n_obs < 2:
+        raise ValueError("score_doublets: at least 2 cells are needed")
+    if not (isinstance(sim_ratio, (int, float, np.integer, np.floating)) and math.isfinite(sim_ratio) and sim_ratio > 0):
+        raise ValueError("score_doublets: sim_ratio must be a positive number")
+    n_sim = int(round(float(sim_ratio) * n_obs))
+    if n_sim < 1 or n_sim > 2**31 - 1:
+        raise ValueError("score_doublets: sim_ratio = %r gives %d simulated cells: between 1 and 2^31 - 1 are possible" % (sim_ratio, n_sim))
+    k_nn = int(round(0.5 * math.sqrt(n_obs))) if n_neighbors is None else _whole(n_neighbors, 1, "n_neighbors")
+    k_nn = max(k_nn, 1)
+    k_adj = int(round(k_nn * (1 + n_sim / float(n_obs))))
+    if k_adj + 1 > DOUBLET_KNN_LIMIT or k_adj + 1 > n_obs + n_sim:
+        raise ValueError("score_doublets: sim_ratio = %r and n_neighbors = %d ask for k_adj + 1 = %d neighbours of %d joint cells; one "
+                         "search returns at most %d: lower sim_ratio or n_neighbors" % (sim_ratio, k_nn, k_adj + 1, n_obs + n_sim,
+                                                                                     DOUBLET_KNN_LIMIT))
+    rho, se_rho = float(expected_rate), float(stdev_rate)
+    if not 0.0 < rho < 1.0:
+        raise ValueError("score_doublets: expected_rate must lie in (0, 1)")
+    if not se_rho >= 0.0 or not math.isfinite(se_rho):
+        raise ValueError("score_doublets: stdev_rate must be a finite number, not negative")
+    if threshold is not None and not (isinstance(threshold, (int, float, np.integer, np.floating)) and math.isfinite(threshold)):
+        raise ValueError("score_doublets: threshold must be a finite number or None")
+    mkw = {**_metric_kw(metric), **_nn_method_kw(nn_method, n_lists, n_probe)}
+    sim_batch = _whole(sim_batch, 0, "sim_batch")
+    if not (isinstance(scale_factor, (int, float, np.integer, np.floating)) and math.isfinite(scale_factor) and scale_factor > 0):
+        raise ValueError("score_doublets: scale_factor must be a positive number")
+    L1f, L2f = float(_pair(L1)[1]), float(_pair(L2)[1])   # the H side of a pair, as run_nmf reads it
+    if not (0 <= L1f < 1) or L2f < 0:
+        raise ValueError("score_doublets: L1 must lie in [0, 1) and L2 must not be negative")
+    rows = None
+    if nfeatures is not None:
+        if features is not None:
+            raise ValueError("score_doublets: pass either features or nfeatures (the variable features selected here), not both")
+        nfeatures = _whole(nfeatures, 1, "nfeatures")
+        if nfeatures > nrow:
+            raise ValueError("score_doublets: nfeatures = %d is above the %d genes of A" % (nfeatures, nrow))
+    if features is not None:
+        rows = _subset_index([features] if isinstance(features, str) else features, nrow, A.Dimnames[0], "features")
+    m_sub = nfeatures if nfeatures is not None else (nrow if rows is None else int(np.asarray(rows).shape[0]))
+    if (w is None) == (rank is None):
+        raise ValueError("score_doublets: pass either w (a fitted model) or rank (the model is fitted here), not both and not neither")
+    if w is not None:
+        w = np.asarray(w, dtype=np.float64)
+        if w.ndim != 2 or (w.shape[0] != m_sub and w.shape[1] != m_sub):
+            raise ValueError("score_doublets: w must share an edge with the %d selected genes (got %r)" % (m_sub, w.shape))
+        if not np.all(np.isfinite(w)):
+            raise ValueError("score_doublets: w holds a non-finite value")
+        wb = np.ascontiguousarray(w if w.shape[0] == m_sub else w.T)   # (genes, k)
+        if not 1 <= wb.shape[1] <= 1024:
+            raise ValueError("score_doublets: the rank of w must lie in [1, 1024]")
+    else:
+        rank = _whole(rank, 1, "rank")
+        if rank > 1024:
+            raise ValueError("score_doublets: rank must lie in [1, 1024]")
+        _whole(maxit, 1, "maxit")
+    pa, pb = doublet_parents(n_obs, n_sim, seed)
+
+    def stage(c):
+        if is_native:
+            c.upload_native(A)
+        else:
+            c.upload(A, None)
+
+    def embed(c, ws):
+        c.log_normalize(float(scale_factor))
+        if rows is not None:
+            c.subset(rows=rows)
+        c.fit_init(ws.shape[1], ws)
+        c.step_h(L1f, L2f)
+        return c.get_factors(w=False, d=False)[2]
+
+    obs, sim = Context(0), None
+    try:
+        stage(obs)
+        if nfeatures is not None:
+            rows = obs.variable_features(nfeatures)["features"]
+        if w is None:
+            obs.log_normalize(float(scale_factor))
+            if rows is not None:
+                obs.subset(rows=rows)
+            model = run_nmf(None, rank, tol, maxit, False, L1, L2, 0, seed=seed, _fits=_ResidentFits(None, ctx=obs))
+            wb = np.ascontiguousarray(model["w"])
+            stage(obs)   # the simulation needs the counts again
+        ws, _ = obs.op_scale(wb)
+        sim = Context(0)
+        step = sim_batch if sim_batch else n_sim
+        parts = []
+        for s0 in range(0, n_sim, step):
+            obs.simulate_doublets(sim, pa[s0:s0 + step], pb[s0:s0 + step])
+            parts.append(np.array(embed(sim, ws)))
+        H_sim = np.concatenate(parts, axis=0)
+        H_obs = np.array(embed(obs, ws))
+        E = np.ascontiguousarray(np.concatenate([H_obs, H_sim], axis=0).T)
+        idx, _ = sim.knn(k_adj + 1, reference=E, **mkw)
+    finally:
+        obs.close()
+        if sim is not None:
+            sim.close()
+    _refuse_short("score_doublets", idx)
+    sc = doublet_scores(idx, n_obs, n_sim, rho, se_rho)
+    if threshold is None:
+        try:
+            threshold = doublet_threshold(sc["sim_score"], bins)
+        except ValueError as e:
+            raise ValueError("score_doublets: no automatic threshold (%s)" % e) from e
+    return {"scores": sc["score"], "se": sc["se"], "predicted": sc["score"] > float(threshold), "threshold": float(threshold),
+            "parent_a": pa, "parent_b": pb, "sim_scores": sc["sim_score"], "sim_se": sc["sim_se"], "nd": sc["nd"],
+            "sim_nd": sc["sim_nd"], "k_adj": k_adj, "h_obs": H_obs, "h_sim": H_sim, "w": wb}
 
 
 # ---------------------------------------------------------------------------

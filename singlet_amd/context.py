@@ -443,6 +443,44 @@ class Context(_Handle):
         check(self._L.sgl_subset(self._h, ptr(r, i32p), nr, ptr(cl, i32p), nc))
         self.k = 0
 
+    @staticmethod
+    def _parent_lists(parent_a, parent_b, who):
+        """The two parent lists as int32 arrays of one length (an empty list still goes down with an address: the library
+        refuses n_sim = 0 itself); None stays None, which the library refuses as a NULL list."""
+        out = []
+        for v in (parent_a, parent_b):
+            if v is None:
+                out.append(None)
+                continue
+            a = np.asarray(v)
+            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+                raise ValueError("%s: a parent list must be a one-dimensional list of 0-based cell indices" % who)
+            if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+                raise ValueError("%s: a parent index is outside the 32-bit range" % who)
+            out.append(np.ascontiguousarray(a, dtype=np.int32))
+        sizes = {a.shape[0] for a in out if a is not None}
+        if len(sizes) > 1:
+            raise ValueError("%s: parent_a and parent_b must have the same length" % who)
+        n = sizes.pop() if sizes else 0
+        return [a if a is None or n else np.zeros(1, dtype=np.int32) for a in out] + [n]
+
+    def simulate_doublets(self, dst, parent_a, parent_b):
+        """The resident matrix of `dst` (another Context on this device) becomes S, S[:, s] = A[:, parent_a[s]] +
+        A[:, parent_b[s]] over this context's resident matrix, which is only read (sgl_simulate_doublets; the rules are in
+        include/singlet_hip.h, "Simulated doublets").  A fit of dst is dropped; this context keeps its matrix and its fit."""
+        if not isinstance(dst, Context):
+            raise TypeError("simulate_doublets: dst must be a Context")
+        a, b, n = self._parent_lists(parent_a, parent_b, "simulate_doublets")
+        check(self._L.sgl_simulate_doublets(self._h, dst._h, ptr(a, i32p), ptr(b, i32p), n))
+        dst.k = 0
+
+    def doublets_info(self):
+        """What the last simulate_doublets INTO this context, or the last op_pair_columns on it, ran (sgl_doublets_info):
+        {"lds_pairs", "long_pairs", "entries" (stored entries of S), "shared_rows" (rows stored in both parents)}."""
+        out = np.zeros(4, dtype=np.int64)
+        check(self._L.sgl_doublets_info(self._h, ptr(out, i64p)))
+        return dict(zip(("lds_pairs", "long_pairs", "entries", "shared_rows"), (int(v) for v in out)))
+
     def weight_by_split(self, split_by, n_groups):
         """weight_by_split (src/singlet.cpp:119-144) on the resident shard; split_by: 0-based group per local cell."""
         sb = np.ascontiguousarray(split_by, dtype=np.int32)
@@ -1041,6 +1079,19 @@ class Context(_Handle):
         _, nc, _ = self.dims()
         return signature_call(lambda sp, sg, P, R, r2, sc: self._L.sgl_op_signature_scores(
             self._h, sp, sg, P, R, int(lds_cap), int(max_batch_entries), int(pass_sets), r2, sc), nc, sets, max_rank, True)
+
+    # the merge of simulate_doublets alone, with the knob that forces either path (0: the default)
+    def op_pair_columns(self, parent_a, parent_b, lds_cap=0):
+        """(x, i, p) of S, S[:, s] = A[:, parent_a[s]] + A[:, parent_b[s]] over the resident matrix, as CSC slots with 64-bit
+        offsets (sgl_op_pair_columns, called twice: the offsets, then the entries).  A pair whose row indices together fit
+        lds_cap is merged in LDS, a longer one in global memory; the result does not depend on it."""
+        a, b, n = self._parent_lists(parent_a, parent_b, "op_pair_columns")
+        p = np.zeros(n + 1, dtype=np.int64)
+        check(self._L.sgl_op_pair_columns(self._h, ptr(a, i32p), ptr(b, i32p), n, int(lds_cap), ptr(p, i64p), None, None))
+        nnz = int(p[n])
+        x, i = np.empty(max(nnz, 1)), np.empty(max(nnz, 1), dtype=np.int32)
+        check(self._L.sgl_op_pair_columns(self._h, ptr(a, i32p), ptr(b, i32p), n, int(lds_cap), ptr(p, i64p), ptr(i, i32p), ptr(x, f64p)))
+        return x[:nnz], i[:nnz], p
 
     # the stages of the gene set enrichment test, one at a time (no resident matrix is needed)
     def op_gsea_es(self, w, set_ptr, set_genes):

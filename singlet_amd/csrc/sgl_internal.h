@@ -266,6 +266,9 @@ struct sgl_ctx {
     // sgl_signature_info: cells sorted by the small and by the large LDS instance, long cells, batches, set passes, and the
     // caps in force (LDS entries, batch entries, sets per pass) of the last signature call
     int64_t signature_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // sgl_doublets_info: pairs merged on the LDS path and on the long path, stored entries of S, rows stored in both parents,
+    // of the last sgl_simulate_doublets into / sgl_op_pair_columns on this context
+    int64_t doublet_last[4] = {0, 0, 0, 0};
 
     sgl_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
@@ -517,6 +520,13 @@ int sgl_signature_scores_core(sgl_ctx* c, const int64_t* set_ptr, const int32_t*
                               int64_t max_batch_entries, int64_t pass_sets, uint64_t* rank2_out, double* score_out);
 // the doubled capped midrank of every stored entry (nnz values) and of every cell's zero block (ncol values; 0: no zero block)
 int sgl_cell_ranks_core(sgl_ctx* c, int64_t max_rank, int64_t lds_cap, int64_t max_batch_entries, uint64_t* entry_out, uint64_t* zero2_out);
+
+// simulated doublets (kernels_doublet.hip; include/singlet_hip.h, "Simulated doublets"): S = the pair sums of A's columns, built
+// on c's stream from c's pool; the parent lists are the HOST's and have been checked (doublet_host.h).  S comes in empty; on a
+// failure the caller frees what it holds.  info: LDS pairs, long pairs, entries of S, shared rows; *bad_col: the lowest
+// simulated column with a non-finite sum, or -1.  count_only: S.p alone.  Synchronises the stream.
+int sgl_pair_columns_core(sgl_ctx* c, const DevCSC& A, const int32_t* parent_a, const int32_t* parent_b, int64_t n, int64_t lds_cap,
+                          bool count_only, DevCSC& S, int64_t info[4], int64_t* bad_col);
 
 // gene set enrichment (kernels_gsea.hip; include/singlet_hip.h, "Gene set enrichment").  All arrays are the HOST's; every call
 // only reads the context (it records what it ran in gsea_last), allocates its own temporaries and synchronises the stream

@@ -6,6 +6,7 @@
 #include "sgl_internal.h"
 #include "ingest_host.h"
 #include "annotate_host.h"
+#include "doublet_host.h"
 
 #include <math.h>
 #include <string.h>
@@ -976,6 +977,120 @@ extern "C" int sgl_subset(sgl_ctx* c, const int32_t* rows, int64_t n_rows, const
     c->ncells_total = c->A.ncol;
     UPLOADCHK(c, finish_matrix(c));
     if (hipStreamSynchronize(c->stream) != hipSuccess) { sgl_set_error("sgl_subset: HIP call failed"); return drop_matrix(c, SGL_EHIP); }
+    return SGL_OK;
+}
+
+// ---- sgl_simulate_doublets: dst <- the pair sums of src's columns, on the device (include/singlet_hip.h) ----
+// the state rules of one context of the call (role: "src" / "dst" / "the context")
+static int doublet_ctx_state(const char* who, const char* role, const sgl_ctx* c) {
+    if (c->team || c->allreduce) {
+        sgl_set_error("%s: %s is a member of a team or has an all-reduce hook; simulate doublets on a context of its own", who, role);
+        return SGL_ESTATE;
+    }
+    if (c->A.p && (c->cell_offset != 0 || c->ncells_total != (int64_t)c->A.ncol)) {
+        sgl_set_error("%s: %s holds a shard (cells %lld .. %lld of %lld); the parents are drawn from the whole matrix", who, role,
+                      (long long)c->cell_offset, (long long)c->cell_offset + c->A.ncol, (long long)c->ncells_total);
+        return SGL_ESTATE;
+    }
+    return SGL_OK;
+}
+static int doublet_args(const char* who, const int32_t* parent_a, const int32_t* parent_b, int64_t n_sim, int32_t ncol, int64_t lds_cap) {
+    int list = -1;
+    int64_t at = -1, val = 0;
+    switch (doublet_check_args(parent_a, parent_b, n_sim, ncol, lds_cap, &list, &at, &val)) {
+        case DOUBLET_ARGS_OK: return SGL_OK;
+        case DOUBLET_ARGS_NSIM: sgl_set_error("%s: n_sim = %lld must lie in [1, 2^31 - 1]", who, (long long)val); break;
+        case DOUBLET_ARGS_NULL: sgl_set_error("%s: %s is NULL", who, list ? "parent_b" : "parent_a"); break;
+        case DOUBLET_ARGS_CAP: sgl_set_error("%s: lds_cap = %lld is negative (0: the default)", who, (long long)val); break;
+        case DOUBLET_ARGS_PARENT:
+            sgl_set_error("%s: %s[%lld] = %lld is outside [0, ncol = %d)", who, list ? "parent_b" : "parent_a", (long long)at, (long long)val, ncol);
+            break;
+    }
+    return SGL_EINVAL;
+}
+// `later` waits for everything queued on `earlier` so far (an event recorded on the one, waited for on the other)
+static int stream_after(hipStream_t later, hipStream_t earlier) {
+    if (later == earlier) return SGL_OK;
+    hipEvent_t ev = nullptr;
+    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, earlier);
+    if (e == hipSuccess) e = hipStreamWaitEvent(later, ev, 0);
+    (void)hipEventDestroy(ev);   // (released by the runtime once the recorded work has completed)
+    if (e != hipSuccess) { sgl_set_error("stream ordering failed: %s", hipGetErrorString(e)); return SGL_EHIP; }
+    return SGL_OK;
+}
+
+extern "C" int sgl_simulate_doublets(sgl_ctx* src, sgl_ctx* dst, const int32_t* parent_a, const int32_t* parent_b, int64_t n_sim) {
+    static const char* who = "sgl_simulate_doublets";
+    if (!src) { sgl_set_error("null context"); return SGL_EINVAL; }
+    CTX_GUARD(dst);
+    if (src == dst) { sgl_set_error("%s: src and dst are one context; the simulated cells go to a context of their own", who); return SGL_ESTATE; }
+    if (!src->A.p) { sgl_set_error("%s: no matrix resident in src", who); return SGL_ESTATE; }
+    SGLCHK(doublet_ctx_state(who, "src", src));
+    SGLCHK(doublet_ctx_state(who, "dst", dst));
+    if (src->device != dst->device) {
+        sgl_set_error("%s: src is on device %d, dst on device %d; both contexts must be on one device", who, src->device, dst->device);
+        return SGL_EINVAL;
+    }
+    SGLCHK(doublet_args(who, parent_a, parent_b, n_sim, src->A.ncol, 0));
+    // the kernels run on dst's stream, after whatever src's stream still holds (a log_normalize, a synth)
+    SGLCHK(stream_after(dst->stream, src->stream));
+    HIPCHK(hipStreamSynchronize(dst->stream));   // what dst still runs on its old matrix ends before that matrix is freed
+    free_fit(dst);
+    dst->k = 0;
+    free_matrix(dst);
+    dst->cell_offset = 0;
+    dst->ncells_total = n_sim;
+    int64_t bad = -1;
+    int rc = sgl_pair_columns_core(dst, src->A, parent_a, parent_b, n_sim, 0, false, dst->A, dst->doublet_last, &bad);
+    // src's stream waits for the reads of its matrix: a sgl_log_normalize of src issued next cannot overtake them
+    const int rc_back = stream_after(src->stream, dst->stream);
+    if (rc == SGL_OK) rc = rc_back;
+    if (rc == SGL_OK && bad >= 0) {
+        sgl_set_error("%s: non-finite value in simulated column %lld (parents %d and %d): a sum that overflows is refused here as every "
+                      "upload refuses a non-finite value", who, (long long)bad, parent_a[bad], parent_b[bad]);
+        rc = SGL_EINVAL;
+    }
+    if (rc != SGL_OK) return drop_matrix(dst, rc);
+    const double t0 = wall_now();
+    UPLOADCHK(dst, sgl_device_transpose(dst));   // (synchronises the stream)
+    g_times.transpose_s += wall_now() - t0;      // as the transpose of sgl_upload_csc is booked (sgl_call_times_get)
+    UPLOADCHK(dst, finish_matrix(dst));
+    if (hipStreamSynchronize(dst->stream) != hipSuccess) { sgl_set_error("%s: HIP call failed", who); return drop_matrix(dst, SGL_EHIP); }
+    return SGL_OK;
+}
+
+extern "C" int sgl_op_pair_columns(sgl_ctx* c, const int32_t* parent_a, const int32_t* parent_b, int64_t n_sim, int64_t lds_cap,
+                                   int64_t* p_out, int32_t* i_out, double* x_out) {
+    static const char* who = "sgl_op_pair_columns";
+    CTX_GUARD(c);
+    if (!c->A.p) { sgl_set_error("%s: no matrix resident", who); return SGL_ESTATE; }
+    SGLCHK(doublet_ctx_state(who, "the context", c));
+    SGLCHK(doublet_args(who, parent_a, parent_b, n_sim, c->A.ncol, lds_cap));
+    if (!p_out || (i_out == nullptr) != (x_out == nullptr)) {
+        sgl_set_error("%s: p_out is NULL, or only one of i_out / x_out is given (both NULL: the offsets alone)", who);
+        return SGL_EINVAL;
+    }
+    DevCSC S;
+    int64_t bad = -1;
+    int rc = sgl_pair_columns_core(c, c->A, parent_a, parent_b, n_sim, lds_cap, i_out == nullptr, S, c->doublet_last, &bad);
+    hipError_t e = hipSuccess;
+    if (rc == SGL_OK) e = hipMemcpyAsync(p_out, S.p, sizeof(int64_t) * ((size_t)n_sim + 1), hipMemcpyDeviceToHost, c->stream);
+    if (rc == SGL_OK && e == hipSuccess && i_out && S.nnz > 0) {
+        e = hipMemcpyAsync(i_out, S.i, sizeof(int32_t) * (size_t)S.nnz, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(x_out, S.x, sizeof(double) * (size_t)S.nnz, hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);   // on every path: the lists and the outputs are the caller's memory
+    if (e == hipSuccess) e = es;
+    free_csc(S);
+    if (rc == SGL_OK && e != hipSuccess) { sgl_set_error("%s: %s", who, hipGetErrorString(e)); rc = SGL_EHIP; }
+    return rc;
+}
+
+extern "C" int sgl_doublets_info(sgl_ctx* c, int64_t out[4]) {
+    CTX_GUARD(c);
+    if (!out) { sgl_set_error("sgl_doublets_info: NULL out"); return SGL_EINVAL; }
+    std::copy(c->doublet_last, c->doublet_last + 4, out);
     return SGL_OK;
 }
 
