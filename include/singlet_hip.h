@@ -521,6 +521,111 @@ SGL_API int sgl_simulate_doublets(sgl_ctx* src, sgl_ctx* dst, const int32_t* par
  * over the pairs (out[2] + out[3] = the parents' entries together). */
 SGL_API int sgl_doublets_info(sgl_ctx* ctx, int64_t out[4]);
 
+/* Spatial autocorrelation: Moran's I of the genes of the resident matrix and of the rows of an embedding over a sparse
+ * n x n cell graph G (weights w_ij = G[i, j]), the question Seurat asks with FindSpatiallyVariableFeatures(selection.method =
+ * "moransi") and squidpy with spatial_autocorr.  The rules below are this library's own statement of the published
+ * definitions (Cliff & Ord 1981; the randomisation variance as ape::Moran.I writes it); tests/moran_restatement.py restates
+ * them in numpy.  NO parity run against ape, Seurat or squidpy is claimed.  The statistic needs the stored entries only:
+ *     sum_ij w_ij (x_i - m)(x_j - m) = P - m sum_i x_i t_i + m^2 S0,
+ *     P = sum over the stored j of x_j * (sum over the stored rows r of column j of G that the gene stores of w_rj x_r),
+ *     t_i = rowsum_i + colsum_i,
+ * so a gene costs its stored entries times the graph degree, never n^2.
+ *
+ * Graph: Gx / Gi / Gp, an n x n dgCMatrix, n = the cells, checked as sgl_set_graph checks its graph (finite weights, rows
+ * strictly ascending within a column).  It may be asymmetric, may carry a diagonal and negative weights, and is used as
+ * given (the Python front-end strips the diagonal by default).  It is uploaded per call, with 64-bit offsets.
+ *
+ * Graph moments (sgl_moran_graph_moments; host code, O(nnz(G)), once per call; all sums sequential, in double, no product
+ * contracted into an addition):
+ *  - S0 = the sum of w in stored order, one chain over the columns ascending;
+ *  - colsum_j sequential in stored order; rowsum_i through a counting transpose, i.e. sequential over ascending column
+ *    index; t_i = rowsum_i + colsum_i; S2 = the sum of t_i * t_i over ascending i;
+ *  - S1 = 0.5 * the sum over the union pattern of (w_ij + w_ji)^2, walked by merging column j of G with column j of t(G),
+ *    j ascending, rows ascending, an absent partner counting as +0.0 (an off-diagonal pair is met twice, once in each
+ *    column, a diagonal entry once as (2 w_jj)^2);
+ *  - S0 == 0 or a moment that is not finite: SGL_EINVAL.
+ *
+ * Per-gene moments, on the device over t(A), with sgl_op_gene_mean's conventions (c_g stored entries, an explicit zero is a
+ * stored entry, double, no contraction, no floating-point atomics, no trip count that follows the launch):
+ *  - mean_g = sgl_op_gene_mean's value (its kernel runs);
+ *  - M2_g = Q2 + (double)(n - c_g) * (m * m), Q2 = sum d * d, d = x - m;
+ *  - M4_g = Q4 + (double)(n - c_g) * ((m * m) * (m * m)), Q4 = sum (d * d) * (d * d);
+ *  - T_g = sum x * t[cell];
+ *  - Q2, Q4, T in the summation order of sgl_variable_features: segments of 8192 stored entries, lane l of 64 adds the
+ *    segment's entries l, l + 64, ... from +0.0, the butterfly (lane ^ 32, 16, 8, 4, 2, 1), the segment sums ascending from
+ *    +0.0.  One pass produces all three.
+ *
+ * Cross term P_g: for the entry at stored position e (cell j, value x_j), q_e = the sum from +0.0, over column j of G in
+ * stored order, of w * x_r for the rows r that are stored entries of gene g (an absent r contributes nothing), and
+ * p_e = x_j * q_e.  P_g = the sum of the p_e in the block order of sgl_gene_group_moments' E[g]: segments of 8192, blocks of
+ * 64, a lane past the end holds +0.0, ONE butterfly per block, block sums ascending from +0.0 within a segment, segment sums
+ * ascending from +0.0.  P_g is a function of (the gene's entries, G) alone: the path, the batching, the grid and the genes
+ * processed before it change no bit.
+ *  - search path (a gene of at most lds_cap entries; default and largest 5120: 12 bytes per entry + the block sums, 62 080
+ *    bytes, so that two workgroups share the 160 KB of a CU): one workgroup per gene, the gene's ascending cells and its
+ *    values staged in LDS, every lane owns an entry, walks its cell's column of G and finds each neighbour by binary search;
+ *  - table path (a longer gene): a batch of B genes scatters its values into a B x n table in global memory, one wave per
+ *    segment reads the neighbours straight from the table, the table is cleared by walking the entries again.  B is a quarter
+ *    of the free memory / 8 n bytes, at most 4096, at most the genes on this path.  The table is a PLAIN VALUE table on a
+ *    +0.0 background: an absent neighbour adds w * +0.0 = +-0.0 to q_e, and q_e, a sum that starts at +0.0, is never -0.0,
+ *    so adding +-0.0 changes no bit; the values are finite (every upload refuses others), so no NaN arises from it.
+ *  - hub columns of G are walked sequentially by their lane: the stated order demands it.
+ *
+ * Assembly (sgl_moran_stats; host code), nn = (double)n:
+ *  - C = (P - m * T) + (m * m) * S0;  I = (nn / S0) * (C / M2);  EI = -1 / (double)(n - 1);
+ *  - variance 1 "normality": V = ((nn * nn) * S1 - nn * S2 + 3 * (S0 * S0)) / (((nn * nn) - 1) * (S0 * S0)) - EI * EI;
+ *  - variance 0 "randomisation" (ape's): b2 = (nn * M4) / (M2 * M2),
+ *    V = (nn * (((nn * nn) - 3 * nn + 3) * S1 - nn * S2 + 3 * (S0 * S0)) - b2 * ((nn * (nn - 1)) * S1 - (2 * nn) * S2 + 6 * (S0 * S0)))
+ *        / (((nn - 1) * (nn - 2) * (nn - 3)) * (S0 * S0)) - EI * EI;
+ *  - sd = sqrt(V); z = (I - EI) / sd; p by alternative 0 "two.sided": erfc(|z| / sqrt 2), 1 "greater": 0.5 erfc(z / sqrt 2),
+ *    2 "less": 0.5 erfc(-z / sqrt 2);
+ *  - a constant row (M2 == 0) gives NaN for I, z and p: reported, not refused; p_adj is Benjamini-Hochberg over the rows
+ *    whose p is not NaN (the host code of the annotation); n < 4 is refused.
+ *  - cancellation: C is the difference of terms of the size of m^2 S0; for a dense, nearly constant gene its relative
+ *    error grows as m^2 / var(x) ("Spatial autocorrelation").
+ *
+ * sgl_moran: over the resident matrix; genes NULL for all genes, or n_genes distinct 0-based gene indices; moments_out
+ * 6 x n_genes column-major: mean, M2, M4, T, P, (double)c_g, in list order.  The call only reads: the matrix and a fit in
+ * progress are untouched.  Time counts in the "scale" phase; all work goes to the context's stream (sgl_set_stream), which
+ * is synchronised before the call returns.  After sgl_upload_dense it works over the CSC image.  64-bit entry indexing.
+ *  - SGL_EINVAL, the whole list checked before anything is uploaded: a NULL or bad graph, n != ncol, n < 4, a gene index out
+ *    of range or repeated (the message names the position and the value), S0 == 0.
+ *  - SGL_ESTATE: no matrix resident, a team member, an all-reduce hook, a shard.
+ * sgl_c_moran: the one-shot form, A and G from the host, in a context of its own.
+ *
+ * Embedding form (sgl_moran_embedding): F is k x n column-major on the host, or NULL for the embedding held by
+ * sgl_annotate_hold or else the H of the fit (sgl_group_moments' conventions; 1 <= k <= 1024).  Dense, so the centred form
+ * directly: m_f = the sum of F[f, :] in sgl_group_means' order over all cells (chunks of 256 ascending cells, slot s of
+ * S = 256 / min(64, k rounded up to a power of two) adds the positions s, s + S, ..., the binary tree over the slots, the
+ * chunk sums ascending from +0.0) / (double)n; z_j = F[f, j] - m_f; y_j = the sequential stored-order sum from +0.0 over
+ * column j of G of w * z_r; C = sum z_j * y_j, M2 = sum z_j * z_j, M4 = sum (z_j * z_j) * (z_j * z_j), each in that same
+ * order over all cells.  moments_out is 6 x k in sgl_moran_stats' layout with the rows ALREADY centred: +0.0, M2, M4, +0.0,
+ * C, (double)n (the assembly then gives C back unchanged); mean_out (k values) holds m_f.  Either may be NULL.
+ * The fit is only read: continued afterwards it gives the bits it would have given without the call.
+ * There is NO team form and NO R shim entry; permutation p-values, Geary's C and local Moran are not provided. */
+SGL_API int sgl_moran(sgl_ctx* ctx, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* genes, int64_t n_genes,
+                      double* moments_out);
+SGL_API int sgl_c_moran(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, const double* Gx, const int32_t* Gi,
+                        const int32_t* Gp, int32_t n, const int32_t* genes, int64_t n_genes, double* moments_out);
+SGL_API int sgl_moran_embedding(sgl_ctx* ctx, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const double* F, int32_t k,
+                                double* moments_out, double* mean_out);
+SGL_API int sgl_c_moran_embedding(const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const double* F, int32_t k,
+                                  double* moments_out, double* mean_out);
+/* Host only, no device: the graph moments (t: n values, may be NULL) and the assembly (any output may be NULL). */
+SGL_API int sgl_moran_graph_moments(const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, double* S0, double* S1, double* S2,
+                                    double* t);
+SGL_API int sgl_moran_stats(int64_t n, double S0, double S1, double S2, int64_t rows, const double* moments, int variance, int alternative,
+                            double* I, double* EI, double* sd, double* z, double* p, double* p_adj);
+/* The cross term alone (P_out: n_genes values in list order); the refusals of sgl_moran apply, but a graph without weight is
+ * accepted.  path 0 automatic, 1 forces the search path (a gene above 5120 entries still takes the table), 2 forces the table
+ * path; lds_cap 0 the default, otherwise a smaller capacity in entries; table_batch 0 the default B, otherwise B itself.
+ * The result does not depend on any of them. */
+SGL_API int sgl_op_moran_cross(sgl_ctx* ctx, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* genes,
+                               int64_t n_genes, int32_t path, int64_t lds_cap, int64_t table_batch, double* P_out);
+/* What the last sgl_moran / sgl_op_moran_cross on this context ran: out[0] the genes on the search path, out[1] on the table
+ * path, out[2] the table batches, out[3] the table batch B, out[4] the table's bytes, out[5] the LDS cap in force. */
+SGL_API int sgl_moran_info(sgl_ctx* ctx, int64_t out[6]);
+
 /* Start a fit at rank k.  w_init: k x nrow host array, or NULL to fill W on
  * the device with the synthetic init ((rand_{S+2}(f,g) >> 11) + 0.5) * 2^-53.
  * h = 0, d = 1 as in src/singlet.cpp:639-641.

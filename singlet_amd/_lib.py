@@ -79,6 +79,15 @@ SIGNATURES = {
     "sgl_simulate_doublets": (C.c_int, [C.c_void_p, C.c_void_p, i32p, i32p, C.c_int64]),
     "sgl_op_pair_columns": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int64, C.c_int64, i64p, i32p, f64p]),
     "sgl_doublets_info": (C.c_int, [C.c_void_p, i64p]),
+    "sgl_moran": (C.c_int, [C.c_void_p] + _CSC + [C.c_int32, i32p, C.c_int64, f64p]),
+    "sgl_c_moran": (C.c_int, _CSC + [C.c_int32, C.c_int32] + _CSC + [C.c_int32, i32p, C.c_int64, f64p]),
+    "sgl_moran_embedding": (C.c_int, [C.c_void_p] + _CSC + [C.c_int32, f64p, C.c_int32, f64p, f64p]),
+    "sgl_c_moran_embedding": (C.c_int, _CSC + [C.c_int32, f64p, C.c_int32, f64p, f64p]),
+    "sgl_moran_graph_moments": (C.c_int, _CSC + [C.c_int32, f64p, f64p, f64p, f64p]),
+    "sgl_moran_stats": (C.c_int, [C.c_int64, C.c_double, C.c_double, C.c_double, C.c_int64, f64p, C.c_int, C.c_int, f64p, f64p, f64p,
+                                  f64p, f64p, f64p]),
+    "sgl_op_moran_cross": (C.c_int, [C.c_void_p] + _CSC + [C.c_int32, i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, f64p]),
+    "sgl_moran_info": (C.c_int, [C.c_void_p, i64p]),
     "sgl_c_project_model": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                              C.c_uint16, f64p, f64p]),
     "sgl_rcpp_predict": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,

@@ -2790,3 +2790,170 @@ def AnnotateNMF(model_or_context, meta, columns=None, center=True, scale=False, 
     with Context(0) as ctx:
         ctx.hold_embedding(h)
         return run(ctx, fnames)
+
+
+# ---------------------------------------------------------------------------
+# Spatial autocorrelation (Moran's I of genes and factors over a cell graph)
+# ---------------------------------------------------------------------------
+MORAN_VARIANCES = ("randomisation", "normality")
+MORAN_ALTERNATIVES = ("two.sided", "greater", "less")
+
+
+def _moran_choice(value, choices, what):
+    if value not in choices:
+        raise ValueError("%s must be one of %s, not %r" % (what, ", ".join(repr(c) for c in choices), value))
+    return choices.index(value)
+
+
+def moran_graph_moments(G):
+    """{"S0", "S1", "S2", "t"} of the n x n cell graph G (sgl_moran_graph_moments; host code of the library, no device
+    needed): the sums of Cliff & Ord in the stated sequential orders, t[i] = rowsum_i + colsum_i.  The graph is used as given.
+    A graph whose weights sum to zero is refused."""
+    G = _square_graph(G, "moran_graph_moments")
+    s, t = np.zeros(3), np.zeros(max(G.ncol, 1))
+    f = lambda q: ptr(s[q:], f64p)
+    check(_lib.load().sgl_moran_graph_moments(*csc_ptrs(G), G.ncol, f(0), f(1), f(2), ptr(t, f64p)))
+    return {"S0": float(s[0]), "S1": float(s[1]), "S2": float(s[2]), "t": t[:G.ncol]}
+
+
+def moran_stats(n, S0, S1, S2, moments, variance="randomisation", alternative="two.sided"):
+    """Moran's I and its test from the graph moments and the per-row moments (sgl_moran_stats; host code of the library, no
+    device needed).  moments: 6 x rows (mean, M2, M4, T, P, c) as Context.moran returns them.  Returns {"I", "EI", "sd", "z",
+    "p", "p_adj"}, one value per row; a constant row has NaN for I, z and p; p_adj is Benjamini-Hochberg over the others."""
+    v, a = _moran_choice(variance, MORAN_VARIANCES, "variance"), _moran_choice(alternative, MORAN_ALTERNATIVES, "alternative")
+    mo = np.asarray(moments, dtype=np.float64)
+    if mo.ndim != 2 or mo.shape[0] != 6:
+        raise ValueError("moments must be a 6 x rows matrix (mean, M2, M4, T, P, c)")
+    buf = np.ascontiguousarray(mo.T)
+    rows = buf.shape[0]
+    out = [np.zeros(max(rows, 1)) for _ in range(6)]
+    check(_lib.load().sgl_moran_stats(int(n), float(S0), float(S1), float(S2), rows, ptr(buf, f64p), v, a, *(ptr(o, f64p) for o in out)))
+    return dict(zip(("I", "EI", "sd", "z", "p", "p_adj"), (o[:rows] for o in out)))
+
+
+def c_moran(A, G, genes=None):
+    """The one-shot form of Context.moran (sgl_c_moran): A a dgCMatrix or anything as_dgCMatrix accepts, in a context of its
+    own.  Returns the 6 x n_genes moments."""
+    from .context import Context
+    A, G = as_dgCMatrix(A), _square_graph(G, "c_moran")
+    g, ng = Context._gene_list(genes, "c_moran")
+    rows = ng if genes is not None else A.nrow
+    out = np.zeros((max(rows, 1), 6))
+    check(_lib.load().sgl_c_moran(*csc_ptrs(A), A.nrow, A.ncol, *csc_ptrs(G), G.ncol, ptr(g, i32p), ng, ptr(out, f64p)))
+    return out[:rows].T
+
+
+def c_moran_embedding(F, G):
+    """The one-shot form of Context.moran_embedding (sgl_c_moran_embedding): F k x n on the host, in a context of its own.
+    Returns (moments 6 x k, mean k)."""
+    G = _square_graph(G, "c_moran_embedding")
+    buf = colmajor(F, "F must be a k x n matrix")
+    n, k = buf.shape
+    if n != G.ncol:
+        raise ValueError("c_moran_embedding: F has %d columns, the graph %d cells" % (n, G.ncol))
+    kk = max(min(int(k), 1024), 1)
+    out, mean = np.zeros((kk, 6)), np.zeros(kk)
+    check(_lib.load().sgl_c_moran_embedding(*csc_ptrs(G), G.ncol, ptr(buf, f64p), int(k), ptr(out, f64p), ptr(mean, f64p)))
+    return out[:k].T, mean[:k]
+
+
+def _moran_front(who, n, graph, coords, max_dist, max_k, variance, alternative, nfeatures):
+    """The refusals of the front-ends, all before the first upload; returns a function that builds the graph."""
+    _moran_choice(variance, MORAN_VARIANCES, "%s: variance" % who)
+    _moran_choice(alternative, MORAN_ALTERNATIVES, "%s: alternative" % who)
+    if nfeatures is not None and (int(nfeatures) != nfeatures or nfeatures < 1):
+        raise ValueError("%s: nfeatures = %r: at least one feature is ranked" % (who, nfeatures))
+    if (graph is None) == (coords is None):
+        raise ValueError("%s: exactly one of graph and coords (+ max_dist) must be given" % who)
+    if n < 4:
+        raise ValueError("%s: %d cells: the variance of Moran's I needs at least 4" % (who, n))
+    if graph is not None:
+        if max_dist is not None:
+            raise ValueError("%s: max_dist belongs to coords; a graph is used as it is" % who)
+        G = _square_graph(graph, who)
+        if G.ncol != n:
+            raise ValueError("%s: the graph has %d cells, the data %d" % (who, G.ncol, n))
+        return lambda: G
+    xy = np.asarray(coords, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] != n:
+        raise ValueError("%s: coords must be an n x 2 matrix with one row per cell (%d), not %r" % (who, n, xy.shape))
+    if max_dist is None or not max_dist > 0:
+        raise ValueError("%s: coords needs a positive max_dist" % who)
+    return lambda: spatial_graph(xy[:, 0], xy[:, 1], max_dist, max_k)
+
+
+def _moran_table(n, G, moments, variance, alternative):
+    gm = moran_graph_moments(G)
+    st = moran_stats(n, gm["S0"], gm["S1"], gm["S2"], moments, variance, alternative)
+    st["moments"] = moments
+    st["graph_moments"] = {q: gm[q] for q in ("S0", "S1", "S2")}
+    return st
+
+
+def moran_rank(p, I, genes):
+    """The order of find_spatially_variable_features: p ascending, I descending, gene index ascending; NaN rows last."""
+    p, I, genes = np.asarray(p), np.asarray(I), np.asarray(genes)
+    bad = np.isnan(p) | np.isnan(I)
+    return np.lexsort((genes, np.where(bad, 0.0, -I), np.where(bad, np.inf, p), bad))
+
+
+def find_spatially_variable_features(A, graph=None, coords=None, max_dist=None, max_k=100, features=None, nfeatures=2000,
+                                     variance="randomisation", alternative="two.sided", drop_diagonal=True):
+    """Seurat::FindSpatiallyVariableFeatures(selection.method = "moransi") on the device: Moran's I of every gene (or of
+    `features`, distinct 0-based gene indices) over a cell graph, with its expectation, standard deviation, z, p and
+    Benjamini-Hochberg p_adj (sgl_moran; the rules are stated in include/singlet_hip.h, "Spatial autocorrelation" -- this
+    library's own statement of the published definitions, no parity with ape is claimed).  A: anything RunNMF takes, or a
+    Context that holds the matrix.  Exactly one of graph (an n x n sparse matrix, used as it is but for its diagonal, which
+    drop_diagonal removes) and coords (n x 2, turned into spatial_graph(coords, max_dist, max_k)).  Returns {"genes" (the tested
+    gene indices), "I", "EI", "sd", "z", "p", "p_adj", "moments", "graph_moments", "features": the first nfeatures tested genes
+    ranked by (p ascending, I descending, gene index ascending), NaN rows last}.  Every argument is refused before the first
+    upload."""
+    from .context import Context
+    who = "find_spatially_variable_features"
+    is_ctx = isinstance(A, Context)
+    if not is_ctx and not isinstance(A, NativeMatrix):
+        A = as_dgCMatrix(A)
+    m, n = A.dims()[:2] if is_ctx else (A.nrow, A.ncol)
+    build = _moran_front(who, n, graph, coords, max_dist, max_k, variance, alternative, nfeatures)
+    g, ng = Context._gene_list(features, who)
+    if features is not None:
+        if ng and (g[:ng].min() < 0 or g[:ng].max() >= m):
+            raise ValueError("%s: a feature index is outside [0, %d)" % (who, m))
+        if np.unique(g[:ng]).shape[0] != ng:
+            raise ValueError("%s: features holds a gene twice" % who)
+    G = build()
+    if drop_diagonal:
+        G = _without_diagonal(G)
+    genes = np.arange(m, dtype=np.int32) if features is None else g[:ng].copy()
+    if is_ctx:
+        moments = A.moran(G, features)
+    elif isinstance(A, NativeMatrix):
+        moments = _on_native(A, lambda ctx, fits: ctx.moran(G, features))
+    else:
+        moments = c_moran(A, G, features)
+    out = _moran_table(n, G, moments, variance, alternative)
+    out["genes"] = genes
+    out["features"] = genes[moran_rank(out["p"], out["I"], genes)][:int(nfeatures)]
+    return out
+
+
+def moran_factors(h_or_context, graph, variance="randomisation", alternative="two.sided", drop_diagonal=True):
+    """The table of find_spatially_variable_features for the factors: Moran's I of every row of h (k x n, or a model dict's
+    "h") or, for a Context, of its held embedding or else the H of its fit, read in place (sgl_moran_embedding).  Returns
+    {"I", "EI", "sd", "z", "p", "p_adj", "mean", "moments", "graph_moments"}, one value per factor."""
+    from .context import Context
+    who = "moran_factors"
+    is_ctx = isinstance(h_or_context, Context)
+    G = _square_graph(graph, who)
+    _moran_front(who, G.ncol, G, None, None, None, variance, alternative, None)
+    if not is_ctx:
+        h = h_or_context["h"] if isinstance(h_or_context, dict) else h_or_context
+        h = np.asarray(h, dtype=np.float64)
+        if h.ndim != 2 or h.shape[1] != G.ncol:
+            raise ValueError("%s: h must be k x n with one column per cell of the graph (%d), not %r" % (who, G.ncol, h.shape))
+    if drop_diagonal:
+        G = _without_diagonal(G)
+    moments, mean = h_or_context.moran_embedding(G, None) if is_ctx else c_moran_embedding(h, G)
+    out = _moran_table(G.ncol, G, moments, variance, alternative)
+    out["mean"] = mean
+    return out

@@ -574,6 +574,72 @@ class Context(_Handle):
         return annotate_call(lambda *a: self._L.sgl_annotate_genes(self._h, ptr(g, i32p), G, *a), nr, G, center, scale, proportion, tail,
                              with_nz=True)
 
+    @staticmethod
+    def _gene_list(genes, who):
+        """(the int32 array kept alive or None, its length) of a list of distinct 0-based gene indices; None: all genes.  The
+        library checks the range and the repeats itself and names the offender."""
+        if genes is None:
+            return None, 0
+        a = np.asarray(genes)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError("%s: genes must be a one-dimensional list of 0-based gene indices" % who)
+        if a.size and (a.min() < -2**31 or a.max() >= 2**31):
+            raise ValueError("%s: a gene index is outside the 32-bit range" % who)
+        n = int(a.shape[0])
+        return (np.ascontiguousarray(a, dtype=np.int32) if n else np.zeros(1, dtype=np.int32)), n
+
+    @staticmethod
+    def _square_graph(G, who):
+        G = as_dgCMatrix(G)
+        if G.nrow != G.ncol:
+            raise ValueError("%s: the graph is %d x %d, not square" % (who, G.nrow, G.ncol))
+        return G
+
+    def moran(self, G, genes=None):
+        """The per-gene moments behind Moran's I of the resident matrix over the n x n cell graph G (sgl_moran; the rules:
+        include/singlet_hip.h, "Spatial autocorrelation"): a 6 x n_genes array with the rows mean, M2, M4, T, P, c_g, in the
+        order of `genes` (None: all genes).  The graph is used as given.  The matrix and a running fit are only read."""
+        G = self._square_graph(G, "moran")
+        g, ng = self._gene_list(genes, "moran")
+        nr, _, _ = self.dims()
+        rows = ng if genes is not None else nr
+        out = np.zeros((max(rows, 1), 6))
+        check(self._L.sgl_moran(self._h, *csc_ptrs(G), G.ncol, ptr(g, i32p), ng, ptr(out, f64p)))
+        return out[:rows].T
+
+    def op_moran_cross(self, G, genes=None, path=0, lds_cap=0, table_batch=0):
+        """P of sgl_moran alone (sgl_op_moran_cross): one value per listed gene.  path 0 automatic, 1 the search path, 2 the
+        table path; lds_cap and table_batch 0: the defaults.  The result does not depend on any of them; moran_info() says
+        what ran."""
+        G = self._square_graph(G, "op_moran_cross")
+        g, ng = self._gene_list(genes, "op_moran_cross")
+        nr, _, _ = self.dims()
+        rows = ng if genes is not None else nr
+        out = np.zeros(max(rows, 1))
+        check(self._L.sgl_op_moran_cross(self._h, *csc_ptrs(G), G.ncol, ptr(g, i32p), ng, int(path), int(lds_cap), int(table_batch),
+                                         ptr(out, f64p)))
+        return out[:rows]
+
+    def moran_info(self):
+        """What the last moran / op_moran_cross on this context ran (sgl_moran_info): {"search_genes", "table_genes",
+        "batches", "table_batch", "table_bytes", "lds_cap"}."""
+        out = np.zeros(6, dtype=np.int64)
+        check(self._L.sgl_moran_info(self._h, ptr(out, i64p)))
+        return dict(zip(("search_genes", "table_genes", "batches", "table_batch", "table_bytes", "lds_cap"), (int(v) for v in out)))
+
+    def moran_embedding(self, G, F=None):
+        """(moments 6 x k, mean k) behind Moran's I of the rows of F (k x n; None: the held embedding, else the H of the current
+        fit, read where it is) over the cell graph G (sgl_moran_embedding).  The rows of the moments are +0.0, M2, M4, +0.0,
+        C, n: the embedding is centred before the sums, so moran_stats takes them as they are."""
+        G = self._square_graph(G, "moran_embedding")
+        _buf, Fp, k, n = self._embedding_in(F)
+        if F is not None and n != G.ncol:
+            raise ValueError("moran_embedding: F has %d columns, the graph %d cells" % (n, G.ncol))
+        kk = max(min(int(k), 1024), 1)
+        out, mean = np.zeros((kk, 6)), np.zeros(kk)
+        check(self._L.sgl_moran_embedding(self._h, *csc_ptrs(G), G.ncol, Fp, int(k), ptr(out, f64p), ptr(mean, f64p)))
+        return out[:k].T, mean[:k]
+
     def variable_features(self, nfeatures=2000, span=0.3, vmax=None, expected_var=None):
         """Variable features of the resident counts (sgl_variable_features; Seurat's vst selection under this library's
         stated rules): {"features" (int32 gene indices in rank order), "mean", "variance", "variance_expected",

@@ -269,6 +269,9 @@ struct sgl_ctx {
     // sgl_doublets_info: pairs merged on the LDS path and on the long path, stored entries of S, rows stored in both parents,
     // of the last sgl_simulate_doublets into / sgl_op_pair_columns on this context
     int64_t doublet_last[4] = {0, 0, 0, 0};
+    // sgl_moran_info: genes on the search path and on the table path, table batches, the table batch B, the table's bytes and
+    // the LDS cap in force, of the last sgl_moran / sgl_op_moran_cross on this context
+    int64_t moran_last[6] = {0, 0, 0, 0, 0, 0};
 
     sgl_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
@@ -527,6 +530,20 @@ int sgl_cell_ranks_core(sgl_ctx* c, int64_t max_rank, int64_t lds_cap, int64_t m
 // simulated column with a non-finite sum, or -1.  count_only: S.p alone.  Synchronises the stream.
 int sgl_pair_columns_core(sgl_ctx* c, const DevCSC& A, const int32_t* parent_a, const int32_t* parent_b, int64_t n, int64_t lds_cap,
                           bool count_only, DevCSC& S, int64_t info[4], int64_t* bad_col);
+
+// spatial autocorrelation (kernels_moran.hip; include/singlet_hip.h, "Spatial autocorrelation").  All arrays are the HOST's but
+// F, which is the DEVICE's (k x n column-major); every call only reads the context (the gene form records what it ran in
+// moran_last), allocates its own temporaries and synchronises the stream before it returns.  The args check holds every refusal
+// of the arguments (the graph through sgl_graph_check, n, the gene list, the knobs) and launches nothing.
+int sgl_moran_args_check(const char* who, const double* Gx, const int32_t* Gi, const int32_t* Gp, int64_t G_n, int64_t ncells, const int32_t* genes,
+                         int64_t n_genes, int64_t m, int64_t path, int64_t lds_cap, int64_t table_batch);
+// over c->At: moments_out 6 x n_genes (mean, M2, M4, T, P, c_g) with want_moments (a graph without weight is then refused),
+// P_out n_genes; either may be NULL; a knob of 0: the default
+int sgl_moran_genes_core(sgl_ctx* c, const double* Gx, const int32_t* Gi, const int32_t* Gp, const int32_t* genes, int64_t n_genes, int path,
+                         int64_t lds_cap, int64_t table_batch, bool want_moments, double* moments_out, double* P_out);
+// moments_out 6 x k (+0.0, M2, M4, +0.0, C, n: the rows are centred), mean_out k; either may be NULL
+int sgl_moran_embedding_core(sgl_ctx* c, const double* Gx, const int32_t* Gi, const int32_t* Gp, const double* F, int k, int64_t n,
+                             double* moments_out, double* mean_out);
 
 // gene set enrichment (kernels_gsea.hip; include/singlet_hip.h, "Gene set enrichment").  All arrays are the HOST's; every call
 // only reads the context (it records what it ran in gsea_last), allocates its own temporaries and synchronises the stream

@@ -7,6 +7,7 @@
 #include "ingest_host.h"
 #include "annotate_host.h"
 #include "doublet_host.h"
+#include "moran_host.h"
 
 #include <math.h>
 #include <string.h>
@@ -2272,6 +2273,109 @@ extern "C" int sgl_gene_group_moments(sgl_ctx* c, const int32_t* labels, int32_t
     SGLCHK(annotate_gene_state(c, "sgl_gene_group_moments"));
     SGLCHK(sgl_annotate_args_check("sgl_gene_group_moments", labels, c->A.ncol, n_groups, 1));
     return sgl_gene_moments_core(c, labels, n_groups, group_n, nz, sum, rss);
+}
+
+// Spatial autocorrelation (include/singlet_hip.h; kernels_moran.hip, moran_host.h): the refusals, then passes that only read.
+static int moran_gene_state(sgl_ctx* c, const char* who) {
+    if (c->team || c->allreduce) {
+        sgl_set_error("%s: the context is a shard of a team or has an all-reduce hook; the moments of this shard's cells are not the matrix's", who);
+        return SGL_ESTATE;
+    }
+    if (!c->A.p || !c->At.p) { sgl_set_error("%s: no matrix resident", who); return SGL_ESTATE; }
+    if (c->cell_offset != 0 || c->ncells_total != (int64_t)c->A.ncol) {
+        sgl_set_error("%s: the context holds a shard (cells %lld .. %lld of %lld); the graph spans the whole matrix", who,
+                      (long long)c->cell_offset, (long long)c->cell_offset + c->A.ncol, (long long)c->ncells_total);
+        return SGL_ESTATE;
+    }
+    return SGL_OK;
+}
+static int moran_embedding_args(const char* who, const double* Gx, const int32_t* Gi, const int32_t* Gp, int64_t n, int32_t k) {
+    if (k < 1 || k > MORAN_MAX_K) { sgl_set_error("%s: k = %d is outside [1, %d]", who, k, MORAN_MAX_K); return SGL_EINVAL; }
+    return sgl_moran_args_check(who, Gx, Gi, Gp, n, n, nullptr, 0, 0, 0, 0, 0);
+}
+
+extern "C" int sgl_moran(sgl_ctx* c, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* genes, int64_t n_genes,
+                         double* moments_out) {
+    CTX_GUARD(c);
+    SGLCHK(moran_gene_state(c, "sgl_moran"));
+    SGLCHK(sgl_moran_args_check("sgl_moran", Gx, Gi, Gp, n, c->A.ncol, genes, n_genes, c->A.nrow, 0, 0, 0));
+    if (!moments_out) { sgl_set_error("sgl_moran: NULL moments_out"); return SGL_EINVAL; }
+    return sgl_moran_genes_core(c, Gx, Gi, Gp, genes, n_genes, 0, 0, 0, true, moments_out, nullptr);
+}
+
+extern "C" int sgl_c_moran(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, const double* Gx, const int32_t* Gi,
+                           const int32_t* Gp, int32_t n, const int32_t* genes, int64_t n_genes, double* moments_out) {
+    SGLCHK(sgl_moran_args_check("sgl_c_moran", Gx, Gi, Gp, n, ncol, genes, n_genes, std::max(nrow, 0), 0, 0, 0));   // before a context is made
+    if (!moments_out) { sgl_set_error("sgl_c_moran: NULL moments_out"); return SGL_EINVAL; }
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, nullptr, nullptr, nullptr, nrow, ncol, 0, ncol));
+    return sgl_moran(hd.c, Gx, Gi, Gp, n, genes, n_genes, moments_out);
+}
+
+extern "C" int sgl_op_moran_cross(sgl_ctx* c, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* genes,
+                                  int64_t n_genes, int32_t path, int64_t lds_cap, int64_t table_batch, double* P_out) {
+    CTX_GUARD(c);
+    SGLCHK(moran_gene_state(c, "sgl_op_moran_cross"));
+    SGLCHK(sgl_moran_args_check("sgl_op_moran_cross", Gx, Gi, Gp, n, c->A.ncol, genes, n_genes, c->A.nrow, path, lds_cap, table_batch));
+    if (!P_out) { sgl_set_error("sgl_op_moran_cross: NULL P_out"); return SGL_EINVAL; }
+    return sgl_moran_genes_core(c, Gx, Gi, Gp, genes, n_genes, path, lds_cap, table_batch, false, nullptr, P_out);
+}
+
+extern "C" int sgl_moran_info(sgl_ctx* c, int64_t out[6]) {
+    CTX_GUARD(c);
+    if (!out) { sgl_set_error("sgl_moran_info: NULL out"); return SGL_EINVAL; }
+    std::copy(c->moran_last, c->moran_last + 6, out);
+    return SGL_OK;
+}
+
+extern "C" int sgl_moran_embedding(sgl_ctx* c, const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const double* F, int32_t k,
+                                   double* moments_out, double* mean_out) {
+    CTX_GUARD(c);
+    SGLCHK(annotate_embedding_state(c, "sgl_moran_embedding", F, k, n));
+    SGLCHK(moran_embedding_args("sgl_moran_embedding", Gx, Gi, Gp, n, k));
+    if (!F) return sgl_moran_embedding_core(c, Gx, Gi, Gp, c->ann_F ? c->ann_F : c->H, k, n, moments_out, mean_out);
+    DevBuf<double> dF;
+    SGLCHK(dF.alloc((size_t)k * (size_t)n));
+    HIPCHK(hipMemcpyAsync(dF.p, F, sizeof(double) * (size_t)k * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    return sgl_moran_embedding_core(c, Gx, Gi, Gp, dF.p, k, n, moments_out, mean_out);   // (synchronises before dF goes)
+}
+
+extern "C" int sgl_c_moran_embedding(const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, const double* F, int32_t k,
+                                     double* moments_out, double* mean_out) {
+    if (!F) { sgl_set_error("sgl_c_moran_embedding: F is NULL"); return SGL_EINVAL; }
+    SGLCHK(moran_embedding_args("sgl_c_moran_embedding", Gx, Gi, Gp, n, k));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    return sgl_moran_embedding(hd.c, Gx, Gi, Gp, n, F, k, moments_out, mean_out);
+}
+
+extern "C" int sgl_moran_graph_moments(const double* Gx, const int32_t* Gi, const int32_t* Gp, int32_t n, double* S0, double* S1, double* S2,
+                                       double* t) {
+    static const char* who = "sgl_moran_graph_moments";
+    if (!Gx || !Gi || !Gp || !S0 || !S1 || !S2) { sgl_set_error("%s: NULL graph array or output", who); return SGL_EINVAL; }
+    if (n < 1) { sgl_set_error("%s: n = %d: at least one cell", who, n); return SGL_EINVAL; }
+    SGLCHK(sgl_graph_check(who, Gx, Gi, Gp, n, n, n));
+    if (moran_graph_moments(Gx, Gi, Gp, n, S0, S1, S2, t)) {
+        sgl_set_error("%s: the graph's weights sum to S0 = %g, or a graph moment is not finite: Moran's I is not defined", who, *S0);
+        return SGL_EINVAL;
+    }
+    return SGL_OK;
+}
+
+extern "C" int sgl_moran_stats(int64_t n, double S0, double S1, double S2, int64_t rows, const double* moments, int variance, int alternative,
+                               double* I, double* EI, double* sd, double* z, double* p, double* p_adj) {
+    static const char* who = "sgl_moran_stats";
+    if (n < MORAN_MIN_N) { sgl_set_error("%s: n = %lld cells: the variance of Moran's I needs at least %d", who, (long long)n, MORAN_MIN_N); return SGL_EINVAL; }
+    if (rows < 0 || (rows > 0 && !moments)) { sgl_set_error("%s: rows = %lld is negative, or NULL moments", who, (long long)rows); return SGL_EINVAL; }
+    if (S0 == 0.0 || !std::isfinite(S0) || !std::isfinite(S1) || !std::isfinite(S2)) {
+        sgl_set_error("%s: S0 = %g, S1 = %g, S2 = %g: S0 is zero or a graph moment is not finite", who, S0, S1, S2);
+        return SGL_EINVAL;
+    }
+    if (variance < 0 || variance > 1) { sgl_set_error("%s: variance = %d is none of 0 (randomisation), 1 (normality)", who, variance); return SGL_EINVAL; }
+    if (alternative < 0 || alternative > 2) { sgl_set_error("%s: alternative = %d is none of 0 (two.sided), 1 (greater), 2 (less)", who, alternative); return SGL_EINVAL; }
+    moran_stats(n, S0, S1, S2, rows, moments, variance, alternative, I, EI, sd, z, p, p_adj);
+    return SGL_OK;
 }
 
 extern "C" int sgl_annotate_stats(int64_t rows, int32_t n_groups, const int64_t* group_n, const double* sum, const double* rss, int center, int scale,
