@@ -626,6 +626,91 @@ SGL_API int sgl_op_moran_cross(sgl_ctx* ctx, const double* Gx, const int32_t* Gi
  * path, out[2] the table batches, out[3] the table batch B, out[4] the table's bytes, out[5] the LDS cap in force. */
 SGL_API int sgl_moran_info(sgl_ctx* ctx, int64_t out[6]);
 
+/* Neighbourhood enrichment: which classes of cells (clusters) sit next to which on a cell graph, more or less often than under
+ * a random relabelling -- the permutation test squidpy calls gr.nhood_enrichment / gr.interaction_matrix and Giotto
+ * cellProximityEnrichment.  The rules below are this library's own statement of the published scheme;
+ * tests/nhood_restatement.py restates them in numpy.  NO parity with squidpy's seeded numpy shuffles (or with Giotto) is claimed:
+ * the permutations are this library's.  Everything the device computes is an integer, so every result is one function of the
+ * inputs, bit for bit the restatement, whatever the path, the permutations per group or the batch.
+ *
+ * Inputs:
+ *  - graph: G is an n x n CSC graph, Gi / Gp int32.  There is no Gx argument: the values are not read.  Every STORED entry
+ *    counts once, whatever its value, and a repeated row counts again.  Rows need not be sorted.
+ *  - labels: lab[n], int32 in [0, K); K is the caller's, 1 <= K <= 256.  A class without cells is allowed: its rows and columns
+ *    of every table are 0 and its z is NaN.
+ *  - drop_diagonal (non-zero: on; the Python layer's default) skips the entries with row == column.
+ *  - seed uint64; nperm in [1, 2^20].
+ *
+ * Observed counts: C[a + K * b] = the number of counted entries (row i, column j) with lab[j] == a and lab[i] == b: a is the
+ * centre cell's class, b the neighbour's.  int64.
+ *
+ * Null: key(r, c) = rand(seed, r, c), the library's counter hash, exactly as in the null of the gene set enrichment; order_r =
+ * the cells ascending by (key, c); lab_r[c] = lab[order_r[c]].  Every permutation keeps the class sizes exactly.  C_r is the
+ * same tally under lab_r, r in [0, nperm).
+ *
+ * Tallies, integers per pair: S1 = sum_r C_r; S2 = sum_r C_r^2; n_ge = #{r: C_r >= C}; n_le = #{r: C_r <= C}.
+ *
+ * Statistics (sgl_nhood_stats; host code, nhood_host.h):
+ *  - D = nperm * S2 - S1^2 in exact 128-bit integer arithmetic;
+ *  - mean = (double)S1 / (double)nperm;  sd = sqrt((double)D) / (double)nperm (squidpy's std, ddof 0);
+ *  - z = (double)(nperm * C - S1) / sqrt((double)D), NaN when D == 0;
+ *  - p_enriched = (double)(1 + n_ge) / (double)(1 + nperm);  p_depleted = (double)(1 + n_le) / (double)(1 + nperm);
+ *  - Benjamini-Hochberg over the K^2 pairs for each of the two p (the rule and the code of the gene set enrichment; a NaN is
+ *    left out);
+ *  - an integer becomes a double by one conversion that rounds to nearest even.
+ *
+ * Refusals, SGL_EINVAL before anything is uploaded or launched, the message naming the offender, in this order: NULL Gi, Gp or
+ * lab; n < 1; Gp not starting at 0 or descending; a row outside [0, n); K outside [1, 256]; a label outside [0, K) (position and
+ * value); nperm out of range; nperm * nnz^2 >= 2^63 with nnz = Gp[n] (S2 would not fit int64; the message states the largest
+ * nperm that does); a negative batch.
+ *
+ * The plan (nhood_host.h, a pure function of the sizes and the knobs):
+ *  - permutations: stable radix sorts of the keys with the cells entering in ascending order.  Up to 32 768 cells the
+ *    permutations of a chunk are the segments of ONE segmented sort (one workgroup per segment); above, every permutation is one
+ *    device-wide sort.  The environment variable SGL_NHOOD_SORT_SWITCH (read per call) moves the switch; the result does not
+ *    depend on it.  lab_r is written permutation-interleaved: the labels of a cell under the PG permutations of a group are PG
+ *    adjacent bytes, so one load at a neighbour's index serves the group.
+ *  - tally: the work is cut by stored entries, in segments of 4096 entries whatever their columns (a workgroup takes a whole
+ *    number of segments, at most 512 workgroups per group); an entry's column is found once per call by a search in Gp.
+ *    LDS path: the PG x K x K uint32 tiles of a group in at most 128 KiB of LDS -- PG = 16 up to K = 45, 8 up to 64, 4 up to
+ *    90, 2 up to 128, 1 up to 181 -- added to with LDS atomics and flushed (non-zero bins) with global atomics.  A tile's bin
+ *    counts entries of one workgroup, at most nnz < 2^31: a uint32 cannot overflow.  Global path (K >= 182, or forced): global
+ *    atomics straight to the int64 counts, PG = 16.
+ *  - batch: permutations per batch; 0: what 256 MiB hold at n + 8 K^2 bytes per permutation, a multiple of 16, at least 16.
+ *  - integer sums have one value in any order: there are no ordering rules.
+ *
+ * sgl_nhood_enrichment: on the context's device, stream and pool only; no resident matrix is needed and nothing of the context
+ * changes but what sgl_nhood_info reports (a fit in progress continues with its bits).  All work goes to the context's stream
+ * (sgl_set_stream), which is synchronised before the call returns.  Any output may be NULL: counts, S1, S2, n_ge, n_le K x K
+ * int64; null_out nperm x K x K int64 (C_r at null_out[r K^2 + a + K b]), filled only when given.  The result does not
+ * depend on batch.  SGL_ESTATE: a team member, an all-reduce hook, a resident shard.
+ * sgl_c_nhood_enrichment: one-shot, in a context of its own; additionally the statistics (K x K doubles each, any may be NULL),
+ * info (sgl_nhood_info's six values, may be NULL) and stage_ms[3] by events (keys + sort + gather; tallies; reduction; may be NULL).
+ * sgl_nhood_stats: host only, no device; tallies that cannot be those of nperm permutations are refused.
+ * sgl_op_nhood_permute: lab_r of the permutations [r0, r0 + nb) as nb x n int32 (0 <= r0, 1 <= nb, r0 + nb <= 2^20; labels in
+ * [0, 256)), read back from the interleaved table the tally reads.
+ * sgl_op_nhood_tally: the tally of nb given label vectors (labs nb x n int32, each validated) as nb x K x K int64.  path 0
+ * automatic, 1 the LDS path (K >= 182 still takes the global path), 2 the global path; perms_per_group 0 the plan's value,
+ * otherwise a power of two up to what the path holds at this K (else SGL_EINVAL).  The result depends on neither.
+ * sgl_nhood_info: out[0] the tally's path (1 LDS, 2 global, 0 none ran), out[1] the permutations per group, out[2] the batches,
+ * out[3] the permutations per batch, out[4] the LDS bytes per workgroup, out[5] the sort (0 segmented, 1 device-wide) of the
+ * last of these calls on the context.
+ * There is NO team form and NO R shim entry; weighted edge counts, unlabelled cells and an analytic null are not provided. */
+SGL_API int sgl_nhood_enrichment(sgl_ctx* ctx, const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* lab, int32_t K, int drop_diagonal,
+                                 int32_t nperm, uint64_t seed, int32_t batch, int64_t* counts, int64_t* S1, int64_t* S2, int64_t* n_ge,
+                                 int64_t* n_le, int64_t* null_out);
+SGL_API int sgl_c_nhood_enrichment(const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* lab, int32_t K, int drop_diagonal, int32_t nperm,
+                                   uint64_t seed, int32_t batch, int64_t* counts, int64_t* S1, int64_t* S2, int64_t* n_ge, int64_t* n_le,
+                                   int64_t* null_out, double* z, double* mean, double* sd, double* p_enr, double* p_dep, double* padj_enr,
+                                   double* padj_dep, int64_t* info, double* stage_ms);
+SGL_API int sgl_nhood_stats(int32_t K, int32_t nperm, const int64_t* counts, const int64_t* S1, const int64_t* S2, const int64_t* n_ge,
+                            const int64_t* n_le, double* z, double* mean, double* sd, double* p_enr, double* p_dep, double* padj_enr,
+                            double* padj_dep);
+SGL_API int sgl_op_nhood_permute(sgl_ctx* ctx, int32_t n, const int32_t* lab, uint64_t seed, int32_t r0, int32_t nb, int32_t* lab_out);
+SGL_API int sgl_op_nhood_tally(sgl_ctx* ctx, const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* labs, int32_t nb, int32_t K,
+                               int drop_diagonal, int32_t path, int32_t perms_per_group, int64_t* counts_out);
+SGL_API int sgl_nhood_info(sgl_ctx* ctx, int64_t out[6]);
+
 /* Start a fit at rank k.  w_init: k x nrow host array, or NULL to fill W on
  * the device with the synthetic init ((rand_{S+2}(f,g) >> 11) + 0.5) * 2^-53.
  * h = 0, d = 1 as in src/singlet.cpp:639-641.

@@ -88,6 +88,13 @@ SIGNATURES = {
                                   f64p, f64p, f64p]),
     "sgl_op_moran_cross": (C.c_int, [C.c_void_p] + _CSC + [C.c_int32, i32p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, f64p]),
     "sgl_moran_info": (C.c_int, [C.c_void_p, i64p]),
+    "sgl_nhood_enrichment": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int32, i32p, C.c_int32, C.c_int, C.c_int32, C.c_uint64, C.c_int32] + [i64p] * 6),
+    "sgl_c_nhood_enrichment": (C.c_int, [i32p, i32p, C.c_int32, i32p, C.c_int32, C.c_int, C.c_int32, C.c_uint64, C.c_int32] + [i64p] * 6
+                               + [f64p] * 7 + [i64p, f64p]),
+    "sgl_nhood_stats": (C.c_int, [C.c_int32, C.c_int32] + [i64p] * 5 + [f64p] * 7),
+    "sgl_op_nhood_permute": (C.c_int, [C.c_void_p, C.c_int32, i32p, C.c_uint64, C.c_int32, C.c_int32, i32p]),
+    "sgl_op_nhood_tally": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int32, i64p]),
+    "sgl_nhood_info": (C.c_int, [C.c_void_p, i64p]),
     "sgl_c_project_model": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                              C.c_uint16, f64p, f64p]),
     "sgl_rcpp_predict": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,

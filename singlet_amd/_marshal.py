@@ -101,6 +101,27 @@ def label_list(labels, n, n_groups):
     return g, G
 
 
+NHOOD_TALLIES = ("counts", "S1", "S2", "n_ge", "n_le")
+NHOOD_STATS = ("zscore", "mean", "sd", "p_enriched", "p_depleted", "p_adj_enriched", "p_adj_depleted")
+NHOOD_INFO = ("path", "perms_per_group", "batches", "batch", "lds_bytes", "sort")
+
+
+def nhood_labels(labels, n, n_classes, who):
+    """(int32 labels, K) of the neighbourhood enrichment calls: one integer class per cell (a column of find_clusters'
+    "clusters" is one); n_classes None: 1 + the largest label.  The library checks the range and names the offender."""
+    g = np.asarray(labels)
+    if g.ndim == 2 and 1 in g.shape:
+        g = g.reshape(-1)
+    if g.ndim != 1 or g.size < 1 or g.dtype.kind not in "iub" or (n is not None and g.shape[0] != n):
+        raise ValueError("%s: labels must hold one integer class per cell%s" % (who, "" if n is None else " (%d)" % n))
+    if g.min() < -2**31 or g.max() >= 2**31:
+        raise ValueError("%s: a label is outside the 32-bit range" % who)
+    K = int(n_classes) if n_classes is not None else max(int(g.max()) + 1, 1)
+    if not -2**31 <= K < 2**31:
+        raise ValueError("%s: n_classes is outside the 32-bit range" % who)
+    return np.ascontiguousarray(g, dtype=np.int32), K
+
+
 def markers_call(fn, nrow, labels, G, transform, pseudocount):
     """Shared by Context.markers and api.c_markers: fn(labels, n_groups, transform, pseudocount, group_n, pos, sum, rank2, tie,
     pct_in, pct_out, log2fc, z, p) is the library call.  Returns the dict of the arrays, the per-(gene, cluster) ones as

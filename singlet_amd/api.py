@@ -49,7 +49,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from ._marshal import ArdOutputs, NmfOutputs, annotate_call, annotate_tail, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, knn_weighting, label_list, markers_call, signature_call
+from ._marshal import NHOOD_INFO, NHOOD_STATS, NHOOD_TALLIES, nhood_labels, ArdOutputs, NmfOutputs, annotate_call, annotate_tail, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, knn_weighting, label_list, markers_call, signature_call
 from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
@@ -2957,3 +2957,120 @@ def moran_factors(h_or_context, graph, variance="randomisation", alternative="tw
     out = _moran_table(G.ncol, G, moments, variance, alternative)
     out["mean"] = mean
     return out
+
+
+# ---------------------------------------------------------------------------
+# Neighbourhood enrichment (which clusters sit next to which on a cell graph; include/singlet_hip.h, "Neighbourhood enrichment")
+# ---------------------------------------------------------------------------
+def nhood_stats(nperm, counts, S1, S2, n_ge, n_le):
+    """z, mean, sd, the two p and their Benjamini-Hochberg adjustments from the integer tallies of a neighbourhood enrichment
+    call (sgl_nhood_stats; host code of the library, no device needed).  Every table is K x K, [a, b] = centre class a, neighbour
+    class b.  Returns {"zscore", "mean", "sd", "p_enriched", "p_depleted", "p_adj_enriched", "p_adj_depleted"}; z is NaN where
+    every permutation gave the same count."""
+    t = [np.asarray(a) for a in (counts, S1, S2, n_ge, n_le)]
+    K = t[0].shape[0] if t[0].ndim == 2 else 0
+    if K < 1 or any(a.shape != (K, K) or a.dtype.kind not in "iu" for a in t):
+        raise ValueError("nhood_stats: counts, S1, S2, n_ge and n_le must be K x K integer tables")
+    t = [np.ascontiguousarray(a.T, dtype=np.int64) for a in t]
+    out = [np.zeros((K, K)) for _ in NHOOD_STATS]
+    check(_lib.load().sgl_nhood_stats(K, int(nperm), *(ptr(a, _lib.i64p) for a in t), *(ptr(o, f64p) for o in out)))
+    return {name: np.ascontiguousarray(o.T) for name, o in zip(NHOOD_STATS, out)}
+
+
+def c_nhood_enrichment(G, labels, n_classes=None, nperm=1000, seed=0, drop_diagonal=True, batch=0, return_null=False, timing=False):
+    """The one-shot form of Context.nhood_enrichment (sgl_c_nhood_enrichment), in a context of its own: the tallies and the
+    statistics of nhood_stats in one dict, plus "info" (Context.nhood_info's fields); with return_null "null" (nperm x K x K),
+    with timing "stage_ms" (keys + sort + gather, tallies, reduction)."""
+    G = _square_graph(G, "c_nhood_enrichment")
+    lab, K = nhood_labels(labels, G.ncol, n_classes, "c_nhood_enrichment")
+    kk = max(min(K, 256), 1)
+    t = [np.zeros((kk, kk), dtype=np.int64) for _ in NHOOD_TALLIES]
+    st = [np.zeros((kk, kk)) for _ in NHOOD_STATS]
+    null = np.zeros((max(min(int(nperm), 1 << 20), 1), kk, kk), dtype=np.int64) if return_null else None
+    info, ms = np.zeros(6, dtype=np.int64), (np.zeros(3) if timing else None)
+    i64p = _lib.i64p
+    check(_lib.load().sgl_c_nhood_enrichment(ptr(G.i, i32p), ptr(G.p, i32p), G.ncol, ptr(lab, i32p), K, int(bool(drop_diagonal)), int(nperm), int(seed),
+                                             int(batch), *(ptr(a, i64p) for a in t), ptr(null, i64p), *(ptr(o, f64p) for o in st), ptr(info, i64p),
+                                             ptr(ms, f64p)))
+    out = {name: np.ascontiguousarray(a.T) for name, a in zip(NHOOD_TALLIES + NHOOD_STATS, t + st)}
+    out["info"] = dict(zip(NHOOD_INFO, (int(v) for v in info)))
+    if return_null:
+        out["null"] = np.ascontiguousarray(null.transpose(0, 2, 1))
+    if timing:
+        out["stage_ms"] = ms
+    return out
+
+
+def _nhood_graph(who, n, graph, coords, max_dist, max_k):
+    """The refusals of the graph arguments; returns a function that builds the graph (the first upload happens there)."""
+    if (graph is None) == (coords is None):
+        raise ValueError("%s: exactly one of graph and coords (+ max_dist) must be given" % who)
+    if graph is not None:
+        if max_dist is not None:
+            raise ValueError("%s: max_dist belongs to coords; a graph is used as it is" % who)
+        if isinstance(graph, dict):
+            if graph.get("snn") is None:
+                raise ValueError("%s: the neighbours were computed without an SNN graph (compute_snn=False)" % who)
+            graph = graph["snn"]
+        G = _square_graph(graph, who)
+        if G.ncol != n:
+            raise ValueError("%s: the graph has %d cells, the labels %d" % (who, G.ncol, n))
+        return lambda: G
+    xy = np.asarray(coords, dtype=np.float64)
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] != n:
+        raise ValueError("%s: coords must be an n x 2 matrix with one row per cell (%d), not %r" % (who, n, xy.shape))
+    if max_dist is None or not max_dist > 0:
+        raise ValueError("%s: coords needs a positive max_dist" % who)
+    return lambda: spatial_graph(xy[:, 0], xy[:, 1], max_dist, max_k)
+
+
+def _nhood_classes(who, labels, n_classes):
+    lab, K = nhood_labels(labels, None, n_classes, who)
+    if not 1 <= K <= 256:
+        raise ValueError("%s: %d classes: between 1 and 256 are taken" % (who, K))
+    if lab.min() < 0 or lab.max() >= K:
+        at = int(np.nonzero((lab < 0) | (lab >= K))[0][0])
+        raise ValueError("%s: labels[%d] = %d is outside [0, %d)" % (who, at, int(lab[at]), K))
+    return lab, K
+
+
+def nhood_enrichment(labels, graph=None, coords=None, max_dist=None, max_k=100, n_classes=None, nperm=1000, seed=0, drop_diagonal=True,
+                     batch=0):
+    """Which clusters sit next to which on a cell graph, more or less often than under a random relabelling: the permutation
+    test of squidpy's gr.nhood_enrichment / Giotto's cellProximityEnrichment on the device (sgl_c_nhood_enrichment; the rules are
+    stated in include/singlet_hip.h, "Neighbourhood enrichment" -- this library's own statement of the published scheme with its
+    own permutations, NO parity with squidpy's seeded shuffles is claimed).  labels: one integer class in [0, n_classes) per cell
+    (a column of find_clusters' "clusters"); n_classes None: 1 + the largest label.  Exactly one of graph (any SciPy matrix or
+    dgCMatrix, or the dict find_neighbors returns, whose "snn" is used; the stored entries count, not their values) and coords
+    (n x 2, turned into spatial_graph(coords, max_dist, max_k)).  drop_diagonal leaves self-loops out.  Returns {"counts",
+    "zscore", "mean", "sd", "p_enriched", "p_depleted", "p_adj_enriched", "p_adj_depleted", "n_ge", "n_le", "class_sizes"}, K x K
+    tables with [a, b] = centre class a, neighbour class b.  Every argument is refused before the first upload."""
+    who = "nhood_enrichment"
+    lab, K = _nhood_classes(who, labels, n_classes)
+    if int(nperm) != nperm or not 1 <= nperm <= 1 << 20:
+        raise ValueError("%s: nperm = %r is outside [1, 2^20]" % (who, nperm))
+    if int(batch) != batch or batch < 0:
+        raise ValueError("%s: batch = %r is negative" % (who, batch))
+    if int(seed) != seed or not 0 <= seed < 2**64:
+        raise ValueError("%s: seed = %r is no unsigned 64-bit integer" % (who, seed))
+    build = _nhood_graph(who, lab.shape[0], graph, coords, max_dist, max_k)
+    res = c_nhood_enrichment(build(), lab, K, nperm, seed, drop_diagonal, batch)
+    out = {name: res[name] for name in ("counts",) + NHOOD_STATS + ("n_ge", "n_le")}
+    out["class_sizes"] = np.bincount(lab, minlength=K).astype(np.int64)
+    return out
+
+
+def interaction_matrix(labels, graph, normalized=False, n_classes=None, drop_diagonal=True):
+    """squidpy's gr.interaction_matrix: the observed class-pair counts of the stored entries of `graph` alone, K x K with [a, b] =
+    centre class a, neighbour class b (sgl_op_nhood_tally on the labels as they are; no permutation is drawn).  graph as in
+    nhood_enrichment.  normalized divides every row by its sum on the host (a row without entries stays 0) and returns doubles."""
+    from .context import Context
+    who = "interaction_matrix"
+    lab, K = _nhood_classes(who, labels, n_classes)
+    G = _nhood_graph(who, lab.shape[0], graph, None, None, None)()
+    with Context(0) as ctx:
+        counts = ctx.op_nhood_tally(G, lab[None, :], K, drop_diagonal)[0]
+    if not normalized:
+        return counts
+    rows = counts.sum(axis=1, keepdims=True)
+    return np.divide(counts, rows, out=np.zeros(counts.shape), where=rows > 0)

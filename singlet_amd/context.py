@@ -6,8 +6,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
-from ._marshal import (KNN_INDEX_FIELDS, MARKER_TRANSFORMS, ArdOutputs, NmfOutputs, annotate_call, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call,
-                       knn_ivf_shape, knn_lists_in, knn_method, knn_metric, knn_weighting, label_list, markers_call, signature_call, transfer_call)
+from ._marshal import (KNN_INDEX_FIELDS, MARKER_TRANSFORMS, NHOOD_INFO, NHOOD_TALLIES, ArdOutputs, NmfOutputs, annotate_call, colmajor, csc_ptrs, gsea_inputs,
+                       gsea_score_type, knn_call, knn_ivf_shape, knn_lists_in, knn_method, knn_metric, knn_weighting, label_list, markers_call, nhood_labels,
+                       signature_call, transfer_call)
 from .sparse import as_dgCMatrix
 
 SYNTH_SEED = 0x5EED
@@ -639,6 +640,55 @@ class Context(_Handle):
         out, mean = np.zeros((kk, 6)), np.zeros(kk)
         check(self._L.sgl_moran_embedding(self._h, *csc_ptrs(G), G.ncol, Fp, int(k), ptr(out, f64p), ptr(mean, f64p)))
         return out[:k].T, mean[:k]
+
+    def nhood_enrichment(self, G, labels, n_classes=None, nperm=1000, seed=0, drop_diagonal=True, batch=0, return_null=False):
+        """The integer tallies of the neighbourhood enrichment test of the classes `labels` on the n x n cell graph G
+        (sgl_nhood_enrichment; the rules: include/singlet_hip.h, "Neighbourhood enrichment"): {"counts", "S1", "S2", "n_ge",
+        "n_le"}, K x K int64 each, [a, b] = centre class a, neighbour class b; with return_null also "null", nperm x K x K.
+        n_classes None: 1 + the largest label.  The stored values of G are not read.  Nothing of the context is touched;
+        nhood_info() says what ran; nhood_stats turns the tallies into z, p and p_adj."""
+        G = self._square_graph(G, "nhood_enrichment")
+        lab, K = nhood_labels(labels, G.ncol, n_classes, "nhood_enrichment")
+        kk = max(min(K, 256), 1)
+        t = [np.zeros((kk, kk), dtype=np.int64) for _ in NHOOD_TALLIES]
+        null = np.zeros((max(min(int(nperm), 1 << 20), 1), kk, kk), dtype=np.int64) if return_null else None
+        check(self._L.sgl_nhood_enrichment(self._h, ptr(G.i, i32p), ptr(G.p, i32p), G.ncol, ptr(lab, i32p), K, int(bool(drop_diagonal)), int(nperm),
+                                           int(seed), int(batch), *(ptr(a, i64p) for a in t), ptr(null, i64p)))
+        out = {name: np.ascontiguousarray(a.T) for name, a in zip(NHOOD_TALLIES, t)}
+        if return_null:
+            out["null"] = np.ascontiguousarray(null.transpose(0, 2, 1))
+        return out
+
+    def op_nhood_permute(self, labels, seed=0, r0=0, nb=1):
+        """lab_r of the permutations [r0, r0 + nb) of the neighbourhood enrichment null (sgl_op_nhood_permute): nb x n int32."""
+        lab, _ = nhood_labels(labels, None, None, "op_nhood_permute")
+        n = int(lab.shape[0])
+        out = np.zeros((max(int(nb), 1), max(n, 1)), dtype=np.int32)
+        check(self._L.sgl_op_nhood_permute(self._h, n, ptr(lab, i32p), int(seed), int(r0), int(nb), ptr(out, i32p)))
+        return out[:, :n]
+
+    def op_nhood_tally(self, G, labs, n_classes, drop_diagonal=True, path=0, perms_per_group=0):
+        """The class-pair counts of G under each of nb given label vectors (labs nb x n; sgl_op_nhood_tally): nb x K x K int64,
+        [q, a, b] = centre class a, neighbour class b.  path 0 automatic, 1 the LDS path, 2 the global path; perms_per_group 0:
+        the plan's value.  The result depends on neither; nhood_info() says what ran."""
+        G = self._square_graph(G, "op_nhood_tally")
+        L = np.asarray(labs)
+        if L.ndim != 2 or L.shape[1] != G.ncol or (L.size and L.dtype.kind not in "iub"):
+            raise ValueError("op_nhood_tally: labs must be an nb x n integer matrix with one column per cell (%d)" % G.ncol)
+        nb, K = int(L.shape[0]), int(n_classes)
+        L = np.ascontiguousarray(L, dtype=np.int32)
+        kk = max(min(K, 256), 1)
+        out = np.zeros((max(nb, 1), kk, kk), dtype=np.int64)
+        check(self._L.sgl_op_nhood_tally(self._h, ptr(G.i, i32p), ptr(G.p, i32p), G.ncol, ptr(L, i32p), nb, K, int(bool(drop_diagonal)), int(path),
+                                         int(perms_per_group), ptr(out, i64p)))
+        return np.ascontiguousarray(out[:nb].transpose(0, 2, 1))
+
+    def nhood_info(self):
+        """What the last neighbourhood enrichment call on this context ran (sgl_nhood_info): {"path" (1 LDS, 2 global, 0 no
+        tally), "perms_per_group", "batches", "batch", "lds_bytes", "sort" (0 segmented, 1 device-wide)}."""
+        out = np.zeros(6, dtype=np.int64)
+        check(self._L.sgl_nhood_info(self._h, ptr(out, i64p)))
+        return dict(zip(NHOOD_INFO, (int(v) for v in out)))
 
     def variable_features(self, nfeatures=2000, span=0.3, vmax=None, expected_var=None):
         """Variable features of the resident counts (sgl_variable_features; Seurat's vst selection under this library's

@@ -272,6 +272,9 @@ struct sgl_ctx {
     // sgl_moran_info: genes on the search path and on the table path, table batches, the table batch B, the table's bytes and
     // the LDS cap in force, of the last sgl_moran / sgl_op_moran_cross on this context
     int64_t moran_last[6] = {0, 0, 0, 0, 0, 0};
+    // sgl_nhood_info: the tally's path (1 LDS, 2 global; 0: none ran), the permutations per group, the batches, the permutations
+    // per batch, the LDS bytes per workgroup and the sort (0 segmented, 1 device-wide) of the last neighbourhood enrichment call
+    int64_t nhood_last[6] = {0, 0, 0, 0, 0, 0};
 
     sgl_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
@@ -544,6 +547,22 @@ int sgl_moran_genes_core(sgl_ctx* c, const double* Gx, const int32_t* Gi, const 
 // moments_out 6 x k (+0.0, M2, M4, +0.0, C, n: the rows are centred), mean_out k; either may be NULL
 int sgl_moran_embedding_core(sgl_ctx* c, const double* Gx, const int32_t* Gi, const int32_t* Gp, const double* F, int k, int64_t n,
                              double* moments_out, double* mean_out);
+
+// neighbourhood enrichment (kernels_nhood.hip; include/singlet_hip.h, "Neighbourhood enrichment").  All arrays are the HOST's;
+// every call reads nothing of the context but its device, stream and pool (it records what it ran in nhood_last), allocates its
+// own temporaries and synchronises the stream before it returns.  The *_args_check functions hold every refusal and launch nothing.
+int sgl_nhood_args_check(const char* who, const int32_t* Gi, const int32_t* Gp, int64_t n, const int32_t* lab, int64_t K, int64_t nperm, int64_t batch);
+int sgl_nhood_permute_args_check(const char* who, int64_t n, const int32_t* lab, int64_t r0, int64_t nb);
+int sgl_nhood_tally_args_check(const char* who, const int32_t* Gi, const int32_t* Gp, int64_t n, const int32_t* labs, int64_t nb, int64_t K, int path,
+                               int64_t pg);
+// lab_out nb x n: lab_r of the permutations [r0, r0 + nb)
+int sgl_nhood_permute_core(sgl_ctx* c, int64_t n, const int32_t* lab, uint64_t seed, int64_t r0, int64_t nb, int32_t* lab_out);
+// counts_out nb x K x K: the tally of nb label vectors; path 0 / 1 / 2, pg 0: the plan's
+int sgl_nhood_tally_core(sgl_ctx* c, const int32_t* Gi, const int32_t* Gp, int64_t n, const int32_t* labs, int64_t nb, int K, int drop, int path,
+                         int64_t pg, int64_t* counts_out);
+// the whole call: any output may be NULL; null_out nperm x K x K; stage_ms (3 values, may be NULL): the stages timed by events
+int sgl_nhood_all(sgl_ctx* c, const int32_t* Gi, const int32_t* Gp, int64_t n, const int32_t* lab, int K, int drop, int64_t nperm, uint64_t seed,
+                  int64_t batch, int64_t* counts, int64_t* S1, int64_t* S2, int64_t* n_ge, int64_t* n_le, int64_t* null_out, double* stage_ms);
 
 // gene set enrichment (kernels_gsea.hip; include/singlet_hip.h, "Gene set enrichment").  All arrays are the HOST's; every call
 // only reads the context (it records what it ran in gsea_last), allocates its own temporaries and synchronises the stream

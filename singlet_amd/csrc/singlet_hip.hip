@@ -8,6 +8,7 @@
 #include "annotate_host.h"
 #include "doublet_host.h"
 #include "moran_host.h"
+#include "nhood_host.h"
 
 #include <math.h>
 #include <string.h>
@@ -2375,6 +2376,92 @@ extern "C" int sgl_moran_stats(int64_t n, double S0, double S1, double S2, int64
     if (variance < 0 || variance > 1) { sgl_set_error("%s: variance = %d is none of 0 (randomisation), 1 (normality)", who, variance); return SGL_EINVAL; }
     if (alternative < 0 || alternative > 2) { sgl_set_error("%s: alternative = %d is none of 0 (two.sided), 1 (greater), 2 (less)", who, alternative); return SGL_EINVAL; }
     moran_stats(n, S0, S1, S2, rows, moments, variance, alternative, I, EI, sd, z, p, p_adj);
+    return SGL_OK;
+}
+
+// Neighbourhood enrichment (include/singlet_hip.h; kernels_nhood.hip, nhood_host.h): the refusals, then calls that read nothing of
+// the context but its device, stream and pool.
+static int nhood_state(sgl_ctx* c, const char* who) {
+    if (c->team || c->allreduce) {
+        sgl_set_error("%s: the context is a shard of a team or has an all-reduce hook; the graph spans all cells", who);
+        return SGL_ESTATE;
+    }
+    if (c->A.p && (c->cell_offset != 0 || c->ncells_total != (int64_t)c->A.ncol)) {
+        sgl_set_error("%s: the context holds a shard (cells %lld .. %lld of %lld); the graph spans all cells", who, (long long)c->cell_offset,
+                      (long long)c->cell_offset + c->A.ncol, (long long)c->ncells_total);
+        return SGL_ESTATE;
+    }
+    return SGL_OK;
+}
+
+extern "C" int sgl_nhood_enrichment(sgl_ctx* c, const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* lab, int32_t K, int drop_diagonal,
+                                    int32_t nperm, uint64_t seed, int32_t batch, int64_t* counts, int64_t* S1, int64_t* S2, int64_t* n_ge,
+                                    int64_t* n_le, int64_t* null_out) {
+    CTX_GUARD(c);
+    SGLCHK(nhood_state(c, "sgl_nhood_enrichment"));
+    SGLCHK(sgl_nhood_args_check("sgl_nhood_enrichment", Gi, Gp, n, lab, K, nperm, batch));
+    return sgl_nhood_all(c, Gi, Gp, n, lab, K, drop_diagonal != 0, nperm, seed, batch, counts, S1, S2, n_ge, n_le, null_out, nullptr);
+}
+
+extern "C" int sgl_nhood_stats(int32_t K, int32_t nperm, const int64_t* counts, const int64_t* S1, const int64_t* S2, const int64_t* n_ge,
+                               const int64_t* n_le, double* z, double* mean, double* sd, double* p_enr, double* p_dep, double* padj_enr,
+                               double* padj_dep) {
+    static const char* who = "sgl_nhood_stats";
+    if (K < 1 || K > NHOOD_MAX_K) { sgl_set_error("%s: K = %d is outside [1, %d]", who, K, NHOOD_MAX_K); return SGL_EINVAL; }
+    if (nperm < 1 || nperm > NHOOD_MAX_NPERM) { sgl_set_error("%s: nperm = %d is outside [1, %lld]", who, nperm, (long long)NHOOD_MAX_NPERM); return SGL_EINVAL; }
+    if (!counts || !S1 || !S2 || !n_ge || !n_le) { sgl_set_error("%s: NULL counts, S1, S2, n_ge or n_le", who); return SGL_EINVAL; }
+    for (int64_t q = 0; q < (int64_t)K * K; ++q)
+        if (counts[q] < 0 || S1[q] < 0 || S2[q] < 0 || n_ge[q] < 0 || n_ge[q] > nperm || n_le[q] < 0 || n_le[q] > nperm || S1[q] > ((int64_t)1 << 52) ||
+            nhood_D(nperm, S1[q], S2[q]) < 0) {
+            sgl_set_error("%s: the tallies of pair (%lld, %lld) are not those of %d permutations (a negative value, a count above nperm, or nperm * S2 < S1^2)",
+                          who, (long long)(q % K), (long long)(q / K), nperm);
+            return SGL_EINVAL;
+        }
+    nhood_stats(K, nperm, counts, S1, S2, n_ge, n_le, z, mean, sd, p_enr, p_dep, padj_enr, padj_dep);
+    return SGL_OK;
+}
+
+extern "C" int sgl_c_nhood_enrichment(const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* lab, int32_t K, int drop_diagonal, int32_t nperm,
+                                      uint64_t seed, int32_t batch, int64_t* counts, int64_t* S1, int64_t* S2, int64_t* n_ge, int64_t* n_le,
+                                      int64_t* null_out, double* z, double* mean, double* sd, double* p_enr, double* p_dep, double* padj_enr,
+                                      double* padj_dep, int64_t* info, double* stage_ms) {
+    SGLCHK(sgl_nhood_args_check("sgl_c_nhood_enrichment", Gi, Gp, n, lab, K, nperm, batch));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    const size_t KK = (size_t)K * (size_t)K;
+    std::vector<int64_t> t(5 * KK);
+    SGLCHK(sgl_nhood_all(hd.c, Gi, Gp, n, lab, K, drop_diagonal != 0, nperm, seed, batch, t.data(), t.data() + KK, t.data() + 2 * KK, t.data() + 3 * KK,
+                         t.data() + 4 * KK, null_out, stage_ms));
+    int64_t* outs[5] = {counts, S1, S2, n_ge, n_le};
+    for (int q = 0; q < 5; ++q)
+        if (outs[q]) std::copy(t.begin() + q * KK, t.begin() + (q + 1) * KK, outs[q]);
+    nhood_stats(K, nperm, t.data(), t.data() + KK, t.data() + 2 * KK, t.data() + 3 * KK, t.data() + 4 * KK, z, mean, sd, p_enr, p_dep, padj_enr,
+                padj_dep);
+    if (info) std::copy(hd.c->nhood_last, hd.c->nhood_last + 6, info);
+    return SGL_OK;
+}
+
+extern "C" int sgl_op_nhood_permute(sgl_ctx* c, int32_t n, const int32_t* lab, uint64_t seed, int32_t r0, int32_t nb, int32_t* lab_out) {
+    CTX_GUARD(c);
+    SGLCHK(nhood_state(c, "sgl_op_nhood_permute"));
+    SGLCHK(sgl_nhood_permute_args_check("sgl_op_nhood_permute", n, lab, r0, nb));
+    if (!lab_out) { sgl_set_error("sgl_op_nhood_permute: NULL lab_out"); return SGL_EINVAL; }
+    return sgl_nhood_permute_core(c, n, lab, seed, r0, nb, lab_out);
+}
+
+extern "C" int sgl_op_nhood_tally(sgl_ctx* c, const int32_t* Gi, const int32_t* Gp, int32_t n, const int32_t* labs, int32_t nb, int32_t K,
+                                  int drop_diagonal, int32_t path, int32_t perms_per_group, int64_t* counts_out) {
+    CTX_GUARD(c);
+    SGLCHK(nhood_state(c, "sgl_op_nhood_tally"));
+    SGLCHK(sgl_nhood_tally_args_check("sgl_op_nhood_tally", Gi, Gp, n, labs, nb, K, path, perms_per_group));
+    if (!counts_out) { sgl_set_error("sgl_op_nhood_tally: NULL counts_out"); return SGL_EINVAL; }
+    return sgl_nhood_tally_core(c, Gi, Gp, n, labs, nb, K, drop_diagonal != 0, path, perms_per_group, counts_out);
+}
+
+extern "C" int sgl_nhood_info(sgl_ctx* c, int64_t out[6]) {
+    CTX_GUARD(c);
+    if (!out) { sgl_set_error("sgl_nhood_info: NULL out"); return SGL_EINVAL; }
+    std::copy(c->nhood_last, c->nhood_last + 6, out);
     return SGL_OK;
 }
 
