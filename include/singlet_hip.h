@@ -711,6 +711,94 @@ SGL_API int sgl_op_nhood_tally(sgl_ctx* ctx, const int32_t* Gi, const int32_t* G
                                int drop_diagonal, int32_t path, int32_t perms_per_group, int64_t* counts_out);
 SGL_API int sgl_nhood_info(sgl_ctx* ctx, int64_t out[6]);
 
+/* Ligand-receptor interactions: which ligand-receptor pairs are expressed between which pairs of clusters more strongly than
+ * under a random relabelling of the cells -- the permutation test of CellPhoneDB (Efremova et al. 2020) and of squidpy's
+ * gr.ligrec.  The rules below are this library's own statement of the published scheme; tests/ligrec_restatement.py restates
+ * them in numpy.  NO parity with squidpy's or CellPhoneDB's seeded shuffles is claimed: the relabellings are this library's.
+ * Every sum is formed in ONE stated order, so every result is one function of the inputs, bit for bit the restatement,
+ * whatever the path, the batch or the label vectors per wave.
+ *
+ * Inputs:
+ *  - the resident matrix, m genes x n cells, its values as they are (normally after sgl_log_normalize);
+ *  - lab[n], int32 in [0, K), 1 <= K <= 256; a class without cells is allowed;
+ *  - genes[G]: distinct gene indices in [0, m), the interacting genes;
+ *  - lig[P], rec[P]: indices INTO genes.  lig[q] == rec[q] and repeated pairs are allowed;
+ *  - nperm in [1, 2^20], seed uint64, threshold in [0, 1].
+ *
+ * Label vectors: vector -1 is lab itself.  Vector r in [0, nperm) is exactly the lab_r sgl_op_nhood_permute returns for
+ * (lab, seed, r): the same seed gives the same relabellings in both tests.  The class sizes n_c are those of lab in every vector.
+ *
+ * Sums, sum_r[g, c], one order for the observed vector and the null:
+ *  - gene g's stored entries in stored order, counted from the gene's first entry, are cut into segments of 8192;
+ *  - within a segment the partial of class c is the sequential sum from +0.0, in stored order, of the values whose cell has
+ *    label c under vector r;
+ *  - the segment partials are added in ascending segment order from +0.0;
+ *  - no floating-point atomics, no contraction: the sums are a function of (gene, label vector) alone;
+ *  - nz[g, c] = the count of stored x != 0 of gene g in class c under lab (observed only, int64);
+ *  - mean_r[g, c] = sum_r[g, c] / (double)n_c, one division; NaN with n_c == 0.
+ *
+ * Score: s_r[q, a, b] = 0.5 * (mean_r[lig[q], a] + mean_r[rec[q], b]) when both means are > 0, else +0.0 (a NaN mean compares
+ * false: +0.0).  s is the score under lab.
+ * Tallies: n_ge[q, a, b] = #{r in [0, nperm): s_r >= s}, int64.
+ * Layouts: group_n[c]; nz, sum, mean at g K + c (class fastest); score and n_ge at q + P (a + K b); null_out (the s_r) at
+ * r P K^2 + q + P (a + K b).
+ *
+ * Statistics (sgl_ligrec_stats; host code, ligrec_host.h):
+ *  - expressed[g, c] = (double)nz[g, c] / (double)n_c >= threshold, false when n_c == 0 (one byte each, at g K + c);
+ *  - p = (double)(1 + n_ge) / (double)(1 + nperm) where expressed[lig, a] and expressed[rec, b] both hold, NaN elsewhere.
+ *    squidpy divides by nperm WITHOUT the + 1: its p can be 0, this one is at least 1 / (nperm + 1);
+ *  - Benjamini-Hochberg with the rule and the code of the gene set enrichment, a NaN left out: per_interaction 0 over all
+ *    P K^2 values, otherwise over the K^2 values of every pair q alone.
+ *
+ * Refusals, SGL_EINVAL before anything is uploaded or launched, every output untouched, the message naming the offender, in this
+ * order: NULL lab, genes, lig or rec; K outside [1, 256]; G outside [1, m]; P < 1; nperm out of range; a label outside [0, K)
+ * (position and value); a gene outside [0, m), or listed twice; a lig / rec index outside [0, G); a threshold outside [0, 1] or
+ * NaN; a negative batch; n != the cells of the matrix.  SGL_ESTATE exactly where sgl_markers gives it: no matrix, a team
+ * member, an all-reduce hook, a resident shard -- for a call on a context, before the arguments are looked at.  The context
+ * stays usable after every refusal.
+ *
+ * The plan (ligrec_host.h, a pure function of the sizes and the knobs):
+ *  - labels: the interleaved tables of the neighbourhood enrichment (groups of 16 label vectors, 16 adjacent bytes per cell);
+ *  - sums: one wave owns (one segment, a group of label vectors), lane l owns vector l; the wave walks the segment in stored
+ *    order and each lane adds the value to its own bin [class][lane].  LDS path: the K x vpw double bins of a wave in at most
+ *    32 KiB -- vpw = 64 vectors per wave up to K = 64, 32 up to 128, 16 up to 256 -- and as many waves per workgroup (at most 8)
+ *    as 64 KiB hold.  Global path (forced only): the same bins in global scratch, the same bits.  A second kernel adds the
+ *    segment partials and divides;
+ *  - batch: label vectors per batch; 0: what 256 MiB hold at n + (segments + 2 G) K x 8 bytes per vector, a multiple of 64, at
+ *    least 64.
+ *
+ * sgl_ligrec: reads only the resident matrix (a fit in progress continues with its bits).  All work goes to the context's stream
+ * (sgl_set_stream), which is synchronised before the call returns.  Any output may be NULL; null_out (nperm x P x K x K doubles)
+ * is filled only when given.  The result does not depend on batch.
+ * sgl_c_ligrec: one-shot from a dgCMatrix in a context of its own; additionally the statistics, info (sgl_ligrec_info's eight
+ * values, may be NULL) and stage_ms[3] by events (labels; sums; tally; may be NULL).
+ * sgl_ligrec_stats: host only, no device; tallies that cannot be those of nperm permutations are refused.
+ * sgl_op_ligrec_sums: the sums of nb given label vectors (labs nb x n int32, each validated) as nb x G x K doubles at
+ * (r G + g) K + c.  path 0 automatic, 1 the LDS path, 2 the global path; vectors_per_wave 0 the plan's value, otherwise a power
+ * of two up to what a wave holds at this K (else SGL_EINVAL).  The result depends on neither.
+ * sgl_op_ligrec_tally: score and n_ge (and the s_r) from mean tables alone: mean_obs G x K, means nb x G x K; no matrix is read.
+ * sgl_ligrec_info: out[0] the sums' path (1 LDS, 2 global, 0 none ran), out[1] the label vectors per wave, out[2] the batches,
+ * out[3] the vectors per batch, out[4] the LDS bytes per workgroup, out[5] the waves per workgroup, out[6] / out[7] the listed
+ * genes on the LDS / on the global path, of the last sgl_ligrec / sgl_c_ligrec / sgl_op_ligrec_sums on the context.
+ * NOT provided: multi-subunit complexes (CellPhoneDB's min over the subunits), unlabelled cells, a team form, an R shim entry, an
+ * interaction database -- the caller brings the pairs. */
+SGL_API int sgl_ligrec(sgl_ctx* ctx, const int32_t* lab, int32_t n, int32_t K, const int32_t* genes, int32_t G, const int32_t* lig, const int32_t* rec,
+                       int32_t P, int32_t nperm, uint64_t seed, int32_t batch, int64_t* group_n, int64_t* nz, double* sum, double* mean,
+                       double* score, int64_t* n_ge, double* null_out);
+SGL_API int sgl_c_ligrec(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, const int32_t* lab, int32_t K,
+                         const int32_t* genes, int32_t G, const int32_t* lig, const int32_t* rec, int32_t P, int32_t nperm, uint64_t seed,
+                         int32_t batch, double threshold, int per_interaction, int64_t* group_n, int64_t* nz, double* sum, double* mean,
+                         double* score, int64_t* n_ge, double* null_out, uint8_t* expressed, double* p, double* padj, int64_t* info,
+                         double* stage_ms);
+SGL_API int sgl_ligrec_stats(int32_t K, int32_t G, int32_t P, int32_t nperm, const int64_t* group_n, const int64_t* nz, const int32_t* lig,
+                             const int32_t* rec, const int64_t* n_ge, double threshold, int per_interaction, uint8_t* expressed, double* p,
+                             double* padj);
+SGL_API int sgl_op_ligrec_sums(sgl_ctx* ctx, const int32_t* labs, int32_t n, int32_t nb, int32_t K, const int32_t* genes, int32_t G, int32_t path,
+                               int32_t vectors_per_wave, double* sum_out);
+SGL_API int sgl_op_ligrec_tally(sgl_ctx* ctx, const double* mean_obs, const double* means, int32_t nb, int32_t K, int32_t G, const int32_t* lig,
+                                const int32_t* rec, int32_t P, double* score_out, int64_t* n_ge_out, double* null_out);
+SGL_API int sgl_ligrec_info(sgl_ctx* ctx, int64_t out[8]);
+
 /* Start a fit at rank k.  w_init: k x nrow host array, or NULL to fill W on
  * the device with the synthetic init ((rand_{S+2}(f,g) >> 11) + 0.5) * 2^-53.
  * h = 0, d = 1 as in src/singlet.cpp:639-641.

@@ -95,6 +95,15 @@ SIGNATURES = {
     "sgl_op_nhood_permute": (C.c_int, [C.c_void_p, C.c_int32, i32p, C.c_uint64, C.c_int32, C.c_int32, i32p]),
     "sgl_op_nhood_tally": (C.c_int, [C.c_void_p, i32p, i32p, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int, C.c_int32, C.c_int32, i64p]),
     "sgl_nhood_info": (C.c_int, [C.c_void_p, i64p]),
+    "sgl_ligrec": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int32, i32p, C.c_int32, i32p, i32p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32,
+                             i64p, i64p, f64p, f64p, f64p, i64p, f64p]),
+    "sgl_c_ligrec": (C.c_int, _CSC + [C.c_int32, C.c_int32, i32p, C.c_int32, i32p, C.c_int32, i32p, i32p, C.c_int32, C.c_int32, C.c_uint64,
+                                      C.c_int32, C.c_double, C.c_int, i64p, i64p, f64p, f64p, f64p, i64p, f64p, u8p, f64p, f64p, i64p, f64p]),
+    "sgl_ligrec_stats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, i64p, i64p, i32p, i32p, i64p, C.c_double, C.c_int, u8p, f64p,
+                                   f64p]),
+    "sgl_op_ligrec_sums": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int32, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, f64p]),
+    "sgl_op_ligrec_tally": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, C.c_int32, f64p, i64p, f64p]),
+    "sgl_ligrec_info": (C.c_int, [C.c_void_p, i64p]),
     "sgl_c_project_model": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                              C.c_uint16, f64p, f64p]),
     "sgl_rcpp_predict": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,

@@ -122,6 +122,55 @@ def nhood_labels(labels, n, n_classes, who):
     return np.ascontiguousarray(g, dtype=np.int32), K
 
 
+LIGREC_INFO = ("path", "vectors_per_wave", "batches", "batch", "lds_bytes", "waves", "lds_genes", "global_genes")
+
+
+def _index_list(a, who, name):
+    a = np.asarray(a)
+    if a.size == 0:
+        a = np.zeros(0, dtype=np.int32)
+    if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (a.min() < -2**31 or a.max() >= 2**31)):
+        raise ValueError("%s: %s must be a one-dimensional list of 32-bit indices" % (who, name))
+    return np.ascontiguousarray(a, dtype=np.int32) if a.size else np.zeros(1, dtype=np.int32)[:0]
+
+
+def ligrec_inputs(labels, n, n_classes, genes, lig, rec, who):
+    """(lab, K, genes, G, lig, rec, P) of the ligand-receptor calls: one integer class per cell, distinct 0-based gene indices,
+    and the pairs as indices into genes.  The library checks the content and names the offender; only what cannot be marshalled
+    is refused here."""
+    lab, K = nhood_labels(labels, n, n_classes, who)
+    g, lg, rc = _index_list(genes, who, "genes"), _index_list(lig, who, "lig"), _index_list(rec, who, "rec")
+    if lg.shape != rc.shape:
+        raise ValueError("%s: lig and rec must hold one index each per pair" % who)
+    return lab, K, g, int(g.shape[0]), lg, rc, int(lg.shape[0])
+
+
+def ligrec_call(fn, K, G, P, nperm, return_null, with_stats=False):
+    """Shared by Context.ligrec and api.c_ligrec: fn(group_n, nz, sum, mean, score, n_ge, null_out[, expressed, p, padj, info,
+    stage_ms]) is the library call with everything before the outputs bound.  Returns the dict of the arrays: "group_n" (K),
+    "nz", "sum", "mean" (G x K), "score", "n_ge" (P x K x K, [q, a, b] = ligand class a, receptor class b), with return_null
+    "null" (nperm x P x K x K); with_stats also "expressed" (G x K bool), "p", "padj", "info" and "stage_ms"."""
+    kk, gg, pp = max(min(K, 256), 1), max(G, 1), max(P, 1)   # outside the legal ranges the library refuses before it writes
+    group_n, nz = np.zeros(kk, dtype=np.int64), np.zeros((gg, kk), dtype=np.int64)
+    s, mean = np.zeros((gg, kk)), np.zeros((gg, kk))
+    score, n_ge = np.zeros((kk, kk, pp)), np.zeros((kk, kk, pp), dtype=np.int64)
+    null = np.zeros((max(min(int(nperm), 1 << 20), 1), kk, kk, pp)) if return_null else None
+    args = [ptr(group_n, i64p), ptr(nz, i64p), ptr(s, f64p), ptr(mean, f64p), ptr(score, f64p), ptr(n_ge, i64p), ptr(null, f64p)]
+    if with_stats:
+        ex, p, padj = np.zeros((gg, kk), dtype=np.uint8), np.zeros((kk, kk, pp)), np.zeros((kk, kk, pp))
+        info, ms = np.zeros(8, dtype=np.int64), np.zeros(3)
+        args += [ptr(ex, C.POINTER(C.c_uint8)), ptr(p, f64p), ptr(padj, f64p), ptr(info, i64p), ptr(ms, f64p)]
+    check(fn(*args))
+    out = {"group_n": group_n, "nz": nz, "sum": s, "mean": mean, "score": np.ascontiguousarray(score.transpose(2, 1, 0)),
+           "n_ge": np.ascontiguousarray(n_ge.transpose(2, 1, 0))}
+    if return_null:
+        out["null"] = np.ascontiguousarray(null.transpose(0, 3, 2, 1))
+    if with_stats:
+        out.update(expressed=ex.astype(bool), p=np.ascontiguousarray(p.transpose(2, 1, 0)), padj=np.ascontiguousarray(padj.transpose(2, 1, 0)),
+                   info=dict(zip(LIGREC_INFO, (int(v) for v in info))), stage_ms=ms)
+    return out
+
+
 def markers_call(fn, nrow, labels, G, transform, pseudocount):
     """Shared by Context.markers and api.c_markers: fn(labels, n_groups, transform, pseudocount, group_n, pos, sum, rank2, tie,
     pct_in, pct_out, log2fc, z, p) is the library call.  Returns the dict of the arrays, the per-(gene, cluster) ones as

@@ -49,7 +49,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, ptr
-from ._marshal import NHOOD_INFO, NHOOD_STATS, NHOOD_TALLIES, nhood_labels, ArdOutputs, NmfOutputs, annotate_call, annotate_tail, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, knn_weighting, label_list, markers_call, signature_call
+from ._marshal import NHOOD_INFO, NHOOD_STATS, NHOOD_TALLIES, ligrec_call, ligrec_inputs, nhood_labels, ArdOutputs, NmfOutputs, annotate_call, annotate_tail, colmajor, csc_ptrs, gsea_inputs, gsea_score_type, knn_call, knn_ivf_shape, knn_method, knn_metric, knn_recall, knn_weighting, label_list, markers_call, signature_call
 from .context import _chunk_lists, _link_image, make_callbacks
 from .native import NativeMatrix
 from .sparse import as_dgCMatrix, dgCMatrix
@@ -3074,3 +3074,159 @@ def interaction_matrix(labels, graph, normalized=False, n_classes=None, drop_dia
         return counts
     rows = counts.sum(axis=1, keepdims=True)
     return np.divide(counts, rows, out=np.zeros(counts.shape), where=rows > 0)
+
+
+# ---------------------------------------------------------------------------
+# Ligand-receptor interactions between clusters (CellPhoneDB's / squidpy's gr.ligrec permutation test; include/singlet_hip.h,
+# "Ligand-receptor interactions")
+# ---------------------------------------------------------------------------
+def ligrec_stats(nperm, group_n, nz, lig, rec, n_ge, threshold=0.01, per_interaction=False):
+    """The expressed mask, p and its Benjamini-Hochberg adjustment from the tallies of a ligand-receptor call (sgl_ligrec_stats;
+    host code of the library, no device needed).  group_n K, nz G x K, n_ge P x K x K ([q, a, b] = ligand class a, receptor class
+    b), lig / rec indices into the G genes.  p = (1 + n_ge) / (1 + nperm) where ligand and receptor are expressed (nz / n_c >=
+    threshold), NaN elsewhere; padj over all P K^2 values, or with per_interaction over the K^2 of every pair alone.  Returns
+    {"expressed" (G x K bool), "p", "padj" (P x K x K)}."""
+    gn, z, ge = np.asarray(group_n), np.asarray(nz), np.asarray(n_ge)
+    lg, rc = np.asarray(lig), np.asarray(rec)
+    if gn.ndim != 1 or z.ndim != 2 or ge.ndim != 3 or lg.ndim != 1 or lg.shape != rc.shape or any(a.dtype.kind not in "iu" for a in (gn, z, ge, lg, rc)):
+        raise ValueError("ligrec_stats: group_n (K), nz (G x K), n_ge (P x K x K), lig and rec (P) must be integer arrays")
+    K, G, P = int(gn.shape[0]), int(z.shape[0]), int(lg.shape[0])
+    if K < 1 or G < 1 or P < 1 or z.shape != (G, K) or ge.shape != (P, K, K):
+        raise ValueError("ligrec_stats: group_n (K), nz (G x K), n_ge (P x K x K), lig and rec (P) must agree in K, G and P")
+    gn, z = np.ascontiguousarray(gn, dtype=np.int64), np.ascontiguousarray(z, dtype=np.int64)
+    ge = np.ascontiguousarray(ge.transpose(2, 1, 0), dtype=np.int64)
+    lg, rc = np.ascontiguousarray(lg, dtype=np.int32), np.ascontiguousarray(rc, dtype=np.int32)
+    ex, p, padj = np.zeros((G, K), dtype=np.uint8), np.zeros((K, K, P)), np.zeros((K, K, P))
+    i64p = _lib.i64p
+    check(_lib.load().sgl_ligrec_stats(K, G, P, int(nperm), ptr(gn, i64p), ptr(z, i64p), ptr(lg, i32p), ptr(rc, i32p), ptr(ge, i64p), float(threshold),
+                                       int(bool(per_interaction)), ptr(ex, _lib.u8p), ptr(p, f64p), ptr(padj, f64p)))
+    return {"expressed": ex.astype(bool), "p": np.ascontiguousarray(p.transpose(2, 1, 0)), "padj": np.ascontiguousarray(padj.transpose(2, 1, 0))}
+
+
+def c_ligrec(A, labels, genes, lig, rec, n_classes=None, threshold=0.01, nperm=1000, seed=0, batch=0, per_interaction=False, return_null=False):
+    """The one-shot form of Context.ligrec (sgl_c_ligrec): A a dgCMatrix or anything as_dgCMatrix accepts, in a context of its
+    own.  The dict of Context.ligrec plus the statistics of ligrec_stats, "info" (Context.ligrec_info's fields) and "stage_ms"
+    (labels, sums, tally)."""
+    A = as_dgCMatrix(A)
+    lab, K, g, G, lg, rc, P = ligrec_inputs(labels, A.ncol, n_classes, genes, lig, rec, "c_ligrec")
+    L = _lib.load()
+    return ligrec_call(lambda *a: L.sgl_c_ligrec(*csc_ptrs(A), A.nrow, A.ncol, ptr(lab, i32p), K, ptr(g, i32p), G, ptr(lg, i32p), ptr(rc, i32p), P,
+                                                 int(nperm), int(seed), int(batch), float(threshold), int(bool(per_interaction)), *a),
+                       K, G, P, nperm, return_null, with_stats=True)
+
+
+def read_interactions(path):
+    """The (ligand, receptor) name pairs of a two-column tab-separated file: one pair per line; empty lines and lines that
+    start with '#' are skipped; a line without exactly two non-empty columns is refused with its number."""
+    pairs = []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            line = line.rstrip("\r\n")
+            if not line.strip() or line.startswith("#"):
+                continue
+            cols = [c.strip() for c in line.split("\t")]
+            if len(cols) != 2 or not cols[0] or not cols[1]:
+                raise ValueError("read_interactions: %s line %d: a ligand and a receptor separated by one tab" % (path, no))
+            pairs.append((cols[0], cols[1]))
+    return pairs
+
+
+def ligrec_parse(interactions, gene_names=None, nrow=None, missing="error"):
+    """The host half of ligrec: interactions = a list of (ligand, receptor) -- names looked up in gene_names (the first row of a
+    name that occurs twice), or 0-based int rows in [0, nrow) when gene_names is None.  A pair with a name absent from
+    gene_names is dropped and reported (missing="skip") or refused (missing="error").  Returns (genes, lig, rec, pairs,
+    dropped): the distinct rows in order of first use, the pairs as indices into them, the kept pairs as given."""
+    if missing not in ("skip", "error"):
+        raise ValueError("ligrec: missing must be 'skip' or 'error'")
+    try:
+        given = [tuple(p) for p in interactions]
+    except TypeError:
+        given = None
+    if not given or any(len(p) != 2 for p in given):
+        raise ValueError("ligrec: interactions must be a non-empty list of (ligand, receptor) pairs")
+    index = None
+    if gene_names is not None:
+        index = {}
+        for r, g in enumerate(gene_names):
+            index.setdefault(g.decode() if isinstance(g, bytes) else str(g), r)
+        nrow = len(gene_names)
+    rows, slot, lig, rec, kept, dropped = [], {}, [], [], [], []
+    for pair in given:
+        at = []
+        for g in pair:
+            if index is not None:
+                r = index.get(g.decode() if isinstance(g, bytes) else str(g))
+            else:
+                if isinstance(g, (str, bytes)) or int(g) != g or not 0 <= int(g) < nrow:
+                    raise ValueError("ligrec: %r is no gene row in [0, %d) (give gene_names to use names)" % (g, nrow))
+                r = int(g)
+            at.append(r)
+        if None in at:
+            if missing == "error":
+                raise ValueError("ligrec: %r of the pair %r is not among the genes of the matrix (missing='skip' drops such pairs)"
+                                 % (pair[at.index(None)], pair))
+            dropped.append(pair)
+            continue
+        for r in at:
+            if r not in slot:
+                slot[r] = len(rows)
+                rows.append(r)
+        lig.append(slot[at[0]])
+        rec.append(slot[at[1]])
+        kept.append(pair)
+    if not kept:
+        raise ValueError("ligrec: no pair is left: none has both genes in the matrix")
+    return np.array(rows, dtype=np.int32), np.array(lig, dtype=np.int32), np.array(rec, dtype=np.int32), kept, dropped
+
+
+def ligrec(A, labels, interactions, gene_names=None, threshold=0.01, nperm=1000, seed=0, n_classes=None, missing="error", per_interaction=False,
+           batch=0):
+    """Which ligand-receptor pairs are expressed between which pairs of clusters more strongly than under a random relabelling
+    of the cells: the permutation test of CellPhoneDB and of squidpy's gr.ligrec on the device (sgl_ligrec; the rules are stated in
+    include/singlet_hip.h, "Ligand-receptor interactions" -- this library's own statement with its own relabellings, NO parity with
+    squidpy's or CellPhoneDB's seeded shuffles, no multi-subunit complexes, no interaction database).  A: a dgCMatrix, anything
+    as_dgCMatrix accepts, a native(...) object, or a Context that holds the (normally log-normalised) matrix.  labels: one integer
+    class in [0, n_classes) per cell.  interactions: a list of (ligand, receptor) gene names (int rows when there are no
+    gene_names), or the path of a two-column TSV file (read_interactions).  gene_names None: the row names of A when it has
+    them.  missing "error" refuses a pair with a name that is not in the matrix, "skip" drops and reports it.  Every argument is
+    refused before the first upload.  Returns {"means", "p", "padj" (P x K x K; [q, a, b] = ligand in class a, receptor in class b;
+    means is the score, p is NaN where ligand or receptor is expressed in less than `threshold` of the class), "expressed"
+    (P x K x K bool), "pairs", "dropped", "n_ge", "class_sizes"}."""
+    from .context import Context
+    who = "ligrec"
+    if isinstance(interactions, (str, bytes, os.PathLike)):
+        interactions = read_interactions(interactions)
+    is_ctx, is_native = isinstance(A, Context), isinstance(A, NativeMatrix)
+    if not is_ctx and not is_native:
+        A = as_dgCMatrix(A)
+    if gene_names is None and not is_ctx and A.Dimnames[0] is not None:
+        gene_names = A.Dimnames[0]
+    nrow, ncol = (A.dims()[0], A.dims()[1]) if is_ctx else (A.nrow, A.ncol)
+    if gene_names is not None and len(gene_names) != nrow:
+        raise ValueError("%s: gene_names must name the %d rows of the matrix" % (who, nrow))
+    lab, K = _nhood_classes(who, labels, n_classes)
+    if lab.shape[0] != ncol:
+        raise ValueError("%s: %d labels, the matrix has %d cells" % (who, lab.shape[0], ncol))
+    if int(nperm) != nperm or not 1 <= nperm <= 1 << 20:
+        raise ValueError("%s: nperm = %r is outside [1, 2^20]" % (who, nperm))
+    if int(batch) != batch or batch < 0:
+        raise ValueError("%s: batch = %r is negative" % (who, batch))
+    if int(seed) != seed or not 0 <= seed < 2**64:
+        raise ValueError("%s: seed = %r is no unsigned 64-bit integer" % (who, seed))
+    if not 0.0 <= float(threshold) <= 1.0:
+        raise ValueError("%s: threshold = %r is outside [0, 1]" % (who, threshold))
+    genes, lg, rc, kept, dropped = ligrec_parse(interactions, gene_names, nrow, missing)
+
+    def on(ctx):
+        t = ctx.ligrec(lab, genes, lg, rc, K, nperm, seed, batch)
+        t.update(ligrec_stats(nperm, t["group_n"], t["nz"], lg, rc, t["n_ge"], threshold, per_interaction))
+        return t
+    if is_ctx:
+        t = on(A)
+    elif is_native:
+        t = _on_native(A, lambda ctx, fits: on(ctx))
+    else:
+        t = c_ligrec(A, lab, genes, lg, rc, K, threshold, nperm, seed, batch, per_interaction)
+    ex = t["expressed"]
+    return {"means": t["score"], "p": t["p"], "padj": t["padj"], "expressed": ex[lg][:, :, None] & ex[rc][:, None, :], "pairs": kept,
+            "dropped": dropped, "n_ge": t["n_ge"], "class_sizes": t["group_n"]}

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, f64p, i32p, i64p, ptr, u64p, u8p
-from ._marshal import (KNN_INDEX_FIELDS, MARKER_TRANSFORMS, NHOOD_INFO, NHOOD_TALLIES, ArdOutputs, NmfOutputs, annotate_call, colmajor, csc_ptrs, gsea_inputs,
+from ._marshal import (KNN_INDEX_FIELDS, LIGREC_INFO, ligrec_call, ligrec_inputs, MARKER_TRANSFORMS, NHOOD_INFO, NHOOD_TALLIES, ArdOutputs, NmfOutputs, annotate_call, colmajor, csc_ptrs, gsea_inputs,
                        gsea_score_type, knn_call, knn_ivf_shape, knn_lists_in, knn_method, knn_metric, knn_weighting, label_list, markers_call, nhood_labels,
                        signature_call, transfer_call)
 from .sparse import as_dgCMatrix
@@ -689,6 +689,55 @@ class Context(_Handle):
         out = np.zeros(6, dtype=np.int64)
         check(self._L.sgl_nhood_info(self._h, ptr(out, i64p)))
         return dict(zip(NHOOD_INFO, (int(v) for v in out)))
+
+    def ligrec(self, labels, genes, lig, rec, n_classes=None, nperm=1000, seed=0, batch=0, return_null=False):
+        """The ligand-receptor permutation test of the resident matrix (sgl_ligrec; the rules: include/singlet_hip.h,
+        "Ligand-receptor interactions"): genes = distinct 0-based gene indices, lig / rec = indices into genes, one pair each.
+        Returns {"group_n" (K), "nz", "sum", "mean" (G x K), "score", "n_ge" (P x K x K, [q, a, b] = ligand class a, receptor
+        class b)}; with return_null also "null", nperm x P x K x K.  The matrix and a running fit are only read; ligrec_info()
+        says what ran; ligrec_stats turns the tallies into p and padj."""
+        lab, K, g, G, lg, rc, P = ligrec_inputs(labels, None, n_classes, genes, lig, rec, "ligrec")
+        return ligrec_call(lambda *a: self._L.sgl_ligrec(self._h, ptr(lab, i32p), int(lab.shape[0]), K, ptr(g, i32p), G, ptr(lg, i32p), ptr(rc, i32p), P,
+                                                         int(nperm), int(seed), int(batch), *a), K, G, P, nperm, return_null)
+
+    def op_ligrec_sums(self, labs, n_classes, genes, path=0, vectors_per_wave=0):
+        """The per-class sums of the listed genes under each of nb given label vectors (labs nb x n; sgl_op_ligrec_sums):
+        nb x G x K doubles.  path 0 automatic, 1 the LDS path, 2 the global path; vectors_per_wave 0: the plan's value.  The
+        result depends on neither; ligrec_info() says what ran."""
+        L = np.asarray(labs)
+        if L.ndim != 2 or (L.size and L.dtype.kind not in "iub"):
+            raise ValueError("op_ligrec_sums: labs must be an nb x n integer matrix with one column per cell")
+        L = np.ascontiguousarray(L, dtype=np.int32)
+        g = np.ascontiguousarray(np.asarray(genes), dtype=np.int32)
+        nb, n, K, G = int(L.shape[0]), int(L.shape[1]), int(n_classes), int(g.shape[0])
+        out = np.zeros((max(nb, 1), max(G, 1), max(min(K, 256), 1)))
+        check(self._L.sgl_op_ligrec_sums(self._h, ptr(L, i32p), n, nb, K, ptr(g, i32p), G, int(path), int(vectors_per_wave), ptr(out, f64p)))
+        return out[:nb]
+
+    def op_ligrec_tally(self, mean_obs, means, lig, rec, return_null=False):
+        """The scores and the tallies from mean tables alone (sgl_op_ligrec_tally): mean_obs G x K, means nb x G x K.  Returns
+        (score, n_ge), P x K x K each; with return_null also the s_r, nb x P x K x K."""
+        mo, mm = np.ascontiguousarray(mean_obs, dtype=np.float64), np.ascontiguousarray(means, dtype=np.float64)
+        if mo.ndim != 2 or mm.ndim != 3 or mm.shape[1:] != mo.shape:
+            raise ValueError("op_ligrec_tally: mean_obs must be G x K and means nb x G x K")
+        lg, rc = np.ascontiguousarray(lig, dtype=np.int32), np.ascontiguousarray(rec, dtype=np.int32)
+        if lg.ndim != 1 or lg.shape != rc.shape:
+            raise ValueError("op_ligrec_tally: lig and rec must hold one index each per pair")
+        G, K, nb, P = int(mo.shape[0]), int(mo.shape[1]), int(mm.shape[0]), int(lg.shape[0])
+        kk, pp = max(min(K, 256), 1), max(P, 1)
+        score, n_ge = np.zeros((kk, kk, pp)), np.zeros((kk, kk, pp), dtype=np.int64)
+        null = np.zeros((max(nb, 1), kk, kk, pp)) if return_null else None
+        check(self._L.sgl_op_ligrec_tally(self._h, ptr(mo, f64p), ptr(mm, f64p), nb, K, G, ptr(lg, i32p), ptr(rc, i32p), P, ptr(score, f64p),
+                                          ptr(n_ge, i64p), ptr(null, f64p)))
+        out = (np.ascontiguousarray(score.transpose(2, 1, 0)), np.ascontiguousarray(n_ge.transpose(2, 1, 0)))
+        return out + (np.ascontiguousarray(null.transpose(0, 3, 2, 1)),) if return_null else out
+
+    def ligrec_info(self):
+        """What the last ligand-receptor call on this context ran (sgl_ligrec_info): {"path" (1 LDS, 2 global, 0 none),
+        "vectors_per_wave", "batches", "batch", "lds_bytes", "waves", "lds_genes", "global_genes"}."""
+        out = np.zeros(8, dtype=np.int64)
+        check(self._L.sgl_ligrec_info(self._h, ptr(out, i64p)))
+        return dict(zip(LIGREC_INFO, (int(v) for v in out)))
 
     def variable_features(self, nfeatures=2000, span=0.3, vmax=None, expected_var=None):
         """Variable features of the resident counts (sgl_variable_features; Seurat's vst selection under this library's

@@ -504,3 +504,29 @@ int sgl_nhood_all(sgl_ctx* c, const int32_t* Gi, const int32_t* Gp, int64_t n, c
                   int64_t batch, int64_t* counts, int64_t* S1, int64_t* S2, int64_t* n_ge, int64_t* n_le, int64_t* null_out, double* stage_ms) {
     return nh_finish(c, nh_all_on(c, Gi, Gp, n, lab, K, drop, nperm, seed, batch, counts, S1, S2, n_ge, n_le, null_out, stage_ms));
 }
+
+// ---- the label tables for the other permutation tests (kernels_ligrec.hip) --------------------------------------------------------------
+// The same keys, sorts and gather, always in groups of NHOOD_MAX_PG: vector l of the table is byte l % 16 of cell c in group l / 16,
+// out8[((l / 16) n + c) 16 + l % 16].  Nothing of the neighbourhood calls above goes through these.
+struct sgl_nhood_labeller {
+    NhPermuter Q;
+};
+int sgl_nhood_labeller_create(sgl_ctx* c, int64_t n, int64_t batch, sgl_nhood_labeller** out) {
+    (void)c;
+    NhoodPlan P;
+    int64_t at, val;
+    (void)nhood_plan(n, 0, NHOOD_MAX_K, batch, 0, 2, NHOOD_MAX_PG, nh_sort_switch(), &P, &at, &val);
+    sgl_nhood_labeller* h = new sgl_nhood_labeller;
+    const int rc = h->Q.alloc(n, P);
+    if (rc != SGL_OK) { delete h; return rc; }
+    *out = h;
+    return SGL_OK;
+}
+void sgl_nhood_labeller_free(sgl_nhood_labeller* h) { delete h; }
+int sgl_nhood_labels_permuted(sgl_ctx* c, sgl_nhood_labeller* h, const int32_t* dlab, int64_t n, uint64_t seed, int64_t r0, int64_t nb, uint8_t* out8) {
+    return nh_permute(c, h->Q, dlab, n, seed, r0, nb, NHOOD_MAX_PG, out8);
+}
+int sgl_nhood_labels_given(sgl_ctx* c, const int32_t* dlabs, int64_t lab_stride, int64_t n, int64_t np, uint8_t* out8) {
+    Phase ph(c, SGL_PH_SCALE);
+    return nh_gather(c->stream, NHOOD_MAX_PG, nullptr, dlabs, lab_stride, n, np, out8);
+}

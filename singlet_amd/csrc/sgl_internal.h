@@ -275,6 +275,10 @@ struct sgl_ctx {
     // sgl_nhood_info: the tally's path (1 LDS, 2 global; 0: none ran), the permutations per group, the batches, the permutations
     // per batch, the LDS bytes per workgroup and the sort (0 segmented, 1 device-wide) of the last neighbourhood enrichment call
     int64_t nhood_last[6] = {0, 0, 0, 0, 0, 0};
+    // sgl_ligrec_info: the sums' path (1 LDS, 2 global; 0: none ran), the label vectors per wave, the batches, the vectors per
+    // batch, the LDS bytes per workgroup, the waves per workgroup and the listed genes on the LDS and on the global path, of the
+    // last ligand-receptor call on this context
+    int64_t ligrec_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     sgl_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
@@ -563,6 +567,37 @@ int sgl_nhood_tally_core(sgl_ctx* c, const int32_t* Gi, const int32_t* Gp, int64
 // the whole call: any output may be NULL; null_out nperm x K x K; stage_ms (3 values, may be NULL): the stages timed by events
 int sgl_nhood_all(sgl_ctx* c, const int32_t* Gi, const int32_t* Gp, int64_t n, const int32_t* lab, int K, int drop, int64_t nperm, uint64_t seed,
                   int64_t batch, int64_t* counts, int64_t* S1, int64_t* S2, int64_t* n_ge, int64_t* n_le, int64_t* null_out, double* stage_ms);
+
+// the interleaved label tables of the permutation tests, made by the neighbourhood unit's keys, sorts and gather in groups of 16
+// (kernels_nhood.hip): vector l of a table is out8[((l / 16) n + c) 16 + l % 16]; a slot past the last vector holds label 0.
+// dlab / dlabs and out8 are the DEVICE's; nothing synchronises.  A labeller holds the sort buffers of batches of up to `batch`.
+struct sgl_nhood_labeller;
+int sgl_nhood_labeller_create(sgl_ctx* c, int64_t n, int64_t batch, sgl_nhood_labeller** out);
+void sgl_nhood_labeller_free(sgl_nhood_labeller* h);
+// lab_r of the permutations [r0, r0 + nb)
+int sgl_nhood_labels_permuted(sgl_ctx* c, sgl_nhood_labeller* h, const int32_t* dlab, int64_t n, uint64_t seed, int64_t r0, int64_t nb, uint8_t* out8);
+// np given label vectors, vector l at dlabs + l * lab_stride
+int sgl_nhood_labels_given(sgl_ctx* c, const int32_t* dlabs, int64_t lab_stride, int64_t n, int64_t np, uint8_t* out8);
+
+// ligand-receptor interactions (kernels_ligrec.hip; include/singlet_hip.h, "Ligand-receptor interactions").  All arrays are the
+// HOST's; every call only reads the context (it records what it ran in ligrec_last), allocates its own temporaries and
+// synchronises the stream before it returns.  The *_args_check functions hold every refusal and launch nothing.
+int sgl_ligrec_args_check(const char* who, const int32_t* lab, int64_t n, int64_t K, const int32_t* genes, int64_t G, int64_t m, const int32_t* lig,
+                          const int32_t* rec, int64_t P, int64_t nperm, double threshold, int64_t batch, int64_t ncol);
+int sgl_ligrec_sums_args_check(const char* who, const int32_t* labs, int64_t n, int64_t nb, int64_t K, const int32_t* genes, int64_t G, int64_t m,
+                               int path, int64_t vpw, int64_t ncol);
+int sgl_ligrec_tally_args_check(const char* who, const double* mean_obs, const double* means, int64_t nb, int64_t K, int64_t G, const int32_t* lig,
+                                const int32_t* rec, int64_t P);
+// the whole call over c->At: any output may be NULL; group_n K; nz, sum, mean G x K (class fastest); score, n_ge P x K x K at
+// q + P (a + K b); null_out nperm x P x K x K; stage_ms (3 values, may be NULL): the stages timed by events
+int sgl_ligrec_all(sgl_ctx* c, const int32_t* lab, int K, const int32_t* genes, int64_t G, const int32_t* lig, const int32_t* rec, int64_t P,
+                   int64_t nperm, uint64_t seed, int64_t batch, int64_t* group_n, int64_t* nz, double* sum, double* mean, double* score, int64_t* n_ge,
+                   double* null_out, double* stage_ms);
+// sum_out nb x G x K: the sums of nb given label vectors; path 0 / 1 / 2, vpw 0: the plan's
+int sgl_ligrec_sums_core(sgl_ctx* c, const int32_t* labs, int64_t nb, int K, const int32_t* genes, int64_t G, int path, int64_t vpw, double* sum_out);
+// score_out, n_ge_out P x K x K, null_out nb x P x K x K from the means alone (no matrix is read); any output may be NULL
+int sgl_ligrec_tally_core(sgl_ctx* c, const double* mean_obs, const double* means, int64_t nb, int K, int64_t G, const int32_t* lig,
+                          const int32_t* rec, int64_t P, double* score_out, int64_t* n_ge_out, double* null_out);
 
 // gene set enrichment (kernels_gsea.hip; include/singlet_hip.h, "Gene set enrichment").  All arrays are the HOST's; every call
 // only reads the context (it records what it ran in gsea_last), allocates its own temporaries and synchronises the stream

@@ -9,6 +9,7 @@
 #include "doublet_host.h"
 #include "moran_host.h"
 #include "nhood_host.h"
+#include "ligrec_host.h"
 
 #include <math.h>
 #include <string.h>
@@ -2462,6 +2463,92 @@ extern "C" int sgl_nhood_info(sgl_ctx* c, int64_t out[6]) {
     CTX_GUARD(c);
     if (!out) { sgl_set_error("sgl_nhood_info: NULL out"); return SGL_EINVAL; }
     std::copy(c->nhood_last, c->nhood_last + 6, out);
+    return SGL_OK;
+}
+
+// Ligand-receptor interactions (include/singlet_hip.h; kernels_ligrec.hip, ligrec_host.h): the state where sgl_markers refuses it,
+// then the refusals of the arguments, then passes that only read the context.
+extern "C" int sgl_ligrec(sgl_ctx* c, const int32_t* lab, int32_t n, int32_t K, const int32_t* genes, int32_t G, const int32_t* lig, const int32_t* rec,
+                          int32_t P, int32_t nperm, uint64_t seed, int32_t batch, int64_t* group_n, int64_t* nz, double* sum, double* mean,
+                          double* score, int64_t* n_ge, double* null_out) {
+    CTX_GUARD(c);
+    SGLCHK(markers_state(c, "sgl_ligrec"));
+    SGLCHK(sgl_ligrec_args_check("sgl_ligrec", lab, n, K, genes, G, c->A.nrow, lig, rec, P, nperm, 0.0, batch, c->A.ncol));
+    return sgl_ligrec_all(c, lab, K, genes, G, lig, rec, P, nperm, seed, batch, group_n, nz, sum, mean, score, n_ge, null_out, nullptr);
+}
+
+extern "C" int sgl_ligrec_stats(int32_t K, int32_t G, int32_t P, int32_t nperm, const int64_t* group_n, const int64_t* nz, const int32_t* lig,
+                                const int32_t* rec, const int64_t* n_ge, double threshold, int per_interaction, uint8_t* expressed, double* p,
+                                double* padj) {
+    static const char* who = "sgl_ligrec_stats";
+    if (!group_n || !nz || !lig || !rec || !n_ge) { sgl_set_error("%s: NULL group_n, nz, lig, rec or n_ge", who); return SGL_EINVAL; }
+    if (K < 1 || K > LIGREC_MAX_K) { sgl_set_error("%s: K = %d is outside [1, %d]", who, K, LIGREC_MAX_K); return SGL_EINVAL; }
+    if (G < 1) { sgl_set_error("%s: G = %d: at least one gene", who, G); return SGL_EINVAL; }
+    if (P < 1) { sgl_set_error("%s: P = %d: at least one pair", who, P); return SGL_EINVAL; }
+    if (nperm < 1 || nperm > LIGREC_MAX_NPERM) { sgl_set_error("%s: nperm = %d is outside [1, %lld]", who, nperm, (long long)LIGREC_MAX_NPERM); return SGL_EINVAL; }
+    for (int64_t q = 0; q < P; ++q)
+        if (lig[q] < 0 || lig[q] >= G || rec[q] < 0 || rec[q] >= G) {
+            sgl_set_error("%s: pair %lld (%d, %d) points outside the %d genes", who, (long long)q, lig[q], rec[q], G);
+            return SGL_EINVAL;
+        }
+    if (!ligrec_threshold_ok(threshold)) { sgl_set_error("%s: threshold is outside [0, 1]", who); return SGL_EINVAL; }
+    for (int64_t c = 0; c < K; ++c)
+        if (group_n[c] < 0) { sgl_set_error("%s: group_n[%lld] = %lld is negative", who, (long long)c, (long long)group_n[c]); return SGL_EINVAL; }
+    for (int64_t q = 0; q < (int64_t)G * K; ++q)
+        if (nz[q] < 0 || nz[q] > group_n[q % K]) {
+            sgl_set_error("%s: nz of gene %lld in class %lld is %lld, the class has %lld cells", who, (long long)(q / K), (long long)(q % K), (long long)nz[q],
+                          (long long)group_n[q % K]);
+            return SGL_EINVAL;
+        }
+    for (int64_t q = 0; q < (int64_t)P * K * K; ++q)
+        if (n_ge[q] < 0 || n_ge[q] > nperm) { sgl_set_error("%s: n_ge[%lld] = %lld is not a count of %d permutations", who, (long long)q, (long long)n_ge[q], nperm); return SGL_EINVAL; }
+    ligrec_stats(K, G, P, nperm, group_n, nz, lig, rec, n_ge, threshold, per_interaction != 0, expressed, p, padj);
+    return SGL_OK;
+}
+
+extern "C" int sgl_c_ligrec(const double* Ax, const int32_t* Ai, const int32_t* Ap, int32_t nrow, int32_t ncol, const int32_t* lab, int32_t K,
+                            const int32_t* genes, int32_t G, const int32_t* lig, const int32_t* rec, int32_t P, int32_t nperm, uint64_t seed,
+                            int32_t batch, double threshold, int per_interaction, int64_t* group_n, int64_t* nz, double* sum, double* mean,
+                            double* score, int64_t* n_ge, double* null_out, uint8_t* expressed, double* p, double* padj, int64_t* info,
+                            double* stage_ms) {
+    SGLCHK(sgl_ligrec_args_check("sgl_c_ligrec", lab, std::max(ncol, 0), K, genes, G, std::max(nrow, 0), lig, rec, P, nperm, threshold, batch,
+                                 std::max(ncol, 0)));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    SGLCHK(sgl_upload_csc(hd.c, Ax, Ai, Ap, nullptr, nullptr, nullptr, nrow, ncol, 0, ncol));
+    SGLCHK(markers_state(hd.c, "sgl_c_ligrec"));
+    const size_t GK = (size_t)G * (size_t)K, PKK = (size_t)P * (size_t)K * (size_t)K;
+    std::vector<int64_t> t_n((size_t)K), t_nz(GK), t_ge(PKK);
+    SGLCHK(sgl_ligrec_all(hd.c, lab, K, genes, G, lig, rec, P, nperm, seed, batch, t_n.data(), t_nz.data(), sum, mean, score, t_ge.data(), null_out,
+                          stage_ms));
+    if (group_n) std::copy(t_n.begin(), t_n.end(), group_n);
+    if (nz) std::copy(t_nz.begin(), t_nz.end(), nz);
+    if (n_ge) std::copy(t_ge.begin(), t_ge.end(), n_ge);
+    ligrec_stats(K, G, P, nperm, t_n.data(), t_nz.data(), lig, rec, t_ge.data(), threshold, per_interaction != 0, expressed, p, padj);
+    if (info) std::copy(hd.c->ligrec_last, hd.c->ligrec_last + 8, info);
+    return SGL_OK;
+}
+
+extern "C" int sgl_op_ligrec_sums(sgl_ctx* c, const int32_t* labs, int32_t n, int32_t nb, int32_t K, const int32_t* genes, int32_t G, int32_t path,
+                                  int32_t vectors_per_wave, double* sum_out) {
+    CTX_GUARD(c);
+    SGLCHK(markers_state(c, "sgl_op_ligrec_sums"));
+    SGLCHK(sgl_ligrec_sums_args_check("sgl_op_ligrec_sums", labs, n, nb, K, genes, G, c->A.nrow, path, vectors_per_wave, c->A.ncol));
+    if (!sum_out) { sgl_set_error("sgl_op_ligrec_sums: NULL sum_out"); return SGL_EINVAL; }
+    return sgl_ligrec_sums_core(c, labs, nb, K, genes, G, path, vectors_per_wave, sum_out);
+}
+
+extern "C" int sgl_op_ligrec_tally(sgl_ctx* c, const double* mean_obs, const double* means, int32_t nb, int32_t K, int32_t G, const int32_t* lig,
+                                   const int32_t* rec, int32_t P, double* score_out, int64_t* n_ge_out, double* null_out) {
+    CTX_GUARD(c);
+    SGLCHK(sgl_ligrec_tally_args_check("sgl_op_ligrec_tally", mean_obs, means, nb, K, G, lig, rec, P));
+    return sgl_ligrec_tally_core(c, mean_obs, means, nb, K, G, lig, rec, P, score_out, n_ge_out, null_out);
+}
+
+extern "C" int sgl_ligrec_info(sgl_ctx* c, int64_t out[8]) {
+    CTX_GUARD(c);
+    if (!out) { sgl_set_error("sgl_ligrec_info: NULL out"); return SGL_EINVAL; }
+    std::copy(c->ligrec_last, c->ligrec_last + 8, out);
     return SGL_OK;
 }
 
