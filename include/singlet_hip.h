@@ -799,6 +799,92 @@ SGL_API int sgl_op_ligrec_tally(sgl_ctx* ctx, const double* mean_obs, const doub
                                 const int32_t* rec, int32_t P, double* score_out, int64_t* n_ge_out, double* null_out);
 SGL_API int sgl_ligrec_info(sgl_ctx* ctx, int64_t out[8]);
 
+/* Co-occurrence by distance: how the presence of class b changes with the distance from a point of class a -- the score of
+ * squidpy's gr.co_occurrence (Tosti et al. 2021) and, in its cumulative same-class form, Ripley's K / L (gr.ripley).  Where the
+ * neighbourhood enrichment asks about adjacency on a graph, this asks about EVERY pair of points up to a radius.  The rules below
+ * are this library's own statement of the published score; tests/cooccur_restatement.py restates them in numpy.  NO parity with
+ * squidpy is claimed and no run against it is made: squidpy works in float32 and picks its thresholds from the data's pairwise
+ * distances.  Everything the device computes is an integer, so the table is one function of the inputs, bit for bit the
+ * restatement, whatever the grid, the bin path, the tiling or the flush bound.
+ *
+ * Inputs:
+ *  - n points (c1[e], c2[e]) in FP64: two dimensions, as sgl_spatial_graph;
+ *  - labels lab[e], int32 in [0, K), 1 <= K <= 256; a class without points is allowed;
+ *  - thresholds r[0] < r[1] < ... < r[T], T intervals, 1 <= T <= 64.
+ *
+ * Distance: dx = fl(c1[i] - c1[j]), dy likewise, d2 = fl(fl(dx * dx) + fl(dy * dy)), uncontracted (the unit is compiled with
+ * -ffp-contract=off): sgl_spatial_graph's sum without the root.  It is bitwise symmetric in (i, j).
+ *
+ * Binning: thr2[t] = fl(r[t] * r[t]), computed once on the host.  Pair (i, j), i != j, lies in interval t iff thr2[t] < d2 <=
+ * thr2[t + 1] -- squidpy's (dist > lo) & (dist <= hi) on squares.  NO root is taken: this can differ from comparing sqrt(d2) with
+ * r only where one rounding decides (d2 within a rounding of r[t]^2).  With r[0] = 0 coincident points (d2 == 0) are in no interval.
+ *
+ * Tallies, int64: N[a + K b + K^2 t] = the number of ORDERED pairs (i, j), i != j, with lab[i] == a, lab[j] == b, in interval
+ * t.  N is symmetric in (a, b) and its diagonal is even (every unordered pair is two ordered ones); sgl_cooccur_stats and
+ * sgl_ripley_stats refuse a table that is not.
+ *
+ * Statistics (host code, cooccur_host.h, pure functions):
+ *  - per interval, or cumulatively: cumulative != 0 first replaces N[t] by sum_{s <= t} N[s] in exact integers;
+ *  - tot = sum_{a, b} N[a, b, t];  row[a] = sum_b N[a, b, t];
+ *  - ratio[a, b, t] = ((double)N / (double)row[a]) / ((double)row[b] / (double)tot), the divisions in this order: P(b | within
+ *    the interval of an a) over P(b among all pairs of the interval), squidpy's probs_con; NaN when row[a] == 0 or row[b] == 0;
+ *  - an integer becomes a double by one conversion that rounds to nearest even;
+ *  - Ripley, from the cumulative diagonal Ncum[a, a, t] = sum_{s <= t} N[a, a, s]: Kfun[a, t] = (area * (double)Ncum[a, a, t]) /
+ *    (double)(n_a (n_a - 1)), the product n_a (n_a - 1) in exact integers; L = sqrt(Kfun / pi), pi = 0x1.921fb54442d18p+1.  area is
+ *    the caller's (the Python layer defaults it to the bounding box).  NaN for n_a < 2.  K_out / L_out hold [a + K t].  Out of
+ *    scope: edge correction, simulation envelopes, the F and G functions.
+ *
+ * Refusals, SGL_EINVAL before anything is uploaded or launched, every output untouched, the message naming the offender, in this
+ * order: NULL c1, c2, lab or r; n < 1; a coordinate that is not finite (position and value); K outside [1, 256]; a label outside
+ * [0, K) (position and value); T outside [1, 64]; r[0] < 0 or a threshold that is not finite; thr2 not strictly ascending or not
+ * finite (the index); a negative knob (or one outside its range).  SGL_ESTATE: a team member, an all-reduce hook, a resident
+ * shard, as sgl_nhood_enrichment.  The context stays usable after every refusal.
+ *
+ * The plan (cooccur_host.h, pure functions of the extent, the sizes and the knobs):
+ *  - bucket sort: the extent is computed on the device; square buckets of side max(r[T], 2^-510) (1 + 2^-10) (raised to the extent
+ *    2^-30), key by * W + bx with b = floor((c - cmin) / side), a stable radix sort, x, y and the label gathered into sorted
+ *    order.  Every pair that passes the test lies in adjacent buckets (the argument is written above cooccur_grid).  When the grid
+ *    would be at most 3 x 3 buckets, or the extent overflows, the plan takes ONE bucket: all pairs, nothing sorted;
+ *  - tally: sorted positions are cut into centre tiles of 256, a lane holds one centre, candidate tiles of 256 are staged in LDS.
+ *    An unordered pair is counted exactly once, by the lower sorted position: a centre's candidates are the positions after its
+ *    own in its bucket row up to the end of bucket bx + 1, and buckets bx - 1 .. bx + 1 of row by + 1; a tile walks a superset of
+ *    its centres' candidates, the exact d2 test and pos_j > pos_i decide.  It adds 1 to bin [t][min(a, b)][max(a, b)]; an epilogue
+ *    mirrors the off-diagonal and doubles the diagonal.  At most 1024 workgroups take contiguous ranges of centre tiles; in the
+ *    all-pairs regime up to 64 workgroups share a range, each taking every split-th candidate tile;
+ *  - bins: LDS path while T K^2 uint32 bins + 6144 bytes of staging fit 128 KiB -- LDS atomics, flushed (non-zero bins) with
+ *    64-bit global atomics at the end and EARLIER whenever the pairs evaluated since the last flush would pass 2^32 - 1, what a
+ *    uint32 bin holds; global path (the bins do not fit, or forced): 64-bit global atomics.  Integer sums have one value in any
+ *    order: there are no ordering rules, only the once-per-unordered-pair rule.  No floating-point atomics anywhere.
+ *
+ * sgl_cooccur: on the context's device, stream and pool only; no resident matrix is needed and nothing of the context changes but
+ * what sgl_cooccur_info reports (a fit in progress continues with its bits).  All work goes to the context's stream
+ * (sgl_set_stream), which is synchronised before the call returns.  counts: T x K x K int64.
+ * sgl_c_cooccur: one-shot, in a context of its own; additionally ratio (the per-interval statistic, T x K x K doubles), info
+ * (sgl_cooccur_info's eight values) and stage_ms[3] by events (sort + gather; tally; epilogue + download); counts and each of
+ * these may be NULL.
+ * sgl_cooccur_stats, sgl_ripley_stats: host only, no device; either of K_out and L_out may be NULL.  Both refuse (SGL_EINVAL, the
+ * message naming the offender, outputs untouched) K outside [1, 256], T outside [1, 64], NULL counts, and a table that is no
+ * tally (a negative count, N[a, b] != N[b, a], an odd diagonal, a total above 2^63 - 1).  sgl_ripley_stats also refuses, in this
+ * order: NULL group_n; an area that is not a positive finite number; a group_n[a] that is negative or above 2^31; a class whose
+ * cumulative diagonal counts more ordered pairs than n_a (n_a - 1), which no n_a points can form.
+ * sgl_op_cooccur_tally: the tally with its knobs.  grid_mode 0 the plan, 1 one bucket (all pairs), 2 the bucket grid whatever its
+ * size; bin_path 0 the plan, 1 the LDS path (bins that do not fit still go global), 2 the global path; flush_pairs 0 the plan's
+ * bound, otherwise a smaller one (a bound below one stage of 256 x 256 pairs flushes before every stage).  The result depends on
+ * none of the three.
+ * sgl_cooccur_info: out[0] the grid mode run (1 one bucket, 2 the bucket grid, 0 none ran), out[1] W, out[2] H, out[3] the bin path
+ * (1 LDS, 2 global), out[4] the LDS bytes per workgroup, out[5] the workgroups, out[6] the flushes of all workgroups (the one at a
+ * workgroup's end included), out[7] the candidate pairs evaluated, of the last co-occurrence call on the context.
+ * NOT provided: a permutation null, 3-D coordinates, a team form, an R shim entry. */
+SGL_API int sgl_cooccur(sgl_ctx* ctx, const double* c1, const double* c2, int32_t n, const int32_t* lab, int32_t K, const double* r, int32_t T,
+                        int64_t* counts);
+SGL_API int sgl_c_cooccur(const double* c1, const double* c2, int32_t n, const int32_t* lab, int32_t K, const double* r, int32_t T, int64_t* counts,
+                          double* ratio, int64_t* info, double* stage_ms);
+SGL_API int sgl_cooccur_stats(int32_t K, int32_t T, const int64_t* counts, int cumulative, double* ratio_out);
+SGL_API int sgl_ripley_stats(int32_t K, int32_t T, const int64_t* counts, const int64_t* group_n, double area, double* K_out, double* L_out);
+SGL_API int sgl_op_cooccur_tally(sgl_ctx* ctx, const double* c1, const double* c2, int32_t n, const int32_t* lab, int32_t K, const double* r, int32_t T,
+                                 int32_t grid_mode, int32_t bin_path, int64_t flush_pairs, int64_t* counts);
+SGL_API int sgl_cooccur_info(sgl_ctx* ctx, int64_t out[8]);
+
 /* Start a fit at rank k.  w_init: k x nrow host array, or NULL to fill W on
  * the device with the synthetic init ((rand_{S+2}(f,g) >> 11) + 0.5) * 2^-53.
  * h = 0, d = 1 as in src/singlet.cpp:639-641.

@@ -15,7 +15,8 @@ from .api import (c_nmf, c_ard_nmf, c_linked_nmf, c_gcnmf, run_gcnmf, c_nmf_dens
                   c_annotate, c_group_moments, get_model_fit, get_model_results, AnnotateNMF, c_signature_scores, signature_parse,
                   score_signatures, doublet_parents, doublet_scores, doublet_threshold, score_doublets, moran_graph_moments, moran_stats,
                   c_moran, c_moran_embedding, moran_rank, find_spatially_variable_features, moran_factors, nhood_stats,
-                  c_nhood_enrichment, nhood_enrichment, interaction_matrix, ligrec_stats, c_ligrec, read_interactions, ligrec)
+                  c_nhood_enrichment, nhood_enrichment, interaction_matrix, ligrec_stats, c_ligrec, read_interactions, ligrec,
+                  cooccur_stats, ripley_stats, c_cooccur, co_occurrence, ripley)
 from .native import native, NativeMatrix  # noqa: F401
 from ._lib import SingletHipError, LIB_PATH  # noqa: F401
 

@@ -104,6 +104,12 @@ SIGNATURES = {
     "sgl_op_ligrec_sums": (C.c_int, [C.c_void_p, i32p, C.c_int32, C.c_int32, C.c_int32, i32p, C.c_int32, C.c_int32, C.c_int32, f64p]),
     "sgl_op_ligrec_tally": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int32, C.c_int32, C.c_int32, i32p, i32p, C.c_int32, f64p, i64p, f64p]),
     "sgl_ligrec_info": (C.c_int, [C.c_void_p, i64p]),
+    "sgl_cooccur": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int32, i32p, C.c_int32, f64p, C.c_int32, i64p]),
+    "sgl_c_cooccur": (C.c_int, [f64p, f64p, C.c_int32, i32p, C.c_int32, f64p, C.c_int32, i64p, f64p, i64p, f64p]),
+    "sgl_cooccur_stats": (C.c_int, [C.c_int32, C.c_int32, i64p, C.c_int, f64p]),
+    "sgl_ripley_stats": (C.c_int, [C.c_int32, C.c_int32, i64p, i64p, C.c_double, f64p, f64p]),
+    "sgl_op_cooccur_tally": (C.c_int, [C.c_void_p, f64p, f64p, C.c_int32, i32p, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, i64p]),
+    "sgl_cooccur_info": (C.c_int, [C.c_void_p, i64p]),
     "sgl_c_project_model": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                              C.c_uint16, f64p, f64p]),
     "sgl_rcpp_predict": (C.c_int, _CSC + [C.c_int32, C.c_int32, f64p, C.c_int32, C.c_int32, C.c_double, C.c_double,

@@ -3230,3 +3230,114 @@ def ligrec(A, labels, interactions, gene_names=None, threshold=0.01, nperm=1000,
     ex = t["expressed"]
     return {"means": t["score"], "p": t["p"], "padj": t["padj"], "expressed": ex[lg][:, :, None] & ex[rc][:, None, :], "pairs": kept,
             "dropped": dropped, "n_ge": t["n_ge"], "class_sizes": t["group_n"]}
+
+
+# ---------------------------------------------------------------------------
+# Co-occurrence of clusters by distance (squidpy's gr.co_occurrence score, Ripley's K / L; include/singlet_hip.h, "Co-occurrence by
+# distance")
+# ---------------------------------------------------------------------------
+def _cooccur_table(counts, who):
+    t = np.asarray(counts)
+    if t.ndim != 3 or t.shape[0] != t.shape[1] or t.shape[0] < 1 or t.shape[2] < 1 or t.dtype.kind not in "iu":
+        raise ValueError("%s: counts must be a K x K x T integer table" % who)
+    from ._cooccur import tba
+    return tba(t.astype(np.int64)), int(t.shape[0]), int(t.shape[2])
+
+
+def cooccur_stats(counts, cumulative=False):
+    """The co-occurrence ratio of a K x K x T tally (sgl_cooccur_stats; host code of the library, no device needed): [a, b, t] =
+    P(b | within interval t of an a) / P(b among all pairs of interval t), of the intervals or with `cumulative` of their running
+    sums; NaN where class a or b has no pair.  A table that is not symmetric with an even diagonal is refused."""
+    from ._cooccur import abt, table_shape
+    buf, K, T = _cooccur_table(counts, "cooccur_stats")
+    out = np.zeros(table_shape(K, T))
+    check(_lib.load().sgl_cooccur_stats(K, T, ptr(buf, _lib.i64p), int(bool(cumulative)), ptr(out, f64p)))
+    return abt(out, K, T)
+
+
+def ripley_stats(counts, group_n, area):
+    """Ripley's K and L of every class from the cumulative diagonal of a K x K x T tally (sgl_ripley_stats; host code):
+    {"K", "L"}, K x T each; NaN for a class of fewer than two points.  No edge correction."""
+    buf, K, T = _cooccur_table(counts, "ripley_stats")
+    g = np.asarray(group_n)
+    if g.shape != (K,) or g.dtype.kind not in "iu":
+        raise ValueError("ripley_stats: group_n must hold one integer count per class (%d)" % K)
+    g = np.ascontiguousarray(g, dtype=np.int64)
+    kk, tt = max(min(K, 256), 1), max(min(T, 64), 1)
+    Kf, L = np.zeros((tt, kk)), np.zeros((tt, kk))
+    check(_lib.load().sgl_ripley_stats(K, T, ptr(buf, _lib.i64p), ptr(g, _lib.i64p), float(area), ptr(Kf, f64p), ptr(L, f64p)))
+    return {"K": np.ascontiguousarray(Kf[:T, :K].T), "L": np.ascontiguousarray(L[:T, :K].T)}
+
+
+def c_cooccur(coords, labels, interval, n_classes=None, timing=False):
+    """The one-shot form of Context.cooccur (sgl_c_cooccur), in a context of its own: {"counts" (K x K x T int64), "ratio" (the
+    per-interval statistic of cooccur_stats), "info" (Context.cooccur_info's fields)}; with timing "stage_ms" (sort + gather,
+    tally, epilogue + download).  The arguments come in Context.cooccur's order, the coordinates before the labels; co_occurrence
+    and ripley take the labels first."""
+    from ._cooccur import COOCCUR_INFO, abt, cooccur_inputs, table_shape
+    c1, c2, n, lab, K, r, T = cooccur_inputs(coords, labels, interval, n_classes, "c_cooccur")
+    counts, ratio = np.zeros(table_shape(K, T), dtype=np.int64), np.zeros(table_shape(K, T))
+    info, ms = np.zeros(8, dtype=np.int64), (np.zeros(3) if timing else None)
+    check(_lib.load().sgl_c_cooccur(ptr(c1, f64p), ptr(c2, f64p), n, ptr(lab, i32p), K, ptr(r, f64p), T, ptr(counts, _lib.i64p), ptr(ratio, f64p),
+                                    ptr(info, _lib.i64p), ptr(ms, f64p)))
+    out = {"counts": abt(counts, K, T), "ratio": abt(ratio, K, T), "info": dict(zip(COOCCUR_INFO, (int(v) for v in info)))}
+    if timing:
+        out["stage_ms"] = ms
+    return out
+
+
+def _cooccur_front(who, labels, coords, interval, n_classes):
+    """Every refusal of co_occurrence / ripley, before the first upload: (c1, c2, lab, K, r)."""
+    from ._cooccur import MAX_INTERVALS, cooccur_coords, cooccur_thresholds, default_interval
+    c1, c2 = cooccur_coords(coords, who)
+    lab, K = _nhood_classes(who, labels, n_classes)
+    if lab.shape[0] != c1.shape[0]:
+        raise ValueError("%s: %d labels, %d points" % (who, lab.shape[0], c1.shape[0]))
+    for name, v in (("first", c1), ("second", c2)):
+        if not np.isfinite(v).all():
+            at = int(np.nonzero(~np.isfinite(v))[0][0])
+            raise ValueError("%s: the %s coordinate of point %d is not finite" % (who, name, at))
+    if np.ndim(interval) == 0:
+        r = default_interval(c1, c2, interval, who)
+    else:
+        r = cooccur_thresholds(interval, who)
+        if not 2 <= r.shape[0] <= MAX_INTERVALS + 1:
+            raise ValueError("%s: %d thresholds: between 2 and %d are taken (at most %d intervals)" % (who, r.shape[0], MAX_INTERVALS + 1, MAX_INTERVALS))
+        if not np.isfinite(r).all() or r[0] < 0:
+            raise ValueError("%s: the thresholds must be finite and start at 0 or above" % who)
+    with np.errstate(over="ignore", under="ignore"):
+        sq = r * r
+    if not np.isfinite(sq).all() or not (np.diff(sq) > 0).all():
+        raise ValueError("%s: the thresholds must ascend strictly, and so must their squares" % who)
+    return c1, c2, lab, K, r
+
+
+def co_occurrence(labels, coords, interval=50, n_classes=None, cumulative=False):
+    """How the presence of class b changes with the distance from a cell of class a: the co-occurrence score of squidpy's
+    gr.co_occurrence on the device (sgl_c_cooccur; the rules are stated in include/singlet_hip.h, "Co-occurrence by distance" --
+    this library's own statement of the published score in FP64, NO parity with squidpy is claimed).  labels: one integer class
+    in [0, n_classes) per cell; coords: n x 2, or a pair of vectors.  interval: an ascending array of distance thresholds (at
+    most 65), or a count T <= 64, which means np.linspace(0, 0.5 * hypot(extent_x, extent_y), T + 1) -- the library's own rule.
+    Returns {"occ" (K x K x T doubles, [a, b, t]; of the running sums with cumulative), "counts" (K x K x T int64 ordered pairs
+    per interval), "interval" (the thresholds)}.  Every argument is refused before the first upload.  The labels come first, as in
+    nhood_enrichment; the calls below this one (c_cooccur, Context.cooccur) take the coordinates first."""
+    who = "co_occurrence"
+    c1, c2, lab, K, r = _cooccur_front(who, labels, coords, interval, n_classes)
+    res = c_cooccur((c1, c2), lab, r, K)
+    return {"occ": cooccur_stats(res["counts"], True) if cumulative else res["ratio"], "counts": res["counts"], "interval": r}
+
+
+def ripley(labels, coords, mode="L", interval=50, area=None, n_classes=None):
+    """Ripley's K or L function of every class (squidpy's gr.ripley without edge correction or simulations), from the same
+    tally as co_occurrence: K x T, [a, t] at radius interval[t + 1].  mode "K" or "L"; area None: the bounding box of the
+    points.  interval as in co_occurrence; a first threshold above 0 leaves the closer pairs out of the cumulative count."""
+    who = "ripley"
+    if mode not in ("K", "L"):
+        raise ValueError("%s: mode = %r is none of 'K', 'L'" % (who, mode))
+    c1, c2, lab, K, r = _cooccur_front(who, labels, coords, interval, n_classes)
+    if area is None:
+        area = float((c1.max() - c1.min()) * (c2.max() - c2.min()))
+    if not (np.isfinite(area) and area > 0):
+        raise ValueError("%s: area = %r is not a positive finite number" % (who, area))
+    res = c_cooccur((c1, c2), lab, r, K)
+    return ripley_stats(res["counts"], np.bincount(lab, minlength=K).astype(np.int64), area)[mode]

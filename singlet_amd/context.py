@@ -739,6 +739,38 @@ class Context(_Handle):
         check(self._L.sgl_ligrec_info(self._h, ptr(out, i64p)))
         return dict(zip(LIGREC_INFO, (int(v) for v in out)))
 
+    def cooccur(self, coords, labels, interval, n_classes=None):
+        """The co-occurrence tally of the classes `labels` of the points `coords` (n x 2, or a pair of vectors) over the distance
+        intervals (interval[t], interval[t + 1]] (sgl_cooccur; the rules: include/singlet_hip.h, "Co-occurrence by distance"):
+        K x K x T int64, [a, b, t] = the ordered pairs (i, j), i != j, of classes a, b whose distance lies in interval t.
+        n_classes None: 1 + the largest label.  Nothing of the context is touched; cooccur_info() says what ran.  ARGUMENT ORDER:
+        the data first, then the labels, as every call on a context (nhood_enrichment(G, labels), ...) and c_cooccur; the
+        user-facing co_occurrence / ripley take the labels first, as nhood_enrichment(labels, ...) does."""
+        return self.op_cooccur_tally(coords, labels, interval, n_classes, _whole=True)
+
+    def op_cooccur_tally(self, coords, labels, interval, n_classes=None, grid_mode=0, bin_path=0, flush_pairs=0, _whole=False):
+        """Context.cooccur with the knobs of its plan (sgl_op_cooccur_tally): grid_mode 0 the plan, 1 one bucket (all pairs), 2
+        the bucket grid; bin_path 0 the plan, 1 the LDS path, 2 the global path; flush_pairs 0 the plan's bound, otherwise a
+        smaller one.  The result depends on none of them; cooccur_info() says what ran."""
+        from ._cooccur import abt, cooccur_inputs, table_shape
+        who = "cooccur" if _whole else "op_cooccur_tally"
+        c1, c2, n, lab, K, r, T = cooccur_inputs(coords, labels, interval, n_classes, who)
+        out = np.zeros(table_shape(K, T), dtype=np.int64)
+        if _whole:
+            check(self._L.sgl_cooccur(self._h, ptr(c1, f64p), ptr(c2, f64p), n, ptr(lab, i32p), K, ptr(r, f64p), T, ptr(out, i64p)))
+        else:
+            check(self._L.sgl_op_cooccur_tally(self._h, ptr(c1, f64p), ptr(c2, f64p), n, ptr(lab, i32p), K, ptr(r, f64p), T, int(grid_mode),
+                                               int(bin_path), int(flush_pairs), ptr(out, i64p)))
+        return abt(out, K, T)
+
+    def cooccur_info(self):
+        """What the last co-occurrence call on this context ran (sgl_cooccur_info): {"grid_mode" (1 one bucket, 2 the bucket
+        grid, 0 none ran), "W", "H", "bin_path" (1 LDS, 2 global), "lds_bytes", "workgroups", "flushes", "pairs"}."""
+        from ._cooccur import COOCCUR_INFO
+        out = np.zeros(8, dtype=np.int64)
+        check(self._L.sgl_cooccur_info(self._h, ptr(out, i64p)))
+        return dict(zip(COOCCUR_INFO, (int(v) for v in out)))
+
     def variable_features(self, nfeatures=2000, span=0.3, vmax=None, expected_var=None):
         """Variable features of the resident counts (sgl_variable_features; Seurat's vst selection under this library's
         stated rules): {"features" (int32 gene indices in rank order), "mean", "variance", "variance_expected",

@@ -279,6 +279,9 @@ struct sgl_ctx {
     // batch, the LDS bytes per workgroup, the waves per workgroup and the listed genes on the LDS and on the global path, of the
     // last ligand-receptor call on this context
     int64_t ligrec_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // sgl_cooccur_info: the grid mode run (1 one bucket, 2 the bucket grid; 0: none ran), W, H, the bin path (1 LDS, 2 global), the
+    // LDS bytes per workgroup, the workgroups, the flushes and the candidate pairs evaluated, of the last co-occurrence call
+    int64_t cooccur_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     sgl_allreduce_fn allreduce = nullptr;
     void* allreduce_user = nullptr;
@@ -598,6 +601,16 @@ int sgl_ligrec_sums_core(sgl_ctx* c, const int32_t* labs, int64_t nb, int K, con
 // score_out, n_ge_out P x K x K, null_out nb x P x K x K from the means alone (no matrix is read); any output may be NULL
 int sgl_ligrec_tally_core(sgl_ctx* c, const double* mean_obs, const double* means, int64_t nb, int K, int64_t G, const int32_t* lig,
                           const int32_t* rec, int64_t P, double* score_out, int64_t* n_ge_out, double* null_out);
+
+// co-occurrence by distance (kernels_cooccur.hip; include/singlet_hip.h, "Co-occurrence by distance").  All arrays are the HOST's;
+// the call reads nothing of the context but its device, stream and pool (it records what it ran in cooccur_last), allocates its
+// own temporaries and synchronises the stream before it returns.  The args check holds every refusal, launches nothing and fills
+// thr2 (T + 1 doubles) with the squared thresholds.
+int sgl_cooccur_args_check(const char* who, const double* c1, const double* c2, int64_t n, const int32_t* lab, int64_t K, const double* r, int64_t T,
+                           int64_t grid_mode, int64_t bin_path, int64_t flush_pairs, double* thr2);
+// counts T x K x K at a + K b + K^2 t; a knob of 0: the plan's; stage_ms (3 values, may be NULL): the stages timed by events
+int sgl_cooccur_core(sgl_ctx* c, const double* c1, const double* c2, int64_t n, const int32_t* lab, int K, const double* r, const double* thr2, int T,
+                     int grid_mode, int bin_path, int64_t flush_pairs, int64_t* counts, double* stage_ms);
 
 // gene set enrichment (kernels_gsea.hip; include/singlet_hip.h, "Gene set enrichment").  All arrays are the HOST's; every call
 // only reads the context (it records what it ran in gsea_last), allocates its own temporaries and synchronises the stream

@@ -10,6 +10,7 @@
 #include "moran_host.h"
 #include "nhood_host.h"
 #include "ligrec_host.h"
+#include "cooccur_host.h"
 
 #include <math.h>
 #include <string.h>
@@ -2549,6 +2550,102 @@ extern "C" int sgl_ligrec_info(sgl_ctx* c, int64_t out[8]) {
     CTX_GUARD(c);
     if (!out) { sgl_set_error("sgl_ligrec_info: NULL out"); return SGL_EINVAL; }
     std::copy(c->ligrec_last, c->ligrec_last + 8, out);
+    return SGL_OK;
+}
+
+// Co-occurrence by distance (include/singlet_hip.h; kernels_cooccur.hip, cooccur_host.h): the state, then the refusals, then a call
+// that reads nothing of the context but its device, stream and pool.
+static int cooccur_state(sgl_ctx* c, const char* who) {
+    if (c->team || c->allreduce) {
+        sgl_set_error("%s: the context is a shard of a team or has an all-reduce hook; the points span all cells", who);
+        return SGL_ESTATE;
+    }
+    if (c->A.p && (c->cell_offset != 0 || c->ncells_total != (int64_t)c->A.ncol)) {
+        sgl_set_error("%s: the context holds a shard (cells %lld .. %lld of %lld); the points span all cells", who, (long long)c->cell_offset,
+                      (long long)c->cell_offset + c->A.ncol, (long long)c->ncells_total);
+        return SGL_ESTATE;
+    }
+    return SGL_OK;
+}
+
+extern "C" int sgl_op_cooccur_tally(sgl_ctx* c, const double* c1, const double* c2, int32_t n, const int32_t* lab, int32_t K, const double* r, int32_t T,
+                                    int32_t grid_mode, int32_t bin_path, int64_t flush_pairs, int64_t* counts) {
+    CTX_GUARD(c);
+    SGLCHK(cooccur_state(c, "sgl_op_cooccur_tally"));
+    double thr2[COOCCUR_MAX_T + 1];
+    SGLCHK(sgl_cooccur_args_check("sgl_op_cooccur_tally", c1, c2, n, lab, K, r, T, grid_mode, bin_path, flush_pairs, thr2));
+    if (!counts) { sgl_set_error("sgl_op_cooccur_tally: NULL counts"); return SGL_EINVAL; }
+    return sgl_cooccur_core(c, c1, c2, n, lab, K, r, thr2, T, grid_mode, bin_path, flush_pairs, counts, nullptr);
+}
+
+extern "C" int sgl_cooccur(sgl_ctx* c, const double* c1, const double* c2, int32_t n, const int32_t* lab, int32_t K, const double* r, int32_t T,
+                           int64_t* counts) {
+    CTX_GUARD(c);
+    SGLCHK(cooccur_state(c, "sgl_cooccur"));
+    double thr2[COOCCUR_MAX_T + 1];
+    SGLCHK(sgl_cooccur_args_check("sgl_cooccur", c1, c2, n, lab, K, r, T, 0, 0, 0, thr2));
+    if (!counts) { sgl_set_error("sgl_cooccur: NULL counts"); return SGL_EINVAL; }
+    return sgl_cooccur_core(c, c1, c2, n, lab, K, r, thr2, T, 0, 0, 0, counts, nullptr);
+}
+
+extern "C" int sgl_cooccur_stats(int32_t K, int32_t T, const int64_t* counts, int cumulative, double* ratio_out) {
+    static const char* who = "sgl_cooccur_stats";
+    if (K < 1 || K > COOCCUR_MAX_K) { sgl_set_error("%s: K = %d is outside [1, %d]", who, K, COOCCUR_MAX_K); return SGL_EINVAL; }
+    if (T < 1 || T > COOCCUR_MAX_T) { sgl_set_error("%s: T = %d intervals is outside [1, %d]", who, T, COOCCUR_MAX_T); return SGL_EINVAL; }
+    if (!counts || !ratio_out) { sgl_set_error("%s: NULL counts or ratio_out", who); return SGL_EINVAL; }
+    int64_t at = -1;
+    if (!cooccur_table_ok(K, T, counts, &at)) {
+        sgl_set_error("%s: counts[%lld, %lld, %lld] = %lld: the table is not a tally (a negative count, N[a, b] != N[b, a], an odd diagonal, or a total above 2^63)",
+                      who, (long long)(at % K), (long long)(at / K % K), (long long)(at / ((int64_t)K * K)), (long long)counts[at]);
+        return SGL_EINVAL;
+    }
+    std::vector<int64_t> scratch((size_t)K * K + (size_t)K);
+    cooccur_stats(K, T, counts, cumulative != 0, ratio_out, scratch.data());
+    return SGL_OK;
+}
+
+extern "C" int sgl_ripley_stats(int32_t K, int32_t T, const int64_t* counts, const int64_t* group_n, double area, double* K_out, double* L_out) {
+    static const char* who = "sgl_ripley_stats";
+    if (K < 1 || K > COOCCUR_MAX_K) { sgl_set_error("%s: K = %d is outside [1, %d]", who, K, COOCCUR_MAX_K); return SGL_EINVAL; }
+    if (T < 1 || T > COOCCUR_MAX_T) { sgl_set_error("%s: T = %d intervals is outside [1, %d]", who, T, COOCCUR_MAX_T); return SGL_EINVAL; }
+    if (!counts || !group_n) { sgl_set_error("%s: NULL counts or group_n", who); return SGL_EINVAL; }
+    int64_t at = -1;
+    if (!cooccur_table_ok(K, T, counts, &at)) {
+        sgl_set_error("%s: counts[%lld, %lld, %lld] = %lld: the table is not a tally (a negative count, N[a, b] != N[b, a], an odd diagonal, or a total above 2^63)",
+                      who, (long long)(at % K), (long long)(at / K % K), (long long)(at / ((int64_t)K * K)), (long long)counts[at]);
+        return SGL_EINVAL;
+    }
+    switch (cooccur_ripley_check(K, T, counts, group_n, area, &at)) {
+    case 1: sgl_set_error("%s: area = %g is not a positive finite number", who, area); return SGL_EINVAL;
+    case 2: sgl_set_error("%s: group_n[%lld] = %lld is negative or above 2^31", who, (long long)at, (long long)group_n[at]); return SGL_EINVAL;
+    case 3:
+        sgl_set_error("%s: class %lld holds %lld points, its diagonal counts more ordered pairs than n (n - 1)", who, (long long)at, (long long)group_n[at]);
+        return SGL_EINVAL;
+    default: break;
+    }
+    cooccur_ripley(K, T, counts, group_n, area, K_out, L_out);
+    return SGL_OK;
+}
+
+extern "C" int sgl_c_cooccur(const double* c1, const double* c2, int32_t n, const int32_t* lab, int32_t K, const double* r, int32_t T, int64_t* counts,
+                             double* ratio, int64_t* info, double* stage_ms) {
+    double thr2[COOCCUR_MAX_T + 1];
+    SGLCHK(sgl_cooccur_args_check("sgl_c_cooccur", c1, c2, n, lab, K, r, T, 0, 0, 0, thr2));   // before a context is made
+    CtxHolder hd;
+    SGLCHK(sgl_create(current_device_or_zero(), &hd.c));
+    const size_t total = (size_t)T * (size_t)K * (size_t)K;
+    std::vector<int64_t> t(total), scratch((size_t)K * K + (size_t)K);
+    SGLCHK(sgl_cooccur_core(hd.c, c1, c2, n, lab, K, r, thr2, T, 0, 0, 0, t.data(), stage_ms));
+    if (counts) std::copy(t.begin(), t.end(), counts);
+    if (ratio) cooccur_stats(K, T, t.data(), false, ratio, scratch.data());
+    if (info) std::copy(hd.c->cooccur_last, hd.c->cooccur_last + 8, info);
+    return SGL_OK;
+}
+
+extern "C" int sgl_cooccur_info(sgl_ctx* c, int64_t out[8]) {
+    CTX_GUARD(c);
+    if (!out) { sgl_set_error("sgl_cooccur_info: NULL out"); return SGL_EINVAL; }
+    std::copy(c->cooccur_last, c->cooccur_last + 8, out);
     return SGL_OK;
 }
 
